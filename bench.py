@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: bound+gradient evaluations per second.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload at N=1: BASELINE.json configs[2]  (1 shard, N=1e6, D=100, M=512, Q=10, ARD-RBF, fixed embeddings = regime A),
 the configuration the metric is quoted on.  With N>1 every rank holds its own shard of the same size (configs[3],
 weak scaling) and the two per-evaluation reductions are RCCL all-reduces.  A step = one evaluation = phase 1 +
 all-reduce + global step + phase 2 + all-reduce + gradient read-back, inputs resident in HBM.
+
+A plain run sets up, warms up, times K steps and prints the JSON line.  ``--dump-outputs DIR`` also writes what the last timed step
+computed as DIR/<name>.npy.  ``--full`` adds what takes runs of its own, all after the timed region: the parity against the
+extended-precision truth, the global step's extended-precision cost, the int8 variant, the "extra" shapes and the CPU baseline.
 """
 import argparse
 import json
@@ -22,6 +26,18 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 FP64_PEAK_TFLOPS = 78.6   # MI355X datasheet FP64 (vector = matrix); ubench ceiling 74 (profiles/r01_ubench_f64_mfma4x4x4.txt)
+
+
+def usable_cpus():
+    """The CPUs this process may keep busy: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it.  Not
+    os.cpu_count(): on a shared host that counts every core, and OpenBLAS segfaults when several concurrent callers each ask it for
+    more threads than the process has CPUs."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    try:
+        n = min(n, int(os.environ.get('OMP_NUM_THREADS', '')))
+    except ValueError:
+        pass
+    return max(1, n)
 
 
 def synthetic(N, D, M, Q, seed, regime='A', z_seed=None):
@@ -56,7 +72,7 @@ def synthetic_threaded(N, D, M, Q, seed, regime='B'):
         if regime == 'B':
             X_S[a:b] = rs.uniform(0.05, 0.55, size=(b - a, Q))
 
-    with ThreadPool(min(32, os.cpu_count() or 8)) as pool:
+    with ThreadPool(min(32, usable_cpus())) as pool:
         pool.map(chunk, range((N + step - 1) // step))
     rs = np.random.RandomState(seed + 1)
     Z = X_mu[rs.permutation(N)[:M]] + 0.3 * rs.randn(M, Q)
@@ -255,11 +271,11 @@ def cpu_baseline(D, M, Q, N_full, budget_rows):
     the same workload, scaled linearly in N.  ``value`` is the BLAS-bound arrangement (evaluate_blas: K_nm kept between the phases, work
     buffers reused, 32768-row chunks) with its row chunks spread over a thread pool -- the element-wise numpy work (exp, products, row sums
     over 32768 x 512 arrays) is single-threaded per call, so one caller leaves most of a many-core host idle; W workers x T BLAS threads
-    with W * T = the host's logical CPUs -- in steady state (the best of the calls after the first, which pays the page faults of the
-    work buffers).  ``cores`` = the logical CPUs the configuration keeps busy; ``single_caller`` is the round-2 configuration (one caller,
+    with W * T = the CPUs this process may use (usable_cpus) -- in steady state (the best of the calls after the first, which pays the
+    page faults of the work buffers).  ``cores`` = the logical CPUs the configuration keeps busy; ``single_caller`` is the round-2 configuration (one caller,
     all BLAS threads); ``two_phase_port`` is the kernel-spec form (evaluate: K_nm regenerated in phase 2, 8192-row chunks)."""
     from oracle import factorised as Fz
-    ncpu = os.cpu_count() or 1
+    ncpu = usable_cpus()
     try:
         from threadpoolctl import threadpool_limits
     except Exception:
@@ -308,6 +324,25 @@ def cpu_baseline(D, M, Q, N_full, budget_rows):
                       % (budget_rows, N_full, D, M, Q, dt, bw, max(1, ncpu // bw), dt1, dt2)}
 
 
+DUMP_MAX_ELEMENTS = 1 << 21      # per array (16 MB of float64): the dump stays well under 64 MB in all
+
+
+def dump_outputs(dirname, out, eng, emb):
+    """What the last timed step computed, as DIR/<name>.npy in float64: the bound and the global gradients the evaluation returns and, with
+    free embeddings, the embedding gradients it left on the device.  An array of more than DUMP_MAX_ELEMENTS is written as a fixed,
+    seeded sample of its rows (the same rows for the same shape), so that two builds can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in out.items()}
+    if emb:
+        arrays['grad_X_mu'] = eng.download('GRAD_X_MU')
+        arrays['grad_X_S'] = eng.download('GRAD_X_S')
+    for name, v in sorted(arrays.items()):
+        if v.size > DUMP_MAX_ELEMENTS:
+            n = v.shape[0]
+            v = v[np.sort(np.random.RandomState(0).choice(n, DUMP_MAX_ELEMENTS // (v.size // n), replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -319,10 +354,16 @@ def main():
     ap.add_argument('--Q', type=int, default=10)
     ap.add_argument('--regime', choices=['A', 'B'], default='A',
                     help='A (default, the metric\'s configuration): X_S = 0, fixed embeddings; B: Bayesian GPLVM, X_S > 0, embedding gradients')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the regime-B shapes reported under "extra" (outside the timed region)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float64)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline: parity against the extended-precision truth, the extended-precision cost, the int8 variant, '
+                         'the "extra" shapes and the CPU baseline (all outside the timed region)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the int8 variant and the shapes reported under "extra"')
     ap.add_argument('--cpu-rows', type=int, default=400000)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if a.gpus != world:
@@ -414,6 +455,8 @@ def main():
         kern[k] /= a.steps
     for k in coll:
         coll[k] /= a.steps
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, eng, emb)
 
     if rank == 0:
         N, D, M, Q = a.N, a.D, a.M, a.Q
@@ -482,20 +525,20 @@ def main():
             res['config']['ms_per_step_by_rank'] = {'min': round(min(rank_ms), 4), 'max': round(max(rank_ms), 4), 'all': [round(v, 4) for v in rank_ms]}
         res['config']['global_step'] = ('float64 blocked Cholesky + inverses; Kmm^-1 Psi2 accumulated in double-double; E = (Kmm + beta Psi2)^-1 Psi1^T Y '
                                         'refined once with a double-double residual (GPARML_DD_KIPSI2 / GPARML_REFINE_E = 0 switch them off)')
-        if a.regime == 'A' and world == 1:
+        if a.full and a.regime == 'A' and world == 1:
             # the price of the two extended-precision pieces: the global step timed (HIP events) with and without them, after the timed region,
             # with grad_Z's distance from the truth for each setting
             res['config']['extended_precision_cost'] = extended_precision_cost(eng, d, N, D, M, Q, 100 + rank)
             if not a.no_extra and (N, D, M, Q) == (1000000, 100, 512, 10):
                 res['config']['int8_variant'] = int8_variants(eng, d, N, D, M, Q, 100 + rank)
-        if a.regime == 'A':
+        if a.full and a.regime == 'A':
             # parity of THIS run's last evaluation against the extended-precision truth of the same workload (rank 0's shard alone:
             # only meaningful for one shard), and the conditioning it was obtained at
             te = truth_errors(d, out, N, D, M, Q, 100 + rank) if world == 1 else None
             if te is not None:
                 res['config'].update({'cond_A': te['cond_A'], 'cond_Kmm': te['cond_Kmm'], 'grad_Z_err_vs_truth': te['grad_Z_err_vs_truth'],
                                       'F_err_vs_truth': te['F_err_vs_truth'], 'parity_vs_truth': te})
-        if not a.no_extra and world == 1 and a.regime == 'A' and (N, D, M, Q) == (1000000, 100, 512, 10):
+        if a.full and not a.no_extra and world == 1 and a.regime == 'A' and (N, D, M, Q) == (1000000, 100, 512, 10):
             # regime B (free embeddings) is not the metric's configuration; two shapes, each a slice of a BASELINE config, measured after
             # the timed region so that the driver's own run carries them
             eng.close()
@@ -506,7 +549,7 @@ def main():
                                            local_rank),
                             regime_b_extra('BASELINE configs[4] at its FULL per-GPU size: N=1e6, D=1000, M=1024, Q=50, free embeddings', 1000000, 1000, 1024, 50,
                                            local_rank, steps=1, threaded=True)]
-        if not a.no_cpu_baseline and world == 1 and a.regime == 'A':     # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1 and a.regime == 'A':     # rank 0 at N=1 only
             # last: its BLAS worker threads keep spinning for a while and slow the host side of whatever is timed after them (configs[1]'s
             # wall clock per evaluation read 1.15 ms behind the CPU baseline, 0.37 ms in a fresh process)
             res['cpu_baseline'] = cpu_baseline(D, M, Q, N, min(a.cpu_rows, N))
