@@ -56,6 +56,7 @@ SIGNATURES = {
     'gp_finish': (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp]),
     'gp_download': (ctypes.c_int, [_vp, ctypes.c_int, _dp, _i64]),
     'gp_set_local_statistics': (ctypes.c_int, [_vp, ctypes.c_double, _dp, _dp, ctypes.c_double, ctypes.c_double]),
+    'gp_predict': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     'gp_last_timings': (ctypes.c_int, [_vp, _dp]),
     'gp_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'gp_i8_status': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), _dp, _dp, _dp, ctypes.POINTER(_i64)]),

@@ -204,6 +204,7 @@ extern "C" int gp_destroy(gp_ctx* c) {
   if (c->p2prog) (void)hipFree(c->p2prog);
   gp::p1v2_free(c);
   gp::p1i8_free(c);
+  gp::pred_free(c);
   gp::comm_free(c);
   for (int i = 0; i < 14; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   if (c->h_out) (void)hipHostFree(c->h_out);
@@ -266,6 +267,7 @@ static int upload_embeddings(gp_ctx* c, const double* X_mu, const double* X_S, i
   GP_HIP(c, hipMemcpyAsync(c->Xs, X_S, nq * 8, hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->state = 0;
+  c->pred_ok = false;
   return GP_OK;
 }
 
@@ -321,6 +323,7 @@ extern "C" int gp_set_direction(gp_ctx* c, const double* d) {
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->have_dir = true;
   c->state = 0;
+  c->pred_ok = false;
   return GP_OK;
 }
 
@@ -395,6 +398,7 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
   c->sf2 = sf2; c->beta = beta; c->N_global = N_global; c->step = step;
   c->have_globals = true;
   c->state = 0;
+  c->pred_ok = false;
   return GP_OK;
 }
 
@@ -410,6 +414,7 @@ extern "C" int gp_phase1(gp_ctx* c) {
   if (!c->regime_A) GP_TRY(run_phase1_b(c));
   GP_EV(c, 2);
   c->state = 1;
+  c->pred_ok = false;
   c->spack_filled = false;
   return GP_OK;
 }
@@ -476,6 +481,7 @@ static int stats_pack(gp_ctx* c, int unpack_) {
   GP_TRY(ensure_spack(c));
   const long n = (long)c->M * c->M + (long)c->M * c->D + SC_COUNT;
   if (unpack_) {
+    c->pred_ok = false;
     // the packed buffer only holds statistics after a pack (it is zero from its allocation): unpacking first would silently wipe phase 1's sums
     if (!c->spack_filled) return fail(c, GP_ERR_STATE, "gp_stats_unpack before gp_stats_pack");
     hipLaunchKernelGGL(stats_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->spack, c->stats, c->M, c->Mp, c->D, c->Dp);
@@ -541,6 +547,7 @@ extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int 
     from = dst->staging;
   }
   hipLaunchKernelGGL(combine_kernel, dim3(blocks_for(n)), dim3(256), 0, dst->stream, which == 0 ? dst->stats : dst->grads, from, n, op);
+  if (which == 0) dst->pred_ok = false;
   GP_HIP(dst, hipGetLastError());
   if (which == 0 && dst->state < 1) dst->state = 1;
   return GP_OK;
@@ -553,7 +560,7 @@ extern "C" int gp_scale_buffer(gp_ctx* c, int which, double f) {
   if (which == 1 && c->state < 3) return fail(c, GP_ERR_STATE, "gp_scale_buffer(gradient sums) before gp_phase2");
   GP_HIP(c, hipSetDevice(c->device));
   const long n = which == 0 ? (long)c->Mp * c->Mp + (long)c->Mp * c->Dp + SC_COUNT : (long)c->M * c->Q + c->Q;
-  if (which == 0) c->spack_filled = false;   // the padded buffer is the source of truth: a later unpack needs a new pack
+  if (which == 0) { c->spack_filled = false; c->pred_ok = false; }   // the padded buffer is the source of truth: a later unpack needs a new pack
   if (f == 0.0) {
     // a dropped shard: the reference never loads its files (local_MapReduce.py:119-129) -- a memset, so that non-finite values in
     // the dropped shard's sums (0 * inf = nan) cannot reach the reduction
@@ -573,11 +580,13 @@ extern "C" int gp_global_step_jitter(gp_ctx* c, int jitter_mask) {
   if (jitter_mask < 0 || jitter_mask > 3) return fail(c, GP_ERR_BAD_ARG, "gp_global_step_jitter: mask must be 0..3");
   GP_HIP(c, hipSetDevice(c->device));
   c->jitter_mask = jitter_mask;
+  c->pred_ok = false;
   GP_EV(c, 3);
   const int rc_gs = run_global_step(c);
   GP_EV(c, 4);
   if (rc_gs != GP_OK) return rc_gs;
   c->state = 2;
+  c->pred_ok = true;           // gp_predict still checks the step's outcome (check_global)
   return GP_OK;
 }
 
@@ -733,8 +742,30 @@ extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* 
   GP_HIP(c, hipMemcpyAsync(c->stats + Mp * Mp + Mp * Dp, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->spack_filled = false;     // the packed payload of an earlier evaluation no longer describes these statistics
+  c->pred_ok = false;
   if (c->state < 1) c->state = 1;
   return GP_OK;
+}
+
+extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, int flags, double* mean, double* var) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict: n must be >= 0");
+  if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_predict: unknown flags %d", flags);
+  if (c->state < 2 || !c->have_globals || !c->pred_ok)
+    return fail(c, GP_ERR_STATE, "gp_predict needs a global step on the statistics and globals as they are now (none since the last phase 1, "
+                "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)");
+  GP_HIP(c, hipSetDevice(c->device));
+  GP_TRY(resolve_i8_check(c));
+  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "gp_predict: the last global step did not succeed (%s)", c->gs_msg.c_str());
+  if (n == 0) return GP_OK;
+  if (!X_mu) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is NULL");
+  const size_t nq = (size_t)n * c->Q;
+  for (size_t i = 0; i < nq; ++i) {
+    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is not finite");
+    if (X_S && (!std::isfinite(X_S[i]) || (!xs_is_raw && X_S[i] < 0.0))) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_S must be finite and >= 0");
+  }
+  if (!mean && !var) return GP_OK;
+  return run_predict(c, (long)n, X_mu, X_S, xs_is_raw, flags, mean, var);
 }
 
 // ---- final gradients ---------------------------------------------------------------------------------------------
@@ -838,7 +869,7 @@ extern "C" int gp_cg_update(gp_ctx* c, int which, double a) {
                      c->Xmu, c->Xs);
   GP_HIP(c, hipGetLastError());
   if (which == 0 || which == 1 || which == 5) c->have_dir = true;
-  if (which == 2) { c->state = 0; c->prep_fixa_valid = false; }   // the embeddings moved: statistics are stale
+  if (which == 2) { c->state = 0; c->prep_fixa_valid = false; c->pred_ok = false; }   // the embeddings moved: statistics are stale
   return GP_OK;
 }
 

@@ -195,6 +195,21 @@ struct gp_ctx {
   double* gen_T = nullptr;    // [gen_P][M][M]
   double* gen_rt = nullptr;   // [gen_P][M][Q + 1]
   long gen_P = 0;             // points per chunk
+  // gp_predict (predict.hip): allocated on first use, pr_rows points per chunk
+  bool pred_ok = false;       // the global step's Inv / Linv / E describe the statistics buffer as it is now (cleared whenever it or Z changes)
+  long pr_rows = 0;
+  double* pr_in = nullptr;    // [2][pr_rows][Q] X_mu | X_S of the chunk as given
+  double* pr_mu = nullptr;    // [pr_rows][Q]
+  double* pr_U = nullptr;     // [pr_rows][Q] alpha / (alpha S + 1)
+  double* pr_lnc1 = nullptr;  // [pr_rows]
+  double* pr_P1 = nullptr;    // [pr_rows][Mp] Psi1 of the chunk
+  double* pr_G = nullptr;     // [pr_rows][Dp + 2 Mp] [mean | Lk^-1 k* | La^-1 k*]
+  double* pr_out = nullptr;   // [2][pr_rows][D] mean | var
+  double* pr_W = nullptr;     // [pr_rows][Q] w = alpha / (2 alpha S + 1)          (uncertain inputs)
+  double* pr_V2 = nullptr;    // [pr_rows][Q] (alpha - w) / 2
+  double* pr_lnc2 = nullptr;  // [pr_rows]    1/2 ln c2
+  double* pr_LEA = nullptr;   // [pr_rows][Mp]
+  double* pr_B = nullptr;     // [Mp][Mp] Ki - P
   // CG vectors (resident): grad_latest/new/old (2,N,Q) each
   double* g_latest = nullptr;
   double* g_new = nullptr;
@@ -264,6 +279,11 @@ int run_phase2_b_generic(gp_ctx* c);
 // psi2_tile.hip (regime B phase 2 on tile pairs)
 bool pt2_applicable(const gp_ctx* c, bool sym_available);
 int run_phase2_b_tiles(gp_ctx* c);
+int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
+// predict.hip
+extern std::atomic<int> g_opt_pred_rows;
+int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
+void pred_free(gp_ctx* c);
 // compat.hip
 int compat_build(gp_ctx* c, int which, double** out, long* count);
 // comm.hip

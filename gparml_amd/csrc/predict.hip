@@ -1,0 +1,348 @@
+// Posterior predictive mean and variance at new inputs (gp_predict), after a global step of this context.
+//
+// With Ki = K_mm^-1, P = (K_mm + beta Psi2)^-1, C = Psi1^T Y and E = P C (the global step's refined product), Titsias' optimal q(u) gives
+//   W = beta E  (M x D),   B = Ki - P.
+// Deterministic inputs x* (X_S == NULL), k* = psi1(x*):
+//   mean = k*^T W,   var_f = sf2 - k*^T B k*   (one value per point)
+// where k*^T B k* is formed as |Lk^-1 k*|^2 - |La^-1 k*|^2 from the global step's inverse Cholesky factors (Linv = [Lk^-1 ; La^-1], lower):
+// two sums of squares of O(sf2) vectors instead of a quadratic form in Ki - P, whose elements are O(cond / sf2) and cancel.
+//   Psi1* rows: psi1_rows (psi.hip's generic Psi1 kernel on prediction-owned buffers);
+//   [mean | Lk^-1 k* | La^-1 k*] = Psi1* [beta E | Linv^T]: two products on the MFMA GEMM core (launch_gemm);
+//   pred_det_rows_kernel: one wave per point, mean out and var = sf2 - sum of squares + sum of squares (+ 1/beta).
+// Uncertain inputs x* ~ N(mu*, diag S*), psi1* = psi1(mu*, S*), psi2* = psi2_point(mu*, S*):
+//   mean_d = psi1*^T W_d,   var_d = sf2 - tr(B psi2*) + W_d^T psi2* W_d - mean_d^2
+//   mean: the same product as above (beta E only);
+//   pred_psi2w_kernel: one workgroup per (point, 128 output columns); psi2* is generated tile by tile from the factorised form of psi2.hip's header,
+//     psi2[m, m'] = exp(LEA[m] + LEA[m'] + sum_q v2_q z_mq z_m'q),  v2 = (alpha - w) / 2,
+//   and fed as the A operand of v_mfma_f64_4x4x4_4b_f64 against E; the epilogue folds the column dot with E and sum(B o psi2) (both in fixed order).
+// Nothing of [n][M][M] is ever stored.  Every prediction buffer is owned by the context, allocated on first use and bounded by the chunk size
+// (pr_rows points per pass); gp_destroy frees them.  The evaluation's buffers are only read: phase 2 / gp_finish after a prediction give the same bits.
+#include "gp_common.h"
+#include "fexp.h"
+#include <algorithm>
+#include <cmath>
+
+namespace gp {
+
+// per point of the chunk (n < rows; rows >= cnt are zero / padding): mu, u = alpha / (alpha S + 1), ln c1 = ln sf2 - 1/2 sum ln(alpha S + 1);
+// uncertain inputs also w = alpha / (2 alpha S + 1), v2 = (alpha - w) / 2 and 1/2 ln c2 = ln sf2 - 1/4 sum ln(2 alpha S + 1)
+__global__ void __launch_bounds__(256) pred_prep_kernel(const double* __restrict__ Xin, const double* __restrict__ Sin, int raw, const double* __restrict__ alpha,
+                                                        long cnt, long rows, int Q, double sf2, double* __restrict__ mu, double* __restrict__ U,
+                                                        double* __restrict__ lnc1, double* __restrict__ Wq, double* __restrict__ V2, double* __restrict__ lnc2h) {
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < rows; n += (long)gridDim.x * 256L) {
+    double l1 = log(sf2), l2 = log(sf2);
+    for (int q = 0; q < Q; ++q) {
+      const long i = n * Q + q;
+      const double a = alpha[q];
+      double m = 0.0, s = 0.0;
+      if (n < cnt) {
+        m = Xin[i];
+        if (Sin) { s = Sin[i]; if (raw) s = log(1.0 + exp(s)); }     // softplus, as the shard's prep (psi.hip)
+      }
+      const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0, w = a / d2;
+      mu[i] = m;
+      U[i] = a / d1;
+      l1 -= 0.5 * log(d1);
+      if (Wq) { Wq[i] = w; V2[i] = 0.5 * (a - w); l2 -= 0.25 * log(d2); }
+    }
+    lnc1[n] = l1;
+    if (lnc2h) lnc2h[n] = l2;
+  }
+}
+
+// LEA[n][m] = 1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2 - 1/2 sum_q v2_nq z_mq^2  (kPadLog for m >= M or n >= cnt: exp gives exactly 0)
+__global__ void __launch_bounds__(256) pred_lea_kernel(const double* __restrict__ mu, const double* __restrict__ Wq, const double* __restrict__ V2,
+                                                       const double* __restrict__ lnc2h, const double* __restrict__ Z, long cnt, long rows, int M, int Mp,
+                                                       int Q, double* __restrict__ LEA) {
+  const long total = rows * Mp;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long n = e / Mp;
+    const int m = (int)(e - n * Mp);
+    double v = kPadLog;
+    if (n < cnt && m < M) {
+      double s = 0.0, t = 0.0;
+      for (int q = 0; q < Q; ++q) {
+        const double z = Z[(long)m * Q + q], d = mu[n * Q + q] - z;
+        s = fma(Wq[n * Q + q] * d, d, s);
+        t = fma(V2[n * Q + q] * z, z, t);
+      }
+      v = lnc2h[n] - 0.5 * (s + t);
+    }
+    LEA[e] = v;
+  }
+}
+
+// B = Ki - P on [Mp][Mp], zero outside M x M
+__global__ void __launch_bounds__(256) pred_bmat_kernel(const double* __restrict__ Inv, int M, int Mp, double* __restrict__ B) {
+  const long mm = (long)Mp * Mp;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < mm; e += (long)gridDim.x * 256L) {
+    const long i = e / Mp, j = e - i * Mp;
+    B[e] = (i < M && j < M) ? Inv[e] - Inv[mm + e] : 0.0;
+  }
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
+  return v;
+}
+
+// deterministic inputs: row n of G = [mean (Dp) | Lk^-1 k* (Mp) | La^-1 k* (Mp)] -> mean[n][0..D), var[n]; one wave per point, fixed summation order
+__global__ void __launch_bounds__(256) pred_det_rows_kernel(const double* __restrict__ G, long ldg, long cnt, int M, int Mp, int D, int Dp, double sf2,
+                                                            double noise, double* __restrict__ mean, double* __restrict__ var) {
+  const int lane = threadIdx.x & 63;
+  const long n = blockIdx.x * 4L + (threadIdx.x >> 6);
+  if (n >= cnt) return;
+  const double* g = G + n * ldg;
+  for (int d = lane; d < D; d += 64) mean[n * D + d] = g[d];
+  double sk = 0.0, sa = 0.0;
+  for (int i = lane; i < M; i += 64) {
+    const double a = g[Dp + i], b = g[Dp + Mp + i];
+    sk = fma(a, a, sk);
+    sa = fma(b, b, sa);
+  }
+  sk = wave_sum(sk);
+  sa = wave_sum(sa);
+  if (lane == 0) var[n] = sf2 - sk + sa + noise;
+}
+
+// ---- uncertain inputs: psi2* E on the FP64 matrix core ---------------------------------------------------------------------------------------
+// Workgroup (point n, column tile c0 = 128 blockIdx.y), four waves.  A pass covers 64 rows m (16 per wave); for every chunk of PW_KC rows m' the
+// workgroup stages E[m'][c0 ..] (pW), z_m' (pZ) and LEA[n][m'] (pL) in LDS, and every wave steps through the chunk four m' at a time:
+//   lane l generates psi2[m = row0 + (l & 15)][m' = k + (l >> 4)] (the A-operand element of the 16 x 4 x 4 product, mma_f64.h's lane map),
+//   adds B[m][m'] psi2 to its trace partial, and issues 32 MFMAs against the 32 four-column groups of the tile (B operand E[m'][c0 + 4j + (l & 3)]).
+// After the pass the accumulators hold (psi2 E)[m][c] for the wave's 16 rows: the epilogue adds E[m][c] (psi2 E)[m][c] to the lane's column partials.
+// QR: compile-time width of the row factors v2_q z_mq kept in registers (16 or 64, zero-padded); QR = 0 reads them from memory (any Q).
+constexpr int PW_DW = 128;              // output columns per workgroup
+constexpr int PW_KC = 32;               // m' rows per LDS chunk
+constexpr int PW_LDW = PW_DW + 4;       // padded row stride of the E chunk: the four m' rows of one read land on different banks
+
+struct PsiWArgs {
+  const double* LEA;    // [rows][Mp]
+  const double* V2;     // [rows][Q]
+  const double* Z;      // [Mp][Q] (rows >= M zero)
+  const double* E;      // [Mp][Dp]
+  const double* B;      // [Mp][Mp]
+  const double* G;      // [rows][ldg]: the mean in columns 0 .. D
+  long ldg;
+  int M, Mp, Q, D, Dp;
+  double sf2, beta, noise;
+  double* var;          // [cnt][D]
+};
+
+template <int QR>
+__global__ void __launch_bounds__(256) pred_psi2w_kernel(PsiWArgs a) {
+  constexpr int QS = QR > 0 ? QR : 1;
+  __shared__ double pW[PW_KC * PW_LDW];
+  __shared__ double pZ[PW_KC * QS];
+  __shared__ double pL[PW_KC];
+  __shared__ double red[4 * PW_DW + 4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long n = blockIdx.x;
+  const int c0 = blockIdx.y * PW_DW;
+  const int M = a.M, Mp = a.Mp, Q = a.Q;
+  const double* lea = a.LEA + n * Mp;
+  const double* v2 = a.V2 + n * Q;
+  const int kend = (M + PW_KC - 1) / PW_KC * PW_KC;   // <= Mp (Mp is a multiple of 128)
+  const int kq = lane >> 4;                           // m' offset inside a four-row step (A and B operands)
+  double vpart[32];
+#pragma unroll
+  for (int j = 0; j < 32; ++j) vpart[j] = 0.0;
+  double tr = 0.0;
+  for (int r0 = 0; r0 < M; r0 += 64) {
+    const int row0 = r0 + 16 * wave;
+    const int m = row0 + (lane & 15);                 // < Mp
+    const double lm = lea[m];                         // kPadLog beyond M
+    double f[QS];
+    if constexpr (QR > 0) {
+#pragma unroll
+      for (int q = 0; q < QR; ++q) f[q] = (q < Q && m < M) ? v2[q] * a.Z[(long)m * Q + q] : 0.0;
+    }
+    double acc[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) acc[j] = 0.0;
+    for (int k0 = 0; k0 < kend; k0 += PW_KC) {
+      __syncthreads();                                // the previous chunk has been consumed
+      for (int e = tid; e < PW_KC * PW_DW; e += 256) {
+        const int r = e >> 7, cc = e & 127, k = k0 + r, col = c0 + cc;
+        pW[r * PW_LDW + cc] = (k < M && col < a.D) ? a.E[(long)k * a.Dp + col] : 0.0;
+      }
+      if constexpr (QR > 0) {
+        for (int e = tid; e < PW_KC * QR; e += 256) {
+          const int r = e / QR, q = e - r * QR, k = k0 + r;
+          pZ[e] = (k < M && q < Q) ? a.Z[(long)k * Q + q] : 0.0;
+        }
+      }
+      if (tid < PW_KC) pL[tid] = lea[k0 + tid];
+      __syncthreads();
+      if (row0 < M) {                                 // wave-uniform: a wave whose 16 rows lie beyond M only helps staging
+#pragma unroll 1
+        for (int kk = 0; kk < PW_KC; kk += 4) {
+          const int r = kk + kq, k = k0 + r;
+          double s = lm + pL[r];
+          if constexpr (QR > 0) {
+#pragma unroll
+            for (int q = 0; q < QR; ++q) s = fma(f[q], pZ[r * QR + q], s);
+          } else {
+            const double* zm = a.Z + (long)min(m, M - 1) * Q;
+            const double* zk = a.Z + (long)min(k, M - 1) * Q;
+            for (int q = 0; q < Q; ++q) s = fma(v2[q] * zm[q], zk[q], s);
+          }
+          const double x = fexp(s);                   // exactly 0 when m or m' is padding (LEA = kPadLog)
+          tr = fma(a.B[(long)m * Mp + k], x, tr);
+          const double* wr = pW + r * PW_LDW + (lane & 3);
+#pragma unroll
+          for (int j = 0; j < 32; ++j) acc[j] = mfma444(x, wr[4 * j], acc[j]);
+        }
+      }
+    }
+    if (row0 < M) {
+      const int mr = row0 + 4 * ((lane >> 2) & 3) + (lane >> 4);      // the accumulator's row (mma_f64.h lane map)
+#pragma unroll
+      for (int j = 0; j < 32; ++j) {
+        const int col = c0 + 4 * j + (lane & 3);
+        if (mr < M && col < a.D) vpart[j] = fma(a.E[(long)mr * a.Dp + col], acc[j], vpart[j]);
+      }
+    }
+  }
+  // column sums over the lanes of one column (same lane & 3), then over the waves in order
+#pragma unroll
+  for (int j = 0; j < 32; ++j)
+#pragma unroll
+    for (int sh = 4; sh < 64; sh <<= 1) vpart[j] += __shfl_xor(vpart[j], sh);
+  tr = wave_sum(tr);
+  __syncthreads();
+  if (lane < 4) {
+#pragma unroll
+    for (int j = 0; j < 32; ++j) red[wave * PW_DW + 4 * j + lane] = vpart[j];
+  }
+  if (lane == 0) red[4 * PW_DW + wave] = tr;
+  __syncthreads();
+  if (tid < PW_DW) {
+    const int d = c0 + tid;
+    if (d < a.D) {
+      const double t = ((red[4 * PW_DW] + red[4 * PW_DW + 1]) + red[4 * PW_DW + 2]) + red[4 * PW_DW + 3];
+      const double v = ((red[tid] + red[PW_DW + tid]) + red[2 * PW_DW + tid]) + red[3 * PW_DW + tid];
+      const double mean = a.G[n * a.ldg + d];
+      a.var[n * a.D + d] = a.sf2 - t + a.beta * a.beta * v - mean * mean + a.noise;
+    }
+  }
+}
+
+// test hook (gp_debug_set_option "predict_rows"): points per chunk, rounded up to 128; 0 = the default below
+std::atomic<int> g_opt_pred_rows{0};
+
+static long pred_rows_for(const gp_ctx* c) {
+  const int opt = g_opt_pred_rows.load();
+  if (opt > 0) return round_up(opt, TILE);
+  // the chunk's product buffer [rows][Dp + 2 Mp] stays near 64 MB
+  const long per_row = 8L * (c->Dp + 2L * c->Mp);
+  return std::max<long>(TILE, std::min<long>(16384, (64L << 20) / per_row / TILE * TILE));
+}
+
+static int pred_alloc(gp_ctx* c, bool uncertain) {
+  const long R = pred_rows_for(c), Mp = c->Mp, Q = c->Q, D = c->D;
+  if (c->pr_rows != R) {
+    double* bufs[] = {c->pr_in, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, c->pr_G, c->pr_out, c->pr_W, c->pr_V2, c->pr_lnc2, c->pr_LEA, c->pr_B};
+    for (double* b : bufs) if (b) (void)hipFree(b);
+    c->pr_in = c->pr_mu = c->pr_U = c->pr_lnc1 = c->pr_P1 = c->pr_G = c->pr_out = c->pr_W = c->pr_V2 = c->pr_lnc2 = c->pr_LEA = c->pr_B = nullptr;
+    c->pr_rows = 0;
+    // every element of these is written before it is read (DA_RAW: NaN-filled in the poison test mode)
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_in, (size_t)2 * R * Q * 8, DA_RAW));          // X_mu | X_S of the chunk, as given
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_mu, (size_t)R * Q * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_U, (size_t)R * Q * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_lnc1, (size_t)R * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_P1, (size_t)R * Mp * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_G, (size_t)R * (c->Dp + 2 * Mp) * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_out, (size_t)2 * R * D * 8, DA_RAW));        // mean | var
+    c->pr_rows = R;
+  }
+  if (uncertain && !c->pr_LEA) {
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_W, (size_t)R * Q * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_V2, (size_t)R * Q * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_lnc2, (size_t)R * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_LEA, (size_t)R * Mp * 8, DA_RAW));
+    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_B, (size_t)Mp * Mp * 8, DA_RAW));
+  }
+  return GP_OK;
+}
+
+void pred_free(gp_ctx* c) {
+  double* bufs[] = {c->pr_in, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, c->pr_G, c->pr_out, c->pr_W, c->pr_V2, c->pr_lnc2, c->pr_LEA, c->pr_B};
+  for (double* b : bufs) if (b) (void)hipFree(b);
+}
+
+int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {
+  const bool unc = X_S != nullptr;
+  GP_TRY_RC(pred_alloc(c, unc));
+  hipStream_t st = c->stream;
+  const long R = c->pr_rows, Mp = c->Mp, Dp = c->Dp, M = c->M, Q = c->Q, D = c->D;
+  const long ldg = Dp + 2 * Mp;
+  const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
+  if (unc && var) {
+    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->Inv, (int)M, (int)Mp, c->pr_B);
+    GP_HIP(c, hipGetLastError());
+  }
+  double* out_mean = c->pr_out;
+  double* out_var = c->pr_out + R * D;
+  for (long n0 = 0; n0 < n; n0 += R) {
+    const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
+    double* xin = c->pr_in;
+    double* sin = c->pr_in + R * Q;
+    GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+    if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, cnt,
+                       rows, (int)Q, c->sf2, c->pr_mu, c->pr_U, c->pr_lnc1, unc ? c->pr_W : nullptr, unc ? c->pr_V2 : nullptr, unc ? c->pr_lnc2 : nullptr);
+    GP_HIP(c, hipGetLastError());
+    GP_TRY_RC(launch_psi1_rows(c, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, cnt, rows, Mp));
+    // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
+    GemmP g;
+    g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
+    g.A = c->pr_P1; g.lda = Mp; g.C = c->pr_G; g.ldc = ldg;
+    g.B = c->E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
+    launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g);
+    if (!unc) {
+      if (var) {
+        g.B = c->Linv; g.ldb = Mp; g.alpha = 1.0; g.C = c->pr_G + Dp;
+        launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g);
+      }
+      GP_HIP(c, hipGetLastError());
+      if (var) {
+        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, (int)M, (int)Mp, (int)D, (int)Dp,
+                           c->sf2, noise, out_mean, out_var);
+      } else {
+        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
+                           c->sf2, noise, out_mean, out_var);
+      }
+      GP_HIP(c, hipGetLastError());
+      if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
+      if (var) GP_HIP(c, hipMemcpyAsync(var + n0, out_var, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+    } else {
+      GP_HIP(c, hipGetLastError());
+      if (mean) {
+        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
+                           c->sf2, noise, out_mean, out_var);
+        GP_HIP(c, hipGetLastError());
+        GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
+      }
+      if (var) {
+        hipLaunchKernelGGL(pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, st, c->pr_mu, c->pr_W, c->pr_V2,
+                           c->pr_lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, c->pr_LEA);
+        PsiWArgs a;
+        a.LEA = c->pr_LEA; a.V2 = c->pr_V2; a.Z = c->Z; a.E = c->E; a.B = c->pr_B; a.G = c->pr_G; a.ldg = ldg;
+        a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;
+        const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
+        if (Q <= 16) hipLaunchKernelGGL(pred_psi2w_kernel<16>, grid, dim3(256), 0, st, a);
+        else if (Q <= 64) hipLaunchKernelGGL(pred_psi2w_kernel<64>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(pred_psi2w_kernel<0>, grid, dim3(256), 0, st, a);
+        GP_HIP(c, hipGetLastError());
+        GP_HIP(c, hipMemcpyAsync(var + n0 * D, out_var, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
+      }
+    }
+  }
+  GP_HIP(c, hipStreamSynchronize(st));
+  ++c->sync_epoch;
+  return GP_OK;
+}
+
+}  // namespace gp

@@ -347,6 +347,14 @@ __global__ void __launch_bounds__(256) psi1_generic_kernel(const double* __restr
   }
 }
 
+// Psi1 of `n` points given as [mu | u | ln c1] tables of `rows` (a multiple of 64) rows into out[rows][ld] (columns >= M and rows >= n zero): the
+// generic kernel above on buffers the caller owns (gp_predict's chunks)
+int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld) {
+  hipLaunchKernelGGL(psi1_generic_kernel, dim3(c->Mp / 128, (unsigned)(rows / 64)), dim3(256), 0, c->stream, mu, U, lnc1, c->Z, out, n, rows, c->M, c->Q, ld);
+  GP_HIP(c, hipGetLastError());
+  return GP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ phase 1
 // out[i][j] = sum_n Kaug[n][ti*128 + i] * Kaug[n][tj*128 + j] over the slice's rows: Psi2 tiles (tj < Mp/128,
 // only tj >= ti) and C = Psi1^T Y tiles (tj >= Mp/128).  Split over n into slices; partial tiles are summed by

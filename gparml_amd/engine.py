@@ -251,6 +251,26 @@ class ShardEngine(object):
                 out['grad_X_S'] = self.download('GRAD_X_S')
         return out
 
+    # ---- prediction (gp_predict) ---------------------------------------------------------------------------
+    def predict(self, X_mu, X_S=None, include_noise=False, xs_is_raw=False):
+        """Posterior predictive at new inputs, after a successful global step of this engine (its reduced statistics: the whole model).
+        Returns (mean (n, D), var): var is (n, 1) for deterministic inputs (X_S None: one variance per point) and (n, D) for uncertain inputs
+        x ~ N(X_mu, diag X_S).  ``include_noise`` adds 1/beta (y instead of f).  The evaluation state is left untouched."""
+        X_mu = np.atleast_2d(np.asarray(X_mu, dtype=np.float64))
+        assert X_mu.ndim == 2 and X_mu.shape[1] == self.Q, 'X_mu shape %s: (n, %d) expected' % (X_mu.shape, self.Q)
+        n = X_mu.shape[0]
+        X_mu, pm = _lib.as_c(X_mu)
+        ps = None
+        if X_S is not None:
+            X_S = np.atleast_2d(np.asarray(X_S, dtype=np.float64))
+            assert X_S.shape == X_mu.shape, 'X_S shape %s != X_mu shape %s' % (X_S.shape, X_mu.shape)
+            X_S, ps = _lib.as_c(X_S)
+        mean = np.empty((n, self.D))
+        var = np.empty((n, 1) if X_S is None else (n, self.D))
+        self._ck(self.lib.gp_predict(self.h, n, pm, ps, 1 if xs_is_raw else 0, 1 if include_noise else 0, mean.ctypes.data_as(_lib._dp),
+                                     var.ctypes.data_as(_lib._dp)), 'gp_predict')
+        return mean, var
+
     regime_A_hint = False
     _jitter_used = 0
     _jitter_hint = 0          # the jitter mask the previous evaluation ended up with (global_step)

@@ -28,6 +28,24 @@ class Predictor(object):
         self.device = device
         self._pt = None
 
+    def predict_outputs(self, X_mu, X_S, include_noise=False):
+        """Reconstruct Y* from q(x*) = N(X_mu, diag X_S) (what ``test`` returns for new rows) with the trained model: the posterior predictive
+        mean (n, D) and variance (n, D) of every output, against the stored accumulated statistics of the training data only (not the new
+        rows' own statistics).  The columns a ``test(..., mask=...)`` call left out are the imputed ones.  ``include_noise`` adds 1/beta.
+        X_S None predicts at the point X_mu (variance (n, 1))."""
+        from .engine import ShardEngine
+        g, a = self.gs, self.acc
+        f = lambda x: float(numpy.asarray(x).reshape(-1)[0])
+        eng = ShardEngine(1, self.D, self.M, self.Q, device=self.device)
+        try:
+            eng.set_globals(numpy.asarray(g['Z'], dtype=float), f(g['sf2']), numpy.asarray(g['alpha'], dtype=float).reshape(-1), f(g['beta']),
+                            N_global=max(self.N, 1))
+            eng.set_local_statistics(f(a['sum_YYT']), a['sum_exp_K_mi_K_im'], a['sum_exp_K_miY'], f(a['sum_exp_K_ii']), f(a['sum_KL']))
+            eng.global_step(sync=True)
+            return eng.predict(X_mu, X_S, include_noise=include_noise)
+        finally:
+            eng.close()
+
     def _partial_terms(self):
         if self._pt is None:
             g = self.gs

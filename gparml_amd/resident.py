@@ -89,6 +89,34 @@ class ResidentModel(object):
             root.stats_unpack()
         self.n_collectives += 1
 
+    _stats_x = None
+    _stats_version = -1
+
+    def predict(self, flat_array, X_mu, X_S=None, include_noise=False):
+        """Posterior predictive mean and variance at new inputs for the model at the optimiser's parameter vector ``flat_array`` (ShardEngine.predict:
+        var is (n, 1) for X_S None, (n, D) otherwise).  When ``flat_array`` is not, bit for bit, the vector of the last evaluation (SCG's last
+        evaluation is a trial point, not the x it returns) or the resident embeddings moved since (an accepted step's update_X), the statistics
+        part is run first at that point with the resident embeddings as they are (phase 1, the reduce, the global step).  That run is COLLECTIVE across ranks: every rank of a multi-GPU job must call predict with the same vector."""
+        flat_array = np.asarray(flat_array, dtype=np.float64)
+        last = self._stats_x
+        if (last is None or last.shape != flat_array.shape or last.tobytes() != flat_array.tobytes()
+                or self._stats_version != self.version):
+            M, Q = self.M, self.Q
+            xt = transform_vec(self._pos, flat_array)
+            Z = xt[:M * Q].reshape(M, Q)
+            sf2, alpha, beta = xt[M * Q], xt[M * Q + 1:M * Q + 1 + Q], xt[M * Q + 1 + Q]
+            for e in self.engines:
+                e.set_globals(Z, sf2, alpha, beta, N_global=self.N, step_size=0.0)
+                e.phase1()
+            root = self.engines[0]
+            for e in self.engines[1:]:
+                root.combine(e, 'stats', 'add')
+            self._allreduce_buffers('stats')
+            root.global_step(sync=True)
+            self._stats_x = np.array(flat_array, copy=True)
+            self._stats_version = self.version
+        return self.engines[0].predict(X_mu, X_S, include_noise=include_noise)
+
     def close(self):
         for e in self.engines:
             e.close()
@@ -124,6 +152,10 @@ class ResidentModel(object):
             except JitterRetry as r:        # same reduced statistics on every rank: all ranks retry together (partial_terms.py:452-456)
                 jitter = r.mask
         self.version += 1                   # grad_latest changed
+        # the vector whose statistics the root engine holds, and the resident vectors' version they were computed with (an optimiser's
+        # update of the embeddings -- scg_adapted / gd after an accepted step -- bumps the version: the statistics are then recomputed)
+        self._stats_x = np.array(flat_array, dtype=np.float64, copy=True)
+        self._stats_version = self.version
         grad = np.concatenate([res['grad_Z'].ravel(), [res['grad_sf2']], res['grad_alpha'], [0.0 if self.fixed_beta else res['grad_beta']]])
         grad = grad * transform_grad_vec(self._pos, flat_array)
         return -res['F'], -grad

@@ -161,6 +161,19 @@ int gp_grads_buffer(gp_ctx* ctx, void** dev_ptr, int64_t* n_doubles);
  * partial_terms.py:207-240, 286-299, 322-333, 340-360).  Any output pointer may be NULL. */
 int gp_finish(gp_ctx* ctx, double* F, double* grad_Z, double* grad_sf2, double* grad_alpha, double* grad_beta);
 
+/* ---- prediction ------------------------------------------------------------------------------- */
+/* posterior predictive at n new inputs, after a successful global step on this context (the reduced statistics of the whole model; also after
+ * gp_set_local_statistics or gp_buffer_combine).  With W = beta (Kmm + beta Psi2)^-1 Psi1^T Y and B = Kmm^-1 - (Kmm + beta Psi2)^-1:
+ * X_S == NULL (deterministic inputs): mean = psi1(x)^T W, var = sf2 - psi1(x)^T B psi1(x) (one value per point);
+ * X_S != NULL (x ~ N(X_mu, diag X_S)): mean_d = psi1^T W_d, var_d = sf2 - tr(B psi2) + W_d^T psi2 W_d - mean_d^2.
+ * X_mu (n,Q); X_S (n,Q) or NULL (xs_is_raw as gp_upload_shard); flags bit 0: add 1/beta (predict y, not f).
+ * mean (n,D) or NULL; var (n,D) when X_S != NULL, (n) when X_S == NULL, or NULL.  Synchronous.  Leaves the evaluation state untouched:
+ * phase 2 / gp_finish after it give bit-identical results.  GP_ERR_STATE before a global step, after one that failed or asked for a jitter
+ * retry, and when the statistics or globals changed since the last global step (gp_phase1, gp_set_globals, gp_set_local_statistics,
+ * gp_buffer_combine / gp_scale_buffer of the statistics, gp_stats_unpack, gp_allreduce(ctx, 0), uploads, gp_cg_update moving the embeddings);
+ * GP_ERR_BAD_ARG for n < 0 or a non-finite mean / negative or non-finite variance; n = 0 writes nothing. */
+int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, int flags, double* mean, double* var);
+
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
 /* set the reduced statistics from the host (partial_terms.set_local_statistics, partial_terms.py:54-61) */
