@@ -18,18 +18,10 @@ int fail(gp_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
+hipStream_t ctx_stream(const gp_ctx* c) { return c ? c->stream : nullptr; }
+
 std::atomic<int> g_opt_poison{[] { const char* e = getenv("GPARML_POISON"); return (e && e[0] == '1') ? 1 : 0; }()};
-int dalloc_bytes(gp_ctx* c, void** p, size_t bytes, int mode) {
-  bytes = std::max<size_t>(bytes, 8);
-  GP_HIP(c, hipMalloc(p, bytes));
-  const bool poison = g_opt_poison.load() && mode != DA_ZERO;
-  if (poison || mode != DA_RAW) GP_HIP(c, hipMemsetAsync(*p, poison ? 0xFF : 0, bytes, c->stream));
-  return GP_OK;
-}
-template <typename T>
-static int dalloc(gp_ctx* c, T** p, size_t count, int mode = DA_INIT) {
-  return dalloc_bytes(c, (void**)p, count * sizeof(T), mode);
-}
+std::atomic<int> g_alloc_fail_after{0};
 #define GP_TRY(x) do { int rc__ = (x); if (rc__ != GP_OK) return rc__; } while (0)
 
 __global__ void sumsq_kernel(const double* __restrict__ x, long n, double* part) {
@@ -89,12 +81,11 @@ static int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n 
 
 static int download_matrix(gp_ctx* c, const double* src, long ld, long rows, long cols, double* dst, int64_t n) {
   if (n != rows * cols) return fail(c, GP_ERR_BAD_ARG, "gp_download: expected %ld doubles, got %ld", rows * cols, (long)n);
-  double* tmp = nullptr;
-  GP_HIP(c, hipMalloc((void**)&tmp, std::max<long>(rows * cols, 1) * 8));
+  DevBuf<double> tmp;
+  GP_TRY(tmp.alloc(c, rows * cols, DA_RAW));
   hipLaunchKernelGGL(gather2d_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, c->stream, src, ld, rows, cols, tmp);
   hipError_t e = hipMemcpyAsync(dst, tmp, rows * cols * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
   if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
   return GP_OK;
 }
@@ -125,59 +116,55 @@ extern "C" int gp_create(gp_ctx** out, int device, int64_t N_s, int D, int M, in
   c->CZ = 2 * Q + 1; c->CZp = (int)round_up(c->CZ, 4);
   const long Mp = c->Mp, Dp = c->Dp, Np = c->Np;
   int rc = GP_OK;
-  auto A = [&](auto** p, size_t n) { if (rc == GP_OK) rc = dalloc(c, p, n); };
-  A(&c->Kaug, (size_t)Np * c->LDK);
-  A(&c->Xmu, (size_t)N_s * Q); A(&c->Xs, (size_t)N_s * Q); A(&c->dir, (size_t)2 * N_s * Q);
-  A(&c->mu, (size_t)Np * Q); A(&c->S, (size_t)Np * Q); A(&c->U, (size_t)Np * Q);
-  if (rc == GP_OK) rc = dalloc(c, &c->PU, (size_t)Np * (2 * std::max(psi1_qp(Q), 2) + 2), DA_ZERO);   // zero contract: the records' columns Q .. QP - 1 (u = 0: no guards in psi1_kernel's q loop) are never written
-  A(&c->lnc1, (size_t)Np); A(&c->Xa, (size_t)Np * c->CXp);
-  A(&c->Z, (size_t)Mp * Q); A(&c->alpha, (size_t)Q); A(&c->Zaug, (size_t)Mp * c->CZp + 8); A(&c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
-  A(&c->stats, (size_t)Mp * Mp + Mp * Dp + SC_COUNT);
-  A(&c->grads, (size_t)M * Q + Q);
+  auto A = [&](auto& b, size_t n, int mode = DA_INIT) { if (rc == GP_OK) rc = b.alloc(c, n, mode); };
+  A(c->Kaug, (size_t)Np * c->LDK);
+  A(c->Xmu, (size_t)N_s * Q); A(c->Xs, (size_t)N_s * Q); A(c->dir, (size_t)2 * N_s * Q);
+  A(c->mu, (size_t)Np * Q); A(c->S, (size_t)Np * Q); A(c->U, (size_t)Np * Q);
+  A(c->PU, (size_t)Np * (2 * std::max(psi1_qp(Q), 2) + 2), DA_ZERO);   // zero contract: the records' columns Q .. QP - 1 (u = 0: no guards in psi1_kernel's q loop) are never written
+  A(c->lnc1, (size_t)Np); A(c->Xa, (size_t)Np * c->CXp);
+  A(c->Z, (size_t)Mp * Q); A(c->alpha, (size_t)Q); A(c->Zaug, (size_t)Mp * c->CZp + 8); A(c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
+  A(c->stats, (size_t)Mp * Mp + Mp * Dp + SC_COUNT);
+  A(c->grads, (size_t)M * Q + Q);
   // phase-1 tile table: Psi2 upper tiles first, then the C tiles
   std::vector<int> tiles;
   const int mt = c->Mp / TILE, dt = c->Dp / TILE;
   for (int i = 0; i < mt; ++i) for (int j = i; j < mt; ++j) { tiles.push_back(i); tiles.push_back(j); }
   for (int i = 0; i < mt; ++i) for (int j = 0; j < dt; ++j) { tiles.push_back(i); tiles.push_back(mt + j); }
   c->n_tiles = (int)tiles.size() / 2;
-  A(&c->tiles, tiles.size());
-  if (rc == GP_OK && hipMemcpy(c->tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = fail(c, GP_ERR_HIP, "tile table upload failed");
+  if (rc == GP_OK) rc = upload(c, c->tiles, tiles);      // (the device synchronisation below completes the copy)
   const int total_chunks = (int)(Np / KC);
   const int S = std::max(1, std::min(512 / std::max(1, std::min(c->n_tiles, mt * dt > 0 ? c->n_tiles : 1)), total_chunks));
   // worst case slices x tiles (regime B uses fewer tiles, hence possibly more slices)
   const int Tb = mt * dt;
   const int Sb = std::max(1, std::min(512 / std::max(1, Tb), total_chunks));
-  c->part_doubles = (size_t)std::max((long)(S + 16) * c->n_tiles, (long)(Sb + 16) * Tb) * TILE * TILE;
-  if (c->part_doubles < (size_t)1100 * TILE * TILE) c->part_doubles = (size_t)1100 * TILE * TILE;   // p1v2: up to 1024 partial tiles
-  A(&c->part, c->part_doubles);
+  // ... and at least the 1024 partial tiles of p1v2
+  A(c->part, std::max((size_t)std::max((long)(S + 16) * c->n_tiles, (long)(Sb + 16) * Tb) * TILE * TILE, (size_t)1100 * TILE * TILE));
   c->kl_blocks = blocks_for(Np);
-  A(&c->klpart, (size_t)c->kl_blocks + 8192);
-  A(&c->Kmm, (size_t)2 * Mp * Mp); A(&c->Lmat, (size_t)2 * Mp * Mp); A(&c->Inv, (size_t)2 * Mp * Mp);
-  if (rc == GP_OK) rc = dalloc(c, &c->Linv, (size_t)2 * Mp * Mp, DA_ZERO);   // zero contract: the 128-blocks above the block diagonal are never written (potrf_inverse_batched's precondition)
+  A(c->klpart, (size_t)c->kl_blocks + 8192);
+  A(c->Kmm, (size_t)2 * Mp * Mp); A(c->Lmat, (size_t)2 * Mp * Mp); A(c->Inv, (size_t)2 * Mp * Mp);
+  A(c->Linv, (size_t)2 * Mp * Mp, DA_ZERO);   // zero contract: the 128-blocks above the block diagonal are never written (potrf_inverse_batched's precondition)
   if (Mp >= 512 && Mp <= 2048) {
     // gsi8.hip: ten digit planes of W = [A | B] for the larger of the two products (K_mm^-1 | Psi2: 2 Mp columns; K_mm + beta Psi2 | E: Mp + Dp), and W's column scales
-    c->gss_count = (size_t)Mp + std::max(Mp, Dp);
-    c->gsd_bytes = (size_t)10 * Mp * c->gss_count;
-    double* tmp = nullptr;
-    A(&tmp, c->gsd_bytes / 8); c->gsd = reinterpret_cast<int8_t*>(tmp);
-    A(&c->gss, c->gss_count);
+    const size_t wcols = (size_t)Mp + std::max(Mp, Dp);
+    A(c->gsd, (size_t)10 * Mp * wcols);
+    A(c->gss, wcols);
   }
-  A(&c->KmmKeep, (size_t)Mp * Mp); A(&c->T1, (size_t)Mp * std::max<long>(std::max(Mp, Dp), 256)); A(&c->T2, (size_t)Mp * std::max(Mp, Dp));
-  A(&c->dFdK, (size_t)Mp * Mp); A(&c->Bbar, (size_t)Mp * Mp);
-  A(&c->E, (size_t)Mp * Dp); A(&c->PsiE, (size_t)Mp * Dp); A(&c->Abar, (size_t)Mp * Dp);
-  A(&c->Bm, (size_t)c->LDK * Mp);
-  A(&c->gs, (size_t)GS_COUNT + 8 + 8 * 64);   // scalars | failure flags | dots_kernel partials [8 jobs][64 blocks]
-  A(&c->gK, (size_t)M * Q + Q);
+  A(c->KmmKeep, (size_t)Mp * Mp); A(c->T1, (size_t)Mp * std::max<long>(std::max(Mp, Dp), 256)); A(c->T2, (size_t)Mp * std::max(Mp, Dp));
+  A(c->dFdK, (size_t)Mp * Mp); A(c->Bbar, (size_t)Mp * Mp);
+  A(c->E, (size_t)Mp * Dp); A(c->PsiE, (size_t)Mp * Dp); A(c->Abar, (size_t)Mp * Dp);
+  A(c->Bm, (size_t)c->LDK * Mp);
+  A(c->gs, (size_t)GS_COUNT + 8 + 8 * 64);   // scalars | failure flags | dots_kernel partials [8 jobs][64 blocks]
+  A(c->gK, (size_t)M * Q + Q);
   // phase 2
   c->p2_slices = std::max(1, std::min<int>(8 * std::max(1, 64 / mt), (int)(Np / TILE)));
-  A(&c->Rpart, (size_t)2 * (c->p2_slices + 8) * Mp * c->CXp);
-  A(&c->HZp, (size_t)(Mp / TILE) * Np * c->CZp);    // p2_gen8_kernel: per-point partials, one array per 128 inducing columns
-  A(&c->gXmu, (size_t)N_s * Q); A(&c->gXs, (size_t)N_s * Q);
+  A(c->Rpart, (size_t)2 * (c->p2_slices + 8) * Mp * c->CXp);
+  A(c->HZp, (size_t)(Mp / TILE) * Np * c->CZp);    // p2_gen8_kernel: per-point partials, one array per 128 inducing columns
+  A(c->gXmu, (size_t)N_s * Q); A(c->gXs, (size_t)N_s * Q);
   c->ga_blocks = blocks_for(Np);
-  A(&c->gapart, (size_t)c->ga_blocks * Q);
+  A(c->gapart, (size_t)c->ga_blocks * Q);
   // fast phase 2: per-wave (eight-wave kernel: blocks * 8 rows of <= 12) or per-256-points (four-wave kernel) partials of grad_alpha's mu^2 term
-  A(&c->hgpart, std::max((size_t)((N_s + 255) / 256) * Q, (size_t)8 * (c->p2_slices + 8) * (Mp / TILE) * 8 * 12));
-  A(&c->g_latest, (size_t)2 * N_s * Q); A(&c->g_new, (size_t)2 * N_s * Q); A(&c->g_old, (size_t)2 * N_s * Q);
+  A(c->hgpart, std::max((size_t)((N_s + 255) / 256) * Q, (size_t)8 * (c->p2_slices + 8) * (Mp / TILE) * 8 * 12));
+  A(c->g_latest, (size_t)2 * N_s * Q); A(c->g_new, (size_t)2 * N_s * Q); A(c->g_old, (size_t)2 * N_s * Q);
   for (int i = 0; i < 14 && rc == GP_OK; ++i) if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = fail(c, GP_ERR_HIP, "hipEventCreate failed");
   if (rc == GP_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(c, GP_ERR_HIP, "device sync failed after allocation");
   if (rc != GP_OK) { gp::g_create_error = c->err; gp_destroy(c); return rc; }
@@ -189,27 +176,10 @@ extern "C" int gp_destroy(gp_ctx* c) {
   if (!c) return GP_OK;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
-  double* bufs[] = {c->Kaug, c->Xmu, c->Xs, c->dir, c->mu, c->S, c->U, c->PU, c->lnc1, c->Xa, c->Z, c->alpha, c->Zaug, c->Zt, reinterpret_cast<double*>(c->gsd), c->gss,
-                    c->stats_external ? nullptr : c->stats, c->grads_external ? nullptr : c->grads, c->part, c->klpart, c->Kmm, c->Lmat,
-                    c->Linv, c->Inv, c->KmmKeep, c->T1, c->T2, c->dFdK, c->Bbar, c->E, c->PsiE, c->Abar, c->Bm, c->gs, c->gK, c->Rpart,
-                    c->HZp, c->gXmu, c->gXs, c->gapart, c->hgpart, c->g_latest, c->g_new, c->g_old, c->LE, c->LET, c->Bbar4, c->Vn, c->Wn, c->V2P, c->ZP, c->Z1P, c->WP, c->MUP, c->alphaP, c->lnc2h, c->DZ2,
-                    c->Gpart, c->Gtmp, c->gapart2, c->pp, c->Z1S, c->ppt, c->Gt, c->spack, c->gen_T, c->gen_rt};
-  for (double* b : bufs) if (b) (void)hipFree(b);
-  if (c->tiles) (void)hipFree(c->tiles);
-  if (c->ptiles) (void)hipFree(c->ptiles);
-  if (c->tiles64) (void)hipFree(c->tiles64);
-  if (c->sym_sched) (void)hipFree(c->sym_sched);
-  if (c->bmap) (void)hipFree(c->bmap);
-  if (c->staging) (void)hipFree(c->staging);
-  if (c->p2prog) (void)hipFree(c->p2prog);
-  gp::p1v2_free(c);
-  gp::p1i8_free(c);
-  gp::pred_free(c);
   gp::comm_free(c);
-  for (int i = 0; i < 14; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  if (c->h_out) (void)hipHostFree(c->h_out);
-  for (int i = 0; i < 2; ++i) { if (c->h_glob[i]) (void)hipHostFree(c->h_glob[i]); if (c->glob_ev[i]) (void)hipEventDestroy(c->glob_ev[i]); }
-  delete c;
+  for (hipEvent_t e : c->ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->glob_ev) if (e) (void)hipEventDestroy(e);
+  delete c;     // the buffers are its DevBuf members
   return GP_OK;
 }
 
@@ -276,8 +246,8 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
   if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "gp_upload_shard: NULL array");
   GP_HIP(c, hipSetDevice(c->device));
   const size_t nd = (size_t)c->N * c->D;
-  double* dY = nullptr;
-  GP_HIP(c, hipMalloc((void**)&dY, nd * 8));
+  DevBuf<double> dY;
+  GP_TRY(dY.alloc(c, nd, DA_RAW));
   hipError_t e = hipMemcpyAsync(dY, Y, nd * 8, hipMemcpyHostToDevice, c->stream);
   int rc = GP_OK;
   if (e != hipSuccess) rc = fail(c, GP_ERR_HIP, "Y upload failed: %s", hipGetErrorString(e));
@@ -296,7 +266,6 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
     c->sumYY = s;
     if (!std::isfinite(s)) rc = fail(c, GP_ERR_NON_FINITE, "Y contains non-finite values");
   }
-  (void)hipFree(dY);
   if (rc != GP_OK) return rc;
   GP_TRY(upload_embeddings(c, X_mu, X_S, xs_is_raw));
   c->have_data = true;
@@ -332,29 +301,13 @@ extern "C" int gp_set_direction(gp_ctx* c, const double* d) {
 // Not refilled: the shard's data and what the prep kernels derive from it alone (they are skipped from the second evaluation on for fixed
 // embeddings), the CG vectors, Linv (its upper blocks are a zero contract), tables and plans.
 static int poison_scratch(gp_ctx* c) {
-  const size_t Mp = c->Mp, Dp = c->Dp, Np = c->Np, M = c->M, Q = c->Q, N = c->N;
-  auto P = [&](void* p, size_t bytes) -> hipError_t { return (p && bytes) ? hipMemsetAsync(p, 0xFF, bytes, c->stream) : hipSuccess; };
-  auto PD = [&](double* p, size_t n) -> hipError_t { return P(p, n * sizeof(double)); };
-  GP_HIP(c, PD(c->part, c->part_doubles));
-  GP_HIP(c, PD(c->Rpart, (size_t)2 * (c->p2_slices + 8) * Mp * c->CXp));
-  GP_HIP(c, PD(c->HZp, (size_t)(Mp / TILE) * Np * c->CZp));
-  GP_HIP(c, PD(c->gapart, (size_t)c->ga_blocks * Q));
-  GP_HIP(c, PD(c->hgpart, std::max((size_t)((N + 255) / 256) * Q, (size_t)8 * (c->p2_slices + 8) * (Mp / TILE) * 8 * 12)));
-  GP_HIP(c, PD(c->Kmm, 2 * Mp * Mp)); GP_HIP(c, PD(c->Lmat, 2 * Mp * Mp)); GP_HIP(c, PD(c->Inv, 2 * Mp * Mp)); GP_HIP(c, PD(c->KmmKeep, Mp * Mp));
-  GP_HIP(c, PD(c->T1, Mp * std::max<size_t>(std::max(Mp, Dp), 256))); GP_HIP(c, PD(c->T2, Mp * std::max(Mp, Dp)));
-  GP_HIP(c, PD(c->dFdK, Mp * Mp)); GP_HIP(c, PD(c->Bbar, Mp * Mp)); GP_HIP(c, PD(c->E, Mp * Dp)); GP_HIP(c, PD(c->PsiE, Mp * Dp)); GP_HIP(c, PD(c->Abar, Mp * Dp));
-  GP_HIP(c, PD(c->Bm, (size_t)c->LDK * Mp)); GP_HIP(c, PD(c->gK, M * Q + Q)); GP_HIP(c, PD(c->gs, (size_t)GS_COUNT + 8 + 8 * 64));
-  if (!c->stats_external) GP_HIP(c, PD(c->stats, Mp * Mp + Mp * Dp + SC_COUNT));
-  if (!c->grads_external) GP_HIP(c, PD(c->grads, M * Q + Q));
-  GP_HIP(c, PD(c->gXmu, N * Q)); GP_HIP(c, PD(c->gXs, N * Q));
-  GP_HIP(c, hipMemset2DAsync(c->Kaug, (size_t)c->LDK * 8, 0xFF, Mp * 8, Np, c->stream));      // the Psi1 columns of [Psi1 | Y]
-  if (c->b_alloc) {
-    GP_HIP(c, PD(c->LE, Np * Mp)); GP_HIP(c, PD(c->LET, Np * Mp));
-    GP_HIP(c, PD(c->Gpart, (size_t)c->pb_blocks * M * Q)); GP_HIP(c, PD(c->gapart2, (size_t)c->pb_blocks * Q)); GP_HIP(c, PD(c->Gtmp, (size_t)64 * M * Q));
-    GP_HIP(c, PD(c->pp, c->pp_doubles));
-    if (c->ppt) GP_HIP(c, PD(c->ppt, (size_t)c->n_tiles64 * (3 * Q + 1) * c->b_ch));
-    if (c->Gt) GP_HIP(c, PD(c->Gt, (size_t)c->b_S * c->n_tiles64 * 2 * 64 * Q));
-  }
+  auto P = [&](const DevBuf<double>& b) -> hipError_t { return b.size() ? hipMemsetAsync(b, 0xFF, b.bytes(), c->stream) : hipSuccess; };
+  for (const DevBuf<double>* b : {&c->part, &c->Rpart, &c->HZp, &c->gapart, &c->hgpart, &c->Kmm, &c->Lmat, &c->Inv, &c->KmmKeep, &c->T1, &c->T2, &c->dFdK,
+                                  &c->Bbar, &c->E, &c->PsiE, &c->Abar, &c->Bm, &c->gK, &c->gs, &c->stats, &c->grads, &c->gXmu, &c->gXs})
+    GP_HIP(c, P(*b));
+  GP_HIP(c, hipMemset2DAsync(c->Kaug, (size_t)c->LDK * 8, 0xFF, (size_t)c->Mp * 8, c->Np, c->stream));      // the Psi1 columns of [Psi1 | Y]
+  if (c->b_alloc)
+    for (const DevBuf<double>* b : {&c->LE, &c->LET, &c->Gpart, &c->gapart2, &c->Gtmp, &c->pp, &c->ppt, &c->Gt}) GP_HIP(c, P(*b));
   return GP_OK;
 }
 
@@ -378,7 +331,7 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
   const size_t nz = (size_t)c->M * c->Q, nq = (size_t)c->Q;
   const int slot = c->glob_slot;
   if (!c->h_glob[slot]) {
-    GP_HIP(c, hipHostMalloc((void**)&c->h_glob[slot], (nz + nq) * sizeof(double), hipHostMallocMapped));
+    GP_TRY(c->h_glob[slot].alloc(c, nz + nq));
   } else if (c->glob_epoch[slot] >= c->sync_epoch) {
     // the kernel that read this slot two calls ago may still be queued: no stream synchronisation has been seen since (never the case in an
     // optimiser's sequence -- every evaluation ends in gp_finish's synchronisation -- so no event is recorded per call: that was one more signal
@@ -460,10 +413,7 @@ __global__ void __launch_bounds__(256) stats_unpack_kernel(const double* __restr
 }
 static int64_t spack_doubles(const gp_ctx* c) { return (int64_t)c->M * (c->M + 1) / 2 + (int64_t)c->M * c->D + SC_COUNT; }
 static int ensure_spack(gp_ctx* c) {
-  if (!c->spack) {
-    GP_TRY(dalloc_bytes(c, (void**)&c->spack, (size_t)spack_doubles(c) * sizeof(double), DA_RAW));
-    GP_HIP(c, hipMemsetAsync(c->spack, 0, (size_t)spack_doubles(c) * sizeof(double), c->stream));
-  }
+  if (!c->spack) GP_TRY(c->spack.alloc(c, spack_doubles(c), DA_ZERO));   // zero contract: gp_stats_packed_buffer hands it out before any pack
   return GP_OK;
 }
 extern "C" int gp_stats_packed_buffer(gp_ctx* c, void** dev_ptr, int64_t* n) {
@@ -537,12 +487,7 @@ extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int 
   if (src->device != dst->device || g_force_staging) {
     // shards on different GPUs of one process (options['devices']): peer copy into a staging buffer on the destination
     // device, then the same combine kernel -- the device-side form of statistics_reducer (local_MapReduce.py:250-277)
-    if (dst->staging_doubles < (size_t)n) {
-      if (dst->staging) (void)hipFree(dst->staging);
-      dst->staging = nullptr; dst->staging_doubles = 0;
-      GP_TRY(dalloc_bytes(dst, (void**)&dst->staging, (size_t)n * 8, DA_RAW));
-      dst->staging_doubles = (size_t)n;
-    }
+    GP_TRY(dst->staging.grow(dst, n, DA_RAW));
     GP_HIP(dst, hipMemcpyPeerAsync(dst->staging, dst->device, from, src->device, (size_t)n * 8, dst->stream));
     from = dst->staging;
   }
@@ -689,13 +634,12 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
       if (c->state < 3 || !c->want_emb) return fail(c, GP_ERR_STATE, "GP_ARR_GRAD_LATEST needs gp_phase2(ctx, 1) first");
       if (n != 2 * N * Q) return fail(c, GP_ERR_BAD_ARG, "GP_ARR_GRAD_LATEST wants %ld doubles", 2 * N * Q);
       if (c->regime_A) return fail(c, GP_ERR_NON_FINITE, "grad_X_S with X_S == 0 (1/S, partial_terms.py:417)");
-      double* tmp = nullptr;
-      GP_HIP(c, hipMalloc((void**)&tmp, 2 * N * Q * 8));
+      DevBuf<double> tmp;
+      GP_TRY(tmp.alloc(c, 2 * N * Q, DA_RAW));
       hipLaunchKernelGGL(grad_latest_kernel, dim3(blocks_for(N * Q)), dim3(256), 0, c->stream, c->gXmu, c->gXs, c->Xs, c->dir, N, (int)Q, c->step,
                          c->xs_raw ? 1 : 0, c->have_dir ? 1 : 0, tmp);
       hipError_t e = hipMemcpyAsync(dst, tmp, 2 * N * Q * 8, hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      (void)hipFree(tmp);
       if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
       return GP_OK;
     }
@@ -710,17 +654,14 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
     }
     case GP_ARR_PSI2_POINTS: case GP_ARR_DKMM_DZ: case GP_ARR_DPSI1TY_DZ: case GP_ARR_DPSI2_DZ: case GP_ARR_DKMM_DALPHA:
     case GP_ARR_DPSI1TY_DALPHA: case GP_ARR_DPSI2_DALPHA: {
-      double* buf = nullptr; long cnt = 0;
-      GP_TRY(compat_build(c, which, &buf, &cnt));
-      int rc = GP_OK;
-      if (cnt != n) rc = fail(c, GP_ERR_BAD_ARG, "gp_download: expected %ld doubles, got %ld", cnt, (long)n);
-      else {
-        hipError_t e = hipMemcpyAsync(dst, buf, cnt * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
-      }
-      (void)hipFree(buf);
-      return rc;
+      DevBuf<double> buf;
+      GP_TRY(compat_build(c, which, buf));
+      const long cnt = (long)buf.size();
+      if (cnt != n) return fail(c, GP_ERR_BAD_ARG, "gp_download: expected %ld doubles, got %ld", cnt, (long)n);
+      hipError_t e = hipMemcpyAsync(dst, buf, cnt * 8, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
+      return GP_OK;
     }
     default: return fail(c, GP_ERR_UNSUPPORTED, "gp_download: array %d not available", which);
   }
@@ -797,7 +738,7 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
     // the one host synchronisation of an evaluation: scalars + failure flags of the global step and the final gradients in one mapped buffer
     const long n = (long)c->M * c->Q + c->Q;
     constexpr int ngs = GS_COUNT + 8;
-    if (!c->h_out) GP_HIP(c, hipHostMalloc((void**)&c->h_out, (size_t)(ngs + n) * sizeof(double), hipHostMallocMapped));
+    if (!c->h_out) GP_TRY(c->h_out.alloc(c, ngs + n));
     double* dout = nullptr;
     GP_HIP(c, hipHostGetDevicePointer((void**)&dout, c->h_out, 0));
     hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->stream, c->gs, ngs, c->gK, c->grads, n, dout);

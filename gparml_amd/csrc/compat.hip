@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(256) gradalpha_parts_kernel(const double* A, c
 static int grid_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 16384)); }
 
 // fills a dense device buffer with the requested reference-shaped array; caller frees *out
-int compat_build(gp_ctx* c, int which, double** out, long* count) {
+int compat_build(gp_ctx* c, int which, DevBuf<double>& out) {
   const long N = c->N, M = c->M, Q = c->Q, D = c->D;
   long n = 0;
   switch (which) {
@@ -135,11 +135,12 @@ int compat_build(gp_ctx* c, int which, double** out, long* count) {
   if (!needs_data && c->state < 2) return fail(c, GP_ERR_STATE, "array %d needs the global step (Kmm) first", which);
   const bool needs_p2 = (which == GP_ARR_PSI2_POINTS || which == GP_ARR_DPSI2_DZ || which == GP_ARR_DPSI2_DALPHA);
   if (needs_p2 && N * M * M > (1L << 28)) return fail(c, GP_ERR_UNSUPPORTED, "per-point psi2 tensor (N,M,M) too large for compat mode (%ld doubles)", N * M * M);
-  double* buf = nullptr;
-  GP_TRY_RC(dalloc_bytes(c, (void**)&buf, (size_t)std::max<long>(n, 1) * 8, DA_RAW));
+  DevBuf<double> buf, p2buf;
+  GP_TRY_RC(buf.alloc(c, n, DA_RAW));
   double* p2 = nullptr;
   if (needs_p2) {
-    if (which == GP_ARR_PSI2_POINTS) p2 = buf; else GP_TRY_RC(dalloc_bytes(c, (void**)&p2, (size_t)(N * M * M) * 8, DA_RAW));
+    if (which != GP_ARR_PSI2_POINTS) GP_TRY_RC(p2buf.alloc(c, N * M * M, DA_RAW));
+    p2 = which == GP_ARR_PSI2_POINTS ? buf.get() : p2buf.get();
     if (!c->regime_A) { const int rc = run_dz2(c); if (rc != GP_OK) return rc; }
     hipLaunchKernelGGL(psi2_points_kernel, dim3(grid_for(N * M * M)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, c->LE, c->Mp, !b_generic(c) && le_interleaved(c->QB), c->Vn, c->DZ2,
                        N, (int)M, (int)Q, c->regime_A ? 1 : 0, p2);
@@ -161,10 +162,8 @@ int compat_build(gp_ctx* c, int which, double** out, long* count) {
   }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (p2 && p2 != buf) (void)hipFree(p2);
-  if (e != hipSuccess) { (void)hipFree(buf); return fail(c, GP_ERR_HIP, "compat kernel failed: %s", hipGetErrorString(e)); }
-  *out = buf;
-  *count = n;
+  if (e != hipSuccess) return fail(c, GP_ERR_HIP, "compat kernel failed: %s", hipGetErrorString(e));
+  out = std::move(buf);
   return GP_OK;
 }
 
@@ -172,9 +171,9 @@ int compat_build(gp_ctx* c, int which, double** out, long* count) {
 
 using namespace gp;
 
-static int up(gp_ctx* c, const double* h, long n, double** d) {
-  GP_TRY_RC(dalloc_bytes(c, (void**)d, (size_t)std::max<long>(n, 1) * 8, DA_RAW));
-  GP_HIP(c, hipMemcpyAsync(*d, h, n * 8, hipMemcpyHostToDevice, c->stream));
+static int up(gp_ctx* c, const double* h, long n, DevBuf<double>& d) {
+  GP_TRY_RC(d.alloc(c, n, DA_RAW));
+  GP_HIP(c, hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, c->stream));
   return GP_OK;
 }
 
@@ -184,22 +183,19 @@ extern "C" int gp_grad_from_parts(gp_ctx* c, int which, const double* dF_dKmm, c
   if (which != 0 && which != 1) return fail(c, GP_ERR_BAD_ARG, "gp_grad_from_parts: which must be 0 (Z) or 1 (alpha)");
   GP_HIP(c, hipSetDevice(c->device));
   const long M = c->M, Q = c->Q, D = c->D;
-  double *A = nullptr, *a3 = nullptr, *B = nullptr, *b3 = nullptr, *C = nullptr, *c3 = nullptr, *o = nullptr;
-  int rc = up(c, dF_dKmm, M * M, &A);
-  if (rc == GP_OK) rc = up(c, dKmm_dX, M * Q * M, &a3);
-  if (rc == GP_OK) rc = up(c, dF_dC, M * D, &B);
-  if (rc == GP_OK) rc = up(c, dC_dX, M * Q * D, &b3);
-  if (rc == GP_OK) rc = up(c, dF_dPsi2, M * M, &C);
-  if (rc == GP_OK) rc = up(c, dPsi2_dX, M * Q * M, &c3);
+  DevBuf<double> A, a3, B, b3, C, c3, o;
+  GP_TRY_RC(up(c, dF_dKmm, M * M, A));
+  GP_TRY_RC(up(c, dKmm_dX, M * Q * M, a3));
+  GP_TRY_RC(up(c, dF_dC, M * D, B));
+  GP_TRY_RC(up(c, dC_dX, M * Q * D, b3));
+  GP_TRY_RC(up(c, dF_dPsi2, M * M, C));
+  GP_TRY_RC(up(c, dPsi2_dX, M * Q * M, c3));
   const long no = which == 0 ? M * Q : Q;
-  if (rc == GP_OK) rc = dalloc_bytes(c, (void**)&o, (size_t)no * 8, DA_RAW);
-  if (rc == GP_OK) {
-    if (which == 0) hipLaunchKernelGGL(gradz_parts_kernel, dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
-    else hipLaunchKernelGGL(gradalpha_parts_kernel, dim3((unsigned)Q), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
-    hipError_t e = hipMemcpyAsync(out, o, no * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(c, GP_ERR_HIP, "gp_grad_from_parts: %s", hipGetErrorString(e));
-  }
-  for (double* p : {A, a3, B, b3, C, c3, o}) if (p) (void)hipFree(p);
-  return rc;
+  GP_TRY_RC(o.alloc(c, no, DA_RAW));
+  if (which == 0) hipLaunchKernelGGL(gradz_parts_kernel, dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
+  else hipLaunchKernelGGL(gradalpha_parts_kernel, dim3((unsigned)Q), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
+  hipError_t e = hipMemcpyAsync(out, o, no * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, GP_ERR_HIP, "gp_grad_from_parts: %s", hipGetErrorString(e));
+  return GP_OK;
 }

@@ -186,10 +186,10 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
   for (long i = 0; i < ar; ++i) for (long j = 0; j < ac; ++j) hA[i * a_cols + j] = A[i * ac + j];
   for (long i = 0; i < br; ++i) for (long j = 0; j < bc; ++j) hB[i * b_cols + j] = B[i * bc + j];
   for (long i = 0; i < m; ++i) for (long j = 0; j < n; ++j) hC[i * np + j] = C[i * n + j];
-  double *dA, *dB, *dC;
-  GP_HIP(ctx, hipMalloc(&dA, hA.size() * 8));
-  GP_HIP(ctx, hipMalloc(&dB, hB.size() * 8));
-  GP_HIP(ctx, hipMalloc(&dC, hC.size() * 8));
+  DevBuf<double> dA, dB, dC;
+  GP_TRY_RC(dA.alloc(ctx, hA.size(), DA_RAW));
+  GP_TRY_RC(dB.alloc(ctx, hB.size(), DA_RAW));
+  GP_TRY_RC(dC.alloc(ctx, hC.size(), DA_RAW));
   GP_HIP(ctx, hipMemcpy(dA, hA.data(), hA.size() * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dB, hB.data(), hB.size() * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dC, hC.data(), hC.size() * 8, hipMemcpyHostToDevice));
@@ -199,7 +199,6 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(hC.data(), dC, hC.size() * 8, hipMemcpyDeviceToHost));
   for (long i = 0; i < m; ++i) for (long j = 0; j < n; ++j) C[i * n + j] = hC[i * np + j];
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
   return GP_OK;
 }
 
@@ -216,8 +215,8 @@ extern "C" int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int
   std::vector<double> h(std::max(na, nb));
   unsigned long long s = 88172645463325252ULL;
   for (auto& x : h) { s ^= s << 13; s ^= s >> 7; s ^= s << 17; x = (double)(s >> 11) / 9007199254740992.0 * 2.0 - 1.0; if (fill == 1) x = 0.0; if (fill == 2) x = 1.25; }
-  double *dA, *dB, *dC;
-  GP_HIP(ctx, hipMalloc(&dA, na * 8)); GP_HIP(ctx, hipMalloc(&dB, nb * 8)); GP_HIP(ctx, hipMalloc(&dC, ncc * 8));
+  DevBuf<double> dA, dB, dC;
+  GP_TRY_RC(dA.alloc(ctx, na, DA_RAW)); GP_TRY_RC(dB.alloc(ctx, nb, DA_RAW)); GP_TRY_RC(dC.alloc(ctx, ncc, DA_RAW));
   GP_HIP(ctx, hipMemcpy(dA, h.data(), na * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dB, h.data(), nb * 8, hipMemcpyHostToDevice));
   GemmP p{dA, dB, dC, a_cols, b_cols, np, 0, 0, 0, (int)kp, 1.0, 0.0, 0};
@@ -232,6 +231,5 @@ extern "C" int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int
   float ms;
   GP_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
   *ms_out = ms / iters;
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC);
   return GP_OK;
 }

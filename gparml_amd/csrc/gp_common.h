@@ -6,9 +6,11 @@
 #include <cstdio>
 #include <cstdarg>
 #include <atomic>
+#include <memory>
 #include <string>
 #include <vector>
 #include "../../include/gparml_hip.h"
+#include "devbuf.h"
 #include "mma_f64.h"
 
 namespace gp {
@@ -51,6 +53,11 @@ enum { SC_SUM_YYT = 0, SC_PSI0 = 1, SC_KL = 2, SC_NLOCAL = 3, SC_COUNT = 8 };
 enum { GS_LOGDET_K = 0, GS_LOGDET_A = 1, GS_F = 2, GS_GRAD_BETA = 3, GS_GRAD_SF2 = 4, GS_FAIL = 5, GS_TR_KIPSI2 = 6, GS_TR_PPSI2 = 7,
        GS_TR_CE = 8, GS_TR_EPSI2E = 9, GS_SUM_V = 10, GS_SUM_AC = 11, GS_SUM_BPSI2 = 12, GS_COUNT = 16 };
 
+struct P1Plan;   // p1v2.hip
+struct I8Plan;   // p1i8.hip
+struct P1PlanDelete { void operator()(P1Plan* p) const; };
+struct I8PlanDelete { void operator()(I8Plan* p) const; };
+
 }  // namespace gp
 
 struct gp_ctx {
@@ -74,38 +81,32 @@ struct gp_ctx {
   bool prep_fixa_valid = false;   // regime A, fixed embeddings: the prep kernels' outputs (mu, features, records) are current
 
   // ---- device buffers ----
-  double* Kaug = nullptr;     // [Np][LDK]  Psi1 | Y
-  double* Xmu = nullptr;      // [N][Q] base means
-  double* Xs = nullptr;       // [N][Q] base variances (raw or actual)
-  double* dir = nullptr;      // [2][N][Q] search direction
-  double* mu = nullptr;       // [Np][Q] trial means
-  double* S = nullptr;        // [Np][Q] trial variances (actual)
-  double* U = nullptr;        // [Np][Q] u = alpha / (alpha S + 1)
-  double* PU = nullptr;       // [Np][2*QP+2] packed [mu | u | ln c1] rows for psi1_kernel (QP = Q rounded up to 2, <= 16)
-  double* lnc1 = nullptr;     // [Np] ln(sf2) - 1/2 sum ln(a S + 1)
-  double* Xa = nullptr;       // [Np][CXp] per-point features for the n-contraction
-  double* Z = nullptr;        // [Mp][Q] (rows >= M zero)
-  double* alpha = nullptr;    // [Q]
-  double* Zaug = nullptr;     // [Mp][CZp]
-  double* Zt = nullptr;       // [Q][Mp] the inducing points transposed (kmm_grads_lds_kernel: lanes = inducing points)
-  int8_t* gsd = nullptr;      // gsi8.hip (M >= 1024): digit planes of the global step's two double-double-grade products on the int8 matrix core
-  size_t gsd_bytes = 0;
-  double* gss = nullptr;      // their column scales
-  size_t gss_count = 0;
-  double* stats = nullptr;    // packed: Psi2 [Mp*Mp] | C [Mp*Dp] | scalars [SC_COUNT]
-  bool stats_external = false;
-  double* spack = nullptr;    // Psi2 upper triangle | C [M][D] | scalars: the all-reduce payload across processes (allocated on first use)
-  double* grads = nullptr;    // packed: gZ_data [M*Q] | galpha_data [Q]
+  gp::DevBuf<double> Kaug;    // [Np][LDK]  Psi1 | Y
+  gp::DevBuf<double> Xmu;     // [N][Q] base means
+  gp::DevBuf<double> Xs;      // [N][Q] base variances (raw or actual)
+  gp::DevBuf<double> dir;     // [2][N][Q] search direction
+  gp::DevBuf<double> mu;      // [Np][Q] trial means
+  gp::DevBuf<double> S;       // [Np][Q] trial variances (actual)
+  gp::DevBuf<double> U;       // [Np][Q] u = alpha / (alpha S + 1)
+  gp::DevBuf<double> PU;      // [Np][2*QP+2] packed [mu | u | ln c1] rows for psi1_kernel (QP = Q rounded up to 2, <= 16)
+  gp::DevBuf<double> lnc1;    // [Np] ln(sf2) - 1/2 sum ln(a S + 1)
+  gp::DevBuf<double> Xa;      // [Np][CXp] per-point features for the n-contraction
+  gp::DevBuf<double> Z;       // [Mp][Q] (rows >= M zero)
+  gp::DevBuf<double> alpha;   // [Q]
+  gp::DevBuf<double> Zaug;    // [Mp][CZp]
+  gp::DevBuf<double> Zt;      // [Q][Mp] the inducing points transposed (kmm_grads_lds_kernel: lanes = inducing points)
+  gp::DevBuf<int8_t> gsd;     // gsi8.hip (M >= 1024): digit planes of the global step's two double-double-grade products on the int8 matrix core
+  gp::DevBuf<double> gss;     // their column scales
+  gp::DevBuf<double> stats;   // packed: Psi2 [Mp*Mp] | C [Mp*Dp] | scalars [SC_COUNT]
+  gp::DevBuf<double> spack;   // Psi2 upper triangle | C [M][D] | scalars: the all-reduce payload across processes (allocated on first use)
+  gp::DevBuf<double> grads;   // packed: gZ_data [M*Q] | galpha_data [Q]
   bool spack_filled = false;  // gp_stats_pack has run since the last gp_phase1 (gp_stats_unpack refuses to run before it)
-  bool grads_external = false;
-  double* staging = nullptr;  // landing buffer for a peer copy from a shard on another device (gp_buffer_combine)
-  size_t staging_doubles = 0;
-  double* part = nullptr;     // phase-1 split-k partials
-  size_t part_doubles = 0;
-  int* tiles = nullptr;       // phase-1 tile table (int2)
+  gp::DevBuf<double> staging; // landing buffer for a peer copy from a shard on another device (gp_buffer_combine)
+  gp::DevBuf<double> part;    // phase-1 split-k partials
+  gp::DevBuf<int> tiles;      // phase-1 tile table (int2)
   int n_tiles = 0, p1_slices = 0, p1_cps = 0;
-  void* p1plan = nullptr;     // regime-A phase-1 plan (job and output tables of p1v2.hip), built on first use
-  void* i8plan = nullptr;     // int8 phase 1 (p1i8.hip): digit buffers, job tables; built on first use
+  std::unique_ptr<gp::P1Plan, gp::P1PlanDelete> p1plan;   // regime-A phase-1 plan (job and output tables of p1v2.hip), built on first use
+  std::unique_ptr<gp::I8Plan, gp::I8PlanDelete> i8plan;   // int8 phase 1 (p1i8.hip): digit buffers, job tables; built on first use
   bool i8_active = false;     // this evaluation's phase 1 runs on the int8 matrix core (psi1_kernel wrote the digits)
   bool i8_y_valid = false;    // Y's digits are current (reset by gp_upload_shard)
   bool i8_unsupported = false;  // the int8 plan could not be built for this context (falls back to the float64 kernels)
@@ -114,29 +115,29 @@ struct gp_ctx {
   bool i8_check_pending = false;   // this evaluation ran both phase-1 paths: gp_finish reads the comparison and decides
   long i8_since_check = 0, i8_checks = 0;
   double i8_rel_psi2 = 0, i8_rel_c = 0, i8_cond_lb = 0;
-  double* i8_cmp = nullptr;        // device: [4] squared Frobenius norms (dPsi2, Psi2, dC, C) | [2] max diag(Psi2), max diag(P) | partials
-  int* bmap = nullptr;        // phase-1 block -> (slice, tile type) placement table
+  gp::DevBuf<double> i8_cmp;       // device: [4] squared Frobenius norms (dPsi2, Psi2, dC, C) | [2] max diag(Psi2), max diag(P) | partials
+  gp::DevBuf<int> bmap;       // phase-1 block -> (slice, tile type) placement table
   int bmap_T = -1, bmap_S = -1, bmap_blocks = 0;
-  double* klpart = nullptr;   // [blocks] partial KL sums
+  gp::DevBuf<double> klpart;  // [blocks] partial KL sums
   int kl_blocks = 0;
   double sumYY = 0;           // host copy, computed at upload
   // global step
-  double* Kmm = nullptr;      // batch of 2: [Kmm ; A] -> factorised in place into [Lk ; La]
-  double* Lmat = nullptr;     // [2][Mp][Mp] Cholesky factors
-  double* Linv = nullptr;     // [2][Mp][Mp] inverse factors
-  double* Inv = nullptr;      // [2][Mp][Mp] Ki, P
-  double* KmmKeep = nullptr;  // [Mp][Mp] Kmm (kept for downloads / derivative parts)
-  double* T1 = nullptr;       // [Mp][Mp] scratch
-  double* T2 = nullptr;       // [Mp][Mp] scratch
-  double* dFdK = nullptr;     // [Mp][Mp]
-  double* Bbar = nullptr;     // [Mp][Mp]
-  double* Bbar4 = nullptr;    // free embeddings, Q <= 16: Bbar with four ROWS interleaved, element (m, m') at ((m / 4) Mp + m') 4 + m % 4 (csrc/psi2.hip)
-  double* E = nullptr;        // [Mp][Dp]
-  double* PsiE = nullptr;     // [Mp][Dp]
-  double* Abar = nullptr;     // [Mp][Dp]
-  double* Bm = nullptr;       // [LDK][Mp] = [2 Bbar ; Abar^T]
-  double* gs = nullptr;       // [GS_COUNT] device scalars
-  double* gK = nullptr;       // [M*Q + Q] Kmm-parts of grad_Z / grad_alpha (+ regime-B alpha term)
+  gp::DevBuf<double> Kmm;     // batch of 2: [Kmm ; A] -> factorised in place into [Lk ; La]
+  gp::DevBuf<double> Lmat;    // [2][Mp][Mp] Cholesky factors
+  gp::DevBuf<double> Linv;    // [2][Mp][Mp] inverse factors
+  gp::DevBuf<double> Inv;     // [2][Mp][Mp] Ki, P
+  gp::DevBuf<double> KmmKeep; // [Mp][Mp] Kmm (kept for downloads / derivative parts)
+  gp::DevBuf<double> T1;      // [Mp][Mp] scratch
+  gp::DevBuf<double> T2;      // [Mp][Mp] scratch
+  gp::DevBuf<double> dFdK;    // [Mp][Mp]
+  gp::DevBuf<double> Bbar;    // [Mp][Mp]
+  gp::DevBuf<double> Bbar4;   // free embeddings, Q <= 16: Bbar with four ROWS interleaved, element (m, m') at ((m / 4) Mp + m') 4 + m % 4 (csrc/psi2.hip)
+  gp::DevBuf<double> E;       // [Mp][Dp]
+  gp::DevBuf<double> PsiE;    // [Mp][Dp]
+  gp::DevBuf<double> Abar;    // [Mp][Dp]
+  gp::DevBuf<double> Bm;      // [LDK][Mp] = [2 Bbar ; Abar^T]
+  gp::DevBuf<double> gs;      // [GS_COUNT] device scalars
+  gp::DevBuf<double> gK;      // [M*Q + Q] Kmm-parts of grad_Z / grad_alpha (+ regime-B alpha term)
   double h_gs[gp::GS_COUNT] = {0};
   bool gs_pending = false;    // a global step was enqueued and its scalars / failure flags have not been read back yet
   int gs_status = 0;          // outcome of the last global step once read back (GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE, GP_RETRY_JITTER)
@@ -144,85 +145,84 @@ struct gp_ctx {
   int jitter_mask = 0;        // bit 0: Kmm, bit 1: Kmm + beta*Psi2 get 1e-7 * I in this global step (partial_terms.py:452-456)
   int retry_mask = 0;         // what a GP_RETRY_JITTER asks the caller to pass to gp_global_step_jitter
   // phase 2
-  double* Rpart = nullptr;    // [p2_slices][Mp][CXp]
+  gp::DevBuf<double> Rpart;   // [p2_slices][Mp][CXp]
   int p2_slices = 0;
-  double* HZp = nullptr;      // [Mp/128][Np][CZp] per-point partials (one array per 128 inducing columns)
-  double* gXmu = nullptr;     // [N][Q]
-  double* gXs = nullptr;      // [N][Q]
-  double* gapart = nullptr;   // [blocks][Q] per-block alpha partial sums from the per-point kernel
+  gp::DevBuf<double> HZp;     // [Mp/128][Np][CZp] per-point partials (one array per 128 inducing columns)
+  gp::DevBuf<double> gXmu;    // [N][Q]
+  gp::DevBuf<double> gXs;     // [N][Q]
+  gp::DevBuf<double> gapart;  // [blocks][Q] per-block alpha partial sums from the per-point kernel
   int ga_blocks = 0;
-  unsigned long long* p2prog = nullptr;   // p2_fast8_kernel: [slices][MT] tile progress of the workgroups of a slice (kept in step for the L2), bases grow per launch
+  gp::DevBuf<unsigned long long> p2prog;  // p2_fast8_kernel: [slices][MT] tile progress of the workgroups of a slice (kept in step for the L2), bases grow per launch
   unsigned long long p2_epoch = 0;
-  double* hgpart = nullptr;   // partial sums of the fast path's mu^2 term of grad_alpha (per wave, or per 256 points from p2_ga_kernel)
+  gp::DevBuf<double> hgpart;  // partial sums of the fast path's mu^2 term of grad_alpha (per wave, or per 256 points from p2_ga_kernel)
   // regime B (variances > 0): pairwise psi2 kernels; allocated on first use
   bool b_alloc = false;
-  double* LE = nullptr;       // [Np][Mp]  1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2   (n-major)
-  double* LET = nullptr;      // [Np][Mp]  LEA = LE + sum_q V_nq z_mq^2 (n-major)
-  double* Vn = nullptr;       // [Np][Q]   -1/4 (alpha_q - w_nq)
-  double* Wn = nullptr;       // [Np][Q]   w_nq = alpha_q / (2 alpha_q S_nq + 1)
-  double* V2P = nullptr;      // [Np][QB]  -2 V_nq, zero-padded to the kernels' compile-time width QB
-  double* WP = nullptr;       // [Np][QB]  w_nq, zero-padded
-  double* MUP = nullptr;      // [Np][QB]  mu_nq, zero-padded
-  double* alphaP = nullptr;   // [QB]      alpha, zero-padded
-  double* Z1P = nullptr;      // [Mp][QB]  Z with a column of ones at index Q (only meaningful when QB > Q)
+  gp::DevBuf<double> LE;      // [Np][Mp]  1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2   (n-major)
+  gp::DevBuf<double> LET;     // [Np][Mp]  LEA = LE + sum_q V_nq z_mq^2 (n-major)
+  gp::DevBuf<double> Vn;      // [Np][Q]   -1/4 (alpha_q - w_nq)
+  gp::DevBuf<double> Wn;      // [Np][Q]   w_nq = alpha_q / (2 alpha_q S_nq + 1)
+  gp::DevBuf<double> V2P;     // [Np][QB]  -2 V_nq, zero-padded to the kernels' compile-time width QB
+  gp::DevBuf<double> WP;      // [Np][QB]  w_nq, zero-padded
+  gp::DevBuf<double> MUP;     // [Np][QB]  mu_nq, zero-padded
+  gp::DevBuf<double> alphaP;  // [QB]      alpha, zero-padded
+  gp::DevBuf<double> Z1P;     // [Mp][QB]  Z with a column of ones at index Q (only meaningful when QB > Q)
   bool b_mfma = false;        // regime-B phase 1 on the matrix core (psi2_pairs_mfma_kernel: latent tables 32 / 52 / 64 wide with a spare column)
   bool b_sym = false;         // regime-B phase 2 on tile pairs (psi2_sym_kernel: Q <= 10, 64 < M <= 1024)
-  double* Z1S = nullptr;      // [Mp][RT]  [Z | 1 at index QB | 0], RT = QB + 1 rounded up to 4: B operand of the row-side MFMAs
-  int* sym_sched = nullptr;   // [rounds][waves] tile of every wave in every round (I | J << 16, -1 idle)
+  gp::DevBuf<double> Z1S;     // [Mp][RT]  [Z | 1 at index QB | 0], RT = QB + 1 rounded up to 4: B operand of the row-side MFMAs
+  gp::DevBuf<int> sym_sched;  // [rounds][waves] tile of every wave in every round (I | J << 16, -1 idle)
   int sym_nw = 0, sym_rounds = 0;
-  double* ZP = nullptr;       // [Mp][QB]  Z zero-padded (rows >= M and columns >= Q are zero)
+  gp::DevBuf<double> ZP;      // [Mp][QB]  Z zero-padded (rows >= M and columns >= Q are zero)
   int QB = 0;                 // 4, 10, 16, 32 or 64: smallest instantiated width >= Q
-  double* lnc2h = nullptr;    // [Np]      1/2 ln c2_n
-  double* DZ2 = nullptr;      // [M][M][Q] (z_mq - z_m'q)^2
-  double* Gpart = nullptr;    // [pb_blocks][M][Q] per-block grad_Z partials of the psi2 part
-  double* Gtmp = nullptr;     // [64][M][Q] second-level grad_Z partials
-  double* gapart2 = nullptr;  // [pb_blocks][Q]
-  double* pp = nullptr;       // [Np][3Q+1] per-point running sums sr, zr, z2r, zt of the psi2 rows kernel
-  size_t pp_doubles = 0;
+  gp::DevBuf<double> lnc2h;   // [Np]      1/2 ln c2_n
+  gp::DevBuf<double> DZ2;     // [M][M][Q] (z_mq - z_m'q)^2
+  gp::DevBuf<double> Gpart;   // [pb_blocks][M][Q] per-block grad_Z partials of the psi2 part
+  gp::DevBuf<double> Gtmp;    // [64][M][Q] second-level grad_Z partials
+  gp::DevBuf<double> gapart2; // [pb_blocks][Q]
+  gp::DevBuf<double> pp;      // [Np][3Q+1] per-point running sums sr, zr, z2r, zt of the psi2 rows kernel
   int pb_blocks = 0;
   int nslab = 0, ppb = 0;     // regime-B phase-2 pair kernel: 64-column slabs of M, points per workgroup
-  int* ptiles = nullptr;      // upper-triangular 16x16 tile table for the psi2 pair kernel
+  gp::DevBuf<int> ptiles;     // upper-triangular 16x16 tile table for the psi2 pair kernel
   int n_ptiles = 0;
-  int* tiles64 = nullptr;     // upper-triangular 64x64 tile table for the MFMA pair kernel (wide latent spaces) and the tile-pair phase 2
+  gp::DevBuf<int> tiles64;    // upper-triangular 64x64 tile table for the MFMA pair kernel (wide latent spaces) and the tile-pair phase 2
   int n_tiles64 = 0;
   // regime-B phase 2 on tile pairs (psi2_tile.hip, Q <= 51)
   bool b_tile = false;        // regime-B phase 2 runs on psi2_tile_kernel
-  double* ppt = nullptr;      // [tiles][3Q+1][b_ch] per-point sums of every tile for the points of one launch
-  double* Gt = nullptr;       // [b_S][tiles][2][64][Q] grad_Z partials per workgroup
+  gp::DevBuf<double> ppt;     // [tiles][3Q+1][b_ch] per-point sums of every tile for the points of one launch
+  gp::DevBuf<double> Gt;      // [b_S][tiles][2][64][Q] grad_Z partials per workgroup
   long b_ch = 0;              // points per launch
   int b_S = 0;                // point slices per launch
   // regime B beyond the compiled latent widths (psi2_generic.hip, Q >= 64): psi2_n of a chunk of points and its row contractions
-  double* gen_T = nullptr;    // [gen_P][M][M]
-  double* gen_rt = nullptr;   // [gen_P][M][Q + 1]
+  gp::DevBuf<double> gen_T;   // [gen_P][M][M]
+  gp::DevBuf<double> gen_rt;  // [gen_P][M][Q + 1]
   long gen_P = 0;             // points per chunk
   // gp_predict (predict.hip): allocated on first use, pr_rows points per chunk
   bool pred_ok = false;       // the global step's Inv / Linv / E describe the statistics buffer as it is now (cleared whenever it or Z changes)
   long pr_rows = 0;
-  double* pr_in = nullptr;    // [2][pr_rows][Q] X_mu | X_S of the chunk as given
-  double* pr_mu = nullptr;    // [pr_rows][Q]
-  double* pr_U = nullptr;     // [pr_rows][Q] alpha / (alpha S + 1)
-  double* pr_lnc1 = nullptr;  // [pr_rows]
-  double* pr_P1 = nullptr;    // [pr_rows][Mp] Psi1 of the chunk
-  double* pr_G = nullptr;     // [pr_rows][Dp + 2 Mp] [mean | Lk^-1 k* | La^-1 k*]
-  double* pr_out = nullptr;   // [2][pr_rows][D] mean | var
-  double* pr_W = nullptr;     // [pr_rows][Q] w = alpha / (2 alpha S + 1)          (uncertain inputs)
-  double* pr_V2 = nullptr;    // [pr_rows][Q] (alpha - w) / 2
-  double* pr_lnc2 = nullptr;  // [pr_rows]    1/2 ln c2
-  double* pr_LEA = nullptr;   // [pr_rows][Mp]
-  double* pr_B = nullptr;     // [Mp][Mp] Ki - P
+  gp::DevBuf<double> pr_in;   // [2][pr_rows][Q] X_mu | X_S of the chunk as given
+  gp::DevBuf<double> pr_mu;   // [pr_rows][Q]
+  gp::DevBuf<double> pr_U;    // [pr_rows][Q] alpha / (alpha S + 1)
+  gp::DevBuf<double> pr_lnc1; // [pr_rows]
+  gp::DevBuf<double> pr_P1;   // [pr_rows][Mp] Psi1 of the chunk
+  gp::DevBuf<double> pr_G;    // [pr_rows][Dp + 2 Mp] [mean | Lk^-1 k* | La^-1 k*]
+  gp::DevBuf<double> pr_out;  // [2][pr_rows][D] mean | var
+  gp::DevBuf<double> pr_W;    // [pr_rows][Q] w = alpha / (2 alpha S + 1)          (uncertain inputs)
+  gp::DevBuf<double> pr_V2;   // [pr_rows][Q] (alpha - w) / 2
+  gp::DevBuf<double> pr_lnc2; // [pr_rows]    1/2 ln c2
+  gp::DevBuf<double> pr_LEA;  // [pr_rows][Mp]
+  gp::DevBuf<double> pr_B;    // [Mp][Mp] Ki - P
   // CG vectors (resident): grad_latest/new/old (2,N,Q) each
-  double* g_latest = nullptr;
-  double* g_new = nullptr;
-  double* g_old = nullptr;
+  gp::DevBuf<double> g_latest;
+  gp::DevBuf<double> g_new;
+  gp::DevBuf<double> g_old;
   // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   void* comm = nullptr;
   int comm_ranks = 0, comm_rank = -1;
   // gp_set_globals: pinned host staging (two slots, [M*Q + Q] doubles each) so that the upload of Z and alpha is a true asynchronous copy --
   // an evaluation then has ONE host synchronisation, the read-back in gp_finish; the slot's event guards its reuse two calls later
-  double* h_glob[2] = {nullptr, nullptr};
+  gp::PinnedBuf<double> h_glob[2];
   hipEvent_t glob_ev[2] = {nullptr, nullptr};
   int glob_slot = 0;
-  double* h_out = nullptr;    // gp_finish: pinned, mapped [GS_COUNT + 8 | M*Q + Q] -- finish_kernel writes the evaluation's results straight into it
+  gp::PinnedBuf<double> h_out;  // gp_finish: pinned, mapped [GS_COUNT + 8 | M*Q + Q] -- finish_kernel writes the evaluation's results straight into it
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
   // evaluation's first and last event (total_ms), 0 = none.  Every recorded event is a signal packet the stream waits on: ~4-7 us of idle
   // stream each, thirteen per evaluation -- 0.3 % of an evaluation at configs[2]'s size, 15 % at configs[1]'s (gp_set_timing)
@@ -235,16 +235,6 @@ struct gp_ctx {
 
 namespace gp {
 extern thread_local std::string g_create_error;
-int fail(gp_ctx* ctx, int code, const char* fmt, ...);
-// Test mode (GPARML_POISON=1 at load time or gp_debug_set_option("poison_alloc", 1)): every device allocation that does not carry a documented
-// zero-initialisation contract is filled with 0xFF bytes (a NaN as a double, -1 as an int) instead of zeros, and gp_set_globals refills the
-// per-evaluation scratch and output buffers with it: a kernel that reads a region this evaluation did not write, or that relies on zeros nobody
-// promised, then fails deterministically (NaN in the outputs) instead of once in a thousand runs.  DA_ZERO marks the buffers whose zeros ARE part of the
-// design (padding nobody writes; each such call site says which region that is), DA_INIT the ones that were zeroed for tidiness only, DA_RAW the
-// ones that are not initialised at all outside the test mode (every element is written before it is read).
-extern std::atomic<int> g_opt_poison;
-enum { DA_ZERO = 0, DA_INIT = 1, DA_RAW = 2 };
-int dalloc_bytes(gp_ctx* c, void** p, size_t bytes, int mode);
 
 // psi.hip
 int run_upload_y(gp_ctx* c, const double* dY);
@@ -260,11 +250,9 @@ int run_phase1_i8(gp_ctx* c);
 int p1i8_check_begin(gp_ctx* c);      // after run_phase1_i8: keep the int8 statistics aside (the caller then runs the float64 phase 1)
 int p1i8_check_compare(gp_ctx* c);    // after the float64 phase 1: norms of the difference (device)
 int p1i8_check_finish(gp_ctx* c);     // gp_finish, after the stream synchronisation of a checked evaluation: decide
-void p1i8_free(gp_ctx* c);
 // p1v2.hip (regime A phase 1 without wasted tile slots)
 bool p1v2_applicable(const gp_ctx* c);
 int run_phase1_v2(gp_ctx* c);
-void p1v2_free(gp_ctx* c);
 // psi2.hip (regime B)
 int ensure_regime_b_buffers(gp_ctx* c);
 int run_generate_b(gp_ctx* c);
@@ -283,9 +271,8 @@ int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double*
 // predict.hip
 extern std::atomic<int> g_opt_pred_rows;
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
-void pred_free(gp_ctx* c);
 // compat.hip
-int compat_build(gp_ctx* c, int which, double** out, long* count);
+int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip
 void comm_free(gp_ctx* c);
 // linalg.hip

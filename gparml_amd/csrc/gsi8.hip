@@ -161,7 +161,7 @@ int run_gs_i8_product(gp_ctx* c, hipStream_t st, const double* A, long lda, int 
                       const double* Csub) {
   const int wcols = nA + nB;
   const long plane = (long)(K / 16) * wcols * 16;
-  if ((size_t)GS_S * plane > c->gsd_bytes || (size_t)wcols > c->gss_count) return fail(c, GP_ERR_STATE, "int8 global-step product: workspace too small");
+  if ((size_t)GS_S * plane > c->gsd.size() || (size_t)wcols > c->gss.size()) return fail(c, GP_ERR_STATE, "int8 global-step product: workspace too small");
   GsMat m0{A, lda, nA, 0}, m1{B, ldb, nB, nA};
   hipLaunchKernelGGL(gsi8_colscale_kernel, dim3((std::max(nA, nB) + 15) / 16, 2), dim3(256), 0, st, m0, m1, K, c->gss);
   hipLaunchKernelGGL(gsi8_digits_kernel, dim3((std::max(nA, nB) + 255) / 256, K / 16, 2), dim3(256), 0, st, m0, m1, (const double*)c->gss, c->gsd, plane, wcols);

@@ -776,7 +776,7 @@ int run_global_step(gp_ctx* c) {
   // factorise [Kmm ; A] in place, invert.  T1 is the 2 x 128 x Mp work panel.
   // split-k workspace: the phase-1 partial buffer is free during the global step (>= 600 tiles)
   double* ws = c->part;
-  const size_t wcap = c->part_doubles;
+  const size_t wcap = c->part.size();
   int rc = potrf_inverse_batched(c, st, Mp, 2, c->Kmm, c->Linv, c->Inv, c->T1, c->gs + GS_LOGDET_K, failf, ws, wcap);
   if (rc != GP_OK) return rc;
   double* Ki = c->Inv;
@@ -882,7 +882,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "gs_i8")) { g_opt_gs_i8.store(value ? 1 : 0); return GP_OK; }
   if (!std::strcmp(name, "poison_alloc")) { g_opt_poison.store(value ? 1 : 0); return GP_OK; }
   if (!std::strcmp(name, "predict_rows")) { g_opt_pred_rows.store(std::max(0, value)); return GP_OK; }
-  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (dd_kipsi2, refine_E, p1_i8, gs_tail, i8_guard_strict, xtx_tri, residual_dd, gemm_big, trtri_rec, gs_i8, poison_alloc, predict_rows)", name);
+  if (!std::strcmp(name, "alloc_fail_after")) { g_alloc_fail_after.store(std::max(0, value)); return GP_OK; }
+  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (dd_kipsi2, refine_E, p1_i8, gs_tail, i8_guard_strict, xtx_tri, residual_dd, gemm_big, trtri_rec, gs_i8, poison_alloc, predict_rows, alloc_fail_after)", name);
 }
 
 extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet) {
@@ -895,9 +896,9 @@ extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double
   const long mm = (long)Mp * Mp;
   std::vector<double> h(mm, 0.0);
   for (int i = 0; i < Mp; ++i) for (int k = 0; k < Mp; ++k) h[(long)i * Mp + k] = (i < n && k < n) ? A[(long)i * n + k] : (i == k ? 1.0 : 0.0);
-  double *dA, *dLi, *dInv, *dT, *dS;
-  GP_HIP(c, hipMalloc((void**)&dA, mm * 8)); GP_HIP(c, hipMalloc((void**)&dLi, mm * 8)); GP_HIP(c, hipMalloc((void**)&dInv, mm * 8));
-  GP_HIP(c, hipMalloc((void**)&dT, mm * 8)); GP_HIP(c, hipMalloc((void**)&dS, 64));
+  DevBuf<double> dA, dLi, dInv, dT, dS;     // (allocated without the context: a failure is reported by gp_last_error(NULL))
+  GP_TRY_RC(dA.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dLi.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dInv.alloc(nullptr, mm, DA_RAW));
+  GP_TRY_RC(dT.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dS.alloc(nullptr, 8, DA_RAW));
   GP_HIP(c, hipMemcpy(dA, h.data(), mm * 8, hipMemcpyHostToDevice));
   GP_HIP(c, hipMemset(dS, 0, 64));
   GP_HIP(c, hipMemset(dLi, 0, mm * 8));
@@ -913,7 +914,6 @@ extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double
   } else {
     gp::g_create_error = c->err;
   }
-  (void)hipFree(dA); (void)hipFree(dLi); (void)hipFree(dInv); (void)hipFree(dT); (void)hipFree(dS);
   return rc;
 }
 

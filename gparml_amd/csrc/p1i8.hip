@@ -273,14 +273,15 @@ __global__ void __launch_bounds__(256) i8_slice_y_kernel(const double* __restric
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 struct I8Plan {
-  int8_t* Sl = nullptr; long strideJ = 0;
-  double* yscale = nullptr; double* pmax = nullptr;
-  double* dpart = nullptr; int row_blocks = 0;     // [row_blocks][Mp] sums of squares of Psi1's columns per psi1_kernel workgroup (the exact diagonal of Psi2)
-  double* diag = nullptr;                          // [Mp] their sums (p1i8_diag_kernel)
-  I8Job* jobs = nullptr; I8Out* outs = nullptr;
+  DevBuf<int8_t> Sl; long strideJ = 0;
+  DevBuf<double> yscale, pmax;
+  DevBuf<double> dpart; int row_blocks = 0;        // [row_blocks][Mp] sums of squares of Psi1's columns per psi1_kernel workgroup (the exact diagonal of Psi2)
+  DevBuf<double> diag;                             // [Mp] their sums (p1i8_diag_kernel)
+  DevBuf<I8Job> jobs; DevBuf<I8Out> outs;
   int blocks = 0, nouts = 0;
   bool y_valid = false;
 };
+void I8PlanDelete::operator()(I8Plan* p) const { delete p; }
 
 // Psi1's digits come from psi1_kernel's four-waves-across-the-columns form (Mp >= 512, Q <= 16) with fixed embeddings
 bool p1i8_applicable_static(const gp_ctx* c) {
@@ -293,21 +294,19 @@ bool p1i8_applicable(const gp_ctx* c) {
 }
 
 int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_blocks) {
-  I8Plan* pl = static_cast<I8Plan*>(c->i8plan);
   if (c->i8_unsupported) return GP_ERR_UNSUPPORTED;
-  if (!pl) {
-    // published only when complete: a failure below frees what was allocated and switches the path off for this context
-    struct Guard { gp_ctx* c; I8Plan* p; ~Guard() { if (p) { c->i8plan = p; p1i8_free(c); c->i8_unsupported = true; } } };
-    pl = new I8Plan();
-    Guard guard{c, pl};
+  if (!c->i8plan) {
+    // built aside and published only when complete: a failure below frees what was allocated and switches the path off for this context
+    std::unique_ptr<I8Plan, I8PlanDelete> pl(new I8Plan());
+    c->i8_unsupported = true;
     const int MT = c->Mp / TILE, DT = c->Dp / TILE;
     pl->strideJ = (c->Np / 16) * (long)c->LDK * 16;
-    GP_TRY_RC(dalloc_bytes(c, (void**)&pl->Sl, (size_t)I8S * pl->strideJ, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&pl->yscale, (size_t)c->Dp * sizeof(double), DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&pl->pmax, (size_t)1024 * c->Dp * sizeof(double), DA_RAW));
+    GP_TRY_RC(pl->Sl.alloc(c, (size_t)I8S * pl->strideJ, DA_RAW));
+    GP_TRY_RC(pl->yscale.alloc(c, (size_t)c->Dp, DA_RAW));
+    GP_TRY_RC(pl->pmax.alloc(c, (size_t)1024 * c->Dp, DA_RAW));
     pl->row_blocks = row_blocks;
-    GP_TRY_RC(dalloc_bytes(c, (void**)&pl->dpart, (size_t)row_blocks * c->Mp * sizeof(double), DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&pl->diag, (size_t)c->Mp * sizeof(double), DA_RAW));
+    GP_TRY_RC(pl->dpart.alloc(c, (size_t)row_blocks * c->Mp, DA_RAW));
+    GP_TRY_RC(pl->diag.alloc(c, (size_t)c->Mp, DA_RAW));
     // tiles of one n-slice: Psi2 upper tiles, then the C tiles; slices per XCD chosen for whole rounds of the XCD's 32 CUs (one workgroup
     // per CU: 320 accumulator registers), every tile of a slice on ONE XCD so that the slice's digits are fetched from HBM once
     std::vector<int> tiles;                                 // (row block, column block) of 128 combined columns [Psi1 | Y]
@@ -322,7 +321,7 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
       const double cost = std::ceil((double)t * T / (double)SLOTS) / t;
       if (cost < best - 1e-9) { best = cost; s8 = t; }
     }
-    const int Smax = (int)(c->part_doubles / ((size_t)T * TILE * TILE));          // the partial buffer holds S x T tiles
+    const int Smax = (int)(c->part.size() / ((size_t)T * TILE * TILE));          // the partial buffer holds S x T tiles
     int S = (int)std::min<long>(std::min<long>(8L * s8, ksteps), Smax);
     if (S < 1 || (c->Np + S - 1) / S + 32 > 87000) return fail(c, GP_ERR_UNSUPPORTED, "int8 phase 1: partial buffer too small for %d tiles", T);
     // placement: block b runs on XCD b % 8, one workgroup per CU, 32 CUs per XCD.  Whole slices first (every tile of a slice on one XCD: the
@@ -357,16 +356,15 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
     for (int x = 0; x < 8; ++x) for (size_t j = 0; j < per_xcd[x].size(); ++j) jobs[j * 8 + x] = per_xcd[x][j];   // block b runs on XCD b % 8
     std::vector<I8Out> outs;
     for (int t = 0; t < T; ++t) outs.push_back(I8Out{tiles[2 * t], tiles[2 * t + 1], t, S, T, tiles[2 * t + 1] >= MT ? 1 : 0, 0, 0});
-    GP_HIP(c, hipMalloc((void**)&pl->jobs, jobs.size() * sizeof(I8Job)));
-    GP_HIP(c, hipMalloc((void**)&pl->outs, outs.size() * sizeof(I8Out)));
-    GP_HIP(c, hipMemcpyAsync(pl->jobs, jobs.data(), jobs.size() * sizeof(I8Job), hipMemcpyHostToDevice, c->stream));
-    GP_HIP(c, hipMemcpyAsync(pl->outs, outs.data(), outs.size() * sizeof(I8Out), hipMemcpyHostToDevice, c->stream));
+    GP_TRY_RC(upload(c, pl->jobs, jobs));
+    GP_TRY_RC(upload(c, pl->outs, outs));
     GP_HIP(c, hipStreamSynchronize(c->stream));
     pl->blocks = (int)jobs.size(); pl->nouts = (int)outs.size();
     pl->y_valid = false;
-    guard.p = nullptr;
-    c->i8plan = pl;
+    c->i8plan = std::move(pl);
+    c->i8_unsupported = false;
   }
+  I8Plan* pl = c->i8plan.get();
   if (!c->i8_y_valid) pl->y_valid = false;
   if (!pl->y_valid) {
     const int nb = 1024;
@@ -384,7 +382,7 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
 }
 
 int run_phase1_i8(gp_ctx* c) {
-  I8Plan* pl = static_cast<I8Plan*>(c->i8plan);
+  const I8Plan* pl = c->i8plan.get();
   if (!pl || !pl->y_valid) return fail(c, GP_ERR_STATE, "int8 phase 1 without its digit buffers (psi1 did not write them)");
   I8Args a;
   a.Sl = pl->Sl; a.strideJ = pl->strideJ; a.LDK = c->LDK; a.jobs = pl->jobs; a.part = c->part;
@@ -449,7 +447,7 @@ __global__ void __launch_bounds__(256) i8_compare_final_kernel(double* __restric
 
 int p1i8_check_begin(gp_ctx* c) {
   const size_t n = (size_t)c->Mp * c->Mp + (size_t)c->Mp * c->Dp;
-  if (!c->i8_cmp) GP_TRY_RC(dalloc_bytes(c, (void**)&c->i8_cmp, (8 + 4 * I8_CMP_BLOCKS + n) * sizeof(double), DA_RAW));
+  if (!c->i8_cmp) GP_TRY_RC(c->i8_cmp.alloc(c, 8 + 4 * I8_CMP_BLOCKS + n, DA_RAW));
   // the int8 statistics aside (behind the comparison scalars): the float64 phase 1 overwrites the statistics buffer
   GP_HIP(c, hipMemcpyAsync(c->i8_cmp + 8 + 4 * I8_CMP_BLOCKS, c->stats, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return GP_OK;
@@ -480,15 +478,6 @@ int p1i8_check_finish(gp_ctx* c) {
   const double score = c->i8_cond_lb * std::max(c->i8_rel_psi2, c->i8_rel_c);
   c->i8_guard = (std::isfinite(score) && score <= (g_opt_i8_guard_strict.load() ? 0.0 : I8_GUARD_TAU)) ? 1 : 2;
   return GP_OK;
-}
-
-void p1i8_free(gp_ctx* c) {
-  if (c->i8_cmp) { (void)hipFree(c->i8_cmp); c->i8_cmp = nullptr; }
-  I8Plan* pl = static_cast<I8Plan*>(c->i8plan);
-  if (!pl) return;
-  for (void* p : {(void*)pl->Sl, (void*)pl->yscale, (void*)pl->pmax, (void*)pl->dpart, (void*)pl->diag, (void*)pl->jobs, (void*)pl->outs}) if (p) (void)hipFree(p);
-  delete pl;
-  c->i8plan = nullptr;
 }
 
 }  // namespace gp

@@ -253,8 +253,9 @@ __global__ void __launch_bounds__(256) p1v2_reduce_kernel(const double* __restri
 struct P1Plan {
   int Mp = -1, Dp = -1, D = -1; long Np = -1;
   int nby = 0, blocks = 0, nouts = 0;
-  P1Job* jobs = nullptr; P1Out* outs = nullptr;
+  DevBuf<P1Job> jobs; DevBuf<P1Out> outs;
 };
+void P1PlanDelete::operator()(P1Plan* p) const { delete p; }
 
 static bool pack_slices(int nF, int SF, int nG, int SG, std::vector<int>& xcd_of_F, std::vector<int>& xcd_of_G) {
   int fill[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -282,9 +283,8 @@ int run_phase1_v2(gp_ctx* c) {
   const int nF = MT * (MT - 1) / 2, nG = MT;
   const int wF = 256, wG = 144 + 8 * nby;   // MFMA blocks per k-step; a sweep of the effective G weight (330..440) is flat around the nominal value
   const int total_chunks = (int)(c->Np / KC);
-  P1Plan* pl = static_cast<P1Plan*>(c->p1plan);
-  if (!pl) { pl = new P1Plan(); c->p1plan = pl; }
-  if (pl->Mp != c->Mp || pl->Dp != c->Dp || pl->D != c->D || pl->Np != c->Np) {
+  const P1Plan* pl = c->p1plan.get();
+  if (!pl || pl->Mp != c->Mp || pl->Dp != c->Dp || pl->D != c->D || pl->Np != c->Np) {
     // slice counts: S_F w_F = S_G w_G (equal running time), as many workgroups as fit 8 XCDs x 64 resident slots with every
     // slice's jobs on one XCD
     int SF = 0, SG = 0;
@@ -308,7 +308,7 @@ int run_phase1_v2(gp_ctx* c) {
     for (int i = 0; i < MT; ++i) for (int j = i + 1; j < MT; ++j) { tF.push_back(i); tF.push_back(j); }
     const int baseF = next_part; next_part += SF * nF;
     const int baseG = next_part; next_part += SG * nG * 2;
-    if ((size_t)next_part * TILE * TILE > c->part_doubles) return fail(c, GP_ERR_UNSUPPORTED, "phase-1 partial buffer too small");
+    if ((size_t)next_part * TILE * TILE > c->part.size()) return fail(c, GP_ERR_UNSUPPORTED, "phase-1 partial buffer too small");
     for (int s = 0; s < SF; ++s) {
       const int c0 = (int)((long)s * total_chunks / SF), c1 = (int)((long)(s + 1) * total_chunks / SF);
       for (int t = 0; t < nF; ++t)
@@ -327,16 +327,15 @@ int run_phase1_v2(gp_ctx* c) {
       outs.push_back(P1Out{1, i, i, baseG + i * 2, SG, nG * 2, TILE, 0});
       outs.push_back(P1Out{2, i, 0, baseG + i * 2 + 1, SG, nG * 2, 4 * nby, 0});
     }
-    if (pl->jobs) (void)hipFree(pl->jobs);
-    if (pl->outs) (void)hipFree(pl->outs);
-    pl->jobs = nullptr; pl->outs = nullptr;
-    GP_HIP(c, hipMalloc((void**)&pl->jobs, jobs.size() * sizeof(P1Job)));
-    GP_HIP(c, hipMalloc((void**)&pl->outs, outs.size() * sizeof(P1Out)));
-    GP_HIP(c, hipMemcpyAsync(pl->jobs, jobs.data(), jobs.size() * sizeof(P1Job), hipMemcpyHostToDevice, c->stream));
-    GP_HIP(c, hipMemcpyAsync(pl->outs, outs.data(), outs.size() * sizeof(P1Out), hipMemcpyHostToDevice, c->stream));
+    // built aside and published only when complete
+    std::unique_ptr<P1Plan, P1PlanDelete> plan(new P1Plan());
+    GP_TRY_RC(upload(c, plan->jobs, jobs));
+    GP_TRY_RC(upload(c, plan->outs, outs));
     GP_HIP(c, hipStreamSynchronize(c->stream));
-    pl->Mp = c->Mp; pl->Dp = c->Dp; pl->D = c->D; pl->Np = c->Np; pl->nby = nby;
-    pl->blocks = (int)jobs.size(); pl->nouts = (int)outs.size();
+    plan->Mp = c->Mp; plan->Dp = c->Dp; plan->D = c->D; plan->Np = c->Np; plan->nby = nby;
+    plan->blocks = (int)jobs.size(); plan->nouts = (int)outs.size();
+    c->p1plan = std::move(plan);
+    pl = c->p1plan.get();
   }
   P1v2Args p;
   p.Kaug = c->Kaug; p.ld = c->LDK; p.jobs = pl->jobs; p.part = c->part;
@@ -351,15 +350,6 @@ int run_phase1_v2(gp_ctx* c) {
                      c->sumYY, c->sf2 * (double)c->N, (double)c->N, C + (long)c->Mp * c->Dp);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
-}
-
-void p1v2_free(gp_ctx* c) {
-  P1Plan* pl = static_cast<P1Plan*>(c->p1plan);
-  if (!pl) return;
-  if (pl->jobs) (void)hipFree(pl->jobs);
-  if (pl->outs) (void)hipFree(pl->outs);
-  delete pl;
-  c->p1plan = nullptr;
 }
 
 }  // namespace gp

@@ -242,34 +242,33 @@ static long pred_rows_for(const gp_ctx* c) {
 
 static int pred_alloc(gp_ctx* c, bool uncertain) {
   const long R = pred_rows_for(c), Mp = c->Mp, Q = c->Q, D = c->D;
+  // two groups, each all or nothing: the chunk buffers (pr_rows != 0 once they exist) and those of uncertain inputs (pr_B, their last, set)
+  // every element of these is written before it is read (DA_RAW: NaN-filled in the poison test mode)
   if (c->pr_rows != R) {
-    double* bufs[] = {c->pr_in, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, c->pr_G, c->pr_out, c->pr_W, c->pr_V2, c->pr_lnc2, c->pr_LEA, c->pr_B};
-    for (double* b : bufs) if (b) (void)hipFree(b);
-    c->pr_in = c->pr_mu = c->pr_U = c->pr_lnc1 = c->pr_P1 = c->pr_G = c->pr_out = c->pr_W = c->pr_V2 = c->pr_lnc2 = c->pr_LEA = c->pr_B = nullptr;
+    for (DevBuf<double>* b : {&c->pr_in, &c->pr_mu, &c->pr_U, &c->pr_lnc1, &c->pr_P1, &c->pr_G, &c->pr_out, &c->pr_W, &c->pr_V2, &c->pr_lnc2, &c->pr_LEA, &c->pr_B})
+      b->reset();
     c->pr_rows = 0;
-    // every element of these is written before it is read (DA_RAW: NaN-filled in the poison test mode)
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_in, (size_t)2 * R * Q * 8, DA_RAW));          // X_mu | X_S of the chunk, as given
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_mu, (size_t)R * Q * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_U, (size_t)R * Q * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_lnc1, (size_t)R * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_P1, (size_t)R * Mp * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_G, (size_t)R * (c->Dp + 2 * Mp) * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_out, (size_t)2 * R * D * 8, DA_RAW));        // mean | var
+    AllocGroup A(c);
+    A(c->pr_in, (size_t)2 * R * Q, DA_RAW);          // X_mu | X_S of the chunk, as given
+    A(c->pr_mu, (size_t)R * Q, DA_RAW);
+    A(c->pr_U, (size_t)R * Q, DA_RAW);
+    A(c->pr_lnc1, (size_t)R, DA_RAW);
+    A(c->pr_P1, (size_t)R * Mp, DA_RAW);
+    A(c->pr_G, (size_t)R * (c->Dp + 2 * Mp), DA_RAW);
+    A(c->pr_out, (size_t)2 * R * D, DA_RAW);        // mean | var
+    GP_TRY_RC(A.commit());
     c->pr_rows = R;
   }
-  if (uncertain && !c->pr_LEA) {
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_W, (size_t)R * Q * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_V2, (size_t)R * Q * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_lnc2, (size_t)R * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_LEA, (size_t)R * Mp * 8, DA_RAW));
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->pr_B, (size_t)Mp * Mp * 8, DA_RAW));
+  if (uncertain && !c->pr_B) {
+    AllocGroup A(c);
+    A(c->pr_W, (size_t)R * Q, DA_RAW);
+    A(c->pr_V2, (size_t)R * Q, DA_RAW);
+    A(c->pr_lnc2, (size_t)R, DA_RAW);
+    A(c->pr_LEA, (size_t)R * Mp, DA_RAW);
+    A(c->pr_B, (size_t)Mp * Mp, DA_RAW);
+    GP_TRY_RC(A.commit());
   }
   return GP_OK;
-}
-
-void pred_free(gp_ctx* c) {
-  double* bufs[] = {c->pr_in, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, c->pr_G, c->pr_out, c->pr_W, c->pr_V2, c->pr_lnc2, c->pr_LEA, c->pr_B};
-  for (double* b : bufs) if (b) (void)hipFree(b);
 }
 
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {

@@ -645,9 +645,7 @@ int run_phase1(gp_ctx* c) {
     std::vector<int> bm(8 * per_xcd * 2);
     for (int j = 0; j < per_xcd; ++j)
       for (int xx = 0; xx < 8; ++xx) { bm[(j * 8 + xx) * 2] = slot[(xx * per_xcd + j) * 2]; bm[(j * 8 + xx) * 2 + 1] = slot[(xx * per_xcd + j) * 2 + 1]; }
-    if (c->bmap) (void)hipFree(c->bmap);
-    GP_HIP(c, hipMalloc((void**)&c->bmap, bm.size() * sizeof(int)));
-    GP_HIP(c, hipMemcpyAsync(c->bmap, bm.data(), bm.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    GP_TRY_RC(upload(c, c->bmap, bm));
     GP_HIP(c, hipStreamSynchronize(c->stream));
     c->bmap_T = T; c->bmap_S = S; c->bmap_blocks = 8 * per_xcd;
   }
@@ -1389,7 +1387,7 @@ int run_phase2(gp_ctx* c) {
   static const bool p2_sync = [] { const char* e = getenv("GPARML_P2_SYNC"); return !(e && e[0] == '0'); }();
   // the in-step wait needs every workgroup of the launch resident at once: the grid is sized for two workgroups per CU on 256 CUs
   if (fast && p2_sync && p.MT > 1 && blocks <= 512) {
-    if (!c->p2prog) GP_TRY_RC(dalloc_bytes(c, (void**)&c->p2prog, (size_t)(c->p2_slices + 8) * p.MT * sizeof(unsigned long long), DA_ZERO));   // zero contract: bases only grow
+    if (!c->p2prog) GP_TRY_RC(c->p2prog.alloc(c, (size_t)(c->p2_slices + 8) * p.MT, DA_ZERO));   // zero contract: bases only grow
     p.prog = c->p2prog; p.prog_base = (unsigned long long)(++c->p2_epoch) << 32;
   }
   GP_EV(c, 12);

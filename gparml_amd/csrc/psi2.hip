@@ -719,45 +719,38 @@ __global__ void __launch_bounds__(256) pb2_reduce_kernel(const double* __restric
   }
 }
 
-template <typename T>
-static int balloc(gp_ctx* c, T** p, size_t count, int mode = DA_INIT) {
-  return dalloc_bytes(c, (void**)p, count * sizeof(T), mode);
-}
-
 int ensure_regime_b_buffers(gp_ctx* c) {
   if (c->b_alloc) return GP_OK;
   const long Np = c->Np, Mp = c->Mp, M = c->M, Q = c->Q;
-  int rc = GP_OK;
-  auto A = [&](auto** p, size_t n) { if (rc == GP_OK) rc = balloc(c, p, n); };
+  AllocGroup A(c);      // all or nothing: a failure anywhere below leaves none of the group's buffers set (and b_alloc false)
   // compiled latent widths; from 25 on the phase-2 kernel is the MFMA one and needs a spare column (QB > Q) for the ones.  r04: 6 and 8 next to 10 -- every
   // pair of every point pays 2 QB + 20 issue slots whatever Q is (N = 1e5, M = 512, same box: Q = 5, 6: 44.6 -> 39.0 ms per evaluation; Q = 7, 8: -4 %, the
   // tile-pair kernel's row tables are 12 wide at 8 as at 10); 12 and 14 next to 16 (the column kernel): Q = 12: 63.9 -> 57.1 ms, Q = 14: 65.8 -> 61.8 ms
   c->QB = Q <= 4 ? 4 : Q <= 6 ? 6 : Q <= 8 ? 8 : Q <= 10 ? 10 : Q <= 12 ? 12 : Q <= 14 ? 14 : Q <= 16 ? 16 : Q <= 24 ? 24 : Q <= 31 ? 32 : Q <= 51 ? 52 : 64;
   if (b_generic(c)) c->QB = (int)Q;       // psi2_generic.hip: the tables are exactly Q wide
   c->b_mfma = Q >= 25 && Q < c->QB;
-  A(&c->LE, (size_t)Np * Mp); A(&c->LET, (size_t)Np * Mp); A(&c->Vn, (size_t)Np * Q); A(&c->Wn, (size_t)Np * Q);
-  A(&c->ZP, (size_t)Mp * c->QB); A(&c->Z1P, (size_t)Mp * c->QB);
+  A(c->LE, (size_t)Np * Mp); A(c->LET, (size_t)Np * Mp); A(c->Vn, (size_t)Np * Q); A(c->Wn, (size_t)Np * Q);
+  A(c->ZP, (size_t)Mp * c->QB); A(c->Z1P, (size_t)Mp * c->QB);
   // zero contract: columns Q .. QB - 1 of the per-point tables and of alphaP are never written (b_tables_kernel fills q < Q) and every kernel runs its q loops to QB
-  auto A0 = [&](auto** p, size_t n) { if (rc == GP_OK) rc = balloc(c, p, n, DA_ZERO); };
-  A0(&c->V2P, (size_t)Np * c->QB); A0(&c->WP, (size_t)Np * c->QB); A0(&c->MUP, (size_t)Np * c->QB);
-  A0(&c->alphaP, (size_t)c->QB);
-  A(&c->lnc2h, (size_t)Np);
+  A(c->V2P, (size_t)Np * c->QB, DA_ZERO); A(c->WP, (size_t)Np * c->QB, DA_ZERO); A(c->MUP, (size_t)Np * c->QB, DA_ZERO);
+  A(c->alphaP, (size_t)c->QB, DA_ZERO);
+  A(c->lnc2h, (size_t)Np);
   // phase-2 pair kernel: grid (point chunks, groups of <= 4 64-column slabs); >= 16 points per workgroup, <= 4096 chunks
   c->nslab = (int)((M + 63) / 64);
   c->ppb = (int)std::max<long>(16, (c->N + 4095) / 4096);
   c->pb_blocks = (int)((c->N + c->ppb - 1) / c->ppb);
-  A(&c->Bbar4, (size_t)Mp * Mp);
-  A(&c->Gpart, (size_t)c->pb_blocks * M * Q); A(&c->gapart2, (size_t)c->pb_blocks * Q); A(&c->Gtmp, (size_t)64 * M * Q);
+  A(c->Bbar4, (size_t)Mp * Mp);
+  A(c->Gpart, (size_t)c->pb_blocks * M * Q); A(c->gapart2, (size_t)c->pb_blocks * Q); A(c->Gtmp, (size_t)64 * M * Q);
   std::vector<int> t;
   const int Mt = (int)((M + 15) / 16);
   for (int i = 0; i < Mt; ++i) for (int j = i; j < Mt; ++j) { t.push_back(i); t.push_back(j); }
   c->n_ptiles = (int)t.size() / 2;
-  A(&c->ptiles, t.size());
+  A(c->ptiles, t);
   std::vector<int> t64;
   const int Mt64 = (int)((M + 63) / 64);
   for (int i = 0; i < Mt64; ++i) for (int j = i; j < Mt64; ++j) { t64.push_back(i); t64.push_back(j); }
   c->n_tiles64 = (int)t64.size() / 2;
-  A(&c->tiles64, t64.size());
+  A(c->tiles64, t64);
   // tile-pair phase 2 (psi2_sym_kernel): Q <= 10, three to sixteen 64-column slabs (two slabs = a single wave per workgroup
   // running three tiles one after the other: slower than the column kernel, configs[1] 4.9 -> 5.2 ms).  Schedule = round-robin tournament over the
   // slabs (circle method; an odd count gets a bye) followed by the diagonal tiles, one tile per wave and round.
@@ -774,8 +767,7 @@ int ensure_regime_b_buffers(gp_ctx* c) {
   // the matrix-core tile-pair phase 2 (psi2_tile.hip) wherever psi2_sym_kernel does not apply; it keeps its own per-launch sums buffer
   c->b_tile = !b_generic(c) && pt2_applicable(c, c->b_sym);
   if (c->b_tile) c->b_sym = false;
-  c->pp_doubles = c->b_tile ? 1 : (size_t)Np * (3 * c->QB + 1) * (c->b_sym ? c->sym_nw : (c->nslab + 3) / 4);     // one group of sums per wave (sym) / per four slabs (cols)
-  A(&c->pp, c->pp_doubles);
+  A(c->pp, c->b_tile ? 1 : (size_t)Np * (3 * c->QB + 1) * (c->b_sym ? c->sym_nw : (c->nslab + 3) / 4));     // one group of sums per wave (sym) / per four slabs (cols)
   std::vector<int> sch;
   if (c->b_sym) {
     const int nv = (c->nslab + 1) / 2 * 2, nw = nv / 2;
@@ -788,22 +780,14 @@ int ensure_regime_b_buffers(gp_ctx* c) {
     for (int d = 0; d < c->nslab; d += nw)
       for (int k = 0; k < nw; ++k) sch.push_back(d + k < c->nslab ? ((d + k) | ((d + k) << 16)) : -1);
     c->sym_nw = nw; c->sym_rounds = (int)sch.size() / nw;
-    A(&c->Z1S, (size_t)Mp * ((c->QB + 1 + 3) / 4 * 4));
-    A(&c->sym_sched, sch.size());
+    A(c->Z1S, (size_t)Mp * ((c->QB + 1 + 3) / 4 * 4));
+    A(c->sym_sched, sch);
   }
-  if (rc != GP_OK) return rc;
-  if (c->b_sym) GP_HIP(c, hipMemcpyAsync(c->sym_sched, sch.data(), sch.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GP_HIP(c, hipMemcpyAsync(c->ptiles, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GP_HIP(c, hipMemcpyAsync(c->tiles64, t64.data(), t64.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GP_HIP(c, hipStreamSynchronize(c->stream));
+  GP_TRY_RC(A.status());
+  GP_HIP(c, hipStreamSynchronize(c->stream));     // the tables' uploads
   // the pair kernel's split-n partials live in c->part: make sure it is large enough
-  const size_t need = std::max((size_t)c->n_ptiles * 256 * 64, (size_t)c->n_tiles64 * 4096 * 32);
-  if (need > c->part_doubles) {
-    (void)hipFree(c->part);
-    c->part = nullptr;
-    GP_TRY_RC(dalloc_bytes(c, (void**)&c->part, need * 8, DA_RAW));
-    c->part_doubles = need;
-  }
+  GP_TRY_RC(c->part.grow(c, std::max((size_t)c->n_ptiles * 256 * 64, (size_t)c->n_tiles64 * 4096 * 32), DA_RAW));
+  GP_TRY_RC(A.commit());
   c->b_alloc = true;
   return GP_OK;
 }
@@ -811,7 +795,7 @@ int ensure_regime_b_buffers(gp_ctx* c) {
 // (z_mq - z_m'q)^2 for the compat path's per-point psi2 tensor only (the pair kernels use the padded Z tables)
 int run_dz2(gp_ctx* c) {
   const long total = (long)c->M * c->M * c->Q;
-  if (!c->DZ2) GP_TRY_RC(dalloc_bytes(c, (void**)&c->DZ2, (size_t)std::max<long>(total, 1) * sizeof(double), DA_RAW));
+  if (!c->DZ2) GP_TRY_RC(c->DZ2.alloc(c, total, DA_RAW));
   hipLaunchKernelGGL(dz2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, c->stream, c->Z, c->M, c->Q, c->DZ2);
   GP_HIP(c, hipGetLastError());
   return GP_OK;

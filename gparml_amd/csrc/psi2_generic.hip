@@ -129,11 +129,13 @@ bool b_generic(const gp_ctx* c) { return c->Q >= 64; }
 
 // the chunk buffers: T [P][M][M] (<= 64 MB, at least one point) and rt [P][M][Q + 1]
 static int ensure_generic(gp_ctx* c) {
-  if (c->gen_T) return GP_OK;
+  if (c->gen_rt) return GP_OK;      // the group's last buffer: both or neither
   const long mm = (long)c->M * c->M;
   c->gen_P = std::max<long>(1, std::min<long>(std::min<long>(c->N, 4096), (8L << 20) / std::max<long>(mm, 1)));
-  GP_TRY_RC(dalloc_bytes(c, (void**)&c->gen_T, (size_t)c->gen_P * mm * sizeof(double), DA_RAW));
-  GP_TRY_RC(dalloc_bytes(c, (void**)&c->gen_rt, (size_t)c->gen_P * c->M * (c->Q + 1) * sizeof(double), DA_RAW));
+  AllocGroup A(c);
+  A(c->gen_T, (size_t)c->gen_P * mm, DA_RAW);
+  A(c->gen_rt, (size_t)c->gen_P * c->M * (c->Q + 1), DA_RAW);
+  GP_TRY_RC(A.commit());
   return GP_OK;
 }
 
