@@ -17,6 +17,7 @@ ARR = dict(KMM=0, KMM_INV=1, PSI1=2, PSI2_SUM=3, PSI1TY=4, KMM_PLUS_OP_INV=5, DF
            DPSI1TY_DALPHA=17, DPSI2_DALPHA=18, X_MU_TRIAL=19, X_S_TRIAL=20, GRAD_LATEST=21)
 
 _dp = ctypes.POINTER(ctypes.c_double)
+_ip = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 
@@ -57,6 +58,8 @@ SIGNATURES = {
     'gp_download': (ctypes.c_int, [_vp, ctypes.c_int, _dp, _i64]),
     'gp_set_local_statistics': (ctypes.c_int, [_vp, ctypes.c_double, _dp, _dp, ctypes.c_double, ctypes.c_double]),
     'gp_predict': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
+    'gp_infer_objective': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    'gp_infer_latent': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     'gp_last_timings': (ctypes.c_int, [_vp, _dp]),
     'gp_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'gp_i8_status': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), _dp, _dp, _dp, ctypes.POINTER(_i64)]),

@@ -709,6 +709,57 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   return run_predict(c, (long)n, X_mu, X_S, xs_is_raw, flags, mean, var);
 }
 
+// gp_infer_objective / gp_infer_latent: gp_predict's preconditions, then the arguments of the new rows
+static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int raw,
+                       bool* nothing) {
+  *nothing = true;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
+  if (cols ? (n_cols < 1 || n_cols > c->D) : n_cols != 0)
+    return fail(c, GP_ERR_BAD_ARG, "%s: n_cols must be 1 .. D with a column list and 0 without one", who);
+  for (int j = 0; cols && j < n_cols; ++j)
+    if (cols[j] < 0 || cols[j] >= c->D || (j && cols[j] <= cols[j - 1]))
+      return fail(c, GP_ERR_BAD_ARG, "%s: cols must be strictly increasing in 0 .. D - 1", who);
+  if (c->state < 2 || !c->have_globals || !c->pred_ok)
+    return fail(c, GP_ERR_STATE, "%s needs a global step on the statistics and globals as they are now (none since the last phase 1, "
+                "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)", who);
+  GP_HIP(c, hipSetDevice(c->device));
+  GP_TRY(resolve_i8_check(c));
+  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "%s: the last global step did not succeed (%s)", who, c->gs_msg.c_str());
+  if (n == 0) return GP_OK;
+  if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, X_mu or X_S is NULL", who);
+  const size_t nq = (size_t)n * c->Q;
+  for (size_t i = 0; i < nq; ++i) {
+    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X_mu is not finite", who);
+    const double s = raw ? std::log(1.0 + std::exp(X_S[i])) : X_S[i];
+    if (!std::isfinite(X_S[i]) || !std::isfinite(s) || !(s > 0.0)) return fail(c, GP_ERR_BAD_ARG, "%s: X_S must be finite and > 0", who);
+  }
+  const int Do = cols ? n_cols : c->D;
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < Do; ++j)
+      if (!std::isfinite(Y[i * c->D + (cols ? cols[j] : j)])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed column", who);
+  *nothing = false;
+  return GP_OK;
+}
+
+extern "C" int gp_infer_objective(gp_ctx* c, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int xs_is_raw,
+                                  double* L, double* grad_mu, double* grad_S) {
+  if (!c) return GP_ERR_BAD_ARG;
+  bool nothing;
+  GP_TRY(infer_check(c, "gp_infer_objective", n, Y, cols, n_cols, X_mu, X_S, xs_is_raw, &nothing));
+  if (nothing || (!L && !grad_mu && !grad_S)) return GP_OK;
+  return run_infer(c, 0, (long)n, Y, cols, n_cols, const_cast<double*>(X_mu), const_cast<double*>(X_S), xs_is_raw ? 1 : 0, 0, 0.0, L, grad_mu, grad_S, nullptr);
+}
+
+extern "C" int gp_infer_latent(gp_ctx* c, int64_t n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
+                               double gtol, double* L, int32_t* iters) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (max_iters < 0 || !(gtol >= 0.0)) return fail(c, GP_ERR_BAD_ARG, "gp_infer_latent: max_iters and gtol must be >= 0");
+  bool nothing;
+  GP_TRY(infer_check(c, "gp_infer_latent", n, Y, cols, n_cols, X_mu, X_S, xs_is_raw, &nothing));
+  if (nothing) return GP_OK;
+  return run_infer(c, 1, (long)n, Y, cols, n_cols, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
+}
+
 // ---- final gradients ---------------------------------------------------------------------------------------------
 // final = Kmm parts (global step) + all-reduced data parts (phase 2)
 __global__ void add_kernel(const double* a, const double* b, double* out, long n) {

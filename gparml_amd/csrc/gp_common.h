@@ -210,6 +210,33 @@ struct gp_ctx {
   gp::DevBuf<double> pr_lnc2; // [pr_rows]    1/2 ln c2
   gp::DevBuf<double> pr_LEA;  // [pr_rows][Mp]
   gp::DevBuf<double> pr_B;    // [Mp][Mp] Ki - P
+  // gp_infer_objective / gp_infer_latent (infer.hip): allocated on first use, in_rows rows per chunk, in_dop padded observed columns
+  long in_rows = 0, in_dop = 0;
+  gp::DevBuf<int> in_cols;      // [D] observed output columns of the call
+  gp::DevBuf<double> in_ZP;     // [Mp][QP] Z zero-padded to the latent table width
+  gp::DevBuf<double> in_ZZ;     // [Mp][QP] Z o Z
+  gp::DevBuf<double> in_T;      // [Mp][Mp] beta^2 Eo Eo^T
+  gp::DevBuf<double> in_Gf;     // [Mp][Mp] G = W_O W_O^T - D_o (Ki - P), folded onto m' >= m
+  gp::DevBuf<double> in_Eo;     // [Mp][in_dop] observed columns of E
+  gp::DevBuf<double> in_Yc;     // [in_rows][D_o] observed columns of the chunk as uploaded
+  gp::DevBuf<double> in_Yo;     // [in_rows][in_dop] the same, zero-padded
+  gp::DevBuf<double> in_yy;     // [in_rows] |y_O|^2
+  gp::DevBuf<double> in_V;      // [in_rows][Mp] beta Yo Eo^T
+  gp::DevBuf<double> in_LEA;    // [in_rows][Mp]
+  gp::DevBuf<double> in_TB;     // [in_rows][5 QP] mu | S | u | w | v2 of the evaluation point
+  gp::DevBuf<double> in_LC;     // [in_rows][2] ln c1, 1/2 ln c2
+  gp::DevBuf<double> in_xe;     // [in_rows][2Q] evaluation point (mu | S or raw S)
+  gp::DevBuf<double> in_fe;     // [in_rows] L at the evaluation point
+  gp::DevBuf<double> in_ge;     // [in_rows][2Q] its gradient
+  gp::DevBuf<double> in_x;      // the optimiser's state (gp_infer_latent): current point, gradients, direction, S at x, scalars, results
+  gp::DevBuf<double> in_gn;
+  gp::DevBuf<double> in_go;
+  gp::DevBuf<double> in_d;
+  gp::DevBuf<double> in_Scur;
+  gp::DevBuf<double> in_sc;
+  gp::DevBuf<double> in_out;
+  gp::DevBuf<unsigned char> in_mask;   // [in_rows] rows of the next evaluation
+  gp::DevBuf<int> in_si;        // [in_rows][4] status, success flag, successes in a row, iterations | the active-row count
   // CG vectors (resident): grad_latest/new/old (2,N,Q) each
   gp::DevBuf<double> g_latest;
   gp::DevBuf<double> g_new;
@@ -271,6 +298,10 @@ int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double*
 // predict.hip
 extern std::atomic<int> g_opt_pred_rows;
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
+// infer.hip
+extern std::atomic<int> g_opt_inf_rows;
+int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
+              double* L, double* grad_mu, double* grad_S, int* iters);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip

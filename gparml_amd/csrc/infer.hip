@@ -1,0 +1,648 @@
+// Latent inference for new, partially observed rows (gp_infer_objective, gp_infer_latent), after a global step of this context.
+//
+// q(u) is frozen at Titsias' optimum of the trained model: W = beta E (M x D), B = Ki - P as in predict.hip.  For a row y with observed columns O
+// (|O| = D_o) and q(x) = N(mu, diag S) the bound is
+//   L(mu, S) = -D_o/2 ln(2 pi / beta) - beta/2 [ |y_O|^2 - 2 psi1^T v + sum(G o psi2) + D_o sf2 ] - 1/2 sum_q (mu_q^2 + S_q - ln S_q - 1)
+//   v = W_O y_O (M),   G = W_O W_O^T - D_o B (M x M, the same for every row of the call).
+// Every row is an independent 2Q-dimensional problem: nothing M^3 and nothing D-wide happens per evaluation.
+// Once per call:  Eo = the observed columns of E, zero-padded;  G = beta^2 Eo Eo^T - D_o B (one product on the MFMA GEMM core, inf_gfold_kernel);
+// per chunk:      V = beta Yo Eo^T (n x M, the GEMM core again) and |y_O|^2.
+// Per evaluation: inf_prep_kernel (per-row tables), inf_lea_kernel (LEA of psi2.hip's factorised form), inf_rows_kernel (the hot kernel).
+//
+// inf_rows_kernel: ONE WAVE PER ROW, lanes = inducing points m.  Everything that depends on the second index m' alone (z_m', z_m'^2, LEA[m']) is
+// wave-uniform and arrives through scalar loads; G is read coalesced along m.  psi2 is symmetric, so only m' >= m is generated: G is stored FOLDED,
+//   Gf[m'][m] = 2 G[m][m'] (m < m'),  G[m][m] (m = m'),  0 (m > m'),
+// built from min/max indices so that both halves of G enter with the same bits.  With T = Gf o psi2 (upper part) and, per lane m,
+//   r_m = sum_m' T,   tz_mq = sum_m' T z_m'q,   tzz_mq = sum_m' T z_m'q^2
+// the three sums the value and both gradients of the psi2 term need are
+//   sum T = sum_m r_m,   sum T (z_m + z_m')_q = sum_m (z_mq r_m + tz_mq),   sum T (z_m + z_m')_q^2 = sum_m (z_mq^2 r_m + 2 z_mq tz_mq + tzz_mq)
+// (zb = (z_m + z_m') / 2 of the gradient formulas is half of that sum).  Per generated pair: Q + 1 (exponent) + 17 (exp) + 2 (T, r) + 2 Q FMA-rate
+// instructions; M (M + 64) / 2 pairs per row.  The psi1 term and KL are O(M Q) and ride in the same kernel.  No [n][M][M] array, no LDS, no scratch.
+// Summation order is fixed (m' ascending per lane, 64-row blocks ascending, one xor butterfly per sum): a row's result does not depend on the other
+// rows of the call or on where a chunk boundary falls.  Latent tables are QP wide: 4, 10 or 16 (compile-time, row factors in registers), and a
+// multiple of 16 beyond (the plain path: the exponent reads its factors from memory and the pair loop is repeated per 16 latent dimensions).
+//
+// gp_infer_latent: Moller's scaled conjugate gradient (the algorithm of scg_adapted.py) per row over x = (mu, softplus-raw S), minimising -L; one state
+// record per row (lambda, kappa, theta, direction, success flag, ...), three small kernels per iteration and two masked evaluations (the probe for the
+// curvature, only after a success, and the trial point).  The host only enqueues; every INF_POLL iterations it reads one integer, the number of rows
+// still running.  Finished rows are skipped by the evaluation kernels at once.
+#include "gp_common.h"
+#include "fexp.h"
+#include <algorithm>
+#include <cmath>
+
+namespace gp {
+
+constexpr int INF_POLL = 8;      // iterations between two reads of the active-row count
+
+// test hook (gp_debug_set_option "infer_rows"): rows per chunk, rounded up to 128; 0 = the default below
+std::atomic<int> g_opt_inf_rows{0};
+
+static inline int inf_qp(int Q) { return Q <= 4 ? 4 : Q <= 10 ? 10 : (int)round_up(Q, 16); }
+
+static long inf_rows_for(const gp_ctx* c, long Dop) {
+  const int opt = g_opt_inf_rows.load();
+  if (opt > 0) return round_up(opt, TILE);
+  // V, LEA and Yo of a chunk stay near 64 MB
+  const long per_row = 8L * (2L * c->Mp + Dop);
+  return std::max<long>(TILE, std::min<long>(16384, (64L << 20) / per_row / TILE * TILE));
+}
+
+// ---- once per call ---------------------------------------------------------------------------------------------------------------------------
+// Eo[m][j] = E[m][cols[j]] for m < M, j < Do; zero elsewhere ([Mp][Dop])
+__global__ void __launch_bounds__(256) inf_gather_e_kernel(const double* __restrict__ E, const int* __restrict__ cols, int M, int Mp, int Dp, int Do, int Dop,
+                                                           double* __restrict__ Eo) {
+  const long total = (long)Mp * Dop;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long m = e / Dop;
+    const int j = (int)(e - m * Dop);
+    Eo[e] = (m < M && j < Do) ? E[m * Dp + cols[j]] : 0.0;
+  }
+}
+
+// Gf[k][m] from T = beta^2 Eo Eo^T and Inv = [Ki ; P]: element (a, b) = (min, max) of both, so G is symmetric bit for bit before it is folded
+__global__ void __launch_bounds__(256) inf_gfold_kernel(const double* __restrict__ T, const double* __restrict__ Inv, int M, int Mp, double Do,
+                                                        double* __restrict__ Gf) {
+  const long mm = (long)Mp * Mp;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < mm; e += (long)gridDim.x * 256L) {
+    const long k = e / Mp, m = e - k * Mp;
+    double g = 0.0;
+    if (k < M && m <= k) {
+      const long u = m * Mp + k;                       // row = the smaller index
+      g = T[u] - Do * (Inv[u] - Inv[mm + u]);
+      if (m < k) g *= 2.0;
+    }
+    Gf[e] = g;
+  }
+}
+
+// ZP = Z, ZZ = Z o Z, both [Mp][QP] zero-padded
+__global__ void __launch_bounds__(256) inf_ztab_kernel(const double* __restrict__ Z, int M, int Mp, int Q, int QP, double* __restrict__ ZP,
+                                                       double* __restrict__ ZZ) {
+  const long total = (long)Mp * QP;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long m = e / QP;
+    const int q = (int)(e - m * QP);
+    const double z = (m < M && q < Q) ? Z[m * Q + q] : 0.0;
+    ZP[e] = z;
+    ZZ[e] = z * z;
+  }
+}
+
+// ---- once per chunk --------------------------------------------------------------------------------------------------------------------------
+// Yo [rows][Dop] from the packed observed columns Yc [cnt][Do] (zero padding) and yy[n] = |y_O|^2; one thread per row
+__global__ void __launch_bounds__(256) inf_ypad_kernel(const double* __restrict__ Yc, long cnt, long rows, int Do, int Dop, double* __restrict__ Yo,
+                                                       double* __restrict__ yy) {
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < rows; n += (long)gridDim.x * 256L) {
+    double s = 0.0;
+    for (int j = 0; j < Dop; ++j) {
+      const double y = (n < cnt && j < Do) ? Yc[n * Do + j] : 0.0;
+      Yo[n * Dop + j] = y;
+      s = fma(y, y, s);
+    }
+    yy[n] = s;
+  }
+}
+
+// ---- per evaluation --------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double inf_softplus(double r) { return log(1.0 + exp(r)); }     // as the shard's prep (psi.hip) and pred_prep_kernel
+
+// Per-row tables of the evaluation point xe[n] = [mu (Q) | S or raw S (Q)], QP wide and zero-padded: TB[n] = [mu | S | u | w | v2] and
+// LC[n] = [ln c1, 1/2 ln c2]; u = alpha / (alpha S + 1), w = alpha / (2 alpha S + 1), v2 = (alpha - w) / 2.  One thread per row.
+__global__ void __launch_bounds__(256) inf_prep_kernel(const double* __restrict__ xe, int raw, const unsigned char* __restrict__ mask,
+                                                       const double* __restrict__ alpha, long cnt, int Q, int QP, double sf2, double* __restrict__ TB,
+                                                       double* __restrict__ LC) {
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < cnt; n += (long)gridDim.x * 256L) {
+    if (mask && !mask[n]) continue;
+    double l1 = log(sf2), l2 = l1;
+    double* t = TB + n * 5 * QP;
+    for (int q = 0; q < QP; ++q) {
+      double m = 0.0, s = 0.0, u = 0.0, w = 0.0, v2 = 0.0;
+      if (q < Q) {
+        const double a = alpha[q];
+        m = xe[n * 2 * Q + q];
+        s = xe[n * 2 * Q + Q + q];
+        if (raw) s = inf_softplus(s);
+        const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0;
+        u = a / d1;
+        w = a / d2;
+        v2 = 0.5 * (a - w);
+        l1 -= 0.5 * log(d1);
+        l2 -= 0.25 * log(d2);
+      }
+      t[q] = m; t[QP + q] = s; t[2 * QP + q] = u; t[3 * QP + q] = w; t[4 * QP + q] = v2;
+    }
+    LC[2 * n] = l1;
+    LC[2 * n + 1] = l2;
+  }
+}
+
+// LEA[n][m] = 1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2 - 1/2 sum_q v2_nq z_mq^2   (kPadLog for m >= M: exp gives exactly 0)
+__global__ void __launch_bounds__(256) inf_lea_kernel(const double* __restrict__ TB, const double* __restrict__ LC, const unsigned char* __restrict__ mask,
+                                                      const double* __restrict__ ZP, const double* __restrict__ ZZ, long cnt, int M, int Mp, int QP,
+                                                      double* __restrict__ LEA) {
+  const long total = cnt * Mp;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long n = e / Mp;
+    const int m = (int)(e - n * Mp);
+    if (mask && !mask[n]) continue;
+    double v = kPadLog;
+    if (m < M) {
+      const double* t = TB + n * 5 * QP;
+      double s = 0.0, r = 0.0;
+      for (int q = 0; q < QP; ++q) {
+        const double d = t[q] - ZP[(long)m * QP + q];
+        s = fma(t[3 * QP + q] * d, d, s);
+        r = fma(t[4 * QP + q], ZZ[(long)m * QP + q], r);
+      }
+      v = LC[2 * n + 1] - 0.5 * (s + r);
+    }
+    LEA[e] = v;
+  }
+}
+
+__device__ __forceinline__ double inf_wave_sum(double v) {
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
+  return v;
+}
+
+struct InfDims {
+  long cnt;
+  int M, Mp, Q, QP, raw;
+  double sf2, beta, Do;
+};
+
+// QR: the table width when it is 4, 10 or 16 (one pass, the row factors v2_q z_mq in registers); WIDE: QP a multiple of 16, one pass per 16 latent
+// dimensions with the exponent's factors read from the tables
+template <int QR, bool WIDE>
+// (the arrays are separate __restrict__ parameters: only then are the wave-uniform reads scalar loads)
+//   xe [cnt][2Q] evaluation points (for the softplus derivative), TB [cnt][5 QP], LC [cnt][2], LEA [cnt][Mp], V [rows][Mp] = beta Yo Eo^T, yy [rows],
+//   ZP, ZZ [Mp][QP], Gf [Mp][Mp] (element (m', m) at m' Mp + m), mask (NULL: every row); out: fe [cnt] = L, ge [cnt][2Q] = dL/dmu | dL/dS (or d/d raw), or NULL
+__global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict__ xe, const double* __restrict__ TB, const double* __restrict__ LC,
+                                                       const double* __restrict__ LEA, const double* __restrict__ V, const double* __restrict__ yy,
+                                                       const double* __restrict__ ZP, const double* __restrict__ ZZ, const double* __restrict__ Gf,
+                                                       const unsigned char* __restrict__ mask, double* __restrict__ fe, double* __restrict__ ge, InfDims a) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long n = blockIdx.x * 4L + wave;                 // wave-uniform
+  if (n >= a.cnt) return;
+  if (mask && !mask[n]) return;
+  const int M = a.M, Mp = a.Mp, Q = a.Q, QP = a.QP;
+  const double* tb = TB + n * 5 * QP;                  // wave-uniform: scalar loads
+  const double* lea = LEA + n * Mp;
+  const double* vrow = V + n * Mp;
+  const double lnc1 = LC[2 * n];
+  for (int qc = 0; qc < QP; qc += QR) {                  // one trip unless WIDE
+    // ---- psi1 term: p_m = psi1_m v_m; b0 = sum p, b1_q = sum p (mu_q - z_mq), b2_q = sum p (mu_q - z_mq)^2
+    double b0 = 0.0, b1[QR], b2[QR];
+#pragma unroll
+    for (int j = 0; j < QR; ++j) b1[j] = b2[j] = 0.0;
+    for (int r0 = 0; r0 < M; r0 += 64) {
+      const int m = r0 + lane;                           // < Mp
+      const double* zm = ZP + (long)m * QP;
+      double s = 0.0;
+      if constexpr (WIDE) {
+        for (int q = 0; q < QP; ++q) { const double d = tb[q] - zm[q]; s = fma(tb[2 * QP + q] * d, d, s); }
+      } else {
+#pragma unroll
+        for (int q = 0; q < QR; ++q) { const double d = tb[q] - zm[q]; s = fma(tb[2 * QP + q] * d, d, s); }
+      }
+      const double p = m < M ? fexp(lnc1 - 0.5 * s) * vrow[m] : 0.0;
+      b0 += p;
+#pragma unroll
+      for (int j = 0; j < QR; ++j) {
+        const double d = tb[qc + j] - zm[qc + j];
+        const double pd = p * d;
+        b1[j] += pd;
+        b2[j] = fma(pd, d, b2[j]);
+      }
+    }
+    // lane j keeps the sums of latent dimension qc + j (one register each instead of QR uniform ones)
+    b0 = inf_wave_sum(b0);
+    double B1 = 0.0, B2 = 0.0, A1 = 0.0, A2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < QR; ++j) {
+      const double v1 = inf_wave_sum(b1[j]), v2 = inf_wave_sum(b2[j]);
+      if (lane == j) { B1 = v1; B2 = v2; }
+    }
+    // ---- psi2 term, m' >= m only (the folded G)
+    double sT = 0.0, a1[QR], a2[QR];
+#pragma unroll
+    for (int j = 0; j < QR; ++j) a1[j] = a2[j] = 0.0;
+    for (int r0 = 0; r0 < M; r0 += 64) {
+      const int m = r0 + lane;
+      const double lm = lea[m];                          // kPadLog beyond M
+      const double* zm = ZP + (long)m * QP;
+      double f[QR], tz[QR];
+#pragma unroll
+      for (int j = 0; j < QR; ++j) { tz[j] = 0.0; if constexpr (!WIDE) f[j] = tb[4 * QP + j] * zm[j]; }
+      double r = 0.0;
+      const double* gcol = Gf + m;
+#pragma unroll 1
+      for (int k = r0; k < M; ++k) {                     // wave-uniform m'
+        const double* zk = ZP + (long)k * QP;
+        const double* zzk = ZZ + (long)k * QP;
+        double s = lm + lea[k];
+        if constexpr (WIDE) {
+          for (int q = 0; q < QP; ++q) s = fma(tb[4 * QP + q] * zm[q], zk[q], s);
+        } else {
+#pragma unroll
+          for (int q = 0; q < QR; ++q) s = fma(f[q], zk[q], s);
+        }
+        const double t = gcol[(long)k * Mp] * fexp(s);   // exactly 0 for m > m' and for padding rows
+        r += t;
+#pragma unroll
+        for (int j = 0; j < QR; ++j) {
+          tz[j] = fma(t, zk[qc + j], tz[j]);
+          a2[j] = fma(t, zzk[qc + j], a2[j]);
+        }
+      }
+      sT += r;
+#pragma unroll
+      for (int j = 0; j < QR; ++j) {
+        const double z = zm[qc + j];
+        a1[j] += fma(z, r, tz[j]);
+        a2[j] += z * fma(z, r, 2.0 * tz[j]);
+      }
+    }
+    sT = inf_wave_sum(sT);
+#pragma unroll
+    for (int j = 0; j < QR; ++j) {
+      const double v1 = inf_wave_sum(a1[j]), v2 = inf_wave_sum(a2[j]);
+      if (lane == j) { A1 = v1; A2 = v2; }
+    }
+    if (qc == 0) {
+      double kl = 0.0;
+      for (int q = 0; q < Q; ++q) { const double mq = tb[q], sq = tb[QP + q]; kl += mq * mq + sq - log(sq) - 1.0; }
+      const double L = -0.5 * a.Do * log(6.283185307179586477 / a.beta) - 0.5 * a.beta * (yy[n] - 2.0 * b0 + sT + a.Do * a.sf2) - 0.5 * kl;
+      if (lane == 0 && fe) fe[n] = L;
+    }
+    const int q = qc + lane;
+    if (ge && lane < QR && q < Q) {
+      const double mq = tb[q], sq = tb[QP + q], u = tb[2 * QP + q], w = tb[3 * QP + q];
+      const double d1mu = -u * B1, d1s = 0.5 * (u * u * B2 - u * b0);
+      const double d2mu = -2.0 * w * (mq * sT - 0.5 * A1);
+      const double d2s = 2.0 * w * w * (mq * mq * sT - mq * A1 + 0.25 * A2) - w * sT;
+      const double gmu = a.beta * d1mu - 0.5 * a.beta * d2mu - mq;
+      double gs = a.beta * d1s - 0.5 * a.beta * d2s - 0.5 * (1.0 - 1.0 / sq);
+      if (a.raw) gs *= 1.0 / (1.0 + exp(-xe[n * 2 * Q + Q + q]));
+      ge[n * 2 * Q + q] = gmu;
+      ge[n * 2 * Q + Q + q] = gs;
+    }
+  }
+}
+
+// ---- the optimiser's state: one record per row -------------------------------------------------------------------------------------------------
+enum { IS_F = 0, IS_LAM, IS_MU, IS_KAPPA, IS_SIGMA, IS_THETA, IS_ALPHA, IS_COUNT };      // doubles per row (sc)
+enum { II_STATUS = 0, II_SUCCESS, II_NSUCC, II_ITERS, II_COUNT };                        // ints per row (si); status 0 running, 1 gradient below gtol, 2 max_iters
+struct ScgArgs {
+  long cnt;
+  int Q, QP, raw_in, max_iters;
+  double gtol;
+  double* x;        // [cnt][2Q] current point (mu | raw S)
+  double* gn;       // gradient of -L at x
+  double* go;       // the one before
+  double* d;        // direction
+  double* xe;       // evaluation point
+  const double* ge; // the evaluation's gradient of L
+  const double* fe; // the evaluation's L
+  const double* TB; // the evaluation's tables (S in [QP, 2 QP))
+  double* Scur;     // [cnt][Q] S at x
+  double* sc;       // [cnt][IS_COUNT]
+  int* si;          // [cnt][II_COUNT]
+  unsigned char* mask;
+};
+
+__device__ __forceinline__ double inf_maxabs(const double* g, int n) {
+  double m = 0.0;
+  for (int i = 0; i < n; ++i) m = fmax(m, fabs(g[i]));
+  return m;
+}
+
+// after the evaluation at the start: x, f, gradient (chain rule to the raw variances when S was given plainly), direction, status
+__global__ void __launch_bounds__(256) inf_scg_init_kernel(ScgArgs a) {
+  const int Q = a.Q, n2 = 2 * Q;
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < a.cnt; n += (long)gridDim.x * 256L) {
+    double* x = a.x + n * n2; double* gn = a.gn + n * n2; double* go = a.go + n * n2; double* d = a.d + n * n2;
+    const double* xe = a.xe + n * n2; const double* ge = a.ge + n * n2;
+    bool finite = isfinite(a.fe[n]);
+    for (int q = 0; q < Q; ++q) {
+      const double s = a.TB[n * 5 * a.QP + a.QP + q];
+      a.Scur[n * Q + q] = s;
+      x[q] = xe[q];
+      x[Q + q] = a.raw_in ? xe[Q + q] : (s > 40.0 ? s : log(expm1(s)));     // softplus^-1
+      const double gm = -ge[q], gs = a.raw_in ? -ge[Q + q] : -ge[Q + q] * (1.0 - exp(-s));     // dS / d raw = 1 - exp(-S)
+      gn[q] = go[q] = gm; d[q] = -gm;
+      gn[Q + q] = go[Q + q] = gs; d[Q + q] = -gs;
+      finite = finite && isfinite(gm) && isfinite(gs) && isfinite(x[Q + q]);
+    }
+    double* sc = a.sc + n * IS_COUNT; int* si = a.si + n * II_COUNT;
+    sc[IS_F] = -a.fe[n]; sc[IS_LAM] = 1.0; sc[IS_MU] = sc[IS_KAPPA] = sc[IS_SIGMA] = sc[IS_THETA] = sc[IS_ALPHA] = 0.0;
+    si[II_SUCCESS] = 1; si[II_NSUCC] = 0; si[II_ITERS] = 0;
+    si[II_STATUS] = (finite && inf_maxabs(gn, n2) <= a.gtol) ? 1 : (a.max_iters <= 0 || !finite) ? 2 : 0;
+    a.mask[n] = 0;
+  }
+}
+
+// running rows whose last step succeeded: slope, length and the probe point x + sigma d for the curvature (scg_adapted.py: "if accepted")
+__global__ void __launch_bounds__(256) inf_scg_probe_kernel(ScgArgs a) {
+  const int n2 = 2 * a.Q;
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < a.cnt; n += (long)gridDim.x * 256L) {
+    const int* si = a.si + n * II_COUNT;
+    const bool go_on = si[II_STATUS] == 0 && si[II_SUCCESS];
+    a.mask[n] = go_on ? 1 : 0;
+    if (!go_on) continue;
+    double* d = a.d + n * n2; const double* gn = a.gn + n * n2; const double* x = a.x + n * n2; double* xe = a.xe + n * n2;
+    double mu = 0.0;
+    for (int i = 0; i < n2; ++i) mu = fma(d[i], gn[i], mu);
+    if (mu >= 0.0) {                                      // not a descent direction: restart along the gradient
+      mu = 0.0;
+      for (int i = 0; i < n2; ++i) { d[i] = -gn[i]; mu = fma(d[i], gn[i], mu); }
+    }
+    double kappa = 0.0;
+    for (int i = 0; i < n2; ++i) kappa = fma(d[i], d[i], kappa);
+    const double sigma = 1.0e-4 / sqrt(kappa);
+    for (int i = 0; i < n2; ++i) xe[i] = fma(sigma, d[i], x[i]);
+    double* sc = a.sc + n * IS_COUNT;
+    sc[IS_MU] = mu; sc[IS_KAPPA] = kappa; sc[IS_SIGMA] = sigma;
+  }
+}
+
+// running rows: curvature from the probe (after a success), the scale that makes the quadratic positive definite, the trial point x + alpha d
+__global__ void __launch_bounds__(256) inf_scg_trial_kernel(ScgArgs a) {
+  const int n2 = 2 * a.Q;
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < a.cnt; n += (long)gridDim.x * 256L) {
+    const int* si = a.si + n * II_COUNT;
+    const bool run = si[II_STATUS] == 0;
+    const bool probed = run && si[II_SUCCESS];
+    a.mask[n] = run ? 1 : 0;
+    if (!run) continue;
+    const double* d = a.d + n * n2; const double* gn = a.gn + n * n2; const double* x = a.x + n * n2; double* xe = a.xe + n * n2;
+    const double* ge = a.ge + n * n2;
+    double* sc = a.sc + n * IS_COUNT;
+    if (probed) {
+      double th = 0.0;
+      for (int i = 0; i < n2; ++i) th = fma(d[i], -ge[i] - gn[i], th);
+      sc[IS_THETA] = th / sc[IS_SIGMA];
+    }
+    const double theta = sc[IS_THETA], kappa = sc[IS_KAPPA];
+    double lam = sc[IS_LAM];
+    double delta = theta + lam * kappa;
+    if (!(delta > 0.0)) {
+      delta = lam * kappa;
+      lam = lam - theta / kappa;
+    }
+    const double alpha = -sc[IS_MU] / delta;
+    sc[IS_LAM] = lam; sc[IS_ALPHA] = alpha;
+    for (int i = 0; i < n2; ++i) xe[i] = fma(alpha, d[i], x[i]);
+  }
+}
+
+// running rows: compare the actual with the predicted decrease; only an improving step moves the row; scale, direction and status
+__global__ void __launch_bounds__(256) inf_scg_update_kernel(ScgArgs a) {
+  const int Q = a.Q, n2 = 2 * Q;
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < a.cnt; n += (long)gridDim.x * 256L) {
+    int* si = a.si + n * II_COUNT;
+    if (si[II_STATUS] != 0) continue;
+    double* x = a.x + n * n2; double* gn = a.gn + n * n2; double* go = a.go + n * n2; double* d = a.d + n * n2;
+    const double* xe = a.xe + n * n2; const double* ge = a.ge + n * n2;
+    double* sc = a.sc + n * IS_COUNT;
+    const double ft = -a.fe[n], fp = sc[IS_F], mu = sc[IS_MU], alpha = sc[IS_ALPHA];
+    bool finite = isfinite(ft);
+    for (int i = 0; i < n2; ++i) finite = finite && isfinite(ge[i]);
+    double Delta = 2.0 * (ft - fp) / (alpha * mu);
+    if (!finite || !isfinite(Delta)) Delta = -1.0;
+    const bool ok = Delta >= 0.0 && ft <= fp;
+    int nsucc = si[II_NSUCC];
+    if (ok) {
+      ++nsucc;
+      for (int i = 0; i < n2; ++i) { x[i] = xe[i]; go[i] = gn[i]; gn[i] = -ge[i]; }
+      for (int q = 0; q < Q; ++q) a.Scur[n * Q + q] = a.TB[n * 5 * a.QP + a.QP + q];
+      sc[IS_F] = ft;
+    }
+    const int it = ++si[II_ITERS];
+    if (ok && inf_maxabs(gn, n2) <= a.gtol) si[II_STATUS] = 1;
+    else if (it >= a.max_iters) si[II_STATUS] = 2;
+    double lam = sc[IS_LAM];
+    if (Delta < 0.25) lam = fmin(4.0 * lam, 1.0e100);
+    if (Delta > 0.75) lam = fmax(0.5 * lam, 1.0e-60);
+    sc[IS_LAM] = lam;
+    if (nsucc == n2) {
+      for (int i = 0; i < n2; ++i) d[i] = -gn[i];
+      nsucc = 0;
+    } else if (ok) {
+      double gg = 0.0, og = 0.0;
+      for (int i = 0; i < n2; ++i) { gg = fma(gn[i], gn[i], gg); og = fma(go[i], gn[i], og); }
+      const double Gamma = (og - gg) / mu;
+      for (int i = 0; i < n2; ++i) d[i] = Gamma * d[i] - gn[i];
+    }
+    si[II_NSUCC] = nsucc;
+    si[II_SUCCESS] = ok ? 1 : 0;
+  }
+}
+
+// one workgroup: *out = number of rows still running
+__global__ void __launch_bounds__(256) inf_count_kernel(const int* __restrict__ si, long cnt, int* __restrict__ out) {
+  __shared__ int part[256];
+  int c = 0;
+  for (long n = threadIdx.x; n < cnt; n += 256) c += si[n * II_COUNT + II_STATUS] == 0 ? 1 : 0;
+  part[threadIdx.x] = c;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = part[0];
+}
+
+// results of the chunk: out[n] = [mu (Q) | S or raw S (Q) | L | iterations]
+__global__ void __launch_bounds__(256) inf_scg_out_kernel(ScgArgs a, double* __restrict__ out) {
+  const int Q = a.Q, n2 = 2 * Q;
+  for (long n = blockIdx.x * 256L + threadIdx.x; n < a.cnt; n += (long)gridDim.x * 256L) {
+    double* o = out + n * (n2 + 2);
+    for (int q = 0; q < Q; ++q) {
+      o[q] = a.x[n * n2 + q];
+      o[Q + q] = a.raw_in ? a.x[n * n2 + Q + q] : a.Scur[n * Q + q];
+    }
+    o[n2] = -a.sc[n * IS_COUNT + IS_F];
+    o[n2 + 1] = (double)a.si[n * II_COUNT + II_ITERS];
+  }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------------------
+static int inf_alloc(gp_ctx* c, long R, long Dop, int QP, bool latent) {
+  const long Mp = c->Mp, Q = c->Q;
+  // three groups, each all or nothing: the model tables (in_Gf, their last, set), the chunk buffers (in_rows != 0 once they exist for this chunk size and
+  // column count) and the optimiser's state (in_si, its last, set).  Every element is written before it is read (DA_RAW: NaN-filled in the poison mode).
+  if (!c->in_Gf) {
+    AllocGroup A(c);
+    A(c->in_cols, (size_t)c->D, DA_RAW);
+    A(c->in_ZP, (size_t)Mp * QP, DA_RAW);
+    A(c->in_ZZ, (size_t)Mp * QP, DA_RAW);
+    A(c->in_T, (size_t)Mp * Mp, DA_RAW);
+    A(c->in_Gf, (size_t)Mp * Mp, DA_RAW);
+    GP_TRY_RC(A.commit());
+  }
+  if (c->in_rows != R || c->in_dop != Dop) {
+    for (DevBuf<double>* b : {&c->in_Eo, &c->in_Yc, &c->in_Yo, &c->in_yy, &c->in_V, &c->in_LEA, &c->in_TB, &c->in_LC, &c->in_xe, &c->in_fe, &c->in_ge, &c->in_x,
+                              &c->in_gn, &c->in_go, &c->in_d, &c->in_Scur, &c->in_sc, &c->in_out})
+      b->reset();
+    c->in_si.reset();
+    c->in_mask.reset();
+    c->in_rows = 0;
+    AllocGroup A(c);
+    A(c->in_Eo, (size_t)Mp * Dop, DA_RAW);
+    A(c->in_Yc, (size_t)R * Dop, DA_RAW);            // the observed columns of the chunk, packed [cnt][Do]
+    A(c->in_Yo, (size_t)R * Dop, DA_RAW);
+    A(c->in_yy, (size_t)R, DA_RAW);
+    A(c->in_V, (size_t)R * Mp, DA_RAW);
+    A(c->in_LEA, (size_t)R * Mp, DA_RAW);
+    A(c->in_TB, (size_t)R * 5 * QP, DA_RAW);
+    A(c->in_LC, (size_t)R * 2, DA_RAW);
+    A(c->in_xe, (size_t)R * 2 * Q, DA_RAW);
+    A(c->in_fe, (size_t)R, DA_RAW);
+    A(c->in_ge, (size_t)R * 2 * Q, DA_RAW);
+    GP_TRY_RC(A.commit());
+    c->in_rows = R;
+    c->in_dop = Dop;
+  }
+  if (latent && !c->in_si) {
+    AllocGroup A(c);
+    A(c->in_x, (size_t)R * 2 * Q, DA_RAW);
+    A(c->in_gn, (size_t)R * 2 * Q, DA_RAW);
+    A(c->in_go, (size_t)R * 2 * Q, DA_RAW);
+    A(c->in_d, (size_t)R * 2 * Q, DA_RAW);
+    A(c->in_Scur, (size_t)R * Q, DA_RAW);
+    A(c->in_sc, (size_t)R * IS_COUNT, DA_RAW);
+    A(c->in_out, (size_t)R * (2 * Q + 2), DA_RAW);
+    A(c->in_mask, (size_t)R, DA_RAW);
+    A(c->in_si, (size_t)R * II_COUNT + 1, DA_RAW);   // the last int: the active-row count
+    GP_TRY_RC(A.commit());
+  }
+  return GP_OK;
+}
+
+static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
+
+// one evaluation of the rows of the chunk that mask selects (NULL: all) at in_xe
+static int inf_evaluate(gp_ctx* c, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
+  hipStream_t st = c->stream;
+  const int M = c->M, Mp = c->Mp, Q = c->Q;
+  hipLaunchKernelGGL(inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, st, c->in_xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, c->in_TB, c->in_LC);
+  hipLaunchKernelGGL(inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, st, c->in_TB, c->in_LC, mask, c->in_ZP, c->in_ZZ, cnt, M, Mp, QP, c->in_LEA);
+  InfDims a;
+  a.cnt = cnt; a.M = M; a.Mp = Mp; a.Q = Q; a.QP = QP; a.raw = raw; a.sf2 = c->sf2; a.beta = c->beta; a.Do = Do;
+  double* ge = want_grad ? c->in_ge.get() : nullptr;
+  const dim3 grid((unsigned)((cnt + 3) / 4));
+#define INF_ROWS(QR, WIDE)                                                                                                                              \
+  hipLaunchKernelGGL((inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, st, c->in_xe.get(), c->in_TB.get(), c->in_LC.get(), c->in_LEA.get(), c->in_V.get(), \
+                     c->in_yy.get(), c->in_ZP.get(), c->in_ZZ.get(), c->in_Gf.get(), mask, c->in_fe.get(), ge, a)
+  if (QP == 4) INF_ROWS(4, false);
+  else if (QP == 10) INF_ROWS(10, false);
+  else if (QP == 16) INF_ROWS(16, false);
+  else INF_ROWS(16, true);
+#undef INF_ROWS
+  GP_HIP(c, hipGetLastError());
+  return GP_OK;
+}
+
+// mode 0: gp_infer_objective (L, grad_mu, grad_S out, any may be NULL); mode 1: gp_infer_latent (X_mu, X_S in/out, L, iters out)
+int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
+              double* L, double* grad_mu, double* grad_S, int* iters) {
+  const long Mp = c->Mp, M = c->M, Q = c->Q, D = c->D;
+  const int Do = cols ? n_cols : (int)D;
+  const long Dop = round_up(Do, TILE);
+  const int QP = inf_qp((int)Q);
+  const long R = inf_rows_for(c, Dop);
+  GP_TRY_RC(inf_alloc(c, R, Dop, QP, mode == 1));
+  hipStream_t st = c->stream;
+  // ---- once per call: the observed columns, G and the latent tables
+  std::vector<int> hc(Do);
+  for (int j = 0; j < Do; ++j) hc[j] = cols ? cols[j] : j;
+  GP_HIP(c, hipMemcpyAsync(c->in_cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->E, c->in_cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, c->in_Eo);
+  hipLaunchKernelGGL(inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, st, c->Z, (int)M, (int)Mp, (int)Q, QP, c->in_ZP, c->in_ZZ);
+  GP_HIP(c, hipGetLastError());
+  GemmP g;
+  g.K = (int)Dop; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
+  g.A = c->in_Eo; g.lda = Dop; g.B = c->in_Eo; g.ldb = Dop; g.C = c->in_T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
+  launch_gemm(st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g);
+  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, c->in_T, c->Inv, (int)M, (int)Mp, (double)Do, c->in_Gf);
+  GP_HIP(c, hipGetLastError());
+  // the observed columns of every row, packed on the host: the others are never read
+  std::vector<double> yc((size_t)n * Do);
+  for (long i = 0; i < n; ++i)
+    for (int j = 0; j < Do; ++j) yc[(size_t)i * Do + j] = Y[i * D + hc[j]];
+  std::vector<double> hx((size_t)std::min(n, R) * 2 * Q), hout;
+  std::vector<double> hg;
+  ScgArgs s;
+  s.Q = (int)Q; s.QP = QP; s.raw_in = raw; s.max_iters = max_iters; s.gtol = gtol;
+  s.x = c->in_x; s.gn = c->in_gn; s.go = c->in_go; s.d = c->in_d; s.xe = c->in_xe; s.ge = c->in_ge; s.fe = c->in_fe; s.TB = c->in_TB; s.Scur = c->in_Scur;
+  s.sc = c->in_sc; s.si = c->in_si; s.mask = c->in_mask;
+  for (long n0 = 0; n0 < n; n0 += R) {
+    const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
+    s.cnt = cnt;
+    for (long i = 0; i < cnt; ++i)
+      for (long q = 0; q < Q; ++q) {
+        hx[i * 2 * Q + q] = X_mu[(n0 + i) * Q + q];
+        hx[i * 2 * Q + Q + q] = X_S[(n0 + i) * Q + q];
+      }
+    GP_HIP(c, hipMemcpyAsync(c->in_xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(c->in_Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, st, c->in_Yc, cnt, rows, Do, (int)Dop, c->in_Yo, c->in_yy);
+    GP_HIP(c, hipGetLastError());
+    g.A = c->in_Yo; g.lda = Dop; g.B = c->in_Eo; g.ldb = Dop; g.C = c->in_V; g.ldc = Mp; g.alpha = c->beta; g.beta = 0.0;
+    launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, g);
+    GP_HIP(c, hipGetLastError());
+    if (mode == 0) {
+      GP_TRY_RC(inf_evaluate(c, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
+      if (L) GP_HIP(c, hipMemcpyAsync(L + n0, c->in_fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+      if (grad_mu || grad_S) {
+        hg.resize((size_t)cnt * 2 * Q);
+        GP_HIP(c, hipMemcpyAsync(hg.data(), c->in_ge, (size_t)cnt * 2 * Q * 8, hipMemcpyDeviceToHost, st));
+      }
+      GP_HIP(c, hipStreamSynchronize(st));
+      for (long i = 0; (grad_mu || grad_S) && i < cnt; ++i)
+        for (long q = 0; q < Q; ++q) {
+          if (grad_mu) grad_mu[(n0 + i) * Q + q] = hg[i * 2 * Q + q];
+          if (grad_S) grad_S[(n0 + i) * Q + q] = hg[i * 2 * Q + Q + q];
+        }
+      continue;
+    }
+    GP_TRY_RC(inf_evaluate(c, cnt, raw, nullptr, true, QP, (double)Do));
+    const dim3 rg(inf_blocks(cnt));
+    hipLaunchKernelGGL(inf_scg_init_kernel, rg, dim3(256), 0, st, s);
+    int* d_active = c->in_si.get() + R * II_COUNT;
+    for (int it = 0; it < max_iters; ++it) {
+      if (it % INF_POLL == 0) {
+        int active = 0;
+        hipLaunchKernelGGL(inf_count_kernel, dim3(1), dim3(256), 0, st, c->in_si, cnt, d_active);
+        GP_HIP(c, hipMemcpyAsync(&active, d_active, sizeof(int), hipMemcpyDeviceToHost, st));
+        GP_HIP(c, hipStreamSynchronize(st));
+        if (active == 0) break;
+      }
+      hipLaunchKernelGGL(inf_scg_probe_kernel, rg, dim3(256), 0, st, s);
+      GP_TRY_RC(inf_evaluate(c, cnt, 1, c->in_mask, true, QP, (double)Do));
+      hipLaunchKernelGGL(inf_scg_trial_kernel, rg, dim3(256), 0, st, s);
+      GP_TRY_RC(inf_evaluate(c, cnt, 1, c->in_mask, true, QP, (double)Do));
+      hipLaunchKernelGGL(inf_scg_update_kernel, rg, dim3(256), 0, st, s);
+    }
+    hipLaunchKernelGGL(inf_scg_out_kernel, rg, dim3(256), 0, st, s, c->in_out.get());
+    GP_HIP(c, hipGetLastError());
+    hout.resize((size_t)cnt * (2 * Q + 2));
+    GP_HIP(c, hipMemcpyAsync(hout.data(), c->in_out, hout.size() * 8, hipMemcpyDeviceToHost, st));
+    GP_HIP(c, hipStreamSynchronize(st));
+    for (long i = 0; i < cnt; ++i) {
+      const double* o = hout.data() + i * (2 * Q + 2);
+      for (long q = 0; q < Q; ++q) { X_mu[(n0 + i) * Q + q] = o[q]; X_S[(n0 + i) * Q + q] = o[Q + q]; }
+      if (L) L[n0 + i] = o[2 * Q];
+      if (iters) iters[n0 + i] = (int)o[2 * Q + 1];
+    }
+  }
+  GP_HIP(c, hipStreamSynchronize(st));
+  ++c->sync_epoch;
+  return GP_OK;
+}
+
+}  // namespace gp

@@ -271,6 +271,43 @@ class ShardEngine(object):
                                      var.ctypes.data_as(_lib._dp)), 'gp_predict')
         return mean, var
 
+    # ---- latent inference for new rows (gp_infer_objective, gp_infer_latent) ---------------------------------
+    def _infer_args(self, Y, X_mu, X_S, cols):
+        Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+        assert Y.ndim == 2 and Y.shape[1] == self.D, 'Y shape %s: (n, %d) expected' % (Y.shape, self.D)
+        n = Y.shape[0]
+        X_mu = np.array(np.atleast_2d(np.asarray(X_mu, dtype=np.float64)), order='C', copy=True)
+        X_S = np.array(np.atleast_2d(np.asarray(X_S, dtype=np.float64)), order='C', copy=True)
+        assert X_mu.shape == (n, self.Q) and X_S.shape == (n, self.Q), 'X_mu %s / X_S %s: (%d, %d) expected' % (X_mu.shape, X_S.shape, n, self.Q)
+        Y, py = _lib.as_c(Y)
+        pc, nc = None, 0
+        if cols is not None:
+            cols = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
+            assert cols.size >= 1, 'cols is empty (None means every column)'
+            pc, nc = cols.ctypes.data_as(_lib._ip), int(cols.size)
+        return n, (Y, py), X_mu, X_S, (cols, pc, nc)
+
+    def infer_objective(self, Y, X_mu, X_S, cols=None, xs_is_raw=False, want_grads=True):
+        """The bound L of every NEW row of Y (n, D) under q(x) = N(X_mu, diag X_S) with q(u) frozen at the trained optimum (after a successful
+        global step, as ``predict``), over the observed output columns ``cols`` (strictly increasing; None: all; the others may hold NaN).
+        Returns (L (n,), grad_mu (n, Q), grad_S (n, Q)); grad_S is with respect to the raw value with ``xs_is_raw``.  Rows are independent."""
+        n, (Y, py), X_mu, X_S, (cols, pc, nc) = self._infer_args(Y, X_mu, X_S, cols)
+        L, gm, gs = np.empty(n), np.empty((n, self.Q)), np.empty((n, self.Q))
+        dp = lambda a: a.ctypes.data_as(_lib._dp)
+        self._ck(self.lib.gp_infer_objective(self.h, n, py, pc, nc, dp(X_mu), dp(X_S), 1 if xs_is_raw else 0, dp(L), dp(gm) if want_grads else None,
+                                             dp(gs) if want_grads else None), 'gp_infer_objective')
+        return (L, gm, gs) if want_grads else (L, None, None)
+
+    def infer_latent(self, Y, X_mu, X_S, cols=None, xs_is_raw=False, max_iters=100, gtol=1e-5):
+        """Maximise that bound per row over (X_mu, softplus-raw X_S) from the given start with the device's per-row scaled conjugate gradients.
+        Returns (X_mu, X_S, L (n,), iters (n,) int32): X_S in the form it came in; a row with iters < max_iters stopped on max |gradient| <= gtol."""
+        n, (Y, py), X_mu, X_S, (cols, pc, nc) = self._infer_args(Y, X_mu, X_S, cols)
+        L, it = np.empty(n), np.zeros(n, dtype=np.int32)
+        dp = lambda a: a.ctypes.data_as(_lib._dp)
+        self._ck(self.lib.gp_infer_latent(self.h, n, py, pc, nc, dp(X_mu), dp(X_S), 1 if xs_is_raw else 0, int(max_iters), float(gtol), dp(L),
+                                          it.ctypes.data_as(_lib._ip)), 'gp_infer_latent')
+        return X_mu, X_S, L, it
+
     regime_A_hint = False
     _jitter_used = 0
     _jitter_hint = 0          # the jitter mask the previous evaluation ended up with (global_step)

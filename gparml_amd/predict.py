@@ -15,11 +15,14 @@ from .scg_adapted import SCG_adapted
 
 
 class Predictor(object):
-    def __init__(self, global_statistics, accumulated_statistics, N_train, D, device=0, partial_terms_class=None):
+    def __init__(self, global_statistics, accumulated_statistics, N_train, D, device=0, partial_terms_class=None, engine_class=None):
         """global_statistics: dict Z (M,Q), sf2, alpha, beta; accumulated_statistics: the five base sums of the trained model
         (the ``accumulated_statistics_*_f.npy`` files, predict.py:31-35).  ``partial_terms_class`` (tests only: a CPU class with the
-        reference's constructor) replaces the GPU class so that the host logic can be checked without a device."""
+        reference's constructor) replaces the GPU class so that the host logic can be checked without a device; ``engine_class`` (tests only: a
+        CPU class with ShardEngine's constructor and its set_globals / set_local_statistics / global_step / infer_latent / predict / close) does the
+        same for ``infer`` and ``impute``."""
         self._cls = partial_terms_class
+        self._engine_cls = engine_class
         self.gs = global_statistics
         self.acc = accumulated_statistics
         Z = numpy.asarray(global_statistics['Z'], dtype=float)
@@ -33,18 +36,93 @@ class Predictor(object):
         mean (n, D) and variance (n, D) of every output, against the stored accumulated statistics of the training data only (not the new
         rows' own statistics).  The columns a ``test(..., mask=...)`` call left out are the imputed ones.  ``include_noise`` adds 1/beta.
         X_S None predicts at the point X_mu (variance (n, 1))."""
-        from .engine import ShardEngine
+        eng = self._trained_engine()
+        try:
+            return eng.predict(X_mu, X_S, include_noise=include_noise)
+        finally:
+            eng.close()
+
+    def _trained_engine(self):
+        """An engine that holds the trained model: the globals, the stored accumulated statistics of the training data and a global step on them."""
+        cls = self._engine_cls
+        if cls is None:
+            from .engine import ShardEngine as cls
         g, a = self.gs, self.acc
         f = lambda x: float(numpy.asarray(x).reshape(-1)[0])
-        eng = ShardEngine(1, self.D, self.M, self.Q, device=self.device)
+        eng = cls(1, self.D, self.M, self.Q, device=self.device)
         try:
             eng.set_globals(numpy.asarray(g['Z'], dtype=float), f(g['sf2']), numpy.asarray(g['alpha'], dtype=float).reshape(-1), f(g['beta']),
                             N_global=max(self.N, 1))
             eng.set_local_statistics(f(a['sum_YYT']), a['sum_exp_K_mi_K_im'], a['sum_exp_K_miY'], f(a['sum_exp_K_ii']), f(a['sum_KL']))
             eng.global_step(sync=True)
-            return eng.predict(X_mu, X_S, include_noise=include_noise)
+        except Exception:
+            eng.close()
+            raise
+        return eng
+
+    def infer(self, Y_test, mask=None, X_mu0=None, X_S0=None, training=None, is_random_init=False, random_restarts=0, iterations=100, gtol=1e-5):
+        """q(x*) = N(X_mu, diag X_S) of every NEW row of ``Y_test`` (n, D) with q(u) frozen at the trained optimum: [X_mu (n, Q), X_S (n, Q), L (n,)],
+        L the row's own bound (ShardEngine.infer_latent: every row is an independent problem, optimised on the device).
+
+        Observed outputs of a row: the columns of ``mask`` (None: all) that are not NaN in it; only these enter the likelihood, so a row with
+        missing outputs is embedded from what it has.  Rows are grouped by that pattern, one device call per pattern.  Starting mean: ``X_mu0``
+        when given; else, as ``test``, the embedding of the nearest training output over the row's observed columns (``training`` = iterable of
+        (Y_shard, X_shard) pairs, kept in memory and searched once per pattern) or, with ``is_random_init``, a random inducing point for EVERY
+        row followed by ``random_restarts`` further random inducing points per row; restarts are laid out as rows of the same call (row i's
+        starts are rows i (R + 1) .. i (R + 1) + R) and the best L is kept per row (the earliest on ties).  Starting variance ``X_S0`` or
+        0.5 + 0.01 randn clipped to [0.001, 1] (predict.py:71-72), shared by a row's restarts."""
+        Y = numpy.atleast_2d(numpy.asarray(Y_test, dtype=float))
+        n, Q = Y.shape[0], self.Q
+        assert Y.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y.shape, self.D)
+        Z = numpy.asarray(self.gs['Z'], dtype=float)
+        cols = numpy.arange(self.D) if mask is None else numpy.unique(numpy.asarray(list(mask), dtype=int))
+        observed = ~numpy.isnan(Y[:, cols])
+        assert observed.any(axis=1).all(), 'a row of Y_test has no observed output among the columns of mask'
+        if X_mu0 is not None:
+            X_mu0 = numpy.atleast_2d(numpy.asarray(X_mu0, dtype=float))
+            assert X_mu0.shape == (n, Q), 'X_mu0 shape %s: (%d, %d) expected' % (X_mu0.shape, n, Q)
+            starts = X_mu0[:, None, :]
+        elif is_random_init:
+            starts = Z[numpy.random.randint(self.M, size=(n, int(random_restarts) + 1))]        # (n, R + 1, Q)
+        else:
+            if training is None:
+                raise AssertionError('Predictor.infer needs the training shards (training=...), an initial mean (X_mu0=...) or is_random_init')
+            training = list(training)
+            starts = None
+        if X_S0 is None:
+            X_S0 = numpy.clip(numpy.ones((n, Q)) * 0.5 + 0.01 * numpy.random.randn(n, Q), 0.001, 1)
+        X_S0 = numpy.atleast_2d(numpy.asarray(X_S0, dtype=float))
+        assert X_S0.shape == (n, Q), 'X_S0 shape %s: (%d, %d) expected' % (X_S0.shape, n, Q)
+        groups = {}
+        for i in range(n):
+            groups.setdefault(observed[i].tobytes(), []).append(i)
+        X_mu, X_S, L = numpy.empty((n, Q)), numpy.empty((n, Q)), numpy.empty(n)
+        eng = self._trained_engine()
+        try:
+            for key in sorted(groups, key=lambda k: groups[k][0]):
+                rows = numpy.asarray(groups[key])
+                c = cols[observed[rows[0]]]
+                if starts is None:
+                    s = self.nearest_training_embeddings(Y[rows], training, Q, c)[:, None, :]
+                else:
+                    s = starts[rows]
+                k = s.shape[1]
+                m, v, l, _ = eng.infer_latent(numpy.repeat(Y[rows], k, axis=0), s.reshape(-1, Q), numpy.repeat(X_S0[rows], k, axis=0),
+                                              cols=None if c.size == self.D else c, max_iters=iterations, gtol=gtol)
+                l = numpy.asarray(l).reshape(len(rows), k)
+                best = numpy.argmax(l, axis=1)                                          # the earliest of equal maxima
+                pick = numpy.arange(len(rows)) * k + best
+                X_mu[rows], X_S[rows], L[rows] = numpy.asarray(m)[pick], numpy.asarray(v)[pick], l[numpy.arange(len(rows)), best]
         finally:
             eng.close()
+        return [X_mu, X_S, L]
+
+    def impute(self, Y_test, mask, include_noise=False, **infer_args):
+        """Reconstruct the outputs of new rows from the observed columns ``mask``: ``infer`` (its keyword arguments pass through), then
+        ``predict_outputs`` at the inferred q(x*).  Returns (mean (n, D), var (n, D), [X_mu, X_S, L]); the columns outside ``mask`` are the imputed ones."""
+        res = self.infer(Y_test, mask=mask, **infer_args)
+        mean, var = self.predict_outputs(res[0], res[1], include_noise=include_noise)
+        return mean, var, res
 
     def _partial_terms(self):
         if self._pt is None:

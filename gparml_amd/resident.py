@@ -92,11 +92,22 @@ class ResidentModel(object):
     _stats_x = None
     _stats_version = -1
 
+    def infer(self, flat_array, Y, X_mu, X_S, cols=None, max_iters=100, gtol=1e-5):
+        """Latent distributions of NEW rows Y for the model at ``flat_array`` (ShardEngine.infer_latent on the root engine: per-row SCG on the device
+        from the start (X_mu, X_S) over the observed columns ``cols``).  Returns (X_mu, X_S, L, iters).  The statistics are brought up to date as in
+        ``predict``, with the same collective rule."""
+        self._refresh_statistics(flat_array)
+        return self.engines[0].infer_latent(Y, X_mu, X_S, cols=cols, max_iters=max_iters, gtol=gtol)
+
     def predict(self, flat_array, X_mu, X_S=None, include_noise=False):
         """Posterior predictive mean and variance at new inputs for the model at the optimiser's parameter vector ``flat_array`` (ShardEngine.predict:
         var is (n, 1) for X_S None, (n, D) otherwise).  When ``flat_array`` is not, bit for bit, the vector of the last evaluation (SCG's last
         evaluation is a trial point, not the x it returns) or the resident embeddings moved since (an accepted step's update_X), the statistics
         part is run first at that point with the resident embeddings as they are (phase 1, the reduce, the global step).  That run is COLLECTIVE across ranks: every rank of a multi-GPU job must call predict with the same vector."""
+        self._refresh_statistics(flat_array)
+        return self.engines[0].predict(X_mu, X_S, include_noise=include_noise)
+
+    def _refresh_statistics(self, flat_array):
         flat_array = np.asarray(flat_array, dtype=np.float64)
         last = self._stats_x
         if (last is None or last.shape != flat_array.shape or last.tobytes() != flat_array.tobytes()
@@ -115,7 +126,6 @@ class ResidentModel(object):
             root.global_step(sync=True)
             self._stats_x = np.array(flat_array, copy=True)
             self._stats_version = self.version
-        return self.engines[0].predict(X_mu, X_S, include_noise=include_noise)
 
     def close(self):
         for e in self.engines:

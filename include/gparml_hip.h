@@ -174,6 +174,27 @@ int gp_finish(gp_ctx* ctx, double* F, double* grad_Z, double* grad_sf2, double* 
  * GP_ERR_BAD_ARG for n < 0 or a non-finite mean / negative or non-finite variance; n = 0 writes nothing. */
 int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, int flags, double* mean, double* var);
 
+/* ---- latent inference for new rows ---------------------------------------------------------------- */
+/* The bound of n NEW rows y (n,D) under q(x) = N(X_mu, diag X_S), with q(u) frozen at the optimum of the trained model (the statistics of the last
+ * global step): per row, with O the observed columns (D_o of them), W and B as for gp_predict, v = W_O y_O and G = W_O W_O^T - D_o B,
+ *   L = -D_o/2 ln(2 pi / beta) - beta/2 [ |y_O|^2 - 2 psi1^T v + sum(G o psi2) + D_o sf2 ] - 1/2 sum_q (mu_q^2 + S_q - ln S_q - 1)
+ *     = -D_o/2 ln(2 pi / beta) - beta/2 sum_{d in O} [(y_d - mean_d)^2 + var_d] - KL,   mean, var = gp_predict at (X_mu, X_S) without the noise flag.
+ * cols: int32 list of the observed output columns, strictly increasing, shared by the call (NULL, 0: all D); the other columns of Y are never read.
+ * X_S (n,Q) > 0, or its softplus-inverse with xs_is_raw (as gp_upload_shard); grad_S is then the derivative with respect to the raw value.
+ * L (n), grad_mu (n,Q), grad_S (n,Q): any may be NULL.  Rows are independent: a row's outputs are bit-identical whatever other rows share the call.
+ * Preconditions, state rule and error codes are gp_predict's (GP_ERR_STATE unless the last global step succeeded on the statistics and globals as
+ * they are now; GP_ERR_BAD_ARG for n < 0, a bad column list, non-finite inputs in what is read, variances that are not > 0); n = 0 writes
+ * nothing.  Synchronous.  Leaves the evaluation state untouched: phase 2 / gp_finish after it give bit-identical results. */
+int gp_infer_objective(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* cols, int n_cols, const double* X_mu, const double* X_S, int xs_is_raw,
+                       double* L, double* grad_mu, double* grad_S);
+/* Maximises that L for every row over (X_mu, softplus-raw X_S), starting at the given values, which are overwritten with the result (X_S in the form
+ * it came in).  Per-row scaled conjugate gradients (Moller), entirely on the device.  A row stops when the largest absolute gradient component in the
+ * optimised variables is <= gtol (also at the start) or after max_iters iterations; iters (n, or NULL) reports the iterations taken, so
+ * iters < max_iters means the gradient criterion.  Only steps that do not lower L are accepted: L (n, or NULL) is gp_infer_objective's value at the
+ * returned point, bit for bit, and never below the value at the start.  Restarts are the caller's rows. */
+int gp_infer_latent(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* cols, int n_cols, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
+                    double gtol, double* L, int32_t* iters);
+
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
 /* set the reduced statistics from the host (partial_terms.set_local_statistics, partial_terms.py:54-61) */
