@@ -306,9 +306,7 @@ static int poison_scratch(gp_ctx* c) {
                                   &c->Bbar, &c->E, &c->PsiE, &c->Abar, &c->Bm, &c->gK, &c->gs, &c->stats, &c->grads, &c->gXmu, &c->gXs})
     GP_HIP(c, P(*b));
   GP_HIP(c, hipMemset2DAsync(c->Kaug, (size_t)c->LDK * 8, 0xFF, (size_t)c->Mp * 8, c->Np, c->stream));      // the Psi1 columns of [Psi1 | Y]
-  if (c->b_alloc)
-    for (const DevBuf<double>* b : {&c->LE, &c->LET, &c->Gpart, &c->gapart2, &c->Gtmp, &c->pp, &c->ppt, &c->Gt}) GP_HIP(c, P(*b));
-  return GP_OK;
+  return b_poison(c);
 }
 
 extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const double* alpha, double beta, int64_t N_global, double step) {

@@ -141,8 +141,10 @@ int compat_build(gp_ctx* c, int which, DevBuf<double>& out) {
   if (needs_p2) {
     if (which != GP_ARR_PSI2_POINTS) GP_TRY_RC(p2buf.alloc(c, N * M * M, DA_RAW));
     p2 = which == GP_ARR_PSI2_POINTS ? buf.get() : p2buf.get();
-    if (!c->regime_A) { const int rc = run_dz2(c); if (rc != GP_OK) return rc; }
-    hipLaunchKernelGGL(psi2_points_kernel, dim3(grid_for(N * M * M)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, c->LE, c->Mp, !b_generic(c) && le_interleaved(c->QB), c->Vn, c->DZ2,
+    const double *LE = nullptr, *Vn = nullptr, *DZ2 = nullptr;
+    bool le_il = false;
+    if (!c->regime_A) GP_TRY_RC(b_point_tables(c, &LE, &le_il, &Vn, &DZ2));
+    hipLaunchKernelGGL(psi2_points_kernel, dim3(grid_for(N * M * M)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, LE, c->Mp, le_il, Vn, DZ2,
                        N, (int)M, (int)Q, c->regime_A ? 1 : 0, p2);
   }
   switch (which) {

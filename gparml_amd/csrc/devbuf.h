@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
-#include <functional>
 #include <vector>
 #include "../../include/gparml_hip.h"
 
@@ -92,25 +91,5 @@ int upload(gp_ctx* c, DevBuf<T>& b, const std::vector<T>& v) {
   b = std::move(t);
   return GP_OK;
 }
-
-// All-or-nothing allocation of a group of a context's owners: each call allocates one (none once one has failed).  Unless a commit() finds every
-// allocation done, the destructor empties every owner the group allocated, so a failure part way -- or any early return before the group is
-// complete -- leaves none of them set.
-class AllocGroup {
- public:
-  explicit AllocGroup(gp_ctx* c) : c_(c) {}
-  ~AllocGroup() { if (!committed_) for (auto& r : undo_) r(); }
-  template <typename T> void operator()(DevBuf<T>& b, size_t n, int mode = DA_INIT) { add(b, [&] { return b.alloc(c_, n, mode); }); }
-  template <typename T> void operator()(DevBuf<T>& b, const std::vector<T>& v) { add(b, [&] { return upload(c_, b, v); }); }
-  int status() const { return rc_; }
-  int commit() { committed_ = rc_ == GP_OK; return rc_; }       // the group stays when it is complete (GP_OK)
-
- private:
-  template <typename T, typename F> void add(DevBuf<T>& b, F&& f) { if (rc_ == GP_OK) { undo_.push_back([&b] { b.reset(); }); rc_ = f(); } }
-  gp_ctx* c_;
-  int rc_ = GP_OK;
-  bool committed_ = false;
-  std::vector<std::function<void()>> undo_;
-};
 
 }  // namespace gp

@@ -53,10 +53,16 @@ enum { SC_SUM_YYT = 0, SC_PSI0 = 1, SC_KL = 2, SC_NLOCAL = 3, SC_COUNT = 8 };
 enum { GS_LOGDET_K = 0, GS_LOGDET_A = 1, GS_F = 2, GS_GRAD_BETA = 3, GS_GRAD_SF2 = 4, GS_FAIL = 5, GS_TR_KIPSI2 = 6, GS_TR_PPSI2 = 7,
        GS_TR_CE = 8, GS_TR_EPSI2E = 9, GS_SUM_V = 10, GS_SUM_AC = 11, GS_SUM_BPSI2 = 12, GS_COUNT = 16 };
 
-struct P1Plan;   // p1v2.hip
-struct I8Plan;   // p1i8.hip
+struct P1Plan;     // p1v2.hip
+struct I8Plan;     // p1i8.hip
+struct BPlan;      // psi2_plan.h
+struct PredPlan;   // predict.hip
+struct InferPlan;  // infer.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
+struct BPlanDelete { void operator()(BPlan* p) const; };
+struct PredPlanDelete { void operator()(PredPlan* p) const; };
+struct InferPlanDelete { void operator()(InferPlan* p) const; };
 
 }  // namespace gp
 
@@ -131,7 +137,6 @@ struct gp_ctx {
   gp::DevBuf<double> T2;      // [Mp][Mp] scratch
   gp::DevBuf<double> dFdK;    // [Mp][Mp]
   gp::DevBuf<double> Bbar;    // [Mp][Mp]
-  gp::DevBuf<double> Bbar4;   // free embeddings, Q <= 16: Bbar with four ROWS interleaved, element (m, m') at ((m / 4) Mp + m') 4 + m % 4 (csrc/psi2.hip)
   gp::DevBuf<double> E;       // [Mp][Dp]
   gp::DevBuf<double> PsiE;    // [Mp][Dp]
   gp::DevBuf<double> Abar;    // [Mp][Dp]
@@ -155,88 +160,10 @@ struct gp_ctx {
   gp::DevBuf<unsigned long long> p2prog;  // p2_fast8_kernel: [slices][MT] tile progress of the workgroups of a slice (kept in step for the L2), bases grow per launch
   unsigned long long p2_epoch = 0;
   gp::DevBuf<double> hgpart;  // partial sums of the fast path's mu^2 term of grad_alpha (per wave, or per 256 points from p2_ga_kernel)
-  // regime B (variances > 0): pairwise psi2 kernels; allocated on first use
-  bool b_alloc = false;
-  gp::DevBuf<double> LE;      // [Np][Mp]  1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2   (n-major)
-  gp::DevBuf<double> LET;     // [Np][Mp]  LEA = LE + sum_q V_nq z_mq^2 (n-major)
-  gp::DevBuf<double> Vn;      // [Np][Q]   -1/4 (alpha_q - w_nq)
-  gp::DevBuf<double> Wn;      // [Np][Q]   w_nq = alpha_q / (2 alpha_q S_nq + 1)
-  gp::DevBuf<double> V2P;     // [Np][QB]  -2 V_nq, zero-padded to the kernels' compile-time width QB
-  gp::DevBuf<double> WP;      // [Np][QB]  w_nq, zero-padded
-  gp::DevBuf<double> MUP;     // [Np][QB]  mu_nq, zero-padded
-  gp::DevBuf<double> alphaP;  // [QB]      alpha, zero-padded
-  gp::DevBuf<double> Z1P;     // [Mp][QB]  Z with a column of ones at index Q (only meaningful when QB > Q)
-  bool b_mfma = false;        // regime-B phase 1 on the matrix core (psi2_pairs_mfma_kernel: latent tables 32 / 52 / 64 wide with a spare column)
-  bool b_sym = false;         // regime-B phase 2 on tile pairs (psi2_sym_kernel: Q <= 10, 64 < M <= 1024)
-  gp::DevBuf<double> Z1S;     // [Mp][RT]  [Z | 1 at index QB | 0], RT = QB + 1 rounded up to 4: B operand of the row-side MFMAs
-  gp::DevBuf<int> sym_sched;  // [rounds][waves] tile of every wave in every round (I | J << 16, -1 idle)
-  int sym_nw = 0, sym_rounds = 0;
-  gp::DevBuf<double> ZP;      // [Mp][QB]  Z zero-padded (rows >= M and columns >= Q are zero)
-  int QB = 0;                 // 4, 10, 16, 32 or 64: smallest instantiated width >= Q
-  gp::DevBuf<double> lnc2h;   // [Np]      1/2 ln c2_n
-  gp::DevBuf<double> DZ2;     // [M][M][Q] (z_mq - z_m'q)^2
-  gp::DevBuf<double> Gpart;   // [pb_blocks][M][Q] per-block grad_Z partials of the psi2 part
-  gp::DevBuf<double> Gtmp;    // [64][M][Q] second-level grad_Z partials
-  gp::DevBuf<double> gapart2; // [pb_blocks][Q]
-  gp::DevBuf<double> pp;      // [Np][3Q+1] per-point running sums sr, zr, z2r, zt of the psi2 rows kernel
-  int pb_blocks = 0;
-  int nslab = 0, ppb = 0;     // regime-B phase-2 pair kernel: 64-column slabs of M, points per workgroup
-  gp::DevBuf<int> ptiles;     // upper-triangular 16x16 tile table for the psi2 pair kernel
-  int n_ptiles = 0;
-  gp::DevBuf<int> tiles64;    // upper-triangular 64x64 tile table for the MFMA pair kernel (wide latent spaces) and the tile-pair phase 2
-  int n_tiles64 = 0;
-  // regime-B phase 2 on tile pairs (psi2_tile.hip, Q <= 51)
-  bool b_tile = false;        // regime-B phase 2 runs on psi2_tile_kernel
-  gp::DevBuf<double> ppt;     // [tiles][3Q+1][b_ch] per-point sums of every tile for the points of one launch
-  gp::DevBuf<double> Gt;      // [b_S][tiles][2][64][Q] grad_Z partials per workgroup
-  long b_ch = 0;              // points per launch
-  int b_S = 0;                // point slices per launch
-  // regime B beyond the compiled latent widths (psi2_generic.hip, Q >= 64): psi2_n of a chunk of points and its row contractions
-  gp::DevBuf<double> gen_T;   // [gen_P][M][M]
-  gp::DevBuf<double> gen_rt;  // [gen_P][M][Q + 1]
-  long gen_P = 0;             // points per chunk
-  // gp_predict (predict.hip): allocated on first use, pr_rows points per chunk
+  std::unique_ptr<gp::BPlan, gp::BPlanDelete> bplan;          // regime B (variances > 0): the pairwise psi2 kernels' plan (psi2_plan.h), built on first use
   bool pred_ok = false;       // the global step's Inv / Linv / E describe the statistics buffer as it is now (cleared whenever it or Z changes)
-  long pr_rows = 0;
-  gp::DevBuf<double> pr_in;   // [2][pr_rows][Q] X_mu | X_S of the chunk as given
-  gp::DevBuf<double> pr_mu;   // [pr_rows][Q]
-  gp::DevBuf<double> pr_U;    // [pr_rows][Q] alpha / (alpha S + 1)
-  gp::DevBuf<double> pr_lnc1; // [pr_rows]
-  gp::DevBuf<double> pr_P1;   // [pr_rows][Mp] Psi1 of the chunk
-  gp::DevBuf<double> pr_G;    // [pr_rows][Dp + 2 Mp] [mean | Lk^-1 k* | La^-1 k*]
-  gp::DevBuf<double> pr_out;  // [2][pr_rows][D] mean | var
-  gp::DevBuf<double> pr_W;    // [pr_rows][Q] w = alpha / (2 alpha S + 1)          (uncertain inputs)
-  gp::DevBuf<double> pr_V2;   // [pr_rows][Q] (alpha - w) / 2
-  gp::DevBuf<double> pr_lnc2; // [pr_rows]    1/2 ln c2
-  gp::DevBuf<double> pr_LEA;  // [pr_rows][Mp]
-  gp::DevBuf<double> pr_B;    // [Mp][Mp] Ki - P
-  // gp_infer_objective / gp_infer_latent (infer.hip): allocated on first use, in_rows rows per chunk, in_dop padded observed columns
-  long in_rows = 0, in_dop = 0;
-  gp::DevBuf<int> in_cols;      // [D] observed output columns of the call
-  gp::DevBuf<double> in_ZP;     // [Mp][QP] Z zero-padded to the latent table width
-  gp::DevBuf<double> in_ZZ;     // [Mp][QP] Z o Z
-  gp::DevBuf<double> in_T;      // [Mp][Mp] beta^2 Eo Eo^T
-  gp::DevBuf<double> in_Gf;     // [Mp][Mp] G = W_O W_O^T - D_o (Ki - P), folded onto m' >= m
-  gp::DevBuf<double> in_Eo;     // [Mp][in_dop] observed columns of E
-  gp::DevBuf<double> in_Yc;     // [in_rows][D_o] observed columns of the chunk as uploaded
-  gp::DevBuf<double> in_Yo;     // [in_rows][in_dop] the same, zero-padded
-  gp::DevBuf<double> in_yy;     // [in_rows] |y_O|^2
-  gp::DevBuf<double> in_V;      // [in_rows][Mp] beta Yo Eo^T
-  gp::DevBuf<double> in_LEA;    // [in_rows][Mp]
-  gp::DevBuf<double> in_TB;     // [in_rows][5 QP] mu | S | u | w | v2 of the evaluation point
-  gp::DevBuf<double> in_LC;     // [in_rows][2] ln c1, 1/2 ln c2
-  gp::DevBuf<double> in_xe;     // [in_rows][2Q] evaluation point (mu | S or raw S)
-  gp::DevBuf<double> in_fe;     // [in_rows] L at the evaluation point
-  gp::DevBuf<double> in_ge;     // [in_rows][2Q] its gradient
-  gp::DevBuf<double> in_x;      // the optimiser's state (gp_infer_latent): current point, gradients, direction, S at x, scalars, results
-  gp::DevBuf<double> in_gn;
-  gp::DevBuf<double> in_go;
-  gp::DevBuf<double> in_d;
-  gp::DevBuf<double> in_Scur;
-  gp::DevBuf<double> in_sc;
-  gp::DevBuf<double> in_out;
-  gp::DevBuf<unsigned char> in_mask;   // [in_rows] rows of the next evaluation
-  gp::DevBuf<int> in_si;        // [in_rows][4] status, success flag, successes in a row, iterations | the active-row count
+  std::unique_ptr<gp::PredPlan, gp::PredPlanDelete> pred;     // gp_predict's buffers (predict.hip), built on first use
+  std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip), built on first use
   // CG vectors (resident): grad_latest/new/old (2,N,Q) each
   gp::DevBuf<double> g_latest;
   gp::DevBuf<double> g_new;
@@ -269,6 +196,7 @@ int run_prep_and_generate(gp_ctx* c);
 int run_phase1(gp_ctx* c);
 int run_phase2(gp_ctx* c);
 bool p2_fast_mode(const gp_ctx* c);
+int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
 // p1i8.hip (regime A phase 1 on the int8 matrix core)
 bool p1i8_applicable(const gp_ctx* c);
 bool p1i8_applicable_static(const gp_ctx* c);     // the shape / regime conditions alone (not the opt-in switch, not the guard)
@@ -280,21 +208,13 @@ int p1i8_check_finish(gp_ctx* c);     // gp_finish, after the stream synchronisa
 // p1v2.hip (regime A phase 1 without wasted tile slots)
 bool p1v2_applicable(const gp_ctx* c);
 int run_phase1_v2(gp_ctx* c);
-// psi2.hip (regime B)
-int ensure_regime_b_buffers(gp_ctx* c);
+// psi2.hip (regime B; the psi2 trio's own declarations: psi2_plan.h)
 int run_generate_b(gp_ctx* c);
 int run_phase1_b(gp_ctx* c);
 int run_phase2_b(gp_ctx* c);
-int run_dz2(gp_ctx* c);
-// psi2_generic.hip (regime B for Q >= 64: plain kernels, any Q)
-bool b_generic(const gp_ctx* c);
-int run_le_generic(gp_ctx* c);
-int run_phase1_b_generic(gp_ctx* c);
-int run_phase2_b_generic(gp_ctx* c);
-// psi2_tile.hip (regime B phase 2 on tile pairs)
-bool pt2_applicable(const gp_ctx* c, bool sym_available);
-int run_phase2_b_tiles(gp_ctx* c);
-int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
+int b_poison(gp_ctx* c);                                              // poison mode: refills the plan's per-evaluation buffers (BPlan::poisoned)
+int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn, const double** DZ2);   // compat: runs dz2_kernel, hands out the tables
+const double* b_debug_table(const gp_ctx* c, bool lea, long* n);      // gp_debug_peek: LE or LEA, NULL / 0 without a plan
 // predict.hip
 extern std::atomic<int> g_opt_pred_rows;
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);

@@ -471,73 +471,79 @@ __global__ void __launch_bounds__(256) inf_scg_out_kernel(ScgArgs a, double* __r
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------------
+// the optimiser's state (gp_infer_latent)
+struct InfOpt {
+  DevBuf<double> x, gn, go, d, Scur, sc, out;   // current point, gradients, direction, S at x, scalars, results
+  DevBuf<unsigned char> mask;   // [rows] rows of the next evaluation
+  DevBuf<int> si;               // [rows][4] status, success flag, successes in a row, iterations | the active-row count
+};
+
+// the chunk buffers, keyed on (rows per chunk, padded observed columns); the optimiser's state goes with them
+struct InfChunk {
+  long rows = 0, dop = 0;
+  DevBuf<double> Eo;            // [Mp][dop] observed columns of E
+  DevBuf<double> Yc, Yo;        // [rows][D_o] observed columns of the chunk as uploaded, [rows][dop] the same zero-padded
+  DevBuf<double> yy;            // [rows] |y_O|^2
+  DevBuf<double> V, LEA;        // [rows][Mp] beta Yo Eo^T, LEA of the evaluation point
+  DevBuf<double> TB;            // [rows][5 QP] mu | S | u | w | v2 of the evaluation point
+  DevBuf<double> LC;            // [rows][2] ln c1, 1/2 ln c2
+  DevBuf<double> xe, fe, ge;    // the evaluation point [rows][2Q] (mu | S or raw S), L there [rows] and its gradient [rows][2Q]
+  std::unique_ptr<InfOpt> opt;
+};
+
+// the model tables (the plan itself: built by the first call, kept for the context's life)
+struct InferPlan {
+  DevBuf<int> cols;             // [D] observed output columns of the call
+  DevBuf<double> ZP, ZZ;        // [Mp][QP] Z zero-padded to the latent table width, Z o Z
+  DevBuf<double> T, Gf;         // [Mp][Mp] beta^2 Eo Eo^T, G = W_O W_O^T - D_o (Ki - P) folded onto m' >= m
+  std::unique_ptr<InfChunk> chunk;
+};
+void InferPlanDelete::operator()(InferPlan* p) const { delete p; }
+
+// Each group is built aside and published only when complete.  Every element is written before it is read (DA_RAW: NaN-filled in the poison mode).
 static int inf_alloc(gp_ctx* c, long R, long Dop, int QP, bool latent) {
   const long Mp = c->Mp, Q = c->Q;
-  // three groups, each all or nothing: the model tables (in_Gf, their last, set), the chunk buffers (in_rows != 0 once they exist for this chunk size and
-  // column count) and the optimiser's state (in_si, its last, set).  Every element is written before it is read (DA_RAW: NaN-filled in the poison mode).
-  if (!c->in_Gf) {
-    AllocGroup A(c);
-    A(c->in_cols, (size_t)c->D, DA_RAW);
-    A(c->in_ZP, (size_t)Mp * QP, DA_RAW);
-    A(c->in_ZZ, (size_t)Mp * QP, DA_RAW);
-    A(c->in_T, (size_t)Mp * Mp, DA_RAW);
-    A(c->in_Gf, (size_t)Mp * Mp, DA_RAW);
-    GP_TRY_RC(A.commit());
+  auto A = [c](auto& b, long n) { return b.alloc(c, (size_t)n, DA_RAW); };
+  if (!c->infer) {
+    std::unique_ptr<InferPlan, InferPlanDelete> p(new InferPlan());
+    GP_TRY_RC(A(p->cols, c->D)); GP_TRY_RC(A(p->ZP, Mp * QP)); GP_TRY_RC(A(p->ZZ, Mp * QP)); GP_TRY_RC(A(p->T, Mp * Mp)); GP_TRY_RC(A(p->Gf, Mp * Mp));
+    c->infer = std::move(p);
   }
-  if (c->in_rows != R || c->in_dop != Dop) {
-    for (DevBuf<double>* b : {&c->in_Eo, &c->in_Yc, &c->in_Yo, &c->in_yy, &c->in_V, &c->in_LEA, &c->in_TB, &c->in_LC, &c->in_xe, &c->in_fe, &c->in_ge, &c->in_x,
-                              &c->in_gn, &c->in_go, &c->in_d, &c->in_Scur, &c->in_sc, &c->in_out})
-      b->reset();
-    c->in_si.reset();
-    c->in_mask.reset();
-    c->in_rows = 0;
-    AllocGroup A(c);
-    A(c->in_Eo, (size_t)Mp * Dop, DA_RAW);
-    A(c->in_Yc, (size_t)R * Dop, DA_RAW);            // the observed columns of the chunk, packed [cnt][Do]
-    A(c->in_Yo, (size_t)R * Dop, DA_RAW);
-    A(c->in_yy, (size_t)R, DA_RAW);
-    A(c->in_V, (size_t)R * Mp, DA_RAW);
-    A(c->in_LEA, (size_t)R * Mp, DA_RAW);
-    A(c->in_TB, (size_t)R * 5 * QP, DA_RAW);
-    A(c->in_LC, (size_t)R * 2, DA_RAW);
-    A(c->in_xe, (size_t)R * 2 * Q, DA_RAW);
-    A(c->in_fe, (size_t)R, DA_RAW);
-    A(c->in_ge, (size_t)R * 2 * Q, DA_RAW);
-    GP_TRY_RC(A.commit());
-    c->in_rows = R;
-    c->in_dop = Dop;
+  InferPlan& p = *c->infer;
+  if (!p.chunk || p.chunk->rows != R || p.chunk->dop != Dop) {
+    p.chunk.reset();
+    auto k = std::make_unique<InfChunk>();
+    GP_TRY_RC(A(k->Eo, Mp * Dop)); GP_TRY_RC(A(k->Yc, R * Dop)); GP_TRY_RC(A(k->Yo, R * Dop)); GP_TRY_RC(A(k->yy, R)); GP_TRY_RC(A(k->V, R * Mp));
+    GP_TRY_RC(A(k->LEA, R * Mp)); GP_TRY_RC(A(k->TB, R * 5 * QP)); GP_TRY_RC(A(k->LC, R * 2));
+    GP_TRY_RC(A(k->xe, R * 2 * Q)); GP_TRY_RC(A(k->fe, R)); GP_TRY_RC(A(k->ge, R * 2 * Q));
+    k->rows = R; k->dop = Dop;
+    p.chunk = std::move(k);
   }
-  if (latent && !c->in_si) {
-    AllocGroup A(c);
-    A(c->in_x, (size_t)R * 2 * Q, DA_RAW);
-    A(c->in_gn, (size_t)R * 2 * Q, DA_RAW);
-    A(c->in_go, (size_t)R * 2 * Q, DA_RAW);
-    A(c->in_d, (size_t)R * 2 * Q, DA_RAW);
-    A(c->in_Scur, (size_t)R * Q, DA_RAW);
-    A(c->in_sc, (size_t)R * IS_COUNT, DA_RAW);
-    A(c->in_out, (size_t)R * (2 * Q + 2), DA_RAW);
-    A(c->in_mask, (size_t)R, DA_RAW);
-    A(c->in_si, (size_t)R * II_COUNT + 1, DA_RAW);   // the last int: the active-row count
-    GP_TRY_RC(A.commit());
+  if (latent && !p.chunk->opt) {
+    auto o = std::make_unique<InfOpt>();
+    GP_TRY_RC(A(o->x, R * 2 * Q)); GP_TRY_RC(A(o->gn, R * 2 * Q)); GP_TRY_RC(A(o->go, R * 2 * Q)); GP_TRY_RC(A(o->d, R * 2 * Q)); GP_TRY_RC(A(o->Scur, R * Q));
+    GP_TRY_RC(A(o->sc, R * IS_COUNT)); GP_TRY_RC(A(o->out, R * (2 * Q + 2))); GP_TRY_RC(A(o->mask, R));
+    GP_TRY_RC(A(o->si, R * II_COUNT + 1));      // the last int: the active-row count
+    p.chunk->opt = std::move(o);
   }
   return GP_OK;
 }
 
 static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
-// one evaluation of the rows of the chunk that mask selects (NULL: all) at in_xe
-static int inf_evaluate(gp_ctx* c, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
+// one evaluation of the rows of the chunk that mask selects (NULL: all) at xe
+static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
   hipStream_t st = c->stream;
   const int M = c->M, Mp = c->Mp, Q = c->Q;
-  hipLaunchKernelGGL(inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, st, c->in_xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, c->in_TB, c->in_LC);
-  hipLaunchKernelGGL(inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, st, c->in_TB, c->in_LC, mask, c->in_ZP, c->in_ZZ, cnt, M, Mp, QP, c->in_LEA);
+  hipLaunchKernelGGL(inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, st, k.xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, k.TB, k.LC);
+  hipLaunchKernelGGL(inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, st, k.TB, k.LC, mask, p.ZP, p.ZZ, cnt, M, Mp, QP, k.LEA);
   InfDims a;
   a.cnt = cnt; a.M = M; a.Mp = Mp; a.Q = Q; a.QP = QP; a.raw = raw; a.sf2 = c->sf2; a.beta = c->beta; a.Do = Do;
-  double* ge = want_grad ? c->in_ge.get() : nullptr;
+  double* ge = want_grad ? k.ge.get() : nullptr;
   const dim3 grid((unsigned)((cnt + 3) / 4));
 #define INF_ROWS(QR, WIDE)                                                                                                                              \
-  hipLaunchKernelGGL((inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, st, c->in_xe.get(), c->in_TB.get(), c->in_LC.get(), c->in_LEA.get(), c->in_V.get(), \
-                     c->in_yy.get(), c->in_ZP.get(), c->in_ZZ.get(), c->in_Gf.get(), mask, c->in_fe.get(), ge, a)
+  hipLaunchKernelGGL((inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, st, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), \
+                     k.yy.get(), p.ZP.get(), p.ZZ.get(), p.Gf.get(), mask, k.fe.get(), ge, a)
   if (QP == 4) INF_ROWS(4, false);
   else if (QP == 10) INF_ROWS(10, false);
   else if (QP == 16) INF_ROWS(16, false);
@@ -556,19 +562,21 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
   const int QP = inf_qp((int)Q);
   const long R = inf_rows_for(c, Dop);
   GP_TRY_RC(inf_alloc(c, R, Dop, QP, mode == 1));
+  const InferPlan& p = *c->infer;
+  const InfChunk& k = *p.chunk;
   hipStream_t st = c->stream;
   // ---- once per call: the observed columns, G and the latent tables
   std::vector<int> hc(Do);
   for (int j = 0; j < Do; ++j) hc[j] = cols ? cols[j] : j;
-  GP_HIP(c, hipMemcpyAsync(c->in_cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->E, c->in_cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, c->in_Eo);
-  hipLaunchKernelGGL(inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, st, c->Z, (int)M, (int)Mp, (int)Q, QP, c->in_ZP, c->in_ZZ);
+  GP_HIP(c, hipMemcpyAsync(p.cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
+  hipLaunchKernelGGL(inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, st, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
   GP_HIP(c, hipGetLastError());
   GemmP g;
   g.K = (int)Dop; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
-  g.A = c->in_Eo; g.lda = Dop; g.B = c->in_Eo; g.ldb = Dop; g.C = c->in_T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
+  g.A = k.Eo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = p.T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
   launch_gemm(st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g);
-  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, c->in_T, c->Inv, (int)M, (int)Mp, (double)Do, c->in_Gf);
+  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, p.T, c->Inv, (int)M, (int)Mp, (double)Do, p.Gf);
   GP_HIP(c, hipGetLastError());
   // the observed columns of every row, packed on the host: the others are never read
   std::vector<double> yc((size_t)n * Do);
@@ -576,10 +584,11 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
     for (int j = 0; j < Do; ++j) yc[(size_t)i * Do + j] = Y[i * D + hc[j]];
   std::vector<double> hx((size_t)std::min(n, R) * 2 * Q), hout;
   std::vector<double> hg;
-  ScgArgs s;
+  ScgArgs s{};
   s.Q = (int)Q; s.QP = QP; s.raw_in = raw; s.max_iters = max_iters; s.gtol = gtol;
-  s.x = c->in_x; s.gn = c->in_gn; s.go = c->in_go; s.d = c->in_d; s.xe = c->in_xe; s.ge = c->in_ge; s.fe = c->in_fe; s.TB = c->in_TB; s.Scur = c->in_Scur;
-  s.sc = c->in_sc; s.si = c->in_si; s.mask = c->in_mask;
+  const InfOpt* o = k.opt.get();      // NULL for gp_infer_objective (unless an earlier gp_infer_latent built it)
+  s.xe = k.xe; s.ge = k.ge; s.fe = k.fe; s.TB = k.TB;
+  if (mode == 1) { s.x = o->x; s.gn = o->gn; s.go = o->go; s.d = o->d; s.Scur = o->Scur; s.sc = o->sc; s.si = o->si; s.mask = o->mask; }
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
     s.cnt = cnt;
@@ -588,19 +597,19 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
         hx[i * 2 * Q + q] = X_mu[(n0 + i) * Q + q];
         hx[i * 2 * Q + Q + q] = X_S[(n0 + i) * Q + q];
       }
-    GP_HIP(c, hipMemcpyAsync(c->in_xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
-    GP_HIP(c, hipMemcpyAsync(c->in_Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, st, c->in_Yc, cnt, rows, Do, (int)Dop, c->in_Yo, c->in_yy);
+    GP_HIP(c, hipMemcpyAsync(k.xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(k.Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, st, k.Yc, cnt, rows, Do, (int)Dop, k.Yo, k.yy);
     GP_HIP(c, hipGetLastError());
-    g.A = c->in_Yo; g.lda = Dop; g.B = c->in_Eo; g.ldb = Dop; g.C = c->in_V; g.ldc = Mp; g.alpha = c->beta; g.beta = 0.0;
+    g.A = k.Yo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = k.V; g.ldc = Mp; g.alpha = c->beta; g.beta = 0.0;
     launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, g);
     GP_HIP(c, hipGetLastError());
     if (mode == 0) {
-      GP_TRY_RC(inf_evaluate(c, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
-      if (L) GP_HIP(c, hipMemcpyAsync(L + n0, c->in_fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+      GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
+      if (L) GP_HIP(c, hipMemcpyAsync(L + n0, k.fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
       if (grad_mu || grad_S) {
         hg.resize((size_t)cnt * 2 * Q);
-        GP_HIP(c, hipMemcpyAsync(hg.data(), c->in_ge, (size_t)cnt * 2 * Q * 8, hipMemcpyDeviceToHost, st));
+        GP_HIP(c, hipMemcpyAsync(hg.data(), k.ge, (size_t)cnt * 2 * Q * 8, hipMemcpyDeviceToHost, st));
       }
       GP_HIP(c, hipStreamSynchronize(st));
       for (long i = 0; (grad_mu || grad_S) && i < cnt; ++i)
@@ -610,28 +619,28 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
         }
       continue;
     }
-    GP_TRY_RC(inf_evaluate(c, cnt, raw, nullptr, true, QP, (double)Do));
+    GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, true, QP, (double)Do));
     const dim3 rg(inf_blocks(cnt));
     hipLaunchKernelGGL(inf_scg_init_kernel, rg, dim3(256), 0, st, s);
-    int* d_active = c->in_si.get() + R * II_COUNT;
+    int* d_active = o->si.get() + R * II_COUNT;
     for (int it = 0; it < max_iters; ++it) {
       if (it % INF_POLL == 0) {
         int active = 0;
-        hipLaunchKernelGGL(inf_count_kernel, dim3(1), dim3(256), 0, st, c->in_si, cnt, d_active);
+        hipLaunchKernelGGL(inf_count_kernel, dim3(1), dim3(256), 0, st, o->si, cnt, d_active);
         GP_HIP(c, hipMemcpyAsync(&active, d_active, sizeof(int), hipMemcpyDeviceToHost, st));
         GP_HIP(c, hipStreamSynchronize(st));
         if (active == 0) break;
       }
       hipLaunchKernelGGL(inf_scg_probe_kernel, rg, dim3(256), 0, st, s);
-      GP_TRY_RC(inf_evaluate(c, cnt, 1, c->in_mask, true, QP, (double)Do));
+      GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
       hipLaunchKernelGGL(inf_scg_trial_kernel, rg, dim3(256), 0, st, s);
-      GP_TRY_RC(inf_evaluate(c, cnt, 1, c->in_mask, true, QP, (double)Do));
+      GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
       hipLaunchKernelGGL(inf_scg_update_kernel, rg, dim3(256), 0, st, s);
     }
-    hipLaunchKernelGGL(inf_scg_out_kernel, rg, dim3(256), 0, st, s, c->in_out.get());
+    hipLaunchKernelGGL(inf_scg_out_kernel, rg, dim3(256), 0, st, s, o->out.get());
     GP_HIP(c, hipGetLastError());
     hout.resize((size_t)cnt * (2 * Q + 2));
-    GP_HIP(c, hipMemcpyAsync(hout.data(), c->in_out, hout.size() * 8, hipMemcpyDeviceToHost, st));
+    GP_HIP(c, hipMemcpyAsync(hout.data(), o->out, hout.size() * 8, hipMemcpyDeviceToHost, st));
     GP_HIP(c, hipStreamSynchronize(st));
     for (long i = 0; i < cnt; ++i) {
       const double* o = hout.data() + i * (2 * Q + 2);

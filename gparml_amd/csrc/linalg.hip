@@ -949,8 +949,7 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   else if (!std::strcmp(name, "Xa")) { src = c->Xa; cnt = (long)c->Np * c->CXp; }
   else if (!std::strcmp(name, "grads")) { src = c->grads; cnt = (long)c->M * c->Q + c->Q; }
   else if (!std::strcmp(name, "Rpart")) { src = c->Rpart; cnt = (long)2 * (c->p2_slices + 8) * c->Mp * c->CXp; }
-  else if (!std::strcmp(name, "LE")) { src = c->LE; cnt = c->LE ? (long)c->Np * c->Mp : 0; }
-  else if (!std::strcmp(name, "LEA")) { src = c->LET; cnt = c->LET ? (long)c->Np * c->Mp : 0; }
+  else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
   GP_HIP(c, hipStreamSynchronize(c->stream));

@@ -16,7 +16,7 @@
 //     psi2[m, m'] = exp(LEA[m] + LEA[m'] + sum_q v2_q z_mq z_m'q),  v2 = (alpha - w) / 2,
 //   and fed as the A operand of v_mfma_f64_4x4x4_4b_f64 against E; the epilogue folds the column dot with E and sum(B o psi2) (both in fixed order).
 // Nothing of [n][M][M] is ever stored.  Every prediction buffer is owned by the context, allocated on first use and bounded by the chunk size
-// (pr_rows points per pass); gp_destroy frees them.  The evaluation's buffers are only read: phase 2 / gp_finish after a prediction give the same bits.
+// (rows points per pass, PredPlan); deleting the context frees them.  The evaluation's buffers are only read: phase 2 / gp_finish after a prediction give the same bits.
 #include "gp_common.h"
 #include "fexp.h"
 #include <algorithm>
@@ -240,33 +240,44 @@ static long pred_rows_for(const gp_ctx* c) {
   return std::max<long>(TILE, std::min<long>(16384, (64L << 20) / per_row / TILE * TILE));
 }
 
+// uncertain inputs: built on the first such prediction
+struct PredUnc {
+  DevBuf<double> W, V2;       // [rows][Q] w = alpha / (2 alpha S + 1), (alpha - w) / 2
+  DevBuf<double> lnc2;        // [rows]    1/2 ln c2
+  DevBuf<double> LEA;         // [rows][Mp]
+  DevBuf<double> B;           // [Mp][Mp]  Ki - P
+};
+
+// the chunk buffers, rows points per chunk: replaced whole when the chunk size changes
+struct PredPlan {
+  long rows = 0;
+  DevBuf<double> in;          // [2][rows][Q] X_mu | X_S of the chunk as given
+  DevBuf<double> mu, U;       // [rows][Q] mu, alpha / (alpha S + 1)
+  DevBuf<double> lnc1;        // [rows]
+  DevBuf<double> P1;          // [rows][Mp] Psi1 of the chunk
+  DevBuf<double> G;           // [rows][Dp + 2 Mp] [mean | Lk^-1 k* | La^-1 k*]
+  DevBuf<double> out;         // [2][rows][D] mean | var
+  std::unique_ptr<PredUnc> unc;
+};
+void PredPlanDelete::operator()(PredPlan* p) const { delete p; }
+
+// Each group is built aside and published only when complete.  Every element of these buffers is written before it is read (DA_RAW: NaN-filled in
+// the poison test mode).
 static int pred_alloc(gp_ctx* c, bool uncertain) {
-  const long R = pred_rows_for(c), Mp = c->Mp, Q = c->Q, D = c->D;
-  // two groups, each all or nothing: the chunk buffers (pr_rows != 0 once they exist) and those of uncertain inputs (pr_B, their last, set)
-  // every element of these is written before it is read (DA_RAW: NaN-filled in the poison test mode)
-  if (c->pr_rows != R) {
-    for (DevBuf<double>* b : {&c->pr_in, &c->pr_mu, &c->pr_U, &c->pr_lnc1, &c->pr_P1, &c->pr_G, &c->pr_out, &c->pr_W, &c->pr_V2, &c->pr_lnc2, &c->pr_LEA, &c->pr_B})
-      b->reset();
-    c->pr_rows = 0;
-    AllocGroup A(c);
-    A(c->pr_in, (size_t)2 * R * Q, DA_RAW);          // X_mu | X_S of the chunk, as given
-    A(c->pr_mu, (size_t)R * Q, DA_RAW);
-    A(c->pr_U, (size_t)R * Q, DA_RAW);
-    A(c->pr_lnc1, (size_t)R, DA_RAW);
-    A(c->pr_P1, (size_t)R * Mp, DA_RAW);
-    A(c->pr_G, (size_t)R * (c->Dp + 2 * Mp), DA_RAW);
-    A(c->pr_out, (size_t)2 * R * D, DA_RAW);        // mean | var
-    GP_TRY_RC(A.commit());
-    c->pr_rows = R;
+  const long R = pred_rows_for(c), Mp = c->Mp, Q = c->Q;
+  auto A = [c](DevBuf<double>& b, long n) { return b.alloc(c, (size_t)n, DA_RAW); };
+  if (!c->pred || c->pred->rows != R) {
+    c->pred.reset();
+    std::unique_ptr<PredPlan, PredPlanDelete> p(new PredPlan());
+    GP_TRY_RC(A(p->in, 2 * R * Q)); GP_TRY_RC(A(p->mu, R * Q)); GP_TRY_RC(A(p->U, R * Q)); GP_TRY_RC(A(p->lnc1, R));
+    GP_TRY_RC(A(p->P1, R * Mp)); GP_TRY_RC(A(p->G, R * (c->Dp + 2 * Mp))); GP_TRY_RC(A(p->out, 2 * R * c->D));
+    p->rows = R;
+    c->pred = std::move(p);
   }
-  if (uncertain && !c->pr_B) {
-    AllocGroup A(c);
-    A(c->pr_W, (size_t)R * Q, DA_RAW);
-    A(c->pr_V2, (size_t)R * Q, DA_RAW);
-    A(c->pr_lnc2, (size_t)R, DA_RAW);
-    A(c->pr_LEA, (size_t)R * Mp, DA_RAW);
-    A(c->pr_B, (size_t)Mp * Mp, DA_RAW);
-    GP_TRY_RC(A.commit());
+  if (uncertain && !c->pred->unc) {
+    auto u = std::make_unique<PredUnc>();
+    GP_TRY_RC(A(u->W, R * Q)); GP_TRY_RC(A(u->V2, R * Q)); GP_TRY_RC(A(u->lnc2, R)); GP_TRY_RC(A(u->LEA, R * Mp)); GP_TRY_RC(A(u->B, Mp * Mp));
+    c->pred->unc = std::move(u);
   }
   return GP_OK;
 }
@@ -274,61 +285,58 @@ static int pred_alloc(gp_ctx* c, bool uncertain) {
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {
   const bool unc = X_S != nullptr;
   GP_TRY_RC(pred_alloc(c, unc));
+  const PredPlan& p = *c->pred;
+  const PredUnc* u = p.unc.get();      // NULL for deterministic inputs (unless an earlier call built it)
   hipStream_t st = c->stream;
-  const long R = c->pr_rows, Mp = c->Mp, Dp = c->Dp, M = c->M, Q = c->Q, D = c->D;
+  const long R = p.rows, Mp = c->Mp, Dp = c->Dp, M = c->M, Q = c->Q, D = c->D;
   const long ldg = Dp + 2 * Mp;
   const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
   if (unc && var) {
-    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->Inv, (int)M, (int)Mp, c->pr_B);
+    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->Inv, (int)M, (int)Mp, u->B);
     GP_HIP(c, hipGetLastError());
   }
-  double* out_mean = c->pr_out;
-  double* out_var = c->pr_out + R * D;
+  double* out_mean = p.out;
+  double* out_var = p.out + R * D;
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
-    double* xin = c->pr_in;
-    double* sin = c->pr_in + R * Q;
+    double* xin = p.in;
+    double* sin = p.in + R * Q;
     GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
     if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, cnt,
-                       rows, (int)Q, c->sf2, c->pr_mu, c->pr_U, c->pr_lnc1, unc ? c->pr_W : nullptr, unc ? c->pr_V2 : nullptr, unc ? c->pr_lnc2 : nullptr);
+                       rows, (int)Q, c->sf2, p.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
     GP_HIP(c, hipGetLastError());
-    GP_TRY_RC(launch_psi1_rows(c, c->pr_mu, c->pr_U, c->pr_lnc1, c->pr_P1, cnt, rows, Mp));
+    GP_TRY_RC(launch_psi1_rows(c, p.mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
     // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
     GemmP g;
     g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
-    g.A = c->pr_P1; g.lda = Mp; g.C = c->pr_G; g.ldc = ldg;
+    g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = ldg;
     g.B = c->E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
     launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g);
     if (!unc) {
       if (var) {
-        g.B = c->Linv; g.ldb = Mp; g.alpha = 1.0; g.C = c->pr_G + Dp;
+        g.B = c->Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.G + Dp;
         launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g);
       }
       GP_HIP(c, hipGetLastError());
-      if (var) {
-        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, (int)M, (int)Mp, (int)D, (int)Dp,
-                           c->sf2, noise, out_mean, out_var);
-      } else {
-        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
-                           c->sf2, noise, out_mean, out_var);
-      }
+      hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
+                         c->sf2, noise, out_mean, out_var);
       GP_HIP(c, hipGetLastError());
       if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       if (var) GP_HIP(c, hipMemcpyAsync(var + n0, out_var, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
     } else {
       GP_HIP(c, hipGetLastError());
       if (mean) {
-        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, c->pr_G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
+        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, p.G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
                            c->sf2, noise, out_mean, out_var);
         GP_HIP(c, hipGetLastError());
         GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
       if (var) {
-        hipLaunchKernelGGL(pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, st, c->pr_mu, c->pr_W, c->pr_V2,
-                           c->pr_lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, c->pr_LEA);
+        hipLaunchKernelGGL(pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, st, p.mu, u->W, u->V2,
+                           u->lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, u->LEA);
         PsiWArgs a;
-        a.LEA = c->pr_LEA; a.V2 = c->pr_V2; a.Z = c->Z; a.E = c->E; a.B = c->pr_B; a.G = c->pr_G; a.ldg = ldg;
+        a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->E; a.B = u->B; a.G = p.G; a.ldg = ldg;
         a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;
         const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
         if (Q <= 16) hipLaunchKernelGGL(pred_psi2w_kernel<16>, grid, dim3(256), 0, st, a);

@@ -640,7 +640,7 @@ int run_phase1(gp_ctx* c) {
         while (fill[x] >= per_xcd) x = (x + 1) & 7;
         const int j = fill[x]++;
         slot[(x * per_xcd + j) * 2] = sl; slot[(x * per_xcd + j) * 2 + 1] = t;
-        if (fill[x] >= per_xcd || (T <= 64 && fill[x] - L * T >= (left + 1) / 2 * 2 && false)) x = (x + 1) & 7;
+        if (fill[x] >= per_xcd) x = (x + 1) & 7;
       }
     std::vector<int> bm(8 * per_xcd * 2);
     for (int j = 0; j < per_xcd; ++j)

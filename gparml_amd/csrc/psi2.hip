@@ -6,7 +6,7 @@
 // Phase 2: T_n = Bbar o psi2_n, r_n = T_n 1, t_n = T_n Z with one LANE per point, the pair index is wave-uniform
 //          (every pair quantity is a scalar operand), giving the psi2 parts of grad_Z / grad_alpha / grad_X_mu / grad_X_S
 //          (partial_terms.py:190-205, 273-284, 388-394, 421-427).
-#include "gp_common.h"
+#include "psi2_plan.h"
 #include "mma_f64.h"
 #include "fexp.h"
 #include "quad_mma.h"
@@ -719,240 +719,268 @@ __global__ void __launch_bounds__(256) pb2_reduce_kernel(const double* __restric
   }
 }
 
-int ensure_regime_b_buffers(gp_ctx* c) {
-  if (c->b_alloc) return GP_OK;
-  const long Np = c->Np, Mp = c->Mp, M = c->M, Q = c->Q;
-  AllocGroup A(c);      // all or nothing: a failure anywhere below leaves none of the group's buffers set (and b_alloc false)
-  // compiled latent widths; from 25 on the phase-2 kernel is the MFMA one and needs a spare column (QB > Q) for the ones.  r04: 6 and 8 next to 10 -- every
+void BPlanDelete::operator()(BPlan* p) const { delete p; }
+
+// The kernel families of a regime-B context and its latent table width QB, from Q, M, Mp and the switches GPARML_B_PHASE2 and GPARML_B_SYM_MAXQ:
+// the one place that picks them, once per plan.  Also the phase-2 slab count and psi2_sym_kernel's waves per workgroup, which the choice depends on.
+static void choose_b_path(const gp_ctx* c, BPlan& p) {
+  // GPARML_B_PHASE2=tiles forces the tile-pair phase 2 below Q = 17 as well (tests: every compiled width); =cols keeps the VALU kernels where they exist (Q <= 16: the default)
+  static const bool force_tiles = [] { const char* e = getenv("GPARML_B_PHASE2"); return e && std::string(e) == "tiles"; }();
+  static const int maxq = [] { const char* e = getenv("GPARML_B_SYM_MAXQ"); return e ? atoi(e) : 12; }();     // 10: the column kernel at Q = 11, 12 (same-box A/B)
+  const int Q = c->Q;
+  p.nslab = (c->M + 63) / 64;
+  p.sym_nw = (p.nslab + 1) / 2;
+  // beyond the compiled latent widths: psi2_generic.hip for both phases, its tables exactly Q wide
+  if (Q >= 64) { p.QB = Q; p.p1 = BP1::GENERIC; p.p2 = BP2::GENERIC; return; }
+  // compiled latent widths; from 25 on the matrix-core pair kernel reads Z1P and needs a spare column (QB > Q) for the ones.  r04: 6 and 8 next to 10 -- every
   // pair of every point pays 2 QB + 20 issue slots whatever Q is (N = 1e5, M = 512, same box: Q = 5, 6: 44.6 -> 39.0 ms per evaluation; Q = 7, 8: -4 %, the
   // tile-pair kernel's row tables are 12 wide at 8 as at 10); 12 and 14 next to 16 (the column kernel): Q = 12: 63.9 -> 57.1 ms, Q = 14: 65.8 -> 61.8 ms
-  c->QB = Q <= 4 ? 4 : Q <= 6 ? 6 : Q <= 8 ? 8 : Q <= 10 ? 10 : Q <= 12 ? 12 : Q <= 14 ? 14 : Q <= 16 ? 16 : Q <= 24 ? 24 : Q <= 31 ? 32 : Q <= 51 ? 52 : 64;
-  if (b_generic(c)) c->QB = (int)Q;       // psi2_generic.hip: the tables are exactly Q wide
-  c->b_mfma = Q >= 25 && Q < c->QB;
-  A(c->LE, (size_t)Np * Mp); A(c->LET, (size_t)Np * Mp); A(c->Vn, (size_t)Np * Q); A(c->Wn, (size_t)Np * Q);
-  A(c->ZP, (size_t)Mp * c->QB); A(c->Z1P, (size_t)Mp * c->QB);
+  p.QB = Q <= 4 ? 4 : Q <= 6 ? 6 : Q <= 8 ? 8 : Q <= 10 ? 10 : Q <= 12 ? 12 : Q <= 14 ? 14 : Q <= 16 ? 16 : Q <= 24 ? 24 : Q <= 31 ? 32 : Q <= 51 ? 52 : 64;
+  // phase 1: the matrix-core pair kernel from the 24-wide latent tables on (17 <= Q): same-box, N = 1e5, M = 512, ms of this kernel at Q = 17 / 20 / 24:
+  // 21.4 / 21.4 / 21.8 against 30.5 for psi2_pairs_kernel<24>; at 16 columns the VALU kernel is still ahead (15.3 ms measured against ~17 by the instruction count)
+  p.p1 = p.QB >= 24 ? BP1::PAIRS_MFMA : BP1::PAIRS;
+  // phase 2: the matrix-core tile pairs (psi2_tile.hip) from Q = 17 on.  A compiled width there has room for the column of ones up to Q = 63 (r04: the 64-wide
+  // instantiation, 230 VGPRs, 156 KB of LDS -- Q = 60, M = 1024, 2e4 points: 89 ms against 161 for psi2_cols_mfma_kernel).  The per-point folds and sums do not
+  // shrink with Q, so below 17 the VALU kernels are faster (same-box, ms of the phase-2 kernel per 1e5 points: Q = 4, M = 512: 21.7 (cols) vs 41.8 (tiles);
+  // Q = 10, M = 512: 31.7 (psi2_sym) vs 40.5; Q = 16, M = 512: 47.2 vs 56.5; Q = 20, M = 256: 23.1 vs 17.0; Q = 24, M = 512: 93.9 vs 69.7; Q = 50, M = 1024,
+  // 2e4 points: 96.4 (psi2_cols_mfma) vs 75.8).  (r06: the column kernels' instantiations for Q >= 17 and psi2_cols_mfma_kernel -- reachable only through
+  // =cols, 28-228 B of scratch per lane -- are gone.)
+  if (Q >= 17 || force_tiles) { p.p2 = BP2::TILES; return; }
+  // psi2_sym_kernel: latent tables up to 12 wide, three to sixteen 64-column slabs (two slabs = a single wave per workgroup running three tiles one after the
+  // other: slower than the column kernel, configs[1] 4.9 -> 5.2 ms), and its per-point array rt (Mp x sym_rs(QB) doubles of LDS per workgroup) must leave room
+  // for twelve waves per CU: with fewer the scalar-operand latency is exposed and the column kernel (four waves per SIMD) is faster (M = 1024: one workgroup
+  // per CU; re-measured in r06: M = 1024, Q = 10 -- one eight-wave workgroup per CU -- 75.5 ms per 5e4 points on this kernel against 69.8 on the column kernel)
+  const size_t smem = (size_t)c->Mp * sym_rs(p.QB) * sizeof(double);
+  const bool sym = p.QB <= std::min(maxq, 12) && p.nslab >= 3 && p.nslab <= 16 && smem <= 160 * 1024 && (160 * 1024 / smem) * p.sym_nw >= 12;
+  p.p2 = sym ? BP2::SYM : BP2::COLS;
+}
+
+// the plan of the first regime-B phase 1, built aside and published only when complete: a failure anywhere leaves no plan
+static int ensure_bplan(gp_ctx* c) {
+  if (c->bplan) return GP_OK;
+  const long Np = c->Np, Mp = c->Mp, M = c->M, Q = c->Q;
+  std::unique_ptr<BPlan, BPlanDelete> pl(new BPlan());
+  BPlan& p = *pl;
+  choose_b_path(c, p);
+  GP_TRY_RC(p.LE.alloc(c, (size_t)Np * Mp)); GP_TRY_RC(p.LET.alloc(c, (size_t)Np * Mp)); GP_TRY_RC(p.Vn.alloc(c, (size_t)Np * Q)); GP_TRY_RC(p.Wn.alloc(c, (size_t)Np * Q));
+  GP_TRY_RC(p.ZP.alloc(c, (size_t)Mp * p.QB)); GP_TRY_RC(p.Z1P.alloc(c, (size_t)Mp * p.QB));
   // zero contract: columns Q .. QB - 1 of the per-point tables and of alphaP are never written (b_tables_kernel fills q < Q) and every kernel runs its q loops to QB
-  A(c->V2P, (size_t)Np * c->QB, DA_ZERO); A(c->WP, (size_t)Np * c->QB, DA_ZERO); A(c->MUP, (size_t)Np * c->QB, DA_ZERO);
-  A(c->alphaP, (size_t)c->QB, DA_ZERO);
-  A(c->lnc2h, (size_t)Np);
+  GP_TRY_RC(p.V2P.alloc(c, (size_t)Np * p.QB, DA_ZERO)); GP_TRY_RC(p.WP.alloc(c, (size_t)Np * p.QB, DA_ZERO)); GP_TRY_RC(p.MUP.alloc(c, (size_t)Np * p.QB, DA_ZERO));
+  GP_TRY_RC(p.alphaP.alloc(c, (size_t)p.QB, DA_ZERO));
+  GP_TRY_RC(p.lnc2h.alloc(c, (size_t)Np));
   // phase-2 pair kernel: grid (point chunks, groups of <= 4 64-column slabs); >= 16 points per workgroup, <= 4096 chunks
-  c->nslab = (int)((M + 63) / 64);
-  c->ppb = (int)std::max<long>(16, (c->N + 4095) / 4096);
-  c->pb_blocks = (int)((c->N + c->ppb - 1) / c->ppb);
-  A(c->Bbar4, (size_t)Mp * Mp);
-  A(c->Gpart, (size_t)c->pb_blocks * M * Q); A(c->gapart2, (size_t)c->pb_blocks * Q); A(c->Gtmp, (size_t)64 * M * Q);
+  p.ppb = (int)std::max<long>(16, (c->N + 4095) / 4096); p.pb_blocks = (int)((c->N + p.ppb - 1) / p.ppb);
+  GP_TRY_RC(p.Bbar4.alloc(c, (size_t)Mp * Mp));
+  GP_TRY_RC(p.Gpart.alloc(c, (size_t)p.pb_blocks * M * Q)); GP_TRY_RC(p.gapart2.alloc(c, (size_t)p.pb_blocks * Q)); GP_TRY_RC(p.Gtmp.alloc(c, (size_t)64 * M * Q));
   std::vector<int> t;
   const int Mt = (int)((M + 15) / 16);
   for (int i = 0; i < Mt; ++i) for (int j = i; j < Mt; ++j) { t.push_back(i); t.push_back(j); }
-  c->n_ptiles = (int)t.size() / 2;
-  A(c->ptiles, t);
+  p.n_ptiles = (int)t.size() / 2; GP_TRY_RC(upload(c, p.ptiles, t));
   std::vector<int> t64;
   const int Mt64 = (int)((M + 63) / 64);
   for (int i = 0; i < Mt64; ++i) for (int j = i; j < Mt64; ++j) { t64.push_back(i); t64.push_back(j); }
-  c->n_tiles64 = (int)t64.size() / 2;
-  A(c->tiles64, t64);
-  // tile-pair phase 2 (psi2_sym_kernel): Q <= 10, three to sixteen 64-column slabs (two slabs = a single wave per workgroup
-  // running three tiles one after the other: slower than the column kernel, configs[1] 4.9 -> 5.2 ms).  Schedule = round-robin tournament over the
-  // slabs (circle method; an odd count gets a bye) followed by the diagonal tiles, one tile per wave and round.
-  // ... and its per-point array rt (Mp x RT doubles of LDS per workgroup) must leave room for twelve waves per CU: with fewer
-  // the scalar-operand latency is exposed and the column kernel (four waves per SIMD) is faster (M = 1024: one workgroup per CU)
-  {
-    const int nv = (c->nslab + 1) / 2 * 2, nw = nv / 2;
-    const size_t smem = (size_t)Mp * sym_rs(c->QB) * sizeof(double);
-    static const int maxq = [] { const char* e = getenv("GPARML_B_SYM_MAXQ"); return e ? atoi(e) : 12; }();     // 10: the column kernel at Q = 11, 12 (same-box A/B)
-    // (>= 12 waves per CU re-measured in r06: M = 1024, Q = 10 -- one eight-wave workgroup per CU -- 75.5 ms per 5e4 points on this kernel against 69.8 on the column kernel)
-    c->b_sym = !c->b_mfma && c->QB <= std::min(maxq, 12) && c->nslab >= 3 && c->nslab <= 16 && smem <= 160 * 1024 && (160 * 1024 / smem) * nw >= 12;
-    c->sym_nw = nw;
-  }
-  // the matrix-core tile-pair phase 2 (psi2_tile.hip) wherever psi2_sym_kernel does not apply; it keeps its own per-launch sums buffer
-  c->b_tile = !b_generic(c) && pt2_applicable(c, c->b_sym);
-  if (c->b_tile) c->b_sym = false;
-  A(c->pp, c->b_tile ? 1 : (size_t)Np * (3 * c->QB + 1) * (c->b_sym ? c->sym_nw : (c->nslab + 3) / 4));     // one group of sums per wave (sym) / per four slabs (cols)
+  p.n_tiles64 = (int)t64.size() / 2; GP_TRY_RC(upload(c, p.tiles64, t64));
+  const int nw = p.sym_nw, nv = 2 * nw;
+  // one group of sums per wave (sym) / per four slabs (cols); the tile-pair phase 2 keeps its own per-launch sums buffer
+  GP_TRY_RC(p.pp.alloc(c, p.p2 == BP2::TILES ? 1 : (size_t)Np * (3 * p.QB + 1) * (p.p2 == BP2::SYM ? nw : (p.nslab + 3) / 4)));
   std::vector<int> sch;
-  if (c->b_sym) {
-    const int nv = (c->nslab + 1) / 2 * 2, nw = nv / 2;
+  if (p.p2 == BP2::SYM) {
+    // round-robin tournament over the slabs (circle method; an odd count gets a bye) followed by the diagonal tiles, one tile per wave and round
     for (int r = 0; r < nv - 1; ++r)
       for (int k = 0; k < nw; ++k) {
         const int x = (k == 0) ? nv - 1 : (r + k) % (nv - 1), y = (k == 0) ? r : (r - k + (nv - 1)) % (nv - 1);
         const int I = std::min(x, y), J = std::max(x, y);
-        sch.push_back(J < c->nslab ? (I | (J << 16)) : -1);
+        sch.push_back(J < p.nslab ? (I | (J << 16)) : -1);
       }
-    for (int d = 0; d < c->nslab; d += nw)
-      for (int k = 0; k < nw; ++k) sch.push_back(d + k < c->nslab ? ((d + k) | ((d + k) << 16)) : -1);
-    c->sym_nw = nw; c->sym_rounds = (int)sch.size() / nw;
-    A(c->Z1S, (size_t)Mp * ((c->QB + 1 + 3) / 4 * 4));
-    A(c->sym_sched, sch);
+    for (int d = 0; d < p.nslab; d += nw)
+      for (int k = 0; k < nw; ++k) sch.push_back(d + k < p.nslab ? ((d + k) | ((d + k) << 16)) : -1);
+    p.sym_rounds = (int)sch.size() / nw;
+    GP_TRY_RC(p.Z1S.alloc(c, (size_t)Mp * ((p.QB + 1 + 3) / 4 * 4)));
+    GP_TRY_RC(upload(c, p.sym_sched, sch));
   }
-  GP_TRY_RC(A.status());
   GP_HIP(c, hipStreamSynchronize(c->stream));     // the tables' uploads
   // the pair kernel's split-n partials live in c->part: make sure it is large enough
-  GP_TRY_RC(c->part.grow(c, std::max((size_t)c->n_ptiles * 256 * 64, (size_t)c->n_tiles64 * 4096 * 32), DA_RAW));
-  GP_TRY_RC(A.commit());
-  c->b_alloc = true;
+  GP_TRY_RC(c->part.grow(c, std::max((size_t)p.n_ptiles * 256 * 64, (size_t)p.n_tiles64 * 4096 * 32), DA_RAW));
+  c->bplan = std::move(pl);
   return GP_OK;
 }
 
+int b_poison(gp_ctx* c) {
+  if (!c->bplan) return GP_OK;
+  for (const DevBuf<double>* b : c->bplan->poisoned())
+    if (b->size()) GP_HIP(c, hipMemsetAsync(*b, 0xFF, b->bytes(), c->stream));
+  return GP_OK;
+}
+
+const double* b_debug_table(const gp_ctx* c, bool lea, long* n) {
+  *n = c->bplan ? (long)c->Np * c->Mp : 0;
+  return !c->bplan ? nullptr : lea ? c->bplan->LET.get() : c->bplan->LE.get();
+}
+
 // (z_mq - z_m'q)^2 for the compat path's per-point psi2 tensor only (the pair kernels use the padded Z tables)
-int run_dz2(gp_ctx* c) {
+int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn, const double** DZ2) {
+  if (!c->bplan) return fail(c, GP_ERR_STATE, "the per-point psi2 tensor of free embeddings needs a gp_phase1 of this context first");
+  BPlan& p = *c->bplan;
   const long total = (long)c->M * c->M * c->Q;
-  if (!c->DZ2) GP_TRY_RC(c->DZ2.alloc(c, total, DA_RAW));
-  hipLaunchKernelGGL(dz2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, c->stream, c->Z, c->M, c->Q, c->DZ2);
+  if (!p.DZ2) GP_TRY_RC(p.DZ2.alloc(c, total, DA_RAW));
+  hipLaunchKernelGGL(dz2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, c->stream, c->Z, c->M, c->Q, p.DZ2);
   GP_HIP(c, hipGetLastError());
+  *LE = p.LE; *le_il = le_interleaved(p.QB); *Vn = p.Vn; *DZ2 = p.DZ2;
   return GP_OK;
 }
 
 template <int QT, int CPL>
-static void launch_le(gp_ctx* c) {
+static void launch_le(gp_ctx* c, const BPlan& p) {
   dim3 grid((c->Mp + 256 * CPL - 1) / (256 * CPL), (unsigned)(c->Np / 16));
-  hipLaunchKernelGGL((b_le_kernel<QT, CPL>), grid, dim3(256), 0, c->stream, (const double*)c->MUP, (const double*)c->WP, (const double*)c->V2P,
-                     (const double*)c->lnc2h, (const double*)c->ZP, (long)c->N, c->M, c->Mp, c->LE, c->LET);
+  hipLaunchKernelGGL((b_le_kernel<QT, CPL>), grid, dim3(256), 0, c->stream, (const double*)p.MUP, (const double*)p.WP, (const double*)p.V2P,
+                     (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, c->M, c->Mp, p.LE, p.LET);
 }
 
 int run_generate_b(gp_ctx* c) {
-  int rc = ensure_regime_b_buffers(c);
-  if (rc != GP_OK) return rc;
+  GP_TRY_RC(ensure_bplan(c));
+  const BPlan& p = *c->bplan;
   hipLaunchKernelGGL(b_tables_kernel, dim3(c->kl_blocks), dim3(256), 0, c->stream, c->mu, c->S, c->alpha, (long)c->N, (long)c->Np, c->Q,
-                     c->sf2, c->Vn, c->Wn, c->lnc2h, c->V2P, c->QB, c->WP, c->MUP);
-  GP_HIP(c, hipMemcpyAsync(c->alphaP, c->alpha, (size_t)c->Q * 8, hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(zpad_kernel, dim3((unsigned)(((long)c->Mp * (c->QB + 6) + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->M, c->Mp, c->Q, c->QB,
-                     c->ZP, c->Z1P, c->b_sym ? c->Z1S : nullptr, (c->QB + 1 + 3) / 4 * 4);
-  if (b_generic(c)) return run_le_generic(c);
-  switch (c->QB) {
-    case 4: launch_le<4, 2>(c); break;
-    case 6: launch_le<6, 2>(c); break;
-    case 8: launch_le<8, 2>(c); break;
-    case 10: launch_le<10, 2>(c); break;
-    case 12: launch_le<12, 2>(c); break;
-    case 14: launch_le<14, 2>(c); break;
-    case 16: launch_le<16, 2>(c); break;
-    case 24: launch_le<24, 2>(c); break;
-    case 32: launch_le<32, 1>(c); break;
-    case 52: launch_le<52, 1>(c); break;
-    default: launch_le<64, 1>(c); break;
+                     c->sf2, p.Vn, p.Wn, p.lnc2h, p.V2P, p.QB, p.WP, p.MUP);
+  GP_HIP(c, hipMemcpyAsync(p.alphaP, c->alpha, (size_t)c->Q * 8, hipMemcpyDeviceToDevice, c->stream));
+  hipLaunchKernelGGL(zpad_kernel, dim3((unsigned)(((long)c->Mp * (p.QB + 6) + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->M, c->Mp, c->Q, p.QB,
+                     p.ZP, p.Z1P, p.p2 == BP2::SYM ? p.Z1S.get() : nullptr, (p.QB + 1 + 3) / 4 * 4);
+  if (p.p1 == BP1::GENERIC) return run_le_generic(c);
+  switch (p.QB) {
+    case 4: launch_le<4, 2>(c, p); break;
+    case 6: launch_le<6, 2>(c, p); break;
+    case 8: launch_le<8, 2>(c, p); break;
+    case 10: launch_le<10, 2>(c, p); break;
+    case 12: launch_le<12, 2>(c, p); break;
+    case 14: launch_le<14, 2>(c, p); break;
+    case 16: launch_le<16, 2>(c, p); break;
+    case 24: launch_le<24, 2>(c, p); break;
+    case 32: launch_le<32, 1>(c, p); break;
+    case 52: launch_le<52, 1>(c, p); break;
+    default: launch_le<64, 1>(c, p); break;
   }
   GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 
 template <int QT>
-static void launch_pairs(gp_ctx* c, int S) {
-  hipLaunchKernelGGL((psi2_pairs_kernel<QT>), dim3(c->n_ptiles, S), dim3(256), 0, c->stream, c->LE, c->V2P, c->ZP, c->ptiles, (long)c->N,
-                     c->Mp, S, c->part, c->n_ptiles);
+static void launch_pairs(gp_ctx* c, const BPlan& p, int S) {
+  hipLaunchKernelGGL((psi2_pairs_kernel<QT>), dim3(p.n_ptiles, S), dim3(256), 0, c->stream, p.LE, p.V2P, p.ZP, p.ptiles, (long)c->N,
+                     c->Mp, S, c->part, p.n_ptiles);
 }
 
 template <int QT>
-static void launch_pairs_mfma(gp_ctx* c, int S) {
-  hipLaunchKernelGGL((psi2_pairs_mfma_kernel<QT>), dim3(c->n_tiles64, S), dim3(256), 0, c->stream, (const double*)c->LET, (const double*)c->V2P,
-                     (const double*)c->ZP, (const int*)c->tiles64, (long)c->N, c->Mp, S, c->part, c->n_tiles64);
+static void launch_pairs_mfma(gp_ctx* c, const BPlan& p, int S) {
+  hipLaunchKernelGGL((psi2_pairs_mfma_kernel<QT>), dim3(p.n_tiles64, S), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P,
+                     (const double*)p.ZP, (const int*)p.tiles64, (long)c->N, c->Mp, S, c->part, p.n_tiles64);
 }
 
 int run_phase1_b(gp_ctx* c) {
-  if (b_generic(c)) { GP_TRY_RC(run_phase1_b_generic(c)); return psi2_zero_pads(c); }
+  const BPlan& p = *c->bplan;
+  if (p.p1 == BP1::GENERIC) { GP_TRY_RC(run_phase1_b_generic(c)); return psi2_zero_pads(c); }
   // gp_last_timings' "p1 kernel" slot: in regime B the Psi2 pair kernel (the C tiles' p1_kernel8 launch recorded the events before)
   GP_EV(c, 10);
-  // the matrix-core pair kernel from the 24-wide latent tables on (17 <= Q): same-box, N = 1e5, M = 512, ms of this kernel at Q = 17 / 20 / 24:
-  // 21.4 / 21.4 / 21.8 against 30.5 for psi2_pairs_kernel<24>; at 16 columns the VALU kernel is still ahead (15.3 ms measured against ~17 by the instruction count)
-  if (c->b_mfma || c->QB == 24) {
+  if (p.p1 == BP1::PAIRS_MFMA) {
     // 64 x 64 tiles x n-slices: several rounds of workgroups over the 512 resident slots, >= 256 points per slice
-    int S = (int)std::max<long>(1, std::min<long>(32, std::max<long>((2048 + c->n_tiles64 - 1) / c->n_tiles64, c->N / 4096)));
+    int S = (int)std::max<long>(1, std::min<long>(32, std::max<long>((2048 + p.n_tiles64 - 1) / p.n_tiles64, c->N / 4096)));
     S = (int)std::min<long>(S, std::max<long>(1, c->N / 256));
-    switch (c->QB) {
-      case 24: launch_pairs_mfma<24>(c, S); break;
-      case 32: launch_pairs_mfma<32>(c, S); break;
-      case 52: launch_pairs_mfma<52>(c, S); break;
-      default: launch_pairs_mfma<64>(c, S); break;
+    switch (p.QB) {
+      case 24: launch_pairs_mfma<24>(c, p, S); break;
+      case 32: launch_pairs_mfma<32>(c, p, S); break;
+      case 52: launch_pairs_mfma<52>(c, p, S); break;
+      default: launch_pairs_mfma<64>(c, p, S); break;
     }
     GP_EV(c, 11);
     GP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(psi2_reduce64_kernel, dim3(c->n_tiles64), dim3(256), 0, c->stream, c->part, c->tiles64, c->n_tiles64, S, c->M, c->Mp, c->stats);
+    hipLaunchKernelGGL(psi2_reduce64_kernel, dim3(p.n_tiles64), dim3(256), 0, c->stream, c->part, p.tiles64, p.n_tiles64, S, c->M, c->Mp, c->stats);
     GP_HIP(c, hipGetLastError());
     return psi2_zero_pads(c);
   }
   // n-slices: many more workgroups than resident slots (256 CUs x 7) so the last round is short, >= 1024 points per slice
-  int S = (int)std::max<long>(1, std::min<long>(64, std::max<long>((4096 + c->n_ptiles - 1) / c->n_ptiles, c->N / 1024)));
+  int S = (int)std::max<long>(1, std::min<long>(64, std::max<long>((4096 + p.n_ptiles - 1) / p.n_ptiles, c->N / 1024)));
   S = (int)std::min<long>(S, c->N);
-  switch (c->QB) {
-    case 4: launch_pairs<4>(c, S); break;
-    case 6: launch_pairs<6>(c, S); break;
-    case 8: launch_pairs<8>(c, S); break;
-    case 10: launch_pairs<10>(c, S); break;
-    case 12: launch_pairs<12>(c, S); break;
-    case 14: launch_pairs<14>(c, S); break;
-    case 16: launch_pairs<16>(c, S); break;
-    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B pair kernel: no instantiation for the latent table width %d", c->QB);
+  switch (p.QB) {
+    case 4: launch_pairs<4>(c, p, S); break;
+    case 6: launch_pairs<6>(c, p, S); break;
+    case 8: launch_pairs<8>(c, p, S); break;
+    case 10: launch_pairs<10>(c, p, S); break;
+    case 12: launch_pairs<12>(c, p, S); break;
+    case 14: launch_pairs<14>(c, p, S); break;
+    case 16: launch_pairs<16>(c, p, S); break;
+    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B pair kernel: no instantiation for the latent table width %d", p.QB);
   }
   GP_EV(c, 11);
   GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(psi2_reduce_kernel, dim3(c->n_ptiles), dim3(256), 0, c->stream, c->part, c->ptiles, c->n_ptiles, S, c->M, c->Mp, c->stats);
+  hipLaunchKernelGGL(psi2_reduce_kernel, dim3(p.n_ptiles), dim3(256), 0, c->stream, c->part, p.ptiles, p.n_ptiles, S, c->M, c->Mp, c->stats);
   GP_HIP(c, hipGetLastError());
   return psi2_zero_pads(c);
 }
 
 template <int QT, bool KEEP>
-static void launch_cols(gp_ctx* c, const PB2Args& a) {     // (the Bbar argument: the row-interleaved table up to QT = 10, the plain one beyond)
-  const int nw = std::min(4, c->nslab);
-  hipLaunchKernelGGL((psi2_cols_kernel<QT, KEEP>), dim3(c->pb_blocks, (c->nslab + nw - 1) / nw), dim3(64 * nw), 0, c->stream, a, (const double*)c->ZP,
-                     (const double*)(cols_b4(QT) ? c->Bbar4 : c->Bbar), (const double*)c->LET, (const double*)c->V2P, (const double*)c->WP, (const double*)c->MUP,
-                     (const double*)c->alphaP);
+static void launch_cols(gp_ctx* c, const BPlan& p, const PB2Args& a) {     // (the Bbar argument: the row-interleaved table up to QT = 10, the plain one beyond)
+  const int nw = std::min(4, p.nslab);
+  hipLaunchKernelGGL((psi2_cols_kernel<QT, KEEP>), dim3(p.pb_blocks, (p.nslab + nw - 1) / nw), dim3(64 * nw), 0, c->stream, a, (const double*)p.ZP,
+                     (const double*)(cols_b4(QT) ? p.Bbar4 : c->Bbar), (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
+                     (const double*)p.alphaP);
 }
 
 template <int QT>
-static int launch_sym(gp_ctx* c, const PB2Args& a) {
+static int launch_sym(gp_ctx* c, const BPlan& p, const PB2Args& a) {
   const size_t smem = (size_t)c->Mp * sym_rs(QT) * sizeof(double);
   GP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(psi2_sym_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((psi2_sym_kernel<QT>), dim3(c->pb_blocks), dim3(64 * c->sym_nw), smem, c->stream, a, (const double*)c->ZP, (const double*)c->Z1S,
-                     (const double*)c->Bbar4, (const double*)c->LET, (const double*)c->V2P, (const double*)c->WP, (const double*)c->MUP,
-                     (const double*)c->alphaP, (const int*)c->sym_sched, c->sym_rounds);
+  hipLaunchKernelGGL((psi2_sym_kernel<QT>), dim3(p.pb_blocks), dim3(64 * p.sym_nw), smem, c->stream, a, (const double*)p.ZP, (const double*)p.Z1S,
+                     (const double*)p.Bbar4, (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
+                     (const double*)p.alphaP, (const int*)p.sym_sched, p.sym_rounds);
   return GP_OK;
 }
 
 int run_phase2_b(gp_ctx* c) {
-  if (c->b_tile) return run_phase2_b_tiles(c);
+  const BPlan& p = *c->bplan;
+  if (p.p2 == BP2::TILES) return run_phase2_b_tiles(c);
+  const bool gen = p.p2 == BP2::GENERIC;
   PB2Args a;
-  a.Wn = c->Wn; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
-  a.Gpart = c->Gpart; a.gapart2 = c->gapart2; a.gmu = c->gXmu; a.gS = c->gXs; a.pp = c->pp;
-  a.N = c->N; a.Np = c->Np; a.M = c->M; a.Mp = c->Mp; a.Q = c->Q; a.QB = c->QB; a.nslab = c->nslab; a.ppb = c->ppb; a.ngrp = (c->nslab + std::min(4, c->nslab) - 1) / std::min(4, c->nslab);
-  if (!b_generic(c)) hipLaunchKernelGGL(bbar_interleave_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 2048)), dim3(256), 0, c->stream,
-                                        (const double*)c->Bbar, c->Mp, c->Bbar4);
+  a.Wn = p.Wn; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
+  a.Gpart = p.Gpart; a.gapart2 = p.gapart2; a.gmu = c->gXmu; a.gS = c->gXs; a.pp = p.pp;
+  a.N = c->N; a.Np = c->Np; a.M = c->M; a.Mp = c->Mp; a.Q = c->Q; a.QB = p.QB; a.nslab = p.nslab; a.ppb = p.ppb; a.ngrp = (p.nslab + std::min(4, p.nslab) - 1) / std::min(4, p.nslab);
+  if (!gen) hipLaunchKernelGGL(bbar_interleave_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 2048)), dim3(256), 0, c->stream,
+                               (const double*)c->Bbar, c->Mp, p.Bbar4);
   GP_EV(c, 12);   // gp_last_timings' "p2 kernel" slot: in regime B the T_n = Bbar o psi2_n kernel
-  if (b_generic(c)) {
+  if (gen) {
     a.ngrp = 1;
     GP_TRY_RC(run_phase2_b_generic(c));
-  } else if (c->b_sym) {
-    a.ngrp = c->sym_nw;
-    int rc = c->QB == 4 ? launch_sym<4>(c, a) : c->QB == 6 ? launch_sym<6>(c, a) : c->QB == 8 ? launch_sym<8>(c, a) : c->QB == 10 ? launch_sym<10>(c, a) : launch_sym<12>(c, a);
+  } else if (p.p2 == BP2::SYM) {
+    a.ngrp = p.sym_nw;
+    int rc = p.QB == 4 ? launch_sym<4>(c, p, a) : p.QB == 6 ? launch_sym<6>(c, p, a) : p.QB == 8 ? launch_sym<8>(c, p, a) : p.QB == 10 ? launch_sym<10>(c, p, a) : launch_sym<12>(c, p, a);
     if (rc != GP_OK) return rc;
   } else
-  switch (c->QB) {
-    case 4: launch_cols<4, true>(c, a); break;
-    case 6: launch_cols<6, true>(c, a); break;
-    case 8: launch_cols<8, true>(c, a); break;
+  switch (p.QB) {
+    case 4: launch_cols<4, true>(c, p, a); break;
+    case 6: launch_cols<6, true>(c, p, a); break;
+    case 8: launch_cols<8, true>(c, p, a); break;
     // (the <10, false> form -- z re-read and grad_Z accumulated in memory per point -- is slower than <10, true>: same box, N = 1e5, M = 128: 2.75 -> 2.98 ms,
     // M = 1024 (5e4 points): 69.2 -> 69.9 ms; profiles/r06_gplvm_experiments.txt)
-    case 10: launch_cols<10, true>(c, a); break;
-    case 12: launch_cols<12, false>(c, a); break;
-    case 14: launch_cols<14, false>(c, a); break;
-    case 16: launch_cols<16, false>(c, a); break;
-    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B column kernel: no instantiation for the latent table width %d (Q = %d runs on psi2_tile_kernel)", c->QB, c->Q);
+    case 10: launch_cols<10, true>(c, p, a); break;
+    case 12: launch_cols<12, false>(c, p, a); break;
+    case 14: launch_cols<14, false>(c, p, a); break;
+    case 16: launch_cols<16, false>(c, p, a); break;
+    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B column kernel: no instantiation for the latent table width %d (Q = %d runs on psi2_tile_kernel)", p.QB, c->Q);
   }
   GP_EV(c, 13);
   GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(psi2_points_finish_kernel, dim3((unsigned)std::min<long>(c->pb_blocks, 256)), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(psi2_points_finish_kernel, dim3((unsigned)std::min<long>(p.pb_blocks, 256)), dim3(256), 0, c->stream, a);
   GP_HIP(c, hipGetLastError());
   const long MQ = (long)c->M * c->Q;
-  const int fin_blocks_g = (int)std::min<long>(c->pb_blocks, 256);
-  if (b_generic(c)) {
+  const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);      // psi2_points_finish_kernel's grid (one gapart2 row per workgroup)
+  if (gen) {
     // grad_Z's psi2 part is in c->grads already: only the alpha partials of the points' finish are left
-    hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, c->Gtmp, c->gapart2, 0, fin_blocks_g, MQ,
+    hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, p.Gtmp, p.gapart2, 0, fin_blocks, MQ,
                        c->Q, c->grads);
     GP_HIP(c, hipGetLastError());
     return GP_OK;
   }
-  const int S2 = std::max(1, std::min(64, c->pb_blocks / 16));
-  hipLaunchKernelGGL(pb2_reduce1_kernel, dim3((unsigned)((MQ + 63) / 64), S2), dim3(256), 0, c->stream, c->Gpart, c->pb_blocks, MQ, S2, c->Gtmp);
-  const int fin_blocks = (int)std::min<long>(c->pb_blocks, 256);      // psi2_points_finish_kernel's grid (one gapart2 row per workgroup)
-  hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, c->Gtmp,
-                     c->gapart2, S2, fin_blocks, MQ, c->Q, c->grads);
+  const int S2 = std::max(1, std::min(64, p.pb_blocks / 16));
+  hipLaunchKernelGGL(pb2_reduce1_kernel, dim3((unsigned)((MQ + 63) / 64), S2), dim3(256), 0, c->stream, p.Gpart, p.pb_blocks, MQ, S2, p.Gtmp);
+  hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, p.Gtmp,
+                     p.gapart2, S2, fin_blocks, MQ, c->Q, c->grads);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
 }

@@ -8,7 +8,7 @@
 //             grad_Z[m, q] += sum_p -alpha_q (z_mq r - t) + w_pq (2 mu_pq r - z_mq r - t)
 // No symmetry is used and every operand comes from memory: correct for every Q, M and N, at a fraction of the tuned kernels' rate (a latent space
 // that wide is outside BASELINE.json's configurations; the reference itself needs an (N, M, M, Q) tensor for it, partial_terms.py:273).
-#include "gp_common.h"
+#include "psi2_plan.h"
 #include "fexp.h"
 #include <algorithm>
 
@@ -125,36 +125,38 @@ __global__ void __launch_bounds__(256) psi2_gz_generic_kernel(const double* __re
 
 static unsigned grid_of(long n) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, 16384)); }
 
-bool b_generic(const gp_ctx* c) { return c->Q >= 64; }
-
 // the chunk buffers: T [P][M][M] (<= 64 MB, at least one point) and rt [P][M][Q + 1]
 static int ensure_generic(gp_ctx* c) {
-  if (c->gen_rt) return GP_OK;      // the group's last buffer: both or neither
+  BPlan& p = *c->bplan;
+  if (p.gen) return GP_OK;
   const long mm = (long)c->M * c->M;
-  c->gen_P = std::max<long>(1, std::min<long>(std::min<long>(c->N, 4096), (8L << 20) / std::max<long>(mm, 1)));
-  AllocGroup A(c);
-  A(c->gen_T, (size_t)c->gen_P * mm, DA_RAW);
-  A(c->gen_rt, (size_t)c->gen_P * c->M * (c->Q + 1), DA_RAW);
-  GP_TRY_RC(A.commit());
+  auto g = std::make_unique<BGeneric>();
+  g->P = std::max<long>(1, std::min<long>(std::min<long>(c->N, 4096), (8L << 20) / std::max<long>(mm, 1)));
+  GP_TRY_RC(g->T.alloc(c, (size_t)g->P * mm, DA_RAW));
+  GP_TRY_RC(g->rt.alloc(c, (size_t)g->P * c->M * (c->Q + 1), DA_RAW));
+  p.gen = std::move(g);
   return GP_OK;
 }
 
 int run_le_generic(gp_ctx* c) {
-  hipLaunchKernelGGL(b_le_generic_kernel, dim3(grid_of(c->Np * c->Mp)), dim3(256), 0, c->stream, (const double*)c->MUP, (const double*)c->WP,
-                     (const double*)c->V2P, (const double*)c->lnc2h, (const double*)c->ZP, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q, c->LE, c->LET);
+  const BPlan& p = *c->bplan;
+  hipLaunchKernelGGL(b_le_generic_kernel, dim3(grid_of(c->Np * c->Mp)), dim3(256), 0, c->stream, (const double*)p.MUP, (const double*)p.WP,
+                     (const double*)p.V2P, (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q, p.LE, p.LET);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 
 int run_phase1_b_generic(gp_ctx* c) {
   GP_TRY_RC(ensure_generic(c));
+  const BPlan& p = *c->bplan;
+  const BGeneric& g = *p.gen;
   const long mm = (long)c->M * c->M;
   GP_EV(c, 10);
-  for (long n0 = 0; n0 < c->N; n0 += c->gen_P) {
-    const long cnt = std::min<long>(c->gen_P, c->N - n0);
-    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)c->LET, (const double*)c->V2P, (const double*)c->ZP,
-                       (const double*)nullptr, n0, cnt, c->M, c->Mp, c->Q, c->gen_T);
-    hipLaunchKernelGGL(psi2_sum_generic_kernel, dim3(grid_of(mm)), dim3(256), 0, c->stream, (const double*)c->gen_T, cnt, c->M, c->Mp, n0 == 0 ? 1 : 0, c->stats);
+  for (long n0 = 0; n0 < c->N; n0 += g.P) {
+    const long cnt = std::min<long>(g.P, c->N - n0);
+    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
+                       (const double*)nullptr, n0, cnt, c->M, c->Mp, c->Q, g.T);
+    hipLaunchKernelGGL(psi2_sum_generic_kernel, dim3(grid_of(mm)), dim3(256), 0, c->stream, (const double*)g.T, cnt, c->M, c->Mp, n0 == 0 ? 1 : 0, c->stats);
   }
   GP_EV(c, 11);
   GP_HIP(c, hipGetLastError());
@@ -164,18 +166,20 @@ int run_phase1_b_generic(gp_ctx* c) {
 // fills pp (one group: ngrp = 1, row width 3 QB + 1 with QB = Q) and adds the psi2 part of grad_Z to c->grads; the caller finishes the points
 int run_phase2_b_generic(gp_ctx* c) {
   GP_TRY_RC(ensure_generic(c));
+  const BPlan& p = *c->bplan;
+  const BGeneric& g = *p.gen;
   const long mm = (long)c->M * c->M;
   const int Q = c->Q, M = c->M;
-  for (long n0 = 0; n0 < c->N; n0 += c->gen_P) {
-    const long cnt = std::min<long>(c->gen_P, c->N - n0);
-    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)c->LET, (const double*)c->V2P, (const double*)c->ZP,
-                       (const double*)c->Bbar, n0, cnt, M, c->Mp, Q, c->gen_T);
-    hipLaunchKernelGGL(psi2_rt_generic_kernel, dim3(grid_of(cnt * M * (Q + 1))), dim3(256), 0, c->stream, (const double*)c->gen_T, (const double*)c->ZP, cnt, M, Q,
-                       c->gen_rt);
-    hipLaunchKernelGGL(psi2_pp_generic_kernel, dim3(grid_of(cnt * (3 * Q + 1))), dim3(256), 0, c->stream, (const double*)c->gen_rt, (const double*)c->ZP, n0, cnt, M, Q,
-                       (long)c->Np, c->pp);
-    hipLaunchKernelGGL(psi2_gz_generic_kernel, dim3(grid_of((long)M * Q)), dim3(256), 0, c->stream, (const double*)c->gen_rt, (const double*)c->ZP,
-                       (const double*)c->WP, (const double*)c->MUP, (const double*)c->alphaP, n0, cnt, M, Q, c->grads);
+  for (long n0 = 0; n0 < c->N; n0 += g.P) {
+    const long cnt = std::min<long>(g.P, c->N - n0);
+    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
+                       (const double*)c->Bbar, n0, cnt, M, c->Mp, Q, g.T);
+    hipLaunchKernelGGL(psi2_rt_generic_kernel, dim3(grid_of(cnt * M * (Q + 1))), dim3(256), 0, c->stream, (const double*)g.T, (const double*)p.ZP, cnt, M, Q,
+                       g.rt);
+    hipLaunchKernelGGL(psi2_pp_generic_kernel, dim3(grid_of(cnt * (3 * Q + 1))), dim3(256), 0, c->stream, (const double*)g.rt, (const double*)p.ZP, n0, cnt, M, Q,
+                       (long)c->Np, p.pp);
+    hipLaunchKernelGGL(psi2_gz_generic_kernel, dim3(grid_of((long)M * Q)), dim3(256), 0, c->stream, (const double*)g.rt, (const double*)p.ZP,
+                       (const double*)p.WP, (const double*)p.MUP, (const double*)p.alphaP, n0, cnt, M, Q, c->grads);
   }
   GP_HIP(c, hipGetLastError());
   return GP_OK;

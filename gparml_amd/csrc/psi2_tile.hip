@@ -17,7 +17,7 @@
 // summed with a reduce-scatter over the four lanes (each lane ends up owning ONE column and every fourth q), and the per-point
 // sums are reduce-scattered over sixteen lanes the same way (lane q ends up holding s_q): ~1 add per value instead of log2(lanes).
 // Workgroup = 8 waves = two point streams (even / odd points of the slice) of four waves; LDS: Z_I, Z_J, two T tiles, tables.
-#include "gp_common.h"
+#include "psi2_plan.h"
 #include "fexp.h"
 #include "quad_mma.h"
 #include "lane_reduce.h"
@@ -444,27 +444,12 @@ static int launch_tile(gp_ctx* c, const PT2Args& a) {
   return GP_OK;
 }
 
-// The tile-pair phase 2 applies when a compiled width has room for the column of ones (Q <= 63; r04: the 64-wide instantiation, 230 VGPRs, 156 KB of LDS -- Q = 60, M = 1024, 2e4 points: 89 ms against 161 for
-// psi2_cols_mfma_kernel) and is used from Q = 17 on: the per-point
-// folds and sums do not shrink with Q, so below that the VALU kernels of psi2.hip are faster (same-box, ms of the phase-2 kernel per 1e5
-// points: Q = 4, M = 512: 21.7 (cols) vs 41.8 here; Q = 10, M = 512: 31.7 (psi2_sym) vs 40.5; Q = 16, M = 512: 47.2 vs 56.5;
-// Q = 20, M = 256: 23.1 vs 17.0; Q = 24, M = 512: 93.9 vs 69.7; Q = 50, M = 1024, 2e4 points: 96.4 (psi2_cols_mfma) vs 75.8).
-// GPARML_B_PHASE2=tiles forces this kernel below Q = 17 as well (tests: every compiled width); =cols keeps the VALU kernels where they exist (Q <= 16).
-// Decided once per context (c->b_tile).  (r06: the column kernels' instantiations for Q >= 17 and psi2_cols_mfma_kernel -- reachable only through =cols,
-// 28-228 B of scratch per lane -- are gone; Q >= 64 runs on psi2_generic.hip.)
-bool pt2_applicable(const gp_ctx* c, bool sym_available) {
-  static const int mode = [] { const char* e = getenv("GPARML_B_PHASE2"); return !e ? 0 : (std::string(e) == "cols" ? 1 : (std::string(e) == "tiles" ? 2 : 0)); }();
-  (void)sym_available;
-  if (pt2_width(c->Q) == 0) return false;
-  if (c->Q >= 17) return true;
-  return mode == 2;
-}
-
 int run_phase2_b_tiles(gp_ctx* c) {
-  const int T = c->n_tiles64, Q = c->Q, PW = 3 * Q + 1;
+  BPlan& p = *c->bplan;
+  const int T = p.n_tiles64, Q = c->Q, PW = 3 * Q + 1;
   const long N = c->N;
   // points per launch: the per-tile sums of a launch live in pp [T][PW][CH] (<= 1.5 GB)
-  if (!c->Gt) {      // the group's last buffer: both or neither
+  if (!p.tiles) {
     long ch = std::min<long>(N, 8192);
     while (ch > 512 && (double)T * PW * ch * 8.0 > 1.5e9) ch /= 2;
     // slices: fill the 256 CUs (one 512-thread workgroup each) in whole rounds, >= 16 points per slice
@@ -475,29 +460,30 @@ int run_phase2_b_tiles(gp_ctx* c) {
     }
     // Neither buffer needs zeroing: the first launch of an evaluation (accumulate = 0) writes every pp[t][i][k < count] and all T * S
     // workgroups store their Gt slot unconditionally.
-    AllocGroup A(c);
-    A(c->ppt, (size_t)T * PW * ch, DA_RAW);
-    A(c->Gt, (size_t)bestS * T * 2 * 64 * Q, DA_RAW);
-    GP_TRY_RC(A.commit());
-    c->b_ch = ch; c->b_S = bestS;
+    auto t = std::make_unique<BTiles>();
+    GP_TRY_RC(t->ppt.alloc(c, (size_t)T * PW * ch, DA_RAW));
+    GP_TRY_RC(t->Gt.alloc(c, (size_t)bestS * T * 2 * 64 * Q, DA_RAW));
+    t->ch = ch; t->S = bestS;
+    p.tiles = std::move(t);
   }
+  const BTiles& tb = *p.tiles;
   PT2Args a;
-  a.ZP = c->ZP; a.Bbar = c->Bbar; a.LEA = c->LET; a.V2P = c->V2P; a.WP = c->WP; a.MUP = c->MUP; a.alphaP = c->alphaP;
-  a.tiles = c->tiles64; a.Gt = c->Gt; a.pp = c->ppt; a.CH = c->b_ch; a.Np = c->Np; a.Mp = c->Mp; a.M = c->M; a.Q = Q; a.QB = c->QB; a.T = T; a.S = c->b_S;
+  a.ZP = p.ZP; a.Bbar = c->Bbar; a.LEA = p.LET; a.V2P = p.V2P; a.WP = p.WP; a.MUP = p.MUP; a.alphaP = p.alphaP;
+  a.tiles = p.tiles64; a.Gt = tb.Gt; a.pp = tb.ppt; a.CH = tb.ch; a.Np = c->Np; a.Mp = c->Mp; a.M = c->M; a.Q = Q; a.QB = p.QB; a.T = T; a.S = tb.S;
   a.dbg = nullptr;
 #ifdef GPARML_TILE_TIMING
   static long long* dbg = nullptr;
-  const size_t ndbg = (size_t)c->b_S * T * 64;
+  const size_t ndbg = (size_t)tb.S * T * 64;
   if (!dbg) GP_HIP(c, hipMalloc((void**)&dbg, ndbg * sizeof(long long)));
   a.dbg = dbg;
 #endif
   PT2Fin f;
-  f.pp = c->ppt; f.Wn = c->Wn; f.mu = c->mu; f.S = c->S; f.alpha = c->alpha; f.gmu = c->gXmu; f.gS = c->gXs; f.gapart2 = c->gapart2; f.CH = c->b_ch; f.Q = Q;
-  const int fin_blocks = (int)std::min<long>(c->pb_blocks, 256);
+  f.pp = tb.ppt; f.Wn = p.Wn; f.mu = c->mu; f.S = c->S; f.alpha = c->alpha; f.gmu = c->gXmu; f.gS = c->gXs; f.gapart2 = p.gapart2; f.CH = tb.ch; f.Q = Q;
+  const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);
   GP_EV(c, 12);
   int k = 0;
-  for (long n0 = 0; n0 < N; n0 += c->b_ch, ++k) {
-    a.n0 = n0; a.n1 = std::min(N, n0 + c->b_ch); a.accumulate = k > 0 ? 1 : 0;
+  for (long n0 = 0; n0 < N; n0 += tb.ch, ++k) {
+    a.n0 = n0; a.n1 = std::min(N, n0 + tb.ch); a.accumulate = k > 0 ? 1 : 0;
     int rc = GP_OK;
     switch (pt2_width(Q)) {
       case 4: rc = launch_tile<4>(c, a); break;
@@ -513,8 +499,8 @@ int run_phase2_b_tiles(gp_ctx* c) {
     if (rc != GP_OK) return rc;
     GP_HIP(c, hipGetLastError());
     const long cnt = a.n1 - a.n0;
-    hipLaunchKernelGGL(pt2_sum_tiles_kernel, dim3((unsigned)std::min<long>(((long)PW * cnt + 255) / 256, 4096)), dim3(256), 0, c->stream, c->ppt, T, PW,
-                       c->b_ch, cnt);
+    hipLaunchKernelGGL(pt2_sum_tiles_kernel, dim3((unsigned)std::min<long>(((long)PW * cnt + 255) / 256, 4096)), dim3(256), 0, c->stream, tb.ppt, T, PW,
+                       tb.ch, cnt);
     f.n0 = a.n0; f.n1 = a.n1; f.accumulate = a.accumulate;
     hipLaunchKernelGGL(pt2_points_finish_kernel, dim3(fin_blocks), dim3(256), 0, c->stream, f);
     GP_HIP(c, hipGetLastError());
@@ -535,8 +521,8 @@ int run_phase2_b_tiles(gp_ctx* c) {
   }
 #endif
   const long MQ = (long)c->M * Q;
-  hipLaunchKernelGGL(pt2_gz_reduce_kernel, dim3((unsigned)std::min<long>((MQ + Q + 255) / 256, 2048)), dim3(256), 0, c->stream, (const double*)c->Gt,
-                     (const int*)c->tiles64, T, c->b_S, c->M, Q, (const double*)c->gapart2, fin_blocks, c->grads);
+  hipLaunchKernelGGL(pt2_gz_reduce_kernel, dim3((unsigned)std::min<long>((MQ + Q + 255) / 256, 2048)), dim3(256), 0, c->stream, (const double*)tb.Gt,
+                     (const int*)p.tiles64, T, tb.S, c->M, Q, (const double*)p.gapart2, fin_blocks, c->grads);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
 }

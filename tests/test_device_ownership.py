@@ -44,17 +44,52 @@ def test_only_the_owner_allocates_device_memory():
     assert RAW_ALLOC.search(_code(os.path.join(CSRC, OWNER)))
 
 
+OWNED = re.compile(r'(?:DevBuf|PinnedBuf)<[^>]*>\s+([^;(]*);')
+PLANNED = re.compile(r'unique_ptr<[^;]*>\s+(\w+);')
+# what this context keeps itself: every feature that only runs on demand owns its buffers in a plan of its own
+GP_CTX_MAX_BUFFERS = 52
+
+
+def _owned(body):
+    """The DevBuf / PinnedBuf members a struct body declares, every declarator of each declaration."""
+    return [re.match(r'\s*(\w+)', d).group(1) for decl in OWNED.findall(body) for d in decl.split(',')]
+
+
+def _owner_structs():
+    """gp_ctx and every struct of csrc/ that owns device memory (a DevBuf or PinnedBuf member): the plans and their groups."""
+    owners = {}
+    for f in sorted(glob.glob(os.path.join(CSRC, '*.hip')) + glob.glob(os.path.join(CSRC, '*.h'))):
+        code = _code(f)
+        for m in re.finditer(r'\bstruct\s+(\w+)\s*\{', code):
+            body = _body(code[m.start():], m.group(0))
+            if m.group(1) == 'gp_ctx' or OWNED.search(body):
+                assert m.group(1) not in owners, 'two owner structs named ' + m.group(1)
+                owners[m.group(1)] = body
+    return owners
+
+
 def test_gp_destroy_names_no_buffer():
-    ctx = _body(_code(os.path.join(CSRC, 'gp_common.h')), 'struct gp_ctx {')
-    owned = re.findall(r'(?:DevBuf|PinnedBuf)<[^>]*>\s+(\w+)', ctx) + re.findall(r'unique_ptr<[^;]*>\s+(\w+);', ctx)
+    owners = _owner_structs()
+    ctx = owners['gp_ctx']
+    owned = [n for body in owners.values() for n in _owned(body) + PLANNED.findall(body)]
     assert len(owned) > 60 and 'Kaug' in owned and 'p1plan' in owned and 'h_out' in owned, owned
-    # every pointer-typed field of the context is an owner (the RCCL communicator and the HIP events are not memory)
-    raw = [m for m in re.findall(r'^\s*[\w:]+\s*\*\s*(\w+)', ctx, re.M) if m != 'comm']
-    assert not raw, 'raw pointer fields in gp_ctx: %s' % raw
+    # the plans of the on-demand families (regime B, predict, infer), each held by the context through one owner
+    for plan, member, field in (('BPlan', 'LET', 'bplan'), ('PredPlan', 'P1', 'pred'), ('InferPlan', 'Gf', 'infer')):
+        assert plan in owners and member in _owned(owners[plan]), (plan, member)
+        assert field in PLANNED.findall(ctx), field
+    # every pointer-typed field of the context and of the plans is an owner (the RCCL communicator and the HIP events are not memory)
+    for name, body in owners.items():
+        raw = [m for m in re.findall(r'^\s*[\w:]+\s*\*\s*(\w+)', body, re.M) if not (name == 'gp_ctx' and m == 'comm')]
+        assert not raw, 'raw pointer fields in %s: %s' % (name, raw)
     body = _body(_code(os.path.join(CSRC, 'api.hip')), 'extern "C" int gp_destroy(gp_ctx* c)')
     named = sorted(set(re.findall(r'c->(\w+)', body)) & set(owned))
     assert not named, 'gp_destroy frees buffers by name: %s' % named
     assert 'delete c' in body
+
+
+def test_gp_ctx_holds_no_feature_buffers():
+    n = len(_owned(_owner_structs()['gp_ctx']))
+    assert n <= GP_CTX_MAX_BUFFERS, 'gp_ctx owns %d device buffers (at most %d): give a new feature a plan of its own' % (n, GP_CTX_MAX_BUFFERS)
 
 
 def test_alloc_fail_after_is_a_known_option():

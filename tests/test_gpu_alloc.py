@@ -1,8 +1,9 @@
 """Device memory of contexts that are created, used and destroyed many times (the optimisers, the fuzz tests, long-lived C consumers): every
 buffer has one owner (csrc/devbuf.h), so destroying a context frees all of it, and an allocation that fails part way through gp_create or through
 a lazily allocated group leaves nothing behind.  The failures are injected with gp_debug_set_option("alloc_fail_after", k): the k-th
-allocation after the call fails with GP_ERR_HIP.  A context whose allocation was made to fail is only destroyed, never evaluated again.
-Each step runs in a child process of its own."""
+allocation after the call fails with GP_ERR_HIP.  A lazily allocated group is published whole or not at all, so a context whose allocation was made
+to fail stays usable: the same call on it, with nothing armed, gives what it gives on a fresh context, bit for bit.  Each step runs in a child process
+of its own."""
 import os
 import subprocess
 import sys
@@ -103,20 +104,29 @@ print('CREATE_OK', k - 1, 'failures', flush=True)
 
 LAZY = PRELUDE + r'''
 def armed(make, call, what):
-    """For k = 1, 2, ...: a fresh context from make(), the k-th allocation of call(e) made to fail, the context destroyed; until call succeeds."""
+    """For k = 1, 2, ...: a fresh context from make(), the k-th allocation of call(e) made to fail; then, with nothing armed, call(e) again on the
+    same context must return what call returns on a fresh context, bit for bit; then the context is destroyed.  Until call succeeds at once."""
+    e = make()
+    ref = call(e)
+    e.close()
     base = free_now()
     k = 1
     while True:
         e = make()
         assert lib.gp_debug_set_option(b'alloc_fail_after', k) == 0
         try:
-            call(e)
+            out = call(e)
             ok = True
         except _lib.GparmlHipError as err:
             ok = False
             assert 'injected' in str(err), (what, k, str(err))
         finally:
             lib.gp_debug_set_option(b'alloc_fail_after', 0)
+        if not ok:
+            out = call(e)
+        assert len(out) == len(ref)
+        for i, (a, b) in enumerate(zip(ref, out)):
+            assert np.array_equal(a, b), (what, 'differs from a fresh context after the failed allocation', k, i)
         e.close()
         free = free_now(base)
         assert abs(free - base) <= SLACK, (what, 'leaks after the failed allocation', k, (free - base) / 2**20)
@@ -129,9 +139,13 @@ def armed(make, call, what):
 # the first phase 1 of a regime-B context: its tables and buffers (LE alone is 1e5 x 512 x 8 B = 410 MB) and the partial buffer's growth
 def make_b():
     return engine(100000, 5, 512, 10, 'B')[0]
-assert armed(make_b, lambda e: e.phase1(), 'phase1_regime_B') >= 10
+def phase1_stats(e):
+    """phase 1, then the packed statistics: Psi2 | C | scalars"""
+    e.phase1()
+    return e.download('PSI2_SUM'), e.download('PSI1TY'), e.download('SCALARS')
+assert armed(make_b, phase1_stats, 'phase1_regime_B') >= 10
 
-# the first prediction at uncertain inputs, after one evaluation: both groups of chunk buffers (16384-point chunks: pr_G is 100 MB)
+# the first prediction at uncertain inputs, after one evaluation: both groups of chunk buffers (16384-point chunks: the product buffer alone is 100 MB)
 X = np.random.RandomState(3).randn(40, 5)
 assert lib.gp_debug_set_option(b'predict_rows', 16384) == 0
 def make_p():
@@ -142,6 +156,15 @@ try:
     assert armed(make_p, lambda e: e.predict(X, np.full(X.shape, 0.2)), 'predict_uncertain') >= 10
 finally:
     lib.gp_debug_set_option(b'predict_rows', 0)
+
+# the first latent inference on a trained regime-A context: its three groups (model tables, chunk buffers, optimiser state; 16384-row chunks: V and
+# LEA are 67 MB each)
+Yi, Xi, Si = np.random.RandomState(4).randn(40, 10), np.random.RandomState(5).randn(40, 5), np.full((40, 5), 0.2)
+assert lib.gp_debug_set_option(b'infer_rows', 16384) == 0
+try:
+    assert armed(make_p, lambda e: e.infer_latent(Yi, Xi, Si, max_iters=2), 'infer_latent') >= 20
+finally:
+    lib.gp_debug_set_option(b'infer_rows', 0)
 print('LAZY_OK', flush=True)
 '''
 
