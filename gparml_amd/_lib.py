@@ -14,7 +14,7 @@ GP_COMM_ID_BYTES = 128
 # gp_download selectors (include/gparml_hip.h)
 ARR = dict(KMM=0, KMM_INV=1, PSI1=2, PSI2_SUM=3, PSI1TY=4, KMM_PLUS_OP_INV=5, DF_DKMM=6, DF_DPSI1TY=7, DF_DPSI2=8,
            GRAD_X_MU=9, GRAD_X_S=10, SCALARS=11, PSI2_POINTS=12, DKMM_DZ=13, DPSI1TY_DZ=14, DPSI2_DZ=15, DKMM_DALPHA=16,
-           DPSI1TY_DALPHA=17, DPSI2_DALPHA=18, X_MU_TRIAL=19, X_S_TRIAL=20, GRAD_LATEST=21)
+           DPSI1TY_DALPHA=17, DPSI2_DALPHA=18, X_MU_TRIAL=19, X_S_TRIAL=20, GRAD_LATEST=21, X_MU=22)
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
@@ -60,6 +60,7 @@ SIGNATURES = {
     'gp_predict': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     'gp_infer_objective': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_infer_latent': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
+    'gp_kmeans_accumulate': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, ctypes.POINTER(_i64), _dp, _ip]),
     'gp_last_timings': (ctypes.c_int, [_vp, _dp]),
     'gp_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'gp_i8_status': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), _dp, _dp, _dp, ctypes.POINTER(_i64)]),

@@ -628,6 +628,9 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
     case GP_ARR_GRAD_X_S: return download_matrix(c, c->gXs, Q, N, Q, dst, n);
     case GP_ARR_X_MU_TRIAL: return download_matrix(c, c->mu, Q, N, Q, dst, n);
     case GP_ARR_X_S_TRIAL: return download_matrix(c, c->S, Q, N, Q, dst, n);
+    case GP_ARR_X_MU:
+      if (!c->have_data) return fail(c, GP_ERR_STATE, "GP_ARR_X_MU before gp_upload_shard");
+      return download_matrix(c, c->Xmu, Q, N, Q, dst, n);
     case GP_ARR_GRAD_LATEST: {
       if (c->state < 3 || !c->want_emb) return fail(c, GP_ERR_STATE, "GP_ARR_GRAD_LATEST needs gp_phase2(ctx, 1) first");
       if (n != 2 * N * Q) return fail(c, GP_ERR_BAD_ARG, "GP_ARR_GRAD_LATEST wants %ld doubles", 2 * N * Q);
@@ -756,6 +759,31 @@ extern "C" int gp_infer_latent(gp_ctx* c, int64_t n, const double* Y, const int*
   GP_TRY(infer_check(c, "gp_infer_latent", n, Y, cols, n_cols, X_mu, X_S, xs_is_raw, &nothing));
   if (nothing) return GP_OK;
   return run_infer(c, 1, (long)n, Y, cols, n_cols, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
+}
+
+// One Lloyd assignment pass (csrc/kmeans.hip).  Nothing of the evaluation is read or written: only the resident X_mu (X == NULL) and the plan's buffers.
+extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2,
+                                    int32_t* labels) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: n must be >= 0");
+  if (K < 1) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: K must be >= 1");
+  if (!centres) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: centres is NULL");
+  if (!X) {
+    if (!c->have_data) return fail(c, GP_ERR_STATE, "gp_kmeans_accumulate: X is NULL (the resident X_mu) before gp_upload_shard");
+    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: X is NULL (the resident X_mu): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
+  }
+  const size_t kq = (size_t)K * c->Q, nq = (size_t)n * c->Q;
+  for (size_t i = 0; i < kq; ++i) if (!std::isfinite(centres[i])) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: centres is not finite");
+  for (size_t i = 0; X && i < nq; ++i) if (!std::isfinite(X[i])) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: X is not finite");
+  if (n == 0) {
+    if (sums) std::fill(sums, sums + kq, 0.0);
+    if (counts) std::fill(counts, counts + K, (int64_t)0);
+    if (dist2) dist2[0] = dist2[1] = 0.0;
+    return GP_OK;
+  }
+  if (!sums && !counts && !dist2 && !labels) return GP_OK;
+  GP_HIP(c, hipSetDevice(c->device));
+  return run_kmeans(c, (long)n, X, K, centres, sums, counts, dist2, labels);
 }
 
 // ---- final gradients ---------------------------------------------------------------------------------------------

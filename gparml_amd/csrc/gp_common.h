@@ -58,11 +58,13 @@ struct I8Plan;     // p1i8.hip
 struct BPlan;      // psi2_plan.h
 struct PredPlan;   // predict.hip
 struct InferPlan;  // infer.hip
+struct KmPlan;     // kmeans.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
 struct PredPlanDelete { void operator()(PredPlan* p) const; };
 struct InferPlanDelete { void operator()(InferPlan* p) const; };
+struct KmPlanDelete { void operator()(KmPlan* p) const; };
 
 }  // namespace gp
 
@@ -164,6 +166,7 @@ struct gp_ctx {
   bool pred_ok = false;       // the global step's Inv / Linv / E describe the statistics buffer as it is now (cleared whenever it or Z changes)
   std::unique_ptr<gp::PredPlan, gp::PredPlanDelete> pred;     // gp_predict's buffers (predict.hip), built on first use
   std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip), built on first use
+  std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip), built on first use
   // CG vectors (resident): grad_latest/new/old (2,N,Q) each
   gp::DevBuf<double> g_latest;
   gp::DevBuf<double> g_new;
@@ -222,6 +225,9 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
 extern std::atomic<int> g_opt_inf_rows;
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
+// kmeans.hip
+extern std::atomic<int> g_opt_km_rows;
+int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip

@@ -883,8 +883,9 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "poison_alloc")) { g_opt_poison.store(value ? 1 : 0); return GP_OK; }
   if (!std::strcmp(name, "predict_rows")) { g_opt_pred_rows.store(std::max(0, value)); return GP_OK; }
   if (!std::strcmp(name, "infer_rows")) { g_opt_inf_rows.store(std::max(0, value)); return GP_OK; }
+  if (!std::strcmp(name, "kmeans_rows")) { g_opt_km_rows.store(std::max(0, value)); return GP_OK; }
   if (!std::strcmp(name, "alloc_fail_after")) { g_alloc_fail_after.store(std::max(0, value)); return GP_OK; }
-  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (dd_kipsi2, refine_E, p1_i8, gs_tail, i8_guard_strict, xtx_tri, residual_dd, gemm_big, trtri_rec, gs_i8, poison_alloc, predict_rows, infer_rows, alloc_fail_after)", name);
+  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (dd_kipsi2, refine_E, p1_i8, gs_tail, i8_guard_strict, xtx_tri, residual_dd, gemm_big, trtri_rec, gs_i8, poison_alloc, predict_rows, infer_rows, kmeans_rows, alloc_fail_after)", name);
 }
 
 extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet) {

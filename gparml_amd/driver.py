@@ -75,11 +75,35 @@ def transform_grad_vec(mask, x):
     return out
 
 
-def init_statistics(map_reduce, options):
+def _device_kmeans(map_reduce, options, names, engine_class=None):
+    """options['init_Z'] == 'device': k-means over the embeddings of ALL shards (gparml_amd.init.kmeans), the assignment passes on the GPUs the
+    shards are spread over -- one temporary engine per device, the embeddings passed as host rows.  The seeds are drawn from numpy's global
+    stream."""
+    from . import init
+    if engine_class is None:
+        from .engine import ShardEngine as engine_class
+    devices = map_reduce._devices(options) if hasattr(map_reduce, '_devices') else [int(options.get('device', 0))]
+    engines, parts = {}, []
+    try:
+        for i, name in enumerate(names):
+            dev = devices[i % len(devices)]                                              # where the shard will live (gpu_MapReduce._device_of)
+            if dev not in engines:
+                engines[dev] = engine_class(1, 1, 1, options['Q'], device=dev)           # K is free of the context's M
+            parts.append(init.HostRows(engines[dev], map_reduce.load(options['embeddings'] + '/' + name + '.embedding.npy')))
+        return init.kmeans(parts, options['M'], restarts=options.get('init_Z_restarts', 1))[0]
+    finally:
+        for e in engines.values():
+            e.close()
+
+
+def init_statistics(map_reduce, options, engine_class=None):
     """parallel_GPLVM.init_statistics (:134-214): the names the backends pass around, the initial global statistics -- inducing points
     Z by k-means over the first shards' embeddings (scipy.cluster.vq.kmeans, topped up with the first embeddings when k-means returns
     fewer than M centres) plus 0.05 * randn, sf2 = alpha = beta = 1 (:179-194), or the ``*_f.npy`` files of a previous run with
-    ``options['load']`` (:195-200) -- and the optimisation bounds.  Returns (options, global_statistics).  One-off host work."""
+    ``options['load']`` (:195-200) -- and the optimisation bounds.  Returns (options, global_statistics).  One-off host work, unless
+    ``options['init_Z'] == 'device'``: the k-means then runs on the GPUs over the embeddings of all shards (_device_kmeans; hours of host
+    time at N = 1e6, M = 512 otherwise), with the same top-up and noise.  ``engine_class`` (tests only) replaces
+    ShardEngine there."""
     M, Q = options['M'], options['Q']
     Driver(options, map_reduce)          # fills the *_names entries and the flat bounds exactly as the evaluations expect them
     if not options.get('load'):
@@ -91,8 +115,11 @@ def init_statistics(map_reduce, options):
             embeddings = numpy.concatenate((embeddings, map_reduce.load(options['embeddings'] + '/' + names[idx] + '.embedding.npy')))
         if embeddings.shape[1] != Q:
             raise Exception('Given Q does not equal existing embedding data dimensions!')
-        import scipy.cluster.vq as cl
-        Z = cl.kmeans(embeddings, M)[0]                                                 # :180-181
+        if options.get('init_Z') == 'device':
+            Z = _device_kmeans(map_reduce, options, names, engine_class)
+        else:
+            import scipy.cluster.vq as cl
+            Z = cl.kmeans(embeddings, M)[0]                                             # :180-181
         missing = M - Z.shape[0]
         if missing > 0:
             Z = numpy.concatenate((Z, embeddings[:missing]))                            # :183-185

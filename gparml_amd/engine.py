@@ -308,6 +308,39 @@ class ShardEngine(object):
                                           it.ctypes.data_as(_lib._ip)), 'gp_infer_latent')
         return X_mu, X_S, L, it
 
+    # ---- initialisation of the inducing points (gp_kmeans_accumulate) -----------------------------------------
+    def kmeans_accumulate(self, centres, X=None, want_labels=False):
+        """One Lloyd assignment pass of k-means (the vq + update_cluster_means pair inside scipy.cluster.vq.kmeans, parallel_GPLVM.py:179-186) over
+        the host rows ``X`` (n, Q), or over the resident X_mu of this engine (``X`` None), against ``centres`` (K, Q), any K >= 1.  Returns
+        (sums (K, Q), counts (K,) int64, dist2 = [sum d^2, sum d], labels (n,) int32 or None): per centre the sum and the number of the rows
+        nearest to it (ties: the lowest index), and the summed squared / plain Euclidean distances.  Shards add; gparml_amd.init.kmeans drives the
+        loop.  The evaluation state is left untouched."""
+        centres = np.atleast_2d(np.asarray(centres, dtype=np.float64))
+        assert centres.ndim == 2 and centres.shape[1] == self.Q, 'centres shape %s: (K, %d) expected' % (centres.shape, self.Q)
+        K = centres.shape[0]
+        centres, pc = _lib.as_c(centres)
+        px, n = None, self.N_s
+        if X is not None:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            assert X.ndim == 2 and X.shape[1] == self.Q, 'X shape %s: (n, %d) expected' % (X.shape, self.Q)
+            n = X.shape[0]
+            X, px = _lib.as_c(X)
+        sums, counts, dist2 = np.empty((K, self.Q)), np.empty(K, dtype=np.int64), np.empty(2)
+        labels = np.empty(n, dtype=np.int32) if want_labels else None
+        self._ck(self.lib.gp_kmeans_accumulate(self.h, n, px, K, pc, sums.ctypes.data_as(_lib._dp), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                               dist2.ctypes.data_as(_lib._dp), labels.ctypes.data_as(_lib._ip) if want_labels else None),
+                 'gp_kmeans_accumulate')
+        return sums, counts, dist2, labels
+
+    @property
+    def n_rows(self):
+        """Rows ``kmeans_accumulate`` clusters with X None (init.kmeans draws its seeds over them)."""
+        return self.N_s
+
+    def take_rows(self, idx):
+        """The rows ``idx`` of the resident X_mu (init.kmeans: the seeds)."""
+        return self.download('X_MU')[np.asarray(idx, dtype=np.int64)]
+
     regime_A_hint = False
     _jitter_used = 0
     _jitter_hint = 0          # the jitter mask the previous evaluation ended up with (global_step)
@@ -353,7 +386,7 @@ class ShardEngine(object):
         'DPSI1TY_DZ': lambda s: (s.M, s.Q, s.D), 'DPSI2_DZ': lambda s: (s.M, s.Q, s.M),
         'DKMM_DALPHA': lambda s: (s.Q, s.M, s.M), 'DPSI1TY_DALPHA': lambda s: (s.Q, s.M, s.D),
         'DPSI2_DALPHA': lambda s: (s.Q, s.M, s.M), 'X_MU_TRIAL': lambda s: (s.N_s, s.Q), 'X_S_TRIAL': lambda s: (s.N_s, s.Q),
-        'GRAD_LATEST': lambda s: (2, s.N_s, s.Q),
+        'GRAD_LATEST': lambda s: (2, s.N_s, s.Q), 'X_MU': lambda s: (s.N_s, s.Q),
     }
 
     def download(self, name):

@@ -1,0 +1,122 @@
+"""Placing the M inducing points: k-means over the embeddings of ALL shards, the assignment passes on the device.
+
+``parallel_GPLVM.init_statistics`` calls ``scipy.cluster.vq.kmeans(embeddings, M)`` on the host, over the first shards that reach M rows
+(parallel_GPLVM.py:179-186).  A pass of that loop is N K Q distance terms -- an hour of host time at N = 1e6, M = 512 with scipy's twenty
+restarts -- and it has the map-reduce shape of an evaluation: every shard yields per-centre sums, counts and summed
+distances (``ShardEngine.kmeans_accumulate``, csrc/kmeans.hip), which add over shards and ranks.  ``kmeans`` here is scipy's ``_kmeans``
+loop restated on those sums: given the same seeds it returns what ``scipy.cluster.vq.kmeans(X_all, seeds, thresh=thresh)`` returns.
+"""
+import numpy
+
+
+class HostRows(object):
+    """A part of ``kmeans`` that passes host rows X (n, Q) through an engine (any object with ShardEngine's ``kmeans_accumulate``)."""
+
+    def __init__(self, engine, X):
+        self.engine = engine
+        self.X = numpy.ascontiguousarray(X, dtype=numpy.float64)
+        self.n_rows, self.Q = self.X.shape
+        self.device = getattr(engine, 'device', 0)
+
+    def kmeans_accumulate(self, centres, want_labels=False):
+        return self.engine.kmeans_accumulate(centres, X=self.X, want_labels=want_labels)
+
+    def take_rows(self, idx):
+        return self.X[numpy.asarray(idx, dtype=numpy.int64)]
+
+
+class _Ranks(object):
+    """Sums over the ranks of a torch.distributed group, as ResidentModel._allreduce_vector does; the identity without one."""
+
+    def __init__(self, dist_group, device):
+        self.dist, self.group, self.device = None, dist_group, device
+        self.rank, self.world = 0, 1
+        if dist_group is not None:
+            import torch.distributed as dist
+            self.dist = dist
+            if dist_group is True:                   # the default group
+                self.group = None
+            self.rank, self.world = dist.get_rank(self.group), dist.get_world_size(self.group)
+
+    def sum(self, values):
+        values = numpy.asarray(values, dtype=numpy.float64)
+        if self.dist is None:
+            return values
+        import torch
+        t = torch.tensor(values.ravel(), dtype=torch.float64,
+                         device=torch.device('cuda', self.device) if self.dist.get_backend(self.group) == 'nccl' else 'cpu')
+        self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
+        return t.cpu().numpy().reshape(values.shape)
+
+
+def _draw_seeds(parts, K, Q, rng, ranks):
+    """K distinct rows over all parts of all ranks (scipy's _kpoints draws rows of its one matrix): global row indices in the order rank, part,
+    row.  Every rank draws, so that equal generators stay in step; rank 0's draw is the one used."""
+    local = [int(p.n_rows) for p in parts]
+    per_rank = numpy.zeros(ranks.world)
+    per_rank[ranks.rank] = sum(local)
+    per_rank = ranks.sum(per_rank).astype(numpy.int64)
+    total = int(per_rank.sum())
+    assert total >= K, 'k-means: %d seeds wanted from %d rows' % (K, total)
+    idx = numpy.asarray(rng.choice(total, K, replace=False), dtype=numpy.float64)
+    idx = ranks.sum(idx if ranks.rank == 0 else numpy.zeros(K)).astype(numpy.int64)
+    seeds = numpy.zeros((K, Q))
+    start = int(per_rank[:ranks.rank].sum())
+    for p, n in zip(parts, local):
+        mine = numpy.nonzero((idx >= start) & (idx < start + n))[0]
+        if mine.size:
+            seeds[mine] = p.take_rows(idx[mine] - start)
+        start += n
+    return ranks.sum(seeds)
+
+
+def _lloyd(parts, code, thresh, max_iters, ranks):
+    """scipy.cluster.vq._kmeans: assign, average, drop the centres without members, until the mean distance moves by at most ``thresh``.  Returns
+    the centres AFTER the last averaging and the mean distance BEFORE it, as scipy does, and the number of passes."""
+    prev, passes = numpy.inf, 0
+    while True:
+        K, Q = code.shape
+        acc = numpy.zeros(K * Q + K + 2)             # sums | counts | sum d^2, sum d: one vector, one collective per pass
+        for p in parts:
+            sums, counts, dist2 = p.kmeans_accumulate(code)[:3]
+            acc[:K * Q] += numpy.asarray(sums, dtype=float).ravel()
+            acc[K * Q:K * Q + K] += counts
+            acc[K * Q + K:] += dist2
+        acc = ranks.sum(acc)
+        sums, counts = acc[:K * Q].reshape(K, Q), acc[K * Q:K * Q + K]
+        avg = acc[K * Q + K + 1] / counts.sum()
+        has = counts > 0
+        code = sums[has] / counts[has, None]
+        passes += 1
+        diff, prev = abs(prev - avg), avg
+        if not diff > thresh or passes >= max_iters:
+            return code, avg, passes
+
+
+def kmeans(parts, K, seeds=None, thresh=1e-5, max_iters=1000, restarts=1, rng=None, dist_group=None):
+    """k-means over the rows of all ``parts``.  Returns (centres (<= K, Q), mean Euclidean distance of a row to its centre, passes).
+
+    parts: objects with ``kmeans_accumulate(centres) -> (sums (K, Q), counts (K,), [sum d^2, sum d], ...)``: ShardEngines with resident embeddings,
+    or ``HostRows(engine, X)``.  Drawing seeds also needs their ``Q``, ``n_rows`` and ``take_rows(idx)``.
+    seeds (K, Q): the starting centres; ``restarts`` is then ignored, as scipy ignores ``iter`` with a guess.  None: K distinct rows over all
+    parts, drawn with ``rng`` (``choice``; default: numpy's global stream), ``restarts`` times, keeping the run with the lowest mean distance.
+    dist_group: a torch.distributed group (True: the default group) whose ranks each hold some of the parts: sums, counts and distances are
+    all-reduced, every rank returns the same centres.  COLLECTIVE: every rank calls with the same K, seeds, thresh, max_iters and restarts.
+    Centres that lose all their members are dropped (the caller tops up: driver.init_statistics)."""
+    parts = list(parts)
+    assert parts and int(K) >= 1
+    ranks = _Ranks(dist_group, getattr(parts[0], 'device', 0))
+    if seeds is not None:
+        seeds = numpy.atleast_2d(numpy.asarray(seeds, dtype=numpy.float64))
+        assert seeds.shape[0] == K, 'seeds shape %s: %d rows expected' % (seeds.shape, K)
+        return _lloyd(parts, seeds, thresh, max_iters, ranks)
+    if rng is None:
+        rng = numpy.random
+    Q = int(parts[0].Q)
+    best = None
+    for _ in range(max(1, int(restarts))):
+        run = _lloyd(parts, _draw_seeds(parts, int(K), Q, rng, ranks), thresh, max_iters, ranks)
+        if best is None or run[1] < best[1]:
+            best = run
+    return best
+

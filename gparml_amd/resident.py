@@ -127,6 +127,16 @@ class ResidentModel(object):
             self._stats_x = np.array(flat_array, copy=True)
             self._stats_version = self.version
 
+    def init_Z(self, K=None, **kw):
+        """Inducing points for this model by k-means over the resident X_mu of every shard of every rank (gparml_amd.init.kmeans on the engines,
+        X = None: nothing is uploaded): (centres (<= K, Q), mean distance, passes); K defaults to M.  The keyword arguments are init.kmeans'
+        (seeds, thresh, max_iters, restarts, rng).  COLLECTIVE across ranks, with this model's group.  The caller tops up and adds the
+        reference's noise (parallel_GPLVM.py:182-187) as driver.init_statistics does."""
+        from . import init
+        if self._dist is not None:
+            kw.setdefault('dist_group', True if self.group is None else self.group)
+        return init.kmeans(self.engines, self.M if K is None else int(K), **kw)
+
     def close(self):
         for e in self.engines:
             e.close()

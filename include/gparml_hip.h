@@ -66,7 +66,8 @@ enum {
   GP_ARR_DPSI2_DALPHA = 18,  /* (Q,M,M) dexp_K_mi_K_im_dalpha()           partial_terms.py:273 */
   GP_ARR_X_MU_TRIAL = 19,    /* (N_s,Q) X_mu + step*d_mu                  local_MapReduce.py:205-211 */
   GP_ARR_X_S_TRIAL = 20,     /* (N_s,Q) softplus(X_S_raw + step*d_S)      local_MapReduce.py:214 */
-  GP_ARR_GRAD_LATEST = 21    /* (2,N_s,Q) -[grad_X_mu, grad_X_S * softplus'(raw trial)], the .grad_latest.npy of local_MapReduce.py:357-360 */
+  GP_ARR_GRAD_LATEST = 21,   /* (2,N_s,Q) -[grad_X_mu, grad_X_S * softplus'(raw trial)], the .grad_latest.npy of local_MapReduce.py:357-360 */
+  GP_ARR_X_MU = 22           /* (N_s,Q) the resident embedding means as uploaded / last updated (the rows gp_kmeans_accumulate clusters with X == NULL) */
 };
 
 /* ---- lifetime -------------------------------------------------------------------------------- */
@@ -194,6 +195,22 @@ int gp_infer_objective(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* c
  * returned point, bit for bit, and never below the value at the start.  Restarts are the caller's rows. */
 int gp_infer_latent(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* cols, int n_cols, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
                     double gtol, double* L, int32_t* iters);
+
+/* ---- initialisation of the inducing points ---------------------------------------------------------- */
+/* One Lloyd assignment pass of k-means: the scipy.cluster.vq.vq + update_cluster_means pair inside scipy.cluster.vq.kmeans, which
+ * parallel_GPLVM.init_statistics runs on the host over the first shards' embeddings to place Z (parallel_GPLVM.py:179-186).  Every row of X (n,Q)
+ * is assigned to the nearest of the K rows of centres (K,Q) in squared Euclidean distance, computed in the direct form sum_q (x_q - z_q)^2, q
+ * ascending (never |x|^2 - 2 x.z + |z|^2, whose cancellation decides near-ties); ties go to the lowest index.  K >= 1 is free of the context's M.
+ * X == NULL: the context's resident X_mu (n must equal N_s; GP_ERR_STATE before an upload).  Outputs, any may be NULL:
+ *   labels (n) the index of the chosen centre; sums (K,Q) per-centre sum of the rows assigned to it; counts (K);
+ *   dist2 (2) = [sum d^2, sum d], d the Euclidean distance to the chosen centre (scipy's stopping rule is on the mean of d).
+ * The shards' results add: a host (or an all-reduce) sums them over shards and divides (gparml_amd/init.py).  Results are bit-identical from run to
+ * run and a row's label never depends on the other rows.  Summation order (csrc/kmeans.hip): rows are taken in chunks, a chunk in segments of 4096
+ * rows; lane l of 64 adds its rows l, l + 64, .. of a segment in ascending order, the lanes are added pairwise (distance 32, 16, .. 1), the
+ * segments and then the chunks in ascending order.  Synchronous.  Leaves the evaluation state untouched: gp_phase2 / gp_finish / gp_predict after
+ * it give bit-identical results.  GP_ERR_BAD_ARG for n < 0, K < 1, NULL centres, non-finite X or centres; n = 0 writes zeros to sums, counts, dist2. */
+int gp_kmeans_accumulate(gp_ctx* ctx, int64_t n, const double* X, int K, const double* centres,
+                         double* sums, int64_t* counts, double* dist2, int32_t* labels);
 
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
