@@ -77,8 +77,6 @@ __global__ void __launch_bounds__(256) zaug_kernel(const double* __restrict__ Zi
   }
 }
 
-static int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 8192)); }
-
 static int download_matrix(gp_ctx* c, const double* src, long ld, long rows, long cols, double* dst, int64_t n) {
   if (n != rows * cols) return fail(c, GP_ERR_BAD_ARG, "gp_download: expected %ld doubles, got %ld", rows * cols, (long)n);
   DevBuf<double> tmp;
@@ -87,6 +85,29 @@ static int download_matrix(gp_ctx* c, const double* src, long ld, long rows, lon
   hipError_t e = hipMemcpyAsync(dst, tmp, rows * cols * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
+  return GP_OK;
+}
+
+// The shared workspace's capacity, a function of the shape alone: the split-k partial tiles of the tile form of phase 1 in either regime, and at
+// least the 1024 partial tiles of p1v2
+static size_t workspace_capacity(const gp_ctx* c) {
+  const int mt = c->Mp / TILE, dt = c->Dp / TILE, n_tiles = c->p1t.n_tiles;
+  const int total_chunks = (int)(c->Np / KC);
+  const int S = std::max(1, std::min(512 / std::max(1, std::min(n_tiles, mt * dt > 0 ? n_tiles : 1)), total_chunks));
+  // worst case slices x tiles (regime B uses fewer tiles, hence possibly more slices)
+  const int Tb = mt * dt;
+  const int Sb = std::max(1, std::min(512 / std::max(1, Tb), total_chunks));
+  // ... and at least the 1024 partial tiles of p1v2
+  return std::max((size_t)std::max((long)(S + 16) * n_tiles, (long)(Sb + 16) * Tb) * TILE * TILE, (size_t)1100 * TILE * TILE);
+}
+int Workspace::alloc(gp_ctx* c) {
+  capacity = workspace_capacity(c);
+  return buf.alloc(c, capacity);
+}
+
+int CgState::alloc(gp_ctx* c) {
+  const size_t n = (size_t)2 * c->N * c->Q;
+  GP_TRY(g_latest.alloc(c, n)); GP_TRY(g_new.alloc(c, n)); GP_TRY(g_old.alloc(c, n));
   return GP_OK;
 }
 }  // namespace gp
@@ -114,7 +135,7 @@ extern "C" int gp_create(gp_ctx** out, int device, int64_t N_s, int D, int M, in
   c->LDK = c->Mp + c->Dp;
   c->CX = 2 * Q + 1; c->CXp = (int)round_up(c->CX, 4);
   c->CZ = 2 * Q + 1; c->CZp = (int)round_up(c->CZ, 4);
-  const long Mp = c->Mp, Dp = c->Dp, Np = c->Np;
+  const long Mp = c->Mp, Np = c->Np;
   int rc = GP_OK;
   auto A = [&](auto& b, size_t n, int mode = DA_INIT) { if (rc == GP_OK) rc = b.alloc(c, n, mode); };
   A(c->Kaug, (size_t)Np * c->LDK);
@@ -123,48 +144,16 @@ extern "C" int gp_create(gp_ctx** out, int device, int64_t N_s, int D, int M, in
   A(c->PU, (size_t)Np * (2 * std::max(psi1_qp(Q), 2) + 2), DA_ZERO);   // zero contract: the records' columns Q .. QP - 1 (u = 0: no guards in psi1_kernel's q loop) are never written
   A(c->lnc1, (size_t)Np); A(c->Xa, (size_t)Np * c->CXp);
   A(c->Z, (size_t)Mp * Q); A(c->alpha, (size_t)Q); A(c->Zaug, (size_t)Mp * c->CZp + 8); A(c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
-  A(c->stats, (size_t)Mp * Mp + Mp * Dp + SC_COUNT);
+  A(c->stats, (size_t)Mp * Mp + Mp * c->Dp + SC_COUNT);
   A(c->grads, (size_t)M * Q + Q);
-  // phase-1 tile table: Psi2 upper tiles first, then the C tiles
-  std::vector<int> tiles;
-  const int mt = c->Mp / TILE, dt = c->Dp / TILE;
-  for (int i = 0; i < mt; ++i) for (int j = i; j < mt; ++j) { tiles.push_back(i); tiles.push_back(j); }
-  for (int i = 0; i < mt; ++i) for (int j = 0; j < dt; ++j) { tiles.push_back(i); tiles.push_back(mt + j); }
-  c->n_tiles = (int)tiles.size() / 2;
-  if (rc == GP_OK) rc = upload(c, c->tiles, tiles);      // (the device synchronisation below completes the copy)
-  const int total_chunks = (int)(Np / KC);
-  const int S = std::max(1, std::min(512 / std::max(1, std::min(c->n_tiles, mt * dt > 0 ? c->n_tiles : 1)), total_chunks));
-  // worst case slices x tiles (regime B uses fewer tiles, hence possibly more slices)
-  const int Tb = mt * dt;
-  const int Sb = std::max(1, std::min(512 / std::max(1, Tb), total_chunks));
-  // ... and at least the 1024 partial tiles of p1v2
-  A(c->part, std::max((size_t)std::max((long)(S + 16) * c->n_tiles, (long)(Sb + 16) * Tb) * TILE * TILE, (size_t)1100 * TILE * TILE));
-  c->kl_blocks = blocks_for(Np);
-  A(c->klpart, (size_t)c->kl_blocks + 8192);
-  A(c->Kmm, (size_t)2 * Mp * Mp); A(c->Lmat, (size_t)2 * Mp * Mp); A(c->Inv, (size_t)2 * Mp * Mp);
-  A(c->Linv, (size_t)2 * Mp * Mp, DA_ZERO);   // zero contract: the 128-blocks above the block diagonal are never written (potrf_inverse_batched's precondition)
-  if (Mp >= 512 && Mp <= 2048) {
-    // gsi8.hip: ten digit planes of W = [A | B] for the larger of the two products (K_mm^-1 | Psi2: 2 Mp columns; K_mm + beta Psi2 | E: Mp + Dp), and W's column scales
-    const size_t wcols = (size_t)Mp + std::max(Mp, Dp);
-    A(c->gsd, (size_t)10 * Mp * wcols);
-    A(c->gss, wcols);
-  }
-  A(c->KmmKeep, (size_t)Mp * Mp); A(c->T1, (size_t)Mp * std::max<long>(std::max(Mp, Dp), 256)); A(c->T2, (size_t)Mp * std::max(Mp, Dp));
-  A(c->dFdK, (size_t)Mp * Mp); A(c->Bbar, (size_t)Mp * Mp);
-  A(c->E, (size_t)Mp * Dp); A(c->PsiE, (size_t)Mp * Dp); A(c->Abar, (size_t)Mp * Dp);
-  A(c->Bm, (size_t)c->LDK * Mp);
-  A(c->gs, (size_t)GS_COUNT + 8 + 8 * 64);   // scalars | failure flags | dots_kernel partials [8 jobs][64 blocks]
-  A(c->gK, (size_t)M * Q + Q);
-  // phase 2
-  c->p2_slices = std::max(1, std::min<int>(8 * std::max(1, 64 / mt), (int)(Np / TILE)));
-  A(c->Rpart, (size_t)2 * (c->p2_slices + 8) * Mp * c->CXp);
-  A(c->HZp, (size_t)(Mp / TILE) * Np * c->CZp);    // p2_gen8_kernel: per-point partials, one array per 128 inducing columns
   A(c->gXmu, (size_t)N_s * Q); A(c->gXs, (size_t)N_s * Q);
-  c->ga_blocks = blocks_for(Np);
-  A(c->gapart, (size_t)c->ga_blocks * Q);
-  // fast phase 2: per-wave (eight-wave kernel: blocks * 8 rows of <= 12) or per-256-points (four-wave kernel) partials of grad_alpha's mu^2 term
-  A(c->hgpart, std::max((size_t)((N_s + 255) / 256) * Q, (size_t)8 * (c->p2_slices + 8) * (Mp / TILE) * 8 * 12));
-  A(c->g_latest, (size_t)2 * N_s * Q); A(c->g_new, (size_t)2 * N_s * Q); A(c->g_old, (size_t)2 * N_s * Q);
+  A(c->red, 8192);
+  // the stages (eager: an evaluation allocates nothing of theirs); the workspace's capacity needs the tile table
+  if (rc == GP_OK) rc = c->p1t.alloc(c);
+  if (rc == GP_OK) rc = c->ws.alloc(c);
+  if (rc == GP_OK) rc = c->gstep.alloc(c);
+  if (rc == GP_OK) rc = c->p2.alloc(c);
+  if (rc == GP_OK) rc = c->cg.alloc(c);
   for (int i = 0; i < 14 && rc == GP_OK; ++i) if (hipEventCreate(&c->ev[i]) != hipSuccess) rc = fail(c, GP_ERR_HIP, "hipEventCreate failed");
   if (rc == GP_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(c, GP_ERR_HIP, "device sync failed after allocation");
   if (rc != GP_OK) { gp::g_create_error = c->err; gp_destroy(c); return rc; }
@@ -178,7 +167,7 @@ extern "C" int gp_destroy(gp_ctx* c) {
   (void)hipDeviceSynchronize();
   gp::comm_free(c);
   for (hipEvent_t e : c->ev) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->glob_ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->glob.glob_ev) if (e) (void)hipEventDestroy(e);
   delete c;     // the buffers are its DevBuf members
   return GP_OK;
 }
@@ -195,11 +184,11 @@ extern "C" int gp_memory_info(gp_ctx* c, int64_t* free_bytes, int64_t* total_byt
 
 extern "C" int gp_i8_status(gp_ctx* c, int* state, double* rel_psi2, double* rel_c, double* cond_lower_bound, int64_t* checks) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (state) *state = !p1i8_applicable_static(c) ? -1 : c->i8_guard;
-  if (rel_psi2) *rel_psi2 = c->i8_rel_psi2;
-  if (rel_c) *rel_c = c->i8_rel_c;
-  if (cond_lower_bound) *cond_lower_bound = c->i8_cond_lb;
-  if (checks) *checks = c->i8_checks;
+  if (state) *state = !p1i8_applicable_static(c) ? -1 : c->i8.guard;
+  if (rel_psi2) *rel_psi2 = c->i8.rel_psi2;
+  if (rel_c) *rel_c = c->i8.rel_c;
+  if (cond_lower_bound) *cond_lower_bound = c->i8.cond_lb;
+  if (checks) *checks = c->i8.checks;
   return GP_OK;
 }
 
@@ -237,7 +226,7 @@ static int upload_embeddings(gp_ctx* c, const double* X_mu, const double* X_S, i
   GP_HIP(c, hipMemcpyAsync(c->Xs, X_S, nq * 8, hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->state = 0;
-  c->pred_ok = false;
+  c->gstep.pred_ok = false;
   return GP_OK;
 }
 
@@ -255,7 +244,7 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
   if (rc == GP_OK) {
     // sum_YYT (partial_terms.py:40) once per upload
     const int nb = 1024;
-    double* part = c->klpart + c->kl_blocks;  // spare tail of the KL partial buffer (8192 doubles)
+    double* part = c->red;
     hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, c->stream, dY, (long)nd, part);
     std::vector<double> h(nb);
     e = hipMemcpyAsync(h.data(), part, nb * 8, hipMemcpyDeviceToHost, c->stream);
@@ -271,8 +260,7 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
   c->have_data = true;
   c->have_dir = false;
   c->prep_fixa_valid = false;
-  c->i8_y_valid = false;
-  c->i8_guard = 0; c->i8_since_check = 0; c->i8_check_pending = false;      // new data: the int8 path is measured again (p1i8.hip, guard)
+  c->i8.reset();      // new data: Y's digits are stale and the int8 path is measured again (p1i8.hip, guard)
   return GP_OK;
 }
 
@@ -292,7 +280,7 @@ extern "C" int gp_set_direction(gp_ctx* c, const double* d) {
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->have_dir = true;
   c->state = 0;
-  c->pred_ok = false;
+  c->gstep.pred_ok = false;
   return GP_OK;
 }
 
@@ -301,11 +289,10 @@ extern "C" int gp_set_direction(gp_ctx* c, const double* d) {
 // Not refilled: the shard's data and what the prep kernels derive from it alone (they are skipped from the second evaluation on for fixed
 // embeddings), the CG vectors, Linv (its upper blocks are a zero contract), tables and plans.
 static int poison_scratch(gp_ctx* c) {
-  auto P = [&](const DevBuf<double>& b) -> hipError_t { return b.size() ? hipMemsetAsync(b, 0xFF, b.bytes(), c->stream) : hipSuccess; };
-  for (const DevBuf<double>* b : {&c->part, &c->Rpart, &c->HZp, &c->gapart, &c->hgpart, &c->Kmm, &c->Lmat, &c->Inv, &c->KmmKeep, &c->T1, &c->T2, &c->dFdK,
-                                  &c->Bbar, &c->E, &c->PsiE, &c->Abar, &c->Bm, &c->gK, &c->gs, &c->stats, &c->grads, &c->gXmu, &c->gXs})
-    GP_HIP(c, P(*b));
+  for (const DevBuf<double>* b : {&c->ws.buf, &c->stats, &c->grads, &c->gXmu, &c->gXs}) GP_HIP(c, poison_fill(c, *b));
   GP_HIP(c, hipMemset2DAsync(c->Kaug, (size_t)c->LDK * 8, 0xFF, (size_t)c->Mp * 8, c->Np, c->stream));      // the Psi1 columns of [Psi1 | Y]
+  GP_TRY(c->p2.poison(c));
+  GP_TRY(c->gstep.poison(c));
   return b_poison(c);
 }
 
@@ -327,29 +314,29 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
   // (mapped) slot itself; two copy commands cost ~25 us of stream time at configs[1]'s size (blit dispatches with idle gaps around them,
   // profiles/r05_config1_timeline.txt) for 10 KB.  The evaluation's only host synchronisation is the read-back in gp_finish
   const size_t nz = (size_t)c->M * c->Q, nq = (size_t)c->Q;
-  const int slot = c->glob_slot;
-  if (!c->h_glob[slot]) {
-    GP_TRY(c->h_glob[slot].alloc(c, nz + nq));
-  } else if (c->glob_epoch[slot] >= c->sync_epoch) {
+  const int slot = c->glob.glob_slot;
+  if (!c->glob.h_glob[slot]) {
+    GP_TRY(c->glob.h_glob[slot].alloc(c, nz + nq));
+  } else if (c->glob.glob_epoch[slot] >= c->sync_epoch) {
     // the kernel that read this slot two calls ago may still be queued: no stream synchronisation has been seen since (never the case in an
     // optimiser's sequence -- every evaluation ends in gp_finish's synchronisation -- so no event is recorded per call: that was one more signal
     // packet on the stream)
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
   }
-  std::memcpy(c->h_glob[slot], Z, nz * sizeof(double));
-  std::memcpy(c->h_glob[slot] + nz, alpha, nq * sizeof(double));
+  std::memcpy(c->glob.h_glob[slot], Z, nz * sizeof(double));
+  std::memcpy(c->glob.h_glob[slot] + nz, alpha, nq * sizeof(double));
   double* dslot = nullptr;
-  GP_HIP(c, hipHostGetDevicePointer((void**)&dslot, c->h_glob[slot], 0));
+  GP_HIP(c, hipHostGetDevicePointer((void**)&dslot, c->glob.h_glob[slot], 0));
   hipLaunchKernelGGL(zaug_kernel, dim3((int)std::min<long>(((long)c->Mp * c->CZp + 255) / 256, 1024)), dim3(256), 0, c->stream, dslot, dslot + nz, c->M, c->Mp, c->Q, c->CZp, c->Z,
                      c->Zaug, c->alpha, c->Zt);
   GP_HIP(c, hipGetLastError());
-  c->glob_epoch[slot] = c->sync_epoch;                      // the slot may be rewritten once a later stream synchronisation has passed
-  c->glob_slot = slot ^ 1;
+  c->glob.glob_epoch[slot] = c->sync_epoch;                      // the slot may be rewritten once a later stream synchronisation has passed
+  c->glob.glob_slot = slot ^ 1;
   c->sf2 = sf2; c->beta = beta; c->N_global = N_global; c->step = step;
   c->have_globals = true;
   c->state = 0;
-  c->pred_ok = false;
+  c->gstep.pred_ok = false;
   return GP_OK;
 }
 
@@ -365,7 +352,7 @@ extern "C" int gp_phase1(gp_ctx* c) {
   if (!c->regime_A) GP_TRY(run_phase1_b(c));
   GP_EV(c, 2);
   c->state = 1;
-  c->pred_ok = false;
+  c->gstep.pred_ok = false;
   c->spack_filled = false;
   return GP_OK;
 }
@@ -429,7 +416,7 @@ static int stats_pack(gp_ctx* c, int unpack_) {
   GP_TRY(ensure_spack(c));
   const long n = (long)c->M * c->M + (long)c->M * c->D + SC_COUNT;
   if (unpack_) {
-    c->pred_ok = false;
+    c->gstep.pred_ok = false;
     // the packed buffer only holds statistics after a pack (it is zero from its allocation): unpacking first would silently wipe phase 1's sums
     if (!c->spack_filled) return fail(c, GP_ERR_STATE, "gp_stats_unpack before gp_stats_pack");
     hipLaunchKernelGGL(stats_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->spack, c->stats, c->M, c->Mp, c->D, c->Dp);
@@ -490,7 +477,7 @@ extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int 
     from = dst->staging;
   }
   hipLaunchKernelGGL(combine_kernel, dim3(blocks_for(n)), dim3(256), 0, dst->stream, which == 0 ? dst->stats : dst->grads, from, n, op);
-  if (which == 0) dst->pred_ok = false;
+  if (which == 0) dst->gstep.pred_ok = false;
   GP_HIP(dst, hipGetLastError());
   if (which == 0 && dst->state < 1) dst->state = 1;
   return GP_OK;
@@ -503,7 +490,7 @@ extern "C" int gp_scale_buffer(gp_ctx* c, int which, double f) {
   if (which == 1 && c->state < 3) return fail(c, GP_ERR_STATE, "gp_scale_buffer(gradient sums) before gp_phase2");
   GP_HIP(c, hipSetDevice(c->device));
   const long n = which == 0 ? (long)c->Mp * c->Mp + (long)c->Mp * c->Dp + SC_COUNT : (long)c->M * c->Q + c->Q;
-  if (which == 0) { c->spack_filled = false; c->pred_ok = false; }   // the padded buffer is the source of truth: a later unpack needs a new pack
+  if (which == 0) { c->spack_filled = false; c->gstep.pred_ok = false; }   // the padded buffer is the source of truth: a later unpack needs a new pack
   if (f == 0.0) {
     // a dropped shard: the reference never loads its files (local_MapReduce.py:119-129) -- a memset, so that non-finite values in
     // the dropped shard's sums (0 * inf = nan) cannot reach the reduction
@@ -522,14 +509,14 @@ extern "C" int gp_global_step_jitter(gp_ctx* c, int jitter_mask) {
   if (c->state < 1) return fail(c, GP_ERR_STATE, "gp_global_step before gp_phase1 / gp_set_local_statistics");
   if (jitter_mask < 0 || jitter_mask > 3) return fail(c, GP_ERR_BAD_ARG, "gp_global_step_jitter: mask must be 0..3");
   GP_HIP(c, hipSetDevice(c->device));
-  c->jitter_mask = jitter_mask;
-  c->pred_ok = false;
+  c->gstep.jitter_mask = jitter_mask;
+  c->gstep.pred_ok = false;
   GP_EV(c, 3);
   const int rc_gs = run_global_step(c);
   GP_EV(c, 4);
   if (rc_gs != GP_OK) return rc_gs;
   c->state = 2;
-  c->pred_ok = true;           // gp_predict still checks the step's outcome (check_global)
+  c->gstep.pred_ok = true;           // gp_predict still checks the step's outcome (check_global)
   return GP_OK;
 }
 
@@ -540,7 +527,7 @@ extern "C" int gp_global_step(gp_ctx* c) { return gp_global_step_jitter(c, 0); }
 // accuracy -- the check then stays pending (guard 0: the next evaluation runs both paths again).  Called wherever an evaluation's global step is
 // known to be over: gp_finish, gp_global_status, gp_download of a global-step array.
 static int resolve_i8_check(gp_ctx* c) {
-  if (!c->i8_check_pending || c->state < 2) return GP_OK;
+  if (!c->i8.check_pending || c->state < 2) return GP_OK;
   if (check_global(c) != GP_OK) return GP_OK;     // the caller reports that status itself
   return p1i8_check_finish(c);
 }
@@ -551,7 +538,7 @@ extern "C" int gp_global_status(gp_ctx* c, int* retry_mask) {
   GP_HIP(c, hipSetDevice(c->device));
   GP_TRY(resolve_i8_check(c));
   const int rc = check_global(c);
-  if (retry_mask) *retry_mask = (rc == GP_RETRY_JITTER) ? c->retry_mask : 0;
+  if (retry_mask) *retry_mask = (rc == GP_RETRY_JITTER) ? c->gstep.retry_mask : 0;
   return rc;
 }
 
@@ -572,9 +559,9 @@ extern "C" int gp_phase2(gp_ctx* c, int want_embedding_grads) {
     // the .grad_latest vector of this evaluation, resident for the optimiser's dot products
     const long nq = (long)c->N * c->Q;
     hipLaunchKernelGGL(grad_latest_kernel, dim3(blocks_for(nq)), dim3(256), 0, c->stream, c->gXmu, c->gXs, c->Xs, c->dir, (long)c->N, c->Q, c->step,
-                       1, c->have_dir ? 1 : 0, c->g_latest);
+                       1, c->have_dir ? 1 : 0, c->cg.g_latest);
     GP_HIP(c, hipGetLastError());
-    c->have_glatest = true;
+    c->cg.have_glatest = true;
   }
   GP_EV(c, 6);
   c->state = 3;
@@ -618,12 +605,12 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
     case GP_ARR_PSI1: return download_matrix(c, c->Kaug, c->LDK, N, M, dst, n);
     case GP_ARR_PSI2_SUM: return download_matrix(c, c->stats, Mp, M, M, dst, n);
     case GP_ARR_PSI1TY: return download_matrix(c, c->stats + Mp * Mp, Dp, M, D, dst, n);
-    case GP_ARR_KMM: return download_matrix(c, c->KmmKeep, Mp, M, M, dst, n);
-    case GP_ARR_KMM_INV: return download_matrix(c, c->Inv, Mp, M, M, dst, n);
-    case GP_ARR_KMM_PLUS_OP_INV: return download_matrix(c, c->Inv + Mp * Mp, Mp, M, M, dst, n);
-    case GP_ARR_DF_DKMM: return download_matrix(c, c->dFdK, Mp, M, M, dst, n);
-    case GP_ARR_DF_DPSI1TY: return download_matrix(c, c->Abar, Dp, M, D, dst, n);
-    case GP_ARR_DF_DPSI2: return download_matrix(c, c->Bbar, Mp, M, M, dst, n);
+    case GP_ARR_KMM: return download_matrix(c, c->gstep.KmmKeep, Mp, M, M, dst, n);
+    case GP_ARR_KMM_INV: return download_matrix(c, c->gstep.Inv, Mp, M, M, dst, n);
+    case GP_ARR_KMM_PLUS_OP_INV: return download_matrix(c, c->gstep.Inv + Mp * Mp, Mp, M, M, dst, n);
+    case GP_ARR_DF_DKMM: return download_matrix(c, c->gstep.dFdK, Mp, M, M, dst, n);
+    case GP_ARR_DF_DPSI1TY: return download_matrix(c, c->gstep.Abar, Dp, M, D, dst, n);
+    case GP_ARR_DF_DPSI2: return download_matrix(c, c->gstep.Bbar, Mp, M, M, dst, n);
     case GP_ARR_GRAD_X_MU: return download_matrix(c, c->gXmu, Q, N, Q, dst, n);
     case GP_ARR_GRAD_X_S: return download_matrix(c, c->gXs, Q, N, Q, dst, n);
     case GP_ARR_X_MU_TRIAL: return download_matrix(c, c->mu, Q, N, Q, dst, n);
@@ -650,7 +637,7 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
       GP_HIP(c, hipMemcpyAsync(sc, c->stats + Mp * Mp + Mp * Dp, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
       GP_HIP(c, hipStreamSynchronize(c->stream));
       dst[0] = sc[SC_SUM_YYT]; dst[1] = sc[SC_PSI0]; dst[2] = sc[SC_KL];
-      dst[3] = c->h_gs[GS_LOGDET_K]; dst[4] = c->h_gs[GS_LOGDET_A]; dst[5] = c->h_gs[GS_F]; dst[6] = c->h_gs[GS_GRAD_BETA]; dst[7] = c->h_gs[GS_GRAD_SF2];
+      dst[3] = c->gstep.h_gs[GS_LOGDET_K]; dst[4] = c->gstep.h_gs[GS_LOGDET_A]; dst[5] = c->gstep.h_gs[GS_F]; dst[6] = c->gstep.h_gs[GS_GRAD_BETA]; dst[7] = c->gstep.h_gs[GS_GRAD_SF2];
       return GP_OK;
     }
     case GP_ARR_PSI2_POINTS: case GP_ARR_DKMM_DZ: case GP_ARR_DPSI1TY_DZ: case GP_ARR_DPSI2_DZ: case GP_ARR_DKMM_DALPHA:
@@ -673,7 +660,7 @@ extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* 
   if (!c->have_globals) return fail(c, GP_ERR_STATE, "gp_set_local_statistics before gp_set_globals");
   GP_HIP(c, hipSetDevice(c->device));
   const long M = c->M, Mp = c->Mp, D = c->D, Dp = c->Dp;
-  double* tmp = c->T2;
+  double* tmp = c->gstep.T2;
   GP_HIP(c, hipMemcpyAsync(tmp, Psi2, M * M * 8, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(scatter2d_kernel, dim3(blocks_for(Mp * Mp)), dim3(256), 0, c->stream, tmp, M, M, c->stats, Mp, Mp, Mp);
   GP_HIP(c, hipStreamSynchronize(c->stream));
@@ -684,7 +671,7 @@ extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* 
   GP_HIP(c, hipMemcpyAsync(c->stats + Mp * Mp + Mp * Dp, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
   c->spack_filled = false;     // the packed payload of an earlier evaluation no longer describes these statistics
-  c->pred_ok = false;
+  c->gstep.pred_ok = false;
   if (c->state < 1) c->state = 1;
   return GP_OK;
 }
@@ -693,12 +680,12 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   if (!c) return GP_ERR_BAD_ARG;
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict: n must be >= 0");
   if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_predict: unknown flags %d", flags);
-  if (c->state < 2 || !c->have_globals || !c->pred_ok)
+  if (c->state < 2 || !c->have_globals || !c->gstep.pred_ok)
     return fail(c, GP_ERR_STATE, "gp_predict needs a global step on the statistics and globals as they are now (none since the last phase 1, "
                 "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)");
   GP_HIP(c, hipSetDevice(c->device));
   GP_TRY(resolve_i8_check(c));
-  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "gp_predict: the last global step did not succeed (%s)", c->gs_msg.c_str());
+  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "gp_predict: the last global step did not succeed (%s)", c->gstep.gs_msg.c_str());
   if (n == 0) return GP_OK;
   if (!X_mu) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is NULL");
   const size_t nq = (size_t)n * c->Q;
@@ -720,12 +707,12 @@ static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, c
   for (int j = 0; cols && j < n_cols; ++j)
     if (cols[j] < 0 || cols[j] >= c->D || (j && cols[j] <= cols[j - 1]))
       return fail(c, GP_ERR_BAD_ARG, "%s: cols must be strictly increasing in 0 .. D - 1", who);
-  if (c->state < 2 || !c->have_globals || !c->pred_ok)
+  if (c->state < 2 || !c->have_globals || !c->gstep.pred_ok)
     return fail(c, GP_ERR_STATE, "%s needs a global step on the statistics and globals as they are now (none since the last phase 1, "
                 "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)", who);
   GP_HIP(c, hipSetDevice(c->device));
   GP_TRY(resolve_i8_check(c));
-  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "%s: the last global step did not succeed (%s)", who, c->gs_msg.c_str());
+  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "%s: the last global step did not succeed (%s)", who, c->gstep.gs_msg.c_str());
   if (n == 0) return GP_OK;
   if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, X_mu or X_S is NULL", who);
   const size_t nq = (size_t)n * c->Q;
@@ -814,21 +801,21 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
   } else {
     // the one host synchronisation of an evaluation: scalars + failure flags of the global step and the final gradients in one mapped buffer
     const long n = (long)c->M * c->Q + c->Q;
-    constexpr int ngs = GS_COUNT + 8;
+    constexpr int ngs = GS_HOST;
     if (!c->h_out) GP_TRY(c->h_out.alloc(c, ngs + n));
     double* dout = nullptr;
     GP_HIP(c, hipHostGetDevicePointer((void**)&dout, c->h_out, 0));
-    hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->stream, c->gs, ngs, c->gK, c->grads, n, dout);
+    hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->stream, c->gstep.gs, ngs, c->gstep.gK, c->grads, n, dout);
     GP_HIP(c, hipGetLastError());
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
-    GP_TRY(check_global_from(c, c->gs_pending ? c->h_out : nullptr));
+    GP_TRY(check_global_from(c, c->gstep.gs_pending ? c->h_out : nullptr));
     if (grad_Z) memcpy(grad_Z, c->h_out + ngs, (size_t)c->M * c->Q * 8);
     if (grad_alpha) memcpy(grad_alpha, c->h_out + ngs + (size_t)c->M * c->Q, (size_t)c->Q * 8);
   }
-  if (F) *F = c->h_gs[GS_F];
-  if (grad_sf2) *grad_sf2 = c->h_gs[GS_GRAD_SF2];
-  if (grad_beta) *grad_beta = c->h_gs[GS_GRAD_BETA];
+  if (F) *F = c->gstep.h_gs[GS_F];
+  if (grad_sf2) *grad_sf2 = c->gstep.h_gs[GS_GRAD_SF2];
+  if (grad_beta) *grad_beta = c->gstep.h_gs[GS_GRAD_BETA];
   return GP_OK;
 }
 // ---- resident CG vectors (scg_adapted_local_MapReduce.py:29-243) --------------------------------------------------------
@@ -880,14 +867,14 @@ extern "C" int gp_cg_update(gp_ctx* c, int which, double a) {
   if (!c) return GP_ERR_BAD_ARG;
   if (which < 0 || which > 5) return fail(c, GP_ERR_BAD_ARG, "gp_cg_update: which must be 0..5");
   GP_TRY(cg_ready(c, "gp_cg_update"));
-  if ((which == 4 || which == 5) && !c->have_glatest) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
+  if ((which == 4 || which == 5) && !c->cg.have_glatest) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
   GP_HIP(c, hipSetDevice(c->device));
   const long nq = (long)c->N * c->Q;
-  hipLaunchKernelGGL(cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, c->stream, which, a, nq, c->dir, c->g_new, c->g_old, c->g_latest,
+  hipLaunchKernelGGL(cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, c->stream, which, a, nq, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest,
                      c->Xmu, c->Xs);
   GP_HIP(c, hipGetLastError());
   if (which == 0 || which == 1 || which == 5) c->have_dir = true;
-  if (which == 2) { c->state = 0; c->prep_fixa_valid = false; c->pred_ok = false; }   // the embeddings moved: statistics are stale
+  if (which == 2) { c->state = 0; c->prep_fixa_valid = false; c->gstep.pred_ok = false; }   // the embeddings moved: statistics are stale
   return GP_OK;
 }
 
@@ -896,8 +883,8 @@ extern "C" int gp_cg_set_grads(gp_ctx* c) { return gp_cg_update(c, 5, 0.0); }
 static int cg_reduce(gp_ctx* c, double* out6) {
   const long n2 = 2L * c->N * c->Q;
   const int nb = std::min(blocks_for(n2), 1024);
-  double* part = c->klpart + c->kl_blocks;   // spare tail (8192 doubles)
-  hipLaunchKernelGGL(cg_dots_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->dir, c->g_new, c->g_old, c->g_latest, part);
+  double* part = c->red;
+  hipLaunchKernelGGL(cg_dots_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest, part);
   std::vector<double> h((size_t)nb * 6);
   GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
@@ -938,8 +925,8 @@ extern "C" int gp_cg_abs(gp_ctx* c, double* out2) {
   GP_HIP(c, hipSetDevice(c->device));
   const long n2 = 2L * c->N * c->Q;
   const int nb = std::min(blocks_for(n2), 1024);
-  double* part = c->klpart + c->kl_blocks;   // spare tail (8192 doubles)
-  hipLaunchKernelGGL(cg_abs_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->g_new, part);
+  double* part = c->red;
+  hipLaunchKernelGGL(cg_abs_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->cg.g_new, part);
   std::vector<double> h((size_t)nb * 2);
   GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));

@@ -108,8 +108,8 @@ extern "C" int gp_comm_info(gp_ctx* c, int* nranks, int* rank, int64_t* stats_by
   if (probe_sum) {
     if (!c->comm) return fail(c, GP_ERR_STATE, "gp_comm_info(probe) before gp_comm_init");
     GP_HIP(c, hipSetDevice(c->device));
-    // one double per rank through the communicator; the last of the device scalars of the global step is free between evaluations
-    double one = 1.0, *slot = c->gs + GS_COUNT - 1;
+    // one double per rank through the communicator, in the global step's spare scalar (GS_PROBE)
+    double one = 1.0, *slot = c->gstep.gs + GS_PROBE;
     GP_HIP(c, hipMemcpyAsync(slot, &one, sizeof(double), hipMemcpyHostToDevice, c->stream));
     const int rc = g_rccl.AllReduce(slot, slot, 1, kNcclFloat64, kNcclSum, c->comm, c->stream);
     if (rc != 0) return rccl_fail(c, "ncclAllReduce(probe)", rc);

@@ -150,7 +150,7 @@ int compat_build(gp_ctx* c, int which, DevBuf<double>& out) {
   switch (which) {
     case GP_ARR_PSI2_POINTS: break;
     case GP_ARR_DKMM_DZ: case GP_ARR_DKMM_DALPHA:
-      hipLaunchKernelGGL(dkmm_kernel, dim3(grid_for(n)), dim3(256), 0, c->stream, c->KmmKeep, c->Mp, c->Z, c->alpha, (int)M, (int)Q,
+      hipLaunchKernelGGL(dkmm_kernel, dim3(grid_for(n)), dim3(256), 0, c->stream, c->gstep.KmmKeep, c->Mp, c->Z, c->alpha, (int)M, (int)Q,
                          which == GP_ARR_DKMM_DZ ? 0 : 1, buf);
       break;
     case GP_ARR_DPSI1TY_DZ: case GP_ARR_DPSI1TY_DALPHA:

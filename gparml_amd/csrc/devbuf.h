@@ -92,4 +92,24 @@ int upload(gp_ctx* c, DevBuf<T>& b, const std::vector<T>& v) {
   return GP_OK;
 }
 
+// The one rule for borrowed workspace.  A stage that needs scratch only for the length of its own launches (the split-k / split-n partial tiles of
+// every phase-1 form, the global step's split-k products) takes it from the context's Workspace instead of owning it.  `capacity` is a pure
+// function of the context's shape (workspace_capacity, api.hip), set once by gp_create: a consumer whose decomposition follows the room there is
+// (p1i8.hip's slice count, linalg.hip's split-k factors) reads `capacity`, never the allocation's size, so its summation order cannot depend on
+// what ran on the context before.  reserve() is for the one plan whose need can exceed the capacity (regime B's pair kernel, psi2.hip): called
+// when the plan is built, it may replace the allocation by a larger one and leaves `capacity` where it is.  take() never allocates.
+struct Workspace {
+  DevBuf<double> buf;
+  size_t capacity = 0;
+  int alloc(gp_ctx* c);                                      // api.hip: capacity from the shape, then the buffer
+  int reserve(gp_ctx* c, size_t n) { return buf.grow(c, n, DA_RAW); }
+  // *out = the workspace, for n doubles; GP_ERR_UNSUPPORTED with a message naming `who` when n exceeds what is allocated
+  int take(gp_ctx* c, size_t n, const char* who, double** out) {
+    *out = nullptr;
+    if (n > buf.size()) return fail(c, GP_ERR_UNSUPPORTED, "%s: needs %zu doubles of workspace, %zu are allocated", who, n, buf.size());
+    *out = buf.get();
+    return GP_OK;
+  }
+};
+
 }  // namespace gp

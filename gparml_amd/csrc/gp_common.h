@@ -20,6 +20,7 @@ namespace gp {
 #endif
 
 inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
+inline int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 8192)); }   // grid of a grid-stride kernel over n elements
 // latent width of the packed per-point records of psi1_kernel (Q <= 16: Q rounded up to 2) / psi1_wide_kernel (24, 32, 52, 64); 0: none
 inline int psi1_qp(int Q) { return Q <= 16 ? (Q + 1) / 2 * 2 : Q <= 24 ? 24 : Q <= 32 ? 32 : Q <= 52 ? 52 : Q <= 64 ? 64 : 0; }
 
@@ -52,6 +53,9 @@ enum { SC_SUM_YYT = 0, SC_PSI0 = 1, SC_KL = 2, SC_NLOCAL = 3, SC_COUNT = 8 };
 // device scalars produced by the global step (GP_ARR_SCALARS order after the first three)
 enum { GS_LOGDET_K = 0, GS_LOGDET_A = 1, GS_F = 2, GS_GRAD_BETA = 3, GS_GRAD_SF2 = 4, GS_FAIL = 5, GS_TR_KIPSI2 = 6, GS_TR_PPSI2 = 7,
        GS_TR_CE = 8, GS_TR_EPSI2E = 9, GS_SUM_V = 10, GS_SUM_AC = 11, GS_SUM_BPSI2 = 12, GS_COUNT = 16 };
+// regions of the global step's device buffer GsState::gs: [GS_COUNT] scalars | [8] failure flags (two used) | dots_kernel's partials [8 jobs][64 blocks]
+enum { GS_FLAGS = GS_COUNT, GS_HOST = GS_FLAGS + 8 /* what the host reads back: scalars | flags */, GS_DOTS = GS_HOST, GS_TOTAL = GS_DOTS + 8 * 64,
+       GS_PROBE = GS_COUNT - 1 /* the last scalar is unused by the step: gp_comm_info's probe borrows it between evaluations */ };
 
 struct P1Plan;     // p1v2.hip
 struct I8Plan;     // p1i8.hip
@@ -68,13 +72,109 @@ struct KmPlanDelete { void operator()(KmPlan* p) const; };
 
 }  // namespace gp
 
+// ---- the stages' own state -------------------------------------------------------------------------------------------------------------
+// One struct per stage of an evaluation: its buffers and the scalars that go with them.  alloc() holds the stage's size formulas and is called
+// once by gp_create (eagerly: nothing here is allocated during an evaluation unless its comment says so); poison() refills, in the test mode
+// (devbuf.h, g_opt_poison), what an evaluation must write before it reads.  Both live next to the code that uses the state.  Nothing outside a
+// stage's home file writes its struct, except where a comment here names the reader.
+namespace gp {
+
+// tile form of phase 1 and the prep kernels' KL partials (psi.hip)
+struct P1Tiles {
+  DevBuf<int> tiles;          // phase-1 tile table (int2): Psi2 upper tiles first, then the C tiles
+  int n_tiles = 0;
+  DevBuf<int> bmap;           // phase-1 block -> (slice, tile type) placement table (built for the (T, S) it was last run with)
+  int bmap_T = -1, bmap_S = -1, bmap_blocks = 0;
+  DevBuf<double> klpart;      // [kl_blocks] partial KL sums of prep_row_kernel (read by the phase-1 scalars kernels; regime B's table kernel uses the same grid)
+  int kl_blocks = 0;
+  int alloc(gp_ctx* c);
+};
+
+// the int8 phase 1's switches and its run-time guard (p1i8.hip, "guard"); gp_i8_status reports them
+struct I8Guard {
+  bool active = false;        // this evaluation's phase 1 runs on the int8 matrix core (psi1_kernel wrote the digits)
+  bool y_valid = false;       // Y's digits are current (reset by gp_upload_shard)
+  bool unsupported = false;   // the int8 plan could not be built for this context (falls back to the float64 kernels)
+  int guard = 0;              // 0 = not checked since the last upload, 1 = accepted, 2 = rejected (float64 from then on)
+  bool check_pending = false; // this evaluation ran both phase-1 paths: gp_finish reads the comparison and decides
+  long since_check = 0, checks = 0;
+  double rel_psi2 = 0, rel_c = 0, cond_lb = 0;
+  DevBuf<double> cmp;         // device: [4] squared Frobenius norms (dPsi2, Psi2, dC, C) | [2] max diag(Psi2), max diag(P) | partials (allocated by the first check)
+  void reset() { y_valid = false; guard = 0; since_check = 0; check_pending = false; }   // new data: the int8 path is measured again
+};
+
+// the global step (linalg.hip; gsd / gss: gsi8.hip).  Readers elsewhere: phase 2 (Bm, Bbar), gp_predict / gp_infer_* (Inv, Linv, E), the guard (Inv),
+// gp_download, gp_finish (gs, gK)
+struct GsState {
+  DevBuf<double> Kmm;         // batch of 2: [Kmm ; A] -> factorised in place into [Lk ; La]
+  DevBuf<double> Lmat;        // [2][Mp][Mp] Cholesky factors
+  DevBuf<double> Linv;        // [2][Mp][Mp] inverse factors
+  DevBuf<double> Inv;         // [2][Mp][Mp] Ki, P
+  DevBuf<double> KmmKeep;     // [Mp][Mp] Kmm (kept for downloads / derivative parts)
+  DevBuf<double> T1;          // [Mp][max(Mp, Dp, 256)] scratch
+  // [Mp][max(Mp, Dp)] scratch.  The step leaves nothing in it that anyone reads: once the step is enqueued phase 2 borrows its first [M][Q] doubles for
+  // the per-row alpha partials (run_phase2: p2_reduce_kernel writes them, colsum2_kernel sums them), and gp_set_local_statistics stages its uploads in it
+  DevBuf<double> T2;
+  DevBuf<double> dFdK;        // [Mp][Mp]
+  DevBuf<double> Bbar;        // [Mp][Mp]
+  DevBuf<double> E;           // [Mp][Dp]
+  DevBuf<double> PsiE;        // [Mp][Dp]
+  DevBuf<double> Abar;        // [Mp][Dp]
+  DevBuf<double> Bm;          // [LDK][Mp] = [2 Bbar ; Abar^T]
+  DevBuf<double> gs;          // [GS_TOTAL] device scalars | failure flags | dots_kernel's partials (the GS_* regions above)
+  DevBuf<double> gK;          // [M*Q + Q] Kmm-parts of grad_Z / grad_alpha (+ regime-B alpha term)
+  DevBuf<int8_t> gsd;         // gsi8.hip (M >= 1024): digit planes of the two double-double-grade products on the int8 matrix core
+  DevBuf<double> gss;         // their column scales
+  double h_gs[GS_COUNT] = {0};
+  bool gs_pending = false;    // a global step was enqueued and its scalars / failure flags have not been read back yet
+  int gs_status = 0;          // outcome of the last global step once read back (GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE, GP_RETRY_JITTER)
+  std::string gs_msg;
+  int jitter_mask = 0;        // bit 0: Kmm, bit 1: Kmm + beta*Psi2 get 1e-7 * I in this global step (partial_terms.py:452-456)
+  int retry_mask = 0;         // what a GP_RETRY_JITTER asks the caller to pass to gp_global_step_jitter
+  bool pred_ok = false;       // Inv / Linv / E describe the statistics buffer as it is now (cleared by whoever changes it or Z)
+  int alloc(gp_ctx* c);
+  int poison(gp_ctx* c);
+};
+
+// phase 2 (psi.hip)
+struct P2State {
+  DevBuf<double> Rpart;       // [2 (p2_slices + 8)][Mp][CXp]
+  int p2_slices = 0;
+  DevBuf<double> HZp;         // [Mp/128][Np][CZp] per-point partials (one array per 128 inducing columns)
+  DevBuf<double> gapart;      // [ga_blocks][Q] per-block alpha partial sums from the per-point kernel
+  int ga_blocks = 0;
+  DevBuf<unsigned long long> p2prog;  // p2_fast8_kernel: [slices][MT] tile progress of the workgroups of a slice (kept in step for the L2), bases grow per launch (allocated on first use)
+  unsigned long long p2_epoch = 0;
+  DevBuf<double> hgpart;      // partial sums of the fast path's mu^2 term of grad_alpha (per wave, or per 256 points from p2_ga_kernel)
+  int alloc(gp_ctx* c);
+  int poison(gp_ctx* c);
+};
+
+// resident CG vectors (the gp_cg_* functions, api.hip): grad_latest/new/old (2,N,Q) each
+struct CgState {
+  DevBuf<double> g_latest;    // written by gp_phase2 with embedding gradients
+  DevBuf<double> g_new;
+  DevBuf<double> g_old;
+  bool have_glatest = false;
+  int alloc(gp_ctx* c);
+};
+
+// gp_set_globals (api.hip): pinned host staging (two slots, [M*Q + Q] doubles each, allocated on first use) so that the upload of Z and alpha is a
+// true asynchronous copy -- an evaluation then has ONE host synchronisation, the read-back in gp_finish; a slot is reused two calls later
+struct GlobSlots {
+  PinnedBuf<double> h_glob[2];
+  hipEvent_t glob_ev[2] = {nullptr, nullptr};
+  int glob_slot = 0;
+  long glob_epoch[2] = {-1, -1};   // gp_ctx::sync_epoch when the slot was last handed to zaug_kernel
+};
+
+}  // namespace gp
+
 struct gp_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   std::string err;
-  // sizes
-  int64_t N = 0;   // local shard rows
-  int64_t Np = 0;  // padded to TILE
+  int64_t N = 0, Np = 0;   // local shard rows, and padded to TILE
   int D = 0, M = 0, Q = 0;
   int Mp = 0, Dp = 0, LDK = 0;  // padded M, D (multiples of TILE) and the row stride of Kaug = Mp + Dp
   int CX = 0, CXp = 0;          // per-point feature columns [f1(Q), f2(Q), 1], padded to 4
@@ -83,12 +183,11 @@ struct gp_ctx {
   double sf2 = 1, beta = 1, step = 0;
   bool regime_A = true;   // every variance exactly zero (fixed embeddings)
   bool xs_raw = false;    // X_S stored in softplus-inverse space
-  bool have_data = false, have_globals = false, have_dir = false, have_glatest = false;
+  bool have_data = false, have_globals = false, have_dir = false;
   int state = 0;          // 0 nothing, 1 phase1 done, 2 stats final (global step done), 3 phase2 done
   bool want_emb = false;
   bool prep_fixa_valid = false;   // regime A, fixed embeddings: the prep kernels' outputs (mu, features, records) are current
-
-  // ---- device buffers ----
+  // ---- the shard's data and what the prep kernels derive from it ----
   gp::DevBuf<double> Kaug;    // [Np][LDK]  Psi1 | Y
   gp::DevBuf<double> Xmu;     // [N][Q] base means
   gp::DevBuf<double> Xs;      // [N][Q] base variances (raw or actual)
@@ -99,99 +198,51 @@ struct gp_ctx {
   gp::DevBuf<double> PU;      // [Np][2*QP+2] packed [mu | u | ln c1] rows for psi1_kernel (QP = Q rounded up to 2, <= 16)
   gp::DevBuf<double> lnc1;    // [Np] ln(sf2) - 1/2 sum ln(a S + 1)
   gp::DevBuf<double> Xa;      // [Np][CXp] per-point features for the n-contraction
+  double sumYY = 0;           // host copy, computed at upload
+  // ---- the globals ----
   gp::DevBuf<double> Z;       // [Mp][Q] (rows >= M zero)
   gp::DevBuf<double> alpha;   // [Q]
   gp::DevBuf<double> Zaug;    // [Mp][CZp]
   gp::DevBuf<double> Zt;      // [Q][Mp] the inducing points transposed (kmm_grads_lds_kernel: lanes = inducing points)
-  gp::DevBuf<int8_t> gsd;     // gsi8.hip (M >= 1024): digit planes of the global step's two double-double-grade products on the int8 matrix core
-  gp::DevBuf<double> gss;     // their column scales
+  // ---- the outputs ----
   gp::DevBuf<double> stats;   // packed: Psi2 [Mp*Mp] | C [Mp*Dp] | scalars [SC_COUNT]
   gp::DevBuf<double> spack;   // Psi2 upper triangle | C [M][D] | scalars: the all-reduce payload across processes (allocated on first use)
-  gp::DevBuf<double> grads;   // packed: gZ_data [M*Q] | galpha_data [Q]
   bool spack_filled = false;  // gp_stats_pack has run since the last gp_phase1 (gp_stats_unpack refuses to run before it)
+  gp::DevBuf<double> grads;   // packed: gZ_data [M*Q] | galpha_data [Q]
+  gp::DevBuf<double> gXmu, gXs;   // [N][Q] each: the embedding gradients
+  gp::PinnedBuf<double> h_out;  // gp_finish: pinned, mapped [GS_HOST | M*Q + Q] -- finish_kernel writes the evaluation's results straight into it
   gp::DevBuf<double> staging; // landing buffer for a peer copy from a shard on another device (gp_buffer_combine)
-  gp::DevBuf<double> part;    // phase-1 split-k partials
-  gp::DevBuf<int> tiles;      // phase-1 tile table (int2)
-  int n_tiles = 0, p1_slices = 0, p1_cps = 0;
-  std::unique_ptr<gp::P1Plan, gp::P1PlanDelete> p1plan;   // regime-A phase-1 plan (job and output tables of p1v2.hip), built on first use
-  std::unique_ptr<gp::I8Plan, gp::I8PlanDelete> i8plan;   // int8 phase 1 (p1i8.hip): digit buffers, job tables; built on first use
-  bool i8_active = false;     // this evaluation's phase 1 runs on the int8 matrix core (psi1_kernel wrote the digits)
-  bool i8_y_valid = false;    // Y's digits are current (reset by gp_upload_shard)
-  bool i8_unsupported = false;  // the int8 plan could not be built for this context (falls back to the float64 kernels)
-  // the int8 path's run-time guard (p1i8.hip, "guard"): 0 = not checked since the last upload, 1 = accepted, 2 = rejected (float64 from then on)
-  int i8_guard = 0;
-  bool i8_check_pending = false;   // this evaluation ran both phase-1 paths: gp_finish reads the comparison and decides
-  long i8_since_check = 0, i8_checks = 0;
-  double i8_rel_psi2 = 0, i8_rel_c = 0, i8_cond_lb = 0;
-  gp::DevBuf<double> i8_cmp;       // device: [4] squared Frobenius norms (dPsi2, Psi2, dC, C) | [2] max diag(Psi2), max diag(P) | partials
-  gp::DevBuf<int> bmap;       // phase-1 block -> (slice, tile type) placement table
-  int bmap_T = -1, bmap_S = -1, bmap_blocks = 0;
-  gp::DevBuf<double> klpart;  // [blocks] partial KL sums
-  int kl_blocks = 0;
-  double sumYY = 0;           // host copy, computed at upload
-  // global step
-  gp::DevBuf<double> Kmm;     // batch of 2: [Kmm ; A] -> factorised in place into [Lk ; La]
-  gp::DevBuf<double> Lmat;    // [2][Mp][Mp] Cholesky factors
-  gp::DevBuf<double> Linv;    // [2][Mp][Mp] inverse factors
-  gp::DevBuf<double> Inv;     // [2][Mp][Mp] Ki, P
-  gp::DevBuf<double> KmmKeep; // [Mp][Mp] Kmm (kept for downloads / derivative parts)
-  gp::DevBuf<double> T1;      // [Mp][Mp] scratch
-  gp::DevBuf<double> T2;      // [Mp][Mp] scratch
-  gp::DevBuf<double> dFdK;    // [Mp][Mp]
-  gp::DevBuf<double> Bbar;    // [Mp][Mp]
-  gp::DevBuf<double> E;       // [Mp][Dp]
-  gp::DevBuf<double> PsiE;    // [Mp][Dp]
-  gp::DevBuf<double> Abar;    // [Mp][Dp]
-  gp::DevBuf<double> Bm;      // [LDK][Mp] = [2 Bbar ; Abar^T]
-  gp::DevBuf<double> gs;      // [GS_COUNT] device scalars
-  gp::DevBuf<double> gK;      // [M*Q + Q] Kmm-parts of grad_Z / grad_alpha (+ regime-B alpha term)
-  double h_gs[gp::GS_COUNT] = {0};
-  bool gs_pending = false;    // a global step was enqueued and its scalars / failure flags have not been read back yet
-  int gs_status = 0;          // outcome of the last global step once read back (GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE, GP_RETRY_JITTER)
-  std::string gs_msg;
-  int jitter_mask = 0;        // bit 0: Kmm, bit 1: Kmm + beta*Psi2 get 1e-7 * I in this global step (partial_terms.py:452-456)
-  int retry_mask = 0;         // what a GP_RETRY_JITTER asks the caller to pass to gp_global_step_jitter
-  // phase 2
-  gp::DevBuf<double> Rpart;   // [p2_slices][Mp][CXp]
-  int p2_slices = 0;
-  gp::DevBuf<double> HZp;     // [Mp/128][Np][CZp] per-point partials (one array per 128 inducing columns)
-  gp::DevBuf<double> gXmu;    // [N][Q]
-  gp::DevBuf<double> gXs;     // [N][Q]
-  gp::DevBuf<double> gapart;  // [blocks][Q] per-block alpha partial sums from the per-point kernel
-  int ga_blocks = 0;
-  gp::DevBuf<unsigned long long> p2prog;  // p2_fast8_kernel: [slices][MT] tile progress of the workgroups of a slice (kept in step for the L2), bases grow per launch
-  unsigned long long p2_epoch = 0;
-  gp::DevBuf<double> hgpart;  // partial sums of the fast path's mu^2 term of grad_alpha (per wave, or per 256 points from p2_ga_kernel)
-  std::unique_ptr<gp::BPlan, gp::BPlanDelete> bplan;          // regime B (variances > 0): the pairwise psi2 kernels' plan (psi2_plan.h), built on first use
-  bool pred_ok = false;       // the global step's Inv / Linv / E describe the statistics buffer as it is now (cleared whenever it or Z changes)
-  std::unique_ptr<gp::PredPlan, gp::PredPlanDelete> pred;     // gp_predict's buffers (predict.hip), built on first use
-  std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip), built on first use
-  std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip), built on first use
-  // CG vectors (resident): grad_latest/new/old (2,N,Q) each
-  gp::DevBuf<double> g_latest;
-  gp::DevBuf<double> g_new;
-  gp::DevBuf<double> g_old;
-  // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
-  void* comm = nullptr;
+  // ---- the stages' own state (each struct above, next to its alloc / poison) and what they may borrow ----
+  gp::P1Tiles p1t;
+  gp::I8Guard i8;
+  gp::GsState gstep;
+  gp::P2State p2;
+  gp::CgState cg;
+  gp::GlobSlots glob;
+  gp::Workspace ws;           // the one borrowed workspace (devbuf.h): a stage takes it for the length of its own launches
+  gp::DevBuf<double> red;     // [8192] per-block partials of the host-side reductions (sum_YYT at upload, gp_cg_dots, gp_cg_abs)
+  // ---- plans of the on-demand features, each built on first use ----
+  std::unique_ptr<gp::P1Plan, gp::P1PlanDelete> p1plan;   // regime-A phase-1 plan (job and output tables of p1v2.hip)
+  std::unique_ptr<gp::I8Plan, gp::I8PlanDelete> i8plan;   // int8 phase 1 (p1i8.hip): digit buffers, job tables
+  std::unique_ptr<gp::BPlan, gp::BPlanDelete> bplan;          // regime B (variances > 0): the pairwise psi2 kernels' plan (psi2_plan.h)
+  std::unique_ptr<gp::PredPlan, gp::PredPlanDelete> pred;     // gp_predict's buffers (predict.hip)
+  std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip)
+  std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip)
+  void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
-  // gp_set_globals: pinned host staging (two slots, [M*Q + Q] doubles each) so that the upload of Z and alpha is a true asynchronous copy --
-  // an evaluation then has ONE host synchronisation, the read-back in gp_finish; the slot's event guards its reuse two calls later
-  gp::PinnedBuf<double> h_glob[2];
-  hipEvent_t glob_ev[2] = {nullptr, nullptr};
-  int glob_slot = 0;
-  gp::PinnedBuf<double> h_out;  // gp_finish: pinned, mapped [GS_COUNT + 8 | M*Q + Q] -- finish_kernel writes the evaluation's results straight into it
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
   // evaluation's first and last event (total_ms), 0 = none.  Every recorded event is a signal packet the stream waits on: ~4-7 us of idle
   // stream each, thirteen per evaluation -- 0.3 % of an evaluation at configs[2]'s size, 15 % at configs[1]'s (gp_set_timing)
   int timing = [] { const char* e = getenv("GPARML_TIMING"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }();
   long sync_epoch = 0;        // stream synchronisations seen so far (gp_set_globals' pinned slots are reused without an event once one has passed)
-  long glob_epoch[2] = {-1, -1};
   hipEvent_t ev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double t_ms[5] = {0, 0, 0, 0, 0};
 };
 
 namespace gp {
 extern thread_local std::string g_create_error;
+// poison mode (devbuf.h, g_opt_poison): refills a buffer an evaluation must write before it reads (the stages' poison() and api.hip's poison_scratch)
+inline hipError_t poison_fill(gp_ctx* c, const DevBuf<double>& b) { return b.size() ? hipMemsetAsync(b, 0xFF, b.bytes(), c->stream) : hipSuccess; }
 
 // psi.hip
 int run_upload_y(gp_ctx* c, const double* dY);
@@ -239,10 +290,10 @@ bool gs_i8_wanted(const gp_ctx* c);
 int run_gs_i8_product(gp_ctx* c, hipStream_t st, const double* A, long lda, int nA, const double* B, long ldb, int nB, int K, double* out, long ldo,
                       const double* Csub);
 int check_global(gp_ctx* c);
-// the same with the scalars + failure flags already on the host (h = [GS_COUNT + 8] doubles, or NULL when nothing is pending)
+// the same with the scalars + failure flags already on the host (h = [GS_HOST] doubles, or NULL when nothing is pending)
 int check_global_from(gp_ctx* c, const double* h);
 // PRECONDITION: the 128-blocks of Linv strictly above the block diagonal must be ZERO on entry -- they are never written here and
-// Inv = Linv^T Linv reads the whole matrix.  gp_create allocates Linv zeroed and nothing else writes those blocks; the test hook
+// Inv = Linv^T Linv reads the whole matrix.  GsState::alloc allocates Linv zeroed and nothing else writes those blocks; the test hook
 // gp_debug_potrf_inverse memsets its own buffer.  A caller that hands in a reused scratch buffer must clear it first.
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A /*in: SPD, out: L*/, double* Linv, double* Inv,
                           double* Twork /*batch * Mp * Mp / 2 doubles*/, double* logdet2 /*device, [batch]*/, double* fail_flag /*device, [batch]*/,

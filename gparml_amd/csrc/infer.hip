@@ -569,14 +569,14 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
   std::vector<int> hc(Do);
   for (int j = 0; j < Do; ++j) hc[j] = cols ? cols[j] : j;
   GP_HIP(c, hipMemcpyAsync(p.cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
+  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->gstep.E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
   hipLaunchKernelGGL(inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, st, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
   GP_HIP(c, hipGetLastError());
   GemmP g;
   g.K = (int)Dop; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
   g.A = k.Eo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = p.T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
   launch_gemm(st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g);
-  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, p.T, c->Inv, (int)M, (int)Mp, (double)Do, p.Gf);
+  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, p.T, c->gstep.Inv, (int)M, (int)Mp, (double)Do, p.Gf);
   GP_HIP(c, hipGetLastError());
   // the observed columns of every row, packed on the host: the others are never read
   std::vector<double> yc((size_t)n * Do);

@@ -690,9 +690,9 @@ std::atomic<int> g_opt_gs_tail{env_on("GPARML_GS_TAIL") ? 1 : 0};
 // Host side of the global step's outcome: one D2H of the scalars + failure flags, at the first call that needs them
 // (gp_global_status, gp_finish, gp_download).  Returns GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE or GP_RETRY_JITTER.
 int check_global(gp_ctx* c) {
-  if (c->gs_pending) {
-    double h[GS_COUNT + 8];
-    GP_HIP(c, hipMemcpyAsync(h, c->gs, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  if (c->gstep.gs_pending) {
+    double h[GS_HOST];
+    GP_HIP(c, hipMemcpyAsync(h, c->gstep.gs, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
     return check_global_from(c, h);
@@ -701,31 +701,57 @@ int check_global(gp_ctx* c) {
 }
 
 int check_global_from(gp_ctx* c, const double* h) {
-  if (c->gs_pending && h) {
-    for (int i = 0; i < GS_COUNT; ++i) c->h_gs[i] = h[i];
-    c->gs_pending = false;
-    const int failed = (h[GS_COUNT] != 0.0 ? 1 : 0) | (h[GS_COUNT + 1] != 0.0 ? 2 : 0);
-    const bool singular = h[GS_COUNT] == 2.0 || h[GS_COUNT + 1] == 2.0;
+  if (c->gstep.gs_pending && h) {
+    for (int i = 0; i < GS_COUNT; ++i) c->gstep.h_gs[i] = h[i];
+    c->gstep.gs_pending = false;
+    const int failed = (h[GS_FLAGS] != 0.0 ? 1 : 0) | (h[GS_FLAGS + 1] != 0.0 ? 2 : 0);
+    const bool singular = h[GS_FLAGS] == 2.0 || h[GS_FLAGS + 1] == 2.0;
     if (singular) {
       // an exactly zero pivot: the reference fails in linalg.inv before any jitter applies (partial_terms.py:60, 95)
-      c->gs_status = GP_ERR_NOT_PD;
-      c->gs_msg = std::string(h[GS_COUNT] == 2.0 ? "Kmm" : "Kmm + beta*Psi2") + " is singular (numpy.linalg.inv: Singular matrix)";
-    } else if (failed & ~c->jitter_mask) {
+      c->gstep.gs_status = GP_ERR_NOT_PD;
+      c->gstep.gs_msg = std::string(h[GS_FLAGS] == 2.0 ? "Kmm" : "Kmm + beta*Psi2") + " is singular (numpy.linalg.inv: Singular matrix)";
+    } else if (failed & ~c->gstep.jitter_mask) {
       // first failure of this matrix: the reference continues with 1e-7 * I added (partial_terms.py:452-456)
-      c->retry_mask = c->jitter_mask | failed;
-      c->gs_status = GP_RETRY_JITTER;
-      c->gs_msg = std::string(failed & 1 ? "Kmm" : "Kmm + beta*Psi2") + " is not positive definite (Cholesky failed); retry with 1e-7 jitter";
+      c->gstep.retry_mask = c->gstep.jitter_mask | failed;
+      c->gstep.gs_status = GP_RETRY_JITTER;
+      c->gstep.gs_msg = std::string(failed & 1 ? "Kmm" : "Kmm + beta*Psi2") + " is not positive definite (Cholesky failed); retry with 1e-7 jitter";
     } else if (failed) {
-      c->gs_status = GP_ERR_NOT_PD;
-      c->gs_msg = std::string(failed & 1 ? "Kmm" : "Kmm + beta*Psi2") + " is not positive definite even with 1e-7 jitter (partial_terms.py:459-461 assertion)";
+      c->gstep.gs_status = GP_ERR_NOT_PD;
+      c->gstep.gs_msg = std::string(failed & 1 ? "Kmm" : "Kmm + beta*Psi2") + " is not positive definite even with 1e-7 jitter (partial_terms.py:459-461 assertion)";
     } else if (!std::isfinite(h[GS_F])) {
-      c->gs_status = GP_ERR_NON_FINITE;
-      c->gs_msg = "bound is not finite";
+      c->gstep.gs_status = GP_ERR_NON_FINITE;
+      c->gstep.gs_msg = "bound is not finite";
     } else {
-      c->gs_status = GP_OK;
+      c->gstep.gs_status = GP_OK;
     }
   }
-  if (c->gs_status != GP_OK) return fail(c, c->gs_status, "%s", c->gs_msg.c_str());
+  if (c->gstep.gs_status != GP_OK) return fail(c, c->gstep.gs_status, "%s", c->gstep.gs_msg.c_str());
+  return GP_OK;
+}
+
+int GsState::alloc(gp_ctx* c) {
+  const long Mp = c->Mp, Dp = c->Dp;
+  int rc = GP_OK;
+  auto A = [&](auto& b, size_t n, int mode = DA_INIT) { if (rc == GP_OK) rc = b.alloc(c, n, mode); };
+  A(Kmm, (size_t)2 * Mp * Mp); A(Lmat, (size_t)2 * Mp * Mp); A(Inv, (size_t)2 * Mp * Mp);
+  A(Linv, (size_t)2 * Mp * Mp, DA_ZERO);   // zero contract: the 128-blocks above the block diagonal are never written (potrf_inverse_batched's precondition)
+  if (Mp >= 512 && Mp <= 2048) {
+    // gsi8.hip: ten digit planes of W = [A | B] for the larger of the two products (K_mm^-1 | Psi2: 2 Mp columns; K_mm + beta Psi2 | E: Mp + Dp), and W's column scales
+    const size_t wcols = (size_t)Mp + std::max(Mp, Dp);
+    A(gsd, (size_t)10 * Mp * wcols);
+    A(gss, wcols);
+  }
+  A(KmmKeep, (size_t)Mp * Mp); A(T1, (size_t)Mp * std::max<long>(std::max(Mp, Dp), 256)); A(T2, (size_t)Mp * std::max(Mp, Dp));
+  A(dFdK, (size_t)Mp * Mp); A(Bbar, (size_t)Mp * Mp);
+  A(E, (size_t)Mp * Dp); A(PsiE, (size_t)Mp * Dp); A(Abar, (size_t)Mp * Dp);
+  A(Bm, (size_t)c->LDK * Mp);
+  A(gs, (size_t)GS_TOTAL);
+  A(gK, (size_t)c->M * c->Q + c->Q);
+  return rc;
+}
+// (not Linv: its upper blocks are a zero contract)
+int GsState::poison(gp_ctx* c) {
+  for (const DevBuf<double>* b : {&Kmm, &Lmat, &Inv, &KmmKeep, &T1, &T2, &dFdK, &Bbar, &E, &PsiE, &Abar, &Bm, &gK, &gs}) GP_HIP(c, poison_fill(c, *b));
   return GP_OK;
 }
 
@@ -736,33 +762,33 @@ int run_global_step(gp_ctx* c) {
   double* Psi2 = c->stats;
   double* C = c->stats + mm;
   double* sc = c->stats + mm + (long)Mp * Dp;
-  c->gs_status = GP_OK;
-  double* failf = c->gs + GS_COUNT;  // [2]
+  c->gstep.gs_status = GP_OK;
+  double* failf = c->gstep.gs + GS_FLAGS;  // [2]
   // T2 is free until G = K_mm^-1 Psi2 is formed: it keeps A for the double-double residual of the refinement step
   const bool gi8 = gs_i8_wanted(c);            // gsi8.hip: both double-double products on the int8 matrix core (M >= 1024)
   const bool res_dd = g_opt_refine_E.load() && ((g_opt_residual_dd.load() && Mp >= 256 && Dp >= 512) || gi8);   // narrow E: too few waves (M = 512, D = 100: +21 us)
-  hipLaunchKernelGGL(build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, st, c->Z, c->alpha, c->sf2, c->beta, Psi2, M, Mp, Q, c->Kmm, c->Kmm + mm,
-                     c->KmmKeep, (c->jitter_mask & 1) ? 1e-7 : 0.0, (c->jitter_mask & 2) ? 1e-7 : 0.0, c->gs, res_dd ? c->T2 : (double*)nullptr);
+  hipLaunchKernelGGL(build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, st, c->Z, c->alpha, c->sf2, c->beta, Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
+                     c->gstep.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, c->gstep.gs, res_dd ? c->gstep.T2 : (double*)nullptr);
   GP_HIP(c, hipGetLastError());
   // one-panel problems (M, D <= 128): the panel kernel, then seven launches of tail_stage_kernel instead of fifteen kernels
   if (Mp == NB && Dp == NB && g_opt_gs_tail.load()) {
     GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
     GP_HIP(c, hipFuncSetAttribute((const void*)tail_stage_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_DOUBLES * 8));
-    hipLaunchKernelGGL(potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, st, c->Kmm, (long)Mp, mm, 0, c->Linv, failf, c->gs + GS_LOGDET_K);
+    hipLaunchKernelGGL(potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, st, c->gstep.Kmm, (long)Mp, mm, 0, c->gstep.Linv, failf, c->gstep.gs + GS_LOGDET_K);
     TailP t;
-    t.Linv = c->Linv; t.Inv = c->Inv; t.Psi2 = Psi2; t.C = C; t.sc = sc; t.Keep = c->KmmKeep;
-    t.E = c->E; t.PsiE = c->PsiE; t.T1 = c->T1; t.T2 = c->T2; t.dFdK = c->dFdK; t.Bbar = c->Bbar; t.Abar = c->Abar; t.Bm = c->Bm;
-    t.Z = c->Z; t.alpha = c->alpha; t.gs = c->gs; t.gK = c->gK;
-    t.beta = c->beta; t.sf2 = c->sf2; t.Dd = (double)D; t.Nglob = (double)c->N_global; t.jitA = (c->jitter_mask & 2) ? 1e-7 : 0.0;
+    t.Linv = c->gstep.Linv; t.Inv = c->gstep.Inv; t.Psi2 = Psi2; t.C = C; t.sc = sc; t.Keep = c->gstep.KmmKeep;
+    t.E = c->gstep.E; t.PsiE = c->gstep.PsiE; t.T1 = c->gstep.T1; t.T2 = c->gstep.T2; t.dFdK = c->gstep.dFdK; t.Bbar = c->gstep.Bbar; t.Abar = c->gstep.Abar; t.Bm = c->gstep.Bm;
+    t.Z = c->Z; t.alpha = c->alpha; t.gs = c->gstep.gs; t.gK = c->gstep.gK;
+    t.beta = c->beta; t.sf2 = c->sf2; t.Dd = (double)D; t.Nglob = (double)c->N_global; t.jitA = (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0;
     t.M = M; t.Q = Q; t.regimeA = c->regime_A ? 1 : 0; t.refine = g_opt_refine_E.load(); t.dd = g_opt_dd_kipsi2.load();
     t.jobs.n = 7;
-    t.jobs.j[0] = {c->Inv, Psi2, Mp, M, M, GS_TR_KIPSI2};
-    t.jobs.j[1] = {c->Inv + mm, Psi2, Mp, M, M, GS_TR_PPSI2};
-    t.jobs.j[2] = {C, c->E, Dp, M, D, GS_TR_CE};
-    t.jobs.j[3] = {c->E, c->PsiE, Dp, M, D, GS_TR_EPSI2E};
-    t.jobs.j[4] = {c->dFdK, c->KmmKeep, Mp, M, M, GS_SUM_V};
-    t.jobs.j[5] = {c->Abar, C, Dp, M, D, GS_SUM_AC};
-    t.jobs.j[6] = {c->Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
+    t.jobs.j[0] = {c->gstep.Inv, Psi2, Mp, M, M, GS_TR_KIPSI2};
+    t.jobs.j[1] = {c->gstep.Inv + mm, Psi2, Mp, M, M, GS_TR_PPSI2};
+    t.jobs.j[2] = {C, c->gstep.E, Dp, M, D, GS_TR_CE};
+    t.jobs.j[3] = {c->gstep.E, c->gstep.PsiE, Dp, M, D, GS_TR_EPSI2E};
+    t.jobs.j[4] = {c->gstep.dFdK, c->gstep.KmmKeep, Mp, M, M, GS_SUM_V};
+    t.jobs.j[5] = {c->gstep.Abar, C, Dp, M, D, GS_SUM_AC};
+    t.jobs.j[6] = {c->gstep.Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
     for (int stage = 0; stage < TAIL_STAGES; ++stage) {
       const int items = tail_items(stage, M, Q, t.refine, t.dd);
       // only the stages with tile products need the operand images
@@ -770,17 +796,18 @@ int run_global_step(gp_ctx* c) {
       if (items > 0) hipLaunchKernelGGL(tail_stage_kernel, dim3(items), dim3(256), lds, st, t, stage);
     }
     GP_HIP(c, hipGetLastError());
-    c->gs_pending = true;
+    c->gstep.gs_pending = true;
     return GP_OK;
   }
   // factorise [Kmm ; A] in place, invert.  T1 is the 2 x 128 x Mp work panel.
-  // split-k workspace: the phase-1 partial buffer is free during the global step (>= 600 tiles)
-  double* ws = c->part;
-  const size_t wcap = c->part.size();
-  int rc = potrf_inverse_batched(c, st, Mp, 2, c->Kmm, c->Linv, c->Inv, c->T1, c->gs + GS_LOGDET_K, failf, ws, wcap);
+  // split-k workspace: the shared workspace is free during the global step (>= 600 tiles); the split factors follow its shape-derived capacity
+  double* ws = nullptr;
+  const size_t wcap = c->ws.capacity;
+  GP_TRY_RC(c->ws.take(c, wcap, "global step", &ws));
+  int rc = potrf_inverse_batched(c, st, Mp, 2, c->gstep.Kmm, c->gstep.Linv, c->gstep.Inv, c->gstep.T1, c->gstep.gs + GS_LOGDET_K, failf, ws, wcap);
   if (rc != GP_OK) return rc;
-  double* Ki = c->Inv;
-  double* P = c->Inv + mm;
+  double* Ki = c->gstep.Inv;
+  double* P = c->gstep.Inv + mm;
   // E = P C ; PsiE = Psi2 E ; T1 = E E^T   and, independent of it,   T2 = Ki Psi2 ; dFdK(tmp) = T2 Ki.   One stream: a side stream for the second
   // chain was measured slower (r03: 0.424 -> 0.455 ms at M = 512 -- every cross-stream event edge costs more than the 5-12 us product it hides)
   // and was removed in r06.
@@ -795,72 +822,72 @@ int run_global_step(gp_ctx* c) {
   const int bigMM = (bigok && (long)(Mp / TILE) * (Mp / TILE) * spMM >= 256) ? 1 : 0;
   g.ws = ws;
   g.big = bigMD; g.splits = bigMD ? spMD : 1;
-  g.A = P; g.lda = Mp; g.B = C; g.ldb = Dp; g.C = c->E; g.ldc = Dp;
+  g.A = P; g.lda = Mp; g.B = C; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp;
   launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
   // one refinement step of E with a double-double residual (PsiE is free until the next product); GPARML_REFINE_E=0 turns it off
   if (g_opt_refine_E.load()) {
     if (gi8) {
-      GP_TRY_RC(run_gs_i8_product(c, st, c->T2, (long)Mp, Mp, c->E, (long)Dp, Dp, Mp, c->PsiE, (long)Dp, C));
+      GP_TRY_RC(run_gs_i8_product(c, st, c->gstep.T2, (long)Mp, Mp, c->gstep.E, (long)Dp, Dp, Mp, c->gstep.PsiE, (long)Dp, C));
     } else if (res_dd) {
-      hipLaunchKernelGGL((ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, st, c->T2, (long)Mp, c->E, (long)Dp, Mp, C, c->PsiE);
+      hipLaunchKernelGGL((ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, st, c->gstep.T2, (long)Mp, c->gstep.E, (long)Dp, Mp, C, c->gstep.PsiE);
     } else {
-      hipLaunchKernelGGL(solve_residual_kernel, dim3(M), dim3(512), 0, st, c->KmmKeep, Psi2, c->beta, (c->jitter_mask & 2) ? 1e-7 : 0.0, C, c->E, M, Mp, Dp,
-                         c->PsiE, 0);
-      if (M < Mp) GP_HIP(c, hipMemsetAsync(c->PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
+      hipLaunchKernelGGL(solve_residual_kernel, dim3(M), dim3(512), 0, st, c->gstep.KmmKeep, Psi2, c->beta, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, C, c->gstep.E, M, Mp, Dp,
+                         c->gstep.PsiE, 0);
+      if (M < Mp) GP_HIP(c, hipMemsetAsync(c->gstep.PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
     }
     GP_HIP(c, hipGetLastError());
-    g.A = P; g.lda = Mp; g.B = c->PsiE; g.ldb = Dp; g.C = c->E; g.ldc = Dp; g.beta = 1.0;
+    g.A = P; g.lda = Mp; g.B = c->gstep.PsiE; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp; g.beta = 1.0;
     launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
     g.beta = 0.0;
   }
-  g.A = Psi2; g.lda = Mp; g.B = c->E; g.ldb = Dp; g.C = c->PsiE; g.ldc = Dp;
+  g.A = Psi2; g.lda = Mp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.PsiE; g.ldc = Dp;
   launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
-  g.K = Dp; g.A = c->E; g.lda = Dp; g.B = c->E; g.ldb = Dp; g.C = c->T1; g.ldc = Mp;   // B(k,j) = E[j][k] -> K_CONTIG
+  g.K = Dp; g.A = c->gstep.E; g.lda = Dp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.T1; g.ldc = Mp;   // B(k,j) = E[j][k] -> K_CONTIG
   { const int sps = g.splits; g.splits = 1; g.big = 0; launch_gemm(st, K_CONTIG, K_CONTIG, Mp, Mp, 1, g); g.splits = sps; }
   // G = Ki Psi2 with double-double accumulation (ddacc_gemm_kernel above: two rows per wave, eight k per trip -- same-box timing of six shapes
   // in profiles/r04_dd_variants.txt: +50 us at M = 512, +9 us at M = 128, +0.29 ms at M = 1024 over the float64 matrix-core product of r03, which
   // GPARML_DD_KIPSI2=0 or gp_debug_set_option("dd_kipsi2", 0) restores)
   if (g_opt_dd_kipsi2.load() && gi8) {
-    GP_TRY_RC(run_gs_i8_product(c, st, Ki, (long)Mp, Mp, Psi2, (long)Mp, Mp, Mp, c->T2, (long)Mp, nullptr));
+    GP_TRY_RC(run_gs_i8_product(c, st, Ki, (long)Mp, Mp, Psi2, (long)Mp, Mp, Mp, c->gstep.T2, (long)Mp, nullptr));
   } else if (g_opt_dd_kipsi2.load()) {
-    hipLaunchKernelGGL((ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, st, Ki, (long)Mp, Psi2, (long)Mp, Mp, c->T2, (long)Mp);
+    hipLaunchKernelGGL((ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, st, Ki, (long)Mp, Psi2, (long)Mp, Mp, c->gstep.T2, (long)Mp);
     GP_HIP(c, hipGetLastError());
   } else {
-    g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1; g.A = Ki; g.lda = Mp; g.B = Psi2; g.ldb = Mp; g.C = c->T2; g.ldc = Mp;
+    g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1; g.A = Ki; g.lda = Mp; g.B = Psi2; g.ldb = Mp; g.C = c->gstep.T2; g.ldc = Mp;
     launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g);
   }
   g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1;
-  g.A = c->T2; g.lda = Mp; g.B = Ki; g.ldb = Mp; g.C = c->dFdK; g.ldc = Mp;
+  g.A = c->gstep.T2; g.lda = Mp; g.B = Ki; g.ldb = Mp; g.C = c->gstep.dFdK; g.ldc = Mp;
   launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g);
   GP_HIP(c, hipGetLastError());
   // dFdK currently holds Ki Psi2 Ki; assemble in place is unsafe (reads KPK, writes dFdK at the same index: fine, same thread)
-  hipLaunchKernelGGL(assemble_kernel, dim3(1024), dim3(256), 0, st, Ki, P, c->T1, c->dFdK, c->E, c->beta, (double)D, Mp, Dp, c->Bbar,
-                     c->dFdK, c->Abar, c->Bm);
+  hipLaunchKernelGGL(assemble_kernel, dim3(1024), dim3(256), 0, st, Ki, P, c->gstep.T1, c->gstep.dFdK, c->gstep.E, c->beta, (double)D, Mp, Dp, c->gstep.Bbar,
+                     c->gstep.dFdK, c->gstep.Abar, c->gstep.Bm);
   GP_HIP(c, hipGetLastError());
   DotJobs jobs;
   jobs.n = 7;
   jobs.j[0] = {Ki, Psi2, Mp, M, M, GS_TR_KIPSI2};
   jobs.j[1] = {P, Psi2, Mp, M, M, GS_TR_PPSI2};
-  jobs.j[2] = {C, c->E, Dp, M, D, GS_TR_CE};
-  jobs.j[3] = {c->E, c->PsiE, Dp, M, D, GS_TR_EPSI2E};
-  jobs.j[4] = {c->dFdK, c->KmmKeep, Mp, M, M, GS_SUM_V};
-  jobs.j[5] = {c->Abar, C, Dp, M, D, GS_SUM_AC};
-  jobs.j[6] = {c->Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
-  double* dpart = c->gs + GS_COUNT + 8;   // [jobs][DOT_BLOCKS]
+  jobs.j[2] = {C, c->gstep.E, Dp, M, D, GS_TR_CE};
+  jobs.j[3] = {c->gstep.E, c->gstep.PsiE, Dp, M, D, GS_TR_EPSI2E};
+  jobs.j[4] = {c->gstep.dFdK, c->gstep.KmmKeep, Mp, M, M, GS_SUM_V};
+  jobs.j[5] = {c->gstep.Abar, C, Dp, M, D, GS_SUM_AC};
+  jobs.j[6] = {c->gstep.Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
+  double* dpart = c->gstep.gs + GS_DOTS;   // [jobs][DOT_BLOCKS]
   // the traces / scalars and the Kmm parts of the gradients both start from the assembled partials and do not touch each other's outputs
   hipLaunchKernelGGL(dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, st, jobs, dpart);
-  hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(64), 0, st, sc, c->gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
+  hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(64), 0, st, sc, c->gstep.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
   // Kmm parts of grad_Z / grad_alpha; alpha partials per row go through T2 (free again)
   static const bool kmm_lds = [] { const char* e = getenv("GPARML_KMM_LDS"); return !(e && e[0] == '0'); }();
   if (kmm_lds && M <= 2048)
-    hipLaunchKernelGGL(kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), st, c->dFdK, c->KmmKeep, c->Bbar, Psi2, c->Z,
-                       c->Zt, c->alpha, M, Mp, Q, c->regime_A ? 1 : 0, c->gK, c->T2);
+    hipLaunchKernelGGL(kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), st, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z,
+                       c->Zt, c->alpha, M, Mp, Q, c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
   else
-    hipLaunchKernelGGL(kmm_grads_kernel, dim3(M), dim3(128), 0, st, c->dFdK, c->KmmKeep, c->Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
-                       c->regime_A ? 1 : 0, c->gK, c->T2);
-  hipLaunchKernelGGL(colsum_kernel, dim3(Q), dim3(256), 0, st, c->T2, M, Q, c->gK + (long)M * Q);
+    hipLaunchKernelGGL(kmm_grads_kernel, dim3(M), dim3(128), 0, st, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
+                       c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
+  hipLaunchKernelGGL(colsum_kernel, dim3(Q), dim3(256), 0, st, c->gstep.T2, M, Q, c->gstep.gK + (long)M * Q);
   GP_HIP(c, hipGetLastError());
-  c->gs_pending = true;   // scalars and failure flags are read back at the next host synchronisation point (check_global)
+  c->gstep.gs_pending = true;   // scalars and failure flags are read back at the next host synchronisation point (check_global)
   return GP_OK;
 }
 
@@ -926,30 +953,30 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   GP_HIP(c, hipSetDevice(c->device));
   const long mm = (long)c->Mp * c->Mp, md = (long)c->Mp * c->Dp;
   const double* src = nullptr; long cnt = 0;
-  if (!std::strcmp(name, "Linv")) { src = c->Linv; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "Inv")) { src = c->Inv; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "E")) { src = c->E; cnt = md; }
-  else if (!std::strcmp(name, "PsiE")) { src = c->PsiE; cnt = md; }
-  else if (!std::strcmp(name, "T1")) { src = c->T1; cnt = mm; }
-  else if (!std::strcmp(name, "T2")) { src = c->T2; cnt = mm; }
-  else if (!std::strcmp(name, "dFdK")) { src = c->dFdK; cnt = mm; }
-  else if (!std::strcmp(name, "Bbar")) { src = c->Bbar; cnt = mm; }
-  else if (!std::strcmp(name, "Abar")) { src = c->Abar; cnt = md; }
-  else if (!std::strcmp(name, "Bm")) { src = c->Bm; cnt = (long)c->LDK * c->Mp; }
-  else if (!std::strcmp(name, "gK")) { src = c->gK; cnt = (long)c->M * c->Q + c->Q; }
-  else if (!std::strcmp(name, "gs")) { src = c->gs; cnt = GS_COUNT + 8 + 8 * 64; }
+  if (!std::strcmp(name, "Linv")) { src = c->gstep.Linv; cnt = 2 * mm; }
+  else if (!std::strcmp(name, "Inv")) { src = c->gstep.Inv; cnt = 2 * mm; }
+  else if (!std::strcmp(name, "E")) { src = c->gstep.E; cnt = md; }
+  else if (!std::strcmp(name, "PsiE")) { src = c->gstep.PsiE; cnt = md; }
+  else if (!std::strcmp(name, "T1")) { src = c->gstep.T1; cnt = mm; }
+  else if (!std::strcmp(name, "T2")) { src = c->gstep.T2; cnt = mm; }
+  else if (!std::strcmp(name, "dFdK")) { src = c->gstep.dFdK; cnt = mm; }
+  else if (!std::strcmp(name, "Bbar")) { src = c->gstep.Bbar; cnt = mm; }
+  else if (!std::strcmp(name, "Abar")) { src = c->gstep.Abar; cnt = md; }
+  else if (!std::strcmp(name, "Bm")) { src = c->gstep.Bm; cnt = (long)c->LDK * c->Mp; }
+  else if (!std::strcmp(name, "gK")) { src = c->gstep.gK; cnt = (long)c->M * c->Q + c->Q; }
+  else if (!std::strcmp(name, "gs")) { src = c->gstep.gs; cnt = (long)c->gstep.gs.size(); }
   // r06 (poison probe, tests/devtools/dev_poison_probe.py): the padded device images of the evaluation's other buffers
   else if (!std::strcmp(name, "stats")) { src = c->stats; cnt = mm + md + SC_COUNT; }
   else if (!std::strcmp(name, "Kaug")) { src = c->Kaug; cnt = (long)c->Np * c->LDK; }
-  else if (!std::strcmp(name, "Kmm")) { src = c->Kmm; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "KmmKeep")) { src = c->KmmKeep; cnt = mm; }
+  else if (!std::strcmp(name, "Kmm")) { src = c->gstep.Kmm; cnt = 2 * mm; }
+  else if (!std::strcmp(name, "KmmKeep")) { src = c->gstep.KmmKeep; cnt = mm; }
   else if (!std::strcmp(name, "Z")) { src = c->Z; cnt = (long)c->Mp * c->Q; }
   else if (!std::strcmp(name, "Zaug")) { src = c->Zaug; cnt = (long)c->Mp * c->CZp; }
   else if (!std::strcmp(name, "mu")) { src = c->mu; cnt = (long)c->Np * c->Q; }
   else if (!std::strcmp(name, "S")) { src = c->S; cnt = (long)c->Np * c->Q; }
   else if (!std::strcmp(name, "Xa")) { src = c->Xa; cnt = (long)c->Np * c->CXp; }
   else if (!std::strcmp(name, "grads")) { src = c->grads; cnt = (long)c->M * c->Q + c->Q; }
-  else if (!std::strcmp(name, "Rpart")) { src = c->Rpart; cnt = (long)2 * (c->p2_slices + 8) * c->Mp * c->CXp; }
+  else if (!std::strcmp(name, "Rpart")) { src = c->p2.Rpart; cnt = (long)c->p2.Rpart.size(); }
   else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);

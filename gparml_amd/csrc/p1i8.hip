@@ -278,27 +278,27 @@ struct I8Plan {
   DevBuf<double> dpart; int row_blocks = 0;        // [row_blocks][Mp] sums of squares of Psi1's columns per psi1_kernel workgroup (the exact diagonal of Psi2)
   DevBuf<double> diag;                             // [Mp] their sums (p1i8_diag_kernel)
   DevBuf<I8Job> jobs; DevBuf<I8Out> outs;
-  int blocks = 0, nouts = 0;
+  int blocks = 0, nouts = 0, part_tiles = 0;   // part_tiles: partial tiles the kernel writes into the shared workspace
   bool y_valid = false;
 };
 void I8PlanDelete::operator()(I8Plan* p) const { delete p; }
 
 // Psi1's digits come from psi1_kernel's four-waves-across-the-columns form (Mp >= 512, Q <= 16) with fixed embeddings
 bool p1i8_applicable_static(const gp_ctx* c) {
-  return !c->i8_unsupported && c->regime_A && c->N >= 65536 && c->Mp >= 512 && psi1_qp(c->Q) > 0 && psi1_qp(c->Q) <= 16;
+  return !c->i8.unsupported && c->regime_A && c->N >= 65536 && c->Mp >= 512 && psi1_qp(c->Q) > 0 && psi1_qp(c->Q) <= 16;
 }
 bool p1i8_applicable(const gp_ctx* c) {
   // from 65536 rows on: below that a workgroup's slice is a few hundred k-steps and the float64 kernels are as fast; and with few rows per
   // inducing point the truncation of the operands weighs more (N = 5e3, M = 600: 2.7e-5 on grad_Z with five digits)
-  return g_opt_p1_i8.load() != 0 && !c->i8_unsupported && c->i8_guard != 2 && c->regime_A && c->N >= 65536 && c->Mp >= 512 && psi1_qp(c->Q) > 0 && psi1_qp(c->Q) <= 16 && !c->want_emb;
+  return g_opt_p1_i8.load() != 0 && !c->i8.unsupported && c->i8.guard != 2 && c->regime_A && c->N >= 65536 && c->Mp >= 512 && psi1_qp(c->Q) > 0 && psi1_qp(c->Q) <= 16 && !c->want_emb;
 }
 
 int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_blocks) {
-  if (c->i8_unsupported) return GP_ERR_UNSUPPORTED;
+  if (c->i8.unsupported) return GP_ERR_UNSUPPORTED;
   if (!c->i8plan) {
     // built aside and published only when complete: a failure below frees what was allocated and switches the path off for this context
     std::unique_ptr<I8Plan, I8PlanDelete> pl(new I8Plan());
-    c->i8_unsupported = true;
+    c->i8.unsupported = true;
     const int MT = c->Mp / TILE, DT = c->Dp / TILE;
     pl->strideJ = (c->Np / 16) * (long)c->LDK * 16;
     GP_TRY_RC(pl->Sl.alloc(c, (size_t)I8S * pl->strideJ, DA_RAW));
@@ -321,7 +321,7 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
       const double cost = std::ceil((double)t * T / (double)SLOTS) / t;
       if (cost < best - 1e-9) { best = cost; s8 = t; }
     }
-    const int Smax = (int)(c->part.size() / ((size_t)T * TILE * TILE));          // the partial buffer holds S x T tiles
+    const int Smax = (int)(c->ws.capacity / ((size_t)T * TILE * TILE));          // the workspace holds S x T partial tiles (its shape-derived capacity: devbuf.h)
     int S = (int)std::min<long>(std::min<long>(8L * s8, ksteps), Smax);
     if (S < 1 || (c->Np + S - 1) / S + 32 > 87000) return fail(c, GP_ERR_UNSUPPORTED, "int8 phase 1: partial buffer too small for %d tiles", T);
     // placement: block b runs on XCD b % 8, one workgroup per CU, 32 CUs per XCD.  Whole slices first (every tile of a slice on one XCD: the
@@ -359,13 +359,13 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
     GP_TRY_RC(upload(c, pl->jobs, jobs));
     GP_TRY_RC(upload(c, pl->outs, outs));
     GP_HIP(c, hipStreamSynchronize(c->stream));
-    pl->blocks = (int)jobs.size(); pl->nouts = (int)outs.size();
+    pl->blocks = (int)jobs.size(); pl->nouts = (int)outs.size(); pl->part_tiles = S * T;
     pl->y_valid = false;
     c->i8plan = std::move(pl);
-    c->i8_unsupported = false;
+    c->i8.unsupported = false;
   }
   I8Plan* pl = c->i8plan.get();
-  if (!c->i8_y_valid) pl->y_valid = false;
+  if (!c->i8.y_valid) pl->y_valid = false;
   if (!pl->y_valid) {
     const int nb = 1024;
     hipLaunchKernelGGL(i8_colmax_kernel, dim3(nb), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, (long)c->Np, c->Mp, c->Dp, pl->pmax);
@@ -374,7 +374,7 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
                        (long)c->Np, c->Mp, c->Dp, c->LDK, pl->yscale, pl->Sl, pl->strideJ);
     GP_HIP(c, hipGetLastError());
     pl->y_valid = true;
-    c->i8_y_valid = true;
+    c->i8.y_valid = true;
   }
   if (pl->row_blocks != row_blocks) return fail(c, GP_ERR_STATE, "int8 phase 1: psi1_kernel's row blocking changed");
   *Sl = pl->Sl; *strideJ = pl->strideJ; *Dpart = pl->dpart;
@@ -385,7 +385,8 @@ int run_phase1_i8(gp_ctx* c) {
   const I8Plan* pl = c->i8plan.get();
   if (!pl || !pl->y_valid) return fail(c, GP_ERR_STATE, "int8 phase 1 without its digit buffers (psi1 did not write them)");
   I8Args a;
-  a.Sl = pl->Sl; a.strideJ = pl->strideJ; a.LDK = c->LDK; a.jobs = pl->jobs; a.part = c->part;
+  a.Sl = pl->Sl; a.strideJ = pl->strideJ; a.LDK = c->LDK; a.jobs = pl->jobs;
+  GP_TRY_RC(c->ws.take(c, (size_t)pl->part_tiles * TILE * TILE, "int8 phase 1", &a.part));
   constexpr int lds = I8_STAGES * I8_STAGE;
   GP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(p1i8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   GP_EV(c, 10);
@@ -396,7 +397,7 @@ int run_phase1_i8(gp_ctx* c) {
   double* C = c->stats + (long)c->Mp * c->Mp;
   // K = 2 sf2 t  (t = the sliced value, |t| <= 1/2)
   hipLaunchKernelGGL(p1i8_diag_kernel, dim3((c->Mp + 31) / 32), dim3(256), 0, c->stream, pl->dpart, pl->row_blocks, c->Mp, pl->diag);
-  hipLaunchKernelGGL(p1i8_reduce_kernel, dim3(TILE * TILE / 256, pl->nouts), dim3(256), 0, c->stream, c->part, pl->outs, pl->yscale, 4.0 * c->sf2 * c->sf2,
+  hipLaunchKernelGGL(p1i8_reduce_kernel, dim3(TILE * TILE / 256, pl->nouts), dim3(256), 0, c->stream, a.part, pl->outs, pl->yscale, 4.0 * c->sf2 * c->sf2,
                      2.0 * c->sf2, Psi2, C, c->Mp, c->Dp, pl->diag);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
@@ -447,36 +448,36 @@ __global__ void __launch_bounds__(256) i8_compare_final_kernel(double* __restric
 
 int p1i8_check_begin(gp_ctx* c) {
   const size_t n = (size_t)c->Mp * c->Mp + (size_t)c->Mp * c->Dp;
-  if (!c->i8_cmp) GP_TRY_RC(c->i8_cmp.alloc(c, 8 + 4 * I8_CMP_BLOCKS + n, DA_RAW));
+  if (!c->i8.cmp) GP_TRY_RC(c->i8.cmp.alloc(c, 8 + 4 * I8_CMP_BLOCKS + n, DA_RAW));
   // the int8 statistics aside (behind the comparison scalars): the float64 phase 1 overwrites the statistics buffer
-  GP_HIP(c, hipMemcpyAsync(c->i8_cmp + 8 + 4 * I8_CMP_BLOCKS, c->stats, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  GP_HIP(c, hipMemcpyAsync(c->i8.cmp + 8 + 4 * I8_CMP_BLOCKS, c->stats, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return GP_OK;
 }
 int p1i8_check_compare(gp_ctx* c) {
   const long n2 = (long)c->Mp * c->Mp, nc = (long)c->Mp * c->Dp;
-  hipLaunchKernelGGL(i8_compare_kernel, dim3(2 * I8_CMP_BLOCKS), dim3(256), 0, c->stream, (const double*)(c->i8_cmp + 8 + 4 * I8_CMP_BLOCKS), (const double*)c->stats, n2, nc,
-                     c->i8_cmp);
+  hipLaunchKernelGGL(i8_compare_kernel, dim3(2 * I8_CMP_BLOCKS), dim3(256), 0, c->stream, (const double*)(c->i8.cmp + 8 + 4 * I8_CMP_BLOCKS), (const double*)c->stats, n2, nc,
+                     c->i8.cmp);
   GP_HIP(c, hipGetLastError());
-  c->i8_check_pending = true;
-  c->i8_since_check = 0;
+  c->i8.check_pending = true;
+  c->i8.since_check = 0;
   return GP_OK;
 }
 int p1i8_check_finish(gp_ctx* c) {
   // called by gp_finish of a checked evaluation, after the global step (P = (K_mm + beta Psi2)^-1 exists) and before its synchronisation is over:
   // one more small kernel and a 48-byte copy, once per 64 evaluations
   const long mm = (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(i8_compare_final_kernel, dim3(1), dim3(256), 0, c->stream, c->i8_cmp, (const double*)c->stats, (const double*)(c->Inv + mm), c->M, c->Mp);
+  hipLaunchKernelGGL(i8_compare_final_kernel, dim3(1), dim3(256), 0, c->stream, c->i8.cmp, (const double*)c->stats, (const double*)(c->gstep.Inv + mm), c->M, c->Mp);
   double h[6];
-  GP_HIP(c, hipMemcpyAsync(h, c->i8_cmp, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  GP_HIP(c, hipMemcpyAsync(h, c->i8.cmp, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
   ++c->sync_epoch;
-  c->i8_check_pending = false;
-  c->i8_rel_psi2 = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : 0.0;
-  c->i8_rel_c = h[3] > 0.0 ? std::sqrt(h[2] / h[3]) : 0.0;
-  c->i8_cond_lb = (c->sf2 + c->beta * h[4]) * h[5];
-  ++c->i8_checks;
-  const double score = c->i8_cond_lb * std::max(c->i8_rel_psi2, c->i8_rel_c);
-  c->i8_guard = (std::isfinite(score) && score <= (g_opt_i8_guard_strict.load() ? 0.0 : I8_GUARD_TAU)) ? 1 : 2;
+  c->i8.check_pending = false;
+  c->i8.rel_psi2 = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : 0.0;
+  c->i8.rel_c = h[3] > 0.0 ? std::sqrt(h[2] / h[3]) : 0.0;
+  c->i8.cond_lb = (c->sf2 + c->beta * h[4]) * h[5];
+  ++c->i8.checks;
+  const double score = c->i8.cond_lb * std::max(c->i8.rel_psi2, c->i8.rel_c);
+  c->i8.guard = (std::isfinite(score) && score <= (g_opt_i8_guard_strict.load() ? 0.0 : I8_GUARD_TAU)) ? 1 : 2;
   return GP_OK;
 }
 

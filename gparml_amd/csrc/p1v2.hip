@@ -252,7 +252,7 @@ __global__ void __launch_bounds__(256) p1v2_reduce_kernel(const double* __restri
 // ---- host: plan (cached per context), launch
 struct P1Plan {
   int Mp = -1, Dp = -1, D = -1; long Np = -1;
-  int nby = 0, blocks = 0, nouts = 0;
+  int nby = 0, blocks = 0, nouts = 0, part_tiles = 0;   // part_tiles: partial tiles the kernel writes into the shared workspace
   DevBuf<P1Job> jobs; DevBuf<P1Out> outs;
 };
 void P1PlanDelete::operator()(P1Plan* p) const { delete p; }
@@ -308,7 +308,6 @@ int run_phase1_v2(gp_ctx* c) {
     for (int i = 0; i < MT; ++i) for (int j = i + 1; j < MT; ++j) { tF.push_back(i); tF.push_back(j); }
     const int baseF = next_part; next_part += SF * nF;
     const int baseG = next_part; next_part += SG * nG * 2;
-    if ((size_t)next_part * TILE * TILE > c->part.size()) return fail(c, GP_ERR_UNSUPPORTED, "phase-1 partial buffer too small");
     for (int s = 0; s < SF; ++s) {
       const int c0 = (int)((long)s * total_chunks / SF), c1 = (int)((long)(s + 1) * total_chunks / SF);
       for (int t = 0; t < nF; ++t)
@@ -333,12 +332,13 @@ int run_phase1_v2(gp_ctx* c) {
     GP_TRY_RC(upload(c, plan->outs, outs));
     GP_HIP(c, hipStreamSynchronize(c->stream));
     plan->Mp = c->Mp; plan->Dp = c->Dp; plan->D = c->D; plan->Np = c->Np; plan->nby = nby;
-    plan->blocks = (int)jobs.size(); plan->nouts = (int)outs.size();
+    plan->blocks = (int)jobs.size(); plan->nouts = (int)outs.size(); plan->part_tiles = next_part;
     c->p1plan = std::move(plan);
     pl = c->p1plan.get();
   }
   P1v2Args p;
-  p.Kaug = c->Kaug; p.ld = c->LDK; p.jobs = pl->jobs; p.part = c->part;
+  p.Kaug = c->Kaug; p.ld = c->LDK; p.jobs = pl->jobs;
+  GP_TRY_RC(c->ws.take(c, (size_t)pl->part_tiles * TILE * TILE, "phase 1 (p1v2)", &p.part));
   GP_EV(c, 10);
   if (pl->nby == 8) hipLaunchKernelGGL((p1v2_kernel<8>), dim3(pl->blocks), dim3(512), 0, c->stream, p);
   else hipLaunchKernelGGL((p1v2_kernel<26>), dim3(pl->blocks), dim3(512), 0, c->stream, p);
@@ -346,7 +346,7 @@ int run_phase1_v2(gp_ctx* c) {
   GP_HIP(c, hipGetLastError());
   double* Psi2 = c->stats;
   double* C = c->stats + (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(p1v2_reduce_kernel, dim3(TILE * TILE / 32, pl->nouts), dim3(256), 0, c->stream, c->part, pl->outs, Psi2, C, c->Mp, c->Dp,
+  hipLaunchKernelGGL(p1v2_reduce_kernel, dim3(TILE * TILE / 32, pl->nouts), dim3(256), 0, c->stream, p.part, pl->outs, Psi2, C, c->Mp, c->Dp,
                      c->sumYY, c->sf2 * (double)c->N, (double)c->N, C + (long)c->Mp * c->Dp);
   GP_HIP(c, hipGetLastError());
   return GP_OK;

@@ -292,7 +292,7 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
   const long ldg = Dp + 2 * Mp;
   const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
   if (unc && var) {
-    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->Inv, (int)M, (int)Mp, u->B);
+    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->gstep.Inv, (int)M, (int)Mp, u->B);
     GP_HIP(c, hipGetLastError());
   }
   double* out_mean = p.out;
@@ -311,11 +311,11 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
     GemmP g;
     g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
     g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = ldg;
-    g.B = c->E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
+    g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
     launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g);
     if (!unc) {
       if (var) {
-        g.B = c->Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.G + Dp;
+        g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.G + Dp;
         launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g);
       }
       GP_HIP(c, hipGetLastError());
@@ -336,7 +336,7 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
         hipLaunchKernelGGL(pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, st, p.mu, u->W, u->V2,
                            u->lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, u->LEA);
         PsiWArgs a;
-        a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->E; a.B = u->B; a.G = p.G; a.ldg = ldg;
+        a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->gstep.E; a.B = u->B; a.G = p.G; a.ldg = ldg;
         a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;
         const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
         if (Q <= 16) hipLaunchKernelGGL(pred_psi2w_kernel<16>, grid, dim3(256), 0, st, a);

@@ -495,7 +495,7 @@ static void launch_psi1(gp_ctx* c, bool fixa) {
   static const int temporal_env = [] { const char* e = getenv("GPARML_PSI1_TEMPORAL"); return e ? atoi(e) : -1; }();
   const int temporal = temporal_env >= 0 ? temporal_env : ((size_t)c->Np * c->LDK * sizeof(double) <= ((size_t)200 << 20) ? 1 : 0);
   dim3 grid((c->Mp + 128 * WC - 1) / (128 * WC), (unsigned)((c->Np / 16 + ngrp - 1) / ngrp));
-  if constexpr (QP <= 16) if (fixa && WC == 4 && c->i8_active) {
+  if constexpr (QP <= 16) if (fixa && WC == 4 && c->i8.active) {
     // int8 phase 1 (p1i8.hip): Psi1's digits are written next to Psi1 itself
     int8_t* Sl = nullptr; long strideJ = 0; double* Dpart = nullptr;
     if (p1i8_prepare(c, &Sl, &strideJ, &Dpart, (int)grid.y) == GP_OK) {
@@ -503,7 +503,7 @@ static void launch_psi1(gp_ctx* c, bool fixa) {
                          (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk, Sl, strideJ, 0.5 / c->sf2, Dpart);
       return;
     }
-    c->i8_active = false;
+    c->i8.active = false;
   }
   if (fixa)
   {
@@ -531,10 +531,22 @@ static void launch_psi1_wide(gp_ctx* c, bool fixa) {
                        (long)c->LDK, (const double*)c->alpha, 0.0, nblk);
 }
 
+int P1Tiles::alloc(gp_ctx* c) {
+  // phase-1 tile table: Psi2 upper tiles first, then the C tiles
+  std::vector<int> t;
+  const int mt = c->Mp / TILE, dt = c->Dp / TILE;
+  for (int i = 0; i < mt; ++i) for (int j = i; j < mt; ++j) { t.push_back(i); t.push_back(j); }
+  for (int i = 0; i < mt; ++i) for (int j = 0; j < dt; ++j) { t.push_back(i); t.push_back(mt + j); }
+  n_tiles = (int)t.size() / 2;
+  GP_TRY_RC(upload(c, tiles, t));      // (gp_create's device synchronisation completes the copy)
+  kl_blocks = blocks_for(c->Np);
+  return klpart.alloc(c, (size_t)kl_blocks);
+}
+
 int run_prep_and_generate(gp_ctx* c) {
   PrepArgs a;
   a.Xmu = c->Xmu; a.Xs = c->Xs; a.dir = c->have_dir ? c->dir : nullptr; a.alpha = c->alpha;
-  a.mu = c->mu; a.S = c->S; a.U = c->U; a.lnc1 = c->lnc1; a.Xa = c->Xa; a.klpart = c->klpart;
+  a.mu = c->mu; a.S = c->S; a.U = c->U; a.lnc1 = c->lnc1; a.Xa = c->Xa; a.klpart = c->p1t.klpart;
   a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CXp = c->CXp; a.step = c->step; a.sf2 = c->sf2;
   a.raw = c->xs_raw ? 1 : 0; a.regimeA = c->regime_A ? 1 : 0; a.fixedA = p2_fast_mode(c) ? 1 : (p2_wide_fixed_mode(c) ? 2 : 0);
   a.QP = psi1_qp(c->Q); a.PU = a.QP > 0 ? c->PU : nullptr;
@@ -544,16 +556,16 @@ int run_prep_and_generate(gp_ctx* c) {
   const bool fixa = a.fixedA && a.PU != nullptr;
   if (!(fixa && c->prep_fixa_valid)) {
     hipLaunchKernelGGL(prep_elem_kernel, dim3((unsigned)std::min<long>((c->Np * c->Q + 255) / 256, 16384)), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(prep_row_kernel, dim3(c->kl_blocks), dim3(256), 0, c->stream, a);
+    hipLaunchKernelGGL(prep_row_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, c->stream, a);
     GP_HIP(c, hipGetLastError());
   }
   c->prep_fixa_valid = fixa;
-  c->i8_active = fixa && p1i8_applicable(c);     // decided per evaluation (gp_debug_set_option("p1_i8", ...) switches it at run time)
+  c->i8.active = fixa && p1i8_applicable(c);     // decided per evaluation (gp_debug_set_option("p1_i8", ...) switches it at run time)
   GP_EV(c, 8);
   const int QP = psi1_qp(c->Q);
   // The Psi1 kernels' fixed-variance form (u = alpha, ln c1 = ln sf2: 2 Q + 14 issue slots per element instead of 3 Q + 14) only needs every variance
   // to be zero -- not the fixed-embedding FEATURE layout, which the fast kernel uses for Q + 1 <= 12 -- so it also serves regime A with embedding gradients and
-  // wider latent spaces (when measured: N = 1e6, M = 512, Q = 30: 2.70 -> 1.89 ms).  The int8 digits (launch_psi1) stay tied to `fixa` through c->i8_active.
+  // wider latent spaces (when measured: N = 1e6, M = 512, Q = 30: 2.70 -> 1.89 ms).  The int8 digits (launch_psi1) stay tied to `fixa` through c->i8.active.
   const bool kfix = c->regime_A && a.PU != nullptr;
   if (QP > 16) {
     switch (QP) {
@@ -584,21 +596,21 @@ int run_prep_and_generate(gp_ctx* c) {
 }
 
 int run_phase1(gp_ctx* c) {
-  if (c->i8_active) {
+  if (c->i8.active) {
     // fixed embeddings on the int8 matrix core: exact integer products of the 35-bit digits psi1_kernel wrote (p1i8.hip)
     int rc = run_phase1_i8(c);
     if (rc != GP_OK) return rc;
     // the guard (p1i8.hip): the first int8 evaluation after an upload and every 64th one also run the float64 phase 1, compare the two sets of
     // statistics on the device and carry on with the float64 ones; gp_finish decides whether the context stays on the int8 path
-    if (c->i8_guard == 0 || ++c->i8_since_check >= 64) {
+    if (c->i8.guard == 0 || ++c->i8.since_check >= 64) {
       GP_TRY_RC(p1i8_check_begin(c));
-      c->i8_active = false;                         // the float64 phase 1 this shape takes by default (p1v2_kernel or the tile kernel)
+      c->i8.active = false;                         // the float64 phase 1 this shape takes by default (p1v2_kernel or the tile kernel)
       const int rc64 = run_phase1(c);
-      c->i8_active = true;
+      c->i8.active = true;
       if (rc64 != GP_OK) return rc64;
       return p1i8_check_compare(c);
     }
-    hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->klpart, c->kl_blocks, c->sumYY, c->sf2, (double)c->N,
+    hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
                        1, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
     GP_HIP(c, hipGetLastError());
     return GP_OK;
@@ -610,10 +622,10 @@ int run_phase1(gp_ctx* c) {
   }
   const int mt = c->Mp / TILE;
   // regime A: Psi2 = Psi1^T Psi1 and C tiles; regime B: only the C tiles here (Psi2 comes from the pair kernel)
-  const int first = c->regime_A ? 0 : c->n_tiles - mt * (c->Dp / TILE);
-  const int T = c->n_tiles - first;
+  const int first = c->regime_A ? 0 : c->p1t.n_tiles - mt * (c->Dp / TILE);
+  const int T = c->p1t.n_tiles - first;
   P1Args p;
-  p.Kaug = c->Kaug; p.ld = c->LDK; p.tiles = c->tiles + 2 * first; p.T = T;
+  p.Kaug = c->Kaug; p.ld = c->LDK; p.tiles = c->p1t.tiles + 2 * first; p.T = T;
   p.total_chunks = (int)(c->Np / KC);
   // Placement (block b runs on XCD b % 8, 64 resident workgroups per XCD at 2 per CU): every XCD gets L = 64/T whole
   // slices (all T tile types of a slice share the XCD's L2, so the slice's rows are fetched from HBM once); the 64 - L*T
@@ -625,8 +637,9 @@ int run_phase1(gp_ctx* c) {
   int S = std::max(1, std::min(8 * L + n_shared, p.total_chunks));
   p.cps = (p.total_chunks + S - 1) / S;
   S = (p.total_chunks + p.cps - 1) / p.cps;
-  p.S = S; p.part = c->part;
-  if (c->bmap_T != T || c->bmap_S != S) {
+  p.S = S;
+  GP_TRY_RC(c->ws.take(c, (size_t)S * T * TILE * TILE, "phase 1 (tile kernel)", &p.part));
+  if (c->p1t.bmap_T != T || c->p1t.bmap_S != S) {
     const int per_xcd = (T <= 64) ? 64 : (S * T + 7) / 8;
     std::vector<int> slot(8 * per_xcd * 2, -1);     // [xcd][j] -> (slice, type)
     std::vector<int> fill(8, 0);
@@ -645,21 +658,21 @@ int run_phase1(gp_ctx* c) {
     std::vector<int> bm(8 * per_xcd * 2);
     for (int j = 0; j < per_xcd; ++j)
       for (int xx = 0; xx < 8; ++xx) { bm[(j * 8 + xx) * 2] = slot[(xx * per_xcd + j) * 2]; bm[(j * 8 + xx) * 2 + 1] = slot[(xx * per_xcd + j) * 2 + 1]; }
-    GP_TRY_RC(upload(c, c->bmap, bm));
+    GP_TRY_RC(upload(c, c->p1t.bmap, bm));
     GP_HIP(c, hipStreamSynchronize(c->stream));
-    c->bmap_T = T; c->bmap_S = S; c->bmap_blocks = 8 * per_xcd;
+    c->p1t.bmap_T = T; c->p1t.bmap_S = S; c->p1t.bmap_blocks = 8 * per_xcd;
   }
-  p.bmap = c->bmap;
-  const int blocks = c->bmap_blocks;
+  p.bmap = c->p1t.bmap;
+  const int blocks = c->p1t.bmap_blocks;
   GP_EV(c, 10);
   hipLaunchKernelGGL(p1_kernel8, dim3(blocks), dim3(512), 0, c->stream, p);
   GP_EV(c, 11);
   GP_HIP(c, hipGetLastError());
   double* Psi2 = c->stats;
   double* C = c->stats + (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(p1_reduce_kernel, dim3(TILE * TILE / 256, T), dim3(256), 0, c->stream, c->part, p.tiles, T, S, Psi2, C, c->Mp, c->Dp);
+  hipLaunchKernelGGL(p1_reduce_kernel, dim3(TILE * TILE / 256, T), dim3(256), 0, c->stream, p.part, p.tiles, T, S, Psi2, C, c->Mp, c->Dp);
   GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->klpart, c->kl_blocks, c->sumYY, c->sf2, (double)c->N,
+  hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
                      c->regime_A ? 1 : 0, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
   GP_HIP(c, hipGetLastError());
   return GP_OK;
@@ -1367,14 +1380,29 @@ bool p2_fast_mode(const gp_ctx* c) { return c->regime_A && !c->want_emb && c->Q 
 // N = 1e6, D = 100, M = 512, Q = 30: phase-2 kernel 13.7 -> 12.0 ms, evaluation 23.6 -> 20.4 ms (same box, with the fixed-variance Psi1 kernel; profiles/r04_shape_sweep.txt)
 bool p2_wide_fixed_mode(const gp_ctx* c) { return c->regime_A && !c->want_emb && c->Q + 1 > 12; }
 
+int P2State::alloc(gp_ctx* c) {
+  const long Mp = c->Mp, Np = c->Np;
+  p2_slices = std::max(1, std::min<int>(8 * std::max(1, 64 / (int)(Mp / TILE)), (int)(Np / TILE)));
+  GP_TRY_RC(Rpart.alloc(c, (size_t)2 * (p2_slices + 8) * Mp * c->CXp));
+  GP_TRY_RC(HZp.alloc(c, (size_t)(Mp / TILE) * Np * c->CZp));    // p2_gen8_kernel: per-point partials, one array per 128 inducing columns
+  ga_blocks = blocks_for(Np);
+  GP_TRY_RC(gapart.alloc(c, (size_t)ga_blocks * c->Q));
+  // fast phase 2: per-wave (eight-wave kernel: blocks * 8 rows of <= 12) or per-256-points (four-wave kernel) partials of grad_alpha's mu^2 term
+  return hgpart.alloc(c, std::max((size_t)((c->N + 255) / 256) * c->Q, (size_t)8 * (p2_slices + 8) * (Mp / TILE) * 8 * 12));
+}
+int P2State::poison(gp_ctx* c) {
+  for (const DevBuf<double>* b : {&Rpart, &HZp, &gapart, &hgpart}) GP_HIP(c, poison_fill(c, *b));
+  return GP_OK;
+}
+
 int run_phase2(gp_ctx* c) {
   const bool fast = p2_fast_mode(c), widefix = p2_wide_fixed_mode(c);
   const bool ppath = !fast && !widefix;
   P2Args p;
-  p.Kaug = c->Kaug; p.ld = c->LDK; p.Bm = c->Bm; p.Xa = c->Xa; p.Zaug = c->Zaug; p.Rpart = c->Rpart; p.HZp = c->HZp;
+  p.Kaug = c->Kaug; p.ld = c->LDK; p.Bm = c->gstep.Bm; p.Xa = c->Xa; p.Zaug = c->Zaug; p.Rpart = c->p2.Rpart; p.HZp = c->p2.HZp;
   p.Mp = c->Mp; p.CXp = c->CXp; p.CZp = c->CZp; p.MT = c->Mp / TILE; p.Np = c->Np;
   p.ntiles = (int)(c->Np / TILE);
-  int S = std::max(1, std::min(c->p2_slices, p.ntiles));
+  int S = std::max(1, std::min(c->p2.p2_slices, p.ntiles));
   p.tps = (p.ntiles + S - 1) / S;
   S = (p.ntiles + p.tps - 1) / p.tps;
   p.S = S;
@@ -1387,8 +1415,8 @@ int run_phase2(gp_ctx* c) {
   static const bool p2_sync = [] { const char* e = getenv("GPARML_P2_SYNC"); return !(e && e[0] == '0'); }();
   // the in-step wait needs every workgroup of the launch resident at once: the grid is sized for two workgroups per CU on 256 CUs
   if (fast && p2_sync && p.MT > 1 && blocks <= 512) {
-    if (!c->p2prog) GP_TRY_RC(c->p2prog.alloc(c, (size_t)(c->p2_slices + 8) * p.MT, DA_ZERO));   // zero contract: bases only grow
-    p.prog = c->p2prog; p.prog_base = (unsigned long long)(++c->p2_epoch) << 32;
+    if (!c->p2.p2prog) GP_TRY_RC(c->p2.p2prog.alloc(c, (size_t)(c->p2.p2_slices + 8) * p.MT, DA_ZERO));   // zero contract: bases only grow
+    p.prog = c->p2.p2prog; p.prog_base = (unsigned long long)(++c->p2.p2_epoch) << 32;
   }
   GP_EV(c, 12);
   p.dbg = nullptr;
@@ -1412,7 +1440,7 @@ int run_phase2(gp_ctx* c) {
   }
 #endif
   if (fast) {                                        // nrb <= 3
-    p.gapart = c->hgpart;
+    p.gapart = c->p2.hgpart;
     // (blocks past the last slice zero their own rows of hgpart)
     switch (nrb) {
       case 1: hipLaunchKernelGGL((p2_fast8_kernel<1>), dim3(blocks), dim3(512), 0, c->stream, p); break;
@@ -1424,24 +1452,24 @@ int run_phase2(gp_ctx* c) {
   GP_HIP(c, hipGetLastError());
   double* gZ = c->grads;
   double* ga = c->grads + (long)c->M * c->Q;
-  // T2 is free after the global step: per-row alpha partials [M][Q]
-  hipLaunchKernelGGL(p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->stream, c->Rpart, 2 * S, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
-                     c->alpha, fast ? 1 : (widefix ? 2 : 0), gZ, c->T2);
+  // the global step's T2 is free once the step is enqueued: borrowed for the per-row alpha partials [M][Q] (GsState::T2)
+  hipLaunchKernelGGL(p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->stream, c->p2.Rpart, 2 * S, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
+                     c->alpha, fast ? 1 : (widefix ? 2 : 0), gZ, c->gstep.T2);
   GP_HIP(c, hipGetLastError());
   if (ppath) {
     PtArgs a;
-    a.HZp = c->HZp; a.nparts = p.MT;            // p2_gen8_kernel: one partial array per 128 inducing columns
+    a.HZp = c->p2.HZp; a.nparts = p.MT;            // p2_gen8_kernel: one partial array per 128 inducing columns
     a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CZp = c->CZp; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
-    a.gmu = c->gXmu; a.gS = c->gXs; a.gapart = c->gapart; a.regimeA = c->regime_A ? 1 : 0;
+    a.gmu = c->gXmu; a.gS = c->gXs; a.gapart = c->p2.gapart; a.regimeA = c->regime_A ? 1 : 0;
     a.pb = point_pb(c->CZp, c->Q);
-    hipLaunchKernelGGL(point_kernel, dim3(c->ga_blocks), dim3(256), (size_t)(a.pb * (c->CZp + c->Q) + c->Q) * sizeof(double), c->stream, a);
+    hipLaunchKernelGGL(point_kernel, dim3(c->p2.ga_blocks), dim3(256), (size_t)(a.pb * (c->CZp + c->Q) + c->Q) * sizeof(double), c->stream, a);
     GP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->T2, c->M, c->Q, c->gapart, c->ga_blocks, c->Q, c->Q, ga);
+    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, c->p2.gapart, c->p2.ga_blocks, c->Q, c->Q, ga);
   } else if (widefix) {
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->T2, c->M, c->Q, (const double*)nullptr, 0, 0, c->Q, ga);
+    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, (const double*)nullptr, 0, 0, c->Q, ga);
   } else {
     const int hb = blocks * 8, hstride = 4 * nrb;    // one partial row of grad_alpha's mu^2 term per wave
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->T2, c->M, c->Q, c->hgpart, hb, hstride, c->Q, ga);
+    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, c->p2.hgpart, hb, hstride, c->Q, ga);
   }
   GP_HIP(c, hipGetLastError());
   return GP_OK;

@@ -799,8 +799,10 @@ static int ensure_bplan(gp_ctx* c) {
     GP_TRY_RC(upload(c, p.sym_sched, sch));
   }
   GP_HIP(c, hipStreamSynchronize(c->stream));     // the tables' uploads
-  // the pair kernel's split-n partials live in c->part: make sure it is large enough
-  GP_TRY_RC(c->part.grow(c, std::max((size_t)p.n_ptiles * 256 * 64, (size_t)p.n_tiles64 * 4096 * 32), DA_RAW));
+  // the pair kernels' split-n partials go to the shared workspace: up to 64 slices of 16 x 16 tiles, or 32 of 64 x 64 tiles.  From M of about 750 on
+  // that is more than the workspace's capacity, so the plan reserves it here, once (devbuf.h: the capacity the other stages plan by does not move)
+  p.part_need = std::max((size_t)p.n_ptiles * 256 * 64, (size_t)p.n_tiles64 * 4096 * 32);
+  GP_TRY_RC(c->ws.reserve(c, p.part_need));
   c->bplan = std::move(pl);
   return GP_OK;
 }
@@ -839,7 +841,7 @@ static void launch_le(gp_ctx* c, const BPlan& p) {
 int run_generate_b(gp_ctx* c) {
   GP_TRY_RC(ensure_bplan(c));
   const BPlan& p = *c->bplan;
-  hipLaunchKernelGGL(b_tables_kernel, dim3(c->kl_blocks), dim3(256), 0, c->stream, c->mu, c->S, c->alpha, (long)c->N, (long)c->Np, c->Q,
+  hipLaunchKernelGGL(b_tables_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, c->stream, c->mu, c->S, c->alpha, (long)c->N, (long)c->Np, c->Q,
                      c->sf2, p.Vn, p.Wn, p.lnc2h, p.V2P, p.QB, p.WP, p.MUP);
   GP_HIP(c, hipMemcpyAsync(p.alphaP, c->alpha, (size_t)c->Q * 8, hipMemcpyDeviceToDevice, c->stream));
   hipLaunchKernelGGL(zpad_kernel, dim3((unsigned)(((long)c->Mp * (p.QB + 6) + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->M, c->Mp, c->Q, p.QB,
@@ -863,20 +865,22 @@ int run_generate_b(gp_ctx* c) {
 }
 
 template <int QT>
-static void launch_pairs(gp_ctx* c, const BPlan& p, int S) {
+static void launch_pairs(gp_ctx* c, const BPlan& p, int S, double* part) {
   hipLaunchKernelGGL((psi2_pairs_kernel<QT>), dim3(p.n_ptiles, S), dim3(256), 0, c->stream, p.LE, p.V2P, p.ZP, p.ptiles, (long)c->N,
-                     c->Mp, S, c->part, p.n_ptiles);
+                     c->Mp, S, part, p.n_ptiles);
 }
 
 template <int QT>
-static void launch_pairs_mfma(gp_ctx* c, const BPlan& p, int S) {
+static void launch_pairs_mfma(gp_ctx* c, const BPlan& p, int S, double* part) {
   hipLaunchKernelGGL((psi2_pairs_mfma_kernel<QT>), dim3(p.n_tiles64, S), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P,
-                     (const double*)p.ZP, (const int*)p.tiles64, (long)c->N, c->Mp, S, c->part, p.n_tiles64);
+                     (const double*)p.ZP, (const int*)p.tiles64, (long)c->N, c->Mp, S, part, p.n_tiles64);
 }
 
 int run_phase1_b(gp_ctx* c) {
   const BPlan& p = *c->bplan;
   if (p.p1 == BP1::GENERIC) { GP_TRY_RC(run_phase1_b_generic(c)); return psi2_zero_pads(c); }
+  double* part = nullptr;
+  GP_TRY_RC(c->ws.take(c, p.part_need, "regime-B phase 1 (pair kernel)", &part));
   // gp_last_timings' "p1 kernel" slot: in regime B the Psi2 pair kernel (the C tiles' p1_kernel8 launch recorded the events before)
   GP_EV(c, 10);
   if (p.p1 == BP1::PAIRS_MFMA) {
@@ -884,14 +888,14 @@ int run_phase1_b(gp_ctx* c) {
     int S = (int)std::max<long>(1, std::min<long>(32, std::max<long>((2048 + p.n_tiles64 - 1) / p.n_tiles64, c->N / 4096)));
     S = (int)std::min<long>(S, std::max<long>(1, c->N / 256));
     switch (p.QB) {
-      case 24: launch_pairs_mfma<24>(c, p, S); break;
-      case 32: launch_pairs_mfma<32>(c, p, S); break;
-      case 52: launch_pairs_mfma<52>(c, p, S); break;
-      default: launch_pairs_mfma<64>(c, p, S); break;
+      case 24: launch_pairs_mfma<24>(c, p, S, part); break;
+      case 32: launch_pairs_mfma<32>(c, p, S, part); break;
+      case 52: launch_pairs_mfma<52>(c, p, S, part); break;
+      default: launch_pairs_mfma<64>(c, p, S, part); break;
     }
     GP_EV(c, 11);
     GP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(psi2_reduce64_kernel, dim3(p.n_tiles64), dim3(256), 0, c->stream, c->part, p.tiles64, p.n_tiles64, S, c->M, c->Mp, c->stats);
+    hipLaunchKernelGGL(psi2_reduce64_kernel, dim3(p.n_tiles64), dim3(256), 0, c->stream, part, p.tiles64, p.n_tiles64, S, c->M, c->Mp, c->stats);
     GP_HIP(c, hipGetLastError());
     return psi2_zero_pads(c);
   }
@@ -899,18 +903,18 @@ int run_phase1_b(gp_ctx* c) {
   int S = (int)std::max<long>(1, std::min<long>(64, std::max<long>((4096 + p.n_ptiles - 1) / p.n_ptiles, c->N / 1024)));
   S = (int)std::min<long>(S, c->N);
   switch (p.QB) {
-    case 4: launch_pairs<4>(c, p, S); break;
-    case 6: launch_pairs<6>(c, p, S); break;
-    case 8: launch_pairs<8>(c, p, S); break;
-    case 10: launch_pairs<10>(c, p, S); break;
-    case 12: launch_pairs<12>(c, p, S); break;
-    case 14: launch_pairs<14>(c, p, S); break;
-    case 16: launch_pairs<16>(c, p, S); break;
+    case 4: launch_pairs<4>(c, p, S, part); break;
+    case 6: launch_pairs<6>(c, p, S, part); break;
+    case 8: launch_pairs<8>(c, p, S, part); break;
+    case 10: launch_pairs<10>(c, p, S, part); break;
+    case 12: launch_pairs<12>(c, p, S, part); break;
+    case 14: launch_pairs<14>(c, p, S, part); break;
+    case 16: launch_pairs<16>(c, p, S, part); break;
     default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B pair kernel: no instantiation for the latent table width %d", p.QB);
   }
   GP_EV(c, 11);
   GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(psi2_reduce_kernel, dim3(p.n_ptiles), dim3(256), 0, c->stream, c->part, p.ptiles, p.n_ptiles, S, c->M, c->Mp, c->stats);
+  hipLaunchKernelGGL(psi2_reduce_kernel, dim3(p.n_ptiles), dim3(256), 0, c->stream, part, p.ptiles, p.n_ptiles, S, c->M, c->Mp, c->stats);
   GP_HIP(c, hipGetLastError());
   return psi2_zero_pads(c);
 }
@@ -919,7 +923,7 @@ template <int QT, bool KEEP>
 static void launch_cols(gp_ctx* c, const BPlan& p, const PB2Args& a) {     // (the Bbar argument: the row-interleaved table up to QT = 10, the plain one beyond)
   const int nw = std::min(4, p.nslab);
   hipLaunchKernelGGL((psi2_cols_kernel<QT, KEEP>), dim3(p.pb_blocks, (p.nslab + nw - 1) / nw), dim3(64 * nw), 0, c->stream, a, (const double*)p.ZP,
-                     (const double*)(cols_b4(QT) ? p.Bbar4 : c->Bbar), (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
+                     (const double*)(cols_b4(QT) ? p.Bbar4 : c->gstep.Bbar), (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
                      (const double*)p.alphaP);
 }
 
@@ -942,7 +946,7 @@ int run_phase2_b(gp_ctx* c) {
   a.Gpart = p.Gpart; a.gapart2 = p.gapart2; a.gmu = c->gXmu; a.gS = c->gXs; a.pp = p.pp;
   a.N = c->N; a.Np = c->Np; a.M = c->M; a.Mp = c->Mp; a.Q = c->Q; a.QB = p.QB; a.nslab = p.nslab; a.ppb = p.ppb; a.ngrp = (p.nslab + std::min(4, p.nslab) - 1) / std::min(4, p.nslab);
   if (!gen) hipLaunchKernelGGL(bbar_interleave_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 2048)), dim3(256), 0, c->stream,
-                               (const double*)c->Bbar, c->Mp, p.Bbar4);
+                               (const double*)c->gstep.Bbar, c->Mp, p.Bbar4);
   GP_EV(c, 12);   // gp_last_timings' "p2 kernel" slot: in regime B the T_n = Bbar o psi2_n kernel
   if (gen) {
     a.ngrp = 1;

@@ -173,7 +173,7 @@ int run_phase2_b_generic(gp_ctx* c) {
   for (long n0 = 0; n0 < c->N; n0 += g.P) {
     const long cnt = std::min<long>(g.P, c->N - n0);
     hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
-                       (const double*)c->Bbar, n0, cnt, M, c->Mp, Q, g.T);
+                       (const double*)c->gstep.Bbar, n0, cnt, M, c->Mp, Q, g.T);
     hipLaunchKernelGGL(psi2_rt_generic_kernel, dim3(grid_of(cnt * M * (Q + 1))), dim3(256), 0, c->stream, (const double*)g.T, (const double*)p.ZP, cnt, M, Q,
                        g.rt);
     hipLaunchKernelGGL(psi2_pp_generic_kernel, dim3(grid_of(cnt * (3 * Q + 1))), dim3(256), 0, c->stream, (const double*)g.rt, (const double*)p.ZP, n0, cnt, M, Q,

@@ -43,6 +43,7 @@ struct BPlan {
   DevBuf<int> tiles64;        // upper-triangular 64x64 tile table of psi2_pairs_mfma_kernel and the tile-pair phase 2
   DevBuf<int> sym_sched;      // [rounds][waves] tile of every wave of psi2_sym_kernel in every round (I | J << 16, -1 idle; SYM only)
   int n_ptiles = 0, n_tiles64 = 0;
+  size_t part_need = 0;       // doubles of the shared workspace the pair kernels' split-n partials take (reserved when the plan is built)
   int nslab = 0, ppb = 0, pb_blocks = 0;     // phase 2: 64-column slabs of M, points per workgroup, workgroups along the points
   int sym_nw = 0, sym_rounds = 0;
   std::unique_ptr<BTiles> tiles;      // TILES: built by the first tile-pair phase 2

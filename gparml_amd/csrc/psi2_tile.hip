@@ -468,7 +468,7 @@ int run_phase2_b_tiles(gp_ctx* c) {
   }
   const BTiles& tb = *p.tiles;
   PT2Args a;
-  a.ZP = p.ZP; a.Bbar = c->Bbar; a.LEA = p.LET; a.V2P = p.V2P; a.WP = p.WP; a.MUP = p.MUP; a.alphaP = p.alphaP;
+  a.ZP = p.ZP; a.Bbar = c->gstep.Bbar; a.LEA = p.LET; a.V2P = p.V2P; a.WP = p.WP; a.MUP = p.MUP; a.alphaP = p.alphaP;
   a.tiles = p.tiles64; a.Gt = tb.Gt; a.pp = tb.ppt; a.CH = tb.ch; a.Np = c->Np; a.Mp = c->Mp; a.M = c->M; a.Q = Q; a.QB = p.QB; a.T = T; a.S = tb.S;
   a.dbg = nullptr;
 #ifdef GPARML_TILE_TIMING

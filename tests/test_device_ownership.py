@@ -46,8 +46,9 @@ def test_only_the_owner_allocates_device_memory():
 
 OWNED = re.compile(r'(?:DevBuf|PinnedBuf)<[^>]*>\s+([^;(]*);')
 PLANNED = re.compile(r'unique_ptr<[^;]*>\s+(\w+);')
-# what this context keeps itself: every feature that only runs on demand owns its buffers in a plan of its own
-GP_CTX_MAX_BUFFERS = 52
+# what this context keeps itself (the shard's data, the globals, the outputs): every stage of an evaluation owns its buffers in a state struct, every
+# feature that only runs on demand in a plan of its own
+GP_CTX_MAX_BUFFERS = 24
 
 
 def _owned(body):
@@ -77,6 +78,11 @@ def test_gp_destroy_names_no_buffer():
     for plan, member, field in (('BPlan', 'LET', 'bplan'), ('PredPlan', 'P1', 'pred'), ('InferPlan', 'Gf', 'infer')):
         assert plan in owners and member in _owned(owners[plan]), (plan, member)
         assert field in PLANNED.findall(ctx), field
+    # the state of the stages of an evaluation, each struct a single member of the context
+    for state, member, field in (('GsState', 'Linv', 'gstep'), ('P2State', 'HZp', 'p2')):
+        assert state in owners and member in _owned(owners[state]), (state, member)
+        assert member not in _owned(ctx), member
+        assert re.search(r'\b%s\s+%s;' % (state, field), ctx), field
     # every pointer-typed field of the context and of the plans is an owner (the RCCL communicator and the HIP events are not memory)
     for name, body in owners.items():
         raw = [m for m in re.findall(r'^\s*[\w:]+\s*\*\s*(\w+)', body, re.M) if not (name == 'gp_ctx' and m == 'comm')]
