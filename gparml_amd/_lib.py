@@ -77,6 +77,8 @@ SIGNATURES = {
     'gp_debug_gemm_bench': (ctypes.c_int, [ctypes.c_int] * 7 + [_dp]),
     'gp_debug_peek': (ctypes.c_int, [_vp, ctypes.c_char_p, _dp, ctypes.c_long]),
     'gp_debug_operands_overlap': (ctypes.c_int, [ctypes.c_long] * 8),
+    'gp_debug_gemm_modes': (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_long), ctypes.c_double, ctypes.c_double, _ip, _dp, _dp, _dp]),
+    'gp_debug_potrf_inverse_batched': (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, _dp, _dp, _dp, _ip]),
 }
 
 _lib = None

@@ -25,10 +25,16 @@ __global__ void __launch_bounds__(256, 2) gemm128_kernel(GemmP p) {
   const double* B = p.B + (long)bi * p.sB + (long)bo * p.oB;
   double* C = p.C + (long)bi * p.sC + (long)bo * p.oC;
   const long row0 = (long)by * TILE, col0 = (long)bx * TILE;
-  // klow (X^T X, X lower-triangular): the tile's k-range starts at its first possibly non-zero k, a multiple of 128; the splits share what is left
+  // klow (X^T X, X lower-triangular): the tile's k-range starts at its first possibly non-zero k, a multiple of 128.  The splits keep the boundaries of
+  // the full product (K / splits each) and drop the chunks below klo from their own segment -- those are exact zeros at the head of a sequential sum, so
+  // every partial tile, and with it the result, has the bits of the product without klow (a segment wholly below klo gives a zero partial at no cost;
+  // the longest workgroup is a split of a klo = 0 tile either way)
   const long klo = p.klow ? (row0 > col0 ? row0 : col0) : 0;
-  const int nc = (int)((p.K - klo) / KC / p.splits);          // chunks of this split
-  const long k0 = klo + (long)sp * nc * KC;
+  const int ncs = (int)(p.K / KC / p.splits);                 // chunks of a split's segment
+  const long seg0 = (long)sp * ncs * KC;
+  const int skip = klo <= seg0 ? 0 : (klo - seg0) / KC < ncs ? (int)((klo - seg0) / KC) : ncs;
+  const int nc = ncs - skip;                                  // chunks of this split
+  const long k0 = seg0 + (long)skip * KC;
   const double* Ab = (LA == K_CONTIG) ? A + row0 * p.lda + k0 : A + row0 + k0 * p.lda;
   const double* Bb = (LB == K_CONTIG) ? B + col0 * p.ldb + k0 : B + col0 + k0 * p.ldb;
   const long a_step = (LA == K_CONTIG) ? KC : (long)KC * p.lda;
@@ -37,10 +43,12 @@ __global__ void __launch_bounds__(256, 2) gemm128_kernel(GemmP p) {
   Acc acc;
   acc.zero();
   const LaneOfs ofs = lane_offsets<LA, LB>(wrow0, wcol0, lane);
-  tile_dma<LA>(lds[0][0], Ab, p.lda, wave, lane);
-  tile_dma<LB>(lds[0][1], Bb, p.ldb, wave, lane);
-  dma_wait();
-  __syncthreads();
+  if (nc > 0) {                                               // (workgroup-uniform; an empty segment stores its zero partial)
+    tile_dma<LA>(lds[0][0], Ab, p.lda, wave, lane);
+    tile_dma<LB>(lds[0][1], Bb, p.ldb, wave, lane);
+    dma_wait();
+    __syncthreads();
+  }
   for (int c = 0; c < nc; ++c) {
     const int cur = c & 1;
     if (c + 1 < nc) {
@@ -147,6 +155,11 @@ void launch_gemm(hipStream_t st, Layout la, Layout lb, int m, int n, int batch, 
     fprintf(stderr, "gparml: launch_gemm called with C overlapping an operand (m %d n %d k %d)\n", m, n, p.K);
     abort();
   }
+  // mirror is defined for beta == 0 only (GemmP): with a beta the three kernels would each do something else
+  if (p.mirror && p.beta != 0.0) {
+    fprintf(stderr, "gparml: launch_gemm called with mirror and beta != 0 (m %d n %d k %d)\n", m, n, p.K);
+    abort();
+  }
   dim3 grid(n / TILE, m / TILE, batch * p.splits), block(256);
   if (!p.big && (long)(n / TILE) * (m / TILE) * batch <= 256) {
     // few tiles (the global step): 32 x 32 tiles spread the product over the chip; split-k is not needed there
@@ -199,6 +212,85 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(hC.data(), dC, hC.size() * 8, hipMemcpyDeviceToHost));
   for (long i = 0; i < m; ++i) for (long j = 0; j < n; ++j) C[i * n + j] = hC[i * np + j];
+  return GP_OK;
+}
+
+// One launch_gemm with every GemmP field chosen by the caller (include/gparml_hip.h).  Everything launch_gemm or a kernel takes on trust is checked here
+// first -- windows inside their parents for every batch entry, 16-byte alignment, the split-k divisibility, mirror without beta, the overlap rule --
+// and refused with GP_ERR_BAD_ARG: no call reaches launch_gemm's abort() or reads or writes outside a parent buffer.
+extern "C" int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int k, int batch_inner, int batch_outer, const long* geom, double alpha,
+                                   double beta, const int* mode, const double* A, const double* B, double* C) {
+  using namespace gp;
+  gp_ctx* ctx = nullptr;
+  auto bad = [&](const char* what) { return fail(ctx, GP_ERR_BAD_ARG, "gp_debug_gemm_modes: %s", what); };
+  if (!geom || !mode || !A || !B || !C) return bad("NULL argument");
+  if ((la != 0 && la != 1) || (lb != 0 && lb != 1)) return bad("layout must be 0 (free index contiguous) or 1 (k contiguous)");
+  if (m <= 0 || n <= 0 || k <= 0 || m % TILE || n % TILE || k % KC) return bad("unaligned size (m, n multiples of 128, k of 16)");
+  if (batch_inner < 1 || batch_outer < 1 || (long)batch_inner * batch_outer > 64) return bad("batch counts must be >= 1, at most 64 entries");
+  const int tri = mode[0], klow = mode[1], mirror = mode[2], splits = mode[3], big = mode[4];
+  if (tri < 0 || tri > 2 || (klow & ~1) || (mirror & ~1) || (big & ~1) || splits < 1 || splits > 16) return bad("mode out of range");
+  if (mirror && beta != 0.0) return bad("mirror requires beta == 0");
+  if (mirror && (m != n || tri != 1)) return bad("mirror needs a square result and tri == 1");
+  if (klow && (m != n || k != m || la != FREE_CONTIG || lb != FREE_CONTIG)) return bad("klow needs m == n == k and both operands stored [k][free]");
+  const int batch = batch_inner * batch_outer, tx = n / TILE, ty = m / TILE;
+  for (int by = 0; by < ty; ++by)
+    for (int bx = 0; bx < tx; ++bx) {
+      if ((tri == 1 && bx > by) || (tri == 2 && bx < by)) continue;
+      const long klo = klow ? (long)std::max(by, bx) * TILE : 0;
+      if (((k - klo) / KC) % splits != 0) return bad("splits does not divide the k-chunks of every tile");
+    }
+  // the three windows: element offset, rows, cols, leading dimension, inner / outer batch stride, length of the parent
+  struct Win { long off, rows, cols, ld, s, o, len; const void* host; };
+  const Win w[3] = {{geom[9], la == K_CONTIG ? m : k, la == K_CONTIG ? k : m, geom[0], geom[3], geom[6], geom[12], A},
+                    {geom[10], lb == K_CONTIG ? n : k, lb == K_CONTIG ? k : n, geom[1], geom[4], geom[7], geom[13], B},
+                    {geom[11], m, n, geom[2], geom[5], geom[8], geom[14], C}};
+  auto at = [&](const Win& x, int bz) { return x.off + (long)(bz % batch_inner) * x.s + (long)(bz / batch_inner) * x.o; };
+  for (const Win& x : w) {
+    if (x.ld < x.cols || x.off < 0 || x.s < 0 || x.o < 0 || x.len <= 0) return bad("leading dimension below the window's width, or a negative offset or stride");
+    if ((x.ld | x.off | x.s | x.o) & 1) return bad("offsets, strides and leading dimensions must be even (16-byte rows)");
+    for (int bz = 0; bz < batch; ++bz)
+      if (at(x, bz) + (x.rows - 1) * x.ld + x.cols > x.len) return bad("a window runs past its parent buffer");
+  }
+  for (int i = 0; i < 3; ++i)
+    for (int j = i + 1; j < 3; ++j)
+      if (w[i].host == w[j].host && w[i].len != w[j].len) return bad("one parent buffer passed with two lengths");
+  // the overlap rule, for every pair of batch entries (launch_gemm checks the first): an operand in C's parent must not meet any C window,
+  // and no two C windows may meet
+  for (int bc = 0; bc < batch; ++bc) {
+    for (int i = 0; i < 2; ++i)
+      if (w[i].host == w[2].host)
+        for (int bz = 0; bz < batch; ++bz)
+          if (windows_meet(at(w[i], bz), w[i].rows, w[i].cols, w[i].ld, at(w[2], bc), m, n, w[2].ld)) return bad("C overlaps an operand");
+    for (int bz = bc + 1; bz < batch; ++bz)
+      if (windows_meet(at(w[2], bz), m, n, w[2].ld, at(w[2], bc), m, n, w[2].ld)) return bad("the C windows of two batch entries overlap");
+  }
+  GP_HIP(ctx, hipSetDevice(device));
+  // one device buffer per distinct host parent (the trailing update of the Cholesky has A == B and C in the same matrix)
+  DevBuf<double> d[3], dW;
+  double* dev[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < i; ++j) if (w[j].host == w[i].host) dev[i] = dev[j];
+    if (dev[i]) continue;
+    GP_TRY_RC(d[i].alloc(ctx, (size_t)w[i].len, DA_RAW));
+    GP_HIP(ctx, hipMemcpy(d[i], w[i].host, (size_t)w[i].len * 8, hipMemcpyHostToDevice));
+    dev[i] = d[i];
+  }
+  GemmP p;
+  p.A = dev[0] + w[0].off; p.B = dev[1] + w[1].off; p.C = dev[2] + w[2].off;
+  p.lda = w[0].ld; p.ldb = w[1].ld; p.ldc = w[2].ld;
+  p.sA = w[0].s; p.sB = w[1].s; p.sC = w[2].s; p.oA = w[0].o; p.oB = w[1].o; p.oC = w[2].o;
+  p.K = k; p.alpha = alpha; p.beta = beta; p.tri = tri; p.inner = batch_inner;
+  p.klow = klow; p.mirror = mirror; p.splits = splits; p.big = big;
+  if (splits > 1) {
+    // split-k workspace: batch * tiles * splits partial tiles, filled with NaN bytes so that a partial nobody wrote shows in the sum
+    GP_TRY_RC(dW.alloc(ctx, (size_t)batch * tx * ty * splits * TILE * TILE, DA_RAW));
+    GP_HIP(ctx, hipMemset(dW, 0xFF, dW.bytes()));
+    p.ws = dW;
+  }
+  launch_gemm(nullptr, la == K_CONTIG ? K_CONTIG : FREE_CONTIG, lb == K_CONTIG ? K_CONTIG : FREE_CONTIG, m, n, batch, p);
+  GP_HIP(ctx, hipGetLastError());
+  GP_HIP(ctx, hipDeviceSynchronize());
+  GP_HIP(ctx, hipMemcpy(C, dev[2], (size_t)w[2].len * 8, hipMemcpyDeviceToHost));
   return GP_OK;
 }
 

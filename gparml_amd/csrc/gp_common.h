@@ -40,8 +40,12 @@ struct GemmP {
   double* ws = nullptr;
   // X^T X with X lower-triangular (both operands FREE_CONTIG, stored [k][free], zero for k < free): with tri = 1 only the tiles on or below the diagonal
   // are computed, klow = 1 starts their k-range at the tile's first possibly non-zero k = max(row0, col0) (the skipped products are exact zeros:
-  // same bits), mirror = 1 stores every off-diagonal tile a second time transposed (the two halves were equal bit for bit before: same k order, and a
-  // product does not depend on which factor is the A operand)
+  // same bits, also under split-k -- the splits keep the full product's boundaries, gemm128_kernel), mirror = 1 stores every off-diagonal tile a second time transposed (the two halves were equal bit for bit before: same k order, and a
+  // product does not depend on which factor is the A operand).
+  // mirror REQUIRES beta == 0: the transposed element would have to be C0's own transposed element times beta, which none of the kernels reads -- the
+  // 32-tile kernel and the split-k reduce would copy beta * C0(r,c) across, the unsplit 128-tile kernel would not mirror at all.  launch_gemm, the one
+  // launch site of all three, refuses the combination (a programming error: abort), so no kernel is reachable with it (the fused tail of the global step
+  // walks gemm32_tile itself and never sets mirror).
   int klow = 0, mirror = 0;
   int big = 0;          // 1: the 128 x 128-tile kernel (with splits) whatever the tile count (the M x M x M products at M >= 1024)
 };

@@ -26,7 +26,7 @@ extern std::atomic<int> g_opt_i8_guard_strict;
 extern std::atomic<int> g_opt_gs_i8;      // gsi8.hip
 
 // r05, the global step at M >= 1024 (each switchable for same-box A/B through gp_debug_set_option):
-std::atomic<int> g_opt_xtx_tri{1};       // A^-1 = X^T X from its lower tiles, k from the tile's first non-zero row, mirrored store (bit-identical)
+std::atomic<int> g_opt_xtx_tri{1};       // A^-1 = X^T X from its lower tiles, k from the tile's first non-zero row, mirrored store (bit-identical, split or not: tests/test_gpu_linalg.py)
 std::atomic<int> g_opt_residual_dd{1};   // the refinement residual through ddacc_block (two rows per wave share E's loads) for Mp >= 256
 std::atomic<int> g_opt_trtri_rec{1};     // L^-1 by halves: two batched launches per level instead of two per block row
 std::atomic<int> g_opt_gemm_big{1};      // the M x M x {M, D} products on the 128 x 128-tile kernel (split-k 8 at M = 1024) for Mp >= 1024
@@ -944,6 +944,54 @@ extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double
     gp::g_create_error = c->err;
   }
   return rc;
+}
+
+// gp_debug_potrf_inverse for a batch, as the global step runs it: per-entry outputs, the raw fail mask, and (with_workspace) the split-k workspace
+// that takes the X^T X product onto the 128-tile kernel for Mp >= 1024.  The workspace has the floor of the shared workspace's capacity
+// (workspace_capacity, api.hip: 1100 tiles); choose_splits never asks for more than 512 partial tiles, so a larger capacity decides nothing differently.
+extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet,
+                                              int* fail_mask) {
+  using namespace gp;
+  gp_ctx tmp;
+  gp_ctx* c = &tmp;
+  if (n <= 0 || batch < 1 || batch > 8 || !A) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_potrf_inverse_batched: bad argument");
+  GP_HIP(c, hipSetDevice(device));
+  const int Mp = (int)round_up(n, NB);
+  const long mm = (long)Mp * Mp, nn = (long)n * n;
+  const size_t wcap = (size_t)1100 * TILE * TILE;
+  std::vector<double> h((size_t)batch * mm, 0.0);
+  for (int b = 0; b < batch; ++b)
+    for (int i = 0; i < Mp; ++i)
+      for (int k = 0; k < Mp; ++k) h[b * mm + (long)i * Mp + k] = (i < n && k < n) ? A[b * nn + (long)i * n + k] : (i == k ? 1.0 : 0.0);
+  DevBuf<double> dA, dLi, dInv, dT, dS, dW;     // (allocated without the context: a failure is reported by gp_last_error(NULL))
+  GP_TRY_RC(dA.alloc(nullptr, batch * mm, DA_RAW)); GP_TRY_RC(dLi.alloc(nullptr, batch * mm, DA_RAW)); GP_TRY_RC(dInv.alloc(nullptr, batch * mm, DA_RAW));
+  GP_TRY_RC(dT.alloc(nullptr, batch * mm / 2, DA_RAW)); GP_TRY_RC(dS.alloc(nullptr, 2 * batch, DA_RAW));
+  if (with_workspace) GP_TRY_RC(dW.alloc(nullptr, wcap, DA_RAW));
+  GP_HIP(c, hipMemcpy(dA, h.data(), dA.bytes(), hipMemcpyHostToDevice));
+  GP_HIP(c, hipMemset(dS, 0, dS.bytes()));
+  GP_HIP(c, hipMemset(dLi, 0, dLi.bytes()));          // the zero contract of Linv's upper blocks
+  // NaN bytes in everything the call must write before it reads
+  GP_HIP(c, hipMemset(dInv, 0xFF, dInv.bytes()));
+  GP_HIP(c, hipMemset(dT, 0xFF, dT.bytes()));
+  if (with_workspace) GP_HIP(c, hipMemset(dW, 0xFF, dW.bytes()));
+  int rc = potrf_inverse_batched(c, nullptr, Mp, batch, dA, dLi, dInv, dT, dS, dS + batch, with_workspace ? dW.get() : nullptr, with_workspace ? wcap : 0);
+  if (rc != GP_OK) { gp::g_create_error = c->err; return rc; }
+  std::vector<double> s(2 * batch);
+  GP_HIP(c, hipDeviceSynchronize());
+  GP_HIP(c, hipMemcpy(s.data(), dS, dS.bytes(), hipMemcpyDeviceToHost));
+  int mask = 0;
+  for (int b = 0; b < batch; ++b) { if (logdet) logdet[b] = s[b]; if (s[batch + b] != 0.0) mask |= 1 << b; }
+  if (fail_mask) *fail_mask = mask;
+  if (L) {
+    GP_HIP(c, hipMemcpy(h.data(), dA, dA.bytes(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; ++b) for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) L[b * nn + (long)i * n + k] = (k <= i) ? h[b * mm + (long)i * Mp + k] : 0.0;
+  }
+  if (Ainv) {
+    GP_HIP(c, hipMemcpy(h.data(), dInv, dInv.bytes(), hipMemcpyDeviceToHost));
+    for (int b = 0; b < batch; ++b) for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) Ainv[b * nn + (long)i * n + k] = h[b * mm + (long)i * Mp + k];
+  }
+  if (mask) return fail(nullptr, GP_ERR_NOT_PD, "gp_debug_potrf_inverse_batched: not positive definite (fail mask %d)", mask);
+  return GP_OK;
 }
 
 // raw copy of an internal buffer of the global step (developer tool, tests/devtools/dev_tail_diff.py; not part of the public header)

@@ -292,6 +292,20 @@ int gp_debug_peek(gp_ctx* ctx, const char* name, double* out, long n);
  * round 6): does an operand stored as rows x cols doubles with leading dimension ld, starting at element offset x_off of a buffer, share an element with the result
  * m x n, leading dimension ldc, at offset c_off of the SAME buffer?  Host arithmetic only (no device needed); returns 0 or 1. */
 int gp_debug_operands_overlap(long x_off, long rows, long cols, long ld, long c_off, long m, long n, long ldc);
+/* ONE internal matrix product with every field of its descriptor (csrc/gp_common.h, GemmP) chosen by the caller: C = alpha op(A) op(B) + beta C on
+ * windows of parent buffers, batched as inner x outer entries.  la / lb: 1 = the operand is stored [free][k] (k contiguous), 0 = [k][free]; m, n
+ * multiples of 128, k of 16.  geom = 15 longs: lda ldb ldc | inner strides sA sB sC | outer strides oA oB oC | element offset of the first window
+ * in its parent, A B C | length of each parent in doubles, A B C.  mode = 5 ints: tri (0 all tiles, 1 lower, 2 upper) | klow | mirror | splits | big.
+ * A, B, C are whole parents (host); equal pointers share one device buffer.  The split-k workspace (batch * tiles * splits * 128^2 doubles) is the
+ * hook's own; the whole C parent is copied back.  GP_ERR_BAD_ARG, without a launch, for unaligned sizes, a window past its parent, a splits that
+ * does not divide a tile's k-chunks, mirror with beta != 0, and any C window that shares an element with an operand or another C window. */
+int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int k, int batch_inner, int batch_outer, const long* geom, double alpha,
+                        double beta, const int* mode, const double* A, const double* B, double* C);
+/* gp_debug_potrf_inverse for `batch` SPD (n,n) matrices at once, as the global step runs it: A, L, Ainv are [batch][n][n], logdet [batch];
+ * *fail_mask gets bit b for a batch entry b that is not positive definite (then GP_ERR_NOT_PD is returned; all outputs are still written).
+ * with_workspace: hand the factorisation a split-k workspace, which moves X^T X to the 128 x 128-tile kernel for n > 896. */
+int gp_debug_potrf_inverse_batched(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet,
+                                   int* fail_mask);
 
 #ifdef __cplusplus
 }
