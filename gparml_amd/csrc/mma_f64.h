@@ -60,10 +60,6 @@ __device__ __forceinline__ void mfma_drain(double& last_acc) { asm volatile("s_n
 __device__ __forceinline__ void acc_fence8(double (&x)[8]) {
   asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
 }
-__device__ __forceinline__ void acc_fence16(double (&x)[16]) {
-  asm volatile("" : "+v"(x[0]), "+v"(x[1]), "+v"(x[2]), "+v"(x[3]), "+v"(x[4]), "+v"(x[5]), "+v"(x[6]), "+v"(x[7]));
-  asm volatile("" : "+v"(x[8]), "+v"(x[9]), "+v"(x[10]), "+v"(x[11]), "+v"(x[12]), "+v"(x[13]), "+v"(x[14]), "+v"(x[15]));
-}
 template <int N>
 __device__ __forceinline__ void acc_fence(double (&x)[N]) {
 #pragma unroll
@@ -233,42 +229,68 @@ __device__ __forceinline__ void mma_chunk(const double* sA, const double* sB, Ac
   mma_step(acc, a1, b1);
 }
 
-// single-buffered variant (40 fewer VGPRs): for kernels that keep other state live across the k-loop
-template <Layout LA, Layout LB>
-__device__ __forceinline__ void mma_chunk_sb(const double* sA, const double* sB, Acc& acc, const LaneOfs& o) {
+// ---- the eight-wave form -------------------------------------------------------------------------------------
+// p1_kernel8, p1v2_kernel's F jobs, p2_fast8_kernel and p2_gen8_kernel (psi.hip, p1v2.hip) run one structure: eight waves on a 128 x 128
+// workgroup tile, every 64 x 64 quadrant shared by two waves (64 rows x 32 columns: 32 accumulators per wave, four waves per SIMD), KC-deep
+// chunks staged by LDS-DMA into two buffers, operand reads as explicit ds_read_b64 and an lgkmcnt ladder in front of the 32 in-place MFMAs
+// of a k-step.  The k-step and the chunk staging live here, once.  The loops around them stay in the kernels: they differ in what travels
+// during the last chunk, and hipcc's schedule of the surrounding scalar code follows the order of the source statements, so every piece
+// below was introduced only where the kernel's assembly stayed the same, instruction for instruction (profiles/kloop8_asm_identity.txt).
+// p1_kernel8 takes the k-step only: with Wave8 or stage8_ff its assembly changes.
+struct Wave8 {
+  int wave, quad, half;   // wave = quad + 4 half: the two waves of a quadrant sit on the same SIMD
+  int wr, wc;             // the quadrant's row and column
+  int wrow0, wcol0;       // first row and column of the wave's 64 x 32 block inside the workgroup tile
+  __device__ __forceinline__ explicit Wave8(int w)
+      : wave(w), quad(w & 3), half(w >> 2), wr(quad >> 1), wc(quad & 1), wrow0(wr * WT), wcol0(wc * WT + 32 * half) {}
+};
+
+// One k-step (k = 4) of the wave's 64 x 32 block: 4 A + 8 B operand reads, then 32 MFMAs that start as soon as A and the first B have landed
+// (twice the LDS rate of the ds_read2_b64 pairs hipcc would form, see above).  aA / aB: LDS byte addresses of the lane's first A / B operand.
+//   B, and A when it is FREE_CONTIG: k-step K4 of the chunk is an immediate offset of K4 * 4 rows
+//   K_CONTIG A (A_KCONTIG): the caller's aA already carries LaneOfs::a[K4]; the four 16-row groups are 2048 B apart
+template <int K4, bool A_KCONTIG>
+__device__ __forceinline__ void kstep8(double (&acc)[4][8], unsigned aA, unsigned aB) {
+  double a[4], b[8];
+  static_for<0, 4>([&](auto ic) {
+    constexpr int ar = decltype(ic)::value;
+    a[ar] = ds_read64<A_KCONTIG ? 2048 * ar : K4 * 4 * LDS_RC * 8 + 128 * ar>(aA);
+  });
+  static_for<0, 8>([&](auto jc) { constexpr int j = decltype(jc)::value; b[j] = ds_read64<K4 * 4 * LDS_RC * 8 + 32 * j>(aB); });
+  static_for<0, 8>([&](auto jc) {
+    constexpr int j = decltype(jc)::value;
+    lgkm_wait<7 - j>();
 #pragma unroll
-  for (int k4 = 0; k4 < KC / 4; ++k4) {
-    double a[4], b[16];
-    load_operands<LA, LB>(sA, sB, o, k4, a, b);
-    mma_step(acc, a, b);
-  }
+    for (int ar = 0; ar < 4; ++ar) mfma444_acc(acc[ar][j], a[ar], b[j]);
+  });
 }
 
-// lowest-register variant: B operands in two groups of 8 (16 fewer VGPRs than mma_chunk_sb)
-template <Layout LA, Layout LB>
-__device__ __forceinline__ void mma_chunk_lo(const double* sA, const double* sB, Acc& acc, const LaneOfs& o) {
+// Chunk staging: 16 LDS-DMA instructions per operand tile, two per wave.
+// Both operands FREE_CONTIG with row stride ld (rows of 128 doubles) into the double-buffered pair of tiles lds[buf]
+using Tiles8 = double[2][2][TILE_LDS_DOUBLES];
+__device__ __forceinline__ void stage8_ff(Tiles8& lds, int buf, const double* a, const double* b, long ld, int wave, int lane) {
 #pragma unroll
-  for (int k4 = 0; k4 < KC / 4; ++k4) {
-    double a[4];
-#pragma unroll
-    for (int ar = 0; ar < 4; ++ar)
-      a[ar] = (LA == FREE_CONTIG) ? sA[o.a[0] + 4 * k4 * LDS_RC + 16 * ar] : sA[o.a[k4] + 256 * ar];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      double b[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int bc = 8 * h + j;
-        b[j] = (LB == FREE_CONTIG)
-                   ? sB[o.b[0] + 4 * k4 * LDS_RC + 4 * bc]
-                   : sB[o.b[k4 & 1] + (bc & 1) * 64 + ((bc >> 1) & 1) * 16 + (bc >> 2) * 256 + (((k4 >> 1) ^ (bc & 1)) << 3)];
-      }
-#pragma unroll
-      for (int ar = 0; ar < 4; ++ar)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) mfma444_acc(acc.v[ar][8 * h + j], a[ar], b[j]);
-    }
+  for (int i = 0; i < 2; ++i) {
+    const int row = wave * 2 + i;
+    glds16(a + (long)row * ld + 2 * lane, lds[buf][0] + row * LDS_RC);
+    glds16(b + (long)row * ld + 2 * lane, lds[buf][1] + row * LDS_RC);
   }
 }
+// A K_CONTIG (row stride lda), B FREE_CONTIG (row stride ldb) into buf = [A tile | B tile]; lane offsets are 32-bit (uniform base + offset addressing)
+__device__ __forceinline__ void stage8_kf(double* buf, const double* a, const double* b, long lda, int ldb, int wave, int lane) {
+  int ld_ = lane;
+  asm volatile("" : "+v"(ld_));                             // recomputed per chunk (a handful of integer ops) instead of held in registers
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int I = wave * 2 + i;
+    const int row = swap03(I * 8 + (ld_ >> 3));
+    // byte offset as an unsigned 32-bit value: uniform base + 32-bit lane offset addressing (one address register instead of two)
+    glds16(reinterpret_cast<const double*>(reinterpret_cast<const char*>(a) + (unsigned)(8 * (row * (int)lda + 2 * ((ld_ & 7) ^ (row & 7))))),
+           buf + I * 8 * KC);
+    glds16(b + (long)I * ldb + 2u * ld_, buf + TILE_LDS_DOUBLES + I * LDS_RC);
+  }
+}
+// (Staging the B tile for every second chunk only -- 25 % fewer LDS-DMA instructions per flop, what a 256 x 128 workgroup tile would issue -- and
+// no staging at all were measured on p2_fast8_kernel with the same instruction stream otherwise: profiles/r03_p2_dma_ablation.txt, r04_power_ab.txt.)
 
 }  // namespace gp

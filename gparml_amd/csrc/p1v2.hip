@@ -21,22 +21,9 @@ namespace gp {
 struct P1Job { int kind; int acol; int bcol; int c0; int c1; int out; int pad0; int pad1; };   // kind: -1 idle, 0 F, 1 G
 struct P1v2Args { const double* Kaug; long ld; const P1Job* jobs; double* part; };
 
-using LdsTiles = double[2][2][TILE_LDS_DOUBLES];
-
-// both operand tiles of one k-chunk: 16 LDS-DMA instructions per tile, two per wave (FREE_CONTIG rows of 128 doubles)
-__device__ __forceinline__ void p1v2_dma(LdsTiles& lds, int buf, const double* a, const double* b, long ld, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int row = wave * 2 + i;
-    glds16(a + (long)row * ld + 2 * lane, lds[buf][0] + row * LDS_RC);
-    glds16(b + (long)row * ld + 2 * lane, lds[buf][1] + row * LDS_RC);
-  }
-}
-
-// ---- F job: a full 128x128 tile, wave = 64 rows x 32 columns (the p1_kernel8 loop)
-__device__ __forceinline__ void p1v2_full(const P1v2Args& p, const P1Job& jb, LdsTiles& lds, int wave, int lane) {
-  const int quad = wave & 3, half = wave >> 2;
-  const int wrow0 = (quad >> 1) * WT, wcol0 = (quad & 1) * WT + 32 * half;
+// ---- F job: a full 128x128 tile on the eight-wave form (mma_f64.h), wave = 64 rows x 32 columns
+__device__ __forceinline__ void p1v2_full(const P1v2Args& p, const P1Job& jb, Tiles8& lds, int wave, int lane) {
+  const Wave8 w(wave);
   const double* Ab = p.Kaug + jb.acol + (long)jb.c0 * KC * p.ld;
   const double* Bb = p.Kaug + jb.bcol + (long)jb.c0 * KC * p.ld;
   const long step = (long)KC * p.ld;
@@ -47,27 +34,16 @@ __device__ __forceinline__ void p1v2_full(const P1v2Args& p, const P1Job& jb, Ld
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[ar][j] = 0.0;
   const int lr = lane & 15, lk = lane >> 4, lj = lane & 3;
-  const int aofs = lk * LDS_RC + wrow0 + lr, bofs = lk * LDS_RC + wcol0 + lj;
-  p1v2_dma(lds, 0, Ab, Bb, p.ld, wave, lane);
+  const int aofs = lk * LDS_RC + w.wrow0 + lr, bofs = lk * LDS_RC + w.wcol0 + lj;
+  stage8_ff(lds, 0, Ab, Bb, p.ld, wave, lane);
   dma_wait();
   __syncthreads();
   for (int c = 0; c < nc; ++c) {
     const int cur = c & 1;
-    if (c + 1 < nc) p1v2_dma(lds, cur ^ 1, Ab + (long)(c + 1) * step, Bb + (long)(c + 1) * step, p.ld, wave, lane);
+    if (c + 1 < nc) stage8_ff(lds, cur ^ 1, Ab + (long)(c + 1) * step, Bb + (long)(c + 1) * step, p.ld, wave, lane);
     const unsigned aA = lds_byte_addr(lds[cur][0]) + 8u * (unsigned)aofs;
     const unsigned aB = lds_byte_addr(lds[cur][1]) + 8u * (unsigned)bofs;
-    static_for<0, KC / 4>([&](auto k4c) {
-      constexpr int k4 = decltype(k4c)::value;
-      double a[4], b[8];
-      static_for<0, 4>([&](auto ic) { constexpr int ar = decltype(ic)::value; a[ar] = ds_read64<k4 * 4 * LDS_RC * 8 + 128 * ar>(aA); });
-      static_for<0, 8>([&](auto jc) { constexpr int j = decltype(jc)::value; b[j] = ds_read64<k4 * 4 * LDS_RC * 8 + 32 * j>(aB); });
-      static_for<0, 8>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        lgkm_wait<7 - j>();
-#pragma unroll
-        for (int ar = 0; ar < 4; ++ar) mfma444_acc(acc[ar][j], a[ar], b[j]);
-      });
-    });
+    static_for<0, KC / 4>([&](auto k4c) { kstep8<decltype(k4c)::value, false>(acc, aA, aB); });
     dma_wait();
     __syncthreads();
   }
@@ -78,7 +54,7 @@ __device__ __forceinline__ void p1v2_full(const P1v2Args& p, const P1Job& jb, Ld
 #pragma unroll
   for (int ar = 0; ar < 4; ++ar)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) out[(wrow0 + acc_row(ar, lane)) * TILE + wcol0 + acc_col(j, lane)] = acc[ar][j];
+    for (int j = 0; j < 8; ++j) out[(w.wrow0 + acc_row(ar, lane)) * TILE + w.wcol0 + acc_col(j, lane)] = acc[ar][j];
 }
 
 // ---- G job, wave (P, H): 16-row groups A1 = P and A2 = 7 - P of diagonal tile i.
@@ -86,7 +62,7 @@ __device__ __forceinline__ void p1v2_full(const P1v2Args& p, const P1Job& jb, Ld
 //   H = 1: C blocks (A1, y >= Y0) and (A2, all y)                                        2 NBY - Y0 accumulators
 // Y0 = NBY - 18 balances the two (NBY >= 18); operands are read in groups of at most eight 4-column groups.
 template <int P, int H, int NBY>
-__device__ __forceinline__ void p1v2_diag(const P1v2Args& p, const P1Job& jb, LdsTiles& lds, int wave, int lane) {
+__device__ __forceinline__ void p1v2_diag(const P1v2Args& p, const P1Job& jb, Tiles8& lds, int wave, int lane) {
   constexpr int A1 = P, A2 = 7 - P;
   constexpr int B1 = 4 * A1, B2 = 4 * A2;                 // first column group of the two row groups' upper-triangle parts (B2 >= B1)
   constexpr int Y0 = NBY > 18 ? NBY - 18 : 0;
@@ -105,12 +81,12 @@ __device__ __forceinline__ void p1v2_diag(const P1v2Args& p, const P1Job& jb, Ld
   const long step = (long)KC * p.ld;
   const int nc = jb.c1 - jb.c0;
   const int lr = lane & 15, lk = lane >> 4, lj = lane & 3;
-  p1v2_dma(lds, 0, Ab, Bb, p.ld, wave, lane);
+  stage8_ff(lds, 0, Ab, Bb, p.ld, wave, lane);
   dma_wait();
   __syncthreads();
   for (int c = 0; c < nc; ++c) {
     const int cur = c & 1;
-    if (c + 1 < nc) p1v2_dma(lds, cur ^ 1, Ab + (long)(c + 1) * step, Bb + (long)(c + 1) * step, p.ld, wave, lane);
+    if (c + 1 < nc) stage8_ff(lds, cur ^ 1, Ab + (long)(c + 1) * step, Bb + (long)(c + 1) * step, p.ld, wave, lane);
     const unsigned rowop = lds_byte_addr(lds[cur][0]) + 8u * (unsigned)(lk * LDS_RC + lr);   // A-operand view of the K tile (16 rows of the output)
     const unsigned colK = lds_byte_addr(lds[cur][0]) + 8u * (unsigned)(lk * LDS_RC + lj);    // B-operand view of the SAME tile (4 output columns)
     const unsigned colY = lds_byte_addr(lds[cur][1]) + 8u * (unsigned)(lk * LDS_RC + lj);    // B-operand view of the Y tile

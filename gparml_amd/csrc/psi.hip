@@ -404,21 +404,9 @@ __global__ void __launch_bounds__(512, 4) p1_kernel8(P1Args p) {
     const int cur = c & 1;
     if (c + 1 < nc) dma(cur ^ 1, Ab + (long)(c + 1) * step, Bb + (long)(c + 1) * step);
     if (!skip) {
-      // operand reads as explicit ds_read_b64 (mma_f64.h): twice the LDS rate of the ds_read2_b64 pairs hipcc would form
       const unsigned aA = lds_byte_addr(lds[cur][0]) + 8u * (unsigned)aofs;
       const unsigned aB = lds_byte_addr(lds[cur][1]) + 8u * (unsigned)bofs;
-      static_for<0, KC / 4>([&](auto k4c) {
-        constexpr int k4 = decltype(k4c)::value;
-        double a[4], b[8];
-        static_for<0, 4>([&](auto ic) { constexpr int ar = decltype(ic)::value; a[ar] = ds_read64<k4 * 4 * LDS_RC * 8 + 128 * ar>(aA); });
-        static_for<0, 8>([&](auto jc) { constexpr int j = decltype(jc)::value; b[j] = ds_read64<k4 * 4 * LDS_RC * 8 + 32 * j>(aB); });
-        static_for<0, 8>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          lgkm_wait<7 - j>();
-#pragma unroll
-          for (int ar = 0; ar < 4; ++ar) mfma444_acc(acc[ar][j], a[ar], b[j]);
-        });
-      });
+      static_for<0, KC / 4>([&](auto k4c) { kstep8<decltype(k4c)::value, false>(acc, aA, aB); });
     }
     dma_wait();
     __syncthreads();
@@ -743,10 +731,9 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
   // Static priority for the second-dispatched half of the workgroup: with both halves at priority 0 the younger waves lose the VALU / LDS
   // issue arbitration in every k-chunk (MI355X_MICROARCH.md, "Two waves per SIMD", item 4); same-box A/B: 10.27 -> 10.14 ms
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-  const int quad = wave & 3, half = wave >> 2;
-  const int wr = quad >> 1, wc = quad & 1;
-  const int wrow0 = wr * WT, wcol0 = wc * WT + 32 * half;
-  const int lr = lane & 15, lk = lane >> 4, lj = lane & 3;
+  const Wave8 w(wave);
+  const int half = w.half, wr = w.wr, wrow0 = w.wrow0, wcol0 = w.wcol0;
+  const int lj = lane & 3;
   const int srow = 4 * ((lane >> 2) & 3) + (lane >> 4);
   const LaneOfs ofs = lane_offsets<K_CONTIG, FREE_CONTIG>(wrow0, wcol0, lane);
   const int nc = p.kend - p.kbeg;
@@ -758,29 +745,6 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
   double r[2][NRB], gq[NRB];
 #pragma unroll
   for (int g = 0; g < NRB; ++g) { r[0][g] = 0.0; r[1][g] = 0.0; gq[g] = 0.0; }
-  // chunk staging: 16 DMA instructions per operand tile, two per wave; lane offsets are 32-bit (uniform base + offset addressing)
-  auto chunk_dma = [&](double* buf, const double* a, const double* b) {
-    int ld_ = lane;
-    asm volatile("" : "+v"(ld_));                             // recomputed per chunk (a handful of integer ops) instead of held in registers
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int I = wave * 2 + i;
-      const int row = swap03(I * 8 + (ld_ >> 3));
-      // byte offset as an unsigned 32-bit value: uniform base + 32-bit lane offset addressing (one address register instead of two)
-#if !defined(GPARML_ABLATE_P2_DMA) || GPARML_ABLATE_P2_DMA < 2
-      glds16(reinterpret_cast<const double*>(reinterpret_cast<const char*>(a) + (unsigned)(8 * (row * (int)p.ld + 2 * ((ld_ & 7) ^ (row & 7))))),
-             buf + I * 8 * KC);
-#endif
-      // ablation builds (tools/r03_p2_ablate.sh; wrong results, same instruction stream otherwise): 1 = the B tile is staged for every
-      // second chunk only -- 25 % fewer LDS-DMA instructions per flop, what a 256 x 128 workgroup tile would issue; 2 = no staging at all
-#if defined(GPARML_ABLATE_P2_DMA) && GPARML_ABLATE_P2_DMA == 1
-      if ((reinterpret_cast<size_t>(b) / (KC * 8 * (size_t)p.Mp)) & 1)
-#endif
-#if !defined(GPARML_ABLATE_P2_DMA) || GPARML_ABLATE_P2_DMA < 2
-      glds16(b + (long)I * p.Mp + 2u * ld_, buf + TILE_LDS_DOUBLES + I * LDS_RC);
-#endif
-    }
-  };
   // Epilogue addressing is derived from an OPAQUE copy of the lane id at its point of use: as loop invariants these values
   // would stay live across the k-loop and push the kernel over its 128 registers (scratch spills).
   struct Epi { int lr, lk, lj, srow, sg, sbase, abase, aflip, dpair; };
@@ -838,7 +802,7 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
     }
     int kc = 0;
     const int b0 = (nc + 1) & 1;                                // buffer of chunk 0; chunk c uses (c + nc + 1) & 1, the last one buf0
-    chunk_dma(lds + b0 * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp);
+    stage8_kf(lds + b0 * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, lane);
     dma_wait();
     __syncthreads();
     for (int c = 0; c < nc; ++c) {
@@ -849,7 +813,7 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
       auto issue_next = [&]() {
         if (c + 1 < nc) {
           ++kc;
-          chunk_dma(lds + (cur ^ 1) * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp);
+          stage8_kf(lds + (cur ^ 1) * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, lane);
         } else {
           // last chunk (computing from buf0): slab 0 of this wave and the tile's Xa rows into buf1 + extra
           const Epi e0 = epi();
@@ -862,30 +826,16 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
         }
       };
       if (half == 0) issue_next();
-      // operand reads as explicit ds_read_b64 (see mma_f64.h): 4 A + 8 B per k-step, MFMAs start as soon as A and the first B landed
       const unsigned sbase_b = lds_base + (unsigned)cur * (4608u * 8u);
       const unsigned aB = sbase_b + TILE_LDS_DOUBLES * 8 + 8u * (unsigned)ofs.b[0];
-      const bool tail = (c == nc - 1);
       static_for<0, KC / 4>([&](auto k4c) {
         constexpr int k4 = decltype(k4c)::value;
         if constexpr (k4 == 2) { if (half == 1) issue_next(); }
-#ifdef GPARML_FAST8_KSKIP
-        // Skipping the k-steps that only multiply Y's zero padding (three of 156 at D = 100) is NOT done here: same kernel time (the last chunk of a
-        // tile waits for the epilogue's first DMA anyway), but FETCH_SIZE 11.55 -> 14.2 GB per launch, reproducibly (tools/r03_traffic_ab.sh): the
-        // shortened last chunk lets the four m-tile workgroups of a slice drift apart and they stop finding each other's rows in L2.
+        // Skipping the last chunk's k-steps that only multiply Y's zero padding (three of 156 at D = 100) is NOT done here: same kernel time (the last
+        // chunk of a tile waits for the epilogue's first DMA anyway), but FETCH_SIZE 11.55 -> 14.2 GB per launch, reproducibly: the shortened last
+        // chunk lets the four m-tile workgroups of a slice drift apart and they stop finding each other's rows in L2.
         // p2_gen8_kernel, whose k-loop at D = 100 is seven chunks, keeps the skip (-10 % of its loop).
-        if (k4 > 0 && tail && k4 >= p.klast) return;
-#endif
-        const unsigned aA = sbase_b + 8u * (unsigned)ofs.a[k4];
-        double a[4], b[8];
-        a[0] = ds_read64<0>(aA); a[1] = ds_read64<2048>(aA); a[2] = ds_read64<4096>(aA); a[3] = ds_read64<6144>(aA);
-        static_for<0, 8>([&](auto jc) { constexpr int j = decltype(jc)::value; b[j] = ds_read64<k4 * 4 * LDS_RC * 8 + 32 * j>(aB); });
-        static_for<0, 8>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          lgkm_wait<7 - j>();
-#pragma unroll
-          for (int ar = 0; ar < 4; ++ar) mfma444_acc(acc[ar][j], a[ar], b[j]);
-        });
+        kstep8<k4, true>(acc, sbase_b + 8u * (unsigned)ofs.a[k4], aB);
       });
       dma_wait();
       __syncthreads();
@@ -975,9 +925,8 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
   __shared__ __attribute__((aligned(16))) double lds[P2W8_LDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-  const int quad = wave & 3, half = wave >> 2;
-  const int wr = quad >> 1, wc = quad & 1;
-  const int wrow0 = wr * WT, wcol0 = wc * WT + 32 * half;
+  const Wave8 w(wave);
+  const int half = w.half, wr = w.wr, wc = w.wc, wrow0 = w.wrow0, wcol0 = w.wcol0;
   const int nc = p.kend - p.kbeg;
   const int t0 = slice * p.tps, t1 = min(p.ntiles, t0 + p.tps);
   const unsigned lds_base = lds_byte_addr(lds);
@@ -990,18 +939,6 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
 #define G8SEC(k)
 #endif
   double* const slab = area + 512;
-  auto chunk_dma = [&](double* buf, const double* a, const double* b) {
-    int ld_ = lane;
-    asm volatile("" : "+v"(ld_));
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int I = wave * 2 + i;
-      const int row = swap03(I * 8 + (ld_ >> 3));
-      glds16(reinterpret_cast<const double*>(reinterpret_cast<const char*>(a) + (unsigned)(8 * (row * (int)p.ld + 2 * ((ld_ & 7) ^ (row & 7))))),
-             buf + I * 8 * KC);
-      glds16(b + (long)I * p.Mp + 2u * ld_, buf + TILE_LDS_DOUBLES + I * LDS_RC);
-    }
-  };
   for (int nt = t0; nt < t1; ++nt) {
     const long n0 = (long)nt * TILE;
     const double* Ab = p.Kaug + n0 * p.ld + (long)p.kbeg * KC;
@@ -1018,13 +955,13 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
 #pragma unroll
     for (int ar = 0; ar < 4; ++ar) acc_fence8(acc[ar]);                  // asm-defined zeros: no rematerialised v_mov in front of an asm MFMA
     G8SEC(7)
-    chunk_dma(lds, Ab, Bb);
+    stage8_kf(lds, Ab, Bb, p.ld, p.Mp, wave, lane);
     dma_wait();
     __syncthreads();
     G8SEC(0)
     for (int c = 0; c < nc; ++c) {
       const int cur = c & 1;
-      auto issue_next = [&]() { if (c + 1 < nc) chunk_dma(lds + (cur ^ 1) * 4608, Ab + (long)(c + 1) * KC, Bb + (long)(c + 1) * KC * p.Mp); };
+      auto issue_next = [&]() { if (c + 1 < nc) stage8_kf(lds + (cur ^ 1) * 4608, Ab + (long)(c + 1) * KC, Bb + (long)(c + 1) * KC * p.Mp, p.ld, p.Mp, wave, lane); };
       if (half == 0) issue_next();
       const unsigned sbase_b = lds_base + (unsigned)cur * (4608u * 8u);
       const unsigned aB = sbase_b + TILE_LDS_DOUBLES * 8 + 8u * (unsigned)ofs.b[0];
@@ -1033,16 +970,7 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
         constexpr int k4 = decltype(k4c)::value;
         if constexpr (k4 == 2) { if (half == 1) issue_next(); }
         if (k4 > 0 && tail && k4 >= p.klast) return;   // k-steps past the last real Y column multiply zeros
-        const unsigned aA = sbase_b + 8u * (unsigned)ofs.a[k4];
-        double a[4], b[8];
-        a[0] = ds_read64<0>(aA); a[1] = ds_read64<2048>(aA); a[2] = ds_read64<4096>(aA); a[3] = ds_read64<6144>(aA);
-        static_for<0, 8>([&](auto jc) { constexpr int j = decltype(jc)::value; b[j] = ds_read64<k4 * 4 * LDS_RC * 8 + 32 * j>(aB); });
-        static_for<0, 8>([&](auto jc) {
-          constexpr int j = decltype(jc)::value;
-          lgkm_wait<7 - j>();
-#pragma unroll
-          for (int ar = 0; ar < 4; ++ar) mfma444_acc(acc[ar][j], a[ar], b[j]);
-        });
+        kstep8<k4, true>(acc, sbase_b + 8u * (unsigned)ofs.a[k4], aB);
       });
       dma_wait();
       __syncthreads();
@@ -1059,9 +987,6 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
     // W = G o Psi1 in the accumulator layout (row 16 ar + srow, column 4 bc + lj of the wave's 64 x 32 block).  The wave's Psi1 block
     // arrives by LDS-DMA in four 16-row slabs, two in flight (register-staged loads of the 32 values do not fit next to the accumulators:
     // the compiler serialised them, one L2 round trip per value); slab image permuted as in p2_fast8_kernel (pair p of row r at p ^ 2 g(r))
-#if defined(GPARML_GEN8_ABLATE) && (GPARML_GEN8_ABLATE & 4)
-    if (p.MT < 0)
-#endif
     {
       const int sg = slab_g(srow), sbase = srow * 32 + lj;
       const int dpair = (le & 15) ^ ((lk & 1) << 3);
@@ -1089,22 +1014,11 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
       }
     }
     G8SEC(2)
-#ifdef GPARML_GEN8_ABLATE   // timing experiments only (results wrong): bit 0 = no m-contraction, bit 1 = no n-contraction, bit 2 = no Psi1 product
-    if (p.MT < 0) {
-#pragma unroll
-      for (int ar = 0; ar < 4; ++ar)
-#pragma unroll
-        for (int bc = 0; bc < 8; ++bc) p.HZp[(ar * 8 + bc) * 64 + le] = acc[ar][bc];
-    }
-#endif
     // ---- n-contraction, straight from the accumulators: R[m][c] += sum_n W[n][m] Xa[n][c], this wave's 32 columns m.
     // v_mfma_f64_4x4x4_4b computes four independent 4x4x4 blocks; lane l = (k = l >> 4, block b = (l >> 2) & 3, j = l & 3) holds
     // W[16 ar + 4 b + k][4 bc + j] in acc[ar][bc] -- exactly the B operand B_b[k][j] of block b.  With A_b[i][k] = Xa[16 ar + 4 b + k][c0 + i]
     // (lane (i = l & 3, b, k): the same row 16 ar + srow, column c0 + lj) block b accumulates its four points' share of R[4 bc + j][c0 + i];
     // the four block partials are added through the wave's LDS area.  No transposed copy of W is needed.
-#if defined(GPARML_GEN8_ABLATE) && (GPARML_GEN8_ABLATE & 2)
-    if (p.MT < 0)
-#endif
     {
       double* Rmine = p.Rpart + ((long)(slice * 2 + wr) * p.Mp + (long)mt * TILE + wcol0) * p.CXp;
       const double* xbase = p.Xa + (n0 + wrow0) * p.CXp;          // uniform bases + 32-bit lane offsets (scalar-base addressing)
@@ -1170,11 +1084,7 @@ __global__ void __launch_bounds__(512, 4) p2_gen8_kernel(P2Args p) {
     // columns per group, staged in LDS by DMA one group ahead (read from global memory it would be one replicated 512-byte load per MFMA).
     // Each wave contracts its own 32 columns; the four partials of a 32-row half are exchanged through LDS and added in column order, so HZp
     // holds ONE array per 128-column tile.  (v_mfma_f64_16x16x4 with 64 distinct B values per load was tried: half rate, same kernel time.)
-#if defined(GPARML_GEN8_ABLATE) && (GPARML_GEN8_ABLATE & 1)
-    if (p.MT < 0)
-#else
     if (PPATH)
-#endif
     {
       int lm = lane;                                        // fresh lane coordinates: carried over from above they are spilled
       asm volatile("" : "+v"(lm));
