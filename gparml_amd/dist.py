@@ -5,12 +5,12 @@ on the GPU box; "gloo" in the CPU tests).
 Per evaluation there are exactly two collectives:
     phase 1:  [Psi2 (Mp*Mp) | Psi1^T Y (Mp*Dp) | sum_YYT, Psi0, KL, n_local]   -> global step (replicated)
     phase 2:  [grad_Z data part (M*Q) | grad_alpha data part (Q)]             -> finish
-The engine object only needs the methods used below, so the CPU tests drive this protocol with an
+The engine object only needs the methods gparml_amd.evaluation uses, so the CPU tests drive this protocol with an
 oracle-backed stand-in while the product path uses gparml_amd.engine.ShardEngine.
 """
 import numpy as np
 
-from ._lib import JitterRetry
+from .evaluation import BufferReduce, evaluate
 
 
 class _DevArray(object):
@@ -157,44 +157,29 @@ class DistributedEvaluator(object):
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self._stats_t = None
-        self._grads_t = None
         self.device = device
         self.force = force_collectives and dist.is_initialized()
-        self._packed = False
         self.time_collectives = False     # bench.py: device-side time of the two all-reduces of the last evaluation
         self._cev = None
+        self.last_jitter = 0              # the jitter mask the last evaluation ended with (0: none)
         # the reduce inside the library (gp_allreduce: RCCL on the engine's stream) when the process group is RCCL; otherwise torch.distributed
-        # all-reduces the same device buffers (gloo in the CPU / one-device tests)
-        self.native = (self.world > 1 or self.force) and init_native_comm(engine, dist, group)
-
-    def _tensors(self):
-        if self._stats_t is None:
-            if hasattr(self.engine, 'host_buffers'):            # CPU stand-in (tests): numpy-backed tensors
-                import torch
-                s, g = self.engine.host_buffers()
-                self._stats_t, self._grads_t = torch.from_numpy(s), torch.from_numpy(g)
-            else:
-                # the packed form (Psi2's upper triangle, no padding) where the engine has it: 1.46 MB instead of 2.6 MB at M=512, D=100
-                self._packed = hasattr(self.engine, 'stats_packed_buffer')
-                p, n = self.engine.stats_packed_buffer() if self._packed else self.engine.stats_buffer()
-                self._stats_t = device_tensor(p, n, self.device)
-                p, n = self.engine.grads_buffer()
-                self._grads_t = device_tensor(p, n, self.device)
-        return self._stats_t, self._grads_t
+        # all-reduces the same device buffers (gloo in the CPU / one-device tests).  Agreed among the ranks here, not in the first evaluation.
+        self._reduce = BufferReduce([engine], dist=dist if (self.world > 1 or self.force) else None, group=group, device=device)
+        self.native = self._reduce.native
+        self._tensors = self._reduce.tensors      # the zero-copy torch views of the two packed buffers (a CPU stand-in: its host_buffers())
 
     def evaluate(self, want_embedding_grads=False, kept_mask=None, kept_fraction=None):
-        """One bound+gradient evaluation across all shards.
+        """One bound+gradient evaluation across all shards (evaluation.evaluate with this rank's engine).
 
         Node drop-out (local_MapReduce.py:119-129, 263-264): ``kept_mask`` is the keep/drop decision for EVERY rank, identical on all
         ranks (``draw_kept_mask`` with a shared seed).  A dropped rank contributes nothing to either reduction -- the reference
         sums all twelve statistics, the derivative sums behind grad_Z / grad_alpha included, over the kept nodes only -- and both
         reduced buffers are divided by ``kept_fraction`` = kept/(kept+dropped).  Every rank still runs phase 2 for its own embedding
         gradients (embeddings_MR visits all nodes, local_MapReduce.py:293-295)."""
-        eng = self.engine
-        collective = self.world > 1 or self.force
-        native = collective and self.native
-        stats_t, grads_t = self._tensors() if (collective and not native) else (None, None)   # zero-copy torch views of the packed device buffers
+        r = self._reduce
+        collective = r.dist is not None
+        if collective and not r.native:
+            self._tensors()             # made before phase 1, as ever
         kept_here = True
         if kept_mask is not None:
             kept_mask = [bool(k) for k in kept_mask]
@@ -202,53 +187,10 @@ class DistributedEvaluator(object):
             kept_here = kept_mask[self.rank]
             if kept_fraction is None:
                 kept_fraction = float(sum(kept_mask)) / len(kept_mask)
-        rescale = kept_fraction is not None and kept_fraction != 1.0
-        cev = self._collective_events() if (collective and self.time_collectives) else None
-        eng.phase1()
-        if not kept_here:
-            eng.scale_buffer('stats', 0.0)
-        if native:
-            if cev:
-                cev[0].record()
-            eng.allreduce('stats')            # pack -> ncclAllReduce -> unpack on the engine's stream
-            if cev:
-                cev[1].record()
-        elif collective:
-            if self._packed:
-                eng.stats_pack()
-            if cev:
-                cev[0].record()
-            self.dist.all_reduce(stats_t, op=self.dist.ReduceOp.SUM, group=self.group)
-            if cev:
-                cev[1].record()
-            if self._packed:
-                eng.stats_unpack()
-        if rescale:
-            eng.scale_buffer('stats', 1.0 / kept_fraction)
-        jitter = 0
-        while True:
-            eng.global_step(sync=False, jitter=jitter)
-            eng.phase2(want_embedding_grads)
-            if not kept_here:
-                eng.scale_buffer('grads', 0.0)
-            if collective:
-                if cev:
-                    cev[2].record()
-                if native:
-                    eng.allreduce('grads')
-                else:
-                    self.dist.all_reduce(grads_t, op=self.dist.ReduceOp.SUM, group=self.group)
-                if cev:
-                    cev[3].record()
-            if rescale:
-                eng.scale_buffer('grads', 1.0 / kept_fraction)
-            try:
-                return eng.finish()       # the evaluation's only host synchronisation
-            except JitterRetry as r:
-                # every rank holds the same reduced statistics and runs the same replicated global step, so all ranks take this
-                # branch together: repeat the global step with the reference's 1e-7 jitter (partial_terms.py:452-456)
-                jitter = r.mask
-
+        r.dropped, r.fraction = not kept_here, kept_fraction
+        r.events = self._collective_events() if (collective and self.time_collectives) else None
+        out, self.last_jitter = evaluate([self.engine], r, want_embedding_grads)
+        return out
 
     def _collective_events(self):
         """Four timing events on torch's current stream (the stream the engine launches on and the collectives are ordered behind)."""

@@ -18,7 +18,7 @@ import time
 
 import numpy
 
-from ._lib import JitterRetry
+from .evaluation import BufferReduce, evaluate
 
 
 def _f(x):
@@ -73,6 +73,13 @@ def transform_grad_vec(mask, x):
     assert numpy.all((-LIM_VAL < xp) & (xp < LIM_VAL))
     out[mask] = 1 / (numpy.exp(-xp) + 1)
     return out
+
+
+def split_flat(flat, M, Q):
+    """(Z (M, Q), sf2, alpha (Q,), beta) of a flat parameter vector: order Z (row-major), sf2, alpha, beta (parallel_GPLVM.py:139-141)."""
+    flat = numpy.asarray(flat, dtype=float)
+    n = M * Q
+    return flat[:n].reshape(M, Q), flat[n], flat[n + 1:n + 1 + Q], flat[n + 1 + Q]
 
 
 def _device_kmeans(map_reduce, options, names, engine_class=None):
@@ -167,12 +174,8 @@ class Driver(object):
         return numpy.concatenate([numpy.asarray(gs[k], dtype=float).flatten() for k in ('Z', 'sf2', 'alpha', 'beta')])
 
     def rebuild_global_statistics(self, flat):
-        gs, start = {}, 0
-        for key, shape in self.options['global_statistics_names'].items():
-            size = shape[0] * shape[1]
-            gs[key] = numpy.asarray(flat[start:start + size], dtype=float).reshape(shape)
-            start += size
-        return gs
+        Z, sf2, alpha, beta = split_flat(flat, self.options['M'], self.options['Q'])
+        return {'Z': Z, 'sf2': sf2.reshape(1, 1), 'alpha': alpha.reshape(1, -1), 'beta': beta.reshape(1, 1)}
 
     # ---- parallel_GPLVM.py:373-404
     def clean(self):
@@ -249,32 +252,16 @@ class Driver(object):
         kept, frac = list(range(len(files))), None
         if o.get('drop_out_fraction', 0) > 0:
             kept, frac = mr._draw_drop_out(len(files), o['drop_out_fraction'])
-        mr._for_each(engines, lambda e: e.phase1())
-        root = engines[kept[0]]
-        for i in kept[1:]:
-            root.combine(engines[i], 'stats', 'add')            # statistics_reducer on the device(s)
-        if frac is not None:
-            root.scale_buffer('stats', 1.0 / frac)
-        for e in engines:
-            if e is not root:
-                e.combine(root, 'stats', 'copy')       # every shard needs the global sums (local_MapReduce.py:318-320)
-        t1 = time.time()
+        reduce = BufferReduce(engines, contributing=[engines[i] for i in kept], fraction=frac)
+        root = reduce.root
         want_emb = not o['fixed_embeddings']
-        jitter = 0
-        while True:
-            def second(e):
-                e.global_step(sync=False, jitter=jitter)   # replicated M x M algebra
-                e.phase2(want_emb)
-            mr._for_each(engines, second)
-            for i in kept[1:]:
-                root.combine(engines[i], 'grads', 'add')
-            if frac is not None:
-                root.scale_buffer('grads', 1.0 / frac)
-            try:
-                res = root.finish()
-                break
-            except JitterRetry as r:
-                jitter = r.mask
+        starts = []
+
+        def for_each(items, fn):                # one thread per shard
+            starts.append(time.time())
+            mr._for_each(items, fn)
+        res, self.last_jitter = evaluate(engines, reduce, want_emb, for_each)
+        t1 = starts[1]          # phase 1 and the statistics reduce end where the first pass of global step + phase 2 begins
         sc = root.scalars()
         # the artefacts other tools read (--load, predict.py): the five base sums and the partial derivatives
         it = str(o['i'])

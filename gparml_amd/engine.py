@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from .evaluation import evaluate
 
 
 class ShardEngine(object):
@@ -151,6 +152,10 @@ class ShardEngine(object):
     def combine(self, src, which='stats', op='add'):
         """dst (self) += src or dst = src for the packed statistics / gradient-sum buffers (same device)."""
         self._ck(self.lib.gp_buffer_combine(self.h, src.h, 0 if which == 'stats' else 1, 0 if op == 'add' else 1), 'gp_buffer_combine')
+        if which == 'stats' and op == 'copy':
+            # the reduced statistics come with what their owner learnt about their factorisation: only the engine that runs finish() sees a
+            # retry request, and an engine without the hint would run phase 2 on the failed plain step its hinted owner has just repeated
+            self._jitter_hint = src._jitter_hint
 
     # ---- resident CG vectors (scg_adapted_local_MapReduce.py:29-243) ----------------------------------
     CG_RESET_D, CG_UPDATE_D, CG_UPDATE_X, CG_GRAD_OLD, CG_GRAD_NEW, CG_SET_GRADS = range(6)
@@ -232,19 +237,7 @@ class ShardEngine(object):
 
     def evaluate(self, want_embedding_grads=False):
         """Single-shard evaluation (no reduction across shards); one host synchronisation, in finish()."""
-        self.phase1()
-        jitter = 0
-        while True:                             # the retry mask only grows (bit 0 Kmm, bit 1 Kmm + beta Psi2): at most two repeats
-            self.global_step(sync=False, jitter=jitter)
-            self.phase2(want_embedding_grads)
-            try:
-                out = self.finish()
-                break
-            except _lib.JitterRetry as r:
-                jitter = r.mask
-        # 0, or the mask of the matrices that needed the reference's 1e-7 jitter in this evaluation (found by finish(), or -- after an evaluation that needed
-        # it -- already inside global_step())
-        self.last_jitter = jitter | self._jitter_used
+        out, self.last_jitter = evaluate([self], None, want_embedding_grads)     # 0, or the matrices that needed the reference's 1e-7 jitter
         if want_embedding_grads:
             out['grad_X_mu'] = self.download('GRAD_X_MU')
             if not self.regime_A_hint:
@@ -361,8 +354,7 @@ class ShardEngine(object):
     def set_timing(self, level):
         """HIP timing events per evaluation: 2 = every stage and dominant kernel (default), 1 = first and last only (total_ms), 0 = none.
         Each event is ~4-7 us of idle stream; an optimiser on a small problem (BASELINE configs[1]) switches them off."""
-        if hasattr(self.lib, "gp_set_timing"):
-            self._ck(self.lib.gp_set_timing(self.h, int(level)), "gp_set_timing")
+        self._ck(self.lib.gp_set_timing(self.h, int(level)), "gp_set_timing")
 
     def timings(self):
         t = np.zeros(8)

@@ -7,35 +7,43 @@ resident vectors.  Across GPUs (one process per GPU) the local scalars are summe
 """
 import numpy as np
 
-from ._lib import JitterRetry
-from .driver import positive_mask, transform_grad_vec, transform_vec
+from .driver import positive_mask, split_flat, transform_grad_vec, transform_vec
 from .engine import ShardEngine
+from .evaluation import BufferReduce, evaluate, refresh_statistics
 
 
 class ResidentModel(object):
-    def __init__(self, shards, M, Q, D, fixed_embeddings=False, fixed_beta=False, device=0, dist_group=None, N_global=None):
-        """shards: list of (Y, X_mu, X_S) held by THIS process (X_S raw = softplus-inverse space unless fixed_embeddings)."""
+    def __init__(self, shards, M, Q, D, fixed_embeddings=False, fixed_beta=False, device=0, dist_group=None, N_global=None,
+                 engine_class=None):
+        """shards: list of (Y, X_mu, X_S) held by THIS process (X_S raw = softplus-inverse space unless fixed_embeddings).  ``engine_class``
+        (tests only) replaces ShardEngine."""
         self.M, self.Q, self.D = M, Q, D
         self.fixed_embeddings, self.fixed_beta = fixed_embeddings, fixed_beta
         self.engines = []
         for (Y, X_mu, X_S) in shards:
-            e = ShardEngine(Y.shape[0], D, M, Q, device=device)
+            e = (engine_class or ShardEngine)(Y.shape[0], D, M, Q, device=device)
             e.set_timing(0)            # an optimiser does not read per-kernel device timings: no timing events on the stream
             e.upload_shard(Y, X_mu, X_S, xs_is_raw=not fixed_embeddings)
             self.engines.append(e)
         self.group = dist_group
         self._dist = None
         self.version = 0            # bumped whenever the resident vectors may have changed (ResidentCG caches its reductions on it)
-        self.n_collectives = 0      # all-reduces issued so far (tests assert the per-iteration count)
+        self.last_jitter = 0        # the jitter mask the last evaluation ended with (0: none)
+        self._n_small = 0           # collectives of _allreduce_vector so far
         if dist_group is not None or self._dist_ready():
             import torch.distributed as dist
             self._dist = dist
+        # the two packed buffers of an evaluation: the shards of this process add into engines[0], the processes all-reduce
+        self._reduce = BufferReduce(self.engines, dist=self._dist, group=self.group)
         n_local = sum(e.N_s for e in self.engines)
         self.N = int(N_global) if N_global is not None else int(self._allreduce_scalar(float(n_local)))
         self.bounds = [(None, None)] * (M * Q) + [(0, None)] + [(0, None)] * Q + [(0, None)]
         self._pos = positive_mask(self.bounds)
-        self._dev_tensors = None
-        self._native = None         # True once the root engine reduces through its own RCCL communicator (gp_allreduce)
+
+    @property
+    def n_collectives(self):
+        """All-reduces issued so far, buffers and small vectors (tests assert the per-iteration count)."""
+        return self._n_small + self._reduce.n_collectives
 
     @staticmethod
     def _dist_ready():
@@ -61,33 +69,8 @@ class ResidentModel(object):
         t = torch.tensor(values, dtype=torch.float64,
                          device=torch.device('cuda', self.engines[0].device) if self._dist.get_backend() == 'nccl' else 'cpu')
         self._dist.all_reduce(t, op=self._dist.ReduceOp.SUM if op == 'sum' else self._dist.ReduceOp.MAX, group=self.group)
-        self.n_collectives += 1
+        self._n_small += 1
         return t.cpu().numpy()
-
-    def _allreduce_buffers(self, which):
-        if self._dist is None:
-            return
-        from .dist import device_tensor, init_native_comm
-        import torch
-        root = self.engines[0]
-        if self._native is None:
-            self._native = init_native_comm(root, self._dist, self.group)
-        if self._native:
-            root.allreduce(which)             # gp_allreduce: RCCL on the engine's stream (statistics packed inside)
-            self.n_collectives += 1
-            return
-        if self._dev_tensors is None:         # zero-copy views of the two device buffers, made once (the pointers never change)
-            p, n = root.stats_packed_buffer()
-            g, m = root.grads_buffer()
-            dev = torch.device('cuda', root.device)
-            self._dev_tensors = {'stats': device_tensor(p, n, dev), 'grads': device_tensor(g, m, dev)}
-        if which == 'stats':
-            # across processes the statistics travel without padding and without Psi2's lower triangle (gp_stats_pack / gp_stats_unpack)
-            root.stats_pack()
-        self._dist.all_reduce(self._dev_tensors[which], op=self._dist.ReduceOp.SUM, group=self.group)
-        if which == 'stats':
-            root.stats_unpack()
-        self.n_collectives += 1
 
     _stats_x = None
     _stats_version = -1
@@ -112,18 +95,10 @@ class ResidentModel(object):
         last = self._stats_x
         if (last is None or last.shape != flat_array.shape or last.tobytes() != flat_array.tobytes()
                 or self._stats_version != self.version):
-            M, Q = self.M, self.Q
-            xt = transform_vec(self._pos, flat_array)
-            Z = xt[:M * Q].reshape(M, Q)
-            sf2, alpha, beta = xt[M * Q], xt[M * Q + 1:M * Q + 1 + Q], xt[M * Q + 1 + Q]
+            Z, sf2, alpha, beta = split_flat(transform_vec(self._pos, flat_array), self.M, self.Q)
             for e in self.engines:
                 e.set_globals(Z, sf2, alpha, beta, N_global=self.N, step_size=0.0)
-                e.phase1()
-            root = self.engines[0]
-            for e in self.engines[1:]:
-                root.combine(e, 'stats', 'add')
-            self._allreduce_buffers('stats')
-            root.global_step(sync=True)
+            refresh_statistics(self.engines, self._reduce)
             self._stats_x = np.array(flat_array, copy=True)
             self._stats_version = self.version
 
@@ -144,33 +119,10 @@ class ResidentModel(object):
 
     # ---- parallel_GPLVM.likelihood_and_gradient (:222-279) on resident shards
     def likelihood_and_gradient(self, flat_array, iteration, step_size=0):
-        M, Q = self.M, self.Q
-        xt = transform_vec(self._pos, flat_array)
-        Z = xt[:M * Q].reshape(M, Q)
-        sf2, alpha, beta = xt[M * Q], xt[M * Q + 1:M * Q + 1 + Q], xt[M * Q + 1 + Q]
-        want_emb = not self.fixed_embeddings
+        Z, sf2, alpha, beta = split_flat(transform_vec(self._pos, flat_array), self.M, self.Q)
         for e in self.engines:
             e.set_globals(Z, sf2, alpha, beta, N_global=self.N, step_size=step_size)
-            e.phase1()
-        root = self.engines[0]
-        for e in self.engines[1:]:
-            root.combine(e, 'stats', 'add')
-        self._allreduce_buffers('stats')
-        for e in self.engines[1:]:
-            e.combine(root, 'stats', 'copy')
-        jitter = 0
-        while True:
-            for e in self.engines:
-                e.global_step(sync=False, jitter=jitter)
-                e.phase2(want_emb)
-            for e in self.engines[1:]:
-                root.combine(e, 'grads', 'add')
-            self._allreduce_buffers('grads')
-            try:
-                res = root.finish()         # the evaluation's only host synchronisation
-                break
-            except JitterRetry as r:        # same reduced statistics on every rank: all ranks retry together (partial_terms.py:452-456)
-                jitter = r.mask
+        res, self.last_jitter = evaluate(self.engines, self._reduce, not self.fixed_embeddings)
         self.version += 1                   # grad_latest changed
         # the vector whose statistics the root engine holds, and the resident vectors' version they were computed with (an optimiser's
         # update of the embeddings -- scg_adapted / gd after an accepted step -- bumps the version: the statistics are then recomputed)
@@ -181,13 +133,22 @@ class ResidentModel(object):
         return -res['F'], -grad
 
 
-class ResidentCG(object):
-    """The helper functions of scg_adapted_local_MapReduce.py on the resident vectors (the ``folder`` argument of the
-    reference's file-based helpers is accepted and ignored)."""
+class _ResidentVectors(object):
+    """What ResidentCG and ResidentGD share: the model, a cache of reductions keyed on its version, the update of every shard's vectors."""
 
     def __init__(self, model):
         self.m = model
-        self._cache = None      # (model.version, the six reductions)
+        self._cache = None      # (model.version, the reductions)
+
+    def _upd(self, which, a=0.0):
+        for e in self.m.engines:
+            e.cg_update(which, a)
+        self.m.version += 1
+
+
+class ResidentCG(_ResidentVectors):
+    """The helper functions of scg_adapted_local_MapReduce.py on the resident vectors (the ``folder`` argument of the
+    reference's file-based helpers is accepted and ignored).  The cache holds the six reductions."""
 
     def _dots(self):
         """[mu, kappa, theta, |g_new|^2, g_new.g_old, max|d|] over all shards of all ranks: one pass over the resident vectors and
@@ -205,11 +166,6 @@ class ResidentCG(object):
             tot[5] = self.m._allreduce_vector(tot[5:6], 'max')[0]
         self._cache = (self.m.version, tot)
         return tot
-
-    def _upd(self, which, a=0.0):
-        for e in self.m.engines:
-            e.cg_update(which, a)
-        self.m.version += 1
 
     def embeddings_set_grads(self, folder=None):
         self._upd(ShardEngine.CG_SET_GRADS)
@@ -248,18 +204,10 @@ class ResidentCG(object):
         self._upd(ShardEngine.CG_GRAD_NEW)
 
 
-class ResidentGD(object):
+class ResidentGD(_ResidentVectors):
     """The helper functions of gd_local_MapReduce.py:14-105 (the gradient-descent optimiser's vector algebra) on the
-    resident vectors; ``grad_now`` is the library's grad_new array.  ``folder`` is accepted and ignored."""
-
-    def __init__(self, model):
-        self.m = model
-        self._cache = None      # (model.version, (sum |grad_now|, max |grad_now|))
-
-    def _upd(self, which, a=0.0):
-        for e in self.m.engines:
-            e.cg_update(which, a)
-        self.m.version += 1
+    resident vectors; ``grad_now`` is the library's grad_new array.  ``folder`` is accepted and ignored.  The cache holds
+    (sum |grad_now|, max |grad_now|)."""
 
     def _abs(self):
         if self._cache is not None and self._cache[0] == self.m.version:
@@ -274,7 +222,6 @@ class ResidentGD(object):
             mx = self.m._allreduce_scalar(mx, 'max')
         self._cache = (self.m.version, (s, mx))
         return s, mx
-
 
     def embeddings_set_grads(self, folder=None):                       # :14-32  grad_now = latest, d = -latest
         self._upd(ShardEngine.CG_SET_GRADS)

@@ -156,20 +156,26 @@ def test_jitter_that_does_not_help_is_a_linalg_error():
 
 @pytest.mark.jitter_expected
 def test_evaluate_recovers_through_the_retry():
-    """ShardEngine.evaluate / DistributedEvaluator.evaluate repeat global step + phase 2 when finish() asks for the jitter."""
+    """ShardEngine.evaluate / DistributedEvaluator.evaluate / ResidentModel.likelihood_and_gradient (one shard, and the shard split in two ragged
+    parts) repeat global step + phase 2 when finish() asks for the jitter."""
     from gparml_amd.dist import DistributedEvaluator
+    from gparml_amd.driver import positive_mask, split_flat, transform_back, transform_grad_vec, transform_vec
     from gparml_amd.engine import ShardEngine
+    from gparml_amd.resident import ResidentModel
     d, (N, D, M, Q) = _setup(seed=4)
     st, _ = _indefinite_stats(d, 5e-8)
 
     class Fixed(ShardEngine):
         bad = True
         phase2_calls = 0
+        stats = st
+        share = 1.0                                # of the hand-made statistics this engine contributes (the shards of a model add up to 1)
 
         def phase1(self):                          # keep the hand-made statistics instead of the shard's own
             ShardEngine.phase1(self)
             if self.bad:
-                self.set_local_statistics(st['sum_YYT'], st['Psi2'], st['C'], st['Psi0'], st['KL'])
+                s, w = self.stats, self.share
+                self.set_local_statistics(w * s['sum_YYT'], w * s['Psi2'], w * s['C'], w * s['Psi0'], w * s['KL'])
 
         def phase2(self, want=False):
             self.phase2_calls += 1
@@ -191,6 +197,32 @@ def test_evaluate_recovers_through_the_retry():
     c2 = eng.evaluate(False)
     assert eng.phase2_calls == 5 and c1['F'] == c2['F'] and np.array_equal(c1['grad_Z'], c2['grad_Z'])
     eng.close()
+
+    # third and fourth leg: ResidentModel.  It takes the optimiser's vector x, so the hyper-parameters are the softplus of x's entries -- equal to
+    # d's up to rounding -- and the indefinite statistics and the ShardEngine.evaluate to compare with are made for exactly those values.
+    bounds = [(None, None)] * (M * Q) + [(0, None)] * (Q + 2)
+    x = np.concatenate([d['Z'].ravel(), [transform_back((0, None), v) for v in [d['sf2']] + list(np.ravel(d['alpha'])) + [d['beta']]]])
+    Z, sf2, alpha, beta = split_flat(transform_vec(positive_mask(bounds), x), M, Q)
+    Fixed.stats, _ = _indefinite_stats(dict(d, Z=Z, sf2=sf2, alpha=alpha, beta=beta), 5e-8)
+    eng = Fixed(N, D, M, Q)
+    eng.upload_shard(d['Y'], d['X_mu'], d['X_S'])
+    eng.set_globals(Z, sf2, alpha, beta)
+    ref = eng.evaluate(False)
+    assert eng.last_jitter != 0 and np.all(np.isfinite(ref['grad_Z']))
+    eng.close()
+    chain = transform_grad_vec(positive_mask(bounds), x)
+    for cuts in ([0, N], [0, 113, N]):
+        Fixed.share = 1.0 / (len(cuts) - 1)                           # 1 or 1/2: the shares add up to the statistics exactly
+        model = ResidentModel([(d['Y'][i:j], d['X_mu'][i:j], d['X_S'][i:j]) for i, j in zip(cuts[:-1], cuts[1:])], M, Q, D, fixed_embeddings=True,
+                              engine_class=Fixed)
+        f1, g1 = model.likelihood_and_gradient(x, 0)
+        assert [e.phase2_calls for e in model.engines] == [2] * len(model.engines) and model.last_jitter != 0, (cuts, model.last_jitter)
+        f2, g2 = model.likelihood_and_gradient(x, 1)
+        assert [e.phase2_calls for e in model.engines] == [3] * len(model.engines) and model.last_jitter != 0, (cuts, model.last_jitter)
+        assert np.isfinite(f1) and np.all(np.isfinite(g1)) and f1 == f2 and np.array_equal(g1, g2), cuts
+        if len(cuts) == 2:      # the model returns (-F, -grad * softplus chain factor): undone, the one-shard model is ShardEngine.evaluate bit for bit
+            assert -f1 == ref['F'] and np.array_equal((-g1 / chain)[:M * Q].reshape(M, Q), ref['grad_Z'])
+        model.close()
 
 
 @pytest.mark.parametrize('regime,emb', [('A', False), ('B', True)])
