@@ -20,7 +20,7 @@ int fail(gp_ctx* ctx, int code, const char* fmt, ...) {
 
 hipStream_t ctx_stream(const gp_ctx* c) { return c ? c->stream : nullptr; }
 
-std::atomic<int> g_opt_poison{[] { const char* e = getenv("GPARML_POISON"); return (e && e[0] == '1') ? 1 : 0; }()};
+std::atomic<int> g_opt_poison{env_flag("GPARML_POISON", false)};
 std::atomic<int> g_alloc_fail_after{0};
 #define GP_TRY(x) do { int rc__ = (x); if (rc__ != GP_OK) return rc__; } while (0)
 
@@ -81,7 +81,7 @@ static int download_matrix(gp_ctx* c, const double* src, long ld, long rows, lon
   if (n != rows * cols) return fail(c, GP_ERR_BAD_ARG, "gp_download: expected %ld doubles, got %ld", rows * cols, (long)n);
   DevBuf<double> tmp;
   GP_TRY(tmp.alloc(c, rows * cols, DA_RAW));
-  hipLaunchKernelGGL(gather2d_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, c->stream, src, ld, rows, cols, tmp);
+  GP_LAUNCH(c, c->stream, gather2d_kernel, dim3(blocks_for(rows * cols)), dim3(256), 0, src, ld, rows, cols, tmp);
   hipError_t e = hipMemcpyAsync(dst, tmp, rows * cols * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
@@ -245,7 +245,7 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
     // sum_YYT (partial_terms.py:40) once per upload
     const int nb = 1024;
     double* part = c->red;
-    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, c->stream, dY, (long)nd, part);
+    GP_LAUNCH(c, c->stream, sumsq_kernel, dim3(nb), dim3(256), 0, dY, (long)nd, part);
     std::vector<double> h(nb);
     e = hipMemcpyAsync(h.data(), part, nb * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -328,9 +328,8 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
   std::memcpy(c->glob.h_glob[slot] + nz, alpha, nq * sizeof(double));
   double* dslot = nullptr;
   GP_HIP(c, hipHostGetDevicePointer((void**)&dslot, c->glob.h_glob[slot], 0));
-  hipLaunchKernelGGL(zaug_kernel, dim3((int)std::min<long>(((long)c->Mp * c->CZp + 255) / 256, 1024)), dim3(256), 0, c->stream, dslot, dslot + nz, c->M, c->Mp, c->Q, c->CZp, c->Z,
-                     c->Zaug, c->alpha, c->Zt);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, zaug_kernel, dim3((int)std::min<long>(((long)c->Mp * c->CZp + 255) / 256, 1024)), dim3(256), 0, dslot, dslot + nz, c->M, c->Mp, c->Q, c->CZp, c->Z,
+            c->Zaug, c->alpha, c->Zt);
   c->glob.glob_epoch[slot] = c->sync_epoch;                      // the slot may be rewritten once a later stream synchronisation has passed
   c->glob.glob_slot = slot ^ 1;
   c->sf2 = sf2; c->beta = beta; c->N_global = N_global; c->step = step;
@@ -419,12 +418,11 @@ static int stats_pack(gp_ctx* c, int unpack_) {
     c->gstep.pred_ok = false;
     // the packed buffer only holds statistics after a pack (it is zero from its allocation): unpacking first would silently wipe phase 1's sums
     if (!c->spack_filled) return fail(c, GP_ERR_STATE, "gp_stats_unpack before gp_stats_pack");
-    hipLaunchKernelGGL(stats_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->spack, c->stats, c->M, c->Mp, c->D, c->Dp);
+    GP_LAUNCH(c, c->stream, stats_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, (const double*)c->spack, c->stats, c->M, c->Mp, c->D, c->Dp);
   } else {
-    hipLaunchKernelGGL(stats_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, (const double*)c->stats, c->spack, c->M, c->Mp, c->D, c->Dp);
+    GP_LAUNCH(c, c->stream, stats_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, (const double*)c->stats, c->spack, c->M, c->Mp, c->D, c->Dp);
     c->spack_filled = true;
   }
-  GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 extern "C" int gp_stats_pack(gp_ctx* c) { return stats_pack(c, 0); }
@@ -476,9 +474,8 @@ extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int 
     GP_HIP(dst, hipMemcpyPeerAsync(dst->staging, dst->device, from, src->device, (size_t)n * 8, dst->stream));
     from = dst->staging;
   }
-  hipLaunchKernelGGL(combine_kernel, dim3(blocks_for(n)), dim3(256), 0, dst->stream, which == 0 ? dst->stats : dst->grads, from, n, op);
+  GP_LAUNCH(dst, dst->stream, combine_kernel, dim3(blocks_for(n)), dim3(256), 0, which == 0 ? dst->stats : dst->grads, from, n, op);
   if (which == 0) dst->gstep.pred_ok = false;
-  GP_HIP(dst, hipGetLastError());
   if (which == 0 && dst->state < 1) dst->state = 1;
   return GP_OK;
 }
@@ -497,8 +494,7 @@ extern "C" int gp_scale_buffer(gp_ctx* c, int which, double f) {
     GP_HIP(c, hipMemsetAsync(which == 0 ? c->stats : c->grads, 0, (size_t)n * sizeof(double), c->stream));
     return GP_OK;
   }
-  hipLaunchKernelGGL(scale_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, which == 0 ? c->stats : c->grads, n, f);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, scale_kernel, dim3(blocks_for(n)), dim3(256), 0, which == 0 ? c->stats : c->grads, n, f);
   return GP_OK;
 }
 
@@ -558,9 +554,8 @@ extern "C" int gp_phase2(gp_ctx* c, int want_embedding_grads) {
   if (c->want_emb && c->xs_raw) {
     // the .grad_latest vector of this evaluation, resident for the optimiser's dot products
     const long nq = (long)c->N * c->Q;
-    hipLaunchKernelGGL(grad_latest_kernel, dim3(blocks_for(nq)), dim3(256), 0, c->stream, c->gXmu, c->gXs, c->Xs, c->dir, (long)c->N, c->Q, c->step,
-                       1, c->have_dir ? 1 : 0, c->cg.g_latest);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, grad_latest_kernel, dim3(blocks_for(nq)), dim3(256), 0, c->gXmu, c->gXs, c->Xs, c->dir, (long)c->N, c->Q, c->step,
+              1, c->have_dir ? 1 : 0, c->cg.g_latest);
     c->cg.have_glatest = true;
   }
   GP_EV(c, 6);
@@ -624,8 +619,8 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
       if (c->regime_A) return fail(c, GP_ERR_NON_FINITE, "grad_X_S with X_S == 0 (1/S, partial_terms.py:417)");
       DevBuf<double> tmp;
       GP_TRY(tmp.alloc(c, 2 * N * Q, DA_RAW));
-      hipLaunchKernelGGL(grad_latest_kernel, dim3(blocks_for(N * Q)), dim3(256), 0, c->stream, c->gXmu, c->gXs, c->Xs, c->dir, N, (int)Q, c->step,
-                         c->xs_raw ? 1 : 0, c->have_dir ? 1 : 0, tmp);
+      GP_LAUNCH(c, c->stream, grad_latest_kernel, dim3(blocks_for(N * Q)), dim3(256), 0, c->gXmu, c->gXs, c->Xs, c->dir, N, (int)Q, c->step,
+                c->xs_raw ? 1 : 0, c->have_dir ? 1 : 0, tmp);
       hipError_t e = hipMemcpyAsync(dst, tmp, 2 * N * Q * 8, hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
       if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
@@ -662,10 +657,10 @@ extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* 
   const long M = c->M, Mp = c->Mp, D = c->D, Dp = c->Dp;
   double* tmp = c->gstep.T2;
   GP_HIP(c, hipMemcpyAsync(tmp, Psi2, M * M * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(scatter2d_kernel, dim3(blocks_for(Mp * Mp)), dim3(256), 0, c->stream, tmp, M, M, c->stats, Mp, Mp, Mp);
+  GP_LAUNCH(c, c->stream, scatter2d_kernel, dim3(blocks_for(Mp * Mp)), dim3(256), 0, tmp, M, M, c->stats, Mp, Mp, Mp);
   GP_HIP(c, hipStreamSynchronize(c->stream));
   GP_HIP(c, hipMemcpyAsync(tmp, C, M * D * 8, hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(scatter2d_kernel, dim3(blocks_for(Mp * Dp)), dim3(256), 0, c->stream, tmp, M, D, c->stats + Mp * Mp, Dp, Mp, Dp);
+  GP_LAUNCH(c, c->stream, scatter2d_kernel, dim3(blocks_for(Mp * Dp)), dim3(256), 0, tmp, M, D, c->stats + Mp * Mp, Dp, Mp, Dp);
   double sc[SC_COUNT] = {0};
   sc[SC_SUM_YYT] = sum_YYT; sc[SC_PSI0] = sum_exp_K_ii; sc[SC_KL] = KL; sc[SC_NLOCAL] = sum_exp_K_ii / c->sf2;
   GP_HIP(c, hipMemcpyAsync(c->stats + Mp * Mp + Mp * Dp, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
@@ -805,8 +800,7 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
     if (!c->h_out) GP_TRY(c->h_out.alloc(c, ngs + n));
     double* dout = nullptr;
     GP_HIP(c, hipHostGetDevicePointer((void**)&dout, c->h_out, 0));
-    hipLaunchKernelGGL(finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->stream, c->gstep.gs, ngs, c->gstep.gK, c->grads, n, dout);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->gstep.gs, ngs, c->gstep.gK, c->grads, n, dout);
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
     GP_TRY(check_global_from(c, c->gstep.gs_pending ? c->h_out : nullptr));
@@ -870,9 +864,8 @@ extern "C" int gp_cg_update(gp_ctx* c, int which, double a) {
   if ((which == 4 || which == 5) && !c->cg.have_glatest) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
   GP_HIP(c, hipSetDevice(c->device));
   const long nq = (long)c->N * c->Q;
-  hipLaunchKernelGGL(cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, c->stream, which, a, nq, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest,
-                     c->Xmu, c->Xs);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, which, a, nq, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest,
+            c->Xmu, c->Xs);
   if (which == 0 || which == 1 || which == 5) c->have_dir = true;
   if (which == 2) { c->state = 0; c->prep_fixa_valid = false; c->gstep.pred_ok = false; }   // the embeddings moved: statistics are stale
   return GP_OK;
@@ -884,7 +877,7 @@ static int cg_reduce(gp_ctx* c, double* out6) {
   const long n2 = 2L * c->N * c->Q;
   const int nb = std::min(blocks_for(n2), 1024);
   double* part = c->red;
-  hipLaunchKernelGGL(cg_dots_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest, part);
+  GP_LAUNCH(c, c->stream, cg_dots_kernel, dim3(nb), dim3(256), 0, n2, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest, part);
   std::vector<double> h((size_t)nb * 6);
   GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
@@ -926,7 +919,7 @@ extern "C" int gp_cg_abs(gp_ctx* c, double* out2) {
   const long n2 = 2L * c->N * c->Q;
   const int nb = std::min(blocks_for(n2), 1024);
   double* part = c->red;
-  hipLaunchKernelGGL(cg_abs_kernel, dim3(nb), dim3(256), 0, c->stream, n2, c->cg.g_new, part);
+  GP_LAUNCH(c, c->stream, cg_abs_kernel, dim3(nb), dim3(256), 0, n2, c->cg.g_new, part);
   std::vector<double> h((size_t)nb * 2);
   GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
@@ -943,4 +936,23 @@ extern "C" int gp_cg_max_d(gp_ctx* c, double alpha, double* out) {
   GP_TRY(cg_reduce(c, o));
   *out = std::fabs(alpha) * o[5];
   return GP_OK;
+}
+
+// ---- run-time switches (test hooks, same-box A/B) ----------------------------------------------------------------------------
+// Every option by name; each atomic is defined next to the code it switches (gp_common.h declares them).  A flag stores value != 0, a count max(0, value).
+extern "C" int gp_debug_set_option(const char* name, int value) {
+  using namespace gp;
+  static const struct { const char* name; std::atomic<int>* opt; bool is_flag; } options[] = {
+      {"dd_kipsi2", &g_opt_dd_kipsi2, true},     {"refine_E", &g_opt_refine_E, true},       {"p1_i8", &g_opt_p1_i8, true},
+      {"gs_tail", &g_opt_gs_tail, true},         {"i8_guard_strict", &g_opt_i8_guard_strict, true}, {"xtx_tri", &g_opt_xtx_tri, true},
+      {"residual_dd", &g_opt_residual_dd, true}, {"gemm_big", &g_opt_gemm_big, true},       {"trtri_rec", &g_opt_trtri_rec, true},
+      {"gs_i8", &g_opt_gs_i8, true},             {"poison_alloc", &g_opt_poison, true},     {"predict_rows", &g_opt_pred_rows, false},
+      {"infer_rows", &g_opt_inf_rows, false},    {"kmeans_rows", &g_opt_km_rows, false},    {"alloc_fail_after", &g_alloc_fail_after, false}};
+  if (!name) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: NULL name");
+  std::string known;
+  for (const auto& o : options) {
+    if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }
+    known += (known.empty() ? "" : ", ") + std::string(o.name);
+  }
+  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (%s)", name, known.c_str());
 }

@@ -144,27 +144,25 @@ int compat_build(gp_ctx* c, int which, DevBuf<double>& out) {
     const double *LE = nullptr, *Vn = nullptr, *DZ2 = nullptr;
     bool le_il = false;
     if (!c->regime_A) GP_TRY_RC(b_point_tables(c, &LE, &le_il, &Vn, &DZ2));
-    hipLaunchKernelGGL(psi2_points_kernel, dim3(grid_for(N * M * M)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, LE, c->Mp, le_il, Vn, DZ2,
-                       N, (int)M, (int)Q, c->regime_A ? 1 : 0, p2);
+    GP_LAUNCH(c, c->stream, psi2_points_kernel, dim3(grid_for(N * M * M)), dim3(256), 0, c->Kaug, (long)c->LDK, LE, c->Mp, le_il, Vn, DZ2,
+              N, (int)M, (int)Q, c->regime_A ? 1 : 0, p2);
   }
   switch (which) {
     case GP_ARR_PSI2_POINTS: break;
     case GP_ARR_DKMM_DZ: case GP_ARR_DKMM_DALPHA:
-      hipLaunchKernelGGL(dkmm_kernel, dim3(grid_for(n)), dim3(256), 0, c->stream, c->gstep.KmmKeep, c->Mp, c->Z, c->alpha, (int)M, (int)Q,
-                         which == GP_ARR_DKMM_DZ ? 0 : 1, buf);
+      GP_LAUNCH(c, c->stream, dkmm_kernel, dim3(grid_for(n)), dim3(256), 0, c->gstep.KmmKeep, c->Mp, c->Z, c->alpha, (int)M, (int)Q,
+                which == GP_ARR_DKMM_DZ ? 0 : 1, buf);
       break;
     case GP_ARR_DPSI1TY_DZ: case GP_ARR_DPSI1TY_DALPHA:
-      hipLaunchKernelGGL(dpsi1y_kernel, dim3(grid_for(n)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, c->Mp, c->mu, c->S, c->Z, c->alpha, N,
-                         (int)M, (int)Q, (int)D, which == GP_ARR_DPSI1TY_DZ ? 0 : 1, buf);
+      GP_LAUNCH(c, c->stream, dpsi1y_kernel, dim3(grid_for(n)), dim3(256), 0, c->Kaug, (long)c->LDK, c->Mp, c->mu, c->S, c->Z, c->alpha, N,
+                (int)M, (int)Q, (int)D, which == GP_ARR_DPSI1TY_DZ ? 0 : 1, buf);
       break;
     case GP_ARR_DPSI2_DZ: case GP_ARR_DPSI2_DALPHA:
-      hipLaunchKernelGGL(dpsi2_kernel, dim3(grid_for(n)), dim3(256), 0, c->stream, p2, c->mu, c->S, c->Z, c->alpha, N, (int)M, (int)Q,
-                         which == GP_ARR_DPSI2_DZ ? 0 : 1, buf);
+      GP_LAUNCH(c, c->stream, dpsi2_kernel, dim3(grid_for(n)), dim3(256), 0, p2, c->mu, c->S, c->Z, c->alpha, N, (int)M, (int)Q,
+                which == GP_ARR_DPSI2_DZ ? 0 : 1, buf);
       break;
   }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) return fail(c, GP_ERR_HIP, "compat kernel failed: %s", hipGetErrorString(e));
+  GP_HIP(c, hipStreamSynchronize(c->stream));
   out = std::move(buf);
   return GP_OK;
 }
@@ -194,8 +192,8 @@ extern "C" int gp_grad_from_parts(gp_ctx* c, int which, const double* dF_dKmm, c
   GP_TRY_RC(up(c, dPsi2_dX, M * Q * M, c3));
   const long no = which == 0 ? M * Q : Q;
   GP_TRY_RC(o.alloc(c, no, DA_RAW));
-  if (which == 0) hipLaunchKernelGGL(gradz_parts_kernel, dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
-  else hipLaunchKernelGGL(gradalpha_parts_kernel, dim3((unsigned)Q), dim3(256), 0, c->stream, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
+  if (which == 0) GP_LAUNCH(c, c->stream, gradz_parts_kernel, dim3((unsigned)((M * Q + 255) / 256)), dim3(256), 0, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
+  else GP_LAUNCH(c, c->stream, gradalpha_parts_kernel, dim3((unsigned)Q), dim3(256), 0, A, a3, B, b3, C, c3, (int)M, (int)Q, (int)D, o);
   hipError_t e = hipMemcpyAsync(out, o, no * 8, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e != hipSuccess) return fail(c, GP_ERR_HIP, "gp_grad_from_parts: %s", hipGetErrorString(e));

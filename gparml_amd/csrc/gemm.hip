@@ -147,35 +147,38 @@ static bool operand_meets_c(const double* X, long rows, long cols, long ld, cons
   return windows_meet((long)(reinterpret_cast<uintptr_t>(X) / sizeof(double)), rows, cols, ld, (long)(reinterpret_cast<uintptr_t>(C) / sizeof(double)), m, n, ldc);
 }
 
-void launch_gemm(hipStream_t st, Layout la, Layout lb, int m, int n, int batch, const GemmP& p) {
-  // No product here may write a tile another workgroup still reads: C must not share an element with A or B (the in-place panel solve of the blocked
-  // Cholesky did until r06 -- a race visible only on a cold start, profiles/r06_first_evaluation_race.txt).  A programming error, never a user's: abort.
+// What launch_gemm refuses, as a reason, or NULL for an acceptable call.  Both are programming errors, never a user's.
+//  - No product may write a tile another workgroup still reads: C must not share an element with A or B (the in-place panel solve of the blocked
+//    Cholesky did until r06 -- a race visible only on a cold start, profiles/r06_first_evaluation_race.txt).  Only batch entry 0 is looked at;
+//    gp_debug_gemm_modes checks every pair of entries itself.
+//  - mirror is defined for beta == 0 only (GemmP): with a beta the three kernels would each do something else.
+static const char* gemm_refusal(Layout la, Layout lb, int m, int n, const GemmP& p) {
   if (operand_meets_c(p.A, la == K_CONTIG ? m : p.K, la == K_CONTIG ? p.K : m, p.lda, p.C, m, n, p.ldc) ||
-      operand_meets_c(p.B, lb == K_CONTIG ? n : p.K, lb == K_CONTIG ? p.K : n, p.ldb, p.C, m, n, p.ldc)) {
-    fprintf(stderr, "gparml: launch_gemm called with C overlapping an operand (m %d n %d k %d)\n", m, n, p.K);
-    abort();
-  }
-  // mirror is defined for beta == 0 only (GemmP): with a beta the three kernels would each do something else
-  if (p.mirror && p.beta != 0.0) {
-    fprintf(stderr, "gparml: launch_gemm called with mirror and beta != 0 (m %d n %d k %d)\n", m, n, p.K);
-    abort();
-  }
+      operand_meets_c(p.B, lb == K_CONTIG ? n : p.K, lb == K_CONTIG ? p.K : n, p.ldb, p.C, m, n, p.ldc))
+    return "C overlaps an operand";
+  if (p.mirror && p.beta != 0.0) return "mirror with beta != 0";
+  return nullptr;
+}
+
+int launch_gemm(gp_ctx* c, hipStream_t st, Layout la, Layout lb, int m, int n, int batch, const GemmP& p) {
+  if (const char* why = gemm_refusal(la, lb, m, n, p)) return fail(c, GP_ERR_STATE, "launch_gemm: %s (m %d n %d k %d)", why, m, n, p.K);
   dim3 grid(n / TILE, m / TILE, batch * p.splits), block(256);
   if (!p.big && (long)(n / TILE) * (m / TILE) * batch <= 256) {
     // few tiles (the global step): 32 x 32 tiles spread the product over the chip; split-k is not needed there
     dim3 g32(n / ST, m / ST, batch);
-    if (la == K_CONTIG && lb == FREE_CONTIG) hipLaunchKernelGGL((gemm32_kernel<K_CONTIG, FREE_CONTIG>), g32, block, 0, st, p);
-    else if (la == K_CONTIG && lb == K_CONTIG) hipLaunchKernelGGL((gemm32_kernel<K_CONTIG, K_CONTIG>), g32, block, 0, st, p);
-    else if (la == FREE_CONTIG && lb == FREE_CONTIG) hipLaunchKernelGGL((gemm32_kernel<FREE_CONTIG, FREE_CONTIG>), g32, block, 0, st, p);
-    else hipLaunchKernelGGL((gemm32_kernel<FREE_CONTIG, K_CONTIG>), g32, block, 0, st, p);
-    return;
+    if (la == K_CONTIG && lb == FREE_CONTIG) GP_LAUNCH(c, st, (gemm32_kernel<K_CONTIG, FREE_CONTIG>), g32, block, 0, p);
+    else if (la == K_CONTIG && lb == K_CONTIG) GP_LAUNCH(c, st, (gemm32_kernel<K_CONTIG, K_CONTIG>), g32, block, 0, p);
+    else if (la == FREE_CONTIG && lb == FREE_CONTIG) GP_LAUNCH(c, st, (gemm32_kernel<FREE_CONTIG, FREE_CONTIG>), g32, block, 0, p);
+    else GP_LAUNCH(c, st, (gemm32_kernel<FREE_CONTIG, K_CONTIG>), g32, block, 0, p);
+    return GP_OK;
   }
-  if (la == K_CONTIG && lb == FREE_CONTIG) hipLaunchKernelGGL((gemm128_kernel<K_CONTIG, FREE_CONTIG>), grid, block, 0, st, p);
-  else if (la == K_CONTIG && lb == K_CONTIG) hipLaunchKernelGGL((gemm128_kernel<K_CONTIG, K_CONTIG>), grid, block, 0, st, p);
-  else if (la == FREE_CONTIG && lb == FREE_CONTIG) hipLaunchKernelGGL((gemm128_kernel<FREE_CONTIG, FREE_CONTIG>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((gemm128_kernel<FREE_CONTIG, K_CONTIG>), grid, block, 0, st, p);
+  if (la == K_CONTIG && lb == FREE_CONTIG) GP_LAUNCH(c, st, (gemm128_kernel<K_CONTIG, FREE_CONTIG>), grid, block, 0, p);
+  else if (la == K_CONTIG && lb == K_CONTIG) GP_LAUNCH(c, st, (gemm128_kernel<K_CONTIG, K_CONTIG>), grid, block, 0, p);
+  else if (la == FREE_CONTIG && lb == FREE_CONTIG) GP_LAUNCH(c, st, (gemm128_kernel<FREE_CONTIG, FREE_CONTIG>), grid, block, 0, p);
+  else GP_LAUNCH(c, st, (gemm128_kernel<FREE_CONTIG, K_CONTIG>), grid, block, 0, p);
   if (p.splits > 1)
-    hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((n / TILE) * (m / TILE) * 16, batch), block, 0, st, p, n / TILE, m / TILE);
+    GP_LAUNCH(c, st, gemm_splitk_reduce_kernel, dim3((n / TILE) * (m / TILE) * 16, batch), block, 0, p, n / TILE, m / TILE);
+  return GP_OK;
 }
 
 }  // namespace gp
@@ -207,8 +210,7 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
   GP_HIP(ctx, hipMemcpy(dB, hB.data(), hB.size() * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dC, hC.data(), hC.size() * 8, hipMemcpyHostToDevice));
   GemmP p{dA, dB, dC, a_cols, b_cols, np, 0, 0, 0, (int)kp, alpha, beta, 0};
-  launch_gemm(nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p);
-  GP_HIP(ctx, hipGetLastError());
+  GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p));
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(hC.data(), dC, hC.size() * 8, hipMemcpyDeviceToHost));
   for (long i = 0; i < m; ++i) for (long j = 0; j < n; ++j) C[i * n + j] = hC[i * np + j];
@@ -217,7 +219,7 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
 
 // One launch_gemm with every GemmP field chosen by the caller (include/gparml_hip.h).  Everything launch_gemm or a kernel takes on trust is checked here
 // first -- windows inside their parents for every batch entry, 16-byte alignment, the split-k divisibility, mirror without beta, the overlap rule --
-// and refused with GP_ERR_BAD_ARG: no call reaches launch_gemm's abort() or reads or writes outside a parent buffer.
+// and refused with GP_ERR_BAD_ARG: no call reaches launch_gemm's own refusals (GP_ERR_STATE) or reads or writes outside a parent buffer.
 extern "C" int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int k, int batch_inner, int batch_outer, const long* geom, double alpha,
                                    double beta, const int* mode, const double* A, const double* B, double* C) {
   using namespace gp;
@@ -287,8 +289,7 @@ extern "C" int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int
     GP_HIP(ctx, hipMemset(dW, 0xFF, dW.bytes()));
     p.ws = dW;
   }
-  launch_gemm(nullptr, la == K_CONTIG ? K_CONTIG : FREE_CONTIG, lb == K_CONTIG ? K_CONTIG : FREE_CONTIG, m, n, batch, p);
-  GP_HIP(ctx, hipGetLastError());
+  GP_TRY_RC(launch_gemm(ctx, nullptr, la == K_CONTIG ? K_CONTIG : FREE_CONTIG, lb == K_CONTIG ? K_CONTIG : FREE_CONTIG, m, n, batch, p));
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(C, dev[2], (size_t)w[2].len * 8, hipMemcpyDeviceToHost));
   return GP_OK;
@@ -296,9 +297,8 @@ extern "C" int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int
 
 // device-resident timing of the GEMM core (tools/ only; not part of the public header)
 extern "C" int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int k, int iters, double* ms_out) {
-  const char* fill_env = getenv("GP_BENCH_FILL");
-  const int fill = fill_env ? atoi(fill_env) : 0;  // 0 random, 1 zeros, 2 constant
   using namespace gp;
+  const int fill = env_int("GP_BENCH_FILL", 0);  // 0 random, 1 zeros, 2 constant
   gp_ctx* ctx = nullptr;
   GP_HIP(ctx, hipSetDevice(device));
   const long mp = round_up(m, TILE), np = round_up(n, TILE), kp = round_up(k, KC);
@@ -314,10 +314,10 @@ extern "C" int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int
   GemmP p{dA, dB, dC, a_cols, b_cols, np, 0, 0, 0, (int)kp, 1.0, 0.0, 0};
   hipEvent_t e0, e1;
   GP_HIP(ctx, hipEventCreate(&e0)); GP_HIP(ctx, hipEventCreate(&e1));
-  launch_gemm(nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p);
+  GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p));
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipEventRecord(e0));
-  for (int i = 0; i < iters; ++i) launch_gemm(nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p);
+  for (int i = 0; i < iters; ++i) GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p));
   GP_HIP(ctx, hipEventRecord(e1));
   GP_HIP(ctx, hipEventSynchronize(e1));
   float ms;

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/gparml_hip.h"
 #include "devbuf.h"
@@ -18,6 +19,12 @@ namespace gp {
 #ifndef GP_I8_DIGITS
 #define GP_I8_DIGITS 6     // signed 7-bit digits per operand of the int8 phase-1 prototype (p1i8.hip): 42 bits below the operand's scale
 #endif
+
+// run-time switches read from the environment when the library is loaded (or on first use).  A flag that defaults to on is switched off by a value
+// starting with '0', one that defaults to off is switched on by a value starting with '1'; anything else leaves the default
+inline bool env_flag(const char* name, bool dflt) { const char* e = getenv(name); return e ? (dflt ? e[0] != '0' : e[0] == '1') : dflt; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && std::string(e) == value; }
 
 inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 inline int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 8192)); }   // grid of a grid-stride kernel over n elements
@@ -44,13 +51,14 @@ struct GemmP {
   // product does not depend on which factor is the A operand).
   // mirror REQUIRES beta == 0: the transposed element would have to be C0's own transposed element times beta, which none of the kernels reads -- the
   // 32-tile kernel and the split-k reduce would copy beta * C0(r,c) across, the unsplit 128-tile kernel would not mirror at all.  launch_gemm, the one
-  // launch site of all three, refuses the combination (a programming error: abort), so no kernel is reachable with it (the fused tail of the global step
-  // walks gemm32_tile itself and never sets mirror).
+  // launch site of all three, refuses the combination (a programming error: GP_ERR_STATE before anything is launched), so no kernel is reachable with it
+  // (the fused tail of the global step walks gemm32_tile itself and never sets mirror).
   int klow = 0, mirror = 0;
   int big = 0;          // 1: the 128 x 128-tile kernel (with splits) whatever the tile count (the M x M x M products at M >= 1024)
 };
-// m, n multiples of TILE; la/lb: Layout of A (free index = rows of C) and B (free index = cols of C)
-void launch_gemm(hipStream_t st, Layout la, Layout lb, int m, int n, int batch, const GemmP& p);
+// m, n multiples of TILE; la/lb: Layout of A (free index = rows of C) and B (free index = cols of C).  c may be NULL (the debug hooks).  GP_ERR_STATE,
+// with nothing launched, when C meets an operand (checked for batch entry 0 only) or mirror comes with beta != 0; GP_ERR_HIP when a launch is refused
+int launch_gemm(gp_ctx* c, hipStream_t st, Layout la, Layout lb, int m, int n, int batch, const GemmP& p);
 
 // index of the scalars at the tail of the packed statistics buffer
 enum { SC_SUM_YYT = 0, SC_PSI0 = 1, SC_KL = 2, SC_NLOCAL = 3, SC_COUNT = 8 };
@@ -237,7 +245,7 @@ struct gp_ctx {
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
   // evaluation's first and last event (total_ms), 0 = none.  Every recorded event is a signal packet the stream waits on: ~4-7 us of idle
   // stream each, thirteen per evaluation -- 0.3 % of an evaluation at configs[2]'s size, 15 % at configs[1]'s (gp_set_timing)
-  int timing = [] { const char* e = getenv("GPARML_TIMING"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2; }();
+  int timing = [] { const int t = gp::env_int("GPARML_TIMING", 2); return t >= 0 && t <= 2 ? t : 2; }();
   long sync_epoch = 0;        // stream synchronisations seen so far (gp_set_globals' pinned slots are reused without an event once one has passed)
   hipEvent_t ev[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double t_ms[5] = {0, 0, 0, 0, 0};
@@ -274,14 +282,11 @@ int b_poison(gp_ctx* c);                                              // poison 
 int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn, const double** DZ2);   // compat: runs dz2_kernel, hands out the tables
 const double* b_debug_table(const gp_ctx* c, bool lea, long* n);      // gp_debug_peek: LE or LEA, NULL / 0 without a plan
 // predict.hip
-extern std::atomic<int> g_opt_pred_rows;
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
 // infer.hip
-extern std::atomic<int> g_opt_inf_rows;
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
 // kmeans.hip
-extern std::atomic<int> g_opt_km_rows;
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
@@ -302,9 +307,25 @@ int check_global_from(gp_ctx* c, const double* h);
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A /*in: SPD, out: L*/, double* Linv, double* Inv,
                           double* Twork /*batch * Mp * Mp / 2 doubles*/, double* logdet2 /*device, [batch]*/, double* fail_flag /*device, [batch]*/,
                           double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0);
+// the options of gp_debug_set_option (api.hip holds the table and the ones without a home file), each next to the code it switches
+extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
+extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip
+extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
+extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }
 __host__ __device__ inline long le_index(bool il, long n, long m, long Mp) { return il ? ((((n >> 2) * Mp + m) << 2) + (n & 3)) : n * Mp + m; }
+
+
+// Calls f(std::integral_constant<int, W>) for the W among Ws that equals w and returns its status: the one place a run-time latent width picks a
+// compile-time instantiation.  A width outside the list is GP_ERR_UNSUPPORTED, never the nearest kernel.  (A left fold: the compiler then emits the
+// kernels in the order of the list, as a switch did.)
+template <int... Ws, typename F>
+int for_width(gp_ctx* c, const char* what, int w, F&& f) {
+  int rc = GP_OK;
+  const bool found = (... || (w == Ws && ((rc = f(std::integral_constant<int, Ws>{})), true)));
+  return found ? rc : fail(c, GP_ERR_UNSUPPORTED, "%s: no instantiation for the latent table width %d", what, w);
+}
 
 }  // namespace gp
 
@@ -315,5 +336,14 @@ __host__ __device__ inline long le_index(bool il, long n, long m, long Mp) { ret
   do {                                                                                            \
     hipError_t e__ = (call);                                                                      \
     if (e__ != hipSuccess) return gp::fail(ctx, GP_ERR_HIP, "%s failed: %s (%s:%d)", #call,      \
+                                            hipGetErrorString(e__), __FILE__, __LINE__);           \
+  } while (0)
+// The one way to launch a kernel: the launch is checked where it is made, and a refused one is reported by the kernel's name before anything else is
+// enqueued.  `kernel` may be a parenthesised template name, (psi1_kernel<QP, true>); ctx may be NULL.  Returns from the enclosing function on failure.
+#define GP_LAUNCH(ctx, stream, kernel, grid, block, lds_bytes, ...)                                \
+  do {                                                                                            \
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, __VA_ARGS__);                      \
+    hipError_t e__ = hipGetLastError();                                                           \
+    if (e__ != hipSuccess) return gp::fail(ctx, GP_ERR_HIP, "launch of %s failed: %s (%s:%d)", #kernel, \
                                             hipGetErrorString(e__), __FILE__, __LINE__);           \
   } while (0)

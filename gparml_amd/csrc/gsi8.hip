@@ -29,7 +29,7 @@ constexpr int GS_S = 10;                   // digits per operand
 typedef int gs_v4i __attribute__((ext_vector_type(4)));
 typedef int gs_v16i __attribute__((ext_vector_type(16)));
 
-std::atomic<int> g_opt_gs_i8{[] { const char* e = getenv("GPARML_GS_I8"); return (e && e[0] == '0') ? 0 : 1; }()};
+std::atomic<int> g_opt_gs_i8{env_flag("GPARML_GS_I8", true)};
 
 struct GsMat { const double* X; long ld; int ncols; int c0; };      // a block of W's columns: X [K rows][ncols] row-major, columns c0 .. c0 + ncols of W
 
@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(256, 1) gsi8_gemm_kernel(GsI8Args a) {
 }
 
 // GPARML_GS_I8_MIN_M (default 1024): the smallest padded M the int8 products replace the double-double kernels at (512: measured)
-static const int g_gs_i8_min_m = [] { const char* e = getenv("GPARML_GS_I8_MIN_M"); const int v = e ? atoi(e) : 1024; return v >= 512 ? v : 512; }();
+static const int g_gs_i8_min_m = std::max(512, env_int("GPARML_GS_I8_MIN_M", 1024));
 bool gs_i8_wanted(const gp_ctx* c) { return g_opt_gs_i8.load() && c->Mp >= g_gs_i8_min_m && c->Mp <= 2048 && c->gstep.gsd != nullptr; }
 
 // out [nA][nB] = (A-side)^T-columns x B-side columns over K rows: out[i][j] = sum_k A[k][i] B[k][j]   (A symmetric in both uses: = sum_k A[i][k] B[k][j])
@@ -163,11 +163,10 @@ int run_gs_i8_product(gp_ctx* c, hipStream_t st, const double* A, long lda, int 
   const long plane = (long)(K / 16) * wcols * 16;
   if ((size_t)GS_S * plane > c->gstep.gsd.size() || (size_t)wcols > c->gstep.gss.size()) return fail(c, GP_ERR_STATE, "int8 global-step product: workspace too small");
   GsMat m0{A, lda, nA, 0}, m1{B, ldb, nB, nA};
-  hipLaunchKernelGGL(gsi8_colscale_kernel, dim3((std::max(nA, nB) + 15) / 16, 2), dim3(256), 0, st, m0, m1, K, c->gstep.gss);
-  hipLaunchKernelGGL(gsi8_digits_kernel, dim3((std::max(nA, nB) + 255) / 256, K / 16, 2), dim3(256), 0, st, m0, m1, (const double*)c->gstep.gss, c->gstep.gsd, plane, wcols);
+  GP_LAUNCH(c, st, gsi8_colscale_kernel, dim3((std::max(nA, nB) + 15) / 16, 2), dim3(256), 0, m0, m1, K, c->gstep.gss);
+  GP_LAUNCH(c, st, gsi8_digits_kernel, dim3((std::max(nA, nB) + 255) / 256, K / 16, 2), dim3(256), 0, m0, m1, (const double*)c->gstep.gss, c->gstep.gsd, plane, wcols);
   GsI8Args g{c->gstep.gsd, plane, wcols, 0, nA, K, c->gstep.gss, out, ldo, Csub};
-  hipLaunchKernelGGL(gsi8_gemm_kernel, dim3(nB / 64, nA / 64), dim3(256), 0, st, g);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, st, gsi8_gemm_kernel, dim3(nB / 64, nA / 64), dim3(256), 0, g);
   return GP_OK;
 }
 

@@ -535,22 +535,20 @@ static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)s
 static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
   hipStream_t st = c->stream;
   const int M = c->M, Mp = c->Mp, Q = c->Q;
-  hipLaunchKernelGGL(inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, st, k.xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, k.TB, k.LC);
-  hipLaunchKernelGGL(inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, st, k.TB, k.LC, mask, p.ZP, p.ZZ, cnt, M, Mp, QP, k.LEA);
+  GP_LAUNCH(c, st, inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, k.xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, k.TB, k.LC);
+  GP_LAUNCH(c, st, inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, k.TB, k.LC, mask, p.ZP, p.ZZ, cnt, M, Mp, QP, k.LEA);
   InfDims a;
   a.cnt = cnt; a.M = M; a.Mp = Mp; a.Q = Q; a.QP = QP; a.raw = raw; a.sf2 = c->sf2; a.beta = c->beta; a.Do = Do;
   double* ge = want_grad ? k.ge.get() : nullptr;
   const dim3 grid((unsigned)((cnt + 3) / 4));
-#define INF_ROWS(QR, WIDE)                                                                                                                              \
-  hipLaunchKernelGGL((inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, st, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), \
-                     k.yy.get(), p.ZP.get(), p.ZZ.get(), p.Gf.get(), mask, k.fe.get(), ge, a)
-  if (QP == 4) INF_ROWS(4, false);
-  else if (QP == 10) INF_ROWS(10, false);
-  else if (QP == 16) INF_ROWS(16, false);
-  else INF_ROWS(16, true);
-#undef INF_ROWS
-  GP_HIP(c, hipGetLastError());
-  return GP_OK;
+  // up to 16 latent columns one pass over the row tables at their own width; beyond, 16 columns at a time (width 0 here)
+  return for_width<4, 10, 16, 0>(c, "latent inference row kernel", QP <= 16 ? QP : 0, [&](auto W) -> int {
+    constexpr bool WIDE = W() == 0;
+    constexpr int QR = WIDE ? 16 : W();
+    GP_LAUNCH(c, st, (inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), k.yy.get(), p.ZP.get(),
+              p.ZZ.get(), p.Gf.get(), mask, k.fe.get(), ge, a);
+    return GP_OK;
+  });
 }
 
 // mode 0: gp_infer_objective (L, grad_mu, grad_S out, any may be NULL); mode 1: gp_infer_latent (X_mu, X_S in/out, L, iters out)
@@ -569,15 +567,13 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
   std::vector<int> hc(Do);
   for (int j = 0; j < Do; ++j) hc[j] = cols ? cols[j] : j;
   GP_HIP(c, hipMemcpyAsync(p.cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, st, c->gstep.E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
-  hipLaunchKernelGGL(inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, st, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, st, inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, c->gstep.E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
+  GP_LAUNCH(c, st, inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
   GemmP g;
   g.K = (int)Dop; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
   g.A = k.Eo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = p.T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
-  launch_gemm(st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g);
-  hipLaunchKernelGGL(inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, st, p.T, c->gstep.Inv, (int)M, (int)Mp, (double)Do, p.Gf);
-  GP_HIP(c, hipGetLastError());
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g));
+  GP_LAUNCH(c, st, inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, p.T, c->gstep.Inv, (int)M, (int)Mp, (double)Do, p.Gf);
   // the observed columns of every row, packed on the host: the others are never read
   std::vector<double> yc((size_t)n * Do);
   for (long i = 0; i < n; ++i)
@@ -599,11 +595,9 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
       }
     GP_HIP(c, hipMemcpyAsync(k.xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
     GP_HIP(c, hipMemcpyAsync(k.Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, st, k.Yc, cnt, rows, Do, (int)Dop, k.Yo, k.yy);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, k.Yc, cnt, rows, Do, (int)Dop, k.Yo, k.yy);
     g.A = k.Yo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = k.V; g.ldc = Mp; g.alpha = c->beta; g.beta = 0.0;
-    launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, g);
-    GP_HIP(c, hipGetLastError());
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, g));
     if (mode == 0) {
       GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
       if (L) GP_HIP(c, hipMemcpyAsync(L + n0, k.fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
@@ -621,24 +615,23 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
     }
     GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, true, QP, (double)Do));
     const dim3 rg(inf_blocks(cnt));
-    hipLaunchKernelGGL(inf_scg_init_kernel, rg, dim3(256), 0, st, s);
+    GP_LAUNCH(c, st, inf_scg_init_kernel, rg, dim3(256), 0, s);
     int* d_active = o->si.get() + R * II_COUNT;
     for (int it = 0; it < max_iters; ++it) {
       if (it % INF_POLL == 0) {
         int active = 0;
-        hipLaunchKernelGGL(inf_count_kernel, dim3(1), dim3(256), 0, st, o->si, cnt, d_active);
+        GP_LAUNCH(c, st, inf_count_kernel, dim3(1), dim3(256), 0, o->si, cnt, d_active);
         GP_HIP(c, hipMemcpyAsync(&active, d_active, sizeof(int), hipMemcpyDeviceToHost, st));
         GP_HIP(c, hipStreamSynchronize(st));
         if (active == 0) break;
       }
-      hipLaunchKernelGGL(inf_scg_probe_kernel, rg, dim3(256), 0, st, s);
+      GP_LAUNCH(c, st, inf_scg_probe_kernel, rg, dim3(256), 0, s);
       GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
-      hipLaunchKernelGGL(inf_scg_trial_kernel, rg, dim3(256), 0, st, s);
+      GP_LAUNCH(c, st, inf_scg_trial_kernel, rg, dim3(256), 0, s);
       GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
-      hipLaunchKernelGGL(inf_scg_update_kernel, rg, dim3(256), 0, st, s);
+      GP_LAUNCH(c, st, inf_scg_update_kernel, rg, dim3(256), 0, s);
     }
-    hipLaunchKernelGGL(inf_scg_out_kernel, rg, dim3(256), 0, st, s, o->out.get());
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, inf_scg_out_kernel, rg, dim3(256), 0, s, o->out.get());
     hout.resize((size_t)cnt * (2 * Q + 2));
     GP_HIP(c, hipMemcpyAsync(hout.data(), o->out, hout.size() * 8, hipMemcpyDeviceToHost, st));
     GP_HIP(c, hipStreamSynchronize(st));

@@ -182,8 +182,9 @@ struct KmPlan {
 void KmPlanDelete::operator()(KmPlan* p) const { delete p; }
 
 template <int QT>
-static void km_launch_assign(hipStream_t st, unsigned blocks, const double* X, const double* cen, long cnt, int Q, int K, int* lab, double* dpart) {
-  hipLaunchKernelGGL(km_assign_kernel<QT>, dim3(blocks), dim3(256), 0, st, X, cen, cnt, Q, K, lab, dpart);
+static int km_launch_assign(gp_ctx* c, hipStream_t st, unsigned blocks, const double* X, const double* cen, long cnt, int Q, int K, int* lab, double* dpart) {
+  GP_LAUNCH(c, st, km_assign_kernel<QT>, dim3(blocks), dim3(256), 0, X, cen, cnt, Q, K, lab, dpart);
+  return GP_OK;
 }
 
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels) {
@@ -212,23 +213,18 @@ int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres,
       x = p.in;
     }
     const unsigned blocks = (unsigned)((cnt + 255) / 256), segs = (unsigned)((cnt + KM_SEG - 1) / KM_SEG);
-    switch (QT) {
-#define KM_CASE(W) case W: km_launch_assign<W>(st, blocks, x, p.cen, cnt, (int)Q, K, p.lab, p.dpart); break
-      KM_CASE(2); KM_CASE(4); KM_CASE(6); KM_CASE(8); KM_CASE(10); KM_CASE(12); KM_CASE(14); KM_CASE(16); KM_CASE(24); KM_CASE(32); KM_CASE(52); KM_CASE(64);
-#undef KM_CASE
-      default: km_launch_assign<0>(st, blocks, x, p.cen, cnt, (int)Q, K, p.lab, p.dpart);
-    }
-    GP_HIP(c, hipGetLastError());
+    // (width 0: the kernel with a run-time Q, beyond the 64-wide records)
+    GP_TRY_RC((for_width<2, 4, 6, 8, 10, 12, 14, 16, 24, 32, 52, 64, 0>(c, "k-means assignment kernel", QT, [&](auto W) {
+      return km_launch_assign<W()>(c, st, blocks, x, p.cen, cnt, (int)Q, K, p.lab, p.dpart);
+    })));
     if (labels) GP_HIP(c, hipMemcpyAsync(labels + n0, p.lab, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
     if (sums || counts) {
-      hipLaunchKernelGGL(km_reduce_kernel, dim3(segs, (unsigned)((K + KM_CG - 1) / KM_CG)), dim3(256), 0, st, x, p.lab, cnt, (int)Q, K, p.part, p.pcnt);
-      GP_HIP(c, hipGetLastError());
+      GP_LAUNCH(c, st, km_reduce_kernel, dim3(segs, (unsigned)((K + KM_CG - 1) / KM_CG)), dim3(256), 0, x, p.lab, cnt, (int)Q, K, p.part, p.pcnt);
     }
     // without sums and counts only the last workgroup (the distances) has work
     const unsigned fblocks = (sums || counts) ? (unsigned)((std::max<long>(kq, K) + 255) / 256) : 0u;
-    hipLaunchKernelGGL(km_final_kernel, dim3(fblocks + 1), dim3(256), 0, st, p.part, p.pcnt, p.dpart, (int)segs, (int)blocks, kq, K, n0 == 0 ? 1 : 0, p.out,
-                       p.cnt, p.out + kq);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, km_final_kernel, dim3(fblocks + 1), dim3(256), 0, p.part, p.pcnt, p.dpart, (int)segs, (int)blocks, kq, K, n0 == 0 ? 1 : 0, p.out,
+              p.cnt, p.out + kq);
   }
   static_assert(sizeof(long long) == sizeof(int64_t), "counts are copied out as they are");
   if (sums) GP_HIP(c, hipMemcpyAsync(sums, p.out, (size_t)kq * 8, hipMemcpyDeviceToHost, st));

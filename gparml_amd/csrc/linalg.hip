@@ -18,12 +18,8 @@ namespace gp {
 
 // switches of the global step's extended-precision pieces (default on; environment at load time, gp_debug_set_option at run time: bench.py
 // prices them by timing the global step with and without)
-static bool env_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
-std::atomic<int> g_opt_dd_kipsi2{env_on("GPARML_DD_KIPSI2") ? 1 : 0};
-std::atomic<int> g_opt_refine_E{env_on("GPARML_REFINE_E") ? 1 : 0};
-extern std::atomic<int> g_opt_p1_i8;      // p1i8.hip
-extern std::atomic<int> g_opt_i8_guard_strict;
-extern std::atomic<int> g_opt_gs_i8;      // gsi8.hip
+std::atomic<int> g_opt_dd_kipsi2{env_flag("GPARML_DD_KIPSI2", true)};
+std::atomic<int> g_opt_refine_E{env_flag("GPARML_REFINE_E", true)};
 
 // r05, the global step at M >= 1024 (each switchable for same-box A/B through gp_debug_set_option):
 std::atomic<int> g_opt_xtx_tri{1};       // A^-1 = X^T X from its lower tiles, k from the tile's first non-zero row, mirrored store (bit-identical, split or not: tests/test_gpu_linalg.py)
@@ -62,7 +58,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
   GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
   // Linv's 128-blocks above the diagonal are never written and are zero from the allocation (gp_create / the test hook)
   for (int j = 0; j < nt; ++j) {
-    hipLaunchKernelGGL(potrf_trinv128_kernel, dim3(batch), dim3(512), POTRF_LDS_DOUBLES * 8, st, A, ld, bs, j, Linv, fail_flag, logdet2);
+    GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3(batch), dim3(512), POTRF_LDS_DOUBLES * 8, A, ld, bs, j, Linv, fail_flag, logdet2);
     const int rem = nt - j - 1;
     if (rem > 0) {
       // panel: L[i,j] = A[i,j] * inv(L_jj)^T, i > j   (rows rem*128, cols 128, k 128) -- through the work panel, see below
@@ -79,16 +75,16 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
       // in place (+ ~5 us per panel; the 128 x 128-tile kernel in place -- one workgroup owns all columns of its rows -- is safe too but costs 20 us per panel).
       // profiles/r06_first_evaluation_race.txt, tests/test_gpu_first_evaluation.py.
       p.C = Twork; p.ldc = NB; p.sC = (long)rem * NB * NB;
-      launch_gemm(st, K_CONTIG, K_CONTIG, rem * NB, NB, batch, p);
-      hipLaunchKernelGGL(panel_copy_kernel, dim3((unsigned)std::min<long>(((long)rem * NB * NB / 2 + 255) / 256, 512), batch), dim3(256), 0, st, (const double*)Twork,
-                         (long)rem * NB * NB, A + ((long)(j + 1) * NB) * ld + (long)j * NB, ld, bs, (long)rem * NB);
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, NB, batch, p));
+      GP_LAUNCH(c, st, panel_copy_kernel, dim3((unsigned)std::min<long>(((long)rem * NB * NB / 2 + 255) / 256, 512), batch), dim3(256), 0, (const double*)Twork,
+                (long)rem * NB * NB, A + ((long)(j + 1) * NB) * ld + (long)j * NB, ld, bs, (long)rem * NB);
       // trailing update: A[i,k] -= L[i,j] L[k,j]^T for i >= k > j (lower tiles)
       GemmP q;
       q.A = A + ((long)(j + 1) * NB) * ld + (long)j * NB; q.lda = ld; q.sA = bs;
       q.B = q.A; q.ldb = ld; q.sB = bs;                                         // B(k,c) = L[c][k] -> K_CONTIG
       q.C = A + ((long)(j + 1) * NB) * ld + (long)(j + 1) * NB; q.ldc = ld; q.sC = bs;
       q.K = NB; q.alpha = -1.0; q.beta = 1.0; q.tri = 1;
-      launch_gemm(st, K_CONTIG, K_CONTIG, rem * NB, rem * NB, batch, q);
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, rem * NB, batch, q));
     }
   }
   if (g_opt_trtri_rec.load()) {
@@ -99,7 +95,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
     for (int h = 1; h < nt; h *= 2) {
       const long b = (long)h * NB, ps = 2 * b * (ld + 1);
       const int full = nt / (2 * h), rem = nt - full * 2 * h - h;
-      auto level = [&](int p0, int np, int rows2) {
+      auto level = [&](int p0, int np, int rows2) -> int {
         const long o11 = ((long)(2 * p0 * h) * NB) * (ld + 1), o22 = o11 + b * (ld + 1), o21 = o11 + b * ld;
         const long m2 = (long)rows2 * NB;
         GemmP p;                                                        // T = L21 X11
@@ -107,16 +103,17 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
         p.B = Linv + o11; p.ldb = ld; p.sB = ps; p.oB = bs;             // X11 stored [k][c], FREE_CONTIG
         p.C = Twork; p.ldc = b; p.sC = m2 * b; p.oC = (long)np * m2 * b;
         p.K = (int)b; p.alpha = 1.0; p.beta = 0.0; p.tri = 0; p.inner = np;
-        launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, p);
+        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, p));
         GemmP q;                                                        // X21 = -X22 T
         q.A = Linv + o22; q.lda = ld; q.sA = ps; q.oA = bs;             // X22 [m][k], K_CONTIG
         q.B = Twork; q.ldb = b; q.sB = m2 * b; q.oB = (long)np * m2 * b;
         q.C = Linv + o21; q.ldc = ld; q.sC = ps; q.oC = bs;
         q.K = (int)m2; q.alpha = -1.0; q.beta = 0.0; q.tri = 0; q.inner = np;
-        launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, q);
+        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, q));
+        return GP_OK;
       };
-      if (full > 0) level(0, full, h);
-      if (rem > 0) level(full, 1, rem);
+      if (full > 0) GP_TRY_RC(level(0, full, h));
+      if (rem > 0) GP_TRY_RC(level(full, 1, rem));
     }
   } else {
     // block rows of X = L^-1: X[i,0:i] = -X_ii * (L[i,0:i] * X[0:i,0:i])
@@ -126,13 +123,13 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
       p.B = Linv; p.ldb = ld; p.sB = bs;                               // X[0:i,0:i] stored [k][c] -> FREE_CONTIG
       p.C = Twork; p.ldc = Mp; p.sC = (long)NB * Mp;
       p.K = i * NB; p.alpha = 1.0; p.beta = 0.0; p.tri = 0;
-      launch_gemm(st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, p);
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, p));
       GemmP q;
       q.A = Linv + ((long)i * NB) * ld + (long)i * NB; q.lda = ld; q.sA = bs;   // X_ii, K_CONTIG
       q.B = Twork; q.ldb = Mp; q.sB = (long)NB * Mp;                            // T stored [k][c] -> FREE_CONTIG
       q.C = Linv + ((long)i * NB) * ld; q.ldc = ld; q.sC = bs;
       q.K = NB; q.alpha = -1.0; q.beta = 0.0; q.tri = 0;
-      launch_gemm(st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, q);
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, q));
     }
   }
   // A^-1 = X^T X
@@ -150,8 +147,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
   } else if (splitk_ws && Mp >= 256 && Mp <= 1024 && (Mp / KC) % kSplitK == 0 && (size_t)batch * (Mp / TILE) * (Mp / TILE) * kSplitK * TILE * TILE <= splitk_cap) {
     r.splits = kSplitK; r.ws = splitk_ws;       // (ignored by the small-tile kernel that serves these sizes)
   }
-  launch_gemm(st, FREE_CONTIG, FREE_CONTIG, Mp, Mp, batch, r);
-  GP_HIP(c, hipGetLastError());
+  GP_TRY_RC(launch_gemm(c, st, FREE_CONTIG, FREE_CONTIG, Mp, Mp, batch, r));
   return GP_OK;
 }
 
@@ -685,7 +681,7 @@ __global__ void __launch_bounds__(256, 1) tail_stage_kernel(TailP p, int stage) 
     else colsum_block(p.T2, p.M, p.Q, p.gK + (long)p.M * p.Q, t - 1, red);
   }
 }
-std::atomic<int> g_opt_gs_tail{env_on("GPARML_GS_TAIL") ? 1 : 0};
+std::atomic<int> g_opt_gs_tail{env_flag("GPARML_GS_TAIL", true)};
 
 // Host side of the global step's outcome: one D2H of the scalars + failure flags, at the first call that needs them
 // (gp_global_status, gp_finish, gp_download).  Returns GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE or GP_RETRY_JITTER.
@@ -767,14 +763,13 @@ int run_global_step(gp_ctx* c) {
   // T2 is free until G = K_mm^-1 Psi2 is formed: it keeps A for the double-double residual of the refinement step
   const bool gi8 = gs_i8_wanted(c);            // gsi8.hip: both double-double products on the int8 matrix core (M >= 1024)
   const bool res_dd = g_opt_refine_E.load() && ((g_opt_residual_dd.load() && Mp >= 256 && Dp >= 512) || gi8);   // narrow E: too few waves (M = 512, D = 100: +21 us)
-  hipLaunchKernelGGL(build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, st, c->Z, c->alpha, c->sf2, c->beta, Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
-                     c->gstep.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, c->gstep.gs, res_dd ? c->gstep.T2 : (double*)nullptr);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, st, build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, c->Z, c->alpha, c->sf2, c->beta, Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
+            c->gstep.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, c->gstep.gs, res_dd ? c->gstep.T2 : (double*)nullptr);
   // one-panel problems (M, D <= 128): the panel kernel, then seven launches of tail_stage_kernel instead of fifteen kernels
   if (Mp == NB && Dp == NB && g_opt_gs_tail.load()) {
     GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
     GP_HIP(c, hipFuncSetAttribute((const void*)tail_stage_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_DOUBLES * 8));
-    hipLaunchKernelGGL(potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, st, c->gstep.Kmm, (long)Mp, mm, 0, c->gstep.Linv, failf, c->gstep.gs + GS_LOGDET_K);
+    GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, c->gstep.Kmm, (long)Mp, mm, 0, c->gstep.Linv, failf, c->gstep.gs + GS_LOGDET_K);
     TailP t;
     t.Linv = c->gstep.Linv; t.Inv = c->gstep.Inv; t.Psi2 = Psi2; t.C = C; t.sc = sc; t.Keep = c->gstep.KmmKeep;
     t.E = c->gstep.E; t.PsiE = c->gstep.PsiE; t.T1 = c->gstep.T1; t.T2 = c->gstep.T2; t.dFdK = c->gstep.dFdK; t.Bbar = c->gstep.Bbar; t.Abar = c->gstep.Abar; t.Bm = c->gstep.Bm;
@@ -793,9 +788,8 @@ int run_global_step(gp_ctx* c) {
       const int items = tail_items(stage, M, Q, t.refine, t.dd);
       // only the stages with tile products need the operand images
       const size_t lds = (stage <= 4) ? (size_t)TAIL_LDS_DOUBLES * 8 : 4096;
-      if (items > 0) hipLaunchKernelGGL(tail_stage_kernel, dim3(items), dim3(256), lds, st, t, stage);
+      if (items > 0) GP_LAUNCH(c, st, tail_stage_kernel, dim3(items), dim3(256), lds, t, stage);
     }
-    GP_HIP(c, hipGetLastError());
     c->gstep.gs_pending = true;
     return GP_OK;
   }
@@ -823,47 +817,43 @@ int run_global_step(gp_ctx* c) {
   g.ws = ws;
   g.big = bigMD; g.splits = bigMD ? spMD : 1;
   g.A = P; g.lda = Mp; g.B = C; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp;
-  launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
   // one refinement step of E with a double-double residual (PsiE is free until the next product); GPARML_REFINE_E=0 turns it off
   if (g_opt_refine_E.load()) {
     if (gi8) {
       GP_TRY_RC(run_gs_i8_product(c, st, c->gstep.T2, (long)Mp, Mp, c->gstep.E, (long)Dp, Dp, Mp, c->gstep.PsiE, (long)Dp, C));
     } else if (res_dd) {
-      hipLaunchKernelGGL((ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, st, c->gstep.T2, (long)Mp, c->gstep.E, (long)Dp, Mp, C, c->gstep.PsiE);
+      GP_LAUNCH(c, st, (ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, c->gstep.T2, (long)Mp, c->gstep.E, (long)Dp, Mp, C, c->gstep.PsiE);
     } else {
-      hipLaunchKernelGGL(solve_residual_kernel, dim3(M), dim3(512), 0, st, c->gstep.KmmKeep, Psi2, c->beta, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, C, c->gstep.E, M, Mp, Dp,
-                         c->gstep.PsiE, 0);
+      GP_LAUNCH(c, st, solve_residual_kernel, dim3(M), dim3(512), 0, c->gstep.KmmKeep, Psi2, c->beta, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, C, c->gstep.E, M, Mp, Dp,
+                c->gstep.PsiE, 0);
       if (M < Mp) GP_HIP(c, hipMemsetAsync(c->gstep.PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
     }
-    GP_HIP(c, hipGetLastError());
     g.A = P; g.lda = Mp; g.B = c->gstep.PsiE; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp; g.beta = 1.0;
-    launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
     g.beta = 0.0;
   }
   g.A = Psi2; g.lda = Mp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.PsiE; g.ldc = Dp;
-  launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g);
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
   g.K = Dp; g.A = c->gstep.E; g.lda = Dp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.T1; g.ldc = Mp;   // B(k,j) = E[j][k] -> K_CONTIG
-  { const int sps = g.splits; g.splits = 1; g.big = 0; launch_gemm(st, K_CONTIG, K_CONTIG, Mp, Mp, 1, g); g.splits = sps; }
+  { const int sps = g.splits; g.splits = 1; g.big = 0; GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, Mp, Mp, 1, g)); g.splits = sps; }
   // G = Ki Psi2 with double-double accumulation (ddacc_gemm_kernel above: two rows per wave, eight k per trip -- same-box timing of six shapes
   // in profiles/r04_dd_variants.txt: +50 us at M = 512, +9 us at M = 128, +0.29 ms at M = 1024 over the float64 matrix-core product of r03, which
   // GPARML_DD_KIPSI2=0 or gp_debug_set_option("dd_kipsi2", 0) restores)
   if (g_opt_dd_kipsi2.load() && gi8) {
     GP_TRY_RC(run_gs_i8_product(c, st, Ki, (long)Mp, Mp, Psi2, (long)Mp, Mp, Mp, c->gstep.T2, (long)Mp, nullptr));
   } else if (g_opt_dd_kipsi2.load()) {
-    hipLaunchKernelGGL((ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, st, Ki, (long)Mp, Psi2, (long)Mp, Mp, c->gstep.T2, (long)Mp);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, (ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, Ki, (long)Mp, Psi2, (long)Mp, Mp, c->gstep.T2, (long)Mp);
   } else {
     g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1; g.A = Ki; g.lda = Mp; g.B = Psi2; g.ldb = Mp; g.C = c->gstep.T2; g.ldc = Mp;
-    launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g);
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g));
   }
   g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1;
   g.A = c->gstep.T2; g.lda = Mp; g.B = Ki; g.ldb = Mp; g.C = c->gstep.dFdK; g.ldc = Mp;
-  launch_gemm(st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g);
-  GP_HIP(c, hipGetLastError());
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g));
   // dFdK currently holds Ki Psi2 Ki; assemble in place is unsafe (reads KPK, writes dFdK at the same index: fine, same thread)
-  hipLaunchKernelGGL(assemble_kernel, dim3(1024), dim3(256), 0, st, Ki, P, c->gstep.T1, c->gstep.dFdK, c->gstep.E, c->beta, (double)D, Mp, Dp, c->gstep.Bbar,
-                     c->gstep.dFdK, c->gstep.Abar, c->gstep.Bm);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, st, assemble_kernel, dim3(1024), dim3(256), 0, Ki, P, c->gstep.T1, c->gstep.dFdK, c->gstep.E, c->beta, (double)D, Mp, Dp, c->gstep.Bbar,
+            c->gstep.dFdK, c->gstep.Abar, c->gstep.Bm);
   DotJobs jobs;
   jobs.n = 7;
   jobs.j[0] = {Ki, Psi2, Mp, M, M, GS_TR_KIPSI2};
@@ -875,18 +865,17 @@ int run_global_step(gp_ctx* c) {
   jobs.j[6] = {c->gstep.Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
   double* dpart = c->gstep.gs + GS_DOTS;   // [jobs][DOT_BLOCKS]
   // the traces / scalars and the Kmm parts of the gradients both start from the assembled partials and do not touch each other's outputs
-  hipLaunchKernelGGL(dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, st, jobs, dpart);
-  hipLaunchKernelGGL(scalars_kernel, dim3(1), dim3(64), 0, st, sc, c->gstep.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
+  GP_LAUNCH(c, st, dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, jobs, dpart);
+  GP_LAUNCH(c, st, scalars_kernel, dim3(1), dim3(64), 0, sc, c->gstep.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
   // Kmm parts of grad_Z / grad_alpha; alpha partials per row go through T2 (free again)
-  static const bool kmm_lds = [] { const char* e = getenv("GPARML_KMM_LDS"); return !(e && e[0] == '0'); }();
+  static const bool kmm_lds = env_flag("GPARML_KMM_LDS", true);
   if (kmm_lds && M <= 2048)
-    hipLaunchKernelGGL(kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), st, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z,
-                       c->Zt, c->alpha, M, Mp, Q, c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
+    GP_LAUNCH(c, st, kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z,
+              c->Zt, c->alpha, M, Mp, Q, c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
   else
-    hipLaunchKernelGGL(kmm_grads_kernel, dim3(M), dim3(128), 0, st, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
-                       c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
-  hipLaunchKernelGGL(colsum_kernel, dim3(Q), dim3(256), 0, st, c->gstep.T2, M, Q, c->gstep.gK + (long)M * Q);
-  GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
+              c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
+  GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, c->gstep.T2, M, Q, c->gstep.gK + (long)M * Q);
   c->gstep.gs_pending = true;   // scalars and failure flags are read back at the next host synchronisation point (check_global)
   return GP_OK;
 }
@@ -894,27 +883,6 @@ int run_global_step(gp_ctx* c) {
 }  // namespace gp
 
 // ---- test hooks ------------------------------------------------------------------------------------------------
-extern "C" int gp_debug_set_option(const char* name, int value) {
-  using namespace gp;
-  if (!name) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: NULL name");
-  if (!std::strcmp(name, "dd_kipsi2")) { g_opt_dd_kipsi2.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "refine_E")) { g_opt_refine_E.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "p1_i8")) { g_opt_p1_i8.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "gs_tail")) { g_opt_gs_tail.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "i8_guard_strict")) { g_opt_i8_guard_strict.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "xtx_tri")) { g_opt_xtx_tri.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "residual_dd")) { g_opt_residual_dd.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "gemm_big")) { g_opt_gemm_big.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "trtri_rec")) { g_opt_trtri_rec.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "gs_i8")) { g_opt_gs_i8.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "poison_alloc")) { g_opt_poison.store(value ? 1 : 0); return GP_OK; }
-  if (!std::strcmp(name, "predict_rows")) { g_opt_pred_rows.store(std::max(0, value)); return GP_OK; }
-  if (!std::strcmp(name, "infer_rows")) { g_opt_inf_rows.store(std::max(0, value)); return GP_OK; }
-  if (!std::strcmp(name, "kmeans_rows")) { g_opt_km_rows.store(std::max(0, value)); return GP_OK; }
-  if (!std::strcmp(name, "alloc_fail_after")) { g_alloc_fail_after.store(std::max(0, value)); return GP_OK; }
-  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (dd_kipsi2, refine_E, p1_i8, gs_tail, i8_guard_strict, xtx_tri, residual_dd, gemm_big, trtri_rec, gs_i8, poison_alloc, predict_rows, infer_rows, kmeans_rows, alloc_fail_after)", name);
-}
-
 extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet) {
   using namespace gp;
   gp_ctx tmp;

@@ -50,7 +50,7 @@ constexpr long I8_MAX_ROWS = 81920;        // rows per workgroup slice (int32 ac
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-std::atomic<int> g_opt_p1_i8{[] { const char* e = getenv("GPARML_P1_I8"); return (e && e[0] == '1') ? 1 : 0; }()};   // opt-in (see the header)
+std::atomic<int> g_opt_p1_i8{env_flag("GPARML_P1_I8", false)};   // opt-in (see the header)
 constexpr int I8L = 7;                     // digit products with a + b <= I8L (digits numbered from 1) are kept: 21 of 36
 constexpr int I8O = I8L - 1;               // accumulators: orders a + b = 2 .. I8L
 
@@ -368,11 +368,10 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
   if (!c->i8.y_valid) pl->y_valid = false;
   if (!pl->y_valid) {
     const int nb = 1024;
-    hipLaunchKernelGGL(i8_colmax_kernel, dim3(nb), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK, (long)c->Np, c->Mp, c->Dp, pl->pmax);
-    hipLaunchKernelGGL(i8_yscale_kernel, dim3((c->Dp + 255) / 256), dim3(256), 0, c->stream, pl->pmax, nb, c->Dp, pl->yscale);
-    hipLaunchKernelGGL(i8_slice_y_kernel, dim3((c->Dp + 255) / 256, (unsigned)std::min<long>(c->Np / 16, 4096)), dim3(256), 0, c->stream, c->Kaug, (long)c->LDK,
-                       (long)c->Np, c->Mp, c->Dp, c->LDK, pl->yscale, pl->Sl, pl->strideJ);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, i8_colmax_kernel, dim3(nb), dim3(256), 0, c->Kaug, (long)c->LDK, (long)c->Np, c->Mp, c->Dp, pl->pmax);
+    GP_LAUNCH(c, c->stream, i8_yscale_kernel, dim3((c->Dp + 255) / 256), dim3(256), 0, pl->pmax, nb, c->Dp, pl->yscale);
+    GP_LAUNCH(c, c->stream, i8_slice_y_kernel, dim3((c->Dp + 255) / 256, (unsigned)std::min<long>(c->Np / 16, 4096)), dim3(256), 0, c->Kaug, (long)c->LDK,
+              (long)c->Np, c->Mp, c->Dp, c->LDK, pl->yscale, pl->Sl, pl->strideJ);
     pl->y_valid = true;
     c->i8.y_valid = true;
   }
@@ -390,16 +389,14 @@ int run_phase1_i8(gp_ctx* c) {
   constexpr int lds = I8_STAGES * I8_STAGE;
   GP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(p1i8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   GP_EV(c, 10);
-  hipLaunchKernelGGL(p1i8_kernel, dim3(pl->blocks), dim3(512), lds, c->stream, a);
+  GP_LAUNCH(c, c->stream, p1i8_kernel, dim3(pl->blocks), dim3(512), lds, a);
   GP_EV(c, 11);
-  GP_HIP(c, hipGetLastError());
   double* Psi2 = c->stats;
   double* C = c->stats + (long)c->Mp * c->Mp;
   // K = 2 sf2 t  (t = the sliced value, |t| <= 1/2)
-  hipLaunchKernelGGL(p1i8_diag_kernel, dim3((c->Mp + 31) / 32), dim3(256), 0, c->stream, pl->dpart, pl->row_blocks, c->Mp, pl->diag);
-  hipLaunchKernelGGL(p1i8_reduce_kernel, dim3(TILE * TILE / 256, pl->nouts), dim3(256), 0, c->stream, a.part, pl->outs, pl->yscale, 4.0 * c->sf2 * c->sf2,
-                     2.0 * c->sf2, Psi2, C, c->Mp, c->Dp, pl->diag);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, p1i8_diag_kernel, dim3((c->Mp + 31) / 32), dim3(256), 0, pl->dpart, pl->row_blocks, c->Mp, pl->diag);
+  GP_LAUNCH(c, c->stream, p1i8_reduce_kernel, dim3(TILE * TILE / 256, pl->nouts), dim3(256), 0, a.part, pl->outs, pl->yscale, 4.0 * c->sf2 * c->sf2,
+            2.0 * c->sf2, Psi2, C, c->Mp, c->Dp, pl->diag);
   return GP_OK;
 }
 
@@ -455,9 +452,8 @@ int p1i8_check_begin(gp_ctx* c) {
 }
 int p1i8_check_compare(gp_ctx* c) {
   const long n2 = (long)c->Mp * c->Mp, nc = (long)c->Mp * c->Dp;
-  hipLaunchKernelGGL(i8_compare_kernel, dim3(2 * I8_CMP_BLOCKS), dim3(256), 0, c->stream, (const double*)(c->i8.cmp + 8 + 4 * I8_CMP_BLOCKS), (const double*)c->stats, n2, nc,
-                     c->i8.cmp);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, i8_compare_kernel, dim3(2 * I8_CMP_BLOCKS), dim3(256), 0, (const double*)(c->i8.cmp + 8 + 4 * I8_CMP_BLOCKS), (const double*)c->stats, n2, nc,
+            c->i8.cmp);
   c->i8.check_pending = true;
   c->i8.since_check = 0;
   return GP_OK;
@@ -466,7 +462,7 @@ int p1i8_check_finish(gp_ctx* c) {
   // called by gp_finish of a checked evaluation, after the global step (P = (K_mm + beta Psi2)^-1 exists) and before its synchronisation is over:
   // one more small kernel and a 48-byte copy, once per 64 evaluations
   const long mm = (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(i8_compare_final_kernel, dim3(1), dim3(256), 0, c->stream, c->i8.cmp, (const double*)c->stats, (const double*)(c->gstep.Inv + mm), c->M, c->Mp);
+  GP_LAUNCH(c, c->stream, i8_compare_final_kernel, dim3(1), dim3(256), 0, c->i8.cmp, (const double*)c->stats, (const double*)(c->gstep.Inv + mm), c->M, c->Mp);
   double h[6];
   GP_HIP(c, hipMemcpyAsync(h, c->i8.cmp, sizeof(h), hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));

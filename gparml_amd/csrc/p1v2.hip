@@ -316,15 +316,13 @@ int run_phase1_v2(gp_ctx* c) {
   p.Kaug = c->Kaug; p.ld = c->LDK; p.jobs = pl->jobs;
   GP_TRY_RC(c->ws.take(c, (size_t)pl->part_tiles * TILE * TILE, "phase 1 (p1v2)", &p.part));
   GP_EV(c, 10);
-  if (pl->nby == 8) hipLaunchKernelGGL((p1v2_kernel<8>), dim3(pl->blocks), dim3(512), 0, c->stream, p);
-  else hipLaunchKernelGGL((p1v2_kernel<26>), dim3(pl->blocks), dim3(512), 0, c->stream, p);
+  if (pl->nby == 8) GP_LAUNCH(c, c->stream, (p1v2_kernel<8>), dim3(pl->blocks), dim3(512), 0, p);
+  else GP_LAUNCH(c, c->stream, (p1v2_kernel<26>), dim3(pl->blocks), dim3(512), 0, p);
   GP_EV(c, 11);
-  GP_HIP(c, hipGetLastError());
   double* Psi2 = c->stats;
   double* C = c->stats + (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(p1v2_reduce_kernel, dim3(TILE * TILE / 32, pl->nouts), dim3(256), 0, c->stream, p.part, pl->outs, Psi2, C, c->Mp, c->Dp,
-                     c->sumYY, c->sf2 * (double)c->N, (double)c->N, C + (long)c->Mp * c->Dp);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, p1v2_reduce_kernel, dim3(TILE * TILE / 32, pl->nouts), dim3(256), 0, p.part, pl->outs, Psi2, C, c->Mp, c->Dp,
+            c->sumYY, c->sf2 * (double)c->N, (double)c->N, C + (long)c->Mp * c->Dp);
   return GP_OK;
 }
 

@@ -292,8 +292,7 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
   const long ldg = Dp + 2 * Mp;
   const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
   if (unc && var) {
-    hipLaunchKernelGGL(pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, st, c->gstep.Inv, (int)M, (int)Mp, u->B);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, c->gstep.Inv, (int)M, (int)Mp, u->B);
   }
   double* out_mean = p.out;
   double* out_var = p.out + R * D;
@@ -303,46 +302,40 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
     double* sin = p.in + R * Q;
     GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
     if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, cnt,
-                       rows, (int)Q, c->sf2, p.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, cnt,
+              rows, (int)Q, c->sf2, p.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
     GP_TRY_RC(launch_psi1_rows(c, p.mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
     // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
     GemmP g;
     g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
     g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = ldg;
     g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
-    launch_gemm(st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g);
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g));
     if (!unc) {
       if (var) {
         g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.G + Dp;
-        launch_gemm(st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g);
+        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g));
       }
-      GP_HIP(c, hipGetLastError());
-      hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
-                         c->sf2, noise, out_mean, out_var);
-      GP_HIP(c, hipGetLastError());
+      GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
+                c->sf2, noise, out_mean, out_var);
       if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       if (var) GP_HIP(c, hipMemcpyAsync(var + n0, out_var, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
     } else {
-      GP_HIP(c, hipGetLastError());
       if (mean) {
-        hipLaunchKernelGGL(pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, st, p.G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
-                           c->sf2, noise, out_mean, out_var);
-        GP_HIP(c, hipGetLastError());
+        GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
+                  c->sf2, noise, out_mean, out_var);
         GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
       if (var) {
-        hipLaunchKernelGGL(pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, st, p.mu, u->W, u->V2,
-                           u->lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, u->LEA);
+        GP_LAUNCH(c, st, pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, p.mu, u->W, u->V2,
+                  u->lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, u->LEA);
         PsiWArgs a;
         a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->gstep.E; a.B = u->B; a.G = p.G; a.ldg = ldg;
         a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;
         const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
-        if (Q <= 16) hipLaunchKernelGGL(pred_psi2w_kernel<16>, grid, dim3(256), 0, st, a);
-        else if (Q <= 64) hipLaunchKernelGGL(pred_psi2w_kernel<64>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(pred_psi2w_kernel<0>, grid, dim3(256), 0, st, a);
-        GP_HIP(c, hipGetLastError());
+        // the latent width the kernel keeps in registers: 16, 64, or (0) a run-time Q beyond
+        GP_TRY_RC((for_width<16, 64, 0>(c, "predictive variance kernel", Q <= 16 ? 16 : Q <= 64 ? 64 : 0,
+                                        [&](auto W) -> int { GP_LAUNCH(c, st, pred_psi2w_kernel<W()>, grid, dim3(256), 0, a); return GP_OK; })));
         GP_HIP(c, hipMemcpyAsync(var + n0 * D, out_var, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
     }

@@ -350,8 +350,7 @@ __global__ void __launch_bounds__(256) psi1_generic_kernel(const double* __restr
 // Psi1 of `n` points given as [mu | u | ln c1] tables of `rows` (a multiple of 64) rows into out[rows][ld] (columns >= M and rows >= n zero): the
 // generic kernel above on buffers the caller owns (gp_predict's chunks)
 int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld) {
-  hipLaunchKernelGGL(psi1_generic_kernel, dim3(c->Mp / 128, (unsigned)(rows / 64)), dim3(256), 0, c->stream, mu, U, lnc1, c->Z, out, n, rows, c->M, c->Q, ld);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, psi1_generic_kernel, dim3(c->Mp / 128, (unsigned)(rows / 64)), dim3(256), 0, mu, U, lnc1, c->Z, out, n, rows, c->M, c->Q, ld);
   return GP_OK;
 }
 
@@ -467,56 +466,57 @@ bool p2_wide_fixed_mode(const gp_ctx* c);
 int run_upload_y(gp_ctx* c, const double* dY) {
   const long total = c->Np * (long)c->Dp;
   const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
-  hipLaunchKernelGGL(copy_y_kernel, dim3(blocks), dim3(256), 0, c->stream, dY, c->Kaug, (long)c->N, (long)c->Np, c->D, c->Dp, c->Mp,
-                     (long)c->LDK);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, copy_y_kernel, dim3(blocks), dim3(256), 0, dY, c->Kaug, (long)c->N, (long)c->Np, c->D, c->Dp, c->Mp,
+            (long)c->LDK);
   return GP_OK;
 }
 
 template <int QP>
-static void launch_psi1(gp_ctx* c, bool fixa) {
+static int launch_psi1(gp_ctx* c, bool fixa) {
   const int WC = c->Mp >= 512 ? 4 : (c->Mp >= 256 ? 2 : 1);
   // 16-row groups per workgroup: 512 rows on large shards (still >= 7 workgroups per CU at N = 1e6), 128 rows below 2^17 rows (64-row workgroups on
   // configs[1]'s 1e5 x 128 shard -- every workgroup resident at once -- changed nothing: 43-44 us, r05)
   const int ngrp = c->Np >= (1L << 17) ? 32 : 8;
   const int nblk = ngrp;
-  static const int temporal_env = [] { const char* e = getenv("GPARML_PSI1_TEMPORAL"); return e ? atoi(e) : -1; }();
+  static const int temporal_env = env_int("GPARML_PSI1_TEMPORAL", -1);
   const int temporal = temporal_env >= 0 ? temporal_env : ((size_t)c->Np * c->LDK * sizeof(double) <= ((size_t)200 << 20) ? 1 : 0);
   dim3 grid((c->Mp + 128 * WC - 1) / (128 * WC), (unsigned)((c->Np / 16 + ngrp - 1) / ngrp));
   if constexpr (QP <= 16) if (fixa && WC == 4 && c->i8.active) {
     // int8 phase 1 (p1i8.hip): Psi1's digits are written next to Psi1 itself
     int8_t* Sl = nullptr; long strideJ = 0; double* Dpart = nullptr;
     if (p1i8_prepare(c, &Sl, &strideJ, &Dpart, (int)grid.y) == GP_OK) {
-      hipLaunchKernelGGL((psi1_kernel<QP, true, GP_I8_DIGITS>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                         (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk, Sl, strideJ, 0.5 / c->sf2, Dpart);
-      return;
+      GP_LAUNCH(c, c->stream, (psi1_kernel<QP, true, GP_I8_DIGITS>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+                (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk, Sl, strideJ, 0.5 / c->sf2, Dpart);
+      return GP_OK;
     }
     c->i8.active = false;
   }
   if (fixa)
   {
     if (temporal)
-      hipLaunchKernelGGL((psi1_kernel<QP, true, 0, true>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                         (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk);
+      GP_LAUNCH(c, c->stream, (psi1_kernel<QP, true, 0, true>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+                (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk);
     else
-      hipLaunchKernelGGL((psi1_kernel<QP, true>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                         (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk);
+      GP_LAUNCH(c, c->stream, (psi1_kernel<QP, true>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+                (long)c->LDK, WC, (const double*)c->alpha, log(c->sf2), nblk);
   }
   else
-    hipLaunchKernelGGL((psi1_kernel<QP, false>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                       (long)c->LDK, WC, (const double*)c->alpha, 0.0, nblk);
+    GP_LAUNCH(c, c->stream, (psi1_kernel<QP, false>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+              (long)c->LDK, WC, (const double*)c->alpha, 0.0, nblk);
+  return GP_OK;
 }
 
 template <int QP>
-static void launch_psi1_wide(gp_ctx* c, bool fixa) {
+static int launch_psi1_wide(gp_ctx* c, bool fixa) {
   const int nblk = c->Np >= (1L << 17) ? 4 : 1;
   dim3 grid((c->Mp + 255) / 256, (unsigned)((c->Np / PSI1_ROWS + nblk - 1) / nblk));
   if (fixa)
-    hipLaunchKernelGGL((psi1_wide_kernel<QP, true>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                       (long)c->LDK, (const double*)c->alpha, log(c->sf2), nblk);
+    GP_LAUNCH(c, c->stream, (psi1_wide_kernel<QP, true>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+              (long)c->LDK, (const double*)c->alpha, log(c->sf2), nblk);
   else
-    hipLaunchKernelGGL((psi1_wide_kernel<QP, false>), grid, dim3(256), 0, c->stream, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
-                       (long)c->LDK, (const double*)c->alpha, 0.0, nblk);
+    GP_LAUNCH(c, c->stream, (psi1_wide_kernel<QP, false>), grid, dim3(256), 0, c->PU, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q,
+              (long)c->LDK, (const double*)c->alpha, 0.0, nblk);
+  return GP_OK;
 }
 
 int P1Tiles::alloc(gp_ctx* c) {
@@ -543,9 +543,8 @@ int run_prep_and_generate(gp_ctx* c) {
   // upload / mode switch; Psi1 then takes alpha and sf2 as arguments (psi1_kernel<QP, true>).
   const bool fixa = a.fixedA && a.PU != nullptr;
   if (!(fixa && c->prep_fixa_valid)) {
-    hipLaunchKernelGGL(prep_elem_kernel, dim3((unsigned)std::min<long>((c->Np * c->Q + 255) / 256, 16384)), dim3(256), 0, c->stream, a);
-    hipLaunchKernelGGL(prep_row_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, c->stream, a);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, prep_elem_kernel, dim3((unsigned)std::min<long>((c->Np * c->Q + 255) / 256, 16384)), dim3(256), 0, a);
+    GP_LAUNCH(c, c->stream, prep_row_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, a);
   }
   c->prep_fixa_valid = fixa;
   c->i8.active = fixa && p1i8_applicable(c);     // decided per evaluation (gp_debug_set_option("p1_i8", ...) switches it at run time)
@@ -556,30 +555,19 @@ int run_prep_and_generate(gp_ctx* c) {
   // wider latent spaces (when measured: N = 1e6, M = 512, Q = 30: 2.70 -> 1.89 ms).  The int8 digits (launch_psi1) stay tied to `fixa` through c->i8.active.
   const bool kfix = c->regime_A && a.PU != nullptr;
   if (QP > 16) {
-    switch (QP) {
-      case 24: launch_psi1<24>(c, kfix); break;       // two columns per lane as long as 4 QP registers of z fit (psi1_wide_kernel's comment)
-      case 32: launch_psi1<32>(c, kfix); break;
-      case 52: launch_psi1_wide<52>(c, kfix); break;
-      default: launch_psi1_wide<64>(c, kfix); break;
-    }
+    // two columns per lane as long as 4 QP registers of z fit (psi1_wide_kernel's comment)
+    GP_TRY_RC((for_width<24, 32, 52, 64>(c, "wide Psi1 kernel", QP, [&](auto W) {
+      if constexpr (W() <= 32) return launch_psi1<W()>(c, kfix);
+      else return launch_psi1_wide<W()>(c, kfix);
+    })));
   } else if (QP > 0) {
-    switch (QP) {
-      case 2: launch_psi1<2>(c, kfix); break;
-      case 4: launch_psi1<4>(c, kfix); break;
-      case 6: launch_psi1<6>(c, kfix); break;
-      case 8: launch_psi1<8>(c, kfix); break;
-      case 10: launch_psi1<10>(c, kfix); break;
-      case 12: launch_psi1<12>(c, kfix); break;
-      case 14: launch_psi1<14>(c, kfix); break;
-      default: launch_psi1<16>(c, kfix); break;
-    }
+    GP_TRY_RC((for_width<2, 4, 6, 8, 10, 12, 14, 16>(c, "Psi1 kernel", QP, [&](auto W) { return launch_psi1<W()>(c, kfix); })));
   } else {
     dim3 grid(c->Mp / 128, (unsigned)(c->Np / 64));
-    hipLaunchKernelGGL(psi1_generic_kernel, grid, dim3(256), 0, c->stream, c->mu, c->U, c->lnc1, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M,
-                       c->Q, (long)c->LDK);
+    GP_LAUNCH(c, c->stream, psi1_generic_kernel, grid, dim3(256), 0, c->mu, c->U, c->lnc1, c->Z, c->Kaug, (long)c->N, (long)c->Np, c->M,
+              c->Q, (long)c->LDK);
   }
   GP_EV(c, 9);
-  GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 
@@ -598,9 +586,8 @@ int run_phase1(gp_ctx* c) {
       if (rc64 != GP_OK) return rc64;
       return p1i8_check_compare(c);
     }
-    hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
-                       1, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, p1_scalars_kernel, dim3(1), dim3(256), 0, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
+              1, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
     return GP_OK;
   }
   if (p1v2_applicable(c)) {
@@ -653,16 +640,13 @@ int run_phase1(gp_ctx* c) {
   p.bmap = c->p1t.bmap;
   const int blocks = c->p1t.bmap_blocks;
   GP_EV(c, 10);
-  hipLaunchKernelGGL(p1_kernel8, dim3(blocks), dim3(512), 0, c->stream, p);
+  GP_LAUNCH(c, c->stream, p1_kernel8, dim3(blocks), dim3(512), 0, p);
   GP_EV(c, 11);
-  GP_HIP(c, hipGetLastError());
   double* Psi2 = c->stats;
   double* C = c->stats + (long)c->Mp * c->Mp;
-  hipLaunchKernelGGL(p1_reduce_kernel, dim3(TILE * TILE / 256, T), dim3(256), 0, c->stream, p.part, p.tiles, T, S, Psi2, C, c->Mp, c->Dp);
-  GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(p1_scalars_kernel, dim3(1), dim3(256), 0, c->stream, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
-                     c->regime_A ? 1 : 0, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, p1_reduce_kernel, dim3(TILE * TILE / 256, T), dim3(256), 0, p.part, p.tiles, T, S, Psi2, C, c->Mp, c->Dp);
+  GP_LAUNCH(c, c->stream, p1_scalars_kernel, dim3(1), dim3(256), 0, c->p1t.klpart, c->p1t.kl_blocks, c->sumYY, c->sf2, (double)c->N,
+            c->regime_A ? 1 : 0, c->stats + (long)c->Mp * c->Mp + (long)c->Mp * c->Dp);
   return GP_OK;
 }
 
@@ -1322,7 +1306,7 @@ int run_phase2(gp_ctx* c) {
   const int blocks = 8 * ((S + 7) / 8) * p.MT;
   const int nrb = (c->Q + 1 + 3) / 4;                // fast path: feature columns [mu (Q) | 1] in groups of four
   p.prog = nullptr; p.prog_base = 0;
-  static const bool p2_sync = [] { const char* e = getenv("GPARML_P2_SYNC"); return !(e && e[0] == '0'); }();
+  static const bool p2_sync = env_flag("GPARML_P2_SYNC", true);
   // the in-step wait needs every workgroup of the launch resident at once: the grid is sized for two workgroups per CU on 256 CUs
   if (fast && p2_sync && p.MT > 1 && blocks <= 512) {
     if (!c->p2.p2prog) GP_TRY_RC(c->p2.p2prog.alloc(c, (size_t)(c->p2.p2_slices + 8) * p.MT, DA_ZERO));   // zero contract: bases only grow
@@ -1335,8 +1319,8 @@ int run_phase2(gp_ctx* c) {
   if (!g8dbg) GP_HIP(c, hipMalloc((void**)&g8dbg, (size_t)65536 * 64 * sizeof(long long)));
   p.dbg = g8dbg;
 #endif
-  if (ppath) hipLaunchKernelGGL((p2_gen8_kernel<true>), dim3(blocks), dim3(512), 0, c->stream, p);
-  if (widefix) hipLaunchKernelGGL((p2_gen8_kernel<false>), dim3(blocks), dim3(512), 0, c->stream, p);
+  if (ppath) GP_LAUNCH(c, c->stream, (p2_gen8_kernel<true>), dim3(blocks), dim3(512), 0, p);
+  if (widefix) GP_LAUNCH(c, c->stream, (p2_gen8_kernel<false>), dim3(blocks), dim3(512), 0, p);
 #ifdef GPARML_GEN8_TIMING
   if (ppath || widefix) {
     std::vector<long long> h((size_t)blocks * 64);
@@ -1352,36 +1336,29 @@ int run_phase2(gp_ctx* c) {
   if (fast) {                                        // nrb <= 3
     p.gapart = c->p2.hgpart;
     // (blocks past the last slice zero their own rows of hgpart)
-    switch (nrb) {
-      case 1: hipLaunchKernelGGL((p2_fast8_kernel<1>), dim3(blocks), dim3(512), 0, c->stream, p); break;
-      case 2: hipLaunchKernelGGL((p2_fast8_kernel<2>), dim3(blocks), dim3(512), 0, c->stream, p); break;
-      default: hipLaunchKernelGGL((p2_fast8_kernel<3>), dim3(blocks), dim3(512), 0, c->stream, p); break;
-    }
+    GP_TRY_RC((for_width<1, 2, 3>(c, "fast phase-2 kernel (groups of four feature columns)", nrb,
+                                  [&](auto W) -> int { GP_LAUNCH(c, c->stream, (p2_fast8_kernel<W()>), dim3(blocks), dim3(512), 0, p); return GP_OK; })));
   }
   GP_EV(c, 13);
-  GP_HIP(c, hipGetLastError());
   double* gZ = c->grads;
   double* ga = c->grads + (long)c->M * c->Q;
   // the global step's T2 is free once the step is enqueued: borrowed for the per-row alpha partials [M][Q] (GsState::T2)
-  hipLaunchKernelGGL(p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->stream, c->p2.Rpart, 2 * S, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
-                     c->alpha, fast ? 1 : (widefix ? 2 : 0), gZ, c->gstep.T2);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->p2.Rpart, 2 * S, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
+            c->alpha, fast ? 1 : (widefix ? 2 : 0), gZ, c->gstep.T2);
   if (ppath) {
     PtArgs a;
     a.HZp = c->p2.HZp; a.nparts = p.MT;            // p2_gen8_kernel: one partial array per 128 inducing columns
     a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CZp = c->CZp; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
     a.gmu = c->gXmu; a.gS = c->gXs; a.gapart = c->p2.gapart; a.regimeA = c->regime_A ? 1 : 0;
     a.pb = point_pb(c->CZp, c->Q);
-    hipLaunchKernelGGL(point_kernel, dim3(c->p2.ga_blocks), dim3(256), (size_t)(a.pb * (c->CZp + c->Q) + c->Q) * sizeof(double), c->stream, a);
-    GP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, c->p2.gapart, c->p2.ga_blocks, c->Q, c->Q, ga);
+    GP_LAUNCH(c, c->stream, point_kernel, dim3(c->p2.ga_blocks), dim3(256), (size_t)(a.pb * (c->CZp + c->Q) + c->Q) * sizeof(double), a);
+    GP_LAUNCH(c, c->stream, colsum2_kernel, dim3(c->Q), dim3(256), 0, c->gstep.T2, c->M, c->Q, c->p2.gapart, c->p2.ga_blocks, c->Q, c->Q, ga);
   } else if (widefix) {
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, (const double*)nullptr, 0, 0, c->Q, ga);
+    GP_LAUNCH(c, c->stream, colsum2_kernel, dim3(c->Q), dim3(256), 0, c->gstep.T2, c->M, c->Q, (const double*)nullptr, 0, 0, c->Q, ga);
   } else {
     const int hb = blocks * 8, hstride = 4 * nrb;    // one partial row of grad_alpha's mu^2 term per wave
-    hipLaunchKernelGGL(colsum2_kernel, dim3(c->Q), dim3(256), 0, c->stream, c->gstep.T2, c->M, c->Q, c->p2.hgpart, hb, hstride, c->Q, ga);
+    GP_LAUNCH(c, c->stream, colsum2_kernel, dim3(c->Q), dim3(256), 0, c->gstep.T2, c->M, c->Q, c->p2.hgpart, hb, hstride, c->Q, ga);
   }
-  GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 

@@ -355,8 +355,7 @@ __global__ void __launch_bounds__(256) psi2_pad_zero_kernel(double* __restrict__
 }
 int psi2_zero_pads(gp_ctx* c) {
   if (c->M == c->Mp) return GP_OK;
-  hipLaunchKernelGGL(psi2_pad_zero_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 1024)), dim3(256), 0, c->stream, c->stats, c->M, c->Mp);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, psi2_pad_zero_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 1024)), dim3(256), 0, c->stats, c->M, c->Mp);
   return GP_OK;
 }
 
@@ -725,8 +724,8 @@ void BPlanDelete::operator()(BPlan* p) const { delete p; }
 // the one place that picks them, once per plan.  Also the phase-2 slab count and psi2_sym_kernel's waves per workgroup, which the choice depends on.
 static void choose_b_path(const gp_ctx* c, BPlan& p) {
   // GPARML_B_PHASE2=tiles forces the tile-pair phase 2 below Q = 17 as well (tests: every compiled width); =cols keeps the VALU kernels where they exist (Q <= 16: the default)
-  static const bool force_tiles = [] { const char* e = getenv("GPARML_B_PHASE2"); return e && std::string(e) == "tiles"; }();
-  static const int maxq = [] { const char* e = getenv("GPARML_B_SYM_MAXQ"); return e ? atoi(e) : 12; }();     // 10: the column kernel at Q = 11, 12 (same-box A/B)
+  static const bool force_tiles = env_is("GPARML_B_PHASE2", "tiles");
+  static const int maxq = env_int("GPARML_B_SYM_MAXQ", 12);     // 10: the column kernel at Q = 11, 12 (same-box A/B)
   const int Q = c->Q;
   p.nslab = (c->M + 63) / 64;
   p.sym_nw = (p.nslab + 1) / 2;
@@ -825,55 +824,46 @@ int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn,
   BPlan& p = *c->bplan;
   const long total = (long)c->M * c->M * c->Q;
   if (!p.DZ2) GP_TRY_RC(p.DZ2.alloc(c, total, DA_RAW));
-  hipLaunchKernelGGL(dz2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, c->stream, c->Z, c->M, c->Q, p.DZ2);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, dz2_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, c->Z, c->M, c->Q, p.DZ2);
   *LE = p.LE; *le_il = le_interleaved(p.QB); *Vn = p.Vn; *DZ2 = p.DZ2;
   return GP_OK;
 }
 
 template <int QT, int CPL>
-static void launch_le(gp_ctx* c, const BPlan& p) {
+static int launch_le(gp_ctx* c, const BPlan& p) {
   dim3 grid((c->Mp + 256 * CPL - 1) / (256 * CPL), (unsigned)(c->Np / 16));
-  hipLaunchKernelGGL((b_le_kernel<QT, CPL>), grid, dim3(256), 0, c->stream, (const double*)p.MUP, (const double*)p.WP, (const double*)p.V2P,
-                     (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, c->M, c->Mp, p.LE, p.LET);
+  GP_LAUNCH(c, c->stream, (b_le_kernel<QT, CPL>), grid, dim3(256), 0, (const double*)p.MUP, (const double*)p.WP, (const double*)p.V2P,
+            (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, c->M, c->Mp, p.LE, p.LET);
+  return GP_OK;
 }
 
 int run_generate_b(gp_ctx* c) {
   GP_TRY_RC(ensure_bplan(c));
   const BPlan& p = *c->bplan;
-  hipLaunchKernelGGL(b_tables_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, c->stream, c->mu, c->S, c->alpha, (long)c->N, (long)c->Np, c->Q,
-                     c->sf2, p.Vn, p.Wn, p.lnc2h, p.V2P, p.QB, p.WP, p.MUP);
+  GP_LAUNCH(c, c->stream, b_tables_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, c->mu, c->S, c->alpha, (long)c->N, (long)c->Np, c->Q,
+            c->sf2, p.Vn, p.Wn, p.lnc2h, p.V2P, p.QB, p.WP, p.MUP);
   GP_HIP(c, hipMemcpyAsync(p.alphaP, c->alpha, (size_t)c->Q * 8, hipMemcpyDeviceToDevice, c->stream));
-  hipLaunchKernelGGL(zpad_kernel, dim3((unsigned)(((long)c->Mp * (p.QB + 6) + 255) / 256)), dim3(256), 0, c->stream, c->Z, c->M, c->Mp, c->Q, p.QB,
-                     p.ZP, p.Z1P, p.p2 == BP2::SYM ? p.Z1S.get() : nullptr, (p.QB + 1 + 3) / 4 * 4);
+  GP_LAUNCH(c, c->stream, zpad_kernel, dim3((unsigned)(((long)c->Mp * (p.QB + 6) + 255) / 256)), dim3(256), 0, c->Z, c->M, c->Mp, c->Q, p.QB,
+            p.ZP, p.Z1P, p.p2 == BP2::SYM ? p.Z1S.get() : nullptr, (p.QB + 1 + 3) / 4 * 4);
   if (p.p1 == BP1::GENERIC) return run_le_generic(c);
-  switch (p.QB) {
-    case 4: launch_le<4, 2>(c, p); break;
-    case 6: launch_le<6, 2>(c, p); break;
-    case 8: launch_le<8, 2>(c, p); break;
-    case 10: launch_le<10, 2>(c, p); break;
-    case 12: launch_le<12, 2>(c, p); break;
-    case 14: launch_le<14, 2>(c, p); break;
-    case 16: launch_le<16, 2>(c, p); break;
-    case 24: launch_le<24, 2>(c, p); break;
-    case 32: launch_le<32, 1>(c, p); break;
-    case 52: launch_le<52, 1>(c, p); break;
-    default: launch_le<64, 1>(c, p); break;
-  }
-  GP_HIP(c, hipGetLastError());
+  return for_width<4, 6, 8, 10, 12, 14, 16, 24, 32, 52, 64>(c, "regime-B LE table kernel", p.QB, [&](auto W) {
+    constexpr int CPL = W() <= 24 ? 2 : 1;     // columns per lane
+    return launch_le<W(), CPL>(c, p);
+  });
+}
+
+template <int QT>
+static int launch_pairs(gp_ctx* c, const BPlan& p, int S, double* part) {
+  GP_LAUNCH(c, c->stream, (psi2_pairs_kernel<QT>), dim3(p.n_ptiles, S), dim3(256), 0, p.LE, p.V2P, p.ZP, p.ptiles, (long)c->N,
+            c->Mp, S, part, p.n_ptiles);
   return GP_OK;
 }
 
 template <int QT>
-static void launch_pairs(gp_ctx* c, const BPlan& p, int S, double* part) {
-  hipLaunchKernelGGL((psi2_pairs_kernel<QT>), dim3(p.n_ptiles, S), dim3(256), 0, c->stream, p.LE, p.V2P, p.ZP, p.ptiles, (long)c->N,
-                     c->Mp, S, part, p.n_ptiles);
-}
-
-template <int QT>
-static void launch_pairs_mfma(gp_ctx* c, const BPlan& p, int S, double* part) {
-  hipLaunchKernelGGL((psi2_pairs_mfma_kernel<QT>), dim3(p.n_tiles64, S), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P,
-                     (const double*)p.ZP, (const int*)p.tiles64, (long)c->N, c->Mp, S, part, p.n_tiles64);
+static int launch_pairs_mfma(gp_ctx* c, const BPlan& p, int S, double* part) {
+  GP_LAUNCH(c, c->stream, (psi2_pairs_mfma_kernel<QT>), dim3(p.n_tiles64, S), dim3(256), 0, (const double*)p.LET, (const double*)p.V2P,
+            (const double*)p.ZP, (const int*)p.tiles64, (long)c->N, c->Mp, S, part, p.n_tiles64);
+  return GP_OK;
 }
 
 int run_phase1_b(gp_ctx* c) {
@@ -887,53 +877,36 @@ int run_phase1_b(gp_ctx* c) {
     // 64 x 64 tiles x n-slices: several rounds of workgroups over the 512 resident slots, >= 256 points per slice
     int S = (int)std::max<long>(1, std::min<long>(32, std::max<long>((2048 + p.n_tiles64 - 1) / p.n_tiles64, c->N / 4096)));
     S = (int)std::min<long>(S, std::max<long>(1, c->N / 256));
-    switch (p.QB) {
-      case 24: launch_pairs_mfma<24>(c, p, S, part); break;
-      case 32: launch_pairs_mfma<32>(c, p, S, part); break;
-      case 52: launch_pairs_mfma<52>(c, p, S, part); break;
-      default: launch_pairs_mfma<64>(c, p, S, part); break;
-    }
+    GP_TRY_RC((for_width<24, 32, 52, 64>(c, "regime-B MFMA pair kernel", p.QB, [&](auto W) { return launch_pairs_mfma<W()>(c, p, S, part); })));
     GP_EV(c, 11);
-    GP_HIP(c, hipGetLastError());
-    hipLaunchKernelGGL(psi2_reduce64_kernel, dim3(p.n_tiles64), dim3(256), 0, c->stream, part, p.tiles64, p.n_tiles64, S, c->M, c->Mp, c->stats);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, psi2_reduce64_kernel, dim3(p.n_tiles64), dim3(256), 0, part, p.tiles64, p.n_tiles64, S, c->M, c->Mp, c->stats);
     return psi2_zero_pads(c);
   }
   // n-slices: many more workgroups than resident slots (256 CUs x 7) so the last round is short, >= 1024 points per slice
   int S = (int)std::max<long>(1, std::min<long>(64, std::max<long>((4096 + p.n_ptiles - 1) / p.n_ptiles, c->N / 1024)));
   S = (int)std::min<long>(S, c->N);
-  switch (p.QB) {
-    case 4: launch_pairs<4>(c, p, S, part); break;
-    case 6: launch_pairs<6>(c, p, S, part); break;
-    case 8: launch_pairs<8>(c, p, S, part); break;
-    case 10: launch_pairs<10>(c, p, S, part); break;
-    case 12: launch_pairs<12>(c, p, S, part); break;
-    case 14: launch_pairs<14>(c, p, S, part); break;
-    case 16: launch_pairs<16>(c, p, S, part); break;
-    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B pair kernel: no instantiation for the latent table width %d", p.QB);
-  }
+  GP_TRY_RC((for_width<4, 6, 8, 10, 12, 14, 16>(c, "regime-B pair kernel", p.QB, [&](auto W) { return launch_pairs<W()>(c, p, S, part); })));
   GP_EV(c, 11);
-  GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(psi2_reduce_kernel, dim3(p.n_ptiles), dim3(256), 0, c->stream, part, p.ptiles, p.n_ptiles, S, c->M, c->Mp, c->stats);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, psi2_reduce_kernel, dim3(p.n_ptiles), dim3(256), 0, part, p.ptiles, p.n_ptiles, S, c->M, c->Mp, c->stats);
   return psi2_zero_pads(c);
 }
 
 template <int QT, bool KEEP>
-static void launch_cols(gp_ctx* c, const BPlan& p, const PB2Args& a) {     // (the Bbar argument: the row-interleaved table up to QT = 10, the plain one beyond)
+static int launch_cols(gp_ctx* c, const BPlan& p, const PB2Args& a) {     // (the Bbar argument: the row-interleaved table up to QT = 10, the plain one beyond)
   const int nw = std::min(4, p.nslab);
-  hipLaunchKernelGGL((psi2_cols_kernel<QT, KEEP>), dim3(p.pb_blocks, (p.nslab + nw - 1) / nw), dim3(64 * nw), 0, c->stream, a, (const double*)p.ZP,
-                     (const double*)(cols_b4(QT) ? p.Bbar4 : c->gstep.Bbar), (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
-                     (const double*)p.alphaP);
+  GP_LAUNCH(c, c->stream, (psi2_cols_kernel<QT, KEEP>), dim3(p.pb_blocks, (p.nslab + nw - 1) / nw), dim3(64 * nw), 0, a, (const double*)p.ZP,
+            (const double*)(cols_b4(QT) ? p.Bbar4 : c->gstep.Bbar), (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
+            (const double*)p.alphaP);
+  return GP_OK;
 }
 
 template <int QT>
 static int launch_sym(gp_ctx* c, const BPlan& p, const PB2Args& a) {
   const size_t smem = (size_t)c->Mp * sym_rs(QT) * sizeof(double);
   GP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(psi2_sym_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((psi2_sym_kernel<QT>), dim3(p.pb_blocks), dim3(64 * p.sym_nw), smem, c->stream, a, (const double*)p.ZP, (const double*)p.Z1S,
-                     (const double*)p.Bbar4, (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
-                     (const double*)p.alphaP, (const int*)p.sym_sched, p.sym_rounds);
+  GP_LAUNCH(c, c->stream, (psi2_sym_kernel<QT>), dim3(p.pb_blocks), dim3(64 * p.sym_nw), smem, a, (const double*)p.ZP, (const double*)p.Z1S,
+            (const double*)p.Bbar4, (const double*)p.LET, (const double*)p.V2P, (const double*)p.WP, (const double*)p.MUP,
+            (const double*)p.alphaP, (const int*)p.sym_sched, p.sym_rounds);
   return GP_OK;
 }
 
@@ -945,47 +918,37 @@ int run_phase2_b(gp_ctx* c) {
   a.Wn = p.Wn; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
   a.Gpart = p.Gpart; a.gapart2 = p.gapart2; a.gmu = c->gXmu; a.gS = c->gXs; a.pp = p.pp;
   a.N = c->N; a.Np = c->Np; a.M = c->M; a.Mp = c->Mp; a.Q = c->Q; a.QB = p.QB; a.nslab = p.nslab; a.ppb = p.ppb; a.ngrp = (p.nslab + std::min(4, p.nslab) - 1) / std::min(4, p.nslab);
-  if (!gen) hipLaunchKernelGGL(bbar_interleave_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 2048)), dim3(256), 0, c->stream,
-                               (const double*)c->gstep.Bbar, c->Mp, p.Bbar4);
+  if (!gen) GP_LAUNCH(c, c->stream, bbar_interleave_kernel, dim3((unsigned)std::min<long>(((long)c->Mp * c->Mp + 255) / 256, 2048)), dim3(256), 0,
+                      (const double*)c->gstep.Bbar, c->Mp, p.Bbar4);
   GP_EV(c, 12);   // gp_last_timings' "p2 kernel" slot: in regime B the T_n = Bbar o psi2_n kernel
   if (gen) {
     a.ngrp = 1;
     GP_TRY_RC(run_phase2_b_generic(c));
   } else if (p.p2 == BP2::SYM) {
     a.ngrp = p.sym_nw;
-    int rc = p.QB == 4 ? launch_sym<4>(c, p, a) : p.QB == 6 ? launch_sym<6>(c, p, a) : p.QB == 8 ? launch_sym<8>(c, p, a) : p.QB == 10 ? launch_sym<10>(c, p, a) : launch_sym<12>(c, p, a);
-    if (rc != GP_OK) return rc;
-  } else
-  switch (p.QB) {
-    case 4: launch_cols<4, true>(c, p, a); break;
-    case 6: launch_cols<6, true>(c, p, a); break;
-    case 8: launch_cols<8, true>(c, p, a); break;
+    GP_TRY_RC((for_width<4, 6, 8, 10, 12>(c, "regime-B symmetric kernel", p.QB, [&](auto W) { return launch_sym<W()>(c, p, a); })));
+  } else {
     // (the <10, false> form -- z re-read and grad_Z accumulated in memory per point -- is slower than <10, true>: same box, N = 1e5, M = 128: 2.75 -> 2.98 ms,
     // M = 1024 (5e4 points): 69.2 -> 69.9 ms; profiles/r06_gplvm_experiments.txt)
-    case 10: launch_cols<10, true>(c, p, a); break;
-    case 12: launch_cols<12, false>(c, p, a); break;
-    case 14: launch_cols<14, false>(c, p, a); break;
-    case 16: launch_cols<16, false>(c, p, a); break;
-    default: return fail(c, GP_ERR_UNSUPPORTED, "regime-B column kernel: no instantiation for the latent table width %d (Q = %d runs on psi2_tile_kernel)", p.QB, c->Q);
+    GP_TRY_RC((for_width<4, 6, 8, 10, 12, 14, 16>(c, "regime-B column kernel (wider tables run on psi2_tile_kernel)", p.QB, [&](auto W) {
+      constexpr bool KEEP = W() <= 10;
+      return launch_cols<W(), KEEP>(c, p, a);
+    })));
   }
   GP_EV(c, 13);
-  GP_HIP(c, hipGetLastError());
-  hipLaunchKernelGGL(psi2_points_finish_kernel, dim3((unsigned)std::min<long>(p.pb_blocks, 256)), dim3(256), 0, c->stream, a);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, psi2_points_finish_kernel, dim3((unsigned)std::min<long>(p.pb_blocks, 256)), dim3(256), 0, a);
   const long MQ = (long)c->M * c->Q;
   const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);      // psi2_points_finish_kernel's grid (one gapart2 row per workgroup)
   if (gen) {
     // grad_Z's psi2 part is in c->grads already: only the alpha partials of the points' finish are left
-    hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, p.Gtmp, p.gapart2, 0, fin_blocks, MQ,
-                       c->Q, c->grads);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, p.Gtmp, p.gapart2, 0, fin_blocks, MQ,
+              c->Q, c->grads);
     return GP_OK;
   }
   const int S2 = std::max(1, std::min(64, p.pb_blocks / 16));
-  hipLaunchKernelGGL(pb2_reduce1_kernel, dim3((unsigned)((MQ + 63) / 64), S2), dim3(256), 0, c->stream, p.Gpart, p.pb_blocks, MQ, S2, p.Gtmp);
-  hipLaunchKernelGGL(pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, c->stream, p.Gtmp,
-                     p.gapart2, S2, fin_blocks, MQ, c->Q, c->grads);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, pb2_reduce1_kernel, dim3((unsigned)((MQ + 63) / 64), S2), dim3(256), 0, p.Gpart, p.pb_blocks, MQ, S2, p.Gtmp);
+  GP_LAUNCH(c, c->stream, pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, p.Gtmp,
+            p.gapart2, S2, fin_blocks, MQ, c->Q, c->grads);
   return GP_OK;
 }
 

@@ -140,9 +140,8 @@ static int ensure_generic(gp_ctx* c) {
 
 int run_le_generic(gp_ctx* c) {
   const BPlan& p = *c->bplan;
-  hipLaunchKernelGGL(b_le_generic_kernel, dim3(grid_of(c->Np * c->Mp)), dim3(256), 0, c->stream, (const double*)p.MUP, (const double*)p.WP,
-                     (const double*)p.V2P, (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q, p.LE, p.LET);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, b_le_generic_kernel, dim3(grid_of(c->Np * c->Mp)), dim3(256), 0, (const double*)p.MUP, (const double*)p.WP,
+            (const double*)p.V2P, (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q, p.LE, p.LET);
   return GP_OK;
 }
 
@@ -154,12 +153,11 @@ int run_phase1_b_generic(gp_ctx* c) {
   GP_EV(c, 10);
   for (long n0 = 0; n0 < c->N; n0 += g.P) {
     const long cnt = std::min<long>(g.P, c->N - n0);
-    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
-                       (const double*)nullptr, n0, cnt, c->M, c->Mp, c->Q, g.T);
-    hipLaunchKernelGGL(psi2_sum_generic_kernel, dim3(grid_of(mm)), dim3(256), 0, c->stream, (const double*)g.T, cnt, c->M, c->Mp, n0 == 0 ? 1 : 0, c->stats);
+    GP_LAUNCH(c, c->stream, psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
+              (const double*)nullptr, n0, cnt, c->M, c->Mp, c->Q, g.T);
+    GP_LAUNCH(c, c->stream, psi2_sum_generic_kernel, dim3(grid_of(mm)), dim3(256), 0, (const double*)g.T, cnt, c->M, c->Mp, n0 == 0 ? 1 : 0, c->stats);
   }
   GP_EV(c, 11);
-  GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 
@@ -172,16 +170,15 @@ int run_phase2_b_generic(gp_ctx* c) {
   const int Q = c->Q, M = c->M;
   for (long n0 = 0; n0 < c->N; n0 += g.P) {
     const long cnt = std::min<long>(g.P, c->N - n0);
-    hipLaunchKernelGGL(psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, c->stream, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
-                       (const double*)c->gstep.Bbar, n0, cnt, M, c->Mp, Q, g.T);
-    hipLaunchKernelGGL(psi2_rt_generic_kernel, dim3(grid_of(cnt * M * (Q + 1))), dim3(256), 0, c->stream, (const double*)g.T, (const double*)p.ZP, cnt, M, Q,
-                       g.rt);
-    hipLaunchKernelGGL(psi2_pp_generic_kernel, dim3(grid_of(cnt * (3 * Q + 1))), dim3(256), 0, c->stream, (const double*)g.rt, (const double*)p.ZP, n0, cnt, M, Q,
-                       (long)c->Np, p.pp);
-    hipLaunchKernelGGL(psi2_gz_generic_kernel, dim3(grid_of((long)M * Q)), dim3(256), 0, c->stream, (const double*)g.rt, (const double*)p.ZP,
-                       (const double*)p.WP, (const double*)p.MUP, (const double*)p.alphaP, n0, cnt, M, Q, c->grads);
+    GP_LAUNCH(c, c->stream, psi2n_generic_kernel, dim3(grid_of(cnt * mm)), dim3(256), 0, (const double*)p.LET, (const double*)p.V2P, (const double*)p.ZP,
+              (const double*)c->gstep.Bbar, n0, cnt, M, c->Mp, Q, g.T);
+    GP_LAUNCH(c, c->stream, psi2_rt_generic_kernel, dim3(grid_of(cnt * M * (Q + 1))), dim3(256), 0, (const double*)g.T, (const double*)p.ZP, cnt, M, Q,
+              g.rt);
+    GP_LAUNCH(c, c->stream, psi2_pp_generic_kernel, dim3(grid_of(cnt * (3 * Q + 1))), dim3(256), 0, (const double*)g.rt, (const double*)p.ZP, n0, cnt, M, Q,
+              (long)c->Np, p.pp);
+    GP_LAUNCH(c, c->stream, psi2_gz_generic_kernel, dim3(grid_of((long)M * Q)), dim3(256), 0, (const double*)g.rt, (const double*)p.ZP,
+              (const double*)p.WP, (const double*)p.MUP, (const double*)p.alphaP, n0, cnt, M, Q, c->grads);
   }
-  GP_HIP(c, hipGetLastError());
   return GP_OK;
 }
 

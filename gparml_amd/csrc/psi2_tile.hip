@@ -440,7 +440,7 @@ template <int QT>
 static int launch_tile(gp_ctx* c, const PT2Args& a) {
   const size_t smem = std::max(pt2_lds_bytes<QT>(), (size_t)2 * 2 * 64 * QT * sizeof(double));
   GP_HIP(c, hipFuncSetAttribute(reinterpret_cast<const void*>(psi2_tile_kernel<QT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  hipLaunchKernelGGL((psi2_tile_kernel<QT>), dim3(a.T, a.S), dim3(512), smem, c->stream, a);
+  GP_LAUNCH(c, c->stream, (psi2_tile_kernel<QT>), dim3(a.T, a.S), dim3(512), smem, a);
   return GP_OK;
 }
 
@@ -484,26 +484,12 @@ int run_phase2_b_tiles(gp_ctx* c) {
   int k = 0;
   for (long n0 = 0; n0 < N; n0 += tb.ch, ++k) {
     a.n0 = n0; a.n1 = std::min(N, n0 + tb.ch); a.accumulate = k > 0 ? 1 : 0;
-    int rc = GP_OK;
-    switch (pt2_width(Q)) {
-      case 4: rc = launch_tile<4>(c, a); break;
-      case 8: rc = launch_tile<8>(c, a); break;
-      case 12: rc = launch_tile<12>(c, a); break;
-      case 16: rc = launch_tile<16>(c, a); break;
-      case 24: rc = launch_tile<24>(c, a); break;
-      case 32: rc = launch_tile<32>(c, a); break;
-      case 40: rc = launch_tile<40>(c, a); break;
-      case 52: rc = launch_tile<52>(c, a); break;
-      default: rc = launch_tile<64>(c, a); break;
-    }
-    if (rc != GP_OK) return rc;
-    GP_HIP(c, hipGetLastError());
+    GP_TRY_RC((for_width<4, 8, 12, 16, 24, 32, 40, 52, 64>(c, "regime-B tile-pair kernel", pt2_width(Q), [&](auto W) { return launch_tile<W()>(c, a); })));
     const long cnt = a.n1 - a.n0;
-    hipLaunchKernelGGL(pt2_sum_tiles_kernel, dim3((unsigned)std::min<long>(((long)PW * cnt + 255) / 256, 4096)), dim3(256), 0, c->stream, tb.ppt, T, PW,
-                       tb.ch, cnt);
+    GP_LAUNCH(c, c->stream, pt2_sum_tiles_kernel, dim3((unsigned)std::min<long>(((long)PW * cnt + 255) / 256, 4096)), dim3(256), 0, tb.ppt, T, PW,
+              tb.ch, cnt);
     f.n0 = a.n0; f.n1 = a.n1; f.accumulate = a.accumulate;
-    hipLaunchKernelGGL(pt2_points_finish_kernel, dim3(fin_blocks), dim3(256), 0, c->stream, f);
-    GP_HIP(c, hipGetLastError());
+    GP_LAUNCH(c, c->stream, pt2_points_finish_kernel, dim3(fin_blocks), dim3(256), 0, f);
   }
   GP_EV(c, 13);
 #ifdef GPARML_TILE_TIMING
@@ -521,9 +507,8 @@ int run_phase2_b_tiles(gp_ctx* c) {
   }
 #endif
   const long MQ = (long)c->M * Q;
-  hipLaunchKernelGGL(pt2_gz_reduce_kernel, dim3((unsigned)std::min<long>((MQ + Q + 255) / 256, 2048)), dim3(256), 0, c->stream, (const double*)tb.Gt,
-                     (const int*)p.tiles64, T, tb.S, c->M, Q, (const double*)p.gapart2, fin_blocks, c->grads);
-  GP_HIP(c, hipGetLastError());
+  GP_LAUNCH(c, c->stream, pt2_gz_reduce_kernel, dim3((unsigned)std::min<long>((MQ + Q + 255) / 256, 2048)), dim3(256), 0, (const double*)tb.Gt,
+            (const int*)p.tiles64, T, tb.S, c->M, Q, (const double*)p.gapart2, fin_blocks, c->grads);
   return GP_OK;
 }
 

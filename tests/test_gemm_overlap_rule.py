@@ -1,4 +1,4 @@
-"""The rule every internal matrix product is launched under (csrc/gemm.hip: launch_gemm aborts on a result that shares an element with an operand).  Round 6: the
+"""The rule every internal matrix product is launched under (csrc/gemm.hip: launch_gemm refuses, with GP_ERR_STATE and nothing launched, a result that shares an element with an operand).  Round 6: the
 blocked Cholesky's panel solve wrote its result over its own operand through 32 x 32 tiles -- a race visible only on the first evaluation of a fresh process
 (profiles/r06_first_evaluation_race.txt).  Host arithmetic: runs without a GPU."""
 import itertools
@@ -38,3 +38,18 @@ def test_windows_of_one_parent_matrix_against_brute_force():
 def test_different_leading_dimensions_fall_back_to_address_ranges():
     assert not meets(0, 16, 16, 64, 16 * 64, 16, 16, 16)         # disjoint ranges
     assert meets(0, 16, 16, 64, 8, 16, 16, 16)                   # ranges intersect: refused even if no element is shared (conservative)
+
+
+OPTIONS = ["dd_kipsi2", "refine_E", "p1_i8", "gs_tail", "i8_guard_strict", "xtx_tri", "residual_dd", "gemm_big", "trtri_rec", "gs_i8", "poison_alloc",
+           "predict_rows", "infer_rows", "kmeans_rows", "alloc_fail_after"]
+
+
+def test_an_unknown_option_is_refused_and_the_message_names_every_option():
+    """gp_debug_set_option's table (csrc/api.hip) is the one list of run-time switches: the message for a name outside it is generated from it.  No real
+    option is set here: there is no getter to restore one."""
+    lib = _lib.load()
+    assert lib.gp_debug_set_option(b"no_such_option", 1) == _lib.GP_ERR_BAD_ARG
+    msg = lib.gp_last_error(None).decode()
+    assert "no_such_option" in msg
+    listed = msg[msg.rindex("(") + 1:msg.rindex(")")].split(", ")
+    assert sorted(listed) == sorted(OPTIONS), msg

@@ -104,7 +104,7 @@ def test_rounding(la, lb, big):
 
 @pytest.mark.parametrize('name', sorted(G.refusal_cases()))
 def test_hook_refusals(name):
-    """everything that would reach launch_gemm's abort(), drop a k tail or leave a parent buffer is refused with GP_ERR_BAD_ARG, and gp_last_error says why"""
+    """everything that would reach launch_gemm's own refusals (GP_ERR_STATE), drop a k tail or leave a parent buffer is refused with GP_ERR_BAD_ARG, and gp_last_error says why"""
     from gparml_amd import _lib
     case, word = G.refusal_cases()[name]
     bufs = {p: np.full(length, 7.0) for p, length in case['parents'].items()}
