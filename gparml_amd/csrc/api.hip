@@ -768,6 +768,54 @@ extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K
   return run_kmeans(c, (long)n, X, K, centres, sums, counts, dist2, labels);
 }
 
+// The two passes of the PCA initialisation (csrc/pca.hip).  Nothing of the evaluation is read or written: only the Y columns of Kaug (Y == NULL) and
+// the plan's buffers.
+static bool all_finite(const double* x, size_t n) {
+  for (size_t i0 = 0; i0 < n; i0 += 4096) {
+    bool ok = true;
+    for (size_t i = i0, e = std::min(n, i0 + 4096); i < e; ++i) ok = ok && std::isfinite(x[i]);
+    if (!ok) return false;
+  }
+  return true;
+}
+static int pca_rows_check(gp_ctx* c, const char* who, int64_t n, const double* Y) {
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
+  if (!Y) {
+    if (!c->have_data) return fail(c, GP_ERR_STATE, "%s: Y is NULL (the resident Y) before gp_upload_shard", who);
+    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "%s: Y is NULL (the resident Y): n must be N_s = %ld, got %ld", who, (long)c->N, (long)n);
+  } else if (!all_finite(Y, (size_t)n * c->D)) {
+    return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite", who);
+  }
+  return GP_OK;
+}
+
+extern "C" int gp_scatter_accumulate(gp_ctx* c, int64_t n, const double* Y, const double* centre, double* sum, double* gram) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (!centre) return fail(c, GP_ERR_BAD_ARG, "gp_scatter_accumulate: centre is NULL");
+  GP_TRY(pca_rows_check(c, "gp_scatter_accumulate", n, Y));
+  if (!all_finite(centre, (size_t)c->D)) return fail(c, GP_ERR_BAD_ARG, "gp_scatter_accumulate: centre is not finite");
+  if (n == 0) {
+    if (sum) std::fill(sum, sum + c->D, 0.0);
+    if (gram) std::fill(gram, gram + (size_t)c->D * c->D, 0.0);
+    return GP_OK;
+  }
+  if (!sum && !gram) return GP_OK;
+  GP_HIP(c, hipSetDevice(c->device));
+  return run_scatter(c, (long)n, Y, centre, sum, gram);
+}
+
+extern "C" int gp_project_rows(gp_ctx* c, int64_t n, const double* Y, const double* mean, const double* P, int Q_out, double* X) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (Q_out < 1) return fail(c, GP_ERR_BAD_ARG, "gp_project_rows: Q_out must be >= 1");
+  if (!mean || !P) return fail(c, GP_ERR_BAD_ARG, "gp_project_rows: mean or P is NULL");
+  GP_TRY(pca_rows_check(c, "gp_project_rows", n, Y));
+  if (!all_finite(mean, (size_t)c->D) || !all_finite(P, (size_t)c->D * Q_out)) return fail(c, GP_ERR_BAD_ARG, "gp_project_rows: mean or P is not finite");
+  if (n == 0) return GP_OK;
+  if (!X) return fail(c, GP_ERR_BAD_ARG, "gp_project_rows: X is NULL");
+  GP_HIP(c, hipSetDevice(c->device));
+  return run_project(c, (long)n, Y, mean, P, Q_out, X);
+}
+
 // ---- final gradients ---------------------------------------------------------------------------------------------
 // final = Kmm parts (global step) + all-reduced data parts (phase 2)
 __global__ void add_kernel(const double* a, const double* b, double* out, long n) {

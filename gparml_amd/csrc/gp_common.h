@@ -75,12 +75,14 @@ struct BPlan;      // psi2_plan.h
 struct PredPlan;   // predict.hip
 struct InferPlan;  // infer.hip
 struct KmPlan;     // kmeans.hip
+struct PcaPlan;    // pca.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
 struct PredPlanDelete { void operator()(PredPlan* p) const; };
 struct InferPlanDelete { void operator()(InferPlan* p) const; };
 struct KmPlanDelete { void operator()(KmPlan* p) const; };
+struct PcaPlanDelete { void operator()(PcaPlan* p) const; };
 
 }  // namespace gp
 
@@ -240,6 +242,7 @@ struct gp_ctx {
   std::unique_ptr<gp::PredPlan, gp::PredPlanDelete> pred;     // gp_predict's buffers (predict.hip)
   std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip)
   std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip)
+  std::unique_ptr<gp::PcaPlan, gp::PcaPlanDelete> pca;       // gp_scatter_accumulate / gp_project_rows' buffers (pca.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -288,6 +291,9 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
               double* L, double* grad_mu, double* grad_S, int* iters);
 // kmeans.hip
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
+// pca.hip
+int run_scatter(gp_ctx* c, long n, const double* Y, const double* centre, double* sum, double* gram);
+int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const double* P, int Q, double* X);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip
@@ -311,7 +317,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
 extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
 extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip
 extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
-extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip
+extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }
 __host__ __device__ inline long le_index(bool il, long n, long m, long Mp) { return il ? ((((n >> 2) * Mp + m) << 2) + (n & 3)) : n * Mp + m; }

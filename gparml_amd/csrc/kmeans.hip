@@ -158,7 +158,7 @@ __global__ void __launch_bounds__(256) km_final_kernel(const double* __restrict_
   if (tid == 0) { dist[0] = first ? red[0] : dist[0] + red[0]; dist[1] = first ? red[256] : dist[1] + red[256]; }
 }
 
-// test hook (gp_debug_set_option "kmeans_rows"): rows per chunk, rounded up to KM_SEG; 0 = the default below
+// test hook (gp_debug_set_option "kmeans_rows"): rows per chunk, rounded up to KM_SEG; 0 = the default below (pca.hip reads the same switch)
 std::atomic<int> g_opt_km_rows{0};
 
 static long km_rows_for(const gp_ctx* c) {

@@ -325,9 +325,48 @@ class ShardEngine(object):
                  'gp_kmeans_accumulate')
         return sums, counts, dist2, labels
 
+    # ---- initialisation of the embeddings (gp_scatter_accumulate, gp_project_rows) --------------------------------
+    def _rows_arg(self, Y):
+        if Y is None:
+            return None, None, self.N_s
+        Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+        assert Y.ndim == 2 and Y.shape[1] == self.D, 'Y shape %s: (n, %d) expected' % (Y.shape, self.D)
+        Y, py = _lib.as_c(Y)
+        return Y, py, Y.shape[0]
+
+    def scatter_accumulate(self, centre, Y=None, want_gram=True):
+        """The PCA initialisation's accumulation pass over the host rows ``Y`` (n, D), or over the resident Y of this engine (``Y`` None): returns
+        (sum (D,), gram (D, D) or None) of the rows minus ``centre`` (D,), the centre subtracted before the products.  gram is bit-for-bit
+        symmetric; results are bit-identical from run to run and between host and resident rows; ``want_gram`` False skips the D^2 work and
+        returns the same sum.  Shards add; gparml_amd.init.pca drives the passes.  The evaluation state is left untouched."""
+        centre = np.asarray(centre, dtype=np.float64).reshape(-1)
+        assert centre.shape == (self.D,), 'centre shape %s: (%d,) expected' % (centre.shape, self.D)
+        centre, pc = _lib.as_c(centre)
+        Y, py, n = self._rows_arg(Y)
+        ssum = np.empty(self.D)
+        gram = np.empty((self.D, self.D)) if want_gram else None
+        self._ck(self.lib.gp_scatter_accumulate(self.h, n, py, pc, ssum.ctypes.data_as(_lib._dp), gram.ctypes.data_as(_lib._dp) if want_gram else None),
+                 'gp_scatter_accumulate')
+        return ssum, gram
+
+    def project_rows(self, mean, P, Y=None):
+        """(Y - mean) P for the host rows ``Y`` (n, D) or the resident Y (``Y`` None): P (D, Q_out) with any Q_out >= 1 (the caller folds 1 / std
+        into it); returns X (n, Q_out).  Rows are independent, bit for bit.  The resident X_mu is not written: ``upload_embeddings`` commits."""
+        mean = np.asarray(mean, dtype=np.float64).reshape(-1)
+        P = np.asarray(P, dtype=np.float64)
+        if P.ndim == 1:
+            P = P[:, None]
+        assert mean.shape == (self.D,) and P.ndim == 2 and P.shape[0] == self.D and P.shape[1] >= 1, 'mean %s, P %s' % (mean.shape, P.shape)
+        mean, pm = _lib.as_c(mean)
+        P, pp = _lib.as_c(P)
+        Y, py, n = self._rows_arg(Y)
+        X = np.empty((n, P.shape[1]))
+        self._ck(self.lib.gp_project_rows(self.h, n, py, pm, pp, P.shape[1], X.ctypes.data_as(_lib._dp)), 'gp_project_rows')
+        return X
+
     @property
     def n_rows(self):
-        """Rows ``kmeans_accumulate`` clusters with X None (init.kmeans draws its seeds over them)."""
+        """Rows ``kmeans_accumulate`` clusters with X None (init.kmeans draws its seeds over them) and ``scatter_accumulate`` sums with Y None."""
         return self.N_s
 
     def take_rows(self, idx):

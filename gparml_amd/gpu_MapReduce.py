@@ -88,7 +88,8 @@ def _streaming_pca(options, names):
     shifted by a provisional centre (the first shard's mean: keeps the later correction for the true mean small against the scatter);
     `eigh` of the D x D matrix gives the axes V and the variances lambda / N; pass 2 projects each shard, X_s = (Y_s - mean) V / sqrt(lambda / N).
     Identical to the SVD form up to the sign of a component (fixed here: the largest entry of every axis is positive) and rounding
-    (tests/test_init_against_reference.py: 1e-9 against the reference's own files).  Returns the per-shard projection."""
+    (tests/test_init_against_reference.py: 1e-9 against the reference's own files).  The eigen part is gparml_amd.init.pca_axes.  Returns the
+    per-shard projection."""
     Q = options['Q']
     n_tot, shift, ssum, gram = 0, None, None, None
     for name in names:
@@ -100,20 +101,8 @@ def _streaming_pca(options, names):
         n_tot += Y.shape[0]
         ssum += Yc.sum(axis=0)
         gram += Yc.T.dot(Yc)
-    delta = ssum / n_tot                                            # true mean - provisional centre
-    scatter = gram - n_tot * numpy.outer(delta, delta)
-    lam, V = numpy.linalg.eigh(scatter)
-    order = numpy.argsort(lam)[::-1][:Q]
-    lam, V = lam[order], V[:, order]
-    # rank-deficient data (Q beyond the rank of the centred data, or cancellation in the mean correction) leaves zero or slightly negative
-    # trailing eigenvalues: dividing by their root would write inf / nan embeddings without a word (the reference's SVD form divides by a
-    # tiny standard deviation in the same case and returns noise)
-    floor = numpy.finfo(float).eps * max(float(lam[0]), 0.0) * scatter.shape[0]
-    if not (lam[-1] > floor):
-        raise numpy.linalg.LinAlgError('PCA initialisation: the data has fewer than Q = %d principal directions (eigenvalue %d of the scatter '
-                                       'matrix is %.3e against a largest one of %.3e)' % (Q, int(numpy.sum(lam > floor)) + 1, lam[-1], lam[0]))
-    V = V * numpy.sign(V[numpy.argmax(numpy.abs(V), axis=0), numpy.arange(V.shape[1])])[None, :]
-    mean, std = shift + delta, numpy.sqrt(lam / n_tot)              # X.std(axis=0) of the projected data (ddof = 0)
+    from .init import pca_axes
+    mean, V, std = pca_axes(n_tot, shift, ssum, gram, Q)
 
     def project(name):
         return (_read_csv(options['input'] + '/' + name) - mean).dot(V) / std
@@ -121,11 +110,34 @@ def _streaming_pca(options, names):
     return project
 
 
+def _device_pca(options, names, lengths):
+    """options['init_X'] == 'device': the same PCA with the accumulation and projection passes on the GPUs the shards are spread over
+    (gparml_amd.init.pca) -- one temporary engine per device, each shard's rows passed from the host, each CSV parsed once per pass (the
+    mean, the scatter, the projection).  Returns the per-shard projection."""
+    from . import init as _init
+    D = _read_csv(options['input'] + '/' + names[0]).shape[1] if 'D' not in options else int(options['D'])
+    devices = _devices(options)
+    engines, parts = {}, []
+    try:
+        for i, (name, n) in enumerate(zip(names, lengths)):
+            dev = devices[i % len(devices)]                                              # where the shard will live (_device_of)
+            if dev not in engines:
+                engines[dev] = ShardEngine(1, D, 1, 1, device=dev)                       # the rows come from the host: only D counts
+            parts.append(_init.HostY(engines[dev], lambda name=name: _read_csv(options['input'] + '/' + name), n_rows=n))
+        X = _init.pca(parts, options['Q'])[3]
+    finally:
+        for e in engines.values():
+            e.close()
+    X = dict(zip(names, X))
+    return lambda name: X[name]
+
+
 def init(options):
     """local_MapReduce.init (local_MapReduce.py:27-104): count the points; create embeddings / variances unless
     loading or using fixed embeddings.  The PCA / random initialisation is one-off host preprocessing (out of the hot
     path); PCA streams over the shards (_streaming_pca: per-shard D x D scatter sums + eigh) instead of concatenating all data on one
-    host; PPCA / FA initialisers of supporting_functions.py are not provided."""
+    host, or, with ``options['init_X'] == 'device'``, with its passes over the rows on the GPUs of ``options['devices']`` (_device_pca);
+    PPCA / FA initialisers of supporting_functions.py are not provided."""
     names = sorted(os.listdir(options['input'] + '/'))
     lengths = []
     for name in names:
@@ -135,7 +147,7 @@ def init(options):
     if not options['fixed_embeddings'] and not options['load']:
         if options['init'] == 'PCA':
             X = None
-            project = _streaming_pca(options, names)
+            project = _device_pca(options, names, lengths) if options.get('init_X') == 'device' else _streaming_pca(options, names)
         elif options['init'] == 'random':
             X = numpy.random.randn(options['N'], options['Q'])
             project = None

@@ -1,10 +1,16 @@
-"""Placing the M inducing points: k-means over the embeddings of ALL shards, the assignment passes on the device.
+"""The two initialisations on the device: the k-means that places the inducing points, and the PCA that turns Y into the starting embeddings.
 
-``parallel_GPLVM.init_statistics`` calls ``scipy.cluster.vq.kmeans(embeddings, M)`` on the host, over the first shards that reach M rows
+k-means.  ``parallel_GPLVM.init_statistics`` calls ``scipy.cluster.vq.kmeans(embeddings, M)`` on the host, over the first shards that reach M rows
 (parallel_GPLVM.py:179-186).  A pass of that loop is N K Q distance terms -- an hour of host time at N = 1e6, M = 512 with scipy's twenty
 restarts -- and it has the map-reduce shape of an evaluation: every shard yields per-centre sums, counts and summed
 distances (``ShardEngine.kmeans_accumulate``, csrc/kmeans.hip), which add over shards and ranks.  ``kmeans`` here is scipy's ``_kmeans``
 loop restated on those sums: given the same seeds it returns what ``scipy.cluster.vq.kmeans(X_all, seeds, thresh=thresh)`` returns.
+
+PCA (the second half of this file).  ``supporting_functions.PCA`` (supporting_functions.py:102-121: left singular vectors of the centred data,
+each scaled to unit standard deviation) runs over ALL data (local_MapReduce.py:50-65: per-subset PCA "gives rise to rotation problems").  The
+same axes are the eigenvectors of the D x D scatter matrix, a SUM over shards and ranks: ``ShardEngine.scatter_accumulate`` (csrc/pca.hip) yields
+per shard the column sums and the Gram matrix of the rows shifted by a centre, ``pca_axes`` is the eigen part on the host,
+``ShardEngine.project_rows`` projects; ``pca`` drives the passes.
 """
 import numpy
 
@@ -120,3 +126,79 @@ def kmeans(parts, K, seeds=None, thresh=1e-5, max_iters=1000, restarts=1, rng=No
             best = run
     return best
 
+
+# ------------------------------------------------------------------------------------------------- PCA
+def pca_axes(n_tot, shift, ssum, gram, Q):
+    """The eigen part of the streaming PCA.  n_tot rows; ``ssum`` (D,) and ``gram`` (D, D) are the sums over all rows of (y - shift) and of
+    (y - shift)(y - shift)^T for a provisional centre ``shift`` (near the mean: the correction for the true mean then stays small against the
+    scatter).  Returns (mean (D,), V (D, Q), std (Q,)): the embeddings are (Y - mean) V / std, identical to supporting_functions.PCA's SVD form up
+    to the sign of a component (fixed here: the largest entry of every axis is positive) and rounding.  Raises LinAlgError when the data has fewer
+    than Q principal directions."""
+    delta = ssum / n_tot                                            # true mean - provisional centre
+    scatter = gram - n_tot * numpy.outer(delta, delta)
+    lam, V = numpy.linalg.eigh(scatter)
+    order = numpy.argsort(lam)[::-1][:Q]
+    lam, V = lam[order], V[:, order]
+    # rank-deficient data (Q beyond the rank of the centred data, or cancellation in the mean correction) leaves zero or slightly negative
+    # trailing eigenvalues: dividing by their root would write inf / nan embeddings without a word (the reference's SVD form divides by a
+    # tiny standard deviation in the same case and returns noise)
+    floor = numpy.finfo(float).eps * max(float(lam[0]), 0.0) * scatter.shape[0]
+    if not (lam[-1] > floor):
+        raise numpy.linalg.LinAlgError('PCA initialisation: the data has fewer than Q = %d principal directions (eigenvalue %d of the scatter '
+                                       'matrix is %.3e against a largest one of %.3e)' % (Q, int(numpy.sum(lam > floor)) + 1, lam[-1], lam[0]))
+    V = V * numpy.sign(V[numpy.argmax(numpy.abs(V), axis=0), numpy.arange(V.shape[1])])[None, :]
+    return shift + delta, V, numpy.sqrt(lam / n_tot)                # std: X.std(axis=0) of the projected data (ddof = 0)
+
+
+class HostY(object):
+    """A part of ``pca`` that passes host rows through an engine (any object with ShardEngine's ``scatter_accumulate`` / ``project_rows``).
+    ``Y``: the rows (n, D), or a callable returning them, called once per pass (a shard that is parsed from its file and not kept); ``n_rows`` is
+    then required."""
+
+    def __init__(self, engine, Y, n_rows=None):
+        self.engine = engine
+        self._Y = Y if callable(Y) else numpy.ascontiguousarray(numpy.atleast_2d(Y), dtype=numpy.float64)
+        self.n_rows = int(n_rows) if callable(Y) else self._Y.shape[0]
+        self.D = engine.D
+
+    def _rows(self):
+        return self._Y() if callable(self._Y) else self._Y
+
+    def scatter_accumulate(self, centre, want_gram=True):
+        return self.engine.scatter_accumulate(centre, Y=self._rows(), want_gram=want_gram)
+
+    def project_rows(self, mean, P):
+        return self.engine.project_rows(mean, P, Y=self._rows())
+
+
+def pca(parts, Q, allreduce=None):
+    """PCA over the rows of all ``parts`` of all ranks.  Returns (mean (D,), V (D, Q), std (Q,), X): X the list of this rank's projected parts,
+    (Y_part - mean) V / std.
+
+    parts: objects with ``scatter_accumulate(centre, want_gram=True) -> (sum, gram)``, ``project_rows(mean, P) -> X``, ``n_rows`` and ``D``:
+    ShardEngines with resident data, or ``HostY(engine, Y)``.
+    allreduce: a function that sums a float64 vector over the ranks holding the other parts (None: this process holds them all).  Its result
+    is bit-identical on every rank, so every rank gets the same axes.  COLLECTIVE then: three calls, in this order.
+    Pass 1 sums the rows (centre 0) for the global mean; pass 2 accumulates sums and Gram matrix centred on that mean -- the centre is
+    subtracted before the products, so nothing cancels; pass 3 projects."""
+    parts = list(parts)
+    assert parts and int(Q) >= 1
+    D = int(parts[0].D)
+    red = allreduce if allreduce is not None else (lambda v: v)
+    acc = numpy.zeros(D + 1)
+    for p in parts:
+        acc[:D] += p.scatter_accumulate(numpy.zeros(D), want_gram=False)[0]
+        acc[D] += p.n_rows
+    acc = numpy.asarray(red(acc), dtype=numpy.float64)
+    n_tot = int(round(acc[D]))
+    assert n_tot >= 1, 'PCA initialisation: no rows'
+    centre = acc[:D] / n_tot
+    acc = numpy.zeros(D + D * D)
+    for p in parts:
+        ssum, gram = p.scatter_accumulate(centre)
+        acc[:D] += ssum
+        acc[D:] += gram.ravel()
+    acc = numpy.asarray(red(acc), dtype=numpy.float64)
+    mean, V, std = pca_axes(n_tot, centre, acc[:D], acc[D:].reshape(D, D), int(Q))
+    P = V / std
+    return mean, V, std, [p.project_rows(mean, P) for p in parts]

@@ -20,6 +20,8 @@ class ResidentModel(object):
         self.M, self.Q, self.D = M, Q, D
         self.fixed_embeddings, self.fixed_beta = fixed_embeddings, fixed_beta
         self.engines = []
+        # the variances as given, copied (N x Q doubles per shard on the host): init_X commits new means next to exactly what was uploaded
+        self._X_S = [np.array(X_S, dtype=np.float64) for (_, _, X_S) in shards]
         for (Y, X_mu, X_S) in shards:
             e = (engine_class or ShardEngine)(Y.shape[0], D, M, Q, device=device)
             e.set_timing(0)            # an optimiser does not read per-kernel device timings: no timing events on the stream
@@ -111,6 +113,18 @@ class ResidentModel(object):
         if self._dist is not None:
             kw.setdefault('dist_group', True if self.group is None else self.group)
         return init.kmeans(self.engines, self.M if K is None else int(K), **kw)
+
+    def init_X(self):
+        """Initial embeddings for this model by PCA over the resident Y of every shard of every rank (gparml_amd.init.pca on the engines, Y = None:
+        nothing is uploaded but the result): supporting_functions.PCA over ALL data, as the reference insists (local_MapReduce.py:50-65).  The
+        means of every shard are replaced (upload_embeddings) and keep the variances the model was built with.  Returns (mean (D,), V (D, Q),
+        std (Q,)): a new row y embeds as (y - mean) V / std.  COLLECTIVE across ranks, with this model's group: every rank gets the same axes."""
+        from . import init
+        mean, V, std, X = init.pca(self.engines, self.Q, allreduce=self._allreduce_vector if self._dist is not None else None)
+        for e, x, s in zip(self.engines, X, self._X_S):
+            e.upload_embeddings(x, s, xs_is_raw=not self.fixed_embeddings)
+        self.version += 1                   # the resident embeddings moved: cached statistics and reductions are stale
+        return mean, V, std
 
     def close(self):
         for e in self.engines:

@@ -212,6 +212,35 @@ int gp_infer_latent(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* cols
 int gp_kmeans_accumulate(gp_ctx* ctx, int64_t n, const double* X, int K, const double* centres,
                          double* sums, int64_t* counts, double* dist2, int32_t* labels);
 
+/* ---- initialisation of the embeddings --------------------------------------------------------------- */
+/* The two device passes of the PCA that turns Y into the starting X_mu: supporting_functions.PCA (supporting_functions.py:102-121) over ALL data
+ * (local_MapReduce.py:50-65) in its streaming form -- per shard the column sums and the Gram matrix of the rows shifted by a centre, which add
+ * over shards and ranks; the eigen part is the host's (gparml_amd/init.py: pca_axes, pca); then every row is projected on the axes.
+ *
+ * gp_scatter_accumulate: for the rows y_r (r < n) of width D (the context's D)
+ *   sum (D)     sum[d]     = sum_r (y_rd - centre_d)
+ *   gram (D,D)  gram[i][j] = sum_r (y_ri - centre_i)(y_rj - centre_j), the full row-major matrix.
+ * Y == NULL: the context's resident Y (n must equal N_s; GP_ERR_STATE before an upload); otherwise host rows (n,D), taken in chunks through the
+ * library's own buffers.  Either output may be NULL; gram == NULL skips the D^2 work (the sum-only pass with centre 0 finds the true mean), and
+ * sum carries the same bits with and without gram.  The centre (D) is subtracted from every element BEFORE the product (never Y^T Y - n c c^T:
+ * its cancellation is why there is a centre); padding rows and columns of the resident layout contribute exact zeros.  gram[i][j] and gram[j][i]
+ * carry the same bits: one triangle of 128 x 128 tiles is computed (FP64 matrix-core instructions) and mirrored.  Results are bit-identical from
+ * run to run, and host rows and resident rows give the same bits.  Summation order (csrc/pca.hip), a function of the row index, n and D alone:
+ * the rows are cut into slices of L = max(512, ceil(n / S) rounded up to 64) rows, S = min(512, 64 MB / (T x 128 KB)) with T the number of tile
+ * pairs ceil(D / 128) (ceil(D / 128) + 1) / 2; host chunks are multiples of L.  gram: inside a slice the rows go through the 4x4x4 FP64 MFMA in
+ * ascending order, four rows per instruction; sum: wave p of four adds the slice's rows p, p + 4, .. in ascending order and the four are added as
+ * (0 + 1) + (2 + 3).  Slices, then chunks, are added in ascending order.  No floating-point atomics.
+ *
+ * gp_project_rows: X[r][q] = sum_d (y_rd - mean_d) P[d][q], d ascending with one fused multiply-add per term; mean (D), P (D,Q_out) row-major
+ * (the caller folds 1/std into P), X host (n,Q_out); Q_out >= 1 is free of the context's Q.  A row's output never depends on the other rows: it
+ * is bit-identical alone, in a batch and across a chunk boundary.  Y as above.  The resident X_mu is not written (gp_upload_embeddings commits).
+ *
+ * Both: synchronous; the evaluation state is left untouched (gp_phase2 / gp_finish / gp_predict after them give bit-identical results).
+ * GP_ERR_BAD_ARG for n < 0, a NULL centre / mean / P, Q_out < 1, non-finite Y, centre, mean or P, a NULL X with n > 0, and Y == NULL with
+ * n != N_s; n = 0 writes zeros to sum and gram, nothing to X. */
+int gp_scatter_accumulate(gp_ctx* ctx, int64_t n, const double* Y, const double* centre, double* sum, double* gram);
+int gp_project_rows(gp_ctx* ctx, int64_t n, const double* Y, const double* mean, const double* P, int Q_out, double* X);
+
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
 /* set the reduced statistics from the host (partial_terms.set_local_statistics, partial_terms.py:54-61) */
