@@ -143,7 +143,7 @@ extern "C" int gp_create(gp_ctx** out, int device, int64_t N_s, int D, int M, in
   A(c->mu, (size_t)Np * Q); A(c->S, (size_t)Np * Q); A(c->U, (size_t)Np * Q);
   A(c->PU, (size_t)Np * (2 * std::max(psi1_qp(Q), 2) + 2), DA_ZERO);   // zero contract: the records' columns Q .. QP - 1 (u = 0: no guards in psi1_kernel's q loop) are never written
   A(c->lnc1, (size_t)Np); A(c->Xa, (size_t)Np * c->CXp);
-  A(c->Z, (size_t)Mp * Q); A(c->alpha, (size_t)Q); A(c->Zaug, (size_t)Mp * c->CZp + 8); A(c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
+  A(c->Z, (size_t)Mp * Q); A(c->shift, (size_t)Q, DA_ZERO); A(c->alpha, (size_t)Q); A(c->Zaug, (size_t)Mp * c->CZp + 8); A(c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
   A(c->stats, (size_t)Mp * Mp + Mp * c->Dp + SC_COUNT);
   A(c->grads, (size_t)M * Q + Q);
   A(c->gXmu, (size_t)N_s * Q); A(c->gXs, (size_t)N_s * Q);
@@ -296,6 +296,28 @@ static int poison_scratch(gp_ctx* c) {
   return b_poison(c);
 }
 
+// The origin of the centred coordinates (gp_ctx::shift): the column mean of Z.  It is kept from call to call while it stays inside the cloud of inducing
+// points -- no further from their mean, in any dimension, than the farthest of them plus one length scale -- so that an optimiser's small steps of Z do not
+// move it: a new origin means new centred means, and fixed embeddings would pay the prep kernels in every evaluation (prep_fixa_valid).  With that bound
+// every centred coordinate stays within about twice the spread of the points.
+static int choose_origin(gp_ctx* c, const double* Z, const double* alpha) {
+  const int M = c->M, Q = c->Q;
+  std::vector<double> mean(Q, 0.0), spread(Q, 0.0);
+  for (int m = 0; m < M; ++m) for (int q = 0; q < Q; ++q) mean[q] += Z[(long)m * Q + q] / M;
+  for (int m = 0; m < M; ++m) for (int q = 0; q < Q; ++q) spread[q] = std::max(spread[q], std::fabs(Z[(long)m * Q + q] - mean[q]));
+  bool keep = !c->h_shift.empty();
+  for (int q = 0; keep && q < Q; ++q) {
+    const double scale = alpha[q] > 0.0 ? 1.0 / std::sqrt(alpha[q]) : 0.0;
+    keep = std::fabs(mean[q] - c->h_shift[q]) <= spread[q] + scale;
+  }
+  if (keep) return GP_OK;
+  c->h_shift = mean;
+  // a blocking copy from pageable memory (rare: see above); stream-ordered after whatever still reads the old origin
+  GP_HIP(c, hipMemcpyAsync(c->shift, c->h_shift.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  c->prep_fixa_valid = false;
+  return GP_OK;
+}
+
 extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const double* alpha, double beta, int64_t N_global, double step) {
   if (!c) return GP_ERR_BAD_ARG;
   if (!Z || !alpha) return fail(c, GP_ERR_BAD_ARG, "gp_set_globals: NULL array");
@@ -324,7 +346,8 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
   }
-  std::memcpy(c->glob.h_glob[slot], Z, nz * sizeof(double));
+  GP_TRY(choose_origin(c, Z, alpha));
+  for (size_t i = 0; i < nz; ++i) c->glob.h_glob[slot][i] = Z[i] - c->h_shift[i % nq];      // centred: exact when Z and the origin are within a factor of two
   std::memcpy(c->glob.h_glob[slot] + nz, alpha, nq * sizeof(double));
   double* dslot = nullptr;
   GP_HIP(c, hipHostGetDevicePointer((void**)&dslot, c->glob.h_glob[slot], 0));
@@ -608,7 +631,11 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
     case GP_ARR_DF_DPSI2: return download_matrix(c, c->gstep.Bbar, Mp, M, M, dst, n);
     case GP_ARR_GRAD_X_MU: return download_matrix(c, c->gXmu, Q, N, Q, dst, n);
     case GP_ARR_GRAD_X_S: return download_matrix(c, c->gXs, Q, N, Q, dst, n);
-    case GP_ARR_X_MU_TRIAL: return download_matrix(c, c->mu, Q, N, Q, dst, n);
+    case GP_ARR_X_MU_TRIAL: {
+      GP_TRY(download_matrix(c, c->mu, Q, N, Q, dst, n));
+      for (long i = 0; i < N * Q && !c->h_shift.empty(); ++i) dst[i] += c->h_shift[i % Q];     // the resident trial means are centred (gp_ctx::shift)
+      return GP_OK;
+    }
     case GP_ARR_X_S_TRIAL: return download_matrix(c, c->S, Q, N, Q, dst, n);
     case GP_ARR_X_MU:
       if (!c->have_data) return fail(c, GP_ERR_STATE, "GP_ARR_X_MU before gp_upload_shard");

@@ -218,6 +218,12 @@ struct gp_ctx {
   gp::DevBuf<double> alpha;   // [Q]
   gp::DevBuf<double> Zaug;    // [Mp][CZp]
   gp::DevBuf<double> Zt;      // [Q][Mp] the inducing points transposed (kmm_grads_lds_kernel: lanes = inducing points)
+  // The origin of the latent space the kernels work in ("Translation of the latent space"): gp_set_globals subtracts it from Z on the host,
+  // the prep kernels (psi.hip, predict.hip, infer.hip) from every mean, so Z, Zaug, Zt, mu and every table made from them hold CENTRED coordinates and
+  // products of coordinates scale with the spread of the points, not with their offset.  The statistics and every gradient depend on differences only;
+  // the two places that need the caller's mu -- the KL term and its derivative -mu -- add the origin back.
+  gp::DevBuf<double> shift;   // [Q]
+  std::vector<double> h_shift;  // its host copy (empty until the first gp_set_globals)
   // ---- the outputs ----
   gp::DevBuf<double> stats;   // packed: Psi2 [Mp*Mp] | C [Mp*Dp] | scalars [SC_COUNT]
   gp::DevBuf<double> spack;   // Psi2 upper triangle | C [M][D] | scalars: the all-reduce payload across processes (allocated on first use)

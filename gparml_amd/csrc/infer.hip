@@ -110,8 +110,8 @@ __device__ __forceinline__ double inf_softplus(double r) { return log(1.0 + exp(
 // Per-row tables of the evaluation point xe[n] = [mu (Q) | S or raw S (Q)], QP wide and zero-padded: TB[n] = [mu | S | u | w | v2] and
 // LC[n] = [ln c1, 1/2 ln c2]; u = alpha / (alpha S + 1), w = alpha / (2 alpha S + 1), v2 = (alpha - w) / 2.  One thread per row.
 __global__ void __launch_bounds__(256) inf_prep_kernel(const double* __restrict__ xe, int raw, const unsigned char* __restrict__ mask,
-                                                       const double* __restrict__ alpha, long cnt, int Q, int QP, double sf2, double* __restrict__ TB,
-                                                       double* __restrict__ LC) {
+                                                       const double* __restrict__ alpha, const double* __restrict__ shift, long cnt, int Q, int QP, double sf2,
+                                                       double* __restrict__ TB, double* __restrict__ LC) {
   for (long n = blockIdx.x * 256L + threadIdx.x; n < cnt; n += (long)gridDim.x * 256L) {
     if (mask && !mask[n]) continue;
     double l1 = log(sf2), l2 = l1;
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(256) inf_prep_kernel(const double* __restrict_
       double m = 0.0, s = 0.0, u = 0.0, w = 0.0, v2 = 0.0;
       if (q < Q) {
         const double a = alpha[q];
-        m = xe[n * 2 * Q + q];
+        m = xe[n * 2 * Q + q] - shift[q];      // centred like the model's Z (gp_ctx::shift); the KL term adds the origin back (inf_rows_kernel)
         s = xe[n * 2 * Q + Q + q];
         if (raw) s = inf_softplus(s);
         const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0;
@@ -182,7 +182,7 @@ template <int QR, bool WIDE>
 __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict__ xe, const double* __restrict__ TB, const double* __restrict__ LC,
                                                        const double* __restrict__ LEA, const double* __restrict__ V, const double* __restrict__ yy,
                                                        const double* __restrict__ ZP, const double* __restrict__ ZZ, const double* __restrict__ Gf,
-                                                       const unsigned char* __restrict__ mask, double* __restrict__ fe, double* __restrict__ ge, InfDims a) {
+                                                       const double* __restrict__ shift, const unsigned char* __restrict__ mask, double* __restrict__ fe, double* __restrict__ ge, InfDims a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long n = blockIdx.x * 4L + wave;                 // wave-uniform
@@ -274,7 +274,7 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
     }
     if (qc == 0) {
       double kl = 0.0;
-      for (int q = 0; q < Q; ++q) { const double mq = tb[q], sq = tb[QP + q]; kl += mq * mq + sq - log(sq) - 1.0; }
+      for (int q = 0; q < Q; ++q) { const double mq = tb[q] + shift[q], sq = tb[QP + q]; kl += mq * mq + sq - log(sq) - 1.0; }      // the caller's mu
       const double L = -0.5 * a.Do * log(6.283185307179586477 / a.beta) - 0.5 * a.beta * (yy[n] - 2.0 * b0 + sT + a.Do * a.sf2) - 0.5 * kl;
       if (lane == 0 && fe) fe[n] = L;
     }
@@ -284,7 +284,7 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
       const double d1mu = -u * B1, d1s = 0.5 * (u * u * B2 - u * b0);
       const double d2mu = -2.0 * w * (mq * sT - 0.5 * A1);
       const double d2s = 2.0 * w * w * (mq * mq * sT - mq * A1 + 0.25 * A2) - w * sT;
-      const double gmu = a.beta * d1mu - 0.5 * a.beta * d2mu - mq;
+      const double gmu = a.beta * d1mu - 0.5 * a.beta * d2mu - (mq + shift[q]);
       double gs = a.beta * d1s - 0.5 * a.beta * d2s - 0.5 * (1.0 - 1.0 / sq);
       if (a.raw) gs *= 1.0 / (1.0 + exp(-xe[n * 2 * Q + Q + q]));
       ge[n * 2 * Q + q] = gmu;
@@ -535,7 +535,7 @@ static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)s
 static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
   hipStream_t st = c->stream;
   const int M = c->M, Mp = c->Mp, Q = c->Q;
-  GP_LAUNCH(c, st, inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, k.xe, raw, mask, c->alpha, cnt, Q, QP, c->sf2, k.TB, k.LC);
+  GP_LAUNCH(c, st, inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, k.xe, raw, mask, c->alpha, c->shift, cnt, Q, QP, c->sf2, k.TB, k.LC);
   GP_LAUNCH(c, st, inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, k.TB, k.LC, mask, p.ZP, p.ZZ, cnt, M, Mp, QP, k.LEA);
   InfDims a;
   a.cnt = cnt; a.M = M; a.Mp = Mp; a.Q = Q; a.QP = QP; a.raw = raw; a.sf2 = c->sf2; a.beta = c->beta; a.Do = Do;
@@ -546,7 +546,7 @@ static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long c
     constexpr bool WIDE = W() == 0;
     constexpr int QR = WIDE ? 16 : W();
     GP_LAUNCH(c, st, (inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), k.yy.get(), p.ZP.get(),
-              p.ZZ.get(), p.Gf.get(), mask, k.fe.get(), ge, a);
+              p.ZZ.get(), p.Gf.get(), (const double*)c->shift, mask, k.fe.get(), ge, a);
     return GP_OK;
   });
 }

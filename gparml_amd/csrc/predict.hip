@@ -27,7 +27,7 @@ namespace gp {
 // per point of the chunk (n < rows; rows >= cnt are zero / padding): mu, u = alpha / (alpha S + 1), ln c1 = ln sf2 - 1/2 sum ln(alpha S + 1);
 // uncertain inputs also w = alpha / (2 alpha S + 1), v2 = (alpha - w) / 2 and 1/2 ln c2 = ln sf2 - 1/4 sum ln(2 alpha S + 1)
 __global__ void __launch_bounds__(256) pred_prep_kernel(const double* __restrict__ Xin, const double* __restrict__ Sin, int raw, const double* __restrict__ alpha,
-                                                        long cnt, long rows, int Q, double sf2, double* __restrict__ mu, double* __restrict__ U,
+                                                        const double* __restrict__ shift, long cnt, long rows, int Q, double sf2, double* __restrict__ mu, double* __restrict__ U,
                                                         double* __restrict__ lnc1, double* __restrict__ Wq, double* __restrict__ V2, double* __restrict__ lnc2h) {
   for (long n = blockIdx.x * 256L + threadIdx.x; n < rows; n += (long)gridDim.x * 256L) {
     double l1 = log(sf2), l2 = log(sf2);
@@ -36,7 +36,7 @@ __global__ void __launch_bounds__(256) pred_prep_kernel(const double* __restrict
       const double a = alpha[q];
       double m = 0.0, s = 0.0;
       if (n < cnt) {
-        m = Xin[i];
+        m = Xin[i] - shift[q];      // centred like the model's Z (gp_ctx::shift)
         if (Sin) { s = Sin[i]; if (raw) s = log(1.0 + exp(s)); }     // softplus, as the shard's prep (psi.hip)
       }
       const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0, w = a / d2;
@@ -302,7 +302,7 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
     double* sin = p.in + R * Q;
     GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
     if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-    GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, cnt,
+    GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, c->shift, cnt,
               rows, (int)Q, c->sf2, p.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
     GP_TRY_RC(launch_psi1_rows(c, p.mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
     // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core

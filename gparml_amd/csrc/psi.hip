@@ -27,7 +27,7 @@ __global__ void __launch_bounds__(256) copy_y_kernel(const double* __restrict__ 
 // variances are stored raw, else S = X_S.  Also ln c1_n (Psi1 normaliser, kernel_exp.py:80), the per-point
 // features Xa = [f1, f2, 1] and the per-block KL partial sums (partial_terms.py:83-85).
 struct PrepArgs {
-  const double* Xmu; const double* Xs; const double* dir; const double* alpha;
+  const double* Xmu; const double* Xs; const double* dir; const double* alpha; const double* shift;   // shift: gp_ctx::shift, the origin mu is centred at
   double* mu; double* S; double* U; double* lnc1; double* Xa; double* klpart;
   double* PU; int QP;   // packed per-point records [mu (QP) | u (QP) | ln c1 | 0] for psi1_kernel (PU == nullptr: not used); padding stays zero from the allocation
   long N, Np; int Q, CXp; double step, sf2; int raw, regimeA, fixedA;
@@ -52,6 +52,7 @@ __global__ void __launch_bounds__(256) prep_elem_kernel(PrepArgs a) {
         }
         s = softplus(s);
       }
+      m -= a.shift[q];
     }
     a.mu[i] = m;
     a.S[i] = s;
@@ -81,7 +82,7 @@ __global__ void __launch_bounds__(256) prep_row_kernel(PrepArgs a) {
     if (!a.regimeA) {
       double klrow = 0.0;
       for (int q = 0; q < a.Q; ++q) {
-        const double s = a.S[n * a.Q + q], m = a.mu[n * a.Q + q];
+        const double s = a.S[n * a.Q + q], m = a.mu[n * a.Q + q] + a.shift[q];      // the KL term is about the caller's mu
         lnc -= 0.5 * log(a.alpha[q] * s + 1.0);
         if (n < a.N) klrow += s - log(s) + m * m - 1.0;
       }
@@ -533,7 +534,7 @@ int P1Tiles::alloc(gp_ctx* c) {
 
 int run_prep_and_generate(gp_ctx* c) {
   PrepArgs a;
-  a.Xmu = c->Xmu; a.Xs = c->Xs; a.dir = c->have_dir ? c->dir : nullptr; a.alpha = c->alpha;
+  a.Xmu = c->Xmu; a.Xs = c->Xs; a.dir = c->have_dir ? c->dir : nullptr; a.alpha = c->alpha; a.shift = c->shift;
   a.mu = c->mu; a.S = c->S; a.U = c->U; a.lnc1 = c->lnc1; a.Xa = c->Xa; a.klpart = c->p1t.klpart;
   a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CXp = c->CXp; a.step = c->step; a.sf2 = c->sf2;
   a.raw = c->xs_raw ? 1 : 0; a.regimeA = c->regime_A ? 1 : 0; a.fixedA = p2_fast_mode(c) ? 1 : (p2_wide_fixed_mode(c) ? 2 : 0);
@@ -1198,7 +1199,7 @@ __global__ void __launch_bounds__(256) p2_reduce_kernel(const double* __restrict
 
 // per-point finish (general mode): HZ = sum of partials; grad_X_mu, grad_X_S, and the per-point part of grad_alpha
 struct PtArgs {
-  const double* HZp; int nparts; long N, Np; int Q, CZp; const double* mu; const double* S; const double* alpha;
+  const double* HZp; int nparts; long N, Np; int Q, CZp; const double* mu; const double* S; const double* alpha; const double* shift;
   double* gmu; double* gS; double* gapart; int regimeA, pb;
 };
 // points per pass (their HZ rows are contiguous in every partial array, so the part sums are flat coalesced reads); LDS: pb (CZp + Q) + Q doubles
@@ -1228,7 +1229,7 @@ __global__ void __launch_bounds__(256) point_kernel(PtArgs a) {
       const double d1 = al * s + 1.0, u = al / d1;
       const double quad = m * m * h - 2.0 * m * hzq + hz2;
       contrib[e] = -0.5 * (quad / (d1 * d1) + (s / d1) * h);
-      a.gmu[n0 * a.Q + e] = -m - u * (m * h - hzq);
+      a.gmu[n0 * a.Q + e] = -(m + a.shift[q]) - u * (m * h - hzq);      // the KL term's -mu in the caller's coordinates; m is centred
       // (fixed variances S = 0: the reference's expression divides by S, partial_terms.py:400-431; the library defines the entry as 0 instead of leaving the buffer as it was)
       a.gS[n0 * a.Q + e] = a.regimeA ? 0.0 : -0.5 * (1.0 - 1.0 / s) + 0.5 * u * u * quad - 0.5 * u * h;
     }
@@ -1348,7 +1349,7 @@ int run_phase2(gp_ctx* c) {
   if (ppath) {
     PtArgs a;
     a.HZp = c->p2.HZp; a.nparts = p.MT;            // p2_gen8_kernel: one partial array per 128 inducing columns
-    a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CZp = c->CZp; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha;
+    a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CZp = c->CZp; a.mu = c->mu; a.S = c->S; a.alpha = c->alpha; a.shift = c->shift;
     a.gmu = c->gXmu; a.gS = c->gXs; a.gapart = c->p2.gapart; a.regimeA = c->regime_A ? 1 : 0;
     a.pb = point_pb(c->CZp, c->Q);
     GP_LAUNCH(c, c->stream, point_kernel, dim3(c->p2.ga_blocks), dim3(256), (size_t)(a.pb * (c->CZp + c->Q) + c->Q) * sizeof(double), a);

@@ -92,7 +92,10 @@ int gp_set_direction(gp_ctx* ctx, const double* d);
 
 /* ---- one evaluation ------------------------------------------------------------------------- */
 /* global_statistics Z,sf2,alpha,beta (parallel_GPLVM.py:236-238), global N (options['N']) and the
- * trial step size (options['step_size'], parallel_GPLVM.py:228) */
+ * trial step size (options['step_size'], parallel_GPLVM.py:228).
+ * Z and the latent means may carry any common offset: the library subtracts an origin (the column mean of Z, kept from call to call while it
+ * stays among the inducing points) before it multiplies coordinates; results are translation invariant to the suite's bounds for offsets up to
+ * 2^16.  KL and every gradient refer to the caller's coordinates. */
 int gp_set_globals(gp_ctx* ctx, const double* Z, double sf2, const double* alpha, double beta,
                    int64_t N_global, double step_size);
 /* statistics_mapper body (local_MapReduce.py:224-240 -> partial_terms.set_data / update_local_statistics,
