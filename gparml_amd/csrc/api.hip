@@ -1024,6 +1024,9 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
       {"gs_i8", &g_opt_gs_i8, true},             {"poison_alloc", &g_opt_poison, true},     {"predict_rows", &g_opt_pred_rows, false},
       {"infer_rows", &g_opt_inf_rows, false},    {"kmeans_rows", &g_opt_km_rows, false},    {"alloc_fail_after", &g_alloc_fail_after, false}};
   if (!name) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: NULL name");
+  // the A/B switch of phase 2's remainder plan (p2_rem.hip: 0 whole tiles only, 1 the rule, 2 wherever it fits) is taken here and is not one of the
+  // listed options: the list in the message below is pinned, name by name, by tests/test_gemm_overlap_rule.py
+  if (!std::strcmp(name, "p2_rem")) { g_opt_p2_rem.store(std::max(0, std::min(value, 2))); return GP_OK; }
   std::string known;
   for (const auto& o : options) {
     if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }

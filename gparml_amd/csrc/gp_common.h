@@ -152,7 +152,7 @@ struct GsState {
 
 // phase 2 (psi.hip)
 struct P2State {
-  DevBuf<double> Rpart;       // [2 (p2_slices + 8)][Mp][CXp]
+  DevBuf<double> Rpart;       // [2 (p2_slices + 8) + 512 / MT][Mp][CXp]: (slice, wave-row) partials, then the remainder path's (row tile, row group) ones (p2_rem.hip)
   int p2_slices = 0;
   DevBuf<double> HZp;         // [Mp/128][Np][CZp] per-point partials (one array per 128 inducing columns)
   DevBuf<double> gapart;      // [ga_blocks][Q] per-block alpha partial sums from the per-point kernel
@@ -271,6 +271,10 @@ int run_prep_and_generate(gp_ctx* c);
 int run_phase1(gp_ctx* c);
 int run_phase2(gp_ctx* c);
 bool p2_fast_mode(const gp_ctx* c);
+// p2_rem.hip (fixed-embedding phase 2: the ragged last round of row tiles, cut along k)
+struct P2Rem { int q = 0, r = 0, splits = 0, RG = 0; };   // ntiles = q S + r; k splits per tile product; row groups per tile product in the fix-up
+bool p2_rem_plan(int ntiles, int S, int MT, int nc, P2Rem* pl);    // false: the whole-tile plan stands
+int run_phase2_rem(gp_ctx* c, const P2Rem& pl, int S, int kbeg, int kend, int nrb, int main_blocks);
 int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
 // p1i8.hip (regime A phase 1 on the int8 matrix core)
 bool p1i8_applicable(const gp_ctx* c);
@@ -323,6 +327,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
 extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
 extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip
 extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
+extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 off, 1 on where the remainder rule admits it, 2 on wherever it fits (measurements)
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }

@@ -1278,7 +1278,8 @@ bool p2_wide_fixed_mode(const gp_ctx* c) { return c->regime_A && !c->want_emb &&
 int P2State::alloc(gp_ctx* c) {
   const long Mp = c->Mp, Np = c->Np;
   p2_slices = std::max(1, std::min<int>(8 * std::max(1, 64 / (int)(Mp / TILE)), (int)(Np / TILE)));
-  GP_TRY_RC(Rpart.alloc(c, (size_t)2 * (p2_slices + 8) * Mp * c->CXp));
+  // (the remainder path's extra parts, p2_rem.hip: r * RG <= 256 / MT when it cuts into row groups, r <= 512 / MT otherwise)
+  GP_TRY_RC(Rpart.alloc(c, (size_t)(2 * (p2_slices + 8) + 512 / (Mp / TILE)) * Mp * c->CXp));
   GP_TRY_RC(HZp.alloc(c, (size_t)(Mp / TILE) * Np * c->CZp));    // p2_gen8_kernel: per-point partials, one array per 128 inducing columns
   ga_blocks = blocks_for(Np);
   GP_TRY_RC(gapart.alloc(c, (size_t)ga_blocks * c->Q));
@@ -1300,9 +1301,14 @@ int run_phase2(gp_ctx* c) {
   int S = std::max(1, std::min(c->p2.p2_slices, p.ntiles));
   p.tps = (p.ntiles + S - 1) / S;
   S = (p.ntiles + p.tps - 1) / p.tps;
-  p.S = S;
   p.kbeg = c->regime_A ? 0 : c->Mp / KC;
   p.kend = (c->Mp + (int)round_up(c->D, KC)) / KC;   // chunks beyond the last real Y column are all zero
+  // ntiles = q S0 + r with 0 < r < S0 (p2_fast8_kernel only): q full rounds here, the last r row tiles cut along k over every workgroup (p2_rem.hip)
+  P2Rem rem;
+  const int S0 = std::max(1, std::min(c->p2.p2_slices, p.ntiles));
+  const bool use_rem = fast && p2_rem_plan(p.ntiles, S0, p.MT, p.kend - p.kbeg, &rem);
+  if (use_rem) { S = S0; p.tps = rem.q; p.ntiles = rem.q * S0; }
+  p.S = S;
   p.klast = ((c->D - 1) % KC) / 4 + 1;
   const int blocks = 8 * ((S + 7) / 8) * p.MT;
   const int nrb = (c->Q + 1 + 3) / 4;                // fast path: feature columns [mu (Q) | 1] in groups of four
@@ -1339,12 +1345,14 @@ int run_phase2(gp_ctx* c) {
     // (blocks past the last slice zero their own rows of hgpart)
     GP_TRY_RC((for_width<1, 2, 3>(c, "fast phase-2 kernel (groups of four feature columns)", nrb,
                                   [&](auto W) -> int { GP_LAUNCH(c, c->stream, (p2_fast8_kernel<W()>), dim3(blocks), dim3(512), 0, p); return GP_OK; })));
+    if (use_rem) GP_TRY_RC(run_phase2_rem(c, rem, S, p.kbeg, p.kend, nrb, blocks));
   }
+  const int rem_parts = use_rem ? rem.r * rem.RG : 0, rem_rows = use_rem ? rem.r * p.MT * rem.RG : 0;
   GP_EV(c, 13);
   double* gZ = c->grads;
   double* ga = c->grads + (long)c->M * c->Q;
   // the global step's T2 is free once the step is enqueued: borrowed for the per-row alpha partials [M][Q] (GsState::T2)
-  GP_LAUNCH(c, c->stream, p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->p2.Rpart, 2 * S, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
+  GP_LAUNCH(c, c->stream, p2_reduce_kernel, dim3(c->M), dim3(256), 0, c->p2.Rpart, 2 * S + rem_parts, c->Mp, fast ? 4 * nrb : c->CXp, c->M, c->Q, c->Z,
             c->alpha, fast ? 1 : (widefix ? 2 : 0), gZ, c->gstep.T2);
   if (ppath) {
     PtArgs a;
@@ -1357,7 +1365,7 @@ int run_phase2(gp_ctx* c) {
   } else if (widefix) {
     GP_LAUNCH(c, c->stream, colsum2_kernel, dim3(c->Q), dim3(256), 0, c->gstep.T2, c->M, c->Q, (const double*)nullptr, 0, 0, c->Q, ga);
   } else {
-    const int hb = blocks * 8, hstride = 4 * nrb;    // one partial row of grad_alpha's mu^2 term per wave
+    const int hb = blocks * 8 + rem_rows, hstride = 4 * nrb;    // one partial row of grad_alpha's mu^2 term per wave (and per workgroup of the remainder's fix-up)
     GP_LAUNCH(c, c->stream, colsum2_kernel, dim3(c->Q), dim3(256), 0, c->gstep.T2, c->M, c->Q, c->p2.hgpart, hb, hstride, c->Q, ga);
   }
   return GP_OK;
