@@ -144,8 +144,8 @@ extern "C" int gp_create(gp_ctx** out, int device, int64_t N_s, int D, int M, in
   A(c->PU, (size_t)Np * (2 * std::max(psi1_qp(Q), 2) + 2), DA_ZERO);   // zero contract: the records' columns Q .. QP - 1 (u = 0: no guards in psi1_kernel's q loop) are never written
   A(c->lnc1, (size_t)Np); A(c->Xa, (size_t)Np * c->CXp);
   A(c->Z, (size_t)Mp * Q); A(c->shift, (size_t)Q, DA_ZERO); A(c->alpha, (size_t)Q); A(c->Zaug, (size_t)Mp * c->CZp + 8); A(c->Zt, (size_t)Mp * Q);   // + 8: p2_gen8_kernel stages feature columns in groups of eight
-  A(c->stats, (size_t)Mp * Mp + Mp * c->Dp + SC_COUNT);
-  A(c->grads, (size_t)M * Q + Q);
+  A(c->stats, (size_t)stats_doubles(c));
+  A(c->grads, (size_t)grads_doubles(c));
   A(c->gXmu, (size_t)N_s * Q); A(c->gXs, (size_t)N_s * Q);
   A(c->red, 8192);
   // the stages (eager: an evaluation allocates nothing of theirs); the workspace's capacity needs the tile table
@@ -221,12 +221,10 @@ static int upload_embeddings(gp_ctx* c, const double* X_mu, const double* X_S, i
   }
   c->xs_raw = xs_is_raw != 0;
   c->regime_A = (!xs_is_raw) && all_zero;
-  c->prep_fixa_valid = false;
+  c->life.embeddings_changed();
   GP_HIP(c, hipMemcpyAsync(c->Xmu, X_mu, nq * 8, hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipMemcpyAsync(c->Xs, X_S, nq * 8, hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
-  c->state = 0;
-  c->gstep.pred_ok = false;
   return GP_OK;
 }
 
@@ -257,16 +255,14 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
   }
   if (rc != GP_OK) return rc;
   GP_TRY(upload_embeddings(c, X_mu, X_S, xs_is_raw));
-  c->have_data = true;
-  c->have_dir = false;
-  c->prep_fixa_valid = false;
+  c->life.data_uploaded();
   c->i8.reset();      // new data: Y's digits are stale and the int8 path is measured again (p1i8.hip, guard)
   return GP_OK;
 }
 
 extern "C" int gp_upload_embeddings(gp_ctx* c, const double* X_mu, const double* X_S, int xs_is_raw) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (!c->have_data) return fail(c, GP_ERR_STATE, "gp_upload_embeddings before gp_upload_shard");
+  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_upload_embeddings before gp_upload_shard");
   if (!X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "gp_upload_embeddings: NULL array");
   GP_HIP(c, hipSetDevice(c->device));
   return upload_embeddings(c, X_mu, X_S, xs_is_raw);
@@ -275,12 +271,10 @@ extern "C" int gp_upload_embeddings(gp_ctx* c, const double* X_mu, const double*
 extern "C" int gp_set_direction(gp_ctx* c, const double* d) {
   if (!c) return GP_ERR_BAD_ARG;
   GP_HIP(c, hipSetDevice(c->device));
-  if (!d) { c->have_dir = false; return GP_OK; }
+  if (!d) { c->life.direction_set(false); return GP_OK; }
   GP_HIP(c, hipMemcpyAsync(c->dir, d, (size_t)2 * c->N * c->Q * 8, hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
-  c->have_dir = true;
-  c->state = 0;
-  c->gstep.pred_ok = false;
+  c->life.direction_set(true);
   return GP_OK;
 }
 
@@ -298,7 +292,7 @@ static int poison_scratch(gp_ctx* c) {
 
 // The origin of the centred coordinates (gp_ctx::shift): the column mean of Z.  It is kept from call to call while it stays inside the cloud of inducing
 // points -- no further from their mean, in any dimension, than the farthest of them plus one length scale -- so that an optimiser's small steps of Z do not
-// move it: a new origin means new centred means, and fixed embeddings would pay the prep kernels in every evaluation (prep_fixa_valid).  With that bound
+// move it: a new origin means new centred means, and fixed embeddings would pay the prep kernels in every evaluation (Lifecycle::origin_moved).  With that bound
 // every centred coordinate stays within about twice the spread of the points.
 static int choose_origin(gp_ctx* c, const double* Z, const double* alpha) {
   const int M = c->M, Q = c->Q;
@@ -314,7 +308,7 @@ static int choose_origin(gp_ctx* c, const double* Z, const double* alpha) {
   c->h_shift = mean;
   // a blocking copy from pageable memory (rare: see above); stream-ordered after whatever still reads the old origin
   GP_HIP(c, hipMemcpyAsync(c->shift, c->h_shift.data(), (size_t)Q * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  c->prep_fixa_valid = false;
+  c->life.origin_moved();
   return GP_OK;
 }
 
@@ -356,15 +350,13 @@ extern "C" int gp_set_globals(gp_ctx* c, const double* Z, double sf2, const doub
   c->glob.glob_epoch[slot] = c->sync_epoch;                      // the slot may be rewritten once a later stream synchronisation has passed
   c->glob.glob_slot = slot ^ 1;
   c->sf2 = sf2; c->beta = beta; c->N_global = N_global; c->step = step;
-  c->have_globals = true;
-  c->state = 0;
-  c->gstep.pred_ok = false;
+  c->life.globals_set();
   return GP_OK;
 }
 
 extern "C" int gp_phase1(gp_ctx* c) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (!c->have_data || !c->have_globals) return fail(c, GP_ERR_STATE, "gp_phase1 needs gp_upload_shard and gp_set_globals first");
+  if (!c->life.can_phase1()) return fail(c, GP_ERR_STATE, "gp_phase1 needs gp_upload_shard and gp_set_globals first");
   GP_HIP(c, hipSetDevice(c->device));
   GP_EV(c, 0);
   GP_TRY(run_prep_and_generate(c));
@@ -373,16 +365,14 @@ extern "C" int gp_phase1(gp_ctx* c) {
   GP_TRY(run_phase1(c));
   if (!c->regime_A) GP_TRY(run_phase1_b(c));
   GP_EV(c, 2);
-  c->state = 1;
-  c->gstep.pred_ok = false;
-  c->spack_filled = false;
+  c->life.phase1_ran();
   return GP_OK;
 }
 
 extern "C" int gp_stats_buffer(gp_ctx* c, void** dev_ptr, int64_t* n) {
   if (!c) return GP_ERR_BAD_ARG;
   if (dev_ptr) *dev_ptr = c->stats;
-  if (n) *n = (int64_t)c->Mp * c->Mp + (int64_t)c->Mp * c->Dp + SC_COUNT;
+  if (n) *n = stats_doubles(c);
   return GP_OK;
 }
 
@@ -418,7 +408,6 @@ __global__ void __launch_bounds__(256) stats_unpack_kernel(const double* __restr
     if (spack_map(e, M, Mp, D, Dp, &k, &s0, &s1)) { const double v = pk[k]; stats[s0] = v; if (s1 >= 0) stats[s1] = v; }
   }
 }
-static int64_t spack_doubles(const gp_ctx* c) { return (int64_t)c->M * (c->M + 1) / 2 + (int64_t)c->M * c->D + SC_COUNT; }
 static int ensure_spack(gp_ctx* c) {
   if (!c->spack) GP_TRY(c->spack.alloc(c, spack_doubles(c), DA_ZERO));   // zero contract: gp_stats_packed_buffer hands it out before any pack
   return GP_OK;
@@ -433,18 +422,18 @@ extern "C" int gp_stats_packed_buffer(gp_ctx* c, void** dev_ptr, int64_t* n) {
 }
 static int stats_pack(gp_ctx* c, int unpack_) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (c->state < 1) return fail(c, GP_ERR_STATE, "gp_stats_pack / gp_stats_unpack before gp_phase1");
+  if (!c->life.has_stats()) return fail(c, GP_ERR_STATE, "gp_stats_pack / gp_stats_unpack before gp_phase1");
   GP_HIP(c, hipSetDevice(c->device));
   GP_TRY(ensure_spack(c));
   const long n = (long)c->M * c->M + (long)c->M * c->D + SC_COUNT;
   if (unpack_) {
-    c->gstep.pred_ok = false;
+    c->life.stats_unpacked();
     // the packed buffer only holds statistics after a pack (it is zero from its allocation): unpacking first would silently wipe phase 1's sums
-    if (!c->spack_filled) return fail(c, GP_ERR_STATE, "gp_stats_unpack before gp_stats_pack");
+    if (!c->life.packed_is_current()) return fail(c, GP_ERR_STATE, "gp_stats_unpack before gp_stats_pack");
     GP_LAUNCH(c, c->stream, stats_unpack_kernel, dim3(blocks_for(n)), dim3(256), 0, (const double*)c->spack, c->stats, c->M, c->Mp, c->D, c->Dp);
   } else {
     GP_LAUNCH(c, c->stream, stats_pack_kernel, dim3(blocks_for(n)), dim3(256), 0, (const double*)c->stats, c->spack, c->M, c->Mp, c->D, c->Dp);
-    c->spack_filled = true;
+    c->life.stats_packed();
   }
   return GP_OK;
 }
@@ -454,7 +443,7 @@ extern "C" int gp_stats_unpack(gp_ctx* c) { return stats_pack(c, 1); }
 extern "C" int gp_grads_buffer(gp_ctx* c, void** dev_ptr, int64_t* n) {
   if (!c) return GP_ERR_BAD_ARG;
   if (dev_ptr) *dev_ptr = c->grads;
-  if (n) *n = (int64_t)c->M * c->Q + c->Q;
+  if (n) *n = grads_doubles(c);
   return GP_OK;
 }
 
@@ -482,7 +471,7 @@ extern "C" int gp_debug_force_staging(int on) { g_force_staging = on != 0; retur
 extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int op) {
   if (!dst || !src) return GP_ERR_BAD_ARG;
   if (dst->M != src->M || dst->Q != src->Q || dst->D != src->D) return fail(dst, GP_ERR_BAD_ARG, "gp_buffer_combine: shape mismatch");
-  const long n = which == 0 ? (long)dst->Mp * dst->Mp + (long)dst->Mp * dst->Dp + SC_COUNT : (long)dst->M * dst->Q + dst->Q;
+  const long n = which == 0 ? stats_doubles(dst) : grads_doubles(dst);
   const double* from = which == 0 ? src->stats : src->grads;
   // the source context's work must have finished before its buffer is read from another stream / device
   if (src->stream != dst->stream || src->device != dst->device) {
@@ -498,19 +487,18 @@ extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int 
     from = dst->staging;
   }
   GP_LAUNCH(dst, dst->stream, combine_kernel, dim3(blocks_for(n)), dim3(256), 0, which == 0 ? dst->stats : dst->grads, from, n, op);
-  if (which == 0) dst->gstep.pred_ok = false;
-  if (which == 0 && dst->state < 1) dst->state = 1;
+  if (which == 0) dst->life.stats_combined();
   return GP_OK;
 }
 
 extern "C" int gp_scale_buffer(gp_ctx* c, int which, double f) {
   if (!c) return GP_ERR_BAD_ARG;
   if (which != 0 && which != 1) return fail(c, GP_ERR_BAD_ARG, "gp_scale_buffer: which must be 0 (statistics) or 1 (gradient sums)");
-  if (which == 0 && c->state < 1) return fail(c, GP_ERR_STATE, "gp_scale_buffer(statistics) before gp_phase1");
-  if (which == 1 && c->state < 3) return fail(c, GP_ERR_STATE, "gp_scale_buffer(gradient sums) before gp_phase2");
+  if (which == 0 && !c->life.has_stats()) return fail(c, GP_ERR_STATE, "gp_scale_buffer(statistics) before gp_phase1");
+  if (which == 1 && !c->life.phase2_done()) return fail(c, GP_ERR_STATE, "gp_scale_buffer(gradient sums) before gp_phase2");
   GP_HIP(c, hipSetDevice(c->device));
-  const long n = which == 0 ? (long)c->Mp * c->Mp + (long)c->Mp * c->Dp + SC_COUNT : (long)c->M * c->Q + c->Q;
-  if (which == 0) { c->spack_filled = false; c->gstep.pred_ok = false; }   // the padded buffer is the source of truth: a later unpack needs a new pack
+  const long n = which == 0 ? stats_doubles(c) : grads_doubles(c);
+  if (which == 0) c->life.stats_scaled();   // a later unpack needs a new pack
   if (f == 0.0) {
     // a dropped shard: the reference never loads its files (local_MapReduce.py:119-129) -- a memset, so that non-finite values in
     // the dropped shard's sums (0 * inf = nan) cannot reach the reduction
@@ -525,17 +513,16 @@ extern "C" int gp_scale_stats(gp_ctx* c, double f) { return gp_scale_buffer(c, 0
 
 extern "C" int gp_global_step_jitter(gp_ctx* c, int jitter_mask) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (c->state < 1) return fail(c, GP_ERR_STATE, "gp_global_step before gp_phase1 / gp_set_local_statistics");
+  if (!c->life.has_stats()) return fail(c, GP_ERR_STATE, "gp_global_step before gp_phase1 / gp_set_local_statistics");
   if (jitter_mask < 0 || jitter_mask > 3) return fail(c, GP_ERR_BAD_ARG, "gp_global_step_jitter: mask must be 0..3");
   GP_HIP(c, hipSetDevice(c->device));
   c->gstep.jitter_mask = jitter_mask;
-  c->gstep.pred_ok = false;
+  c->life.step_started();
   GP_EV(c, 3);
   const int rc_gs = run_global_step(c);
   GP_EV(c, 4);
   if (rc_gs != GP_OK) return rc_gs;
-  c->state = 2;
-  c->gstep.pred_ok = true;           // gp_predict still checks the step's outcome (check_global)
+  c->life.step_enqueued();           // scalars and failure flags are read back at the next host synchronisation point (check_global)
   return GP_OK;
 }
 
@@ -546,14 +533,14 @@ extern "C" int gp_global_step(gp_ctx* c) { return gp_global_step_jitter(c, 0); }
 // accuracy -- the check then stays pending (guard 0: the next evaluation runs both paths again).  Called wherever an evaluation's global step is
 // known to be over: gp_finish, gp_global_status, gp_download of a global-step array.
 static int resolve_i8_check(gp_ctx* c) {
-  if (!c->i8.check_pending || c->state < 2) return GP_OK;
+  if (!c->i8.check_pending || !c->life.step_done()) return GP_OK;
   if (check_global(c) != GP_OK) return GP_OK;     // the caller reports that status itself
   return p1i8_check_finish(c);
 }
 
 extern "C" int gp_global_status(gp_ctx* c, int* retry_mask) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (c->state < 2) return fail(c, GP_ERR_STATE, "gp_global_status before gp_global_step");
+  if (!c->life.step_done()) return fail(c, GP_ERR_STATE, "gp_global_status before gp_global_step");
   GP_HIP(c, hipSetDevice(c->device));
   GP_TRY(resolve_i8_check(c));
   const int rc = check_global(c);
@@ -563,26 +550,26 @@ extern "C" int gp_global_status(gp_ctx* c, int* retry_mask) {
 
 extern "C" int gp_phase2(gp_ctx* c, int want_embedding_grads) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (c->state < 2) return fail(c, GP_ERR_STATE, "gp_phase2 before gp_global_step");
-  if (!c->have_data) return fail(c, GP_ERR_STATE, "gp_phase2 without shard data");
+  if (!c->life.step_done()) return fail(c, GP_ERR_STATE, "gp_phase2 before gp_global_step");
+  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_phase2 without shard data");
   GP_HIP(c, hipSetDevice(c->device));
   GP_EV(c, 5);
-  if ((want_embedding_grads != 0) != c->want_emb) {
+  if ((want_embedding_grads != 0) != c->life.embedding_mode()) {
     // the per-point feature matrix depends on the mode: rebuild the trial point
-    c->want_emb = want_embedding_grads != 0;
+    c->life.phase2_mode(want_embedding_grads != 0);
     GP_TRY(run_prep_and_generate(c));
   }
   GP_TRY(run_phase2(c));
   if (!c->regime_A) GP_TRY(run_phase2_b(c));
-  if (c->want_emb && c->xs_raw) {
+  if (c->life.embedding_mode() && c->xs_raw) {
     // the .grad_latest vector of this evaluation, resident for the optimiser's dot products
     const long nq = (long)c->N * c->Q;
     GP_LAUNCH(c, c->stream, grad_latest_kernel, dim3(blocks_for(nq)), dim3(256), 0, c->gXmu, c->gXs, c->Xs, c->dir, (long)c->N, c->Q, c->step,
-              1, c->have_dir ? 1 : 0, c->cg.g_latest);
-    c->cg.have_glatest = true;
+              1, c->life.has_direction() ? 1 : 0, c->cg.g_latest);
+    c->life.grad_latest_written();
   }
   GP_EV(c, 6);
-  c->state = 3;
+  c->life.phase2_ran();
   return GP_OK;
 }
 
@@ -595,18 +582,18 @@ extern "C" int gp_last_timings(gp_ctx* c, double* out8) {
   float ms;
   ++c->sync_epoch;
   if (c->timing == 1) {       // only the evaluation's first and last event were recorded
-    if (c->state >= 3 && hipEventElapsedTime(&ms, c->ev[0], c->ev[6]) == hipSuccess) out5[4] = ms;
+    if (c->life.phase2_timed() && hipEventElapsedTime(&ms, c->ev[0], c->ev[6]) == hipSuccess) out5[4] = ms;
     return GP_OK;
   }
   if (c->timing == 0) return GP_OK;
-  if (c->state >= 1 && hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) out5[0] = ms;
-  if (c->state >= 1 && hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) out5[1] = ms;
-  if (c->state >= 2 && hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) out5[2] = ms;
-  if (c->state >= 3 && hipEventElapsedTime(&ms, c->ev[5], c->ev[6]) == hipSuccess) out5[3] = ms;
+  if (c->life.phase1_timed() && hipEventElapsedTime(&ms, c->ev[0], c->ev[1]) == hipSuccess) out5[0] = ms;
+  if (c->life.phase1_timed() && hipEventElapsedTime(&ms, c->ev[1], c->ev[2]) == hipSuccess) out5[1] = ms;
+  if (c->life.step_timed() && hipEventElapsedTime(&ms, c->ev[3], c->ev[4]) == hipSuccess) out5[2] = ms;
+  if (c->life.phase2_timed() && hipEventElapsedTime(&ms, c->ev[5], c->ev[6]) == hipSuccess) out5[3] = ms;
   out5[4] = out5[0] + out5[1] + out5[2] + out5[3];
-  if (c->state >= 1 && hipEventElapsedTime(&ms, c->ev[8], c->ev[9]) == hipSuccess) out8[5] = ms;
-  if (c->state >= 1 && hipEventElapsedTime(&ms, c->ev[10], c->ev[11]) == hipSuccess) out8[6] = ms;
-  if (c->state >= 3 && hipEventElapsedTime(&ms, c->ev[12], c->ev[13]) == hipSuccess) out8[7] = ms;
+  if (c->life.phase1_timed() && hipEventElapsedTime(&ms, c->ev[8], c->ev[9]) == hipSuccess) out8[5] = ms;
+  if (c->life.phase1_timed() && hipEventElapsedTime(&ms, c->ev[10], c->ev[11]) == hipSuccess) out8[6] = ms;
+  if (c->life.phase2_timed() && hipEventElapsedTime(&ms, c->ev[12], c->ev[13]) == hipSuccess) out8[7] = ms;
   return GP_OK;
 }
 
@@ -614,7 +601,7 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
   if (!c || !dst) return GP_ERR_BAD_ARG;
   GP_HIP(c, hipSetDevice(c->device));
   const long M = c->M, Mp = c->Mp, D = c->D, Dp = c->Dp, N = c->N, Q = c->Q;
-  if (c->state >= 2 && (which == GP_ARR_KMM_INV || which == GP_ARR_KMM_PLUS_OP_INV || which == GP_ARR_DF_DKMM || which == GP_ARR_DF_DPSI1TY ||
+  if (c->life.step_done() && (which == GP_ARR_KMM_INV || which == GP_ARR_KMM_PLUS_OP_INV || which == GP_ARR_DF_DKMM || which == GP_ARR_DF_DPSI1TY ||
                         which == GP_ARR_DF_DPSI2 || which == GP_ARR_SCALARS)) {
     GP_TRY(resolve_i8_check(c));
     GP_TRY(check_global(c));
@@ -638,16 +625,16 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
     }
     case GP_ARR_X_S_TRIAL: return download_matrix(c, c->S, Q, N, Q, dst, n);
     case GP_ARR_X_MU:
-      if (!c->have_data) return fail(c, GP_ERR_STATE, "GP_ARR_X_MU before gp_upload_shard");
+      if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "GP_ARR_X_MU before gp_upload_shard");
       return download_matrix(c, c->Xmu, Q, N, Q, dst, n);
     case GP_ARR_GRAD_LATEST: {
-      if (c->state < 3 || !c->want_emb) return fail(c, GP_ERR_STATE, "GP_ARR_GRAD_LATEST needs gp_phase2(ctx, 1) first");
+      if (!c->life.grad_latest_ready()) return fail(c, GP_ERR_STATE, "GP_ARR_GRAD_LATEST needs gp_phase2(ctx, 1) first");
       if (n != 2 * N * Q) return fail(c, GP_ERR_BAD_ARG, "GP_ARR_GRAD_LATEST wants %ld doubles", 2 * N * Q);
       if (c->regime_A) return fail(c, GP_ERR_NON_FINITE, "grad_X_S with X_S == 0 (1/S, partial_terms.py:417)");
       DevBuf<double> tmp;
       GP_TRY(tmp.alloc(c, 2 * N * Q, DA_RAW));
       GP_LAUNCH(c, c->stream, grad_latest_kernel, dim3(blocks_for(N * Q)), dim3(256), 0, c->gXmu, c->gXs, c->Xs, c->dir, N, (int)Q, c->step,
-                c->xs_raw ? 1 : 0, c->have_dir ? 1 : 0, tmp);
+                c->xs_raw ? 1 : 0, c->life.has_direction() ? 1 : 0, tmp);
       hipError_t e = hipMemcpyAsync(dst, tmp, 2 * N * Q * 8, hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
       if (e != hipSuccess) return fail(c, GP_ERR_HIP, "download failed: %s", hipGetErrorString(e));
@@ -679,7 +666,7 @@ extern "C" int gp_download(gp_ctx* c, int which, double* dst, int64_t n) {
 
 extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* Psi2, const double* C, double sum_exp_K_ii, double KL) {
   if (!c || !Psi2 || !C) return GP_ERR_BAD_ARG;
-  if (!c->have_globals) return fail(c, GP_ERR_STATE, "gp_set_local_statistics before gp_set_globals");
+  if (!c->life.has_globals()) return fail(c, GP_ERR_STATE, "gp_set_local_statistics before gp_set_globals");
   GP_HIP(c, hipSetDevice(c->device));
   const long M = c->M, Mp = c->Mp, D = c->D, Dp = c->Dp;
   double* tmp = c->gstep.T2;
@@ -692,9 +679,18 @@ extern "C" int gp_set_local_statistics(gp_ctx* c, double sum_YYT, const double* 
   sc[SC_SUM_YYT] = sum_YYT; sc[SC_PSI0] = sum_exp_K_ii; sc[SC_KL] = KL; sc[SC_NLOCAL] = sum_exp_K_ii / c->sf2;
   GP_HIP(c, hipMemcpyAsync(c->stats + Mp * Mp + Mp * Dp, sc, sizeof(sc), hipMemcpyHostToDevice, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
-  c->spack_filled = false;     // the packed payload of an earlier evaluation no longer describes these statistics
-  c->gstep.pred_ok = false;
-  if (c->state < 1) c->state = 1;
+  c->life.stats_injected();    // the packed payload of an earlier evaluation no longer describes these statistics
+  return GP_OK;
+}
+
+// gp_predict / gp_infer_*: the model of a global step that saw the statistics and globals as they are now, and succeeded
+static int model_ready(gp_ctx* c, const char* who) {
+  if (!c->life.model_current())
+    return fail(c, GP_ERR_STATE, "%s needs a global step on the statistics and globals as they are now (none since the last phase 1, "
+                "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)", who);
+  GP_HIP(c, hipSetDevice(c->device));
+  GP_TRY(resolve_i8_check(c));
+  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "%s: the last global step did not succeed (%s)", who, c->gstep.gs_msg.c_str());
   return GP_OK;
 }
 
@@ -702,12 +698,7 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   if (!c) return GP_ERR_BAD_ARG;
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict: n must be >= 0");
   if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_predict: unknown flags %d", flags);
-  if (c->state < 2 || !c->have_globals || !c->gstep.pred_ok)
-    return fail(c, GP_ERR_STATE, "gp_predict needs a global step on the statistics and globals as they are now (none since the last phase 1, "
-                "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)");
-  GP_HIP(c, hipSetDevice(c->device));
-  GP_TRY(resolve_i8_check(c));
-  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "gp_predict: the last global step did not succeed (%s)", c->gstep.gs_msg.c_str());
+  GP_TRY(model_ready(c, "gp_predict"));
   if (n == 0) return GP_OK;
   if (!X_mu) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is NULL");
   const size_t nq = (size_t)n * c->Q;
@@ -729,12 +720,7 @@ static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, c
   for (int j = 0; cols && j < n_cols; ++j)
     if (cols[j] < 0 || cols[j] >= c->D || (j && cols[j] <= cols[j - 1]))
       return fail(c, GP_ERR_BAD_ARG, "%s: cols must be strictly increasing in 0 .. D - 1", who);
-  if (c->state < 2 || !c->have_globals || !c->gstep.pred_ok)
-    return fail(c, GP_ERR_STATE, "%s needs a global step on the statistics and globals as they are now (none since the last phase 1, "
-                "gp_set_globals, gp_set_local_statistics, gp_buffer_combine, gp_scale_buffer or gp_stats_unpack)", who);
-  GP_HIP(c, hipSetDevice(c->device));
-  GP_TRY(resolve_i8_check(c));
-  if (check_global(c) != GP_OK) return fail(c, GP_ERR_STATE, "%s: the last global step did not succeed (%s)", who, c->gstep.gs_msg.c_str());
+  GP_TRY(model_ready(c, who));
   if (n == 0) return GP_OK;
   if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, X_mu or X_S is NULL", who);
   const size_t nq = (size_t)n * c->Q;
@@ -778,7 +764,7 @@ extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K
   if (K < 1) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: K must be >= 1");
   if (!centres) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: centres is NULL");
   if (!X) {
-    if (!c->have_data) return fail(c, GP_ERR_STATE, "gp_kmeans_accumulate: X is NULL (the resident X_mu) before gp_upload_shard");
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_kmeans_accumulate: X is NULL (the resident X_mu) before gp_upload_shard");
     if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: X is NULL (the resident X_mu): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
   }
   const size_t kq = (size_t)K * c->Q, nq = (size_t)n * c->Q;
@@ -808,7 +794,7 @@ static bool all_finite(const double* x, size_t n) {
 static int pca_rows_check(gp_ctx* c, const char* who, int64_t n, const double* Y) {
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
   if (!Y) {
-    if (!c->have_data) return fail(c, GP_ERR_STATE, "%s: Y is NULL (the resident Y) before gp_upload_shard", who);
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: Y is NULL (the resident Y) before gp_upload_shard", who);
     if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "%s: Y is NULL (the resident Y): n must be N_s = %ld, got %ld", who, (long)c->N, (long)n);
   } else if (!all_finite(Y, (size_t)n * c->D)) {
     return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite", who);
@@ -858,11 +844,11 @@ __global__ void finish_kernel(const double* __restrict__ gs, int ngs, const doub
 
 extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2, double* grad_alpha, double* grad_beta) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (c->state < 2) return fail(c, GP_ERR_STATE, "gp_finish before gp_global_step");
+  if (!c->life.step_done()) return fail(c, GP_ERR_STATE, "gp_finish before gp_global_step");
   GP_HIP(c, hipSetDevice(c->device));
   const bool want_grads = grad_Z || grad_alpha;
   GP_TRY(resolve_i8_check(c));      // this evaluation ran both phase-1 paths: decide whether the context stays on int8 (only behind a successful global step)
-  if (want_grads && c->state < 3) {
+  if (want_grads && !c->life.phase2_done()) {
     GP_TRY(check_global(c));   // a failed global step is the more useful message
     return fail(c, GP_ERR_STATE, "gp_finish: gradients requested before gp_phase2");
   }
@@ -870,7 +856,7 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
     GP_TRY(check_global(c));
   } else {
     // the one host synchronisation of an evaluation: scalars + failure flags of the global step and the final gradients in one mapped buffer
-    const long n = (long)c->M * c->Q + c->Q;
+    const long n = grads_doubles(c);
     constexpr int ngs = GS_HOST;
     if (!c->h_out) GP_TRY(c->h_out.alloc(c, ngs + n));
     double* dout = nullptr;
@@ -878,7 +864,7 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
     GP_LAUNCH(c, c->stream, finish_kernel, dim3(blocks_for(ngs + n)), dim3(256), 0, c->gstep.gs, ngs, c->gstep.gK, c->grads, n, dout);
     GP_HIP(c, hipStreamSynchronize(c->stream));
     ++c->sync_epoch;
-    GP_TRY(check_global_from(c, c->gstep.gs_pending ? c->h_out : nullptr));
+    GP_TRY(check_global_from(c, c->life.step_outcome_pending() ? c->h_out : nullptr));
     if (grad_Z) memcpy(grad_Z, c->h_out + ngs, (size_t)c->M * c->Q * 8);
     if (grad_alpha) memcpy(grad_alpha, c->h_out + ngs + (size_t)c->M * c->Q, (size_t)c->Q * 8);
   }
@@ -927,7 +913,7 @@ __global__ void __launch_bounds__(256) cg_dots_kernel(long n2, const double* __r
 }
 
 static int cg_ready(gp_ctx* c, const char* what) {
-  if (!c->have_data) return fail(c, GP_ERR_STATE, "%s: no shard data", what);
+  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: no shard data", what);
   if (!c->xs_raw) return fail(c, GP_ERR_STATE, "%s: the resident CG vectors exist only for free embeddings (raw variances)", what);
   return GP_OK;
 }
@@ -936,13 +922,13 @@ extern "C" int gp_cg_update(gp_ctx* c, int which, double a) {
   if (!c) return GP_ERR_BAD_ARG;
   if (which < 0 || which > 5) return fail(c, GP_ERR_BAD_ARG, "gp_cg_update: which must be 0..5");
   GP_TRY(cg_ready(c, "gp_cg_update"));
-  if ((which == 4 || which == 5) && !c->cg.have_glatest) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
+  if ((which == 4 || which == 5) && !c->life.has_grad_latest()) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
   GP_HIP(c, hipSetDevice(c->device));
   const long nq = (long)c->N * c->Q;
   GP_LAUNCH(c, c->stream, cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, which, a, nq, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest,
             c->Xmu, c->Xs);
-  if (which == 0 || which == 1 || which == 5) c->have_dir = true;
-  if (which == 2) { c->state = 0; c->prep_fixa_valid = false; c->gstep.pred_ok = false; }   // the embeddings moved: statistics are stale
+  if (which == 0 || which == 1 || which == 5) c->life.direction_rewritten();
+  if (which == 2) c->life.embeddings_changed();
   return GP_OK;
 }
 
@@ -967,7 +953,7 @@ static int cg_reduce(gp_ctx* c, double* out6) {
 extern "C" int gp_cg_dots(gp_ctx* c, double* out6) {
   if (!c || !out6) return GP_ERR_BAD_ARG;
   GP_TRY(cg_ready(c, "gp_cg_dots"));
-  if (!c->have_dir) return fail(c, GP_ERR_STATE, "gp_cg_dots: no search direction (gp_cg_set_grads first)");
+  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_dots: no search direction (gp_cg_set_grads first)");
   GP_HIP(c, hipSetDevice(c->device));
   return cg_reduce(c, out6);
 }
@@ -989,7 +975,7 @@ __global__ void __launch_bounds__(256) cg_abs_kernel(long n2, const double* __re
 extern "C" int gp_cg_abs(gp_ctx* c, double* out2) {
   if (!c || !out2) return GP_ERR_BAD_ARG;
   GP_TRY(cg_ready(c, "gp_cg_abs"));
-  if (!c->have_dir) return fail(c, GP_ERR_STATE, "gp_cg_abs: no gradient vectors (gp_cg_set_grads first)");
+  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_abs: no gradient vectors (gp_cg_set_grads first)");
   GP_HIP(c, hipSetDevice(c->device));
   const long n2 = 2L * c->N * c->Q;
   const int nb = std::min(blocks_for(n2), 1024);

@@ -130,8 +130,8 @@ extern "C" int gp_allreduce(gp_ctx* c, int which) {
   if (!c) return GP_ERR_BAD_ARG;
   if (which != 0 && which != 1) return fail(c, GP_ERR_BAD_ARG, "gp_allreduce: which must be 0 (statistics) or 1 (gradient sums)");
   if (!c->comm) return fail(c, GP_ERR_STATE, "gp_allreduce before gp_comm_init");
-  if (which == 0 && c->state < 1) return fail(c, GP_ERR_STATE, "gp_allreduce(statistics) before gp_phase1");
-  if (which == 1 && c->state < 3) return fail(c, GP_ERR_STATE, "gp_allreduce(gradient sums) before gp_phase2");
+  if (which == 0 && !c->life.has_stats()) return fail(c, GP_ERR_STATE, "gp_allreduce(statistics) before gp_phase1");
+  if (which == 1 && !c->life.phase2_done()) return fail(c, GP_ERR_STATE, "gp_allreduce(gradient sums) before gp_phase2");
   GP_HIP(c, hipSetDevice(c->device));
   if (which == 0) {
     // the statistics travel packed: Psi2's upper triangle | C | scalars (gp_stats_pack / gp_stats_unpack)
@@ -142,7 +142,7 @@ extern "C" int gp_allreduce(gp_ctx* c, int which) {
     if (rc != 0) return rccl_fail(c, "ncclAllReduce(statistics)", rc);
     GP_TRY_RC(gp_stats_unpack(c));
   } else {
-    const size_t n = (size_t)c->M * c->Q + c->Q;
+    const size_t n = (size_t)grads_doubles(c);
     const int rc = g_rccl.AllReduce(c->grads, c->grads, n, kNcclFloat64, kNcclSum, c->comm, c->stream);
     if (rc != 0) return rccl_fail(c, "ncclAllReduce(gradient sums)", rc);
   }

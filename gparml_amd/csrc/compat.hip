@@ -131,8 +131,8 @@ int compat_build(gp_ctx* c, int which, DevBuf<double>& out) {
     default: return fail(c, GP_ERR_BAD_ARG, "compat_build: unknown array %d", which);
   }
   const bool needs_data = !(which == GP_ARR_DKMM_DZ || which == GP_ARR_DKMM_DALPHA);
-  if (needs_data && (!c->have_data || c->state < 1)) return fail(c, GP_ERR_STATE, "array %d needs set_data / phase 1 first", which);
-  if (!needs_data && c->state < 2) return fail(c, GP_ERR_STATE, "array %d needs the global step (Kmm) first", which);
+  if (needs_data && !c->life.psi1_available()) return fail(c, GP_ERR_STATE, "array %d needs set_data / phase 1 first", which);
+  if (!needs_data && !c->life.step_done()) return fail(c, GP_ERR_STATE, "array %d needs the global step (Kmm) first", which);
   const bool needs_p2 = (which == GP_ARR_PSI2_POINTS || which == GP_ARR_DPSI2_DZ || which == GP_ARR_DPSI2_DALPHA);
   if (needs_p2 && N * M * M > (1L << 28)) return fail(c, GP_ERR_UNSUPPORTED, "per-point psi2 tensor (N,M,M) too large for compat mode (%ld doubles)", N * M * M);
   DevBuf<double> buf, p2buf;

@@ -12,6 +12,7 @@
 #include <vector>
 #include "../../include/gparml_hip.h"
 #include "devbuf.h"
+#include "lifecycle.h"
 #include "mma_f64.h"
 
 namespace gp {
@@ -140,12 +141,10 @@ struct GsState {
   DevBuf<int8_t> gsd;         // gsi8.hip (M >= 1024): digit planes of the two double-double-grade products on the int8 matrix core
   DevBuf<double> gss;         // their column scales
   double h_gs[GS_COUNT] = {0};
-  bool gs_pending = false;    // a global step was enqueued and its scalars / failure flags have not been read back yet
   int gs_status = 0;          // outcome of the last global step once read back (GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE, GP_RETRY_JITTER)
   std::string gs_msg;
   int jitter_mask = 0;        // bit 0: Kmm, bit 1: Kmm + beta*Psi2 get 1e-7 * I in this global step (partial_terms.py:452-456)
   int retry_mask = 0;         // what a GP_RETRY_JITTER asks the caller to pass to gp_global_step_jitter
-  bool pred_ok = false;       // Inv / Linv / E describe the statistics buffer as it is now (cleared by whoever changes it or Z)
   int alloc(gp_ctx* c);
   int poison(gp_ctx* c);
 };
@@ -169,7 +168,6 @@ struct CgState {
   DevBuf<double> g_latest;    // written by gp_phase2 with embedding gradients
   DevBuf<double> g_new;
   DevBuf<double> g_old;
-  bool have_glatest = false;
   int alloc(gp_ctx* c);
 };
 
@@ -197,10 +195,7 @@ struct gp_ctx {
   double sf2 = 1, beta = 1, step = 0;
   bool regime_A = true;   // every variance exactly zero (fixed embeddings)
   bool xs_raw = false;    // X_S stored in softplus-inverse space
-  bool have_data = false, have_globals = false, have_dir = false;
-  int state = 0;          // 0 nothing, 1 phase1 done, 2 stats final (global step done), 3 phase2 done
-  bool want_emb = false;
-  bool prep_fixa_valid = false;   // regime A, fixed embeddings: the prep kernels' outputs (mu, features, records) are current
+  gp::Lifecycle life;     // where the context is in its evaluation (lifecycle.h): every entry point raises its events and asks its queries
   // ---- the shard's data and what the prep kernels derive from it ----
   gp::DevBuf<double> Kaug;    // [Np][LDK]  Psi1 | Y
   gp::DevBuf<double> Xmu;     // [N][Q] base means
@@ -227,7 +222,6 @@ struct gp_ctx {
   // ---- the outputs ----
   gp::DevBuf<double> stats;   // packed: Psi2 [Mp*Mp] | C [Mp*Dp] | scalars [SC_COUNT]
   gp::DevBuf<double> spack;   // Psi2 upper triangle | C [M][D] | scalars: the all-reduce payload across processes (allocated on first use)
-  bool spack_filled = false;  // gp_stats_pack has run since the last gp_phase1 (gp_stats_unpack refuses to run before it)
   gp::DevBuf<double> grads;   // packed: gZ_data [M*Q] | galpha_data [Q]
   gp::DevBuf<double> gXmu, gXs;   // [N][Q] each: the embedding gradients
   gp::PinnedBuf<double> h_out;  // gp_finish: pinned, mapped [GS_HOST | M*Q + Q] -- finish_kernel writes the evaluation's results straight into it
@@ -262,6 +256,10 @@ struct gp_ctx {
 
 namespace gp {
 extern thread_local std::string g_create_error;
+// element counts of the padded statistics buffer, of the gradient sums and of the packed all-reduce payload (Psi2's upper triangle | C | scalars)
+inline int64_t stats_doubles(const gp_ctx* c) { return (int64_t)c->Mp * c->Mp + (int64_t)c->Mp * c->Dp + SC_COUNT; }
+inline int64_t grads_doubles(const gp_ctx* c) { return (int64_t)c->M * c->Q + c->Q; }
+inline int64_t spack_doubles(const gp_ctx* c) { return (int64_t)c->M * (c->M + 1) / 2 + (int64_t)c->M * c->D + SC_COUNT; }
 // poison mode (devbuf.h, g_opt_poison): refills a buffer an evaluation must write before it reads (the stages' poison() and api.hip's poison_scratch)
 inline hipError_t poison_fill(gp_ctx* c, const DevBuf<double>& b) { return b.size() ? hipMemsetAsync(b, 0xFF, b.bytes(), c->stream) : hipSuccess; }
 

@@ -686,7 +686,7 @@ std::atomic<int> g_opt_gs_tail{env_flag("GPARML_GS_TAIL", true)};
 // Host side of the global step's outcome: one D2H of the scalars + failure flags, at the first call that needs them
 // (gp_global_status, gp_finish, gp_download).  Returns GP_OK, GP_ERR_NOT_PD, GP_ERR_NON_FINITE or GP_RETRY_JITTER.
 int check_global(gp_ctx* c) {
-  if (c->gstep.gs_pending) {
+  if (c->life.step_outcome_pending()) {
     double h[GS_HOST];
     GP_HIP(c, hipMemcpyAsync(h, c->gstep.gs, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     GP_HIP(c, hipStreamSynchronize(c->stream));
@@ -697,9 +697,9 @@ int check_global(gp_ctx* c) {
 }
 
 int check_global_from(gp_ctx* c, const double* h) {
-  if (c->gstep.gs_pending && h) {
+  if (c->life.step_outcome_pending() && h) {
     for (int i = 0; i < GS_COUNT; ++i) c->gstep.h_gs[i] = h[i];
-    c->gstep.gs_pending = false;
+    c->life.step_read_back();
     const int failed = (h[GS_FLAGS] != 0.0 ? 1 : 0) | (h[GS_FLAGS + 1] != 0.0 ? 2 : 0);
     const bool singular = h[GS_FLAGS] == 2.0 || h[GS_FLAGS + 1] == 2.0;
     if (singular) {
@@ -790,7 +790,6 @@ int run_global_step(gp_ctx* c) {
       const size_t lds = (stage <= 4) ? (size_t)TAIL_LDS_DOUBLES * 8 : 4096;
       if (items > 0) GP_LAUNCH(c, st, tail_stage_kernel, dim3(items), dim3(256), lds, t, stage);
     }
-    c->gstep.gs_pending = true;
     return GP_OK;
   }
   // factorise [Kmm ; A] in place, invert.  T1 is the 2 x 128 x Mp work panel.
@@ -876,7 +875,6 @@ int run_global_step(gp_ctx* c) {
     GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
               c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
   GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, c->gstep.T2, M, Q, c->gstep.gK + (long)M * Q);
-  c->gstep.gs_pending = true;   // scalars and failure flags are read back at the next host synchronisation point (check_global)
   return GP_OK;
 }
 

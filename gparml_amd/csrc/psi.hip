@@ -534,7 +534,7 @@ int P1Tiles::alloc(gp_ctx* c) {
 
 int run_prep_and_generate(gp_ctx* c) {
   PrepArgs a;
-  a.Xmu = c->Xmu; a.Xs = c->Xs; a.dir = c->have_dir ? c->dir : nullptr; a.alpha = c->alpha; a.shift = c->shift;
+  a.Xmu = c->Xmu; a.Xs = c->Xs; a.dir = c->life.has_direction() ? c->dir : nullptr; a.alpha = c->alpha; a.shift = c->shift;
   a.mu = c->mu; a.S = c->S; a.U = c->U; a.lnc1 = c->lnc1; a.Xa = c->Xa; a.klpart = c->p1t.klpart;
   a.N = c->N; a.Np = c->Np; a.Q = c->Q; a.CXp = c->CXp; a.step = c->step; a.sf2 = c->sf2;
   a.raw = c->xs_raw ? 1 : 0; a.regimeA = c->regime_A ? 1 : 0; a.fixedA = p2_fast_mode(c) ? 1 : (p2_wide_fixed_mode(c) ? 2 : 0);
@@ -543,11 +543,11 @@ int run_prep_and_generate(gp_ctx* c) {
   // feature matrix is [mu | 1] and KL = 0 -- nothing the prep kernels write depends on the hyper-parameters, so they run once per
   // upload / mode switch; Psi1 then takes alpha and sf2 as arguments (psi1_kernel<QP, true>).
   const bool fixa = a.fixedA && a.PU != nullptr;
-  if (!(fixa && c->prep_fixa_valid)) {
+  if (!c->life.prep_is_current(fixa)) {
     GP_LAUNCH(c, c->stream, prep_elem_kernel, dim3((unsigned)std::min<long>((c->Np * c->Q + 255) / 256, 16384)), dim3(256), 0, a);
     GP_LAUNCH(c, c->stream, prep_row_kernel, dim3(c->p1t.kl_blocks), dim3(256), 0, a);
   }
-  c->prep_fixa_valid = fixa;
+  c->life.prep_ran(fixa);
   c->i8.active = fixa && p1i8_applicable(c);     // decided per evaluation (gp_debug_set_option("p1_i8", ...) switches it at run time)
   GP_EV(c, 8);
   const int QP = psi1_qp(c->Q);
@@ -1269,11 +1269,11 @@ __global__ void colsum2_kernel(const double* __restrict__ a, int rows_a, int lda
 }
 
 // fixed-embedding fast path: regime A without embedding gradients and Q + 1 <= 12 feature columns (p2_fast8_kernel)
-bool p2_fast_mode(const gp_ctx* c) { return c->regime_A && !c->want_emb && c->Q + 1 <= 12; }
+bool p2_fast_mode(const gp_ctx* c) { return c->regime_A && !c->life.embedding_mode() && c->Q + 1 <= 12; }
 // fixed embeddings with a wider latent space: the general eight-wave kernel WITHOUT its per-point m-contraction, on the hyper-parameter independent
 // features [mu | 1 | mu^2] (the mu^2 term of grad_alpha comes out of the same n-contraction; no point_kernel, the prep kernels run once per upload).
 // N = 1e6, D = 100, M = 512, Q = 30: phase-2 kernel 13.7 -> 12.0 ms, evaluation 23.6 -> 20.4 ms (same box, with the fixed-variance Psi1 kernel; profiles/r04_shape_sweep.txt)
-bool p2_wide_fixed_mode(const gp_ctx* c) { return c->regime_A && !c->want_emb && c->Q + 1 > 12; }
+bool p2_wide_fixed_mode(const gp_ctx* c) { return c->regime_A && !c->life.embedding_mode() && c->Q + 1 > 12; }
 
 int P2State::alloc(gp_ctx* c) {
   const long Mp = c->Mp, Np = c->Np;

@@ -25,6 +25,7 @@ class ShardEngine(object):
 
     # ---- lifetime ---------------------------------------------------------------------------------
     def close(self):
+        self.globals_key = None
         if getattr(self, 'h', None):
             self.lib.gp_destroy(self.h)
             self.h = None
@@ -53,6 +54,7 @@ class ShardEngine(object):
         Y, pY = _lib.as_c(Y)
         X_mu, pm = _lib.as_c(X_mu)
         X_S, ps = _lib.as_c(X_S)
+        self.globals_key = None
         self._ck(self.lib.gp_upload_shard(self.h, pY, pm, ps, 1 if xs_is_raw else 0), 'gp_upload_shard')
 
     def upload_embeddings(self, X_mu, X_S, xs_is_raw=False):
@@ -61,9 +63,11 @@ class ShardEngine(object):
         assert X_mu.shape == X_S.shape == (self.N_s, self.Q)
         X_mu, pm = _lib.as_c(X_mu)
         X_S, ps = _lib.as_c(X_S)
+        self.globals_key = None
         self._ck(self.lib.gp_upload_embeddings(self.h, pm, ps, 1 if xs_is_raw else 0), 'gp_upload_embeddings')
 
     def set_direction(self, d):
+        self.globals_key = None
         if d is None:
             self._ck(self.lib.gp_set_direction(self.h, None), 'gp_set_direction')
             return
@@ -71,6 +75,16 @@ class ShardEngine(object):
         assert d.shape == (2, self.N_s, self.Q)
         d, pd = _lib.as_c(d)
         self._ck(self.lib.gp_set_direction(self.h, pd), 'gp_set_direction')
+
+    # What the device holds of the globals: the key of the last set_globals, None once anything has moved the context away from the evaluation that call
+    # started (a new shard, new embeddings, a direction, a CG update, close).  set_globals itself never skips; a caller that wants to push each distinct
+    # set once (partial_terms._push_globals) compares its own key with this one.
+    globals_key = None
+
+    @staticmethod
+    def make_globals_key(Z, sf2, alpha, beta, N_global, step_size=0.0):
+        return (np.ascontiguousarray(Z, dtype=np.float64).tobytes(), float(sf2), np.ascontiguousarray(alpha, dtype=np.float64).tobytes(), float(beta),
+                int(N_global), float(step_size))
 
     def set_globals(self, Z, sf2, alpha, beta, N_global=None, step_size=0.0):
         Z = np.asarray(Z, dtype=np.float64)
@@ -80,7 +94,9 @@ class ShardEngine(object):
         Z, pZ = _lib.as_c(Z)
         alpha, pa = _lib.as_c(alpha)
         Ng = self.N_s if N_global is None else int(N_global)
+        self.globals_key = None
         self._ck(self.lib.gp_set_globals(self.h, pZ, float(sf2), pa, float(beta), Ng, float(step_size)), 'gp_set_globals')
+        self.globals_key = (Z.tobytes(), float(sf2), alpha.tobytes(), float(beta), Ng, float(step_size))     # make_globals_key on what as_c made
 
     # ---- evaluation ---------------------------------------------------------------------------------
     def phase1(self):
@@ -176,6 +192,7 @@ class ShardEngine(object):
         return out
 
     def cg_update(self, which, a=0.0):
+        self.globals_key = None
         self._ck(self.lib.gp_cg_update(self.h, int(which), float(a)), 'gp_cg_update')
 
     def scale_stats(self, factor):
