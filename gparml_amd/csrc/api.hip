@@ -710,6 +710,44 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   return run_predict(c, (long)n, X_mu, X_S, xs_is_raw, flags, mean, var);
 }
 
+// gp_predict_joint / gp_predict_sample: gp_predict's preconditions and argument errors for deterministic inputs, then the size limit
+static int joint_check(gp_ctx* c, const char* who, int64_t n, const double* X, int flags, int64_t n_max, bool* nothing) {
+  *nothing = true;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
+  if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "%s: unknown flags %d", who, flags);
+  GP_TRY(model_ready(c, who));
+  if (n == 0) return GP_OK;
+  if (!X) return fail(c, GP_ERR_BAD_ARG, "%s: X is NULL", who);
+  if (n > n_max) return fail(c, GP_ERR_UNSUPPORTED, "%s: n = %ld is beyond the limit of %ld points of one call (the n x n matrix is held on the device)", who, (long)n, (long)n_max);
+  const size_t nq = (size_t)n * c->Q;
+  for (size_t i = 0; i < nq; ++i)
+    if (!std::isfinite(X[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X is not finite", who);
+  *nothing = false;
+  return GP_OK;
+}
+
+extern "C" int gp_predict_joint(gp_ctx* c, int64_t n, const double* X, int flags, double* mean, double* cov) {
+  if (!c) return GP_ERR_BAD_ARG;
+  bool nothing;
+  GP_TRY(joint_check(c, "gp_predict_joint", n, X, flags, 16384, &nothing));
+  if (nothing || (!mean && !cov)) return GP_OK;
+  return run_predict_joint(c, (long)n, X, flags, mean, cov);
+}
+
+extern "C" int gp_predict_sample(gp_ctx* c, int64_t n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (!(jitter >= 0.0) || !std::isfinite(jitter)) return fail(c, GP_ERR_BAD_ARG, "gp_predict_sample: jitter must be finite and >= 0");
+  if (n_draws < 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict_sample: n_draws must be >= 0");
+  if (n_draws > 0 && (!eps || !out)) return fail(c, GP_ERR_BAD_ARG, "gp_predict_sample: eps or out is NULL");
+  bool nothing;
+  GP_TRY(joint_check(c, "gp_predict_sample", n, X, flags, 8192, &nothing));
+  if (nothing || n_draws == 0) return GP_OK;
+  const size_t ne = (size_t)n_draws * n * c->D;
+  for (size_t i = 0; i < ne; ++i)
+    if (!std::isfinite(eps[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict_sample: eps is not finite");
+  return run_predict_sample(c, (long)n, X, flags, jitter, n_draws, eps, out, mean);
+}
+
 // gp_infer_objective / gp_infer_latent: gp_predict's preconditions, then the arguments of the new rows
 static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int raw,
                        bool* nothing) {

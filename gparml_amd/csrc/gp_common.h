@@ -77,6 +77,7 @@ struct PredPlan;   // predict.hip
 struct InferPlan;  // infer.hip
 struct KmPlan;     // kmeans.hip
 struct PcaPlan;    // pca.hip
+struct JointPlan;  // joint.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -84,6 +85,7 @@ struct PredPlanDelete { void operator()(PredPlan* p) const; };
 struct InferPlanDelete { void operator()(InferPlan* p) const; };
 struct KmPlanDelete { void operator()(KmPlan* p) const; };
 struct PcaPlanDelete { void operator()(PcaPlan* p) const; };
+struct JointPlanDelete { void operator()(JointPlan* p) const; };
 
 }  // namespace gp
 
@@ -243,6 +245,7 @@ struct gp_ctx {
   std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip)
   std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip)
   std::unique_ptr<gp::PcaPlan, gp::PcaPlanDelete> pca;       // gp_scatter_accumulate / gp_project_rows' buffers (pca.hip)
+  std::unique_ptr<gp::JointPlan, gp::JointPlanDelete> joint;  // gp_predict_joint / gp_predict_sample's buffers (joint.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -294,6 +297,14 @@ int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn,
 const double* b_debug_table(const gp_ctx* c, bool lea, long* n);      // gp_debug_peek: LE or LEA, NULL / 0 without a plan
 // predict.hip
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
+// gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
+// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed); the chunk's mean rows
+int pred_chunk_plan(gp_ctx* c, long* rows);
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf);
+int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
+// joint.hip
+int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
+int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
 // infer.hip
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
@@ -320,7 +331,7 @@ int check_global_from(gp_ctx* c, const double* h);
 // gp_debug_potrf_inverse memsets its own buffer.  A caller that hands in a reused scratch buffer must clear it first.
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A /*in: SPD, out: L*/, double* Linv, double* Inv,
                           double* Twork /*batch * Mp * Mp / 2 doubles*/, double* logdet2 /*device, [batch]*/, double* fail_flag /*device, [batch]*/,
-                          double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0);
+                          double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0, bool factor_only = false);
 // the options of gp_debug_set_option (api.hip holds the table and the ones without a home file), each next to the code it switches
 extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
 extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip

@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) panel_copy_kernel(const double* __restric
 }
 
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A, double* Linv, double* Inv, double* Twork,
-                          double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap) {
+                          double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap, bool factor_only) {
   const int nt = Mp / NB;
   const long ld = Mp, bs = (long)Mp * Mp;
   // a per-device attribute: set on every call (cheap) rather than once per process -- contexts may live on several GPUs
@@ -87,6 +87,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
       GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, rem * NB, batch, q));
     }
   }
+  if (factor_only) return GP_OK;
   if (g_opt_trtri_rec.load()) {
     // X = L^-1 below the diagonal blocks by halves (r05): with L = [L11 0 ; L21 L22], X21 = -X22 (L21 X11).  Level h = 1, 2, 4, ... (half size in
     // 128-blocks): every pair of halves of that size is independent of the others, so a level is TWO batched launches whatever M -- 2 log2(M / 128)

@@ -208,15 +208,24 @@ __device__ __forceinline__ void mma_step(Acc& acc, const double (&a)[4], const d
     for (int bc = 0; bc < 16; ++bc) mfma444_acc(acc.v[ar][bc], a[ar], b[bc]);
 }
 
+// the first k-step of a chain: C is the inline constant 0, the accumulators need no zeroing in C++ (DESIGN.md section 3's rule)
+__device__ __forceinline__ void mma_step_zero(Acc& acc, const double (&a)[4], const double (&b)[16]) {
+#pragma unroll
+  for (int ar = 0; ar < 4; ++ar)
+#pragma unroll
+    for (int bc = 0; bc < 16; ++bc) mfma444_zero(acc.v[ar][bc], a[ar], b[bc]);
+}
+
 // Operand registers are double-buffered: the ds_reads of step k4+1 are issued before the 64 MFMAs of step k4,
-// so one wave alone keeps the matrix pipe busy inside a chunk.
-template <Layout LA, Layout LB>
+// so one wave alone keeps the matrix pipe busy inside a chunk.  FIRST: the chunk opens the accumulation (mma_step_zero).
+template <Layout LA, Layout LB, bool FIRST = false>
 __device__ __forceinline__ void mma_chunk(const double* sA, const double* sB, Acc& acc, const LaneOfs& o) {
   double a0[4], b0[16], a1[4], b1[16];
   load_operands<LA, LB>(sA, sB, o, 0, a0, b0);
   load_operands<LA, LB>(sA, sB, o, 1, a1, b1);
   __builtin_amdgcn_sched_barrier(0);
-  mma_step(acc, a0, b0);
+  if constexpr (FIRST) mma_step_zero(acc, a0, b0);
+  else mma_step(acc, a0, b0);
   __builtin_amdgcn_sched_barrier(0);
   load_operands<LA, LB>(sA, sB, o, 2, a0, b0);
   __builtin_amdgcn_sched_barrier(0);

@@ -282,6 +282,50 @@ static int pred_alloc(gp_ctx* c, bool uncertain) {
   return GP_OK;
 }
 
+// One chunk of points through the front of the pipeline: upload, pred_prep_kernel, Psi1*, the mean product into the chunk's G and (fac != NULL) the
+// two inverse-factor products [Lk^-1 k* | La^-1 k*] into fac (leading dimension ldf).  gp_predict keeps the centred inputs and the factor rows in
+// the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf) {
+  const PredPlan& p = *c->pred;
+  const bool unc = X_S != nullptr;
+  const PredUnc* u = p.unc.get();
+  hipStream_t st = c->stream;
+  const long R = p.rows, Mp = c->Mp, Dp = c->Dp, Q = c->Q, rows = round_up(cnt, TILE);
+  double* xin = p.in;
+  double* sin = p.in + R * Q;
+  GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+  if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+  GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, c->shift, cnt,
+            rows, (int)Q, c->sf2, mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
+  GP_TRY_RC(launch_psi1_rows(c, mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
+  // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
+  GemmP g;
+  g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
+  g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = Dp + 2 * Mp;
+  g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g));
+  if (fac) {
+    g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = fac; g.ldc = ldf;
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g));
+  }
+  return GP_OK;
+}
+
+// the chunk plan for deterministic inputs (built on first use) and its rows per chunk
+int pred_chunk_plan(gp_ctx* c, long* rows) {
+  GP_TRY_RC(pred_alloc(c, false));
+  *rows = c->pred->rows;
+  return GP_OK;
+}
+
+// the mean rows [cnt][D] of the chunk pred_chunk_front has just run, out of G into a device buffer of the caller
+int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
+  const PredPlan& p = *c->pred;
+  GP_LAUNCH(c, c->stream, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, (long)c->Dp + 2L * c->Mp, cnt, 0, c->Mp, c->D, c->Dp, c->sf2,
+            0.0, mean, p.out + p.rows * c->D);
+  return GP_OK;
+}
+
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {
   const bool unc = X_S != nullptr;
   GP_TRY_RC(pred_alloc(c, unc));
@@ -298,24 +342,8 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
   double* out_var = p.out + R * D;
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
-    double* xin = p.in;
-    double* sin = p.in + R * Q;
-    GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-    if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-    GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, c->shift, cnt,
-              rows, (int)Q, c->sf2, p.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
-    GP_TRY_RC(launch_psi1_rows(c, p.mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
-    // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
-    GemmP g;
-    g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
-    g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = ldg;
-    g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g));
+    GP_TRY_RC(pred_chunk_front(c, X_mu, X_S, raw, n0, cnt, p.mu, !unc && var ? p.G + Dp : nullptr, ldg));
     if (!unc) {
-      if (var) {
-        g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.G + Dp;
-        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g));
-      }
       GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
                 c->sf2, noise, out_mean, out_var);
       if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));

@@ -281,6 +281,40 @@ class ShardEngine(object):
                                      var.ctypes.data_as(_lib._dp)), 'gp_predict')
         return mean, var
 
+    # ---- joint prediction (gp_predict_joint, gp_predict_sample) ------------------------------------------------
+    def _joint_X(self, X):
+        X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+        assert X.ndim == 2 and X.shape[1] == self.Q, 'X shape %s: (n, %d) expected' % (X.shape, self.Q)
+        return _lib.as_c(X)
+
+    def predict_joint(self, X, include_noise=False):
+        """Joint posterior of f (``include_noise``: of y) at the new deterministic inputs X (n, Q), n <= 16384, after a successful global step as
+        ``predict``.  Returns (mean (n, D), cov (n, n)): one covariance matrix shared by all D outputs, symmetric bit for bit, whose diagonal is
+        ``predict``'s variance.  The evaluation state is left untouched."""
+        X, px = self._joint_X(X)
+        n = X.shape[0]
+        mean, cov = np.empty((n, self.D)), np.empty((n, n))
+        self._ck(self.lib.gp_predict_joint(self.h, n, px, 1 if include_noise else 0, mean.ctypes.data_as(_lib._dp), cov.ctypes.data_as(_lib._dp)),
+                 'gp_predict_joint')
+        return mean, cov
+
+    def predict_sample(self, X, n_draws, include_noise=False, jitter=1e-8, eps=None, seed=None):
+        """``n_draws`` coherent function samples at X (n, Q), n <= 8192: draws[s, :, d] = mean[:, d] + Lc eps[s, :, d] with Lc the lower Cholesky
+        factor of cov + (noise + jitter sf2) I (``predict_joint``'s cov; ``jitter`` is relative to sf2).  ``eps`` (n_draws, n, D) standard normals,
+        drawn with numpy.random.default_rng(seed) when not given.  Returns (draws (n_draws, n, D), mean (n, D))."""
+        X, px = self._joint_X(X)
+        n, n_draws = X.shape[0], int(n_draws)
+        if eps is None:
+            assert n_draws >= 0, 'n_draws must be >= 0'
+            eps = np.random.default_rng(seed).standard_normal((n_draws, n, self.D))
+        eps = np.asarray(eps, dtype=np.float64)
+        assert eps.shape == (n_draws, n, self.D), 'eps shape %s: (%d, %d, %d) expected' % (eps.shape, n_draws, n, self.D)
+        eps, pe = _lib.as_c(eps)
+        draws, mean = np.empty((n_draws, n, self.D)), np.empty((n, self.D))
+        self._ck(self.lib.gp_predict_sample(self.h, n, px, 1 if include_noise else 0, float(jitter), n_draws, pe, draws.ctypes.data_as(_lib._dp),
+                                            mean.ctypes.data_as(_lib._dp)), 'gp_predict_sample')
+        return draws, mean
+
     # ---- latent inference for new rows (gp_infer_objective, gp_infer_latent) ---------------------------------
     def _infer_args(self, Y, X_mu, X_S, cols):
         Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))

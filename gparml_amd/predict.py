@@ -42,6 +42,23 @@ class Predictor(object):
         finally:
             eng.close()
 
+    def predict_joint(self, X, include_noise=False):
+        """Joint posterior of the outputs at the points X (n, Q) with the trained model: mean (n, D) and the covariance (n, n) between the points,
+        shared by all D outputs (ShardEngine.predict_joint), against the stored accumulated statistics of the training data."""
+        eng = self._trained_engine()
+        try:
+            return eng.predict_joint(X, include_noise=include_noise)
+        finally:
+            eng.close()
+
+    def predict_sample(self, X, n_draws, include_noise=False, jitter=1e-8, eps=None, seed=None):
+        """``n_draws`` coherent samples (n_draws, n, D) of the outputs at the points X (n, Q), and the mean (n, D) (ShardEngine.predict_sample)."""
+        eng = self._trained_engine()
+        try:
+            return eng.predict_sample(X, n_draws, include_noise=include_noise, jitter=jitter, eps=eps, seed=seed)
+        finally:
+            eng.close()
+
     def _trained_engine(self):
         """An engine that holds the trained model: the globals, the stored accumulated statistics of the training data and a global step on them."""
         cls = self._engine_cls

@@ -92,6 +92,18 @@ class ResidentModel(object):
         self._refresh_statistics(flat_array)
         return self.engines[0].predict(X_mu, X_S, include_noise=include_noise)
 
+    def predict_joint(self, flat_array, X, include_noise=False):
+        """Joint posterior mean (n, D) and covariance (n, n) at the new inputs X for the model at ``flat_array`` (ShardEngine.predict_joint on the
+        root engine).  The statistics are brought up to date as in ``predict``, with the same collective rule."""
+        self._refresh_statistics(flat_array)
+        return self.engines[0].predict_joint(X, include_noise=include_noise)
+
+    def predict_sample(self, flat_array, X, n_draws, include_noise=False, jitter=1e-8, eps=None, seed=None):
+        """``n_draws`` coherent posterior samples (n_draws, n, D) and the mean (n, D) at X for the model at ``flat_array``
+        (ShardEngine.predict_sample on the root engine).  The statistics are brought up to date as in ``predict``, with the same collective rule."""
+        self._refresh_statistics(flat_array)
+        return self.engines[0].predict_sample(X, n_draws, include_noise=include_noise, jitter=jitter, eps=eps, seed=seed)
+
     def _refresh_statistics(self, flat_array):
         flat_array = np.asarray(flat_array, dtype=np.float64)
         last = self._stats_x

@@ -178,6 +178,22 @@ int gp_finish(gp_ctx* ctx, double* F, double* grad_Z, double* grad_sf2, double* 
  * GP_ERR_BAD_ARG for n < 0 or a non-finite mean / negative or non-finite variance; n = 0 writes nothing. */
 int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, int flags, double* mean, double* var);
 
+/* Joint posterior at n new deterministic inputs X (n,Q), after a successful global step as gp_predict.  With k_i = psi1(x_i), a_i = Lk^-1 k_i and
+ * b_i = La^-1 k_i (Lk, La the Cholesky factors of Kmm and Kmm + beta Psi2):
+ *   mean[i][d] = k_i^T W_d (as gp_predict),   cov[i][j] = k(x_i, x_j) - a_i . a_j + b_i . b_j   (one n x n matrix, shared by all D outputs),
+ * the inverse-factor form of gp_predict's variance: diag(cov) is that variance.  flags bit 0 adds 1/beta to the diagonal (y, not f).
+ * gp_predict_joint: mean (n,D) or NULL, cov (n,n) row-major or NULL; cov[i][j] and cov[j][i] carry the same bits.  n <= 16384.
+ * gp_predict_sample: out[s][i][d] = mean[i][d] + sum_j Lc[i][j] eps[s][j][d] for s < n_draws, where Lc Lc^T = cov + (noise + jitter sf2) I, Lc lower
+ * with a positive diagonal (noise = 1/beta with flags bit 0, else 0; jitter >= 0 is relative to sf2).  eps (n_draws,n,D): standard normals from the
+ * caller (there is no device generator); out (n_draws,n,D); mean (n,D) or NULL.  n <= 8192.  GP_ERR_NOT_PD when the factorisation fails (raise jitter).
+ * Both: preconditions, state rule and argument errors are gp_predict's (GP_ERR_STATE unless the last global step succeeded on the statistics and
+ * globals as they are now; GP_ERR_BAD_ARG for n < 0, unknown flags, non-finite X or eps, jitter < 0 or non-finite, n_draws < 0, NULL eps / out with
+ * n_draws > 0); GP_ERR_UNSUPPORTED beyond the limits on n; n = 0 or n_draws = 0 writes nothing.  Synchronous, bit-identical from run to run (fixed
+ * summation order, no floating-point atomics).  The evaluation state is left untouched: gp_phase2 / gp_finish / gp_predict after them give
+ * bit-identical results. */
+int gp_predict_joint(gp_ctx* ctx, int64_t n, const double* X, int flags, double* mean, double* cov);
+int gp_predict_sample(gp_ctx* ctx, int64_t n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
+
 /* ---- latent inference for new rows ---------------------------------------------------------------- */
 /* The bound of n NEW rows y (n,D) under q(x) = N(X_mu, diag X_S), with q(u) frozen at the optimum of the trained model (the statistics of the last
  * global step): per row, with O the observed columns (D_o of them), W and B as for gp_predict, v = W_O y_O and G = W_O W_O^T - D_o B,
