@@ -60,6 +60,7 @@ SIGNATURES = {
     'gp_predict': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     'gp_predict_joint': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_predict_sample': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp]),
+    'gp_predict_grad': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     'gp_infer_objective': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_infer_latent': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     'gp_kmeans_accumulate': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, ctypes.POINTER(_i64), _dp, _ip]),

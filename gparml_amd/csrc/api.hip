@@ -748,6 +748,17 @@ extern "C" int gp_predict_sample(gp_ctx* c, int64_t n, const double* X, int flag
   return run_predict_sample(c, (long)n, X, flags, jitter, n_draws, eps, out, mean);
 }
 
+extern "C" int gp_predict_grad(gp_ctx* c, int64_t n, const double* X, int flags, double* jac, double* dvar, double* metric, double* logdet) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (flags != 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict_grad: flags is reserved and must be 0 (got %d)", flags);
+  bool nothing;
+  GP_TRY(joint_check(c, "gp_predict_grad", n, X, 0, INT64_MAX, &nothing));
+  if (nothing || (!jac && !dvar && !metric && !logdet)) return GP_OK;
+  if (logdet && c->Q > 64)
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_predict_grad: logdet is computed on the device for Q <= 64 only (Q = %d): pass NULL and take slogdet of the metric", c->Q);
+  return run_predict_grad(c, (long)n, X, jac, dvar, metric, logdet);
+}
+
 // gp_infer_objective / gp_infer_latent: gp_predict's preconditions, then the arguments of the new rows
 static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int raw,
                        bool* nothing) {

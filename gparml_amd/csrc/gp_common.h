@@ -78,6 +78,7 @@ struct InferPlan;  // infer.hip
 struct KmPlan;     // kmeans.hip
 struct PcaPlan;    // pca.hip
 struct JointPlan;  // joint.hip
+struct GradPlan;   // grad.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -86,6 +87,7 @@ struct InferPlanDelete { void operator()(InferPlan* p) const; };
 struct KmPlanDelete { void operator()(KmPlan* p) const; };
 struct PcaPlanDelete { void operator()(PcaPlan* p) const; };
 struct JointPlanDelete { void operator()(JointPlan* p) const; };
+struct GradPlanDelete { void operator()(GradPlan* p) const; };
 
 }  // namespace gp
 
@@ -246,6 +248,7 @@ struct gp_ctx {
   std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip)
   std::unique_ptr<gp::PcaPlan, gp::PcaPlanDelete> pca;       // gp_scatter_accumulate / gp_project_rows' buffers (pca.hip)
   std::unique_ptr<gp::JointPlan, gp::JointPlanDelete> joint;  // gp_predict_joint / gp_predict_sample's buffers (joint.hip)
+  std::unique_ptr<gp::GradPlan, gp::GradPlanDelete> grad;     // gp_predict_grad's buffers (grad.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -298,13 +301,17 @@ const double* b_debug_table(const gp_ctx* c, bool lea, long* n);      // gp_debu
 // predict.hip
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
 // gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
-// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed); the chunk's mean rows
+// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed); the chunk's mean rows;
+// the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them)
 int pred_chunk_plan(gp_ctx* c, long* rows);
+const double* pred_chunk_psi1(const gp_ctx* c);
 int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf);
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
 // joint.hip
 int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
 int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
+// grad.hip
+int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dvar, double* metric, double* logdet);
 // infer.hip
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);

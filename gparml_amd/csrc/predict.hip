@@ -318,6 +318,8 @@ int pred_chunk_plan(gp_ctx* c, long* rows) {
   return GP_OK;
 }
 
+const double* pred_chunk_psi1(const gp_ctx* c) { return c->pred->P1; }
+
 // the mean rows [cnt][D] of the chunk pred_chunk_front has just run, out of G into a device buffer of the caller
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
   const PredPlan& p = *c->pred;

@@ -315,6 +315,27 @@ class ShardEngine(object):
                                             mean.ctypes.data_as(_lib._dp)), 'gp_predict_sample')
         return draws, mean
 
+    # ---- derivatives of the prediction with respect to the input (gp_predict_grad) ----------------------------
+    def predict_grad(self, X, jac=True, dvar=True, metric=True, logdet=True):
+        """Derivatives of ``predict`` at the new deterministic inputs X (n, Q), after a successful global step as ``predict``.  Returns a dict of the
+        requested arrays: ``jac`` (n, D, Q) d mean_d / d x_q, ``dvar`` (n, Q) d var_f / d x_q, ``metric`` (n, Q, Q) the expected metric tensor
+        E[J]^T E[J] + D Cov(J) (symmetric bit for bit) and ``logdet`` (n,) ln det metric (Q <= 64; the magnification factor is exp(logdet / 2)).
+        The noise enters none of them.  The evaluation state is left untouched."""
+        X, px = self._joint_X(X)
+        n, Q = X.shape[0], self.Q
+        out = {}
+        if jac:
+            out['jac'] = np.empty((n, self.D, Q))
+        if dvar:
+            out['dvar'] = np.empty((n, Q))
+        if metric:
+            out['metric'] = np.empty((n, Q, Q))
+        if logdet:
+            out['logdet'] = np.empty(n)
+        p = lambda k: out[k].ctypes.data_as(_lib._dp) if k in out else None
+        self._ck(self.lib.gp_predict_grad(self.h, n, px, 0, p('jac'), p('dvar'), p('metric'), p('logdet')), 'gp_predict_grad')
+        return out
+
     # ---- latent inference for new rows (gp_infer_objective, gp_infer_latent) ---------------------------------
     def _infer_args(self, Y, X_mu, X_S, cols):
         Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))

@@ -59,6 +59,30 @@ class Predictor(object):
         finally:
             eng.close()
 
+    def _predict_grad(self, X, **which):
+        eng = self._trained_engine()
+        try:
+            return eng.predict_grad(X, **which)
+        finally:
+            eng.close()
+
+    def predict_jacobian(self, X):
+        """(jac (n, D, Q), dvar (n, Q)): the derivatives of the predictive mean and of the variance of f with respect to the input, at the points
+        X (n, Q) with the trained model (ShardEngine.predict_grad)."""
+        out = self._predict_grad(X, jac=True, dvar=True, metric=False, logdet=False)
+        return out['jac'], out['dvar']
+
+    def predict_metric(self, X):
+        """The expected metric tensor (n, Q, Q) of the mapping at the points X: E[J]^T E[J] + D Cov(J) (ShardEngine.predict_grad)."""
+        return self._predict_grad(X, jac=False, dvar=False, metric=True, logdet=False)['metric']
+
+    def predict_magnification(self, X):
+        """The magnification factor sqrt(det metric) (n,) at the points X.  The log-determinant comes from the device for Q <= 64; beyond that it
+        is numpy.linalg.slogdet of the returned metric."""
+        if self.Q <= 64:
+            return numpy.exp(0.5 * self._predict_grad(X, jac=False, dvar=False, metric=False, logdet=True)['logdet'])
+        return numpy.exp(0.5 * numpy.linalg.slogdet(self.predict_metric(X))[1])
+
     def _trained_engine(self):
         """An engine that holds the trained model: the globals, the stored accumulated statistics of the training data and a global step on them."""
         cls = self._engine_cls

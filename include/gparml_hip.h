@@ -194,6 +194,24 @@ int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, in
 int gp_predict_joint(gp_ctx* ctx, int64_t n, const double* X, int flags, double* mean, double* cov);
 int gp_predict_sample(gp_ctx* ctx, int64_t n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
 
+/* Derivatives of the prediction with respect to the input, at n new deterministic inputs X (n,Q), after a successful global step as gp_predict.
+ * With k = psi1(x), a = Lk^-1 k, b = La^-1 k as above, dk_q = d k / d x_q = -alpha_q (x_q - z_q) o k (difference first, on the centred coordinates),
+ * a'_q = Lk^-1 dk_q and b'_q = La^-1 dk_q:
+ *   jac[i][d][q]    = dk_q^T W_d                                         (n,D,Q)   d mean_d / d x_q
+ *   dvar[i][q]      = -2 (a . a'_q - b . b'_q)                           (n,Q)     d var_f / d x_q
+ *   metric[i][q][r] = sum_d jac_dq jac_dr + D (sf2 alpha_q [q == r] - a'_q . a'_r + b'_q . b'_r)   (n,Q,Q)
+ *   logdet[i]       = ln det metric[i]                                   (n)       the magnification factor is exp(logdet / 2)
+ * metric is the expected metric tensor E[J^T J] = E[J]^T E[J] + D Cov(J) of the mapping x -> f(x); Cov(J) is the mixed second derivative of
+ * gp_predict_joint's cov at x = x'.  The noise enters none of them: flags is reserved and must be 0.  Any output may be NULL; a subset gives the bits
+ * of the full call.  metric[i] is symmetric bit for bit.  A point's outputs are the same bits alone and in any batch.  jac, dvar and metric work
+ * for any Q; logdet is computed on the device for Q <= 64 (beyond: GP_ERR_UNSUPPORTED when logdet is not NULL -- take slogdet of the metric).
+ * GP_ERR_NOT_PD when a point's metric does not factorise (not expected for finite inputs; the message names the first such point, its logdet is
+ * NaN, every other output of the call is valid).  Preconditions, state rule and argument errors are gp_predict_joint's (GP_ERR_STATE unless the last
+ * global step succeeded on the statistics and globals as they are now; GP_ERR_BAD_ARG for n < 0, flags != 0, non-finite X); n = 0 writes nothing.
+ * Synchronous, bit-identical from run to run (fixed summation order, no floating-point atomics).  The evaluation state is left untouched: gp_phase2 /
+ * gp_finish / gp_predict / gp_predict_joint after it give bit-identical results.  Not covered: uncertain inputs, second derivatives. */
+int gp_predict_grad(gp_ctx* ctx, int64_t n, const double* X, int flags, double* jac, double* dvar, double* metric, double* logdet);
+
 /* ---- latent inference for new rows ---------------------------------------------------------------- */
 /* The bound of n NEW rows y (n,D) under q(x) = N(X_mu, diag X_S), with q(u) frozen at the optimum of the trained model (the statistics of the last
  * global step): per row, with O the observed columns (D_o of them), W and B as for gp_predict, v = W_O y_O and G = W_O W_O^T - D_o B,
