@@ -6,7 +6,7 @@
 //   phase 1   Psi2 += sum_p psi2_p
 //   phase 2   T_p = Bbar o psi2_p;  r_p = T_p 1,  t_p = T_p Z;  per-point sums [sr, zr_q, z2r_q, zt_q] -> pp (finished by psi2_points_finish_kernel);
 //             grad_Z[m, q] += sum_p -alpha_q (z_mq r - t) + w_pq (2 mu_pq r - z_mq r - t)
-// No symmetry is used and every operand comes from memory: correct for every Q, M and N, at a fraction of the tuned kernels' rate (a latent space
+// No symmetry is used to save work and every operand comes from memory: correct for every Q, M and N, at a fraction of the tuned kernels' rate (a latent space
 // that wide is outside BASELINE.json's configurations; the reference itself needs an (N, M, M, Q) tensor for it, partial_terms.py:273).
 #include "psi2_plan.h"
 #include "fexp.h"
@@ -47,8 +47,9 @@ __global__ void __launch_bounds__(256) psi2n_generic_kernel(const double* __rest
     const long p = e / mm, r = e - p * mm, n = n0 + p;
     const int m = (int)(r / M), m2 = (int)(r - (long)m * M);
     const double* v = V2P + n * Q;
-    const double* za = ZP + (long)m * Q;
-    const double* zb = ZP + (long)m2 * Q;
+    // the operands in the order (min, max) of the pair: fl(v z_a) z_b is not fl(v z_b) z_a, and psi2_n -- with it Psi2 -- is symmetric bit for bit on every other path
+    const double* za = ZP + (long)(m < m2 ? m : m2) * Q;
+    const double* zb = ZP + (long)(m < m2 ? m2 : m) * Q;
     double s = LEA[n * Mp + m] + LEA[n * Mp + m2];
     for (int q = 0; q < Q; ++q) s = fma(v[q] * za[q], zb[q], s);
     const double x = fexp(s);

@@ -498,6 +498,13 @@ class ShardEngine(object):
         self._ck(self.lib.gp_download(self.h, _lib.ARR[name], out.ctypes.data_as(_lib._dp), out.size), 'gp_download(%s)' % name)
         return out
 
+    def peek(self, name, count):
+        """The first ``count`` doubles of an internal device buffer as it lies in memory, padding included (gp_debug_peek: 'Bbar', 'Abar', 'stats',
+        'grads', ...; a developer and test tool).  ``count`` must be at least the buffer's size; the rest of the result is left as allocated."""
+        buf = np.empty(int(count))
+        self._ck(self.lib.gp_debug_peek(self.h, name.encode(), buf.ctypes.data_as(_lib._dp), buf.size), 'gp_debug_peek(%s)' % name)
+        return buf
+
     def scalars(self):
         s = self.download('SCALARS')
         return dict(sum_YYT=s[0], sum_exp_K_ii=s[1], KL=s[2], logdet_Kmm=s[3], logdet_A=s[4], F=s[5], grad_beta=s[6], grad_sf2=s[7])
