@@ -1,5 +1,7 @@
 // extern "C" entry points of libgparml_hip.so (see include/gparml_hip.h).
 #include "gp_common.h"
+#include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -28,13 +30,8 @@ __global__ void sumsq_kernel(const double* __restrict__ x, long n, double* part)
   __shared__ double red[256];
   double s = 0.0;
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256L) s += x[i] * x[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  const double tot = block_sum<256>(red, s);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
 // gather a padded device matrix [rows_p][ld] into a dense host-shaped [rows][cols] staging buffer
@@ -459,7 +456,7 @@ __global__ void grad_latest_kernel(const double* __restrict__ gmu, const double*
     if (raw) {
       double x = Xs[i];
       if (have_dir && step != 0.0) x += step * dir[nq + i];
-      g *= 1.0 / (exp(-x) + 1.0);      // transformVar_grad, supporting_functions.py:165-168
+      g *= softplus_slope(x);      // transformVar_grad, supporting_functions.py:165-168
     }
     out[nq + i] = -g;
   }
@@ -951,13 +948,10 @@ __global__ void __launch_bounds__(256) cg_dots_kernel(long n2, const double* __r
   }
   for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = s[k];
   __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) {
-      for (int k = 0; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + w];
-      red[5][threadIdx.x] = fmax(red[5][threadIdx.x], red[5][threadIdx.x + w]);
-    }
-    __syncthreads();
-  }
+  block_fold<256>([&](int i, int j) {
+    for (int k = 0; k < 5; ++k) red[k][i] += red[k][j];
+    red[5][i] = fmax(red[5][i], red[5][j]);
+  });
   if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -1014,10 +1008,7 @@ __global__ void __launch_bounds__(256) cg_abs_kernel(long n2, const double* __re
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) { const double a = fabs(gnew[i]); s += a; m = fmax(m, a); }
   red[0][threadIdx.x] = s; red[1][threadIdx.x] = m;
   __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) { red[0][threadIdx.x] += red[0][threadIdx.x + w]; red[1][threadIdx.x] = fmax(red[1][threadIdx.x], red[1][threadIdx.x + w]); }
-    __syncthreads();
-  }
+  block_fold<256>([&](int i, int j) { red[0][i] += red[0][j]; red[1][i] = fmax(red[1][i], red[1][j]); });
   if (threadIdx.x < 2) part[blockIdx.x * 2 + threadIdx.x] = red[threadIdx.x][0];
 }
 

@@ -4,6 +4,8 @@
 // this backend; the fast path never materialises them (gp_phase2 contracts on the device instead).  Plain one-thread-
 // per-output kernels: the shapes are the reference's (M,Q,M)/(Q,M,M)/(M,Q,D)/(Q,M,D) layouts.
 #include "gp_common.h"
+#include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 
 namespace gp {
@@ -60,7 +62,7 @@ __global__ void __launch_bounds__(256) dpsi1y_kernel(const double* __restrict__ 
     double acc = 0.0;
     for (long n = 0; n < N; ++n) {
       const double s = S[n * Q + q], m = mu[n * Q + q];
-      const double d1 = a * s + 1.0;
+      const double d1 = var_q(a, s).d1;
       const double p = Kaug[n * ld + j] * Kaug[n * ld + Mp + d];
       if (which == 0) acc += p * a * (m - z) / d1;
       else { const double t = (m - z) / d1; acc += -0.5 * p * (t * t + s / d1); }
@@ -82,7 +84,7 @@ __global__ void __launch_bounds__(256) dpsi2_kernel(const double* __restrict__ P
     double acc = 0.0;
     for (long n = 0; n < N; ++n) {
       const double s = S[n * Q + q], m = mu[n * Q + q];
-      const double d2 = 2.0 * a * s + 1.0;
+      const double d2 = var_q(a, s).d2;
       const double p = P2[(n * M + j) * M + m2];
       if (which == 0) acc += p * (-0.5 * a * (zj - zm) + 0.5 * a * (2.0 * m - zj - zm) / d2);
       else { const double t = (2.0 * m - zj - zm) / d2; acc += p * (-0.25 * (zj - zm) * (zj - zm) - 0.25 * t * t - s / d2); }
@@ -112,10 +114,8 @@ __global__ void __launch_bounds__(256) gradalpha_parts_kernel(const double* A, c
   double s = 0.0;
   for (long i = threadIdx.x; i < (long)M * M; i += 256) s += A[i] * a3[(long)q * M * M + i] + C[i] * c3[(long)q * M * M + i];
   for (long i = threadIdx.x; i < (long)M * D; i += 256) s += B[i] * b3[(long)q * M * D + i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
-  if (threadIdx.x == 0) out[q] = red[0];
+  const double tot = block_sum<256>(red, s);
+  if (threadIdx.x == 0) out[q] = tot;
 }
 
 static int grid_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 16384)); }

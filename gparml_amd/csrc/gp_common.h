@@ -298,7 +298,15 @@ int run_phase2_b(gp_ctx* c);
 int b_poison(gp_ctx* c);                                              // poison mode: refills the plan's per-evaluation buffers (BPlan::poisoned)
 int b_point_tables(gp_ctx* c, const double** LE, bool* le_il, const double** Vn, const double** DZ2);   // compat: runs dz2_kernel, hands out the tables
 const double* b_debug_table(const gp_ctx* c, bool lea, long* n);      // gp_debug_peek: LE or LEA, NULL / 0 without a plan
+// lea.hip: LE (NULL: not wanted) and LEA [rows][Mp] of the points in the rows of mu, w, v2 (row stride ld) and lnc2h (stride ldl) against the rows of
+// Z (stride ldz), Q latent dimensions; rows >= cnt and columns >= M get kPadLog; rows a mask (NULL: none) switches off are not written
+struct LeaRows {
+  const double* mu; const double* w; const double* v2; long ld; const double* lnc2h; long ldl; const double* Z; long ldz;
+  int Q; long cnt, rows; int M, Mp; const unsigned char* mask; double* LE; double* LEA;
+};
+int launch_lea_rows(gp_ctx* c, hipStream_t st, const LeaRows& a);
 // predict.hip
+const double* pred_debug_lea(const gp_ctx* c, long* n);               // gp_debug_peek: the uncertain-input plan's LEA, NULL / 0 without one
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
 // gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
 // Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed); the chunk's mean rows;
@@ -315,6 +323,7 @@ int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dv
 // infer.hip
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
+const double* infer_debug_lea(const gp_ctx* c, long* n);              // gp_debug_peek: the chunk's LEA, NULL / 0 without a plan
 // kmeans.hip
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
 // pca.hip

@@ -21,6 +21,7 @@
 // context's GradPlan; the evaluation's and gp_predict's buffers are only read.
 // Not covered: uncertain inputs, second derivatives, generating dK inside the GEMM's staging, pinned or pipelined host copies.
 #include "gp_common.h"
+#include "lane_reduce.h"
 #include <algorithm>
 #include <cmath>
 
@@ -72,12 +73,6 @@ __device__ __forceinline__ void grad_pair(int p, int& q, int& r) {
   while (r * (r + 1) / 2 > p) --r;
   while ((r + 1) * (r + 2) / 2 <= p) ++r;
   q = p - r * (r + 1) / 2;
-}
-
-__device__ __forceinline__ double grad_wave_sum(double v) {
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
-  return v;
 }
 
 // slices of a column group for Q: the (pair, slice) items fill the workgroup's IT x 256 slots
@@ -260,7 +255,7 @@ __global__ void __launch_bounds__(256) grad_point_kernel<0>(GradArgs a) {
         t = fma(u.x, w.x, t);
         if (c + 1 < len) t = fma(u.y, w.y, t);
       }
-      s[sec] = grad_wave_sum(t);
+      s[sec] = wave_sum(t);
     }
     if (lane == 0) {
       const double u = s[2] - s[1];

@@ -7,7 +7,7 @@
 // Every row is an independent 2Q-dimensional problem: nothing M^3 and nothing D-wide happens per evaluation.
 // Once per call:  Eo = the observed columns of E, zero-padded;  G = beta^2 Eo Eo^T - D_o B (one product on the MFMA GEMM core, inf_gfold_kernel);
 // per chunk:      V = beta Yo Eo^T (n x M, the GEMM core again) and |y_O|^2.
-// Per evaluation: inf_prep_kernel (per-row tables), inf_lea_kernel (LEA of psi2.hip's factorised form), inf_rows_kernel (the hot kernel).
+// Per evaluation: inf_prep_kernel (per-row tables), lea_rows_kernel (lea.hip: LEA of psi2.hip's factorised form), inf_rows_kernel (the hot kernel).
 //
 // inf_rows_kernel: ONE WAVE PER ROW, lanes = inducing points m.  Everything that depends on the second index m' alone (z_m', z_m'^2, LEA[m']) is
 // wave-uniform and arrives through scalar loads; G is read coalesced along m.  psi2 is symmetric, so only m' >= m is generated: G is stored FOLDED,
@@ -28,6 +28,8 @@
 // still running.  Finished rows are skipped by the evaluation kernels at once.
 #include "gp_common.h"
 #include "fexp.h"
+#include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 #include <cmath>
 
@@ -105,8 +107,6 @@ __global__ void __launch_bounds__(256) inf_ypad_kernel(const double* __restrict_
 }
 
 // ---- per evaluation --------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double inf_softplus(double r) { return log(1.0 + exp(r)); }     // as the shard's prep (psi.hip) and pred_prep_kernel
-
 // Per-row tables of the evaluation point xe[n] = [mu (Q) | S or raw S (Q)], QP wide and zero-padded: TB[n] = [mu | S | u | w | v2] and
 // LC[n] = [ln c1, 1/2 ln c2]; u = alpha / (alpha S + 1), w = alpha / (2 alpha S + 1), v2 = (alpha - w) / 2.  One thread per row.
 __global__ void __launch_bounds__(256) inf_prep_kernel(const double* __restrict__ xe, int raw, const unsigned char* __restrict__ mask,
@@ -122,49 +122,17 @@ __global__ void __launch_bounds__(256) inf_prep_kernel(const double* __restrict_
         const double a = alpha[q];
         m = xe[n * 2 * Q + q] - shift[q];      // centred like the model's Z (gp_ctx::shift); the KL term adds the origin back (inf_rows_kernel)
         s = xe[n * 2 * Q + Q + q];
-        if (raw) s = inf_softplus(s);
-        const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0;
-        u = a / d1;
-        w = a / d2;
-        v2 = 0.5 * (a - w);
-        l1 -= 0.5 * log(d1);
-        l2 -= 0.25 * log(d2);
+        if (raw) s = softplus(s);
+        const VarQ f = var_q(a, s);
+        u = f.u; w = f.w; v2 = f.v2;
+        l1 -= var_log1(f);
+        l2 -= var_half_log2(f);
       }
       t[q] = m; t[QP + q] = s; t[2 * QP + q] = u; t[3 * QP + q] = w; t[4 * QP + q] = v2;
     }
     LC[2 * n] = l1;
     LC[2 * n + 1] = l2;
   }
-}
-
-// LEA[n][m] = 1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2 - 1/2 sum_q v2_nq z_mq^2   (kPadLog for m >= M: exp gives exactly 0)
-__global__ void __launch_bounds__(256) inf_lea_kernel(const double* __restrict__ TB, const double* __restrict__ LC, const unsigned char* __restrict__ mask,
-                                                      const double* __restrict__ ZP, const double* __restrict__ ZZ, long cnt, int M, int Mp, int QP,
-                                                      double* __restrict__ LEA) {
-  const long total = cnt * Mp;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const long n = e / Mp;
-    const int m = (int)(e - n * Mp);
-    if (mask && !mask[n]) continue;
-    double v = kPadLog;
-    if (m < M) {
-      const double* t = TB + n * 5 * QP;
-      double s = 0.0, r = 0.0;
-      for (int q = 0; q < QP; ++q) {
-        const double d = t[q] - ZP[(long)m * QP + q];
-        s = fma(t[3 * QP + q] * d, d, s);
-        r = fma(t[4 * QP + q], ZZ[(long)m * QP + q], r);
-      }
-      v = LC[2 * n + 1] - 0.5 * (s + r);
-    }
-    LEA[e] = v;
-  }
-}
-
-__device__ __forceinline__ double inf_wave_sum(double v) {
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
-  return v;
 }
 
 struct InfDims {
@@ -219,11 +187,11 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
       }
     }
     // lane j keeps the sums of latent dimension qc + j (one register each instead of QR uniform ones)
-    b0 = inf_wave_sum(b0);
+    b0 = wave_sum(b0);
     double B1 = 0.0, B2 = 0.0, A1 = 0.0, A2 = 0.0;
 #pragma unroll
     for (int j = 0; j < QR; ++j) {
-      const double v1 = inf_wave_sum(b1[j]), v2 = inf_wave_sum(b2[j]);
+      const double v1 = wave_sum(b1[j]), v2 = wave_sum(b2[j]);
       if (lane == j) { B1 = v1; B2 = v2; }
     }
     // ---- psi2 term, m' >= m only (the folded G)
@@ -266,10 +234,10 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
         a2[j] += z * fma(z, r, 2.0 * tz[j]);
       }
     }
-    sT = inf_wave_sum(sT);
+    sT = wave_sum(sT);
 #pragma unroll
     for (int j = 0; j < QR; ++j) {
-      const double v1 = inf_wave_sum(a1[j]), v2 = inf_wave_sum(a2[j]);
+      const double v1 = wave_sum(a1[j]), v2 = wave_sum(a2[j]);
       if (lane == j) { A1 = v1; A2 = v2; }
     }
     if (qc == 0) {
@@ -286,7 +254,7 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
       const double d2s = 2.0 * w * w * (mq * mq * sT - mq * A1 + 0.25 * A2) - w * sT;
       const double gmu = a.beta * d1mu - 0.5 * a.beta * d2mu - (mq + shift[q]);
       double gs = a.beta * d1s - 0.5 * a.beta * d2s - 0.5 * (1.0 - 1.0 / sq);
-      if (a.raw) gs *= 1.0 / (1.0 + exp(-xe[n * 2 * Q + Q + q]));
+      if (a.raw) gs *= softplus_slope(xe[n * 2 * Q + Q + q]);
       ge[n * 2 * Q + q] = gmu;
       ge[n * 2 * Q + Q + q] = gs;
     }
@@ -447,13 +415,8 @@ __global__ void __launch_bounds__(256) inf_count_kernel(const int* __restrict__ 
   __shared__ int part[256];
   int c = 0;
   for (long n = threadIdx.x; n < cnt; n += 256) c += si[n * II_COUNT + II_STATUS] == 0 ? 1 : 0;
-  part[threadIdx.x] = c;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = part[0];
+  const int tot = block_sum<256>(part, c);
+  if (threadIdx.x == 0) *out = tot;
 }
 
 // results of the chunk: out[n] = [mu (Q) | S or raw S (Q) | L | iterations]
@@ -529,6 +492,12 @@ static int inf_alloc(gp_ctx* c, long R, long Dop, int QP, bool latent) {
   return GP_OK;
 }
 
+const double* infer_debug_lea(const gp_ctx* c, long* n) {
+  const InfChunk* k = c->infer ? c->infer->chunk.get() : nullptr;
+  *n = k ? (long)k->LEA.size() : 0;
+  return k ? k->LEA.get() : nullptr;
+}
+
 static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
 // one evaluation of the rows of the chunk that mask selects (NULL: all) at xe
@@ -536,7 +505,11 @@ static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long c
   hipStream_t st = c->stream;
   const int M = c->M, Mp = c->Mp, Q = c->Q;
   GP_LAUNCH(c, st, inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, k.xe, raw, mask, c->alpha, c->shift, cnt, Q, QP, c->sf2, k.TB, k.LC);
-  GP_LAUNCH(c, st, inf_lea_kernel, dim3(inf_blocks(cnt * Mp)), dim3(256), 0, k.TB, k.LC, mask, p.ZP, p.ZZ, cnt, M, Mp, QP, k.LEA);
+  // LEA from the w and v2 sections of TB and the 1/2 ln c2 column of LC
+  LeaRows t;
+  t.mu = k.TB; t.w = k.TB + 3 * QP; t.v2 = k.TB + 4 * QP; t.ld = 5 * QP; t.lnc2h = k.LC + 1; t.ldl = 2; t.Z = p.ZP; t.ldz = QP; t.Q = Q;
+  t.cnt = cnt; t.rows = cnt; t.M = M; t.Mp = Mp; t.mask = mask; t.LE = nullptr; t.LEA = k.LEA;
+  GP_TRY_RC(launch_lea_rows(c, st, t));
   InfDims a;
   a.cnt = cnt; a.M = M; a.Mp = Mp; a.Q = Q; a.QP = QP; a.raw = raw; a.sf2 = c->sf2; a.beta = c->beta; a.Do = Do;
   double* ge = want_grad ? k.ge.get() : nullptr;

@@ -19,6 +19,7 @@
 // Every buffer belongs to the context's KmPlan (allocated on first use, grown on demand, freed with the context).  All of them are written before
 // they are read (DA_RAW: NaN-filled in the poison test mode).  Nothing of the evaluation is touched: only the resident X_mu is read (X == NULL).
 #include "gp_common.h"
+#include "lane_reduce.h"
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -74,10 +75,7 @@ __global__ void __launch_bounds__(256) km_assign_kernel(const double* __restrict
   red[tid] = live ? best : 0.0;
   red[256 + tid] = live ? sqrt(best) : 0.0;
   __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) { red[tid] += red[tid + h]; red[256 + tid] += red[256 + tid + h]; }
-    __syncthreads();
-  }
+  block_fold<256>([&](int i, int j) { red[i] += red[j]; red[256 + i] += red[256 + j]; });
   if (tid == 0) { dpart[2 * blockIdx.x] = red[0]; dpart[2 * blockIdx.x + 1] = red[256]; }
 }
 
@@ -111,15 +109,14 @@ __global__ void __launch_bounds__(256) km_reduce_kernel(const double* __restrict
 #pragma unroll
       for (int j = 0; j < KM_QS; ++j) {
 #pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) acc[j] += __shfl_xor(acc[j], sh);
+        for (int sh = 32; sh > 0; sh >>= 1) acc[j] += __shfl_xor(acc[j], sh);      // wave_sum (lane_reduce.h) spelled out: KM_QS calls change the register allocation
       }
       if (lane == 0) {
 #pragma unroll
         for (int j = 0; j < KM_QS; ++j) if (q0 + j < Q) out[q0 + j] = acc[j];
       }
       if (q0 == 0) {
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) mine += __shfl_xor(mine, sh);
+        mine = wave_sum(mine);
         if (lane == 0) pcnt[(long)blockIdx.x * K + k] = mine;
       }
     }
@@ -151,10 +148,7 @@ __global__ void __launch_bounds__(256) km_final_kernel(const double* __restrict_
   red[tid] = a;
   red[256 + tid] = b;
   __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if (tid < h) { red[tid] += red[tid + h]; red[256 + tid] += red[256 + tid + h]; }
-    __syncthreads();
-  }
+  block_fold<256>([&](int i, int j) { red[i] += red[j]; red[256 + i] += red[256 + j]; });
   if (tid == 0) { dist[0] = first ? red[0] : dist[0] + red[0]; dist[1] = first ? red[256] : dist[1] + red[256]; }
 }
 

@@ -6,6 +6,33 @@
 
 namespace gp {
 
+// ---- whole-value reductions: one definition each of the workgroup's LDS tree and of the wave's xor butterfly -------------------------------------
+// The tree over the NT threads of a workgroup, halving from NT / 2 down to STOP with a barrier behind every level: fold(i, j) combines slot j into
+// slot i of whatever arrays the caller has filled (and synchronised) -- one array, several, sums or maxima -- in a fixed order.
+template <int NT, int STOP = 1, typename F>
+__device__ __forceinline__ void block_fold(F&& fold) {
+  for (int k = NT / 2; k >= STOP; k >>= 1) {
+    if ((int)threadIdx.x < k) fold((int)threadIdx.x, (int)threadIdx.x + k);
+    __syncthreads();
+  }
+}
+// sum of v over the NT threads through red (NT slots of LDS), returned to every thread; a caller that reuses red puts a barrier before the next write
+template <int NT, typename T>
+__device__ __forceinline__ T block_sum(T* red, T v) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  block_fold<NT>([&](int i, int j) { red[i] += red[j]; });
+  return red[0];
+}
+// sum over the 64 lanes of a wave (all lanes active), the same bits in every lane: xor 32, 16, ..., 1
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
+  return v;
+}
+
+// ---- many values at once: reduce-scatters ------------------------------------------------------------------------------------------------------
 template <int MASK>
 __device__ __forceinline__ double lane_xor(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);

@@ -8,6 +8,7 @@
 #include "gp_common.h"
 #include "potrf128.h"
 #include "gemm32.h"
+#include "lane_reduce.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -355,13 +356,8 @@ __device__ __forceinline__ void dots_block(const DotJobs& jobs, double* part, in
   double s = 0.0;
   for (int r = vbx; r < jb.rows; r += DOT_BLOCKS)
     for (int c = threadIdx.x; c < jb.cols; c += 256) s += jb.x[(long)r * jb.ld + c] * jb.y[(long)r * jb.ld + c];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[vby * DOT_BLOCKS + vbx] = red[0];
+  const double tot = block_sum<256>(red, s);
+  if (threadIdx.x == 0) part[vby * DOT_BLOCKS + vbx] = tot;
   __syncthreads();
 }
 __global__ void __launch_bounds__(256) dots_kernel(DotJobs jobs, double* part) {
@@ -565,10 +561,8 @@ __global__ void __launch_bounds__(128) kmm_grads_lds_kernel(const double* __rest
 __device__ __forceinline__ void colsum_block(const double* __restrict__ part, int rows, int Q, double* __restrict__ out, int q, double* red) {
   double s = 0.0;
   for (int r = threadIdx.x; r < rows; r += 256) s += part[(long)r * Q + q];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
-  if (threadIdx.x == 0) out[q] = red[0];
+  const double tot = block_sum<256>(red, s);
+  if (threadIdx.x == 0) out[q] = tot;
   __syncthreads();
 }
 __global__ void __launch_bounds__(256) colsum_kernel(const double* __restrict__ part, int rows, int Q, double* __restrict__ out) {
@@ -993,6 +987,8 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   else if (!std::strcmp(name, "grads")) { src = c->grads; cnt = (long)c->M * c->Q + c->Q; }
   else if (!std::strcmp(name, "Rpart")) { src = c->p2.Rpart; cnt = (long)c->p2.Rpart.size(); }
   else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
+  else if (!std::strcmp(name, "pred_LEA")) src = pred_debug_lea(c, &cnt);
+  else if (!std::strcmp(name, "infer_LEA")) src = infer_debug_lea(c, &cnt);
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
   GP_HIP(c, hipStreamSynchronize(c->stream));

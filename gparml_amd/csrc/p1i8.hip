@@ -37,6 +37,7 @@
 // 32 rows; both operand panels (S digits x 2 row blocks x 128 columns x 16 B) arrive by LDS-DMA straight in operand order (the digit
 // layout IS the LDS image: no swizzle, no padding) through a three-stage ring.
 #include "gp_common.h"
+#include "lane_reduce.h"
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -423,7 +424,7 @@ __global__ void __launch_bounds__(256) i8_compare_kernel(const double* __restric
   for (long i = blk * 256L + threadIdx.x; i < n; i += I8_CMP_BLOCKS * 256L) { const double x = a[lo + i], y = b[lo + i]; d2 = fma(x - y, x - y, d2); s2 = fma(y, y, s2); }
   r0[threadIdx.x] = d2; r1[threadIdx.x] = s2;
   __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) { r0[threadIdx.x] += r0[threadIdx.x + k]; r1[threadIdx.x] += r1[threadIdx.x + k]; } __syncthreads(); }
+  block_fold<256>([&](int i, int j) { r0[i] += r0[j]; r1[i] += r1[j]; });
   if (threadIdx.x == 0) { cmp[8 + 2 * blockIdx.x] = r0[0]; cmp[8 + 2 * blockIdx.x + 1] = r1[0]; }
 }
 __global__ void __launch_bounds__(256) i8_compare_final_kernel(double* __restrict__ cmp, const double* __restrict__ Psi2, const double* __restrict__ P, int M, int Mp) {
@@ -439,7 +440,7 @@ __global__ void __launch_bounds__(256) i8_compare_final_kernel(double* __restric
   for (int i = threadIdx.x; i < M; i += 256) { m2 = fmax(m2, Psi2[(long)i * Mp + i]); mp = fmax(mp, P[(long)i * Mp + i]); }
   r0[threadIdx.x] = m2; r1[threadIdx.x] = mp;
   __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) { r0[threadIdx.x] = fmax(r0[threadIdx.x], r0[threadIdx.x + k]); r1[threadIdx.x] = fmax(r1[threadIdx.x], r1[threadIdx.x + k]); } __syncthreads(); }
+  block_fold<256>([&](int i, int j) { r0[i] = fmax(r0[i], r0[j]); r1[i] = fmax(r1[i], r1[j]); });
   if (threadIdx.x == 0) { cmp[4] = r0[0]; cmp[5] = r1[0]; }
 }
 

@@ -9,6 +9,7 @@
 //                      and sum_n h_n mu_n^2 into extra rows of Rpart / hgpart that p2_reduce_kernel and colsum2_kernel pick up through their nparts
 // No atomics: every sum has one fixed order, and the split boundaries are a function of the shape alone (p2_rem_plan).
 #include "gp_common.h"
+#include "lane_reduce.h"
 
 namespace gp {
 
@@ -137,13 +138,10 @@ __global__ void __launch_bounds__(256) p2_rem_fix_kernel(P2RemArgs p) {
 #pragma unroll
   for (int c = 0; c < XS; ++c) red[c * 256 + t] = gacc[c];
   __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) {
-    if (t < k) {
+  block_fold<256>([&](int i, int j) {
 #pragma unroll
-      for (int c = 0; c < XS; ++c) red[c * 256 + t] += red[c * 256 + t + k];
-    }
-    __syncthreads();
-  }
+    for (int c = 0; c < XS; ++c) red[c * 256 + i] += red[c * 256 + j];
+  });
   if (t < XS) p.gapart[(long)blockIdx.x * XS + t] = -0.5 * red[t * 256];
 }
 

@@ -19,6 +19,8 @@
 // (rows points per pass, PredPlan); deleting the context frees them.  The evaluation's buffers are only read: phase 2 / gp_finish after a prediction give the same bits.
 #include "gp_common.h"
 #include "fexp.h"
+#include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 #include <cmath>
 
@@ -37,38 +39,16 @@ __global__ void __launch_bounds__(256) pred_prep_kernel(const double* __restrict
       double m = 0.0, s = 0.0;
       if (n < cnt) {
         m = Xin[i] - shift[q];      // centred like the model's Z (gp_ctx::shift)
-        if (Sin) { s = Sin[i]; if (raw) s = log(1.0 + exp(s)); }     // softplus, as the shard's prep (psi.hip)
+        if (Sin) { s = Sin[i]; if (raw) s = softplus(s); }
       }
-      const double d1 = a * s + 1.0, d2 = 2.0 * a * s + 1.0, w = a / d2;
+      const VarQ f = var_q(a, s);
       mu[i] = m;
-      U[i] = a / d1;
-      l1 -= 0.5 * log(d1);
-      if (Wq) { Wq[i] = w; V2[i] = 0.5 * (a - w); l2 -= 0.25 * log(d2); }
+      U[i] = f.u;
+      l1 -= var_log1(f);
+      if (Wq) { Wq[i] = f.w; V2[i] = f.v2; l2 -= var_half_log2(f); }
     }
     lnc1[n] = l1;
     if (lnc2h) lnc2h[n] = l2;
-  }
-}
-
-// LEA[n][m] = 1/2 ln c2_n - 1/2 sum_q w_nq (mu_nq - z_mq)^2 - 1/2 sum_q v2_nq z_mq^2  (kPadLog for m >= M or n >= cnt: exp gives exactly 0)
-__global__ void __launch_bounds__(256) pred_lea_kernel(const double* __restrict__ mu, const double* __restrict__ Wq, const double* __restrict__ V2,
-                                                       const double* __restrict__ lnc2h, const double* __restrict__ Z, long cnt, long rows, int M, int Mp,
-                                                       int Q, double* __restrict__ LEA) {
-  const long total = rows * Mp;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const long n = e / Mp;
-    const int m = (int)(e - n * Mp);
-    double v = kPadLog;
-    if (n < cnt && m < M) {
-      double s = 0.0, t = 0.0;
-      for (int q = 0; q < Q; ++q) {
-        const double z = Z[(long)m * Q + q], d = mu[n * Q + q] - z;
-        s = fma(Wq[n * Q + q] * d, d, s);
-        t = fma(V2[n * Q + q] * z, z, t);
-      }
-      v = lnc2h[n] - 0.5 * (s + t);
-    }
-    LEA[e] = v;
   }
 }
 
@@ -79,12 +59,6 @@ __global__ void __launch_bounds__(256) pred_bmat_kernel(const double* __restrict
     const long i = e / Mp, j = e - i * Mp;
     B[e] = (i < M && j < M) ? Inv[e] - Inv[mm + e] : 0.0;
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) v += __shfl_xor(v, sh);
-  return v;
 }
 
 // deterministic inputs: row n of G = [mean (Dp) | Lk^-1 k* (Mp) | La^-1 k* (Mp)] -> mean[n][0..D), var[n]; one wave per point, fixed summation order
@@ -282,6 +256,12 @@ static int pred_alloc(gp_ctx* c, bool uncertain) {
   return GP_OK;
 }
 
+const double* pred_debug_lea(const gp_ctx* c, long* n) {
+  const PredUnc* u = c->pred ? c->pred->unc.get() : nullptr;
+  *n = u ? (long)u->LEA.size() : 0;
+  return u ? u->LEA.get() : nullptr;
+}
+
 // One chunk of points through the front of the pipeline: upload, pred_prep_kernel, Psi1*, the mean product into the chunk's G and (fac != NULL) the
 // two inverse-factor products [Lk^-1 k* | La^-1 k*] into fac (leading dimension ldf).  gp_predict keeps the centred inputs and the factor rows in
 // the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.
@@ -357,8 +337,10 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
         GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
       if (var) {
-        GP_LAUNCH(c, st, pred_lea_kernel, dim3((unsigned)std::min<long>((rows * Mp + 255) / 256, 16384)), dim3(256), 0, p.mu, u->W, u->V2,
-                  u->lnc2, c->Z, cnt, rows, (int)M, (int)Mp, (int)Q, u->LEA);
+        LeaRows t;
+        t.mu = p.mu; t.w = u->W; t.v2 = u->V2; t.ld = Q; t.lnc2h = u->lnc2; t.ldl = 1; t.Z = c->Z; t.ldz = Q; t.Q = (int)Q;
+        t.cnt = cnt; t.rows = rows; t.M = (int)M; t.Mp = (int)Mp; t.mask = nullptr; t.LE = nullptr; t.LEA = u->LEA;
+        GP_TRY_RC(launch_lea_rows(c, st, t));
         PsiWArgs a;
         a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->gstep.E; a.B = u->B; a.G = p.G; a.ldg = ldg;
         a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;

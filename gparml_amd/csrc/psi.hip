@@ -4,6 +4,8 @@
 #include "gp_common.h"
 #include <vector>
 #include "fexp.h"
+#include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -33,8 +35,6 @@ struct PrepArgs {
   long N, Np; int Q, CXp; double step, sf2; int raw, regimeA, fixedA;
 };
 
-__device__ __forceinline__ double softplus(double x) { return log(1.0 + exp(x)); }
-
 // element-wise part: one thread per (n, q), fully coalesced
 __global__ void __launch_bounds__(256) prep_elem_kernel(PrepArgs a) {
   const long total = a.Np * a.Q;
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) prep_elem_kernel(PrepArgs a) {
     a.mu[i] = m;
     a.S[i] = s;
     const double al = a.alpha[q];
-    const double u = al / (al * s + 1.0);
+    const double u = var_q(al, s).u;
     a.U[i] = u;
     if (a.PU) { double* rec = a.PU + n * (2 * a.QP + 2); rec[q] = m; rec[a.QP + q] = u; }
     // per-point features of the n-contraction: fixed embeddings [mu (Q) | 1 | 0 ...] (fixedA = 1: Q + 1 <= 12, p2_fast8_kernel) or
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) prep_row_kernel(PrepArgs a) {
       double klrow = 0.0;
       for (int q = 0; q < a.Q; ++q) {
         const double s = a.S[n * a.Q + q], m = a.mu[n * a.Q + q] + a.shift[q];      // the KL term is about the caller's mu
-        lnc -= 0.5 * log(a.alpha[q] * s + 1.0);
+        lnc -= var_log1(var_q(a.alpha[q], s));
         if (n < a.N) klrow += s - log(s) + m * m - 1.0;
       }
       kl += 0.5 * klrow;
@@ -94,13 +94,8 @@ __global__ void __launch_bounds__(256) prep_row_kernel(PrepArgs a) {
     a.Xa[n * a.CXp + c1] = (n < a.N) ? 1.0 : 0.0;
     for (int c = (a.fixedA == 2 ? 2 * a.Q : c1) + 1; c < a.CXp; ++c) a.Xa[n * a.CXp + c] = 0.0;   // fixedA = 2: columns Q + 1 .. 2 Q hold mu^2
   }
-  red[threadIdx.x] = kl;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) a.klpart[blockIdx.x] = red[0];
+  const double tot = block_sum<256>(red, kl);
+  if (threadIdx.x == 0) a.klpart[blockIdx.x] = tot;
 }
 
 // ------------------------------------------------------------------------------------------------ Psi1
@@ -447,11 +442,8 @@ __global__ void p1_scalars_kernel(const double* klpart, int nblocks, double sumY
   __shared__ double red[256];
   double part = 0.0;
   if (!regimeA) for (int i = threadIdx.x; i < nblocks; i += 256) part += klpart[i];
-  red[threadIdx.x] = part;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
+  const double kl = block_sum<256>(red, part);
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const double kl = red[0];
     sc[SC_SUM_YYT] = sumYY;
     sc[SC_PSI0] = sf2 * nlocal;
     sc[SC_KL] = regimeA ? 0.0 : kl;
@@ -1180,7 +1172,7 @@ __global__ void __launch_bounds__(256) p2_reduce_kernel(const double* __restrict
     }
     red[threadIdx.x] = s;
     __syncthreads();
-    for (int k = 128; k >= 8; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
+    block_fold<256, 8>([&](int i, int j) { red[i] += red[j]; });
     if (threadIdx.x < 8 && c0 + threadIdx.x < CXp) R[c0 + threadIdx.x] = red[threadIdx.x];
     __syncthreads();
   }
@@ -1226,7 +1218,8 @@ __global__ void __launch_bounds__(256) point_kernel(PtArgs a) {
       const double* row = hz + pi * a.CZp;
       const double h = row[0], hzq = row[1 + q], hz2 = row[1 + a.Q + q];
       const double m = a.mu[n0 * a.Q + e], s = a.S[n0 * a.Q + e], al = a.alpha[q];
-      const double d1 = al * s + 1.0, u = al / d1;
+      const VarQ f = var_q(al, s);
+      const double d1 = f.d1, u = f.u;
       const double quad = m * m * h - 2.0 * m * hzq + hz2;
       contrib[e] = -0.5 * (quad / (d1 * d1) + (s / d1) * h);
       a.gmu[n0 * a.Q + e] = -(m + a.shift[q]) - u * (m * h - hzq);      // the KL term's -mu in the caller's coordinates; m is centred
@@ -1262,10 +1255,8 @@ __global__ void colsum2_kernel(const double* __restrict__ a, int rows_a, int lda
   };
   strided(a, rows_a, lda);
   if (b) strided(b, rows_b, ldb);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k]; __syncthreads(); }
-  if (threadIdx.x == 0) out[q] = red[0];
+  const double tot = block_sum<256>(red, s);
+  if (threadIdx.x == 0) out[q] = tot;
 }
 
 // fixed-embedding fast path: regime A without embedding gradients and Q + 1 <= 12 feature columns (p2_fast8_kernel)

@@ -11,6 +11,7 @@
 #include "fexp.h"
 #include "quad_mma.h"
 #include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 
 namespace gp {
@@ -25,14 +26,13 @@ __global__ void __launch_bounds__(256) b_tables_kernel(const double* __restrict_
   for (long n = blockIdx.x * 256L + threadIdx.x; n < Np; n += (long)gridDim.x * 256L) {
     double l = log(sf2);   // half of ln c2 = ln sf2 - 1/4 sum ln(2 a S + 1)
     for (int q = 0; q < Q; ++q) {
-      const double a = alpha[q], s = S[n * Q + q];
-      const double d2 = 2.0 * a * s + 1.0, w = a / d2;
-      Wn[n * Q + q] = w;
-      Vn[n * Q + q] = -0.25 * (a - w);
-      V2P[n * QB + q] = 0.5 * (a - w);      // -2 V_nq (columns >= Q stay zero from the allocation)
-      WP[n * QB + q] = w;
+      const VarQ f = var_q(alpha[q], S[n * Q + q]);
+      Wn[n * Q + q] = f.w;
+      Vn[n * Q + q] = -0.5 * f.v2;
+      V2P[n * QB + q] = f.v2;               // -2 V_nq (columns >= Q stay zero from the allocation)
+      WP[n * QB + q] = f.w;
       MUP[n * QB + q] = mu[n * Q + q];
-      l -= 0.25 * log(d2);
+      l -= var_half_log2(f);
     }
     lnc2h[n] = l;
   }
@@ -75,6 +75,7 @@ __global__ void __launch_bounds__(256) b_le_kernel(const double* __restrict__ MU
     double e[CPL], ea[CPL];
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
+      // lea_sums (varpoint.h), kept verbatim on the registers: the call changes the register allocation
       double s = 0.0, t = 0.0;
 #pragma unroll
       for (int q = 0; q < QT; ++q) {
@@ -83,7 +84,7 @@ __global__ void __launch_bounds__(256) b_le_kernel(const double* __restrict__ MU
         t = fma(v2[q] * z[c][q], z[c][q], t);
       }
       const bool live = n < N && col + c < M;
-      e[c] = live ? l0 - 0.5 * s : kPadLog;
+      e[c] = live ? l0 - 0.5 * s : kPadLog;      // le_value and lea_value (varpoint.h)
       ea[c] = live ? e[c] - 0.5 * t : kPadLog;   // V = -V2P / 2
     }
     if (CPL == 2) {
@@ -649,7 +650,7 @@ __global__ void __launch_bounds__(512, QT == 8 ? 4 : (QT <= 6 ? 5 : 3)) psi2_sym
           s1[qi] = fma(zq, r, s1[qi]); s2[qi] = fma(zq * zq, r, s2[qi]); s3[qi] = fma(zq, tq, s3[qi]);
         }
       }
-      // the waves' sums go to pp as they are, one group per wave (a.ngrp = waves): psi2_points_finish_kernel adds the groups in wave order, and the [waves][PW]
+      // the waves' sums go to pp as they are, one group per wave (a.ngrp = waves): pt2_points_finish_kernel adds the groups in wave order, and the [waves][PW]
       // LDS array of r03-r05 with its second barrier is gone (r06).  The sums across the wave as ONE reduce-scatter of the pass's 3 QC (+ 1) values (lane_reduce.h):
       // about one cross-lane move and one add per value where 3 QC + 1 butterfly sums took six of each (372 ds_bpermute per point at QT = 10), and one store
       // by the lanes that end up owning a sum instead of 3 QC + 1 single-lane stores.
@@ -664,32 +665,6 @@ __global__ void __launch_bounds__(512, QT == 8 ? 4 : (QT <= 6 ? 5 : 3)) psi2_sym
       if (lane < NV) ppw[(long)row * a.Np] = tot;
     });
     __syncthreads();       // every row of rt has been read and cleared before the next point's tiles add to it
-  }
-}
-
-// per-point finish of the psi2 part from the running sums pp[n] = [sr, zr_q, z2r_q, zt_q]
-__global__ void __launch_bounds__(256) psi2_points_finish_kernel(PB2Args a) {
-  __shared__ double redq[256];
-  for (int q = 0; q < a.Q; ++q) {
-    double ga = 0.0;
-    for (long n = blockIdx.x * 256L + threadIdx.x; n < a.N; n += (long)gridDim.x * 256L) {
-      double sr = 0.0, zr = 0.0, z2r = 0.0, zt = 0.0;
-      for (int sp = 0; sp < a.ngrp; ++sp) {                     // one slab of sums per group of column slabs (workgroup row)
-        const double* ppn = a.pp + (long)sp * (3 * a.QB + 1) * a.Np + n;
-        sr += ppn[0]; zr += ppn[(long)(1 + q) * a.Np]; z2r += ppn[(long)(1 + a.QB + q) * a.Np]; zt += ppn[(long)(1 + 2 * a.QB + q) * a.Np];
-      }
-      const double s = a.S[n * a.Q + q], al = a.alpha[q], w = a.Wn[n * a.Q + q], mu = a.mu[n * a.Q + q];
-      const double d2 = 2.0 * al * s + 1.0;
-      const double quad = 4.0 * mu * mu * sr - 8.0 * mu * zr + 2.0 * z2r + 2.0 * zt;
-      ga += -0.25 * quad / (d2 * d2) - (s / d2) * sr;
-      a.gmu[n * a.Q + q] += -w * (2.0 * mu * sr - 2.0 * zr);
-      a.gS[n * a.Q + q] += 0.5 * w * w * quad - w * sr;
-    }
-    redq[threadIdx.x] = ga;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) redq[threadIdx.x] += redq[threadIdx.x + k]; __syncthreads(); }
-    if (threadIdx.x == 0) a.gapart2[(long)blockIdx.x * a.Q + q] = redq[0];
-    __syncthreads();
   }
 }
 
@@ -936,9 +911,12 @@ int run_phase2_b(gp_ctx* c) {
     })));
   }
   GP_EV(c, 13);
-  GP_LAUNCH(c, c->stream, psi2_points_finish_kernel, dim3((unsigned)std::min<long>(p.pb_blocks, 256)), dim3(256), 0, a);
   const long MQ = (long)c->M * c->Q;
-  const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);      // psi2_points_finish_kernel's grid (one gapart2 row per workgroup)
+  const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);      // pt2_points_finish_kernel's grid (one gapart2 row per workgroup)
+  PT2Fin f;      // the points' finish from pp [ngrp][3 QB + 1][Np]
+  f.pp = p.pp; f.Wn = p.Wn; f.mu = c->mu; f.S = c->S; f.alpha = c->alpha; f.gmu = c->gXmu; f.gS = c->gXs; f.gapart2 = p.gapart2;
+  f.n0 = 0; f.n1 = c->N; f.CH = c->Np; f.GS = (3L * p.QB + 1) * c->Np; f.Q = c->Q; f.QK = p.QB; f.ngrp = a.ngrp; f.accumulate = 0;
+  GP_TRY_RC(launch_points_finish(c, fin_blocks, f));
   if (gen) {
     // grad_Z's psi2 part is in c->grads already: only the alpha partials of the points' finish are left
     GP_LAUNCH(c, c->stream, pb2_reduce_kernel, dim3((unsigned)std::min<long>((MQ + c->Q + 255) / 256, 1024)), dim3(256), 0, p.Gtmp, p.gapart2, 0, fin_blocks, MQ,

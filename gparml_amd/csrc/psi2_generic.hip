@@ -4,7 +4,7 @@
 //   psi2_n[m, m'] = exp(LEA[n, m] + LEA[n, m'] + sum_q (-2 V_nq) z_mq z_m'q)                 (the factorised form of psi2.hip's header)
 // for a chunk of P points in HBM ([P][M][M] doubles, <= 64 MB) and runs both phases on it with one thread per output element:
 //   phase 1   Psi2 += sum_p psi2_p
-//   phase 2   T_p = Bbar o psi2_p;  r_p = T_p 1,  t_p = T_p Z;  per-point sums [sr, zr_q, z2r_q, zt_q] -> pp (finished by psi2_points_finish_kernel);
+//   phase 2   T_p = Bbar o psi2_p;  r_p = T_p 1,  t_p = T_p Z;  per-point sums [sr, zr_q, z2r_q, zt_q] -> pp (finished by pt2_points_finish_kernel);
 //             grad_Z[m, q] += sum_p -alpha_q (z_mq r - t) + w_pq (2 mu_pq r - z_mq r - t)
 // No symmetry is used to save work and every operand comes from memory: correct for every Q, M and N, at a fraction of the tuned kernels' rate (a latent space
 // that wide is outside BASELINE.json's configurations; the reference itself needs an (N, M, M, Q) tensor for it, partial_terms.py:273).
@@ -13,30 +13,6 @@
 #include <algorithm>
 
 namespace gp {
-
-// LE and LEA [Np][Mp] as b_le_kernel writes them (padded entries = kPadLog), Q at run time
-__global__ void __launch_bounds__(256) b_le_generic_kernel(const double* __restrict__ MUP, const double* __restrict__ WP, const double* __restrict__ V2P,
-                                                            const double* __restrict__ lnc2h, const double* __restrict__ ZP, long N, long Np, int M,
-                                                            int Mp, int Q, double* __restrict__ LE, double* __restrict__ LEA) {
-  const long total = Np * Mp;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const long n = e / Mp;
-    const int m = (int)(e - n * Mp);
-    double le = kPadLog, lea = kPadLog;
-    if (n < N && m < M) {
-      double s = 0.0, t = 0.0;
-      for (int q = 0; q < Q; ++q) {
-        const double z = ZP[(long)m * Q + q], d = MUP[n * Q + q] - z;
-        s = fma(WP[n * Q + q] * d, d, s);
-        t = fma(V2P[n * Q + q] * z, z, t);
-      }
-      le = lnc2h[n] - 0.5 * s;
-      lea = le - 0.5 * t;                        // V = -V2P / 2
-    }
-    LE[e] = le;
-    LEA[e] = lea;
-  }
-}
 
 // T[p][m][m'] = (Bbar ? Bbar[m][m'] : 1) * psi2_(n0 + p)[m][m']
 __global__ void __launch_bounds__(256) psi2n_generic_kernel(const double* __restrict__ LEA, const double* __restrict__ V2P, const double* __restrict__ ZP,
@@ -141,9 +117,11 @@ static int ensure_generic(gp_ctx* c) {
 
 int run_le_generic(gp_ctx* c) {
   const BPlan& p = *c->bplan;
-  GP_LAUNCH(c, c->stream, b_le_generic_kernel, dim3(grid_of(c->Np * c->Mp)), dim3(256), 0, (const double*)p.MUP, (const double*)p.WP,
-            (const double*)p.V2P, (const double*)p.lnc2h, (const double*)p.ZP, (long)c->N, (long)c->Np, c->M, c->Mp, c->Q, p.LE, p.LET);
-  return GP_OK;
+  // the tables are exactly Q wide on this path (QB = Q)
+  LeaRows a;
+  a.mu = p.MUP; a.w = p.WP; a.v2 = p.V2P; a.ld = p.QB; a.lnc2h = p.lnc2h; a.ldl = 1; a.Z = p.ZP; a.ldz = p.QB; a.Q = c->Q;
+  a.cnt = c->N; a.rows = c->Np; a.M = c->M; a.Mp = c->Mp; a.mask = nullptr; a.LE = p.LE; a.LEA = p.LET;
+  return launch_lea_rows(c, c->stream, a);
 }
 
 int run_phase1_b_generic(gp_ctx* c) {

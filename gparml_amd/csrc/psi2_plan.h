@@ -56,6 +56,14 @@ struct BPlan {
   }
 };
 
+// the points' finish of phase 2 (psi2_tile.hip) for the points n0 <= n < n1: row i of group g of the summed sums [sr | zr_q | z2r_q | zt_q] of point n sits at
+// pp[g GS + i CH + n - n0], the rows of one kind QK apart; ngrp groups are added in order
+struct PT2Fin {
+  const double* pp; const double* Wn; const double* mu; const double* S; const double* alpha;
+  double* gmu; double* gS; double* gapart2; long n0, n1, CH, GS; int Q, QK, ngrp, accumulate;
+};
+int launch_points_finish(gp_ctx* c, int blocks, const PT2Fin& f);
+
 // shared by the psi2 trio
 int run_le_generic(gp_ctx* c);
 int run_phase1_b_generic(gp_ctx* c);

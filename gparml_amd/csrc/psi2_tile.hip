@@ -21,6 +21,7 @@
 #include "fexp.h"
 #include "quad_mma.h"
 #include "lane_reduce.h"
+#include "varpoint.h"
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -381,30 +382,29 @@ __global__ void __launch_bounds__(256) pt2_sum_tiles_kernel(double* __restrict__
   }
 }
 
-// per-point finish from the summed sums [sr | zr_q | z2r_q | zt_q] (psi2.hip, psi2_points_finish_kernel)
-struct PT2Fin {
-  const double* pp; const double* Wn; const double* mu; const double* S; const double* alpha;
-  double* gmu; double* gS; double* gapart2; long n0, n1, CH; int Q, accumulate;
-};
+// per-point finish from the summed sums [sr | zr_q | z2r_q | zt_q] (PT2Fin, psi2_plan.h): the psi2 parts of grad_X_mu, grad_X_S and, one row of gapart2 per
+// workgroup, of grad_alpha.  The sums over the groups start from the first group's own value.
 __global__ void __launch_bounds__(256) pt2_points_finish_kernel(PT2Fin a) {
   __shared__ double redq[256];
   for (int q = 0; q < a.Q; ++q) {
     double ga = 0.0;
     for (long n = a.n0 + blockIdx.x * 256L + threadIdx.x; n < a.n1; n += (long)gridDim.x * 256L) {
       const long k = n - a.n0;
-      const double sr = a.pp[k], zr = a.pp[(long)(1 + q) * a.CH + k], z2r = a.pp[(long)(1 + a.Q + q) * a.CH + k],
-                   zt = a.pp[(long)(1 + 2 * a.Q + q) * a.CH + k];
-      const double s = a.S[n * a.Q + q], al = a.alpha[q], w = a.Wn[n * a.Q + q], mu = a.mu[n * a.Q + q];
-      const double d2 = 2.0 * al * s + 1.0;
+      const double* ppn = a.pp + k;
+      double sr = ppn[0], zr = ppn[(long)(1 + q) * a.CH], z2r = ppn[(long)(1 + a.QK + q) * a.CH], zt = ppn[(long)(1 + 2 * a.QK + q) * a.CH];
+      for (int g = 1; g < a.ngrp; ++g) {
+        ppn += a.GS;
+        sr += ppn[0]; zr += ppn[(long)(1 + q) * a.CH]; z2r += ppn[(long)(1 + a.QK + q) * a.CH]; zt += ppn[(long)(1 + 2 * a.QK + q) * a.CH];
+      }
+      const double s = a.S[n * a.Q + q], w = a.Wn[n * a.Q + q], mu = a.mu[n * a.Q + q];
+      const double d2 = var_q(a.alpha[q], s).d2;
       const double quad = 4.0 * mu * mu * sr - 8.0 * mu * zr + 2.0 * z2r + 2.0 * zt;
       ga += -0.25 * quad / (d2 * d2) - (s / d2) * sr;
       a.gmu[n * a.Q + q] += -w * (2.0 * mu * sr - 2.0 * zr);
       a.gS[n * a.Q + q] += 0.5 * w * w * quad - w * sr;
     }
-    redq[threadIdx.x] = ga;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) { if (threadIdx.x < k) redq[threadIdx.x] += redq[threadIdx.x + k]; __syncthreads(); }
-    if (threadIdx.x == 0) { double* d = a.gapart2 + (long)blockIdx.x * a.Q + q; *d = (a.accumulate ? *d : 0.0) + redq[0]; }
+    const double tot = block_sum<256>(redq, ga);
+    if (threadIdx.x == 0) { double* d = a.gapart2 + (long)blockIdx.x * a.Q + q; *d = (a.accumulate ? *d : 0.0) + tot; }
     __syncthreads();
   }
 }
@@ -429,6 +429,11 @@ __global__ void __launch_bounds__(256) pt2_gz_reduce_kernel(const double* __rest
     }
     grads[i] += s;
   }
+}
+
+int launch_points_finish(gp_ctx* c, int blocks, const PT2Fin& f) {
+  GP_LAUNCH(c, c->stream, pt2_points_finish_kernel, dim3(blocks), dim3(256), 0, f);
+  return GP_OK;
 }
 
 int pt2_width(int Q) { return Q <= 3 ? 4 : Q <= 7 ? 8 : Q <= 11 ? 12 : Q <= 15 ? 16 : Q <= 23 ? 24 : Q <= 31 ? 32 : Q <= 39 ? 40 : Q <= 51 ? 52 : Q <= 63 ? 64 : 0; }
@@ -478,7 +483,7 @@ int run_phase2_b_tiles(gp_ctx* c) {
   a.dbg = dbg;
 #endif
   PT2Fin f;
-  f.pp = tb.ppt; f.Wn = p.Wn; f.mu = c->mu; f.S = c->S; f.alpha = c->alpha; f.gmu = c->gXmu; f.gS = c->gXs; f.gapart2 = p.gapart2; f.CH = tb.ch; f.Q = Q;
+  f.pp = tb.ppt; f.Wn = p.Wn; f.mu = c->mu; f.S = c->S; f.alpha = c->alpha; f.gmu = c->gXmu; f.gS = c->gXs; f.gapart2 = p.gapart2; f.CH = tb.ch; f.GS = 0; f.Q = Q; f.QK = Q; f.ngrp = 1;
   const int fin_blocks = (int)std::min<long>(p.pb_blocks, 256);
   GP_EV(c, 12);
   int k = 0;
@@ -489,7 +494,7 @@ int run_phase2_b_tiles(gp_ctx* c) {
     GP_LAUNCH(c, c->stream, pt2_sum_tiles_kernel, dim3((unsigned)std::min<long>(((long)PW * cnt + 255) / 256, 4096)), dim3(256), 0, tb.ppt, T, PW,
               tb.ch, cnt);
     f.n0 = a.n0; f.n1 = a.n1; f.accumulate = a.accumulate;
-    GP_LAUNCH(c, c->stream, pt2_points_finish_kernel, dim3(fin_blocks), dim3(256), 0, f);
+    GP_TRY_RC(launch_points_finish(c, fin_blocks, f));
   }
   GP_EV(c, 13);
 #ifdef GPARML_TILE_TIMING

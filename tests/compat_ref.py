@@ -372,7 +372,7 @@ CASES = [
     ('B_q31', 60, 2, 40, 31, 'B', 0.08),                  # 32
     ('B_q40_Dp256', 50, 129, 20, 40, 'B', 0.05),          # psi1_wide_kernel<52>
     ('B_q63_spare_column', 45, 2, 12, 63, 'B', 0.05),     # 64
-    ('B_q64_generic_psi2', 40, 2, 9, 64, 'B', 0.05),      # b_le_generic_kernel + psi1_wide_kernel<64>
+    ('B_q64_generic_psi2', 40, 2, 9, 64, 'B', 0.05),      # lea_rows_kernel + psi1_wide_kernel<64>
     ('B_q70_generic', 40, 2, 9, 70, 'B', 0.05),           # ... + psi1_generic_kernel
     ('A_q2_Mp384', 130, 4, 257, 2, 'A', 30.0),            # WC 2, the fixed-variance form; 257 inducing points in the plane
     ('A_q30', 100, 3, 40, 30, 'A', 0.05),

@@ -13,7 +13,7 @@ What is computed (``phase1`` and ``phase2``; oracle/factorised.py states the sam
             grad_z_data (M, Q), grad_alpha_data (Q,): the contractions of dpsi1ty_dz, dpsi2_dz, dpsi1ty_dalpha, dpsi2_dalpha with Abar and Bbar
             (partial_terms.py:207-240, 286-299 without the K_mm terms), and grad_x_mu, grad_x_s (N, Q) (partial_terms.py:367-431) with their KL parts.
 
-What the device arrays hold (read from finish_kernel, psi2_points_finish_kernel, point_kernel and p2_reduce_kernel).
+What the device arrays hold (read from finish_kernel, pt2_points_finish_kernel, point_kernel and p2_reduce_kernel).
   * ``grads`` (gp_debug_peek) = grad_z_data | grad_alpha_data: the sums over the points only.  gp_finish adds the global step's gK to it, and gK holds
     the K_mm parts AND the term -1/4 sum (Bbar o Psi2)(z - z')^2 of grad_alpha, which needs the reduced Psi2 only (csrc/linalg.hip).  So that term is
     NOT part of grad_alpha_data, exactly as oracle.factorised.phase2 leaves it to finish().

@@ -1,6 +1,6 @@
 """The free-embedding (regime B) kernels of both phases against tests/psi2_ref.py, element by element: psi2_pairs_kernel, psi2_pairs_mfma_kernel, the
 generic path and their reduces in phase 1; psi2_cols_kernel, psi2_sym_kernel, psi2_tile_kernel, the generic path, bbar_interleave_kernel,
-psi2_points_finish_kernel and the pb2 reduces in phase 2.  The global step is taken out of the comparison: the device's own Bbar and Abar
+pt2_points_finish_kernel and the pb2 reduces in phase 2.  The global step is taken out of the comparison: the device's own Bbar and Abar
 (gp_debug_peek) are the exact float64 inputs of the phase-2 reference, so every output is a plain sum of products of exponentials and is held to
 |dev - ref| <= 2 (T + n_terms u A) + 2^-1022 with the long-double value and the derived A, T of psi2_ref's docstring -- about eight orders of magnitude
 below the 1e-5 of a block's largest entry that the parity tests can ask for behind the global step.  One case per launch shape (psi2_ref.CASES), the
