@@ -209,8 +209,8 @@ extern "C" int gp_debug_gemm(int device, int ta, int tb, int m, int n, int k, do
   GP_HIP(ctx, hipMemcpy(dA, hA.data(), hA.size() * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dB, hB.data(), hB.size() * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dC, hC.data(), hC.size() * 8, hipMemcpyHostToDevice));
-  GemmP p{dA, dB, dC, a_cols, b_cols, np, 0, 0, 0, (int)kp, alpha, beta, 0};
-  GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p));
+  GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1,
+                        gemm_of({dA, a_cols}, {dB, b_cols}, {dC, np}, (int)kp, alpha, beta)));
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(hC.data(), dC, hC.size() * 8, hipMemcpyDeviceToHost));
   for (long i = 0; i < m; ++i) for (long j = 0; j < n; ++j) C[i * n + j] = hC[i * np + j];
@@ -277,19 +277,15 @@ extern "C" int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int
     GP_HIP(ctx, hipMemcpy(d[i], w[i].host, (size_t)w[i].len * 8, hipMemcpyHostToDevice));
     dev[i] = d[i];
   }
-  GemmP p;
-  p.A = dev[0] + w[0].off; p.B = dev[1] + w[1].off; p.C = dev[2] + w[2].off;
-  p.lda = w[0].ld; p.ldb = w[1].ld; p.ldc = w[2].ld;
-  p.sA = w[0].s; p.sB = w[1].s; p.sC = w[2].s; p.oA = w[0].o; p.oB = w[1].o; p.oC = w[2].o;
-  p.K = k; p.alpha = alpha; p.beta = beta; p.tri = tri; p.inner = batch_inner;
-  p.klow = klow; p.mirror = mirror; p.splits = splits; p.big = big;
   if (splits > 1) {
     // split-k workspace: batch * tiles * splits partial tiles, filled with NaN bytes so that a partial nobody wrote shows in the sum
     GP_TRY_RC(dW.alloc(ctx, (size_t)batch * tx * ty * splits * TILE * TILE, DA_RAW));
     GP_HIP(ctx, hipMemset(dW, 0xFF, dW.bytes()));
-    p.ws = dW;
   }
-  GP_TRY_RC(launch_gemm(ctx, nullptr, la == K_CONTIG ? K_CONTIG : FREE_CONTIG, lb == K_CONTIG ? K_CONTIG : FREE_CONTIG, m, n, batch, p));
+  auto in = [&](int i) { return GemmIn{dev[i] + w[i].off, w[i].ld, w[i].s, w[i].o}; };
+  GP_TRY_RC(launch_gemm(ctx, nullptr, la == K_CONTIG ? K_CONTIG : FREE_CONTIG, lb == K_CONTIG ? K_CONTIG : FREE_CONTIG, m, n, batch,
+                        gemm_of(in(0), in(1), {dev[2] + w[2].off, w[2].ld, w[2].s, w[2].o}, k, alpha, beta)
+                            .triangle(tri, klow, mirror).batched(batch_inner).split(splits, dW.get()).on_big(big)));
   GP_HIP(ctx, hipDeviceSynchronize());
   GP_HIP(ctx, hipMemcpy(C, dev[2], (size_t)w[2].len * 8, hipMemcpyDeviceToHost));
   return GP_OK;
@@ -311,7 +307,7 @@ extern "C" int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int
   GP_TRY_RC(dA.alloc(ctx, na, DA_RAW)); GP_TRY_RC(dB.alloc(ctx, nb, DA_RAW)); GP_TRY_RC(dC.alloc(ctx, ncc, DA_RAW));
   GP_HIP(ctx, hipMemcpy(dA, h.data(), na * 8, hipMemcpyHostToDevice));
   GP_HIP(ctx, hipMemcpy(dB, h.data(), nb * 8, hipMemcpyHostToDevice));
-  GemmP p{dA, dB, dC, a_cols, b_cols, np, 0, 0, 0, (int)kp, 1.0, 0.0, 0};
+  const GemmP p = gemm_of({dA, a_cols}, {dB, b_cols}, {dC, np}, (int)kp);
   hipEvent_t e0, e1;
   GP_HIP(ctx, hipEventCreate(&e0)); GP_HIP(ctx, hipEventCreate(&e1));
   GP_TRY_RC(launch_gemm(ctx, nullptr, ta ? FREE_CONTIG : K_CONTIG, tb ? K_CONTIG : FREE_CONTIG, (int)mp, (int)np, 1, p));

@@ -1,5 +1,5 @@
 // The 32 x 32-tile FP64 product of the global step as a device function: gemm32_kernel (gemm.hip) runs one tile per workgroup; the fused
-// small-M tail of the global step (linalg.hip: gs_tail128_kernel) walks the same tiles from a persistent grid.  One body, so both give the
+// small-M tail of the global step (linalg.hip: tail_stage_kernel) walks the same tiles, one work item per workgroup.  One body, so both give the
 // same bits.
 #pragma once
 #include "gp_common.h"

@@ -33,15 +33,16 @@ inline int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n 
 inline int psi1_qp(int Q) { return Q <= 16 ? (Q + 1) / 2 * 2 : Q <= 24 ? 24 : Q <= 32 ? 32 : Q <= 52 ? 52 : Q <= 64 ? 64 : 0; }
 
 // dense batched GEMM on tile-aligned buffers: C = alpha * op(A) op(B) + beta * C
+// A product is built in one expression by gemm_of() and the setters below, at the point of the call; no field is assigned afterwards.
 struct GemmP {
-  const double* A;
-  const double* B;
-  double* C;
-  long lda, ldb, ldc;
-  long sA, sB, sC;  // batch strides (doubles) of the inner batch index
-  int K;            // multiple of KC
-  double alpha, beta;
-  int tri;          // 0 all tiles, 1 only tiles with row-tile >= col-tile (lower), 2 only upper
+  const double* A = nullptr;
+  const double* B = nullptr;
+  double* C = nullptr;
+  long lda = 0, ldb = 0, ldc = 0;
+  long sA = 0, sB = 0, sC = 0;  // batch strides (doubles) of the inner batch index
+  int K = 0;            // multiple of KC
+  double alpha = 0.0, beta = 0.0;
+  int tri = 0;          // 0 all tiles, 1 only tiles with row-tile >= col-tile (lower), 2 only upper
   int inner = 1 << 30;  // blockIdx.z = i + inner * o: inner index i uses sA/sB/sC, outer index o uses oA/oB/oC
   long oA = 0, oB = 0, oC = 0;
   int splits = 1;       // split-k: partial tiles go to ws, gemm_splitk_reduce applies alpha/beta (small grids only)
@@ -56,7 +57,25 @@ struct GemmP {
   // (the fused tail of the global step walks gemm32_tile itself and never sets mirror).
   int klow = 0, mirror = 0;
   int big = 0;          // 1: the 128 x 128-tile kernel (with splits) whatever the tile count (the M x M x M products at M >= 1024)
+  // the modifiers: each returns the product with one group of fields set
+  __host__ __device__ GemmP triangle(int t, int kl = 0, int mir = 0) const { GemmP p = *this; p.tri = t; p.klow = kl; p.mirror = mir; return p; }
+  __host__ __device__ GemmP batched(int inner_count) const { GemmP p = *this; p.inner = inner_count; return p; }
+  __host__ __device__ GemmP split(int s, double* w) const { GemmP p = *this; p.splits = s; p.ws = w; return p; }
+  __host__ __device__ GemmP on_big(int b) const { GemmP p = *this; p.big = b; return p; }
 };
+// an operand of a product: pointer, leading dimension, inner and outer batch stride (doubles)
+template <class T> struct GemmOpT { T* p; long ld; long s = 0, o = 0; };
+using GemmIn = GemmOpT<const double>;
+using GemmOut = GemmOpT<double>;
+// C = alpha op(A) op(B) + beta C over K; every other field keeps GemmP's default
+__host__ __device__ inline GemmP gemm_of(GemmIn A, GemmIn B, GemmOut C, int K, double alpha = 1.0, double beta = 0.0) {
+  GemmP p;
+  p.A = A.p; p.lda = A.ld; p.sA = A.s; p.oA = A.o;
+  p.B = B.p; p.ldb = B.ld; p.sB = B.s; p.oB = B.o;
+  p.C = C.p; p.ldc = C.ld; p.sC = C.s; p.oC = C.o;
+  p.K = K; p.alpha = alpha; p.beta = beta;
+  return p;
+}
 // m, n multiples of TILE; la/lb: Layout of A (free index = rows of C) and B (free index = cols of C).  c may be NULL (the debug hooks).  GP_ERR_STATE,
 // with nothing launched, when C meets an operand (checked for batch entry 0 only) or mirror comes with beta != 0; GP_ERR_HIP when a launch is refused
 int launch_gemm(gp_ctx* c, hipStream_t st, Layout la, Layout lb, int m, int n, int batch, const GemmP& p);

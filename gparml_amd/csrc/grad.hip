@@ -315,17 +315,8 @@ int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dv
     GP_TRY_RC(pred_chunk_front(c, X, nullptr, 0, n0, cnt, p.X, need_l ? p.R.get() : nullptr, 2 * Mp));
     GP_LAUNCH(c, st, grad_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, pred_chunk_psi1(c), p.X, c->Zt, c->alpha, cnt, rows, c->M, (int)Mp,
               (int)Q, p.dK);
-    GemmP g;
-    g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0; g.beta = 0.0;
-    g.A = p.dK; g.lda = Mp; g.ldc = ldt;
-    if (need_e) {
-      g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.C = p.T;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g));
-    }
-    if (need_l) {
-      g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = p.T + Dp;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g));
-    }
+    if (need_e) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.dK, Mp}, {c->gstep.E, Dp}, {p.T, ldt}, (int)Mp, c->beta)));
+    if (need_l) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.dK, Mp}, {c->gstep.Linv, Mp}, {p.T + Dp, ldt}, (int)Mp)));
     GradArgs a;
     a.T = p.T; a.R = p.R; a.alpha = c->alpha; a.ldt = ldt; a.M = c->M; a.Mp = (int)Mp; a.D = (int)D; a.Dp = (int)Dp; a.Q = (int)Q; a.sf2 = c->sf2;
     a.need_e = need_e; a.need_l = need_l;

@@ -542,10 +542,7 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
   GP_HIP(c, hipMemcpyAsync(p.cols, hc.data(), (size_t)Do * sizeof(int), hipMemcpyHostToDevice, st));
   GP_LAUNCH(c, st, inf_gather_e_kernel, dim3(inf_blocks(Mp * Dop)), dim3(256), 0, c->gstep.E, p.cols, (int)M, (int)Mp, c->Dp, Do, (int)Dop, k.Eo);
   GP_LAUNCH(c, st, inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
-  GemmP g;
-  g.K = (int)Dop; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
-  g.A = k.Eo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = p.T; g.ldc = Mp; g.alpha = c->beta * c->beta; g.beta = 0.0;
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, g));
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, 1, gemm_of({k.Eo, Dop}, {k.Eo, Dop}, {p.T, Mp}, (int)Dop, c->beta * c->beta)));
   GP_LAUNCH(c, st, inf_gfold_kernel, dim3(inf_blocks(Mp * Mp, 4096)), dim3(256), 0, p.T, c->gstep.Inv, (int)M, (int)Mp, (double)Do, p.Gf);
   // the observed columns of every row, packed on the host: the others are never read
   std::vector<double> yc((size_t)n * Do);
@@ -569,8 +566,7 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
     GP_HIP(c, hipMemcpyAsync(k.xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
     GP_HIP(c, hipMemcpyAsync(k.Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
     GP_LAUNCH(c, st, inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, k.Yc, cnt, rows, Do, (int)Dop, k.Yo, k.yy);
-    g.A = k.Yo; g.lda = Dop; g.B = k.Eo; g.ldb = Dop; g.C = k.V; g.ldc = Mp; g.alpha = c->beta; g.beta = 0.0;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, g));
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, gemm_of({k.Yo, Dop}, {k.Eo, Dop}, {k.V, Mp}, (int)Dop, c->beta)));
     if (mode == 0) {
       GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
       if (L) GP_HIP(c, hipMemcpyAsync(L + n0, k.fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));

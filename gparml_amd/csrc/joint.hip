@@ -278,10 +278,8 @@ int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jit
     for (long s = 0; s < g; ++s)
       GP_HIP(c, hipMemcpy2DAsync(d.eps + s * D, (size_t)cols * 8, eps + (s0 + s) * n * D, (size_t)D * 8, (size_t)D * 8, (size_t)n, hipMemcpyHostToDevice, st));
     GP_LAUNCH(c, st, joint_fill_mean_kernel, dim3((unsigned)blocks_for(np * cols)), dim3(256), 0, p.mean, n, (int)D, np, cols, g * D, d.out);
-    GemmP q;
-    q.A = p.cov; q.lda = np; q.B = d.eps; q.ldb = cols; q.C = d.out; q.ldc = cols;     // Lc [i][k] K_CONTIG, eps [k][column] FREE_CONTIG
-    q.sA = q.sB = q.sC = 0; q.K = (int)np; q.alpha = 1.0; q.beta = 1.0; q.tri = 0;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)np, (int)cols, 1, q));
+    // out += Lc eps: Lc [i][k] K_CONTIG, eps [k][column] FREE_CONTIG
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)np, (int)cols, 1, gemm_of({p.cov, np}, {d.eps, cols}, {d.out, cols}, (int)np, 1.0, 1.0)));
     for (long s = 0; s < g; ++s)
       GP_HIP(c, hipMemcpy2DAsync(out + (s0 + s) * n * D, (size_t)D * 8, d.out + s * D, (size_t)cols * 8, (size_t)D * 8, (size_t)n, hipMemcpyDeviceToHost, st));
   }

@@ -28,18 +28,25 @@ std::atomic<int> g_opt_residual_dd{1};   // the refinement residual through ddac
 std::atomic<int> g_opt_trtri_rec{1};     // L^-1 by halves: two batched launches per level instead of two per block row
 std::atomic<int> g_opt_gemm_big{1};      // the M x M x {M, D} products on the 128 x 128-tile kernel (split-k 8 at M = 1024) for Mp >= 1024
 
-constexpr int kSplitK = 8;
 // split-k factor for a product of `tiles` 128 x 128 output tiles (batch included) with contraction length K on the 128-tile kernel: about 512 workgroups
 // (two per CU), a power of two <= 8 that divides the number of k-chunks, and whose partial tiles fit the workspace (cap doubles)
 static int choose_splits(long tiles, int K, size_t cap) {
   int s = 8;
   while (s > 1 && (tiles * s > 512 || (K / KC) % s != 0 || (size_t)tiles * s * TILE * TILE > cap)) s >>= 1;
   return s;
-}   // split-k factor of the M x M x M products of the global step (latency-bound: 16 tiles alone fill 6 % of the chip)
+}
+// The one big-tile / split-k decision of the M x M x {M, D} products and X^T X: the 128 x 128-tile kernel with split-k where that gives >= 256
+// workgroups (M >= 1024: 72-74 -> 63 us per product incl. the reduce at M = 1024; at M = 2048 the M x M x M product 616 -> 392 us without a split, the
+// M x M x D ones have 128 tiles and lose to the small tiles unless split), the small tiles otherwise.  tiles: 128 x 128 output tiles, batch included;
+// cap: doubles of split-k workspace, 0 when there is none (callers pass ws ? capacity : 0; a workspace of no capacity is no workspace: the shared one
+// has a floor of 1100 tiles); gemm_big: g_opt_gemm_big.
+struct GemmPlan { int big, splits; };
+static GemmPlan gemm_plan(long tiles, int K, size_t cap, int gemm_big, int Mp) {
+  if (!gemm_big || Mp < 1024 || cap == 0) return {0, 1};
+  const int s = choose_splits(tiles, K, cap);
+  return tiles * s >= 256 ? GemmPlan{1, s} : GemmPlan{0, 1};
+}
 
-
-
-// A: [batch][Mp][Mp] SPD in, lower Cholesky factor out (upper zeroed); Linv: L^-1; Inv: A^-1; Twork: batch * Mp * Mp / 2 doubles
 // dst[b][r][0:128] = src[b][r][0:128] for r < rows: the panel solve's result from the work panel into the factor (two doubles per thread)
 __global__ void __launch_bounds__(256) panel_copy_kernel(const double* __restrict__ src, long sstride, double* __restrict__ dst, long ld, long dstride, long rows) {
   const double* s = src + (long)blockIdx.y * sstride;
@@ -51,6 +58,7 @@ __global__ void __launch_bounds__(256) panel_copy_kernel(const double* __restric
   }
 }
 
+// A: [batch][Mp][Mp] SPD in, lower Cholesky factor out (upper zeroed); Linv: L^-1; Inv: A^-1; Twork: batch * Mp * Mp / 2 doubles
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A, double* Linv, double* Inv, double* Twork,
                           double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap, bool factor_only) {
   const int nt = Mp / NB;
@@ -62,11 +70,8 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
     GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3(batch), dim3(512), POTRF_LDS_DOUBLES * 8, A, ld, bs, j, Linv, fail_flag, logdet2);
     const int rem = nt - j - 1;
     if (rem > 0) {
+      double* Lpanel = A + ((long)(j + 1) * NB) * ld + (long)j * NB;
       // panel: L[i,j] = A[i,j] * inv(L_jj)^T, i > j   (rows rem*128, cols 128, k 128) -- through the work panel, see below
-      GemmP p;
-      p.A = A + ((long)(j + 1) * NB) * ld + (long)j * NB; p.lda = ld; p.sA = bs;
-      p.B = Linv + ((long)j * NB) * ld + (long)j * NB; p.ldb = ld; p.sB = bs;   // B(k,c) = Xjj[c][k]: stored [c][k] -> K_CONTIG
-      p.K = NB; p.alpha = 1.0; p.beta = 0.0; p.tri = 0;
       // NOT in place (r06).  Until then C was A itself, and launch_gemm's small-tile path (32 x 32 tiles for <= 256 tiles) ran it with four workgroups per 32 rows,
       // each reading all 128 columns of the rows and overwriting 32 of them: a race that timing hid -- every workgroup resident and in step, the reads over long
       // before the first store -- except on a cold start: the FIRST evaluation of a fresh process at M = 1024 with free embeddings came back with both
@@ -75,17 +80,14 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
       // logged 9.97e-5: that was this, its evaluations run in a fresh child process).  The product goes to the work panel and a copy kernel puts it
       // in place (+ ~5 us per panel; the 128 x 128-tile kernel in place -- one workgroup owns all columns of its rows -- is safe too but costs 20 us per panel).
       // profiles/r06_first_evaluation_race.txt, tests/test_gpu_first_evaluation.py.
-      p.C = Twork; p.ldc = NB; p.sC = (long)rem * NB * NB;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, NB, batch, p));
+      // B(k,c) = Xjj[c][k]: stored [c][k] -> K_CONTIG
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, NB, batch,
+                            gemm_of({Lpanel, ld, bs}, {Linv + ((long)j * NB) * ld + (long)j * NB, ld, bs}, {Twork, NB, (long)rem * NB * NB}, NB)));
       GP_LAUNCH(c, st, panel_copy_kernel, dim3((unsigned)std::min<long>(((long)rem * NB * NB / 2 + 255) / 256, 512), batch), dim3(256), 0, (const double*)Twork,
-                (long)rem * NB * NB, A + ((long)(j + 1) * NB) * ld + (long)j * NB, ld, bs, (long)rem * NB);
-      // trailing update: A[i,k] -= L[i,j] L[k,j]^T for i >= k > j (lower tiles)
-      GemmP q;
-      q.A = A + ((long)(j + 1) * NB) * ld + (long)j * NB; q.lda = ld; q.sA = bs;
-      q.B = q.A; q.ldb = ld; q.sB = bs;                                         // B(k,c) = L[c][k] -> K_CONTIG
-      q.C = A + ((long)(j + 1) * NB) * ld + (long)(j + 1) * NB; q.ldc = ld; q.sC = bs;
-      q.K = NB; q.alpha = -1.0; q.beta = 1.0; q.tri = 1;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, rem * NB, batch, q));
+                (long)rem * NB * NB, Lpanel, ld, bs, (long)rem * NB);
+      // trailing update: A[i,k] -= L[i,j] L[k,j]^T for i >= k > j (lower tiles); B(k,c) = L[c][k] -> K_CONTIG
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, rem * NB, rem * NB, batch,
+                            gemm_of({Lpanel, ld, bs}, {Lpanel, ld, bs}, {A + ((long)(j + 1) * NB) * ld + (long)(j + 1) * NB, ld, bs}, NB, -1.0, 1.0).triangle(1)));
     }
   }
   if (factor_only) return GP_OK;
@@ -100,18 +102,13 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
       auto level = [&](int p0, int np, int rows2) -> int {
         const long o11 = ((long)(2 * p0 * h) * NB) * (ld + 1), o22 = o11 + b * (ld + 1), o21 = o11 + b * ld;
         const long m2 = (long)rows2 * NB;
-        GemmP p;                                                        // T = L21 X11
-        p.A = A + o21; p.lda = ld; p.sA = ps; p.oA = bs;                // L21 [m][k], K_CONTIG
-        p.B = Linv + o11; p.ldb = ld; p.sB = ps; p.oB = bs;             // X11 stored [k][c], FREE_CONTIG
-        p.C = Twork; p.ldc = b; p.sC = m2 * b; p.oC = (long)np * m2 * b;
-        p.K = (int)b; p.alpha = 1.0; p.beta = 0.0; p.tri = 0; p.inner = np;
-        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, p));
-        GemmP q;                                                        // X21 = -X22 T
-        q.A = Linv + o22; q.lda = ld; q.sA = ps; q.oA = bs;             // X22 [m][k], K_CONTIG
-        q.B = Twork; q.ldb = b; q.sB = m2 * b; q.oB = (long)np * m2 * b;
-        q.C = Linv + o21; q.ldc = ld; q.sC = ps; q.oC = bs;
-        q.K = (int)m2; q.alpha = -1.0; q.beta = 0.0; q.tri = 0; q.inner = np;
-        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch, q));
+        const GemmOut T = {Twork, b, m2 * b, (long)np * m2 * b};
+        // T = L21 X11: L21 [m][k], K_CONTIG; X11 stored [k][c], FREE_CONTIG
+        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch,
+                              gemm_of({A + o21, ld, ps, bs}, {Linv + o11, ld, ps, bs}, T, (int)b).batched(np)));
+        // X21 = -X22 T: X22 [m][k], K_CONTIG; T stored [k][c], FREE_CONTIG
+        GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)m2, (int)b, np * batch,
+                              gemm_of({Linv + o22, ld, ps, bs}, {T.p, T.ld, T.s, T.o}, {Linv + o21, ld, ps, bs}, (int)m2, -1.0).batched(np)));
         return GP_OK;
       };
       if (full > 0) GP_TRY_RC(level(0, full, h));
@@ -120,36 +117,19 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
   } else {
     // block rows of X = L^-1: X[i,0:i] = -X_ii * (L[i,0:i] * X[0:i,0:i])
     for (int i = 1; i < nt; ++i) {
-      GemmP p;
-      p.A = A + ((long)i * NB) * ld; p.lda = ld; p.sA = bs;            // L row panel (128 x i*128), K_CONTIG
-      p.B = Linv; p.ldb = ld; p.sB = bs;                               // X[0:i,0:i] stored [k][c] -> FREE_CONTIG
-      p.C = Twork; p.ldc = Mp; p.sC = (long)NB * Mp;
-      p.K = i * NB; p.alpha = 1.0; p.beta = 0.0; p.tri = 0;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, p));
-      GemmP q;
-      q.A = Linv + ((long)i * NB) * ld + (long)i * NB; q.lda = ld; q.sA = bs;   // X_ii, K_CONTIG
-      q.B = Twork; q.ldb = Mp; q.sB = (long)NB * Mp;                            // T stored [k][c] -> FREE_CONTIG
-      q.C = Linv + ((long)i * NB) * ld; q.ldc = ld; q.sC = bs;
-      q.K = NB; q.alpha = -1.0; q.beta = 0.0; q.tri = 0;
-      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch, q));
+      // T = L[i,0:i] X[0:i,0:i]: L row panel (128 x i*128), K_CONTIG; X[0:i,0:i] stored [k][c] -> FREE_CONTIG
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch,
+                            gemm_of({A + ((long)i * NB) * ld, ld, bs}, {Linv, ld, bs}, {Twork, Mp, (long)NB * Mp}, i * NB)));
+      // X[i,0:i] = -X_ii T: X_ii, K_CONTIG; T stored [k][c] -> FREE_CONTIG
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, NB, i * NB, batch,
+                            gemm_of({Linv + ((long)i * NB) * ld + (long)i * NB, ld, bs}, {Twork, Mp, (long)NB * Mp}, {Linv + ((long)i * NB) * ld, ld, bs}, NB, -1.0)));
     }
   }
-  // A^-1 = X^T X
-  GemmP r;
-  r.A = Linv; r.lda = ld; r.sA = bs;   // A(i,k) = X[k][i]: stored [k][i] -> FREE_CONTIG
-  r.B = Linv; r.ldb = ld; r.sB = bs;   // B(k,j) = X[k][j] -> FREE_CONTIG
-  r.C = Inv; r.ldc = ld; r.sC = bs;
-  r.K = Mp; r.alpha = 1.0; r.beta = 0.0; r.tri = 0;
-  if (g_opt_xtx_tri.load()) { r.tri = 1; r.klow = 1; r.mirror = 1; }
-  if (g_opt_gemm_big.load() && Mp >= 1024 && splitk_ws) {
-    const long tiles = (long)(Mp / TILE) * (Mp / TILE) * batch;
-    r.splits = choose_splits(tiles, Mp, splitk_cap); r.ws = splitk_ws;
-    r.big = tiles * r.splits >= 256 ? 1 : 0;
-    if (!r.big) r.splits = 1;
-  } else if (splitk_ws && Mp >= 256 && Mp <= 1024 && (Mp / KC) % kSplitK == 0 && (size_t)batch * (Mp / TILE) * (Mp / TILE) * kSplitK * TILE * TILE <= splitk_cap) {
-    r.splits = kSplitK; r.ws = splitk_ws;       // (ignored by the small-tile kernel that serves these sizes)
-  }
-  GP_TRY_RC(launch_gemm(c, st, FREE_CONTIG, FREE_CONTIG, Mp, Mp, batch, r));
+  // A^-1 = X^T X: A(i,k) = X[k][i]: stored [k][i] -> FREE_CONTIG; B(k,j) = X[k][j] -> FREE_CONTIG.  xtx_tri: lower tiles, klow, mirror
+  const int xt = g_opt_xtx_tri.load() ? 1 : 0;
+  const GemmPlan pl = gemm_plan((long)(Mp / TILE) * (Mp / TILE) * batch, Mp, splitk_ws ? splitk_cap : 0, g_opt_gemm_big.load(), Mp);
+  GP_TRY_RC(launch_gemm(c, st, FREE_CONTIG, FREE_CONTIG, Mp, Mp, batch,
+                        gemm_of({Linv, ld, bs}, {Linv, ld, bs}, {Inv, ld, bs}, Mp).triangle(xt, xt, xt).on_big(pl.big).split(pl.splits, splitk_ws)));
   return GP_OK;
 }
 
@@ -570,6 +550,57 @@ __global__ void __launch_bounds__(256) colsum_kernel(const double* __restrict__ 
   colsum_block(part, rows, Q, out, blockIdx.x, red);
 }
 
+// ---------------------------------------------------------------------------------------------- the step's operands and products, named once
+// The global step's buffers (gs_view builds it from the context).  Both forms of the schedule -- run_global_step's launches and tail_stage_kernel's
+// stages -- take their operands, their products and their trace jobs from here.
+struct GsView {
+  double *Ki, *P;                                     // GsState::Inv: [Kmm^-1 ; (Kmm + beta Psi2)^-1]
+  const double *Psi2, *C, *sc;                        // the all-reduced statistics
+  double *KmmKeep, *E, *PsiE, *T1, *T2, *dFdK, *Bbar, *Abar, *Bm, *gs, *gK;
+  const double *Z, *Zt, *alpha;
+};
+static GsView gs_view(gp_ctx* c) {
+  const long mm = (long)c->Mp * c->Mp;
+  GsState& g = c->gstep;
+  return {g.Inv, g.Inv + mm, c->stats, c->stats + mm, c->stats + mm + (long)c->Mp * c->Dp,
+          g.KmmKeep, g.E, g.PsiE, g.T1, g.T2, g.dFdK, g.Bbar, g.Abar, g.Bm, g.gs, g.gK, c->Z, c->Zt, c->alpha};
+}
+// the seven traces of the bound and its partials
+static DotJobs gs_dot_jobs(const GsView& v, int M, int D, int Mp, int Dp) {
+  return {{{v.Ki, v.Psi2, Mp, M, M, GS_TR_KIPSI2},
+           {v.P, v.Psi2, Mp, M, M, GS_TR_PPSI2},
+           {v.C, v.E, Dp, M, D, GS_TR_CE},
+           {v.E, v.PsiE, Dp, M, D, GS_TR_EPSI2E},
+           {v.dFdK, v.KmmKeep, Mp, M, M, GS_SUM_V},
+           {v.Abar, v.C, Dp, M, D, GS_SUM_AC},
+           {v.Bbar, v.Psi2, Mp, M, M, GS_SUM_BPSI2}},
+          7};
+}
+// The six products (five descriptions: E += P R is E_is_P_C's second form), each with its layouts (LA, LB: launch_gemm's la / lb, gemm32_tile's template arguments) and its operands.  The host path adds its
+// big / split choice (gemm_plan), the tail its tile indices.  Mp, Dp are arguments so that the tail's stay compile-time constants.
+struct E_is_P_C {          // E = P C, and the refinement's E += P R (the same product with beta = 1 and the residual R, held in PsiE, for C).  P [m][k] -> K_CONTIG, C / R stored [k][d] -> FREE_CONTIG
+  static constexpr Layout LA = K_CONTIG, LB = FREE_CONTIG;
+  static __host__ __device__ GemmP with(const GsView& v, int Mp, int Dp, const double* C, double beta) { return gemm_of({v.P, Mp}, {C, Dp}, {v.E, Dp}, Mp, 1.0, beta); }
+  static __host__ __device__ GemmP of(const GsView& v, int Mp, int Dp) { return with(v, Mp, Dp, v.C, 0.0); }
+  static __host__ __device__ GemmP plus_P_R(const GsView& v, int Mp, int Dp) { return with(v, Mp, Dp, v.PsiE, 1.0); }
+};
+struct T2_is_Ki_Psi2 {     // the float64 form of G = Kmm^-1 Psi2 (dd_kipsi2 = 0).  Ki [m][k] -> K_CONTIG, Psi2 stored [k][c] -> FREE_CONTIG
+  static constexpr Layout LA = K_CONTIG, LB = FREE_CONTIG;
+  static __host__ __device__ GemmP of(const GsView& v, int Mp) { return gemm_of({v.Ki, Mp}, {v.Psi2, Mp}, {v.T2, Mp}, Mp); }
+};
+struct dFdK_is_T2_Ki {     // Kmm^-1 Psi2 Kmm^-1, into dFdK until the assembly.  T2 [m][k] -> K_CONTIG, Ki stored [k][c] -> FREE_CONTIG
+  static constexpr Layout LA = K_CONTIG, LB = FREE_CONTIG;
+  static __host__ __device__ GemmP of(const GsView& v, int Mp) { return gemm_of({v.T2, Mp}, {v.Ki, Mp}, {v.dFdK, Mp}, Mp); }
+};
+struct PsiE_is_Psi2_E {    // Psi2 [m][k] -> K_CONTIG, E stored [k][d] -> FREE_CONTIG
+  static constexpr Layout LA = K_CONTIG, LB = FREE_CONTIG;
+  static __host__ __device__ GemmP of(const GsView& v, int Mp, int Dp) { return gemm_of({v.Psi2, Mp}, {v.E, Dp}, {v.PsiE, Dp}, Mp); }
+};
+struct T1_is_E_Et {        // E [m][k] -> K_CONTIG; B(k,j) = E[j][k] -> K_CONTIG
+  static constexpr Layout LA = K_CONTIG, LB = K_CONTIG;
+  static __host__ __device__ GemmP of(const GsView& v, int Mp, int Dp) { return gemm_of({v.E, Dp}, {v.E, Dp}, {v.T1, Mp}, Dp); }
+};
+
 // ---------------------------------------------------------------------------------------------- short tail for one-panel problems
 // M <= 128 and D <= 128 (BASELINE configs[1]: M = 128, D = 10): everything of the global step behind the panel factorisation -- the two inverses,
 // E with its refinement step, Psi2 E, E E^T, K_mm^-1 Psi2 in double-double, its product with K_mm^-1, the assembled partials, the seven traces, the
@@ -587,11 +618,8 @@ __global__ void __launch_bounds__(256) colsum_kernel(const double* __restrict__ 
 constexpr int TAIL_STAGES = 7;
 constexpr int TAIL_LDS_DOUBLES = 2 * SmallImg<FREE_CONTIG>::DOUBLES;     // the larger operand image, twice (12288 doubles = 96 KB)
 struct TailP {
-  const double* Linv; double* Inv;                    // [2][128][128]
-  const double* Psi2; const double* C; const double* sc; const double* Keep;
-  double *E, *PsiE, *T1, *T2, *dFdK, *Bbar, *Abar, *Bm;
-  const double* Z; const double* alpha;
-  double* gs; double* gK;
+  GsView v;
+  const double* Linv;                                 // [2][128][128]
   DotJobs jobs;
   double beta, sf2, Dd, Nglob, jitA;
   int M, Q, regimeA, refine, dd;
@@ -615,65 +643,55 @@ __global__ void __launch_bounds__(256, 1) tail_stage_kernel(TailP p, int stage) 
   constexpr int Mp = 128, Dp = 128;
   constexpr long mm = (long)Mp * Mp;
   const int t = blockIdx.x;
-  double* Ki = p.Inv;
-  double* P = p.Inv + mm;
-  GemmP g;
-  g.alpha = 1.0; g.beta = 0.0; g.tri = 0; g.sA = g.sB = g.sC = 0;
+  const GsView& v = p.v;
   if (stage == 0) {
-    g.A = p.Linv; g.lda = Mp; g.sA = mm; g.B = p.Linv; g.ldb = Mp; g.sB = mm; g.C = p.Inv; g.ldc = Mp; g.sC = mm; g.K = Mp;
-    gemm32_tile<FREE_CONTIG, FREE_CONTIG>(g, t & 3, (t >> 2) & 3, t >> 4, sA, sB);
+    gemm32_tile<FREE_CONTIG, FREE_CONTIG>(gemm_of({p.Linv, Mp, mm}, {p.Linv, Mp, mm}, {v.Ki, Mp, mm}, Mp), t & 3, (t >> 2) & 3, t >> 4, sA, sB);
   } else if (stage == 1) {
     if (t < 16) {
-      g.K = Mp; g.A = P; g.lda = Mp; g.B = p.C; g.ldb = Dp; g.C = p.E; g.ldc = Dp;
-      gemm32_tile<K_CONTIG, FREE_CONTIG>(g, t & 3, t >> 2, 0, sA, sB);
+      gemm32_tile<E_is_P_C::LA, E_is_P_C::LB>(E_is_P_C::of(v, Mp, Dp), t & 3, t >> 2, 0, sA, sB);
     } else if (p.dd) {
       // one row per wave: the rows are independent, so the bits are those of the two-rows-per-wave form; 4 us faster at M = 128 (profiles/r04_dd_variants.txt)
-      ddacc_block<1, 8>(Ki, (long)Mp, p.Psi2, (long)Mp, Mp, p.T2, (long)Mp, (t - 16) & 1, (t - 16) >> 1);
+      ddacc_block<1, 8>(v.Ki, (long)Mp, v.Psi2, (long)Mp, Mp, v.T2, (long)Mp, (t - 16) & 1, (t - 16) >> 1);
     } else {
-      g.K = Mp; g.A = Ki; g.lda = Mp; g.B = p.Psi2; g.ldb = Mp; g.C = p.T2; g.ldc = Mp;
-      gemm32_tile<K_CONTIG, FREE_CONTIG>(g, (t - 16) & 3, (t - 16) >> 2, 0, sA, sB);
+      gemm32_tile<T2_is_Ki_Psi2::LA, T2_is_Ki_Psi2::LB>(T2_is_Ki_Psi2::of(v, Mp), (t - 16) & 3, (t - 16) >> 2, 0, sA, sB);
     }
   } else if (stage == 2) {
     if (t < 16) {
-      g.K = Mp; g.A = p.T2; g.lda = Mp; g.B = Ki; g.ldb = Mp; g.C = p.dFdK; g.ldc = Mp;
-      gemm32_tile<K_CONTIG, FREE_CONTIG>(g, t & 3, t >> 2, 0, sA, sB);
+      gemm32_tile<dFdK_is_T2_Ki::LA, dFdK_is_T2_Ki::LB>(dFdK_is_T2_Ki::of(v, Mp), t & 3, t >> 2, 0, sA, sB);
     } else {
       const int m = t - 16;
       double (*ph)[128] = reinterpret_cast<double (*)[128]>(red);
       double (*pl)[128] = reinterpret_cast<double (*)[128]>(red + 3 * 128);
-      if (m < p.M) residual_row256(m, p.Keep, p.Psi2, p.beta, p.jitA, p.C, p.E, p.M, Mp, Dp, p.PsiE, ph, pl);
-      else if (threadIdx.x < Dp) p.PsiE[(long)m * Dp + threadIdx.x] = 0.0;
+      if (m < p.M) residual_row256(m, v.KmmKeep, v.Psi2, p.beta, p.jitA, v.C, v.E, p.M, Mp, Dp, v.PsiE, ph, pl);
+      else if (threadIdx.x < Dp) v.PsiE[(long)m * Dp + threadIdx.x] = 0.0;
     }
   } else if (stage == 3) {
-    g.K = Mp; g.A = P; g.lda = Mp; g.B = p.PsiE; g.ldb = Dp; g.C = p.E; g.ldc = Dp; g.beta = 1.0;
-    gemm32_tile<K_CONTIG, FREE_CONTIG>(g, t & 3, t >> 2, 0, sA, sB);
+    gemm32_tile<E_is_P_C::LA, E_is_P_C::LB>(E_is_P_C::plus_P_R(v, Mp, Dp), t & 3, t >> 2, 0, sA, sB);
   } else if (stage == 4) {
     // the tile product, then the assembled outputs that need nothing but this tile and finished inputs: every element of the assembly is
     // computed once, by the expression of assemble_elem
     const int tt = t & 15, bx = tt & 3, by = tt >> 2;
     if (t < 16) {
-      g.K = Mp; g.A = p.Psi2; g.lda = Mp; g.B = p.E; g.ldb = Dp; g.C = p.PsiE; g.ldc = Dp;
-      gemm32_tile<K_CONTIG, FREE_CONTIG>(g, bx, by, 0, sA, sB);
+      gemm32_tile<PsiE_is_Psi2_E::LA, PsiE_is_Psi2_E::LB>(PsiE_is_Psi2_E::of(v, Mp, Dp), bx, by, 0, sA, sB);
       for (int e = threadIdx.x; e < ST * ST; e += 256)      // Abar and Bm's lower block: only E (finished in stage 3)
-        assemble_elem(mm + (long)(by * ST + (e >> 5)) * Dp + bx * ST + (e & 31), Ki, P, p.T1, p.dFdK, p.E, p.beta, p.Dd, Mp, Dp, p.Bbar, p.dFdK, p.Abar, p.Bm);
+        assemble_elem(mm + (long)(by * ST + (e >> 5)) * Dp + bx * ST + (e & 31), v.Ki, v.P, v.T1, v.dFdK, v.E, p.beta, p.Dd, Mp, Dp, v.Bbar, v.dFdK, v.Abar, v.Bm);
     } else {
-      g.K = Dp; g.A = p.E; g.lda = Dp; g.B = p.E; g.ldb = Dp; g.C = p.T1; g.ldc = Mp;
-      gemm32_tile<K_CONTIG, K_CONTIG>(g, bx, by, 0, sA, sB);
+      gemm32_tile<T1_is_E_Et::LA, T1_is_E_Et::LB>(T1_is_E_Et::of(v, Mp, Dp), bx, by, 0, sA, sB);
       __syncthreads();                                      // the tile of E E^T this workgroup just stored (same CU: visible after the barrier)
       for (int e = threadIdx.x; e < ST * ST; e += 256)
-        assemble_elem((long)(by * ST + (e >> 5)) * Mp + bx * ST + (e & 31), Ki, P, p.T1, p.dFdK, p.E, p.beta, p.Dd, Mp, Dp, p.Bbar, p.dFdK, p.Abar, p.Bm);
+        assemble_elem((long)(by * ST + (e >> 5)) * Mp + bx * ST + (e & 31), v.Ki, v.P, v.T1, v.dFdK, v.E, p.beta, p.Dd, Mp, Dp, v.Bbar, v.dFdK, v.Abar, v.Bm);
     }
   } else if (stage == 5) {
     const int nd = p.jobs.n * DOT_BLOCKS;
-    if (t < nd) dots_block(p.jobs, p.gs + GS_COUNT + 8, t % DOT_BLOCKS, t / DOT_BLOCKS, red);
+    if (t < nd) dots_block(p.jobs, v.gs + GS_COUNT + 8, t % DOT_BLOCKS, t / DOT_BLOCKS, red);
     else {
       const int half = threadIdx.x >> 7, j = 2 * (t - nd) + half;
-      kmm_grads_row(j, j < p.M, threadIdx.x & 127, red + 2 * KG_QC * half, p.dFdK, p.Keep, p.Bbar, p.Psi2, p.Z, p.alpha, p.M, Mp, p.Q, p.regimeA,
-                    p.gK, p.T2);
+      kmm_grads_row(j, j < p.M, threadIdx.x & 127, red + 2 * KG_QC * half, v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z, v.alpha, p.M, Mp, p.Q, p.regimeA,
+                    v.gK, v.T2);
     }
   } else {
-    if (t == 0) scalars_block(p.sc, p.gs, p.jobs, p.gs + GS_COUNT + 8, p.beta, p.sf2, p.Dd, p.Nglob);
-    else colsum_block(p.T2, p.M, p.Q, p.gK + (long)p.M * p.Q, t - 1, red);
+    if (t == 0) scalars_block(v.sc, v.gs, p.jobs, v.gs + GS_COUNT + 8, p.beta, p.sf2, p.Dd, p.Nglob);
+    else colsum_block(v.T2, p.M, p.Q, v.gK + (long)p.M * p.Q, t - 1, red);
   }
 }
 std::atomic<int> g_opt_gs_tail{env_flag("GPARML_GS_TAIL", true)};
@@ -750,35 +768,22 @@ int run_global_step(gp_ctx* c) {
   hipStream_t st = c->stream;
   const int Mp = c->Mp, Dp = c->Dp, M = c->M, D = c->D, Q = c->Q;
   const long mm = (long)Mp * Mp;
-  double* Psi2 = c->stats;
-  double* C = c->stats + mm;
-  double* sc = c->stats + mm + (long)Mp * Dp;
+  const GsView v = gs_view(c);
+  const DotJobs jobs = gs_dot_jobs(v, M, D, Mp, Dp);
+  const double jitA = (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0;
   c->gstep.gs_status = GP_OK;
-  double* failf = c->gstep.gs + GS_FLAGS;  // [2]
+  double* failf = v.gs + GS_FLAGS;  // [2]
   // T2 is free until G = K_mm^-1 Psi2 is formed: it keeps A for the double-double residual of the refinement step
   const bool gi8 = gs_i8_wanted(c);            // gsi8.hip: both double-double products on the int8 matrix core (M >= 1024)
   const bool res_dd = g_opt_refine_E.load() && ((g_opt_residual_dd.load() && Mp >= 256 && Dp >= 512) || gi8);   // narrow E: too few waves (M = 512, D = 100: +21 us)
-  GP_LAUNCH(c, st, build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, c->Z, c->alpha, c->sf2, c->beta, Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
-            c->gstep.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, c->gstep.gs, res_dd ? c->gstep.T2 : (double*)nullptr);
+  GP_LAUNCH(c, st, build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, v.Z, v.alpha, c->sf2, c->beta, v.Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
+            v.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, jitA, v.gs, res_dd ? v.T2 : (double*)nullptr);
   // one-panel problems (M, D <= 128): the panel kernel, then seven launches of tail_stage_kernel instead of fifteen kernels
   if (Mp == NB && Dp == NB && g_opt_gs_tail.load()) {
     GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
     GP_HIP(c, hipFuncSetAttribute((const void*)tail_stage_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TAIL_LDS_DOUBLES * 8));
-    GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, c->gstep.Kmm, (long)Mp, mm, 0, c->gstep.Linv, failf, c->gstep.gs + GS_LOGDET_K);
-    TailP t;
-    t.Linv = c->gstep.Linv; t.Inv = c->gstep.Inv; t.Psi2 = Psi2; t.C = C; t.sc = sc; t.Keep = c->gstep.KmmKeep;
-    t.E = c->gstep.E; t.PsiE = c->gstep.PsiE; t.T1 = c->gstep.T1; t.T2 = c->gstep.T2; t.dFdK = c->gstep.dFdK; t.Bbar = c->gstep.Bbar; t.Abar = c->gstep.Abar; t.Bm = c->gstep.Bm;
-    t.Z = c->Z; t.alpha = c->alpha; t.gs = c->gstep.gs; t.gK = c->gstep.gK;
-    t.beta = c->beta; t.sf2 = c->sf2; t.Dd = (double)D; t.Nglob = (double)c->N_global; t.jitA = (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0;
-    t.M = M; t.Q = Q; t.regimeA = c->regime_A ? 1 : 0; t.refine = g_opt_refine_E.load(); t.dd = g_opt_dd_kipsi2.load();
-    t.jobs.n = 7;
-    t.jobs.j[0] = {c->gstep.Inv, Psi2, Mp, M, M, GS_TR_KIPSI2};
-    t.jobs.j[1] = {c->gstep.Inv + mm, Psi2, Mp, M, M, GS_TR_PPSI2};
-    t.jobs.j[2] = {C, c->gstep.E, Dp, M, D, GS_TR_CE};
-    t.jobs.j[3] = {c->gstep.E, c->gstep.PsiE, Dp, M, D, GS_TR_EPSI2E};
-    t.jobs.j[4] = {c->gstep.dFdK, c->gstep.KmmKeep, Mp, M, M, GS_SUM_V};
-    t.jobs.j[5] = {c->gstep.Abar, C, Dp, M, D, GS_SUM_AC};
-    t.jobs.j[6] = {c->gstep.Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
+    GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3(2), dim3(512), POTRF_LDS_DOUBLES * 8, c->gstep.Kmm, (long)Mp, mm, 0, c->gstep.Linv, failf, v.gs + GS_LOGDET_K);
+    const TailP t = {v, c->gstep.Linv, jobs, c->beta, c->sf2, (double)D, (double)c->N_global, jitA, M, Q, c->regime_A ? 1 : 0, g_opt_refine_E.load(), g_opt_dd_kipsi2.load()};
     for (int stage = 0; stage < TAIL_STAGES; ++stage) {
       const int items = tail_items(stage, M, Q, t.refine, t.dd);
       // only the stages with tile products need the operand images
@@ -792,130 +797,68 @@ int run_global_step(gp_ctx* c) {
   double* ws = nullptr;
   const size_t wcap = c->ws.capacity;
   GP_TRY_RC(c->ws.take(c, wcap, "global step", &ws));
-  int rc = potrf_inverse_batched(c, st, Mp, 2, c->gstep.Kmm, c->gstep.Linv, c->gstep.Inv, c->gstep.T1, c->gstep.gs + GS_LOGDET_K, failf, ws, wcap);
+  int rc = potrf_inverse_batched(c, st, Mp, 2, c->gstep.Kmm, c->gstep.Linv, c->gstep.Inv, v.T1, v.gs + GS_LOGDET_K, failf, ws, wcap);
   if (rc != GP_OK) return rc;
-  double* Ki = c->gstep.Inv;
-  double* P = c->gstep.Inv + mm;
   // E = P C ; PsiE = Psi2 E ; T1 = E E^T   and, independent of it,   T2 = Ki Psi2 ; dFdK(tmp) = T2 Ki.   One stream: a side stream for the second
   // chain was measured slower (r03: 0.424 -> 0.455 ms at M = 512 -- every cross-stream event edge costs more than the 5-12 us product it hides)
-  // and was removed in r06.
-  GemmP g;
-  g.K = Mp; g.alpha = 1.0; g.beta = 0.0; g.tri = 0; g.sA = g.sB = g.sC = 0;
-  // the 128-tile kernel with split-k where that gives >= 256 workgroups (M >= 1024: 72-74 -> 63 us per product incl. the reduce at M = 1024; at M = 2048 the
-  // M x M x M product 616 -> 392 us without a split, the M x M x D ones have 128 tiles and lose to the small tiles unless split); E E^T stays on the small tiles
-  const bool bigok = g_opt_gemm_big.load() && Mp >= 1024 && ws;
-  const int spMD = bigok ? choose_splits((long)(Mp / TILE) * (Dp / TILE), Mp, wcap) : 1;
-  const int spMM = bigok ? choose_splits((long)(Mp / TILE) * (Mp / TILE), Mp, wcap) : 1;
-  const int bigMD = (bigok && (long)(Mp / TILE) * (Dp / TILE) * spMD >= 256) ? 1 : 0;
-  const int bigMM = (bigok && (long)(Mp / TILE) * (Mp / TILE) * spMM >= 256) ? 1 : 0;
-  g.ws = ws;
-  g.big = bigMD; g.splits = bigMD ? spMD : 1;
-  g.A = P; g.lda = Mp; g.B = C; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp;
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
+  // and was removed in r06.  The M x M x D and M x M x M products take gemm_plan's choice; E E^T stays on the small tiles.
+  const int gb = g_opt_gemm_big.load();
+  const GemmPlan md = gemm_plan((long)(Mp / TILE) * (Dp / TILE), Mp, ws ? wcap : 0, gb, Mp);
+  const GemmPlan sq = gemm_plan((long)(Mp / TILE) * (Mp / TILE), Mp, ws ? wcap : 0, gb, Mp);
+  GP_TRY_RC(launch_gemm(c, st, E_is_P_C::LA, E_is_P_C::LB, Mp, Dp, 1, E_is_P_C::of(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
   // one refinement step of E with a double-double residual (PsiE is free until the next product); GPARML_REFINE_E=0 turns it off
   if (g_opt_refine_E.load()) {
     if (gi8) {
-      GP_TRY_RC(run_gs_i8_product(c, st, c->gstep.T2, (long)Mp, Mp, c->gstep.E, (long)Dp, Dp, Mp, c->gstep.PsiE, (long)Dp, C));
+      GP_TRY_RC(run_gs_i8_product(c, st, v.T2, (long)Mp, Mp, v.E, (long)Dp, Dp, Mp, v.PsiE, (long)Dp, v.C));
     } else if (res_dd) {
-      GP_LAUNCH(c, st, (ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, c->gstep.T2, (long)Mp, c->gstep.E, (long)Dp, Mp, C, c->gstep.PsiE);
+      GP_LAUNCH(c, st, (ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, v.T2, (long)Mp, v.E, (long)Dp, Mp, v.C, v.PsiE);
     } else {
-      GP_LAUNCH(c, st, solve_residual_kernel, dim3(M), dim3(512), 0, c->gstep.KmmKeep, Psi2, c->beta, (c->gstep.jitter_mask & 2) ? 1e-7 : 0.0, C, c->gstep.E, M, Mp, Dp,
-                c->gstep.PsiE, 0);
-      if (M < Mp) GP_HIP(c, hipMemsetAsync(c->gstep.PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
+      GP_LAUNCH(c, st, solve_residual_kernel, dim3(M), dim3(512), 0, v.KmmKeep, v.Psi2, c->beta, jitA, v.C, v.E, M, Mp, Dp, v.PsiE, 0);
+      if (M < Mp) GP_HIP(c, hipMemsetAsync(v.PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
     }
-    g.A = P; g.lda = Mp; g.B = c->gstep.PsiE; g.ldb = Dp; g.C = c->gstep.E; g.ldc = Dp; g.beta = 1.0;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
-    g.beta = 0.0;
+    GP_TRY_RC(launch_gemm(c, st, E_is_P_C::LA, E_is_P_C::LB, Mp, Dp, 1, E_is_P_C::plus_P_R(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
   }
-  g.A = Psi2; g.lda = Mp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.PsiE; g.ldc = Dp;
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Dp, 1, g));
-  g.K = Dp; g.A = c->gstep.E; g.lda = Dp; g.B = c->gstep.E; g.ldb = Dp; g.C = c->gstep.T1; g.ldc = Mp;   // B(k,j) = E[j][k] -> K_CONTIG
-  { const int sps = g.splits; g.splits = 1; g.big = 0; GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, Mp, Mp, 1, g)); g.splits = sps; }
+  GP_TRY_RC(launch_gemm(c, st, PsiE_is_Psi2_E::LA, PsiE_is_Psi2_E::LB, Mp, Dp, 1, PsiE_is_Psi2_E::of(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
+  GP_TRY_RC(launch_gemm(c, st, T1_is_E_Et::LA, T1_is_E_Et::LB, Mp, Mp, 1, T1_is_E_Et::of(v, Mp, Dp)));
   // G = Ki Psi2 with double-double accumulation (ddacc_gemm_kernel above: two rows per wave, eight k per trip -- same-box timing of six shapes
   // in profiles/r04_dd_variants.txt: +50 us at M = 512, +9 us at M = 128, +0.29 ms at M = 1024 over the float64 matrix-core product of r03, which
   // GPARML_DD_KIPSI2=0 or gp_debug_set_option("dd_kipsi2", 0) restores)
   if (g_opt_dd_kipsi2.load() && gi8) {
-    GP_TRY_RC(run_gs_i8_product(c, st, Ki, (long)Mp, Mp, Psi2, (long)Mp, Mp, Mp, c->gstep.T2, (long)Mp, nullptr));
+    GP_TRY_RC(run_gs_i8_product(c, st, v.Ki, (long)Mp, Mp, v.Psi2, (long)Mp, Mp, Mp, v.T2, (long)Mp, nullptr));
   } else if (g_opt_dd_kipsi2.load()) {
-    GP_LAUNCH(c, st, (ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, Ki, (long)Mp, Psi2, (long)Mp, Mp, c->gstep.T2, (long)Mp);
+    GP_LAUNCH(c, st, (ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, v.Ki, (long)Mp, v.Psi2, (long)Mp, Mp, v.T2, (long)Mp);
   } else {
-    g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1; g.A = Ki; g.lda = Mp; g.B = Psi2; g.ldb = Mp; g.C = c->gstep.T2; g.ldc = Mp;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g));
+    GP_TRY_RC(launch_gemm(c, st, T2_is_Ki_Psi2::LA, T2_is_Ki_Psi2::LB, Mp, Mp, 1, T2_is_Ki_Psi2::of(v, Mp).on_big(sq.big).split(sq.splits, ws)));
   }
-  g.K = Mp; g.big = bigMM; g.splits = bigMM ? spMM : 1;
-  g.A = c->gstep.T2; g.lda = Mp; g.B = Ki; g.ldb = Mp; g.C = c->gstep.dFdK; g.ldc = Mp;
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, Mp, Mp, 1, g));
+  GP_TRY_RC(launch_gemm(c, st, dFdK_is_T2_Ki::LA, dFdK_is_T2_Ki::LB, Mp, Mp, 1, dFdK_is_T2_Ki::of(v, Mp).on_big(sq.big).split(sq.splits, ws)));
   // dFdK currently holds Ki Psi2 Ki; assemble in place is unsafe (reads KPK, writes dFdK at the same index: fine, same thread)
-  GP_LAUNCH(c, st, assemble_kernel, dim3(1024), dim3(256), 0, Ki, P, c->gstep.T1, c->gstep.dFdK, c->gstep.E, c->beta, (double)D, Mp, Dp, c->gstep.Bbar,
-            c->gstep.dFdK, c->gstep.Abar, c->gstep.Bm);
-  DotJobs jobs;
-  jobs.n = 7;
-  jobs.j[0] = {Ki, Psi2, Mp, M, M, GS_TR_KIPSI2};
-  jobs.j[1] = {P, Psi2, Mp, M, M, GS_TR_PPSI2};
-  jobs.j[2] = {C, c->gstep.E, Dp, M, D, GS_TR_CE};
-  jobs.j[3] = {c->gstep.E, c->gstep.PsiE, Dp, M, D, GS_TR_EPSI2E};
-  jobs.j[4] = {c->gstep.dFdK, c->gstep.KmmKeep, Mp, M, M, GS_SUM_V};
-  jobs.j[5] = {c->gstep.Abar, C, Dp, M, D, GS_SUM_AC};
-  jobs.j[6] = {c->gstep.Bbar, Psi2, Mp, M, M, GS_SUM_BPSI2};
-  double* dpart = c->gstep.gs + GS_DOTS;   // [jobs][DOT_BLOCKS]
+  GP_LAUNCH(c, st, assemble_kernel, dim3(1024), dim3(256), 0, v.Ki, v.P, v.T1, v.dFdK, v.E, c->beta, (double)D, Mp, Dp, v.Bbar, v.dFdK, v.Abar, v.Bm);
+  double* dpart = v.gs + GS_DOTS;   // [jobs][DOT_BLOCKS]
   // the traces / scalars and the Kmm parts of the gradients both start from the assembled partials and do not touch each other's outputs
   GP_LAUNCH(c, st, dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, jobs, dpart);
-  GP_LAUNCH(c, st, scalars_kernel, dim3(1), dim3(64), 0, sc, c->gstep.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
+  GP_LAUNCH(c, st, scalars_kernel, dim3(1), dim3(64), 0, v.sc, v.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
   // Kmm parts of grad_Z / grad_alpha; alpha partials per row go through T2 (free again)
   static const bool kmm_lds = env_flag("GPARML_KMM_LDS", true);
   if (kmm_lds && M <= 2048)
-    GP_LAUNCH(c, st, kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z,
-              c->Zt, c->alpha, M, Mp, Q, c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
+    GP_LAUNCH(c, st, kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z,
+              v.Zt, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
   else
-    GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, c->gstep.dFdK, c->gstep.KmmKeep, c->gstep.Bbar, Psi2, c->Z, c->alpha, M, Mp, Q,
-              c->regime_A ? 1 : 0, c->gstep.gK, c->gstep.T2);
-  GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, c->gstep.T2, M, Q, c->gstep.gK + (long)M * Q);
+    GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
+  GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, v.T2, M, Q, v.gK + (long)M * Q);
   return GP_OK;
 }
 
 }  // namespace gp
 
 // ---- test hooks ------------------------------------------------------------------------------------------------
-extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet) {
+// The body of both factorisation hooks: pad, upload, potrf_inverse_batched as the global step runs it, download, unpad.  Per-entry outputs and the raw
+// fail mask; with_workspace: the split-k workspace that takes the X^T X product onto the 128-tile kernel for Mp >= 1024.  The workspace has the floor of
+// the shared workspace's capacity (workspace_capacity, api.hip: 1100 tiles); choose_splits never asks for more than 512 partial tiles, so a larger
+// capacity decides nothing differently.
+static int potrf_inverse_hook(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet, int* fail_mask) {
   using namespace gp;
   gp_ctx tmp;
   gp_ctx* c = &tmp;
-  if (n <= 0 || !A) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_potrf_inverse: bad argument");
-  GP_HIP(c, hipSetDevice(device));
-  const int Mp = (int)round_up(n, NB);
-  const long mm = (long)Mp * Mp;
-  std::vector<double> h(mm, 0.0);
-  for (int i = 0; i < Mp; ++i) for (int k = 0; k < Mp; ++k) h[(long)i * Mp + k] = (i < n && k < n) ? A[(long)i * n + k] : (i == k ? 1.0 : 0.0);
-  DevBuf<double> dA, dLi, dInv, dT, dS;     // (allocated without the context: a failure is reported by gp_last_error(NULL))
-  GP_TRY_RC(dA.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dLi.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dInv.alloc(nullptr, mm, DA_RAW));
-  GP_TRY_RC(dT.alloc(nullptr, mm, DA_RAW)); GP_TRY_RC(dS.alloc(nullptr, 8, DA_RAW));
-  GP_HIP(c, hipMemcpy(dA, h.data(), mm * 8, hipMemcpyHostToDevice));
-  GP_HIP(c, hipMemset(dS, 0, 64));
-  GP_HIP(c, hipMemset(dLi, 0, mm * 8));
-  int rc = potrf_inverse_batched(c, nullptr, Mp, 1, dA, dLi, dInv, dT, dS, dS + 1, nullptr);
-  if (rc == GP_OK) {
-    double s[2];
-    GP_HIP(c, hipDeviceSynchronize());
-    GP_HIP(c, hipMemcpy(s, dS, 16, hipMemcpyDeviceToHost));
-    if (logdet) *logdet = s[0];
-    if (L) { GP_HIP(c, hipMemcpy(h.data(), dA, mm * 8, hipMemcpyDeviceToHost)); for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) L[(long)i * n + k] = (k <= i) ? h[(long)i * Mp + k] : 0.0; }
-    if (Ainv) { GP_HIP(c, hipMemcpy(h.data(), dInv, mm * 8, hipMemcpyDeviceToHost)); for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) Ainv[(long)i * n + k] = h[(long)i * Mp + k]; }
-    if (s[1] != 0.0) rc = fail(nullptr, GP_ERR_NOT_PD, "matrix is not positive definite");
-  } else {
-    gp::g_create_error = c->err;
-  }
-  return rc;
-}
-
-// gp_debug_potrf_inverse for a batch, as the global step runs it: per-entry outputs, the raw fail mask, and (with_workspace) the split-k workspace
-// that takes the X^T X product onto the 128-tile kernel for Mp >= 1024.  The workspace has the floor of the shared workspace's capacity
-// (workspace_capacity, api.hip: 1100 tiles); choose_splits never asks for more than 512 partial tiles, so a larger capacity decides nothing differently.
-extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet,
-                                              int* fail_mask) {
-  using namespace gp;
-  gp_ctx tmp;
-  gp_ctx* c = &tmp;
-  if (n <= 0 || batch < 1 || batch > 8 || !A) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_potrf_inverse_batched: bad argument");
   GP_HIP(c, hipSetDevice(device));
   const int Mp = (int)round_up(n, NB);
   const long mm = (long)Mp * Mp, nn = (long)n * n;
@@ -942,7 +885,7 @@ extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int 
   GP_HIP(c, hipMemcpy(s.data(), dS, dS.bytes(), hipMemcpyDeviceToHost));
   int mask = 0;
   for (int b = 0; b < batch; ++b) { if (logdet) logdet[b] = s[b]; if (s[batch + b] != 0.0) mask |= 1 << b; }
-  if (fail_mask) *fail_mask = mask;
+  *fail_mask = mask;           // known from here on, whatever the downloads below do
   if (L) {
     GP_HIP(c, hipMemcpy(h.data(), dA, dA.bytes(), hipMemcpyDeviceToHost));
     for (int b = 0; b < batch; ++b) for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) L[b * nn + (long)i * n + k] = (k <= i) ? h[b * mm + (long)i * Mp + k] : 0.0;
@@ -951,6 +894,27 @@ extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int 
     GP_HIP(c, hipMemcpy(h.data(), dInv, dInv.bytes(), hipMemcpyDeviceToHost));
     for (int b = 0; b < batch; ++b) for (int i = 0; i < n; ++i) for (int k = 0; k < n; ++k) Ainv[b * nn + (long)i * n + k] = h[b * mm + (long)i * Mp + k];
   }
+  return GP_OK;
+}
+
+extern "C" int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet) {
+  using namespace gp;
+  if (n <= 0 || !A) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_potrf_inverse: bad argument");
+  int mask = 0;
+  GP_TRY_RC(potrf_inverse_hook(device, n, 1, 0, A, L, Ainv, logdet, &mask));
+  if (mask) return fail(nullptr, GP_ERR_NOT_PD, "matrix is not positive definite");
+  return GP_OK;
+}
+
+// gp_debug_potrf_inverse for a batch
+extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet,
+                                              int* fail_mask) {
+  using namespace gp;
+  if (n <= 0 || batch < 1 || batch > 8 || !A) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_potrf_inverse_batched: bad argument");
+  int mask = -1;                // -1: the body failed before it read the flags back
+  const int rc = potrf_inverse_hook(device, n, batch, with_workspace, A, L, Ainv, logdet, &mask);
+  if (fail_mask && mask >= 0) *fail_mask = mask;
+  if (rc != GP_OK) return rc;
   if (mask) return fail(nullptr, GP_ERR_NOT_PD, "gp_debug_potrf_inverse_batched: not positive definite (fail mask %d)", mask);
   return GP_OK;
 }

@@ -279,15 +279,8 @@ int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, 
             rows, (int)Q, c->sf2, mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
   GP_TRY_RC(launch_psi1_rows(c, mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
   // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
-  GemmP g;
-  g.K = (int)Mp; g.tri = 0; g.sA = g.sB = g.sC = 0; g.splits = 1; g.big = 0;
-  g.A = p.P1; g.lda = Mp; g.C = p.G; g.ldc = Dp + 2 * Mp;
-  g.B = c->gstep.E; g.ldb = Dp; g.alpha = c->beta; g.beta = 0.0;
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, g));
-  if (fac) {
-    g.B = c->gstep.Linv; g.ldb = Mp; g.alpha = 1.0; g.C = fac; g.ldc = ldf;
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, g));
-  }
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.P1, Mp}, {c->gstep.E, Dp}, {p.G, Dp + 2 * Mp}, (int)Mp, c->beta)));
+  if (fac) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.P1, Mp}, {c->gstep.Linv, Mp}, {fac, ldf}, (int)Mp)));
   return GP_OK;
 }
 

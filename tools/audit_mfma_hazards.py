@@ -2,7 +2,7 @@
 inside an asm string, so it inserts none of the wait states the hazard recogniser would.  Two patterns produced wrong numbers in this repository:
   (a) r03, psi2_tile.hip: an accumulator zeroed in C++ is rematerialised as v_mov directly in front of its first asm MFMA (VALU write -> MFMA read
       of SrcC without wait states);
-  (b) r05, gemm32_tile inside gs_tail128_kernel: such a v_mov landed on the register the PREVIOUS MFMA was still reading as its B operand
+  (b) r05, gemm32_tile inside tail_stage_kernel: such a v_mov landed on the register the PREVIOUS MFMA was still reading as its B operand
       (write-after-read inside the MFMA's multi-pass operand read): columns 4..7 of every 32 x 32 tile wrong, run-to-run different.
 (Pattern (b) is (a) in disguise: the register had just been the B operand of the previous MFMA, the zeroing move was put right behind that MFMA and
 right in front of the one that reads it as SrcC.  A VALU write of a register that an in-flight MFMA read as SrcA / SrcB is NOT a hazard -- those are read
