@@ -84,6 +84,7 @@ SIGNATURES = {
     'gp_debug_operands_overlap': (ctypes.c_int, [ctypes.c_long] * 8),
     'gp_debug_gemm_modes': (ctypes.c_int, [ctypes.c_int] * 8 + [ctypes.POINTER(ctypes.c_long), ctypes.c_double, ctypes.c_double, _ip, _dp, _dp, _dp]),
     'gp_debug_potrf_inverse_batched': (ctypes.c_int, [ctypes.c_int] * 4 + [_dp, _dp, _dp, _dp, _ip]),
+    'gp_debug_dd_product': (ctypes.c_int, [ctypes.c_int] * 3 + [_ip, ctypes.c_double, ctypes.c_double, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
 }
 
 _lib = None

@@ -764,6 +764,35 @@ int GsState::poison(gp_ctx* c) {
   return GP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- the two extended-precision products, dispatched once
+// G = K_mm^-1 Psi2 and the refinement residual R = C - (K_mm + beta Psi2) E exist in four device forms; the step chooses here and nowhere else, and
+// gp_debug_dd_product (below) runs either function on operands of its own, in the step's choice or a forced one (tests/test_gpu_dd_products.py).
+enum { DD_FORM_GEMM = 1, DD_FORM_RESIDUAL = 2, DD_FORM_ROW = 3, DD_FORM_I8 = 4 };
+// out [nA][nB] = sum_k A(i, k) B[k][j], or Csub - that sum.  The double-double kernels read A as [nA][K]; the int8 product reads it as [K][nA] (the
+// step's A is symmetric in both uses).  B [K][nB], out and Csub [nA][nB]; the double-double residual takes out's and Csub's row stride from ldb.
+struct DdProduct { const double* A; long lda; int nA; const double* B; long ldb; int nB; int K; double* out; long ldo; const double* Csub; };
+// what only the row form reads: it rebuilds A = fma(beta, Psi2, Keep) + jitA I on the leading M x M block ([Mp][Mp] each, Mp = the product's nA)
+struct RowOperands { const double* Keep; const double* Psi2; double beta, jitA; int M; };
+static int G_form(bool gi8) { return gi8 ? DD_FORM_I8 : DD_FORM_GEMM; }
+// narrow E: too few waves for ddacc_block (M = 512, D = 100: +21 us)
+static int residual_form(bool gi8, int Mp, int Dp) { return gi8 ? DD_FORM_I8 : (g_opt_residual_dd.load() && Mp >= 256 && Dp >= 512) ? DD_FORM_RESIDUAL : DD_FORM_ROW; }
+static int form_G(gp_ctx* c, hipStream_t st, int form, const DdProduct& p) {
+  if (form == DD_FORM_I8) return run_gs_i8_product(c, st, p.A, p.lda, p.nA, p.B, p.ldb, p.nB, p.K, p.out, p.ldo, nullptr);
+  GP_LAUNCH(c, st, (ddacc_gemm_kernel<2, 8>), dim3(p.nB / 64, p.nA / 8), dim3(256), 0, p.A, p.lda, p.B, p.ldb, p.K, p.out, p.ldo);
+  return GP_OK;
+}
+static int form_residual(gp_ctx* c, hipStream_t st, int form, const DdProduct& p, const RowOperands& r) {
+  if (form == DD_FORM_I8) return run_gs_i8_product(c, st, p.A, p.lda, p.nA, p.B, p.ldb, p.nB, p.K, p.out, p.ldo, p.Csub);
+  if (form == DD_FORM_RESIDUAL) {
+    GP_LAUNCH(c, st, (ddacc_residual_kernel<2, 8>), dim3(p.nB / 64, p.nA / 8), dim3(256), 0, p.A, p.lda, p.B, p.ldb, p.K, p.Csub, p.out);
+    return GP_OK;
+  }
+  const int Mp = p.nA, Dp = p.nB;
+  GP_LAUNCH(c, st, solve_residual_kernel, dim3(r.M), dim3(512), 0, r.Keep, r.Psi2, r.beta, r.jitA, p.Csub, p.B, r.M, Mp, Dp, p.out, 0);
+  if (r.M < Mp) GP_HIP(c, hipMemsetAsync(p.out + (long)r.M * Dp, 0, (size_t)(Mp - r.M) * Dp * sizeof(double), st));
+  return GP_OK;
+}
+
 int run_global_step(gp_ctx* c) {
   hipStream_t st = c->stream;
   const int Mp = c->Mp, Dp = c->Dp, M = c->M, D = c->D, Q = c->Q;
@@ -775,7 +804,8 @@ int run_global_step(gp_ctx* c) {
   double* failf = v.gs + GS_FLAGS;  // [2]
   // T2 is free until G = K_mm^-1 Psi2 is formed: it keeps A for the double-double residual of the refinement step
   const bool gi8 = gs_i8_wanted(c);            // gsi8.hip: both double-double products on the int8 matrix core (M >= 1024)
-  const bool res_dd = g_opt_refine_E.load() && ((g_opt_residual_dd.load() && Mp >= 256 && Dp >= 512) || gi8);   // narrow E: too few waves (M = 512, D = 100: +21 us)
+  const int res_form = residual_form(gi8, Mp, Dp);
+  const bool res_dd = g_opt_refine_E.load() && res_form != DD_FORM_ROW;     // the forms that read A's copy
   GP_LAUNCH(c, st, build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, v.Z, v.alpha, c->sf2, c->beta, v.Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
             v.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, jitA, v.gs, res_dd ? v.T2 : (double*)nullptr);
   // one-panel problems (M, D <= 128): the panel kernel, then seven launches of tail_stage_kernel instead of fifteen kernels
@@ -808,14 +838,7 @@ int run_global_step(gp_ctx* c) {
   GP_TRY_RC(launch_gemm(c, st, E_is_P_C::LA, E_is_P_C::LB, Mp, Dp, 1, E_is_P_C::of(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
   // one refinement step of E with a double-double residual (PsiE is free until the next product); GPARML_REFINE_E=0 turns it off
   if (g_opt_refine_E.load()) {
-    if (gi8) {
-      GP_TRY_RC(run_gs_i8_product(c, st, v.T2, (long)Mp, Mp, v.E, (long)Dp, Dp, Mp, v.PsiE, (long)Dp, v.C));
-    } else if (res_dd) {
-      GP_LAUNCH(c, st, (ddacc_residual_kernel<2, 8>), dim3(Dp / 64, Mp / 8), dim3(256), 0, v.T2, (long)Mp, v.E, (long)Dp, Mp, v.C, v.PsiE);
-    } else {
-      GP_LAUNCH(c, st, solve_residual_kernel, dim3(M), dim3(512), 0, v.KmmKeep, v.Psi2, c->beta, jitA, v.C, v.E, M, Mp, Dp, v.PsiE, 0);
-      if (M < Mp) GP_HIP(c, hipMemsetAsync(v.PsiE + (long)M * Dp, 0, (size_t)(Mp - M) * Dp * sizeof(double), st));
-    }
+    GP_TRY_RC(form_residual(c, st, res_form, {v.T2, (long)Mp, Mp, v.E, (long)Dp, Dp, Mp, v.PsiE, (long)Dp, v.C}, {v.KmmKeep, v.Psi2, c->beta, jitA, M}));
     GP_TRY_RC(launch_gemm(c, st, E_is_P_C::LA, E_is_P_C::LB, Mp, Dp, 1, E_is_P_C::plus_P_R(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
   }
   GP_TRY_RC(launch_gemm(c, st, PsiE_is_Psi2_E::LA, PsiE_is_Psi2_E::LB, Mp, Dp, 1, PsiE_is_Psi2_E::of(v, Mp, Dp).on_big(md.big).split(md.splits, ws)));
@@ -823,10 +846,8 @@ int run_global_step(gp_ctx* c) {
   // G = Ki Psi2 with double-double accumulation (ddacc_gemm_kernel above: two rows per wave, eight k per trip -- same-box timing of six shapes
   // in profiles/r04_dd_variants.txt: +50 us at M = 512, +9 us at M = 128, +0.29 ms at M = 1024 over the float64 matrix-core product of r03, which
   // GPARML_DD_KIPSI2=0 or gp_debug_set_option("dd_kipsi2", 0) restores)
-  if (g_opt_dd_kipsi2.load() && gi8) {
-    GP_TRY_RC(run_gs_i8_product(c, st, v.Ki, (long)Mp, Mp, v.Psi2, (long)Mp, Mp, Mp, v.T2, (long)Mp, nullptr));
-  } else if (g_opt_dd_kipsi2.load()) {
-    GP_LAUNCH(c, st, (ddacc_gemm_kernel<2, 8>), dim3(Mp / 64, Mp / 8), dim3(256), 0, v.Ki, (long)Mp, v.Psi2, (long)Mp, Mp, v.T2, (long)Mp);
+  if (g_opt_dd_kipsi2.load()) {
+    GP_TRY_RC(form_G(c, st, G_form(gi8), {v.Ki, (long)Mp, Mp, v.Psi2, (long)Mp, Mp, Mp, v.T2, (long)Mp, nullptr}));
   } else {
     GP_TRY_RC(launch_gemm(c, st, T2_is_Ki_Psi2::LA, T2_is_Ki_Psi2::LB, Mp, Mp, 1, T2_is_Ki_Psi2::of(v, Mp).on_big(sq.big).split(sq.splits, ws)));
   }
@@ -917,6 +938,101 @@ extern "C" int gp_debug_potrf_inverse_batched(int device, int n, int batch, int 
   if (rc != GP_OK) return rc;
   if (mask) return fail(nullptr, GP_ERR_NOT_PD, "gp_debug_potrf_inverse_batched: not positive definite (fail mask %d)", mask);
   return GP_OK;
+}
+
+// One of the two extended-precision products of the global step on the caller's operands (include/gparml_hip.h).  Everything the kernels take on
+// trust is checked first and refused with GP_ERR_BAD_ARG before any HIP call; the context is a temporary one whose only device state is the int8
+// workspace (gstep.gsd / gss, as GsState::alloc sizes it for form 0, as the product needs it for a forced int8 form).
+namespace gp {
+constexpr size_t DD_HOOK_I8_BYTES = (size_t)10 * 2048 * 4096;    // the largest workspace GsState::alloc gives a context with M, D <= 2048
+static int dd_product_body(gp_ctx* c, int device, int residual, int form, const int* dims, double beta, double jitA, const double* A, const double* B,
+                           const double* Csub, const double* Keep, const double* Psi2, double* out, int* form_ran) {
+  auto bad = [&](const char* fmt, auto... a) {
+    char what[200];
+    snprintf(what, sizeof(what), fmt, a...);
+    return fail(c, GP_ERR_BAD_ARG, "gp_debug_dd_product: %s", what);
+  };
+  if (!dims || !out || !form_ran || !B) return bad("NULL argument (dims, B, out and form_ran are always needed)");
+  if (residual != 0 && residual != 1) return bad("product must be 0 (G) or 1 (residual), got %d", residual);
+  if (form < 0 || form > DD_FORM_I8) return bad("form must be 0 (the step's choice) or 1 .. 4, got %d", form);
+  const int M = dims[0], Mp = dims[1], Dp = dims[2];
+  int nA = dims[3], nB = dims[4], K = dims[5];
+  if (form == 0 || form == DD_FORM_ROW) {
+    // the step's own shapes: a context pads M and D to multiples of 128
+    if (Mp < NB || Mp % NB || Mp > 4096) return bad("Mp = %d must be a multiple of 128 in [128, 4096]", Mp);
+    if (Dp < NB || Dp % NB || Dp > 4096) return bad("Dp = %d must be a multiple of 128 in [128, 4096]", Dp);
+    if (nA || nB || K) return bad("nA, nB, K must be 0 with form %d: the sizes are Mp and Dp", form);
+    nA = Mp; K = Mp; nB = residual ? Dp : Mp;
+  }
+  if (form == 0) {
+    if (Mp == NB && Dp == NB && g_opt_gs_tail.load()) return bad("form 0 at Mp = Dp = 128: the step runs the fused one-panel tail there, not these products");
+    if (!residual && !g_opt_dd_kipsi2.load()) return bad("form 0 with dd_kipsi2 off: the step forms G in plain float64");
+    if (residual && !g_opt_refine_E.load()) return bad("form 0 with refine_E off: the step forms no residual");
+  }
+  if ((form == DD_FORM_GEMM && residual) || ((form == DD_FORM_RESIDUAL || form == DD_FORM_ROW) && !residual))
+    return bad("form %d does not compute product %d", form, residual);
+  if (form == DD_FORM_ROW && (M < 1 || M > Mp)) return bad("M = %d must be in [1, Mp]", M);
+  if (form == DD_FORM_GEMM || form == DD_FORM_RESIDUAL) {
+    if (nA < 8 || nA % 8 || nA > 4096) return bad("rows nA = %d must be a multiple of 8 in [8, 4096] (ddacc_block: 8 rows per workgroup)", nA);
+    if (nB < 64 || nB % 64 || nB > 4096) return bad("cols nB = %d must be a multiple of 64 in [64, 4096] (ddacc_block: 64 columns per wave)", nB);
+    if (K < 8 || K % 8 || K > 4096) return bad("K = %d must be a multiple of 8 in [8, 4096] (ddacc_block: 8 k per trip)", K);
+  }
+  if (form == DD_FORM_I8) {
+    if (K < 32 || K % 32 || K > 2048) return bad("K = %d must be a multiple of 32 in [32, 2048] (int8 product: 32 k per step, int32 sums)", K);
+    if (nA < 64 || nA % 64 || nA > 4096) return bad("nA = %d must be a multiple of 64 in [64, 4096] (int8 product: 64 x 64 per workgroup)", nA);
+    if (nB < 64 || nB % 64 || nB > 4096) return bad("nB = %d must be a multiple of 64 in [64, 4096] (int8 product: 64 x 64 per workgroup)", nB);
+    if ((size_t)10 * K * (nA + nB) > DD_HOOK_I8_BYTES) return bad("digit plane of %ld bytes: ten of them exceed the workspace (%zu bytes)", (long)K * (nA + nB), DD_HOOK_I8_BYTES);
+  }
+  if (residual && !Csub) return bad("the residual needs Csub");
+  if (!residual && Csub) return bad("Csub given for G (the int8 product subtracts as product 1)");
+  if (form == DD_FORM_ROW && (!Keep || !Psi2)) return bad("the row-residual form needs Keep and Psi2");
+  if (form && form != DD_FORM_ROW && !A) return bad("form %d needs A", form);
+
+  GP_HIP(c, hipSetDevice(device));
+  c->device = device; c->M = M; c->Mp = Mp; c->Dp = Dp;
+  size_t nd = 0, ns = 0;
+  if (form == DD_FORM_I8) { nd = (size_t)10 * K * (nA + nB); ns = (size_t)nA + nB; }
+  else if (form == 0 && Mp >= 512 && Mp <= 2048) { ns = (size_t)Mp + std::max(Mp, Dp); nd = (size_t)10 * Mp * ns; }     // GsState::alloc
+  if (nd) {
+    GP_TRY_RC(c->gstep.gsd.alloc(c, nd, DA_RAW)); GP_TRY_RC(c->gstep.gss.alloc(c, ns, DA_RAW));
+    GP_HIP(c, hipMemset(c->gstep.gsd, 0xFF, c->gstep.gsd.bytes())); GP_HIP(c, hipMemset(c->gstep.gss, 0xFF, c->gstep.gss.bytes()));
+  }
+  if (form == 0) {
+    const bool gi8 = gs_i8_wanted(c);
+    form = residual ? residual_form(gi8, Mp, Dp) : G_form(gi8);
+    if (form == DD_FORM_ROW) { if (!Keep || !Psi2) return bad("the step's choice here is the row-residual form: it needs Keep and Psi2"); if (M < 1 || M > Mp) return bad("M = %d must be in [1, Mp]", M); }
+    else if (!A) return bad("the step's choice here is form %d: it needs A", form);
+  }
+  *form_ran = form;
+  const size_t na = (size_t)nA * K, nb = (size_t)K * nB, no = (size_t)nA * nB, nout = no + 2 * (size_t)nB;
+  DevBuf<double> dA, dB, dC, dKeep, dPsi2, dOut;
+  auto up = [&](DevBuf<double>& d, const double* h, size_t n) {
+    GP_TRY_RC(d.alloc(c, n, DA_RAW));
+    GP_HIP(c, hipMemcpy(d, h, n * sizeof(double), hipMemcpyHostToDevice));
+    return (int)GP_OK;
+  };
+  GP_TRY_RC(up(dB, B, nb));
+  if (form != DD_FORM_ROW) GP_TRY_RC(up(dA, A, na));
+  else { GP_TRY_RC(up(dKeep, Keep, na)); GP_TRY_RC(up(dPsi2, Psi2, na)); }
+  if (Csub) GP_TRY_RC(up(dC, Csub, no));
+  // NaN bytes in the result and its two sentinel rows: the product must write the first, and only the first
+  GP_TRY_RC(dOut.alloc(c, nout, DA_RAW));
+  GP_HIP(c, hipMemset(dOut, 0xFF, dOut.bytes()));
+  const DdProduct p{dA, form == DD_FORM_I8 ? (long)nA : (long)K, nA, dB, (long)nB, nB, K, dOut, (long)nB, residual ? dC.get() : nullptr};
+  if (residual) GP_TRY_RC(form_residual(c, nullptr, form, p, {dKeep, dPsi2, beta, jitA, M}));
+  else GP_TRY_RC(form_G(c, nullptr, form, p));
+  GP_HIP(c, hipDeviceSynchronize());
+  GP_HIP(c, hipMemcpy(out, dOut, dOut.bytes(), hipMemcpyDeviceToHost));
+  return GP_OK;
+}
+}  // namespace gp
+
+extern "C" int gp_debug_dd_product(int device, int product, int form, const int* dims, double beta, double jitA, const double* A, const double* B,
+                                   const double* Csub, const double* Keep, const double* Psi2, double* out, int* form_ran) {
+  gp_ctx tmp;
+  const int rc = gp::dd_product_body(&tmp, device, product, form, dims, beta, jitA, A, B, Csub, Keep, Psi2, out, form_ran);
+  if (rc != GP_OK) gp::g_create_error = tmp.err;
+  return rc;
 }
 
 // raw copy of an internal buffer of the global step (developer tool, tests/devtools/dev_tail_diff.py; not part of the public header)

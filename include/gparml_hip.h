@@ -372,6 +372,19 @@ int gp_debug_gemm_modes(int device, int la, int lb, int m, int n, int k, int bat
  * with_workspace: hand the factorisation a split-k workspace, which moves X^T X to the 128 x 128-tile kernel for n > 896. */
 int gp_debug_potrf_inverse_batched(int device, int n, int batch, int with_workspace, const double* A, double* L, double* Ainv, double* logdet,
                                    int* fail_mask);
+/* ONE of the global step's two extended-precision products on the caller's operands, through the step's own dispatch (csrc/linalg.hip, form_G /
+ * form_residual).  product: 0 = G = A B, 1 = the residual R = Csub - A B.  form: 0 = what the step chooses for (Mp, Dp) under the current options,
+ * 1 = dd-gemm, 2 = dd-residual, 3 = row-residual, 4 = int8; *form_ran gets the form that ran.  dims = 6 ints: M Mp Dp nA nB K.  Forms 0 and 3 take
+ * the step's shapes (nA = K = Mp, nB = Mp for G, Dp for the residual; pass nA = nB = K = 0); forms 1, 2, 4 take nA, nB, K as given.  Operands,
+ * dense row-major: forms 1, 2 read A [nA][K]; form 4 reads A [K][nA] (out[i][j] = sum_k A[k][i] B[k][j]; the step's A is symmetric); B [K][nB];
+ * Csub [nA][nB].  Form 3 ignores A and rebuilds it as the step does from Keep and Psi2 ([Mp][Mp] each): fma(beta, Psi2, Keep) + jitA on the
+ * diagonal, leading M x M block; B = E and Csub = C are [Mp][Dp]; rows M .. Mp of the result are zeros.  out = [nA + 2][nB]: the result and two
+ * sentinel rows; the device buffer behind it, the digit planes and the column scales start as 0xFF bytes, so the sentinel rows come back as they
+ * were.  GP_ERR_BAD_ARG, before any HIP call, for sizes the kernels cannot take (ddacc_block: nA % 8, nB % 64, K % 8; int8: nA % 64, nB % 64, K % 32,
+ * K > 2048, ten digit planes beyond the largest workspace a context allocates), a form that does not compute the product, and form 0 where the
+ * step would not run these functions (Mp = Dp = 128 with the fused tail; dd_kipsi2 or refine_E switched off). */
+int gp_debug_dd_product(int device, int product, int form, const int* dims, double beta, double jitA, const double* A, const double* B,
+                        const double* Csub, const double* Keep, const double* Psi2, double* out, int* form_ran);
 
 #ifdef __cplusplus
 }
