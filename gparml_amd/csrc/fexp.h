@@ -1,4 +1,4 @@
-// Table-free FP64 exp for the statistics kernels (shared by psi.hip and psi2.hip).
+// Table-free FP64 exp for the statistics kernels (shared by psi1.hip and psi2.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

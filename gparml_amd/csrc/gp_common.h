@@ -294,11 +294,13 @@ int run_prep_and_generate(gp_ctx* c);
 int run_phase1(gp_ctx* c);
 int run_phase2(gp_ctx* c);
 bool p2_fast_mode(const gp_ctx* c);
+// psi1.hip
+int run_psi1(gp_ctx* c, bool kfix);      // Psi1 of the prepared trial point into Kaug (kfix: every variance zero, the fixed-variance form)
+int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
 // p2_rem.hip (fixed-embedding phase 2: the ragged last round of row tiles, cut along k)
 struct P2Rem { int q = 0, r = 0, splits = 0, RG = 0; };   // ntiles = q S + r; k splits per tile product; row groups per tile product in the fix-up
 bool p2_rem_plan(int ntiles, int S, int MT, int nc, P2Rem* pl);    // false: the whole-tile plan stands
 int run_phase2_rem(gp_ctx* c, const P2Rem& pl, int S, int kbeg, int kend, int nrb, int main_blocks);
-int launch_psi1_rows(gp_ctx* c, const double* mu, const double* U, const double* lnc1, double* out, long n, long rows, long ld);
 // p1i8.hip (regime A phase 1 on the int8 matrix core)
 bool p1i8_applicable(const gp_ctx* c);
 bool p1i8_applicable_static(const gp_ctx* c);     // the shape / regime conditions alone (not the opt-in switch, not the guard)

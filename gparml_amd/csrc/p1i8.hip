@@ -31,7 +31,7 @@
 //
 // Digits live in HBM as Sl[j][n / 16][col][16]: the 16 consecutive rows a lane feeds to the matrix core as ONE 16-byte operand, columns =
 // the Mp columns of Psi1 followed by the Dp columns of Y (the layout of Kaug's rows).  Psi1's digits are written by psi1_kernel while it
-// generates Psi1 (psi.hip: each lane already walks 16 rows of its two columns), Y's once per upload.  3.8 GB at N = 1e6, M = 512, D = 100.
+// generates Psi1 (psi1.hip: each lane already walks 16 rows of its two columns), Y's once per upload.  3.8 GB at N = 1e6, M = 512, D = 100.
 //
 // Kernel: one workgroup = one 128 x 128 output tile x one n-slice, 8 waves as 2 x 4 of 64 x 32 (two 32 x 32 MFMA tiles, L - 1 orders), k-step =
 // 32 rows; both operand panels (S digits x 2 row blocks x 128 columns x 16 B) arrive by LDS-DMA straight in operand order (the digit

@@ -6,7 +6,7 @@
 //   mean = k*^T W,   var_f = sf2 - k*^T B k*   (one value per point)
 // where k*^T B k* is formed as |Lk^-1 k*|^2 - |La^-1 k*|^2 from the global step's inverse Cholesky factors (Linv = [Lk^-1 ; La^-1], lower):
 // two sums of squares of O(sf2) vectors instead of a quadratic form in Ki - P, whose elements are O(cond / sf2) and cancel.
-//   Psi1* rows: psi1_rows (psi.hip's generic Psi1 kernel on prediction-owned buffers);
+//   Psi1* rows: psi1_rows (psi1.hip's generic Psi1 kernel on prediction-owned buffers);
 //   [mean | Lk^-1 k* | La^-1 k*] = Psi1* [beta E | Linv^T]: two products on the MFMA GEMM core (launch_gemm);
 //   pred_det_rows_kernel: one wave per point, mean out and var = sf2 - sum of squares + sum of squares (+ 1/beta).
 // Uncertain inputs x* ~ N(mu*, diag S*), psi1* = psi1(mu*, S*), psi2* = psi2_point(mu*, S*):
