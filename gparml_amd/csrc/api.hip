@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
+#include <limits>
 
 namespace gp {
 thread_local std::string g_create_error;
@@ -875,6 +876,41 @@ extern "C" int gp_project_rows(gp_ctx* c, int64_t n, const double* Y, const doub
   return run_project(c, (long)n, Y, mean, P, Q_out, X);
 }
 
+// Per new row the nearest training row (csrc/nearest.hip).  Nothing of the evaluation is read or written: only the Y columns of Kaug and the resident
+// X_mu (Y_train == NULL) and the plan's buffers.
+extern "C" int gp_nearest_rows(gp_ctx* c, int64_t n_train, const double* Y_train, int64_t n, const double* Y_test, const int32_t* cols, int n_cols,
+                               double* dist2, int64_t* index, double* x_near) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n must be >= 0");
+  if (cols && n_cols < 1) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n_cols must be >= 1 with a column list (got %d)", n_cols);
+  for (int j = 0; cols && j < n_cols; ++j)
+    if (cols[j] < 0 || cols[j] >= c->D) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: cols[%d] = %d is outside 0 .. D - 1 = %d", j, cols[j], c->D - 1);
+  if (Y_train && x_near) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: x_near is the base mean of a resident row: it cannot be asked for with host rows (Y_train)");
+  if (!Y_train) {
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_nearest_rows: Y_train is NULL (the resident rows) before gp_upload_shard");
+    n_train = c->N;
+  } else if (n_train < 0) {
+    return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n_train must be >= 0");
+  }
+  if (n == 0) return GP_OK;
+  if (!Y_test) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_test is NULL");
+  const int nc = cols ? n_cols : c->D;
+  for (int64_t i = 0; i < n; ++i) {
+    bool ok = true;
+    for (int j = 0; j < nc; ++j) ok = ok && std::isfinite(Y_test[i * c->D + (cols ? cols[j] : j)]);
+    if (!ok) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_test is not finite in an observed column");
+  }
+  if (Y_train && !all_finite(Y_train, (size_t)n_train * c->D)) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_train is not finite");
+  if (!dist2 && !index && !x_near) return GP_OK;
+  if (n_train == 0) {
+    if (dist2) std::fill(dist2, dist2 + n, std::numeric_limits<double>::infinity());
+    if (index) std::fill(index, index + n, (int64_t)-1);
+    return GP_OK;
+  }
+  GP_HIP(c, hipSetDevice(c->device));
+  return run_nearest(c, (long)n_train, Y_train, (long)n, Y_test, cols, n_cols, dist2, index, x_near);
+}
+
 // ---- final gradients ---------------------------------------------------------------------------------------------
 // final = Kmm parts (global step) + all-reduced data parts (phase 2)
 __global__ void add_kernel(const double* a, const double* b, double* out, long n) {
@@ -1053,6 +1089,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   // the A/B switch of phase 2's remainder plan (p2_rem.hip: 0 whole tiles only, 1 the rule, 2 wherever it fits) is taken here and is not one of the
   // listed options: the list in the message below is pinned, name by name, by tests/test_gemm_overlap_rule.py
   if (!std::strcmp(name, "p2_rem")) { g_opt_p2_rem.store(std::max(0, std::min(value, 2))); return GP_OK; }
+  // likewise the chunk length of gp_nearest_rows (nearest.hip: rows per chunk, 0 = the default), for the same reason
+  if (!std::strcmp(name, "nearest_rows")) { g_opt_nn_rows.store(std::max(0, value)); return GP_OK; }
   std::string known;
   for (const auto& o : options) {
     if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }

@@ -96,6 +96,7 @@ struct PredPlan;   // predict.hip
 struct InferPlan;  // infer.hip
 struct KmPlan;     // kmeans.hip
 struct PcaPlan;    // pca.hip
+struct NnPlan;     // nearest.hip
 struct JointPlan;  // joint.hip
 struct GradPlan;   // grad.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
@@ -105,6 +106,7 @@ struct PredPlanDelete { void operator()(PredPlan* p) const; };
 struct InferPlanDelete { void operator()(InferPlan* p) const; };
 struct KmPlanDelete { void operator()(KmPlan* p) const; };
 struct PcaPlanDelete { void operator()(PcaPlan* p) const; };
+struct NnPlanDelete { void operator()(NnPlan* p) const; };
 struct JointPlanDelete { void operator()(JointPlan* p) const; };
 struct GradPlanDelete { void operator()(GradPlan* p) const; };
 
@@ -266,6 +268,7 @@ struct gp_ctx {
   std::unique_ptr<gp::InferPlan, gp::InferPlanDelete> infer;  // gp_infer_objective / gp_infer_latent's buffers (infer.hip)
   std::unique_ptr<gp::KmPlan, gp::KmPlanDelete> km;          // gp_kmeans_accumulate's buffers (kmeans.hip)
   std::unique_ptr<gp::PcaPlan, gp::PcaPlanDelete> pca;       // gp_scatter_accumulate / gp_project_rows' buffers (pca.hip)
+  std::unique_ptr<gp::NnPlan, gp::NnPlanDelete> nn;          // gp_nearest_rows' buffers (nearest.hip)
   std::unique_ptr<gp::JointPlan, gp::JointPlanDelete> joint;  // gp_predict_joint / gp_predict_sample's buffers (joint.hip)
   std::unique_ptr<gp::GradPlan, gp::GradPlanDelete> grad;     // gp_predict_grad's buffers (grad.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
@@ -350,6 +353,9 @@ int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres,
 // pca.hip
 int run_scatter(gp_ctx* c, long n, const double* Y, const double* centre, double* sum, double* gram);
 int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const double* P, int Q, double* X);
+// nearest.hip
+int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, double* dist2,
+                int64_t* index, double* x_near);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip
@@ -375,6 +381,7 @@ extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip
 extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
 extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 off, 1 on where the remainder rule admits it, 2 on wherever it fits (measurements)
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
+extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }
 __host__ __device__ inline long le_index(bool il, long n, long m, long Mp) { return il ? ((((n >> 2) * Mp + m) << 2) + (n & 3)) : n * Mp + m; }

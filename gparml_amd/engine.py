@@ -436,6 +436,36 @@ class ShardEngine(object):
         self._ck(self.lib.gp_project_rows(self.h, n, py, pm, pp, P.shape[1], X.ctypes.data_as(_lib._dp)), 'gp_project_rows')
         return X
 
+    # ---- the start of latent inference (gp_nearest_rows) ----------------------------------------------------
+    def nearest_rows(self, Y_test, cols=None, Y_train=None, want_x=True):
+        """Per row of ``Y_test`` (n, D) the nearest training row in squared Euclidean distance over the output columns ``cols`` (None: all; the
+        other columns may hold NaN), among the resident rows of this engine (``Y_train`` None) or the host rows ``Y_train`` (n_train, D).  Returns
+        (dist2 (n,), index (n,) int64, x_near): of equally near rows the lowest index; x_near (n, Q) is the base mean X_mu[index] of the winner,
+        None with host rows or ``want_x`` False.  Without training rows every index is -1 and every dist2 inf.  Shards combine by the minimum
+        (gparml_amd.init.nearest_start).  The evaluation state is left untouched."""
+        Y_test = np.atleast_2d(np.asarray(Y_test, dtype=np.float64))
+        assert Y_test.ndim == 2 and Y_test.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y_test.shape, self.D)
+        n = Y_test.shape[0]
+        Y_test, py = _lib.as_c(Y_test)
+        pc, nc = None, 0
+        if cols is not None:
+            cols = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
+            pc, nc = cols.ctypes.data_as(_lib._ip), int(cols.size)
+        pt, n_train = None, 0
+        if Y_train is not None:
+            Y_train = np.asarray(Y_train, dtype=np.float64)
+            if Y_train.ndim == 1:
+                Y_train = Y_train[:, None]
+            assert Y_train.ndim == 2 and Y_train.shape[1] == self.D, 'Y_train shape %s: (n_train, %d) expected' % (Y_train.shape, self.D)
+            n_train = Y_train.shape[0]
+            Y_train, pt = _lib.as_c(Y_train)
+        dist2, index = np.empty(n), np.empty(n, dtype=np.int64)
+        x = np.empty((n, self.Q)) if (want_x and Y_train is None) else None
+        self._ck(self.lib.gp_nearest_rows(self.h, n_train, pt, n, py, pc, nc, dist2.ctypes.data_as(_lib._dp),
+                                          index.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), x.ctypes.data_as(_lib._dp) if x is not None else None),
+                 'gp_nearest_rows')
+        return dist2, index, x
+
     @property
     def n_rows(self):
         """Rows ``kmeans_accumulate`` clusters with X None (init.kmeans draws its seeds over them) and ``scatter_accumulate`` sums with Y None."""

@@ -1,4 +1,5 @@
-"""The two initialisations on the device: the k-means that places the inducing points, and the PCA that turns Y into the starting embeddings.
+"""The initialisations on the device: the k-means that places the inducing points, the PCA that turns Y into the starting embeddings, and the
+nearest-training-row search that starts the latent inference of new rows.
 
 k-means.  ``parallel_GPLVM.init_statistics`` calls ``scipy.cluster.vq.kmeans(embeddings, M)`` on the host, over the first shards that reach M rows
 (parallel_GPLVM.py:179-186).  A pass of that loop is N K Q distance terms -- an hour of host time at N = 1e6, M = 512 with scipy's twenty
@@ -11,6 +12,10 @@ each scaled to unit standard deviation) runs over ALL data (local_MapReduce.py:5
 same axes are the eigenvectors of the D x D scatter matrix, a SUM over shards and ranks: ``ShardEngine.scatter_accumulate`` (csrc/pca.hip) yields
 per shard the column sums and the Gram matrix of the rows shifted by a centre, ``pca_axes`` is the eigen part on the host,
 ``ShardEngine.project_rows`` projects; ``pca`` drives the passes.
+
+Nearest start (the end of this file).  ``predict.test`` starts every new point at the trained embedding of the training output nearest to it,
+searched shard by shard with a k-d tree on the host (predict.py:44-66).  ``ShardEngine.nearest_rows`` (csrc/nearest.hip) yields per shard and new
+row the least squared distance and its row; ``nearest_start`` takes the minimum over shards and ranks with the reference's tie rule and cut-off.
 """
 import numpy
 
@@ -202,3 +207,63 @@ def pca(parts, Q, allreduce=None):
     mean, V, std = pca_axes(n_tot, centre, acc[:D], acc[D:].reshape(D, D), int(Q))
     P = V / std
     return mean, V, std, [p.project_rows(mean, P) for p in parts]
+
+
+# ------------------------------------------------------------------------------------------------- nearest start
+def nearest_start(parts, Y_test, cols=None, cutoff=6.0, allreduce=None, rank=0, world=1):
+    """The starting means of latent inference: every row of ``Y_test`` (n, D) gets the embedding of the training row nearest to it over the
+    output columns ``cols`` (None: all), as ``Predictor.nearest_training_embeddings`` (predict.py:44-66) does with a k-d tree per shard.
+    Returns (X_mu0 (n, Q), dist (n,), owner (n,), index (n,)): the means, the Euclidean distance to the nearest training row (inf without one),
+    the part that holds it (counted over all ranks in the order rank, part) and its row there; owner and index are -1 where the mean stayed zero.
+
+    parts: an iterable (taken one at a time: a generator keeps one shard in memory) of engines whose resident rows and base means are searched
+    (``ShardEngine.nearest_rows``), or of (engine, Y_shard, X_shard) for host rows passed through the engine.
+    The rules are the reference's: inside a part the lowest row wins ties; a later part replaces the best only when strictly nearer
+    (predict.py:63); a new row whose nearest distance is not < ``cutoff`` keeps a zero mean (cKDTree's distance_upper_bound is strict: a row at
+    exactly 6.0 is not returned, one at nextafter(6, 0) is).
+    allreduce: a function that sums a float64 vector over the ranks holding the other parts (None: this process holds them all), as
+    ``pca`` takes; ``rank`` and ``world`` are then this process' place among them.  The minimum distance over the ranks wins, among the ranks that
+    hold it the lowest, and that rank's row is summed out to all.  COLLECTIVE then: two calls -- every rank's distances (each in a slot of its
+    own: a sum that gathers), then the winners' rows -- and every rank returns the same arrays."""
+    Y_test = numpy.atleast_2d(numpy.asarray(Y_test, dtype=numpy.float64))
+    n = Y_test.shape[0]
+    best = numpy.full(n, numpy.inf)
+    owner, index = numpy.full(n, -1, dtype=numpy.int64), numpy.full(n, -1, dtype=numpy.int64)
+    X, n_parts = None, 0
+    for k, part in enumerate(parts):
+        if isinstance(part, (tuple, list)):
+            engine, Ys, Xs = part
+            d2, idx, _ = engine.nearest_rows(Y_test, cols=cols, Y_train=Ys, want_x=False)
+            Xs = numpy.asarray(Xs, dtype=numpy.float64)
+            x = numpy.zeros((n, Xs.shape[1]))
+            x[idx >= 0] = Xs[idx[idx >= 0]]
+        else:
+            d2, idx, x = part.nearest_rows(Y_test, cols=cols)
+        if X is None:
+            X = numpy.zeros((n, x.shape[1]))
+        closer = (d2 < best) & (idx >= 0)                     # strict: an equally near row of a later part does not win
+        best[closer], owner[closer], index[closer], X[closer] = d2[closer], k, idx[closer], x[closer]
+        n_parts = k + 1
+    if allreduce is not None:
+        world, rank = int(world), int(rank)
+        assert 0 <= rank < world, 'nearest_start: rank %d of %d' % (rank, world)
+        slots = numpy.zeros((world, n + 2))                   # a rank's distances | its number of parts | its Q (0 without parts)
+        slots[rank, :n], slots[rank, n], slots[rank, n + 1] = best, n_parts, 0 if X is None else X.shape[1]
+        slots = numpy.asarray(allreduce(slots.ravel()), dtype=numpy.float64).reshape(world, n + 2)
+        winner = numpy.argmin(slots[:, :n], axis=0)           # the first of equal minima: the lowest rank
+        best = slots[winner, numpy.arange(n)]
+        first_part, Q = int(round(slots[:rank, n].sum())), int(round(slots[:, n + 1].max()))
+        mine = (winner == rank) & (index >= 0)
+        row = numpy.full((n, Q + 2), -0.0)                    # -0.0: the identity of the sum, also for a winner's -0.0
+        if mine.any():
+            row[mine, :Q], row[mine, Q], row[mine, Q + 1] = X[mine], first_part + owner[mine], index[mine]
+        row = numpy.asarray(allreduce(row.ravel()), dtype=numpy.float64).reshape(n, Q + 2)
+        found = numpy.isfinite(best)
+        X = numpy.where(found[:, None], row[:, :Q], 0.0)
+        owner = numpy.where(found, numpy.round(row[:, Q]), -1).astype(numpy.int64)
+        index = numpy.where(found, numpy.round(row[:, Q + 1]), -1).astype(numpy.int64)
+    assert X is not None and X.shape[1] >= 1, 'nearest_start: no parts'
+    dist = numpy.sqrt(best)
+    far = ~(dist < cutoff)
+    X[far], owner[far], index[far] = 0.0, -1, -1
+    return X, dist, owner, index

@@ -101,20 +101,23 @@ class Predictor(object):
             raise
         return eng
 
-    def infer(self, Y_test, mask=None, X_mu0=None, X_S0=None, training=None, is_random_init=False, random_restarts=0, iterations=100, gtol=1e-5):
+    def infer(self, Y_test, mask=None, X_mu0=None, X_S0=None, training=None, is_random_init=False, random_restarts=0, iterations=100, gtol=1e-5,
+              nearest='host'):
         """q(x*) = N(X_mu, diag X_S) of every NEW row of ``Y_test`` (n, D) with q(u) frozen at the trained optimum: [X_mu (n, Q), X_S (n, Q), L (n,)],
         L the row's own bound (ShardEngine.infer_latent: every row is an independent problem, optimised on the device).
 
         Observed outputs of a row: the columns of ``mask`` (None: all) that are not NaN in it; only these enter the likelihood, so a row with
         missing outputs is embedded from what it has.  Rows are grouped by that pattern, one device call per pattern.  Starting mean: ``X_mu0``
         when given; else, as ``test``, the embedding of the nearest training output over the row's observed columns (``training`` = iterable of
-        (Y_shard, X_shard) pairs, kept in memory and searched once per pattern) or, with ``is_random_init``, a random inducing point for EVERY
+        (Y_shard, X_shard) pairs, kept in memory and searched once per pattern: with a k-d tree on the host, or, with ``nearest='device'``, by
+        ``init.nearest_start`` on the trained engine) or, with ``is_random_init``, a random inducing point for EVERY
         row followed by ``random_restarts`` further random inducing points per row; restarts are laid out as rows of the same call (row i's
         starts are rows i (R + 1) .. i (R + 1) + R) and the best L is kept per row (the earliest on ties).  Starting variance ``X_S0`` or
         0.5 + 0.01 randn clipped to [0.001, 1] (predict.py:71-72), shared by a row's restarts."""
         Y = numpy.atleast_2d(numpy.asarray(Y_test, dtype=float))
         n, Q = Y.shape[0], self.Q
         assert Y.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y.shape, self.D)
+        assert nearest in ('host', 'device'), "nearest must be 'host' or 'device'"
         Z = numpy.asarray(self.gs['Z'], dtype=float)
         cols = numpy.arange(self.D) if mask is None else numpy.unique(numpy.asarray(list(mask), dtype=int))
         observed = ~numpy.isnan(Y[:, cols])
@@ -143,7 +146,9 @@ class Predictor(object):
             for key in sorted(groups, key=lambda k: groups[k][0]):
                 rows = numpy.asarray(groups[key])
                 c = cols[observed[rows[0]]]
-                if starts is None:
+                if starts is None and nearest == 'device':
+                    s = self._nearest_on_device(eng, Y[rows], training, c)[:, None, :]
+                elif starts is None:
                     s = self.nearest_training_embeddings(Y[rows], training, Q, c)[:, None, :]
                 else:
                     s = starts[rows]
@@ -218,6 +223,13 @@ class Predictor(object):
             X_mu[closer] = numpy.asarray(X)[ind[closer]]
         return X_mu
 
+    @staticmethod
+    def _nearest_on_device(engine, Y_test, training, mask=None):
+        """``nearest_training_embeddings`` with the search on the device: every (Y_shard, X_shard) of ``training`` passes through ``engine`` as
+        host rows (init.nearest_start), one shard in memory at a time; the same tie rule and cut-off."""
+        from . import init
+        return init.nearest_start(((engine, Ys, Xs) for Ys, Xs in training), Y_test, cols=None if mask is None else list(mask))[0]
+
     def _optimise(self, X_mu0, X_S0, iterations):
         x0 = numpy.concatenate((X_mu0.flatten(), X_S0.flatten()))
         x0 = numpy.array([transform_back(b, x) for b, x in zip(self.bounds, x0)])
@@ -226,11 +238,13 @@ class Predictor(object):
         n = len(t) // 2
         return [t[:n].reshape(self.shape), t[n:].reshape(self.shape), -flog[-1]]
 
-    def test(self, Y_test, X_mu0=None, X_S0=None, iterations=100, training=None, mask=None, is_random_init=False, random_restarts=100):
+    def test(self, Y_test, X_mu0=None, X_S0=None, iterations=100, training=None, mask=None, is_random_init=False, random_restarts=100,
+             nearest='host'):
         """predict.test (predict.py:19-111) -> [X_mu, X_S, likelihood] of the new points.
 
         Starting mean: ``X_mu0`` when given; otherwise, as the reference, the embedding of the nearest training output (``training`` =
-        iterable of (Y_shard, X_shard), ``mask`` = output columns to compare; no restarts, predict.py:43) or, with ``is_random_init``, a
+        iterable of (Y_shard, X_shard), ``mask`` = output columns to compare; no restarts, predict.py:43; ``nearest='device'`` searches on the
+        GPU, the shards passing through an engine as host rows, instead of with k-d trees on the host) or, with ``is_random_init``, a
         random inducing point, followed by ``random_restarts`` further optimisations from other random inducing points that keep the best
         likelihood (predict.py:93-108; like the reference this branch starts ONE row of Z, so it serves a single new point).  Starting
         variance 0.5 + 0.01 randn clipped to [0.001, 1] (predict.py:71-72), drawn once; a restart begins at the best variances so far.  The global numpy
@@ -245,7 +259,18 @@ class Predictor(object):
             if training is None:
                 raise AssertionError('predict.test needs the training shards (training=...) or an initial mean (X_mu0=...)')
             random_restarts = 0                                                     # predict.py:43
-            X_mu0 = self.nearest_training_embeddings(self.Y_test, training, self.Q, mask)
+            assert nearest in ('host', 'device'), "nearest must be 'host' or 'device'"
+            if nearest == 'device':
+                cls = self._engine_cls
+                if cls is None:
+                    from .engine import ShardEngine as cls
+                eng = cls(1, self.D, self.M, self.Q, device=self.device)          # host rows pass through it: no model is needed
+                try:
+                    X_mu0 = self._nearest_on_device(eng, self.Y_test, training, mask)
+                finally:
+                    eng.close()
+            else:
+                X_mu0 = self.nearest_training_embeddings(self.Y_test, training, self.Q, mask)
         self.shape = X_mu0.shape
         if X_S0 is None:
             X_S0 = numpy.clip(numpy.ones(self.shape) * 0.5 + 0.01 * numpy.random.randn(*self.shape), 0.001, 1)   # predict.py:71-72

@@ -278,6 +278,25 @@ int gp_kmeans_accumulate(gp_ctx* ctx, int64_t n, const double* X, int K, const d
 int gp_scatter_accumulate(gp_ctx* ctx, int64_t n, const double* Y, const double* centre, double* sum, double* gram);
 int gp_project_rows(gp_ctx* ctx, int64_t n, const double* Y, const double* mean, const double* P, int Q_out, double* X);
 
+/* ---- the start of latent inference ------------------------------------------------------------------ */
+/* predict.test starts every new point at the trained embedding of the training output nearest to it (predict.py:44-66).  For each of the n rows
+ * of Y_test (n,D) this finds, among a set of training rows, the row of least squared Euclidean distance over the observed columns
+ * cols[0 .. n_cols) (each in 0 .. D - 1; cols == NULL: all D columns, n_cols is ignored), computed in the direct form
+ * sum_j (y[cols[j]] - t[cols[j]])^2, j ascending with one fused multiply-add per term (never |y|^2 - 2 y.t + |t|^2, whose cancellation decides
+ * near-ties).  Columns of Y_test outside cols may hold NaN and are never read.  Training rows: Y_train == NULL: the context's resident rows
+ * (n_train is ignored; GP_ERR_STATE before an upload) -- the padding of the resident layout never contributes or wins; otherwise host rows
+ * (n_train,D), taken in chunks through the library's own buffers.  Outputs, any may be NULL: dist2 (n) the least squared distance; index (n) the
+ * row that has it -- of equally near rows the lowest; x_near (n,Q) the base mean X_mu[index] of that row, resident rows only.  No training rows:
+ * every index is -1 and every dist2 +inf.  The minimum over shards is the caller's (gparml_amd/init.py: nearest_start, with the reference's cut-off).
+ * A row replaces the best one only when strictly nearer, or equally near with a lower index, at every level (csrc/nearest.hip); there are no
+ * atomics: results are bit-identical from run to run, between host rows and resident rows, and for every chunking of either side.  A new row's
+ * result never depends on the other new rows.  Synchronous.  Leaves the evaluation state untouched: gp_phase2 / gp_finish / gp_predict after it
+ * give bit-identical results.  GP_ERR_BAD_ARG for n < 0, n_train < 0, a column outside 0 .. D - 1, n_cols < 1 with a column list, x_near together
+ * with host rows, a NULL Y_test with n > 0, and a non-finite Y_train or observed element of Y_test; n = 0 writes nothing. */
+int gp_nearest_rows(gp_ctx* ctx, int64_t n_train, const double* Y_train,   /* NULL: the resident rows, n_train ignored */
+                    int64_t n, const double* Y_test, const int32_t* cols, int n_cols, /* cols NULL: all D columns */
+                    double* dist2, int64_t* index, double* x_near);        /* (n,), (n,), (n,Q) or NULL; x_near needs resident rows */
+
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
 /* set the reduced statistics from the host (partial_terms.set_local_statistics, partial_terms.py:54-61) */
@@ -345,7 +364,8 @@ int gp_debug_force_staging(int on);
  * step of E with a double-double residual.  bench.py times the global step with and without to print their cost.
  * "poison_alloc" (also GPARML_POISON=1 at load time): every allocation without a documented zero contract is filled with NaN bytes and
  * gp_set_globals refills the per-evaluation buffers with them -- a kernel that reads what this evaluation did not write fails
- * deterministically (tests/test_gpu_poison.py). */
+ * deterministically (tests/test_gpu_poison.py).  "nearest_rows", k: gp_nearest_rows takes its new rows k at a time (rounded up to 16) and host
+ * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults. */
 int gp_debug_set_option(const char* name, int value);
 /* in-place lower Cholesky + inverse of an SPD (n,n) matrix; logdet out; returns GP_ERR_NOT_PD on failure */
 int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet);
