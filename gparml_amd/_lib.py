@@ -19,6 +19,7 @@ ARR = dict(KMM=0, KMM_INV=1, PSI1=2, PSI2_SUM=3, PSI1TY=4, KMM_PLUS_OP_INV=5, DF
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int32)
 _vp = ctypes.c_void_p
+_u8p = ctypes.POINTER(ctypes.c_uint8)
 _i64 = ctypes.c_int64
 
 # every symbol include/gparml_hip.h declares: name -> (restype, argtypes)
@@ -63,6 +64,8 @@ SIGNATURES = {
     'gp_predict_grad': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     'gp_infer_objective': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_infer_latent': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
+    'gp_infer_objective_rows': (ctypes.c_int, [_vp, _i64, _dp, _u8p, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    'gp_infer_latent_rows': (ctypes.c_int, [_vp, _i64, _dp, _u8p, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     'gp_kmeans_accumulate': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, ctypes.POINTER(_i64), _dp, _ip]),
     'gp_scatter_accumulate': (ctypes.c_int, [_vp, _i64, _dp, _dp, _dp, _dp]),
     'gp_project_rows': (ctypes.c_int, [_vp, _i64, _dp, _dp, _dp, ctypes.c_int, _dp]),

@@ -803,6 +803,52 @@ extern "C" int gp_infer_latent(gp_ctx* c, int64_t n, const double* Y, const int*
   return run_infer(c, 1, (long)n, Y, cols, n_cols, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
 }
 
+// gp_infer_objective_rows / gp_infer_latent_rows: the same, with the observed set of every row in place of the column list
+static int infer_rows_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const uint8_t* observed, const double* X_mu, const double* X_S, int raw,
+                            bool* nothing) {
+  *nothing = true;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
+  GP_TRY(model_ready(c, who));
+  if (n == 0) return GP_OK;
+  if (!Y || !observed || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, observed, X_mu or X_S is NULL", who);
+  const size_t nq = (size_t)n * c->Q;
+  for (size_t i = 0; i < nq; ++i) {
+    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X_mu is not finite", who);
+    const double s = raw ? std::log(1.0 + std::exp(X_S[i])) : X_S[i];
+    if (!std::isfinite(X_S[i]) || !std::isfinite(s) || !(s > 0.0)) return fail(c, GP_ERR_BAD_ARG, "%s: X_S must be finite and > 0", who);
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    int seen = 0;
+    for (int j = 0; j < c->D; ++j) {
+      if (!observed[i * c->D + j]) continue;
+      ++seen;
+      if (!std::isfinite(Y[i * c->D + j])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed entry (row %ld, column %d)", who, (long)i, j);
+    }
+    if (!seen) return fail(c, GP_ERR_BAD_ARG, "%s: row %ld has no observed column", who, (long)i);
+  }
+  *nothing = false;
+  return GP_OK;
+}
+
+extern "C" int gp_infer_objective_rows(gp_ctx* c, int64_t n, const double* Y, const uint8_t* observed, const double* X_mu, const double* X_S, int xs_is_raw,
+                                       double* L, double* grad_mu, double* grad_S) {
+  if (!c) return GP_ERR_BAD_ARG;
+  bool nothing;
+  GP_TRY(infer_rows_check(c, "gp_infer_objective_rows", n, Y, observed, X_mu, X_S, xs_is_raw, &nothing));
+  if (nothing || (!L && !grad_mu && !grad_S)) return GP_OK;
+  return run_infer_rows(c, 0, (long)n, Y, observed, const_cast<double*>(X_mu), const_cast<double*>(X_S), xs_is_raw ? 1 : 0, 0, 0.0, L, grad_mu, grad_S, nullptr);
+}
+
+extern "C" int gp_infer_latent_rows(gp_ctx* c, int64_t n, const double* Y, const uint8_t* observed, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
+                                    double gtol, double* L, int32_t* iters) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (max_iters < 0 || !(gtol >= 0.0)) return fail(c, GP_ERR_BAD_ARG, "gp_infer_latent_rows: max_iters and gtol must be >= 0");
+  bool nothing;
+  GP_TRY(infer_rows_check(c, "gp_infer_latent_rows", n, Y, observed, X_mu, X_S, xs_is_raw, &nothing));
+  if (nothing) return GP_OK;
+  return run_infer_rows(c, 1, (long)n, Y, observed, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
+}
+
 // One Lloyd assignment pass (csrc/kmeans.hip).  Nothing of the evaluation is read or written: only the resident X_mu (X == NULL) and the plan's buffers.
 extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2,
                                     int32_t* labels) {
@@ -1091,6 +1137,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "p2_rem")) { g_opt_p2_rem.store(std::max(0, std::min(value, 2))); return GP_OK; }
   // likewise the chunk length of gp_nearest_rows (nearest.hip: rows per chunk, 0 = the default), for the same reason
   if (!std::strcmp(name, "nearest_rows")) { g_opt_nn_rows.store(std::max(0, value)); return GP_OK; }
+  // and the distinct patterns per chunk of gp_infer_objective_rows / gp_infer_latent_rows (infer.hip: P_cap, 0 = the default)
+  if (!std::strcmp(name, "infer_patterns")) { g_opt_inf_patterns.store(std::max(0, value)); return GP_OK; }
   std::string known;
   for (const auto& o : options) {
     if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }

@@ -347,6 +347,8 @@ int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dv
 // infer.hip
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
+int run_infer_rows(gp_ctx* c, int mode, long n, const double* Y, const unsigned char* observed, double* X_mu, double* X_S, int raw, int max_iters,
+                   double gtol, double* L, double* grad_mu, double* grad_S, int* iters);
 const double* infer_debug_lea(const gp_ctx* c, long* n);              // gp_debug_peek: the chunk's LEA, NULL / 0 without a plan
 // kmeans.hip
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
@@ -382,6 +384,7 @@ extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
 extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 off, 1 on where the remainder rule admits it, 2 on wherever it fits (measurements)
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
+extern std::atomic<int> g_opt_inf_patterns;                   // infer.hip: distinct patterns per chunk of gp_infer_*_rows
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }
 __host__ __device__ inline long le_index(bool il, long n, long m, long Mp) { return il ? ((((n >> 2) * Mp + m) << 2) + (n & 3)) : n * Mp + m; }

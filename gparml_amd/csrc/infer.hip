@@ -26,16 +26,22 @@
 // record per row (lambda, kappa, theta, direction, success flag, ...), three small kernels per iteration and two masked evaluations (the probe for the
 // curvature, only after a success, and the trial point).  The host only enqueues; every INF_POLL iterations it reads one integer, the number of rows
 // still running.  Finished rows are skipped by the evaluation kernels at once.
+//
+// gp_infer_objective_rows / gp_infer_latent_rows: the same for rows that each observe their own columns, one G per distinct pattern of a chunk (the
+// section "rows that each observe their own columns" below; the row kernel's RAGGED form).
 #include "gp_common.h"
 #include "fexp.h"
 #include "lane_reduce.h"
 #include "varpoint.h"
 #include <algorithm>
 #include <cmath>
+#include <numeric>
+#include <unordered_map>
 
 namespace gp {
 
 constexpr int INF_POLL = 8;      // iterations between two reads of the active-row count
+constexpr int INF_AHEAD = 4;     // ragged row kernel: elements of G a lane requests ahead of their use
 
 // test hook (gp_debug_set_option "infer_rows"): rows per chunk, rounded up to 128; 0 = the default below
 std::atomic<int> g_opt_inf_rows{0};
@@ -63,19 +69,21 @@ __global__ void __launch_bounds__(256) inf_gather_e_kernel(const double* __restr
 }
 
 // Gf[k][m] from T = beta^2 Eo Eo^T and Inv = [Ki ; P]: element (a, b) = (min, max) of both, so G is symmetric bit for bit before it is folded
+__device__ __forceinline__ double inf_gfold_element(const double* __restrict__ T, const double* __restrict__ Inv, int M, int Mp, double Do, long e) {
+  const long mm = (long)Mp * Mp;
+  const long k = e / Mp, m = e - k * Mp;
+  double g = 0.0;
+  if (k < M && m <= k) {
+    const long u = m * Mp + k;                         // row = the smaller index
+    g = T[u] - Do * (Inv[u] - Inv[mm + u]);
+    if (m < k) g *= 2.0;
+  }
+  return g;
+}
 __global__ void __launch_bounds__(256) inf_gfold_kernel(const double* __restrict__ T, const double* __restrict__ Inv, int M, int Mp, double Do,
                                                         double* __restrict__ Gf) {
   const long mm = (long)Mp * Mp;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < mm; e += (long)gridDim.x * 256L) {
-    const long k = e / Mp, m = e - k * Mp;
-    double g = 0.0;
-    if (k < M && m <= k) {
-      const long u = m * Mp + k;                       // row = the smaller index
-      g = T[u] - Do * (Inv[u] - Inv[mm + u]);
-      if (m < k) g *= 2.0;
-    }
-    Gf[e] = g;
-  }
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < mm; e += (long)gridDim.x * 256L) Gf[e] = inf_gfold_element(T, Inv, M, Mp, Do, e);
 }
 
 // ZP = Z, ZZ = Z o Z, both [Mp][QP] zero-padded
@@ -140,17 +148,25 @@ struct InfDims {
   int M, Mp, Q, QP, raw;
   double sf2, beta, Do;
 };
+// the ragged form (gp_infer_*_rows): every row has its own observed set, so its own D_o and its own folded G, entry pat[n] of a table [P][Mp][Mp]
+struct InfDimsRows : InfDims {
+  const int* pat;      // [cnt] the row's pattern within the chunk's table
+  const double* Dor;   // [cnt] the row's D_o
+};
 
 // QR: the table width when it is 4, 10 or 16 (one pass, the row factors v2_q z_mq in registers); WIDE: QP a multiple of 16, one pass per 16 latent
 // dimensions with the exponent's factors read from the tables
-template <int QR, bool WIDE>
+// RAGGED: Gf is the chunk's pattern table and row n reads entry a.pat[n] of it and its own a.Dor[n] (both wave-uniform, loaded once per row); the
+// pair loop then keeps the next INF_AHEAD elements of G in flight, because a row whose pattern no other row shares streams its G from HBM
+template <int QR, bool WIDE, bool RAGGED>
 // (the arrays are separate __restrict__ parameters: only then are the wave-uniform reads scalar loads)
 //   xe [cnt][2Q] evaluation points (for the softplus derivative), TB [cnt][5 QP], LC [cnt][2], LEA [cnt][Mp], V [rows][Mp] = beta Yo Eo^T, yy [rows],
 //   ZP, ZZ [Mp][QP], Gf [Mp][Mp] (element (m', m) at m' Mp + m), mask (NULL: every row); out: fe [cnt] = L, ge [cnt][2Q] = dL/dmu | dL/dS (or d/d raw), or NULL
 __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict__ xe, const double* __restrict__ TB, const double* __restrict__ LC,
                                                        const double* __restrict__ LEA, const double* __restrict__ V, const double* __restrict__ yy,
                                                        const double* __restrict__ ZP, const double* __restrict__ ZZ, const double* __restrict__ Gf,
-                                                       const double* __restrict__ shift, const unsigned char* __restrict__ mask, double* __restrict__ fe, double* __restrict__ ge, InfDims a) {
+                                                       const double* __restrict__ shift, const unsigned char* __restrict__ mask, double* __restrict__ fe, double* __restrict__ ge,
+                                                       std::conditional_t<RAGGED, InfDimsRows, InfDims> a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const long n = blockIdx.x * 4L + wave;                 // wave-uniform
@@ -161,6 +177,9 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
   const double* lea = LEA + n * Mp;
   const double* vrow = V + n * Mp;
   const double lnc1 = LC[2 * n];
+  const double* Gn = Gf;
+  double Dn = a.Do;
+  if constexpr (RAGGED) { Gn = Gf + (long)a.pat[n] * Mp * Mp; Dn = a.Dor[n]; }
   for (int qc = 0; qc < QP; qc += QR) {                  // one trip unless WIDE
     // ---- psi1 term: p_m = psi1_m v_m; b0 = sum p, b1_q = sum p (mu_q - z_mq), b2_q = sum p (mu_q - z_mq)^2
     double b0 = 0.0, b1[QR], b2[QR];
@@ -206,24 +225,47 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
 #pragma unroll
       for (int j = 0; j < QR; ++j) { tz[j] = 0.0; if constexpr (!WIDE) f[j] = tb[4 * QP + j] * zm[j]; }
       double r = 0.0;
-      const double* gcol = Gf + m;
+      const double* gcol = Gn + m;
+      // RAGGED: m' in groups of INF_AHEAD, ascending all the same: while a group is worked on, the G elements of the next one are in flight (rows
+      // clamped to M - 1: what is loaded beyond the column's end is never used)
+      constexpr int STEP = RAGGED ? INF_AHEAD : 1;
+      double ga[STEP], gb[STEP];
+      if constexpr (RAGGED) {
+#pragma unroll
+        for (int u = 0; u < STEP; ++u) ga[u] = gcol[(long)min(r0 + u, M - 1) * Mp];
+      }
 #pragma unroll 1
-      for (int k = r0; k < M; ++k) {                     // wave-uniform m'
-        const double* zk = ZP + (long)k * QP;
-        const double* zzk = ZZ + (long)k * QP;
-        double s = lm + lea[k];
-        if constexpr (WIDE) {
-          for (int q = 0; q < QP; ++q) s = fma(tb[4 * QP + q] * zm[q], zk[q], s);
-        } else {
+      for (int k0 = r0; k0 < M; k0 += STEP) {            // wave-uniform m'
+        if constexpr (RAGGED) {
 #pragma unroll
-          for (int q = 0; q < QR; ++q) s = fma(f[q], zk[q], s);
+          for (int u = 0; u < STEP; ++u) gb[u] = gcol[(long)min(k0 + STEP + u, M - 1) * Mp];
         }
-        const double t = gcol[(long)k * Mp] * fexp(s);   // exactly 0 for m > m' and for padding rows
-        r += t;
 #pragma unroll
-        for (int j = 0; j < QR; ++j) {
-          tz[j] = fma(t, zk[qc + j], tz[j]);
-          a2[j] = fma(t, zzk[qc + j], a2[j]);
+        for (int u = 0; u < STEP; ++u) {
+          const int k = k0 + u;
+          if (RAGGED && k >= M) break;
+          const double* zk = ZP + (long)k * QP;
+          const double* zzk = ZZ + (long)k * QP;
+          double s = lm + lea[k];
+          if constexpr (WIDE) {
+            for (int q = 0; q < QP; ++q) s = fma(tb[4 * QP + q] * zm[q], zk[q], s);
+          } else {
+#pragma unroll
+            for (int q = 0; q < QR; ++q) s = fma(f[q], zk[q], s);
+          }
+          double g;
+          if constexpr (RAGGED) g = ga[u]; else g = gcol[(long)k * Mp];
+          const double t = g * fexp(s);                  // exactly 0 for m > m' and for padding rows
+          r += t;
+#pragma unroll
+          for (int j = 0; j < QR; ++j) {
+            tz[j] = fma(t, zk[qc + j], tz[j]);
+            a2[j] = fma(t, zzk[qc + j], a2[j]);
+          }
+        }
+        if constexpr (RAGGED) {
+#pragma unroll
+          for (int u = 0; u < STEP; ++u) ga[u] = gb[u];
         }
       }
       sT += r;
@@ -243,7 +285,7 @@ __global__ void __launch_bounds__(256) inf_rows_kernel(const double* __restrict_
     if (qc == 0) {
       double kl = 0.0;
       for (int q = 0; q < Q; ++q) { const double mq = tb[q] + shift[q], sq = tb[QP + q]; kl += mq * mq + sq - log(sq) - 1.0; }      // the caller's mu
-      const double L = -0.5 * a.Do * log(6.283185307179586477 / a.beta) - 0.5 * a.beta * (yy[n] - 2.0 * b0 + sT + a.Do * a.sf2) - 0.5 * kl;
+      const double L = -0.5 * Dn * log(6.283185307179586477 / a.beta) - 0.5 * a.beta * (yy[n] - 2.0 * b0 + sT + Dn * a.sf2) - 0.5 * kl;
       if (lane == 0 && fe) fe[n] = L;
     }
     const int q = qc + lane;
@@ -454,12 +496,16 @@ struct InfChunk {
   std::unique_ptr<InfOpt> opt;
 };
 
+struct InfRows;
+struct InfRowsDelete { void operator()(InfRows* p) const; };
+
 // the model tables (the plan itself: built by the first call, kept for the context's life)
 struct InferPlan {
   DevBuf<int> cols;             // [D] observed output columns of the call
   DevBuf<double> ZP, ZZ;        // [Mp][QP] Z zero-padded to the latent table width, Z o Z
   DevBuf<double> T, Gf;         // [Mp][Mp] beta^2 Eo Eo^T, G = W_O W_O^T - D_o (Ki - P) folded onto m' >= m
   std::unique_ptr<InfChunk> chunk;
+  std::unique_ptr<InfRows, InfRowsDelete> ragged;   // gp_infer_*_rows' own buffers
 };
 void InferPlanDelete::operator()(InferPlan* p) const { delete p; }
 
@@ -500,8 +546,16 @@ const double* infer_debug_lea(const gp_ctx* c, long* n) {
 
 static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }
 
+// what the ragged form of the row kernel reads in place of the call's one G and D_o (NULL: the shared form)
+struct InfRag {
+  const double* Gf;    // the chunk's pattern table
+  const int* pat;      // [cnt]
+  const double* Dor;   // [cnt]
+};
+
 // one evaluation of the rows of the chunk that mask selects (NULL: all) at xe
-static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do) {
+static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long cnt, int raw, const unsigned char* mask, bool want_grad, int QP, double Do,
+                        const InfRag* rag) {
   hipStream_t st = c->stream;
   const int M = c->M, Mp = c->Mp, Q = c->Q;
   GP_LAUNCH(c, st, inf_prep_kernel, dim3(inf_blocks(cnt)), dim3(256), 0, k.xe, raw, mask, c->alpha, c->shift, cnt, Q, QP, c->sf2, k.TB, k.LC);
@@ -518,13 +572,99 @@ static int inf_evaluate(gp_ctx* c, const InferPlan& p, const InfChunk& k, long c
   return for_width<4, 10, 16, 0>(c, "latent inference row kernel", QP <= 16 ? QP : 0, [&](auto W) -> int {
     constexpr bool WIDE = W() == 0;
     constexpr int QR = WIDE ? 16 : W();
-    GP_LAUNCH(c, st, (inf_rows_kernel<QR, WIDE>), grid, dim3(256), 0, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), k.yy.get(), p.ZP.get(),
+    if (rag) {
+      InfDimsRows ar;
+      static_cast<InfDims&>(ar) = a;
+      ar.pat = rag->pat; ar.Dor = rag->Dor;
+      GP_LAUNCH(c, st, (inf_rows_kernel<QR, WIDE, true>), grid, dim3(256), 0, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), k.yy.get(),
+                p.ZP.get(), p.ZZ.get(), rag->Gf, (const double*)c->shift, mask, k.fe.get(), ge, ar);
+      return GP_OK;
+    }
+    GP_LAUNCH(c, st, (inf_rows_kernel<QR, WIDE, false>), grid, dim3(256), 0, k.xe.get(), k.TB.get(), k.LC.get(), k.LEA.get(), k.V.get(), k.yy.get(), p.ZP.get(),
               p.ZZ.get(), p.Gf.get(), (const double*)c->shift, mask, k.fe.get(), ge, a);
     return GP_OK;
   });
 }
 
-// mode 0: gp_infer_objective (L, grad_mu, grad_S out, any may be NULL); mode 1: gp_infer_latent (X_mu, X_S in/out, L, iters out)
+// what the caller of an entry point handed in.  mode 0: the objective (L, grad_mu, grad_S out, any may be NULL); mode 1: the optimiser (X_mu, X_S
+// in/out, L, iters out)
+struct InfCall {
+  int mode, raw, max_iters;
+  double gtol;
+  double* X_mu;
+  double* X_S;
+  double* L;
+  double* grad_mu;
+  double* grad_S;
+  int* iters;
+};
+
+// A chunk whose V and yy are in place: rows 0 .. cnt - 1 of the chunk are rows dst[0 .. cnt) of the call.  Uploads their points, evaluates or
+// optimises, and writes the results to the caller's rows.  Ends with the stream synchronised.
+static int inf_chunk_solve(gp_ctx* c, const InferPlan& p, const InfChunk& k, const InfCall& a, long cnt, const long* dst, int QP, double Do, const InfRag* rag) {
+  const long Q = c->Q, R = k.rows;
+  hipStream_t st = c->stream;
+  std::vector<double> hx((size_t)cnt * 2 * Q), hout;
+  for (long i = 0; i < cnt; ++i)
+    for (long q = 0; q < Q; ++q) {
+      hx[i * 2 * Q + q] = a.X_mu[dst[i] * Q + q];
+      hx[i * 2 * Q + Q + q] = a.X_S[dst[i] * Q + q];
+    }
+  GP_HIP(c, hipMemcpyAsync(k.xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
+  if (a.mode == 0) {
+    const bool grads = a.grad_mu || a.grad_S;
+    GP_TRY_RC(inf_evaluate(c, p, k, cnt, a.raw, nullptr, grads, QP, Do, rag));
+    hout.resize((size_t)cnt * (2 * Q + 1));
+    double* hl = hout.data() + (size_t)cnt * 2 * Q;
+    if (a.L) GP_HIP(c, hipMemcpyAsync(hl, k.fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+    if (grads) GP_HIP(c, hipMemcpyAsync(hout.data(), k.ge, (size_t)cnt * 2 * Q * 8, hipMemcpyDeviceToHost, st));
+    GP_HIP(c, hipStreamSynchronize(st));
+    for (long i = 0; i < cnt; ++i) {
+      if (a.L) a.L[dst[i]] = hl[i];
+      for (long q = 0; grads && q < Q; ++q) {
+        if (a.grad_mu) a.grad_mu[dst[i] * Q + q] = hout[i * 2 * Q + q];
+        if (a.grad_S) a.grad_S[dst[i] * Q + q] = hout[i * 2 * Q + Q + q];
+      }
+    }
+    return GP_OK;
+  }
+  const InfOpt* o = k.opt.get();
+  ScgArgs s{};
+  s.cnt = cnt; s.Q = (int)Q; s.QP = QP; s.raw_in = a.raw; s.max_iters = a.max_iters; s.gtol = a.gtol;
+  s.xe = k.xe; s.ge = k.ge; s.fe = k.fe; s.TB = k.TB;
+  s.x = o->x; s.gn = o->gn; s.go = o->go; s.d = o->d; s.Scur = o->Scur; s.sc = o->sc; s.si = o->si; s.mask = o->mask;
+  GP_TRY_RC(inf_evaluate(c, p, k, cnt, a.raw, nullptr, true, QP, Do, rag));
+  const dim3 rg(inf_blocks(cnt));
+  GP_LAUNCH(c, st, inf_scg_init_kernel, rg, dim3(256), 0, s);
+  int* d_active = o->si.get() + R * II_COUNT;
+  for (int it = 0; it < a.max_iters; ++it) {
+    if (it % INF_POLL == 0) {
+      int active = 0;
+      GP_LAUNCH(c, st, inf_count_kernel, dim3(1), dim3(256), 0, o->si, cnt, d_active);
+      GP_HIP(c, hipMemcpyAsync(&active, d_active, sizeof(int), hipMemcpyDeviceToHost, st));
+      GP_HIP(c, hipStreamSynchronize(st));
+      if (active == 0) break;
+    }
+    GP_LAUNCH(c, st, inf_scg_probe_kernel, rg, dim3(256), 0, s);
+    GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, Do, rag));
+    GP_LAUNCH(c, st, inf_scg_trial_kernel, rg, dim3(256), 0, s);
+    GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, Do, rag));
+    GP_LAUNCH(c, st, inf_scg_update_kernel, rg, dim3(256), 0, s);
+  }
+  GP_LAUNCH(c, st, inf_scg_out_kernel, rg, dim3(256), 0, s, o->out.get());
+  hout.resize((size_t)cnt * (2 * Q + 2));
+  GP_HIP(c, hipMemcpyAsync(hout.data(), o->out, hout.size() * 8, hipMemcpyDeviceToHost, st));
+  GP_HIP(c, hipStreamSynchronize(st));
+  for (long i = 0; i < cnt; ++i) {
+    const double* r = hout.data() + i * (2 * Q + 2);
+    for (long q = 0; q < Q; ++q) { a.X_mu[dst[i] * Q + q] = r[q]; a.X_S[dst[i] * Q + q] = r[Q + q]; }
+    if (a.L) a.L[dst[i]] = r[2 * Q];
+    if (a.iters) a.iters[dst[i]] = (int)r[2 * Q + 1];
+  }
+  return GP_OK;
+}
+
+// gp_infer_objective (mode 0) / gp_infer_latent (mode 1)
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters) {
   const long Mp = c->Mp, M = c->M, Q = c->Q, D = c->D;
@@ -548,68 +688,173 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
   std::vector<double> yc((size_t)n * Do);
   for (long i = 0; i < n; ++i)
     for (int j = 0; j < Do; ++j) yc[(size_t)i * Do + j] = Y[i * D + hc[j]];
-  std::vector<double> hx((size_t)std::min(n, R) * 2 * Q), hout;
-  std::vector<double> hg;
-  ScgArgs s{};
-  s.Q = (int)Q; s.QP = QP; s.raw_in = raw; s.max_iters = max_iters; s.gtol = gtol;
-  const InfOpt* o = k.opt.get();      // NULL for gp_infer_objective (unless an earlier gp_infer_latent built it)
-  s.xe = k.xe; s.ge = k.ge; s.fe = k.fe; s.TB = k.TB;
-  if (mode == 1) { s.x = o->x; s.gn = o->gn; s.go = o->go; s.d = o->d; s.Scur = o->Scur; s.sc = o->sc; s.si = o->si; s.mask = o->mask; }
+  const InfCall a{mode, raw, max_iters, gtol, X_mu, X_S, L, grad_mu, grad_S, iters};
+  std::vector<long> dst((size_t)std::min(n, R));
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
-    s.cnt = cnt;
-    for (long i = 0; i < cnt; ++i)
-      for (long q = 0; q < Q; ++q) {
-        hx[i * 2 * Q + q] = X_mu[(n0 + i) * Q + q];
-        hx[i * 2 * Q + Q + q] = X_S[(n0 + i) * Q + q];
-      }
-    GP_HIP(c, hipMemcpyAsync(k.xe, hx.data(), (size_t)cnt * 2 * Q * 8, hipMemcpyHostToDevice, st));
+    std::iota(dst.begin(), dst.begin() + cnt, n0);
     GP_HIP(c, hipMemcpyAsync(k.Yc, yc.data() + (size_t)n0 * Do, (size_t)cnt * Do * 8, hipMemcpyHostToDevice, st));
     GP_LAUNCH(c, st, inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, k.Yc, cnt, rows, Do, (int)Dop, k.Yo, k.yy);
     GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, gemm_of({k.Yo, Dop}, {k.Eo, Dop}, {k.V, Mp}, (int)Dop, c->beta)));
-    if (mode == 0) {
-      GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, grad_mu || grad_S, QP, (double)Do));
-      if (L) GP_HIP(c, hipMemcpyAsync(L + n0, k.fe, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
-      if (grad_mu || grad_S) {
-        hg.resize((size_t)cnt * 2 * Q);
-        GP_HIP(c, hipMemcpyAsync(hg.data(), k.ge, (size_t)cnt * 2 * Q * 8, hipMemcpyDeviceToHost, st));
-      }
-      GP_HIP(c, hipStreamSynchronize(st));
-      for (long i = 0; (grad_mu || grad_S) && i < cnt; ++i)
-        for (long q = 0; q < Q; ++q) {
-          if (grad_mu) grad_mu[(n0 + i) * Q + q] = hg[i * 2 * Q + q];
-          if (grad_S) grad_S[(n0 + i) * Q + q] = hg[i * 2 * Q + Q + q];
-        }
-      continue;
+    GP_TRY_RC(inf_chunk_solve(c, p, k, a, cnt, dst.data(), QP, (double)Do, nullptr));
+  }
+  GP_HIP(c, hipStreamSynchronize(st));
+  ++c->sync_epoch;
+  return GP_OK;
+}
+
+// ---- rows that each observe their own columns (gp_infer_objective_rows, gp_infer_latent_rows) ---------------------------------------------------
+// The objective is the one above with O the row's own observed set.  What depends on O: v_n = W_{O_n} y_{n,O_n} = W y0_n (y0: y zero-filled where
+// unobserved, so V is one product), |y_{O_n}|^2, D_o(n), and G_n = beta^2 E diag(o_n) E^T - D_o(n) (Ki - P), which does not depend on (mu, S): it is
+// built once per distinct pattern of a chunk, into a table of folded matrices the row kernel indexes by the row's pattern.
+//
+// Host: the distinct rows of `observed` are numbered in order of first occurrence, the call's rows are ordered by that number (stably) and the results
+// scattered back.  A chunk is a run of that order of at most inf_rows_for rows and at most inf_patterns_for distinct patterns; a pattern whose rows
+// straddle a chunk boundary is rebuilt in the next chunk.  Rows of one pattern are adjacent, so their waves share the pattern's G through L2.
+//
+// Determinism: every product of this path runs on the 128 x 128-tile GEMM kernel without split-k (on_big), whatever the number of rows or patterns in
+// the launch -- launch_gemm would otherwise pick the 32 x 32-tile kernel for small launches, whose k order differs -- and each element of a product is a
+// sum over k in a fixed order that does not depend on the element's place in its tile or on the batch.  A row's outputs therefore depend on its y,
+// pattern, start and the model only.
+
+// the pattern table of a chunk: at most INF_PAT_BYTES of folded matrices (2 GiB: 1024 patterns at Mp = 512, 2 MiB each), a function of Mp alone
+constexpr long INF_PAT_BYTES = 2L << 30;
+// the unfolded products of the patterns are formed INF_SUB_BYTES at a time (32 patterns at Mp = 512), so that they do not double the table
+constexpr long INF_SUB_BYTES = 64L << 20;
+// test hook (gp_debug_set_option "infer_patterns"): distinct patterns per chunk; 0 = the default below
+std::atomic<int> g_opt_inf_patterns{0};
+
+static long inf_patterns_for(long Mp) {
+  const int opt = g_opt_inf_patterns.load();
+  return opt > 0 ? opt : std::max<long>(1, INF_PAT_BYTES / (Mp * Mp * 8));
+}
+
+// Em[p][m][j] = Eo[m][j] where pattern p observes column j, else 0 ([P][Mp][Dp]; Eo [Mp][Dp] is zero beyond M and D already)
+__global__ void __launch_bounds__(256) inf_emask_kernel(const double* __restrict__ Eo, const unsigned char* __restrict__ pmask, int D, int Dp, long md, int P,
+                                                        double* __restrict__ Em) {
+  const long total = md * P;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long q = e / md, r = e - q * md;
+    const int j = (int)(r % Dp);
+    Em[e] = (j < D && pmask[q * D + j]) ? Eo[r] : 0.0;
+  }
+}
+
+// inf_gfold_kernel for a batch of patterns: T [P][Mp][Mp] (only the tiles on or above the diagonal are formed: row <= column is all the fold reads),
+// Do [P], Gf [P][Mp][Mp]
+__global__ void __launch_bounds__(256) inf_gfold_rows_kernel(const double* __restrict__ T, const double* __restrict__ Inv, int M, int Mp,
+                                                             const double* __restrict__ Do, int P, double* __restrict__ Gf) {
+  const long mm = (long)Mp * Mp, total = mm * P;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long q = e / mm, r = e - q * mm;
+    Gf[e] = inf_gfold_element(T + q * mm, Inv, M, Mp, Do[q], r);
+  }
+}
+
+// the ragged call's own buffers, beside the chunk buffers (InfChunk at dop = Dp) it shares with the other two entries
+struct InfRows {
+  long rows = 0, cap = 0, sub = 0;   // rows per chunk; patterns the table holds; patterns per sub-batch of its build
+  DevBuf<double> Gf;                 // [cap][Mp][Mp] the chunk's pattern table, every entry folded as InferPlan::Gf
+  DevBuf<double> Em, T;              // [sub][Mp][Dp] E o mask_p and [sub][Mp][Mp] beta^2 Em Em^T of a sub-batch
+  DevBuf<unsigned char> pmask;       // [cap][D] the chunk's patterns
+  DevBuf<double> pDo;                // [cap] their D_o
+  DevBuf<int> pat;                   // [rows] the pattern of each row of the chunk
+  DevBuf<double> Dor;                // [rows] its D_o
+};
+void InfRowsDelete::operator()(InfRows* p) const { delete p; }
+
+// after inf_alloc; cap: the patterns a chunk of this call can hold at most (the table only grows)
+static int inf_alloc_rows(gp_ctx* c, long R, long cap) {
+  InferPlan& p = *c->infer;
+  if (p.ragged && p.ragged->rows == R && p.ragged->cap >= cap) return GP_OK;
+  const long Mp = c->Mp, sub = std::min(cap, std::max<long>(1, INF_SUB_BYTES / (Mp * Mp * 8)));
+  auto A = [c](auto& b, long n) { return b.alloc(c, (size_t)n, DA_RAW); };
+  p.ragged.reset();
+  std::unique_ptr<InfRows, InfRowsDelete> r(new InfRows());
+  GP_TRY_RC(A(r->Gf, cap * Mp * Mp)); GP_TRY_RC(A(r->Em, sub * Mp * c->Dp)); GP_TRY_RC(A(r->T, sub * Mp * Mp)); GP_TRY_RC(A(r->pmask, cap * c->D));
+  GP_TRY_RC(A(r->pDo, cap)); GP_TRY_RC(A(r->pat, R)); GP_TRY_RC(A(r->Dor, R));
+  r->rows = R; r->cap = cap; r->sub = sub;
+  p.ragged = std::move(r);
+  return GP_OK;
+}
+
+// gp_infer_objective_rows (mode 0) / gp_infer_latent_rows (mode 1); observed (n, D), non-zero = observed, every row with at least one
+int run_infer_rows(gp_ctx* c, int mode, long n, const double* Y, const unsigned char* observed, double* X_mu, double* X_S, int raw, int max_iters,
+                   double gtol, double* L, double* grad_mu, double* grad_S, int* iters) {
+  const long Mp = c->Mp, M = c->M, Q = c->Q, D = c->D, Dp = c->Dp;
+  const int QP = inf_qp((int)Q);
+  // ---- the patterns in order of first occurrence, and the rows in the order of their patterns
+  std::vector<unsigned char> ob((size_t)n * D);
+  for (size_t e = 0; e < ob.size(); ++e) ob[e] = observed[e] ? 1 : 0;
+  std::unordered_map<std::string, int> number;
+  std::vector<int> pid(n);
+  std::vector<long> first, members;         // per pattern: its first row, the number of its rows
+  for (long i = 0; i < n; ++i) {
+    const auto at = number.emplace(std::string(reinterpret_cast<const char*>(ob.data() + i * D), (size_t)D), (int)first.size());
+    if (at.second) { first.push_back(i); members.push_back(0); }
+    pid[i] = at.first->second;
+    ++members[pid[i]];
+  }
+  const long P_all = (long)first.size();
+  std::vector<long> ord(n), next(P_all + 1, 0);
+  for (long q = 0; q < P_all; ++q) next[q + 1] = next[q] + members[q];
+  for (long i = 0; i < n; ++i) ord[next[pid[i]]++] = i;
+  std::vector<double> pdo(P_all, 0.0);
+  for (long q = 0; q < P_all; ++q)
+    for (long j = 0; j < D; ++j) pdo[q] += ob[first[q] * D + j];
+  // ---- buffers
+  const long R = inf_rows_for(c, Dp), Pcap = inf_patterns_for(Mp);
+  GP_TRY_RC(inf_alloc(c, R, Dp, QP, mode == 1));
+  GP_TRY_RC(inf_alloc_rows(c, R, std::min({Pcap, R, P_all})));
+  const InferPlan& p = *c->infer;
+  const InfChunk& k = *p.chunk;
+  const InfRows& r = *p.ragged;
+  hipStream_t st = c->stream;
+  // ---- once per call: E with its padding zeroed (every column "observed") and the latent tables
+  std::vector<int> hc(D);
+  std::iota(hc.begin(), hc.end(), 0);
+  GP_HIP(c, hipMemcpyAsync(p.cols, hc.data(), (size_t)D * sizeof(int), hipMemcpyHostToDevice, st));
+  GP_LAUNCH(c, st, inf_gather_e_kernel, dim3(inf_blocks(Mp * Dp)), dim3(256), 0, c->gstep.E, p.cols, (int)M, (int)Mp, (int)Dp, (int)D, (int)Dp, k.Eo);
+  GP_LAUNCH(c, st, inf_ztab_kernel, dim3(inf_blocks(Mp * QP)), dim3(256), 0, c->Z, (int)M, (int)Mp, (int)Q, QP, p.ZP, p.ZZ);
+  const InfCall a{mode, raw, max_iters, gtol, X_mu, X_S, L, grad_mu, grad_S, iters};
+  const InfRag rag{r.Gf, r.pat, r.Dor};
+  std::vector<double> y0, hdo, hpdo;
+  std::vector<int> hpat;
+  std::vector<unsigned char> hmask;
+  for (long i0 = 0, i1; i0 < n; i0 = i1) {
+    const int pf = pid[ord[i0]];
+    for (i1 = i0; i1 < n && i1 - i0 < R && pid[ord[i1]] - pf < Pcap;) ++i1;
+    const long cnt = i1 - i0, rows = round_up(cnt, TILE), P = pid[ord[i1 - 1]] - pf + 1;
+    // the chunk's patterns and rows; y zero-filled where unobserved, so that what the caller left there (NaN, anything) never reaches the device
+    hmask.resize((size_t)P * D); hpdo.resize(P); hpat.resize(cnt); hdo.resize(cnt); y0.resize((size_t)cnt * D);
+    for (long q = 0; q < P; ++q) {
+      std::copy_n(ob.data() + first[pf + q] * D, D, hmask.data() + q * D);
+      hpdo[q] = pdo[pf + q];
     }
-    GP_TRY_RC(inf_evaluate(c, p, k, cnt, raw, nullptr, true, QP, (double)Do));
-    const dim3 rg(inf_blocks(cnt));
-    GP_LAUNCH(c, st, inf_scg_init_kernel, rg, dim3(256), 0, s);
-    int* d_active = o->si.get() + R * II_COUNT;
-    for (int it = 0; it < max_iters; ++it) {
-      if (it % INF_POLL == 0) {
-        int active = 0;
-        GP_LAUNCH(c, st, inf_count_kernel, dim3(1), dim3(256), 0, o->si, cnt, d_active);
-        GP_HIP(c, hipMemcpyAsync(&active, d_active, sizeof(int), hipMemcpyDeviceToHost, st));
-        GP_HIP(c, hipStreamSynchronize(st));
-        if (active == 0) break;
-      }
-      GP_LAUNCH(c, st, inf_scg_probe_kernel, rg, dim3(256), 0, s);
-      GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
-      GP_LAUNCH(c, st, inf_scg_trial_kernel, rg, dim3(256), 0, s);
-      GP_TRY_RC(inf_evaluate(c, p, k, cnt, 1, o->mask, true, QP, (double)Do));
-      GP_LAUNCH(c, st, inf_scg_update_kernel, rg, dim3(256), 0, s);
-    }
-    GP_LAUNCH(c, st, inf_scg_out_kernel, rg, dim3(256), 0, s, o->out.get());
-    hout.resize((size_t)cnt * (2 * Q + 2));
-    GP_HIP(c, hipMemcpyAsync(hout.data(), o->out, hout.size() * 8, hipMemcpyDeviceToHost, st));
-    GP_HIP(c, hipStreamSynchronize(st));
     for (long i = 0; i < cnt; ++i) {
-      const double* o = hout.data() + i * (2 * Q + 2);
-      for (long q = 0; q < Q; ++q) { X_mu[(n0 + i) * Q + q] = o[q]; X_S[(n0 + i) * Q + q] = o[Q + q]; }
-      if (L) L[n0 + i] = o[2 * Q];
-      if (iters) iters[n0 + i] = (int)o[2 * Q + 1];
+      const long g = ord[i0 + i];
+      hpat[i] = pid[g] - pf;
+      hdo[i] = pdo[pid[g]];
+      for (long j = 0; j < D; ++j) y0[i * D + j] = ob[g * D + j] ? Y[g * D + j] : 0.0;
     }
+    GP_HIP(c, hipMemcpyAsync(r.pmask, hmask.data(), hmask.size(), hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(r.pDo, hpdo.data(), hpdo.size() * 8, hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(r.pat, hpat.data(), hpat.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(r.Dor, hdo.data(), hdo.size() * 8, hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(k.Yc, y0.data(), y0.size() * 8, hipMemcpyHostToDevice, st));
+    // the pattern table, a sub-batch of unfolded products at a time
+    for (long q0 = 0; q0 < P; q0 += r.sub) {
+      const int ps = (int)std::min(r.sub, P - q0);
+      GP_LAUNCH(c, st, inf_emask_kernel, dim3(inf_blocks(ps * Mp * Dp)), dim3(256), 0, k.Eo.get(), r.pmask.get() + q0 * D, (int)D, (int)Dp, Mp * Dp, ps, r.Em.get());
+      GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)Mp, (int)Mp, ps,
+                            gemm_of({r.Em, Dp, Mp * Dp}, {r.Em, Dp, Mp * Dp}, {r.T, Mp, Mp * Mp}, (int)Dp, c->beta * c->beta).triangle(2).batched(ps).on_big(1)));
+      GP_LAUNCH(c, st, inf_gfold_rows_kernel, dim3(inf_blocks(ps * Mp * Mp)), dim3(256), 0, r.T.get(), c->gstep.Inv.get(), (int)M, (int)Mp, r.pDo.get() + q0, ps,
+                r.Gf.get() + q0 * Mp * Mp);
+    }
+    // V = beta Y0 E^T and |y_O|^2 (the unobserved entries add exact zeros)
+    GP_LAUNCH(c, st, inf_ypad_kernel, dim3(inf_blocks(rows)), dim3(256), 0, k.Yc, cnt, rows, (int)D, (int)Dp, k.Yo, k.yy);
+    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)Mp, 1, gemm_of({k.Yo, Dp}, {k.Eo, Dp}, {k.V, Mp}, (int)Dp, c->beta).on_big(1)));
+    GP_TRY_RC(inf_chunk_solve(c, p, k, a, cnt, ord.data() + i0, QP, 0.0, &rag));
   }
   GP_HIP(c, hipStreamSynchronize(st));
   ++c->sync_epoch;

@@ -373,6 +373,36 @@ class ShardEngine(object):
                                           it.ctypes.data_as(_lib._ip)), 'gp_infer_latent')
         return X_mu, X_S, L, it
 
+    # ---- the same for rows that each observe their own columns (gp_infer_objective_rows, gp_infer_latent_rows) ---
+    def _infer_rows_args(self, Y, X_mu, X_S, observed):
+        n, (Y, py), X_mu, X_S, _ = self._infer_args(Y, X_mu, X_S, None)
+        if observed is None:
+            observed = ~np.isnan(Y)
+        observed = np.ascontiguousarray(np.atleast_2d(np.asarray(observed)) != 0, dtype=np.uint8)
+        assert observed.shape == (n, self.D), 'observed shape %s: (%d, %d) expected' % (observed.shape, n, self.D)
+        return n, (Y, py), X_mu, X_S, (observed, observed.ctypes.data_as(_lib._u8p))
+
+    def infer_objective_rows(self, Y, X_mu, X_S, observed=None, xs_is_raw=False, want_grads=True):
+        """``infer_objective`` with the observed set of EVERY row: ``observed`` (n, D), non-zero where Y is observed (None: where Y is not NaN); the
+        other entries of Y are never read.  One device call whatever the number of distinct patterns.  Returns (L, grad_mu, grad_S) as
+        ``infer_objective``; a row's outputs do not depend on the other rows of the call or on their order, bit for bit."""
+        n, (Y, py), X_mu, X_S, (observed, po) = self._infer_rows_args(Y, X_mu, X_S, observed)
+        L, gm, gs = np.empty(n), np.empty((n, self.Q)), np.empty((n, self.Q))
+        dp = lambda a: a.ctypes.data_as(_lib._dp)
+        self._ck(self.lib.gp_infer_objective_rows(self.h, n, py, po, dp(X_mu), dp(X_S), 1 if xs_is_raw else 0, dp(L), dp(gm) if want_grads else None,
+                                                  dp(gs) if want_grads else None), 'gp_infer_objective_rows')
+        return (L, gm, gs) if want_grads else (L, None, None)
+
+    def infer_latent_rows(self, Y, X_mu, X_S, observed=None, xs_is_raw=False, max_iters=100, gtol=1e-5):
+        """``infer_latent`` with the observed set of every row (``observed`` as for ``infer_objective_rows``), all rows in one device call.
+        Returns (X_mu, X_S, L (n,), iters (n,) int32) as ``infer_latent``."""
+        n, (Y, py), X_mu, X_S, (observed, po) = self._infer_rows_args(Y, X_mu, X_S, observed)
+        L, it = np.empty(n), np.zeros(n, dtype=np.int32)
+        dp = lambda a: a.ctypes.data_as(_lib._dp)
+        self._ck(self.lib.gp_infer_latent_rows(self.h, n, py, po, dp(X_mu), dp(X_S), 1 if xs_is_raw else 0, int(max_iters), float(gtol), dp(L),
+                                               it.ctypes.data_as(_lib._ip)), 'gp_infer_latent_rows')
+        return X_mu, X_S, L, it
+
     # ---- initialisation of the inducing points (gp_kmeans_accumulate) -----------------------------------------
     def kmeans_accumulate(self, centres, X=None, want_labels=False):
         """One Lloyd assignment pass of k-means (the vq + update_cluster_means pair inside scipy.cluster.vq.kmeans, parallel_GPLVM.py:179-186) over

@@ -102,7 +102,7 @@ class Predictor(object):
         return eng
 
     def infer(self, Y_test, mask=None, X_mu0=None, X_S0=None, training=None, is_random_init=False, random_restarts=0, iterations=100, gtol=1e-5,
-              nearest='host'):
+              nearest='host', ragged=False, start=None):
         """q(x*) = N(X_mu, diag X_S) of every NEW row of ``Y_test`` (n, D) with q(u) frozen at the trained optimum: [X_mu (n, Q), X_S (n, Q), L (n,)],
         L the row's own bound (ShardEngine.infer_latent: every row is an independent problem, optimised on the device).
 
@@ -113,11 +113,19 @@ class Predictor(object):
         ``init.nearest_start`` on the trained engine) or, with ``is_random_init``, a random inducing point for EVERY
         row followed by ``random_restarts`` further random inducing points per row; restarts are laid out as rows of the same call (row i's
         starts are rows i (R + 1) .. i (R + 1) + R) and the best L is kept per row (the earliest on ties).  Starting variance ``X_S0`` or
-        0.5 + 0.01 randn clipped to [0.001, 1] (predict.py:71-72), shared by a row's restarts."""
+        0.5 + 0.01 randn clipped to [0.001, 1] (predict.py:71-72), shared by a row's restarts.
+
+        ``ragged=True``: the observed set of a row is the same, but ALL rows and all their restarts go to ONE ``infer_latent_rows`` call, whatever
+        the number of patterns (rows with holes in random places have a pattern each); restarts stay rows of that call and the best L per row is
+        kept, the earliest on ties.  The starts work as above; ``training=...`` still searches once per pattern (a masked nearest-row search is
+        not part of this).  ``start='inducing'`` (``ragged=True`` only) needs no training rows: every row starts at the inducing point whose
+        predicted outputs are nearest to the row over its observed columns (``inducing_start``)."""
         Y = numpy.atleast_2d(numpy.asarray(Y_test, dtype=float))
         n, Q = Y.shape[0], self.Q
         assert Y.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y.shape, self.D)
         assert nearest in ('host', 'device'), "nearest must be 'host' or 'device'"
+        assert start in (None, 'inducing'), "start must be None or 'inducing'"
+        assert start is None or ragged, "start='inducing' needs ragged=True"
         Z = numpy.asarray(self.gs['Z'], dtype=float)
         cols = numpy.arange(self.D) if mask is None else numpy.unique(numpy.asarray(list(mask), dtype=int))
         observed = ~numpy.isnan(Y[:, cols])
@@ -128,6 +136,8 @@ class Predictor(object):
             starts = X_mu0[:, None, :]
         elif is_random_init:
             starts = Z[numpy.random.randint(self.M, size=(n, int(random_restarts) + 1))]        # (n, R + 1, Q)
+        elif start == 'inducing':
+            starts, training = None, None
         else:
             if training is None:
                 raise AssertionError('Predictor.infer needs the training shards (training=...), an initial mean (X_mu0=...) or is_random_init')
@@ -143,6 +153,8 @@ class Predictor(object):
         X_mu, X_S, L = numpy.empty((n, Q)), numpy.empty((n, Q)), numpy.empty(n)
         eng = self._trained_engine()
         try:
+            if ragged:
+                return self._infer_ragged(eng, Y, cols, observed, groups, starts, X_S0, training, nearest, iterations, gtol)
             for key in sorted(groups, key=lambda k: groups[k][0]):
                 rows = numpy.asarray(groups[key])
                 c = cols[observed[rows[0]]]
@@ -162,6 +174,48 @@ class Predictor(object):
         finally:
             eng.close()
         return [X_mu, X_S, L]
+
+    def _infer_ragged(self, eng, Y, cols, observed, groups, starts, X_S0, training, nearest, iterations, gtol):
+        """``infer`` with ``ragged=True`` on the trained engine: one ``infer_latent_rows`` call for every row and restart."""
+        n, Q = Y.shape[0], self.Q
+        obs = numpy.zeros((n, self.D), dtype=bool)
+        obs[:, cols] = observed
+        if starts is None and training is None:                                         # start='inducing'
+            Z = numpy.asarray(self.gs['Z'], dtype=float)
+            starts = self.inducing_start(Y, obs, Z, eng.predict(Z)[0])[:, None, :]
+        elif starts is None:                                                            # the nearest training output, searched per pattern
+            starts = numpy.empty((n, 1, Q))
+            for key in sorted(groups, key=lambda k: groups[k][0]):
+                rows = numpy.asarray(groups[key])
+                c = cols[observed[rows[0]]]
+                find = self._nearest_on_device if nearest == 'device' else None
+                starts[rows, 0] = find(eng, Y[rows], training, c) if find else self.nearest_training_embeddings(Y[rows], training, Q, c)
+        k = starts.shape[1]
+        m, v, l, _ = eng.infer_latent_rows(numpy.repeat(Y, k, axis=0), starts.reshape(-1, Q), numpy.repeat(X_S0, k, axis=0),
+                                           observed=numpy.repeat(obs, k, axis=0), max_iters=iterations, gtol=gtol)
+        l = numpy.asarray(l).reshape(n, k)
+        best = numpy.argmax(l, axis=1)                                                  # the earliest of equal maxima
+        pick = numpy.arange(n) * k + best
+        return [numpy.asarray(m)[pick], numpy.asarray(v)[pick], l[numpy.arange(n), best]]
+
+    @staticmethod
+    def inducing_start(Y, observed, Z, Mz, block=None):
+        """The start of ``infer(..., start='inducing')``: for every row of Y (n, D) the inducing point z_m (row of Z (M, Q)) that minimises
+        sum over the row's observed d of (y_d - Mz[m, d])^2, Mz (M, D) the predicted mean at the inducing points; the lowest m on ties.  Entries of
+        Y outside ``observed`` (n, D) are never used and may be NaN.  Host arithmetic in the direct form (differences first), ``block`` rows at a time (default: about 32 MB of
+        differences): no (n, M, D) array is formed."""
+        Y, Z, Mz = numpy.atleast_2d(numpy.asarray(Y, dtype=float)), numpy.asarray(Z, dtype=float), numpy.asarray(Mz, dtype=float)
+        o = numpy.atleast_2d(numpy.asarray(observed)) != 0
+        assert o.shape == Y.shape and Mz.shape == (Z.shape[0], Y.shape[1]), 'inducing_start: Y %s, observed %s, Mz %s' % (Y.shape, o.shape, Mz.shape)
+        out = numpy.empty((Y.shape[0], Z.shape[1]))
+        if block is None:
+            block = max(1, (4 << 20) // max(1, Mz.size))
+        for i0 in range(0, Y.shape[0], block):
+            ob = o[i0:i0 + block]
+            diff = numpy.where(ob[:, None, :], numpy.where(ob, Y[i0:i0 + block], 0.0)[:, None, :] - Mz[None, :, :], 0.0)      # (block, M, D)
+            d2 = numpy.einsum('bmd,bmd->bm', diff, diff)
+            out[i0:i0 + block] = Z[numpy.argmin(d2, axis=1)]                            # argmin: the first of equal minima
+        return out
 
     def impute(self, Y_test, mask, include_noise=False, **infer_args):
         """Reconstruct the outputs of new rows from the observed columns ``mask``: ``infer`` (its keyword arguments pass through), then

@@ -232,6 +232,29 @@ int gp_infer_objective(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* c
  * returned point, bit for bit, and never below the value at the start.  Restarts are the caller's rows. */
 int gp_infer_latent(gp_ctx* ctx, int64_t n, const double* Y, const int32_t* cols, int n_cols, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
                     double gtol, double* L, int32_t* iters);
+/* The same two for rows that each observe their OWN columns, in one call.  observed (n,D), row-major: a non-zero entry means Y[i][d] is observed; an
+ * entry of Y with observed == 0 is never read and may be NaN.  Each row's L is gp_infer_objective's formula with O that row's own observed set:
+ * v = W_O y_O, |y_O|^2 and D_o are per-row values, and G = W_O W_O^T - D_o B is built once per distinct pattern (row of observed) on the device,
+ * never per evaluation.  Everything else is word for word the contract of the two entries above: X_S and xs_is_raw, the outputs and which may be
+ * NULL, the optimiser (only steps that do not lower L are accepted; L is gp_infer_objective_rows' value at the returned point, bit for bit, and
+ * never below the value at the start; iters per row), the state rule (GP_ERR_STATE unless the last global step succeeded on the statistics and
+ * globals as they are now), n = 0 writes nothing, synchronous, and the evaluation state is left untouched: phase 2 / gp_finish / gp_predict after
+ * it give bit-identical results.  GP_ERR_BAD_ARG, decided before anything is launched, for n < 0, a NULL observed or Y with n > 0, a row with no
+ * observed column (the message names the first such row), a non-finite observed entry of Y, non-finite X_mu, variances that are not > 0,
+ * max_iters < 0 or a gtol that is not >= 0.
+ * Ordering (csrc/infer.hip): the distinct patterns are numbered in order of first occurrence, the rows are processed in the (stable) order of their
+ * pattern's number and the results are scattered back to the caller's order.  A chunk is a run of that order of at most R rows (the chunk length
+ * of the two entries above at D observed columns) and at most P_cap = max(1, 2 GiB / (Mp^2 * 8 bytes)) distinct patterns (Mp = M rounded up to
+ * 128: 1024 patterns at M = 512), a function of M alone and never of the device; a pattern whose rows straddle a chunk boundary is rebuilt in the
+ * next chunk.  Rows of one pattern share its G through the cache; a call whose rows all differ reads Mp^2 * 4 bytes of G per row and evaluation.
+ * Determinism: a row's outputs depend on that row's y, pattern and start and on the model only, bit for bit -- the same alone, in any batch, in
+ * any row order, and wherever a chunk or pattern-table boundary falls (every matrix product of this path runs on one fixed GEMM kernel without
+ * split-k, whatever the launch size; fixed summation order, no floating-point atomics).  They agree with the shared-pattern entries to rounding,
+ * not bit for bit. */
+int gp_infer_objective_rows(gp_ctx* ctx, int64_t n, const double* Y, const uint8_t* observed, const double* X_mu, const double* X_S, int xs_is_raw,
+                            double* L, double* grad_mu, double* grad_S);
+int gp_infer_latent_rows(gp_ctx* ctx, int64_t n, const double* Y, const uint8_t* observed, double* X_mu, double* X_S, int xs_is_raw, int max_iters,
+                         double gtol, double* L, int32_t* iters);
 
 /* ---- initialisation of the inducing points ---------------------------------------------------------- */
 /* One Lloyd assignment pass of k-means: the scipy.cluster.vq.vq + update_cluster_means pair inside scipy.cluster.vq.kmeans, which
@@ -365,7 +388,8 @@ int gp_debug_force_staging(int on);
  * "poison_alloc" (also GPARML_POISON=1 at load time): every allocation without a documented zero contract is filled with NaN bytes and
  * gp_set_globals refills the per-evaluation buffers with them -- a kernel that reads what this evaluation did not write fails
  * deterministically (tests/test_gpu_poison.py).  "nearest_rows", k: gp_nearest_rows takes its new rows k at a time (rounded up to 16) and host
- * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults. */
+ * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults.  "infer_patterns", k: a chunk of
+ * gp_infer_objective_rows / gp_infer_latent_rows holds at most k distinct patterns (P_cap = k); 0 restores the default. */
 int gp_debug_set_option(const char* name, int value);
 /* in-place lower Cholesky + inverse of an SPD (n,n) matrix; logdet out; returns GP_ERR_NOT_PD on failure */
 int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet);
