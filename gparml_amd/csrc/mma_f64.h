@@ -242,7 +242,8 @@ __device__ __forceinline__ void mma_chunk(const double* sA, const double* sB, Ac
 // p1_kernel8, p1v2_kernel's F jobs, p2_fast8_kernel and p2_gen8_kernel (psi.hip, p1v2.hip) run one structure: eight waves on a 128 x 128
 // workgroup tile, every 64 x 64 quadrant shared by two waves (64 rows x 32 columns: 32 accumulators per wave, four waves per SIMD), KC-deep
 // chunks staged by LDS-DMA into two buffers, operand reads as explicit ds_read_b64 and an lgkmcnt ladder in front of the 32 in-place MFMAs
-// of a k-step.  The k-step and the chunk staging live here, once.  The loops around them stay in the kernels: they differ in what travels
+// of a k-step.  The k-step lives here once; the chunk staging of phase 2 in two forms that must write the same LDS image -- stage8_kf (p2_gen8_kernel,
+// p2_rem_kernel) and stage8_kf_s (p2_fast8_kernel): a change to the K_CONTIG swizzle is a change to both.  The loops around them stay in the kernels: they differ in what travels
 // during the last chunk, and hipcc's schedule of the surrounding scalar code follows the order of the source statements, so every piece
 // below was introduced only where the kernel's assembly stayed the same, instruction for instruction (profiles/kloop8_asm_identity.txt).
 // p1_kernel8 takes the k-step only: with Wave8 or stage8_ff its assembly changes.
@@ -297,6 +298,48 @@ __device__ __forceinline__ void stage8_kf(double* buf, const double* a, const do
     glds16(reinterpret_cast<const double*>(reinterpret_cast<const char*>(a) + (unsigned)(8 * (row * (int)lda + 2 * ((ld_ & 7) ^ (row & 7))))),
            buf + I * 8 * KC);
     glds16(b + (long)I * ldb + 2u * ld_, buf + TILE_LDS_DOUBLES + I * LDS_RC);
+  }
+}
+// ---- the same chunk with the lane patterns held and the advance in scalar registers ------------------------------------------------
+// stage8_kf's lane patterns never change during a launch, only a wave-uniform base moves from chunk to chunk; stage8_kf nevertheless
+// rebuilds them in VALU code for every chunk, between the MFMAs (27 VALU instructions per chunk and wave in p2_fast8_kernel<3>, three of
+// them 64-bit adds: profiles/stage8_buffer_dma.txt).  Here every LDS-DMA is  wave-uniform 64-bit base (SGPR pair) + 32-bit lane offset:
+//   A's lane offset (kf8_lane) is computed once per row tile from an opaque copy of the lane id and held across the tile's k-loop,
+//   the wave's rows and the chunk advance go into the scalar base (s_add_u32 / s_addc_u32), so nothing is limited to 32 bits but the
+//   lane offset itself: at most 8 * (14 lda + 16) bytes for A, 1008 for B (STAGE8_MAX_LDA; the launch function checks it and reports).
+// The LDS image, the bytes moved and the order of the instructions are stage8_kf's.
+// (The buffer form, buffer_load_dwordx4 ... offen lds with the tile's window as descriptor, was built first and is the same instruction
+// count per chunk, but its two descriptors are eight more SGPRs held across the k-loop of a kernel that already uses 104: seven SGPR
+// spills and 8 B of scratch in p2_fast8_kernel<2> and <3>.  See profiles/stage8_buffer_dma.txt.)
+constexpr long STAGE8_MAX_LDA = 1L << 24;            // doubles: 8 * (14 lda + 16) < 2^31
+// An asm statement, because hipcc, given base + zero-extended offset in C++, widens the held offsets to 64-bit pairs and adds the base with
+// v_lshl_add_u64 per instruction (six VGPRs held, scratch spills).  M0 is compiler-reserved: saved and restored inside the statement.  hipcc
+// does not count the load: every consumer waits by dma_wait() / an explicit vmcnt as before, and its own vmcnt waits only become stricter.
+// (Fragile where an explicit vmcnt(n > 0) follows: a compiler-tracked global load placed between such a DMA and that wait is counted by the
+// hardware and not by the n in the source.)  sbase and lds_wave_base go to "s" operands: both must be wave-uniform.
+__device__ __forceinline__ void glds16_sv(const double* sbase, unsigned voffset, double* lds_wave_base) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voffset), "s"(sbase), "s"(lds_byte_addr(lds_wave_base)) : "memory");
+}
+// Lane patterns of stage8_kf as byte offsets.  Instruction i of wave w moves slots (2 w + i) * 8 + (lane >> 3), i.e. rows
+//   swap03(slot) = 16 w + r_l + i,   r_l = ((lane >> 3) & 6) | ((lane >> 3) & 1) << 3    (even, lane-only)
+// and 16-byte pair (lane & 7) ^ (row & 7) of them.  With x = (lane & 7) ^ (r_l & 7):  i = 0 reads pair x, i = 1 pair x ^ 1, so
+//   va = 8 r_l lda + 16 x   and the second instruction's offset is va ^ 16  (8 r_l lda is a multiple of 32: r_l and lda are even);
+// the rows 16 w + i go into the scalar base.  B: row 2 w + i in the scalar base, lane offset 16 lane.
+__device__ __forceinline__ unsigned kf8_lane(int lane, long lda) {
+  const int g = lane >> 3, rl = (g & 6) | ((g & 1) << 3);
+  return 8u * ((unsigned)rl * (unsigned)lda) + 16u * (unsigned)((lane & 7) ^ (rl & 7));
+}
+// a / b: the chunk's first element of the WAVE's first row: row 16 wave of the A row tile / k row 2 wave of the B column tile
+__device__ __forceinline__ void stage8_kf_s(double* buf, const double* a, const double* b, long lda, int ldb, int wave, unsigned va_, int lane) {
+  unsigned va = va_, vb = (unsigned)lane;
+  asm volatile("" : "+v"(va), "+v"(vb));            // va ^ 16 and 16 lane are one VALU instruction each per chunk, not two more held registers
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int I = wave * 2 + i;
+    glds16_sv(a + (long)i * lda, va ^ (16u * i), buf + I * 8 * KC);
+    glds16_sv(b + (long)i * ldb, 16u * vb, buf + TILE_LDS_DOUBLES + I * LDS_RC);
   }
 }
 // (Staging the B tile for every second chunk only -- 25 % fewer LDS-DMA instructions per flop, what a 256 x 128 workgroup tile would issue -- and

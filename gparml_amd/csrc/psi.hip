@@ -463,9 +463,16 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
         }
       }
     }
+    // staging (mma_f64.h, stage8_kf_s): the lane offsets come from an opaque copy of the lane id once per tile and are held across its k-loop
+    // only (as loop invariants of the tile loop they would be held across the epilogue too); every chunk advance is scalar
+    int ls_ = lane;
+    asm volatile("" : "+v"(ls_));
+    const unsigned sv = kf8_lane(ls_, p.ld);
+    const double* Aw = Ab + (long)(16 * wave) * p.ld;
+    const double* Bw = Bb + (long)(2 * wave) * p.Mp;
     int kc = 0;
     const int b0 = (nc + 1) & 1;                                // buffer of chunk 0; chunk c uses (c + nc + 1) & 1, the last one buf0
-    stage8_kf(lds + b0 * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, lane);
+    stage8_kf_s(lds + b0 * 4608, Aw + (long)kc * KC, Bw + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, sv, lane);
     dma_wait();
     __syncthreads();
     for (int c = 0; c < nc; ++c) {
@@ -476,7 +483,7 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
       auto issue_next = [&]() {
         if (c + 1 < nc) {
           ++kc;
-          stage8_kf(lds + (cur ^ 1) * 4608, Ab + (long)kc * KC, Bb + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, lane);
+          stage8_kf_s(lds + (cur ^ 1) * 4608, Aw + (long)kc * KC, Bw + (long)kc * KC * p.Mp, p.ld, p.Mp, wave, sv, lane);
         } else {
           // last chunk (computing from buf0): slab 0 of this wave and the tile's Xa rows into buf1 + extra
           const Epi e0 = epi();
@@ -512,6 +519,7 @@ __global__ void __launch_bounds__(512, 4) p2_fast8_kernel(P2Args p) {
 #pragma unroll
     for (int ar = 0; ar < 4; ++ar) {
       double* slab = (ar & 1) ? setB : setA;
+      // (the 4 counts LDS-DMAs only: no global load or store, hipcc-tracked or asm, may be added between the k-loop's last dma_wait and here)
       if (ar < 3) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // slab ar has landed; slab ar + 1 (4 DMAs) may still fly
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       double hs = 0.0;
@@ -1019,6 +1027,10 @@ int run_phase2(gp_ctx* c) {
 #endif
   if (fast) {                                        // nrb <= 3
     p.gapart = c->p2.hgpart;
+    // p2_fast8_kernel's staging holds a 32-bit lane offset of up to 8 * (14 ld + 16) bytes and takes the second instruction's offset by an XOR that
+    // needs an even ld (mma_f64.h, stage8_kf_s).  LDK = Mp + Dp is a multiple of 128 and far below the bound; no fall-back to p2_gen8_kernel: its
+    // stage8_kf forms 8 * row * (int)ld in 32 bits and overflows earlier (ld >= 2^22), so there is no kernel to fall back to
+    if (p.ld >= STAGE8_MAX_LDA || (p.ld & 1)) return fail(c, GP_ERR_UNSUPPORTED, "fast phase-2 kernel: row stride %ld is odd or exceeds the 32-bit lane offsets", p.ld);
     // (blocks past the last slice zero their own rows of hgpart)
     GP_TRY_RC((for_width<1, 2, 3>(c, "fast phase-2 kernel (groups of four feature columns)", nrb,
                                   [&](auto W) -> int { GP_LAUNCH(c, c->stream, (p2_fast8_kernel<W()>), dim3(blocks), dim3(512), 0, p); return GP_OK; })));
