@@ -923,30 +923,39 @@ extern "C" int gp_project_rows(gp_ctx* c, int64_t n, const double* Y, const doub
 }
 
 // Per new row the nearest training row (csrc/nearest.hip).  Nothing of the evaluation is read or written: only the Y columns of Kaug and the resident
-// X_mu (Y_train == NULL) and the plan's buffers.
-extern "C" int gp_nearest_rows(gp_ctx* c, int64_t n_train, const double* Y_train, int64_t n, const double* Y_test, const int32_t* cols, int n_cols,
-                               double* dist2, int64_t* index, double* x_near) {
+// X_mu (Y_train == NULL) and the plan's buffers.  One body for both entries (fn names the entry in the messages): masked = every new row has its
+// own observed set (observed (n,D), nonzero = observed), else the one column list cols for all of them.
+static int nearest_entry(gp_ctx* c, const char* fn, int64_t n_train, const double* Y_train, int64_t n, const double* Y_test, const int32_t* cols,
+                         int n_cols, bool masked, const uint8_t* observed, double* dist2, int64_t* index, double* x_near) {
   if (!c) return GP_ERR_BAD_ARG;
-  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n must be >= 0");
-  if (cols && n_cols < 1) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n_cols must be >= 1 with a column list (got %d)", n_cols);
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", fn);
+  if (cols && n_cols < 1) return fail(c, GP_ERR_BAD_ARG, "%s: n_cols must be >= 1 with a column list (got %d)", fn, n_cols);
   for (int j = 0; cols && j < n_cols; ++j)
-    if (cols[j] < 0 || cols[j] >= c->D) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: cols[%d] = %d is outside 0 .. D - 1 = %d", j, cols[j], c->D - 1);
-  if (Y_train && x_near) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: x_near is the base mean of a resident row: it cannot be asked for with host rows (Y_train)");
+    if (cols[j] < 0 || cols[j] >= c->D) return fail(c, GP_ERR_BAD_ARG, "%s: cols[%d] = %d is outside 0 .. D - 1 = %d", fn, j, cols[j], c->D - 1);
+  if (Y_train && x_near) return fail(c, GP_ERR_BAD_ARG, "%s: x_near is the base mean of a resident row: it cannot be asked for with host rows (Y_train)", fn);
   if (!Y_train) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_nearest_rows: Y_train is NULL (the resident rows) before gp_upload_shard");
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: Y_train is NULL (the resident rows) before gp_upload_shard", fn);
     n_train = c->N;
   } else if (n_train < 0) {
-    return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: n_train must be >= 0");
+    return fail(c, GP_ERR_BAD_ARG, "%s: n_train must be >= 0", fn);
   }
   if (n == 0) return GP_OK;
-  if (!Y_test) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_test is NULL");
+  if (!Y_test) return fail(c, GP_ERR_BAD_ARG, "%s: Y_test is NULL", fn);
+  if (masked && !observed) return fail(c, GP_ERR_BAD_ARG, "%s: observed is NULL", fn);
   const int nc = cols ? n_cols : c->D;
   for (int64_t i = 0; i < n; ++i) {
     bool ok = true;
-    for (int j = 0; j < nc; ++j) ok = ok && std::isfinite(Y_test[i * c->D + (cols ? cols[j] : j)]);
-    if (!ok) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_test is not finite in an observed column");
+    int seen = 0;
+    for (int j = 0; j < nc; ++j) {
+      const int64_t e = i * c->D + (cols ? cols[j] : j);
+      if (masked && !observed[e]) continue;               // an unobserved element is never read: it may be NaN
+      ++seen;
+      ok = ok && std::isfinite(Y_test[e]);
+    }
+    if (!seen) return fail(c, GP_ERR_BAD_ARG, "%s: row %lld of Y_test has no observed column", fn, (long long)i);
+    if (!ok) return fail(c, GP_ERR_BAD_ARG, "%s: Y_test is not finite in an observed column", fn);
   }
-  if (Y_train && !all_finite(Y_train, (size_t)n_train * c->D)) return fail(c, GP_ERR_BAD_ARG, "gp_nearest_rows: Y_train is not finite");
+  if (Y_train && !all_finite(Y_train, (size_t)n_train * c->D)) return fail(c, GP_ERR_BAD_ARG, "%s: Y_train is not finite", fn);
   if (!dist2 && !index && !x_near) return GP_OK;
   if (n_train == 0) {
     if (dist2) std::fill(dist2, dist2 + n, std::numeric_limits<double>::infinity());
@@ -954,7 +963,17 @@ extern "C" int gp_nearest_rows(gp_ctx* c, int64_t n_train, const double* Y_train
     return GP_OK;
   }
   GP_HIP(c, hipSetDevice(c->device));
-  return run_nearest(c, (long)n_train, Y_train, (long)n, Y_test, cols, n_cols, dist2, index, x_near);
+  return run_nearest(c, (long)n_train, Y_train, (long)n, Y_test, cols, n_cols, masked ? observed : nullptr, dist2, index, x_near);
+}
+
+extern "C" int gp_nearest_rows(gp_ctx* c, int64_t n_train, const double* Y_train, int64_t n, const double* Y_test, const int32_t* cols, int n_cols,
+                               double* dist2, int64_t* index, double* x_near) {
+  return nearest_entry(c, "gp_nearest_rows", n_train, Y_train, n, Y_test, cols, n_cols, false, nullptr, dist2, index, x_near);
+}
+
+extern "C" int gp_nearest_rows_masked(gp_ctx* c, int64_t n_train, const double* Y_train, int64_t n, const double* Y_test, const uint8_t* observed,
+                                      double* dist2, int64_t* index, double* x_near) {
+  return nearest_entry(c, "gp_nearest_rows_masked", n_train, Y_train, n, Y_test, nullptr, 0, true, observed, dist2, index, x_near);
 }
 
 // ---- final gradients ---------------------------------------------------------------------------------------------

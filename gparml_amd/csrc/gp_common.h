@@ -356,8 +356,8 @@ int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres,
 int run_scatter(gp_ctx* c, long n, const double* Y, const double* centre, double* sum, double* gram);
 int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const double* P, int Q, double* X);
 // nearest.hip
-int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, double* dist2,
-                int64_t* index, double* x_near);
+int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, const uint8_t* observed,
+                double* dist2, int64_t* index, double* x_near);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip

@@ -13,6 +13,8 @@
 //     only when strictly nearer.  Across the lanes of a wave and the waves of the workgroup the pairs (distance, row) are compared: an equally
 //     near row replaces the best only when its index is lower -- a lane's best need not lie below its neighbour's.  Out: one partial per
 //     (slice, new row).  The padded rows [N, Np) of Kaug are never read, nor any column outside cols (the Psi1 columns among them).
+//     nn_search_kernel<true> (gp_nearest_rows_masked) is the same kernel for new rows that each observe their own columns: two wave-uniform
+//     values per (column, new row) instead of one, the same two operations per term, the same bits over the observed columns of a row.
 //   nn_reduce_kernel: folds the slices in ascending order onto the running best of the call (set by the first chunk of training rows): strictly
 //     nearer only, so the lowest row wins across workgroups and chunks too.  No atomics anywhere; the result does not depend on the slicing.
 //   nn_gather_kernel: the base means Xmu[row] of the winners (resident rows only).
@@ -39,6 +41,10 @@ __device__ __forceinline__ void nn_take(double& d, int& i, double od, int oi) {
 
 // T [cnt][ld] (column 0 = the first data column); Yb [gridDim.x][ncp][NN_NY] (zero beyond n_cols and beyond the call's rows); cols [ncp] (zero
 // beyond n_cols); pd, pi [gridDim.y][ry]: per slice and new row the least distance and its row of T (-1, +inf: none)
+// MASKED (gp_nearest_rows_masked: every new row has its own observed set): Yb [gridDim.x][ncp][2][NN_NY], per column the rows' wy = o ? y : 0, then
+// their nw = o ? -1 : -0.0 (both zero beyond n_cols and beyond the call's rows).  The difference is fma(nw, t, wy): y - t rounded once where
+// the row observes the column -- the bits of the other form -- and an exact zero where it does not (t is finite), which leaves the sum as it is.
+template <bool MASKED>
 __global__ void __launch_bounds__(256) nn_search_kernel(const double* __restrict__ T, long ld, long cnt, int tps, const double* __restrict__ Yb,
                                                         const int* __restrict__ cols, int n_cols, int ncp, long ry, double* __restrict__ pd,
                                                         int* __restrict__ pi) {
@@ -47,7 +53,8 @@ __global__ void __launch_bounds__(256) nn_search_kernel(const double* __restrict
   __shared__ int red_i[4][NN_NY];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sj = tid & (NN_CT - 1), sr = tid >> 4;        // staging: this thread's column of the tile, and its row among 16
-  const double* y = Yb + (long)blockIdx.x * ncp * NN_NY;
+  constexpr int YS = MASKED ? 2 * NN_NY : NN_NY;          // doubles of Yb per column
+  const double* y = Yb + (long)blockIdx.x * ncp * YS;
   const long tiles = (cnt + NN_ROWS - 1) / NN_ROWS;
   const long t0 = (long)blockIdx.y * tps, t1 = min(tiles, t0 + tps);      // t0 < t1: the grid has no empty slice
   const int nct = ncp / NN_CT;
@@ -85,12 +92,17 @@ __global__ void __launch_bounds__(256) nn_search_kernel(const double* __restrict
       const int cn = last_ct ? 0 : ct + 1;
       if (more) fetch(tn, cn);
       const int jn = min(NN_CT, n_cols - ct * NN_CT);
-      const double* yc = y + (long)ct * NN_CT * NN_NY;          // wave-uniform
+      const double* yc = y + (long)ct * NN_CT * YS;             // wave-uniform
 #pragma unroll 2
       for (int jj = 0; jj < jn; ++jj) {
         const double tv = tile[jj * NN_RS + tid];
 #pragma unroll
-        for (int i = 0; i < NN_NY; ++i) { const double d = yc[jj * NN_NY + i] - tv; acc[i] = fma(d, d, acc[i]); }
+        for (int i = 0; i < NN_NY; ++i) {
+          double d;
+          if constexpr (MASKED) d = fma(yc[jj * YS + NN_NY + i], tv, yc[jj * YS + i]);
+          else d = yc[jj * YS + i] - tv;
+          acc[i] = fma(d, d, acc[i]);
+        }
       }
       if (last_ct) {
 #pragma unroll
@@ -152,7 +164,7 @@ std::atomic<int> g_opt_nn_rows{0};
 
 struct NnPlan {
   DevBuf<double> in;          // [rows][D] a chunk of host training rows (not used with the resident Y)
-  DevBuf<double> y;           // [rows / NN_NY][ncp][NN_NY] a chunk of new rows: their observed columns
+  DevBuf<double> y;           // [rows / NN_NY][ncp][NN_NY] a chunk of new rows: their observed columns ([ncp][2][NN_NY] with a mask: wy, nw)
   DevBuf<int> cols;           // [ncp] the observed columns, zero beyond n_cols
   DevBuf<double> pd;          // [slices][rows] per-slice least distances
   DevBuf<int> pi;             // [slices][rows] and their rows
@@ -162,12 +174,26 @@ struct NnPlan {
 };
 void NnPlanDelete::operator()(NnPlan* p) const { delete p; }
 
-int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, double* dist2,
-                int64_t* index, double* x_near) {
-  const int D = c->D, Q = c->Q, nc = cols ? n_cols : D, ncp = (int)round_up(nc, NN_CT);
+// observed (n,D), nonzero = observed, or NULL: the one column list cols (NULL: all D columns) for every new row.  With a mask the columns of the
+// call are those that some row of the call observes, ascending: a column nobody observes costs nothing, and one that only other rows observe adds
+// an exact zero to a row's sum, so a row's result does not depend on the rows it is called with
+int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, const uint8_t* observed,
+                double* dist2, int64_t* index, double* x_near) {
+  const int D = c->D, Q = c->Q;
+  std::vector<int> ocols;
+  if (observed) {
+    std::vector<uint8_t> any((size_t)D, 0);
+    for (long r = 0; r < n; ++r)
+      for (int j = 0; j < D; ++j) any[j] |= observed[r * D + j];
+    for (int j = 0; j < D; ++j)
+      if (any[j]) ocols.push_back(j);
+    cols = ocols.data();
+    n_cols = (int)ocols.size();
+  }
+  const int nc = cols ? n_cols : D, ncp = (int)round_up(nc, NN_CT), ys = observed ? 2 : 1;       // ys: values per (column, new row)
   const int opt = g_opt_nn_rows.load();
   // a chunk of new rows [rows][ncp] and a chunk of host training rows [rows][D] stay near 64 MB each
-  const long RY = std::min(round_up(n, NN_NY), opt > 0 ? round_up(opt, NN_NY) : std::max<long>(NN_NY, std::min<long>(1L << 16, (64L << 20) / (8L * ncp)) / NN_NY * NN_NY));
+  const long RY = std::min(round_up(n, NN_NY), opt > 0 ? round_up(opt, NN_NY) : std::max<long>(NN_NY, std::min<long>(1L << 16, (64L << 20) / (8L * ncp * ys)) / NN_NY * NN_NY));
   const long RT = !Y_train ? n_train
                            : std::min(round_up(n_train, NN_ROWS),
                                       opt > 0 ? round_up(opt, NN_ROWS) : std::max<long>(NN_ROWS, std::min<long>(1L << 20, (64L << 20) / (8L * D)) / NN_ROWS * NN_ROWS));
@@ -177,7 +203,7 @@ int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const do
   if (!c->nn) c->nn.reset(new NnPlan());
   NnPlan& p = *c->nn;
   if (Y_train) GP_TRY_RC(p.in.grow(c, (size_t)(RT * D), DA_RAW));
-  GP_TRY_RC(p.y.grow(c, (size_t)(RY * ncp), DA_RAW));
+  GP_TRY_RC(p.y.grow(c, (size_t)(RY * ncp * ys), DA_RAW));
   GP_TRY_RC(p.cols.grow(c, (size_t)ncp, DA_RAW));
   GP_TRY_RC(p.pd.grow(c, part, DA_RAW));
   GP_TRY_RC(p.pi.grow(c, part, DA_RAW));
@@ -188,18 +214,28 @@ int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const do
   std::vector<int> hcols((size_t)ncp, 0);
   for (int j = 0; j < nc; ++j) hcols[j] = cols ? cols[j] : j;
   GP_HIP(c, hipMemcpyAsync(p.cols, hcols.data(), hcols.size() * 4, hipMemcpyHostToDevice, st));
-  std::vector<double> hy((size_t)(RY * ncp));
+  std::vector<double> hy((size_t)(RY * ncp * ys));
   static_assert(sizeof(long long) == sizeof(int64_t), "the rows are copied out as they are");
   for (long n0 = 0; n0 < n; n0 += RY) {
     const long cnt = std::min(RY, n - n0), ry = round_up(cnt, NN_NY), yb = ry / NN_NY;
-    // the chunk's observed columns, [block][column][row of the block]: columns outside cols are never read, on the host or on the device
-    std::fill(hy.begin(), hy.begin() + (size_t)(ry * ncp), 0.0);
+    // the chunk's observed columns, [block][column][row of the block]: columns outside cols are never read, on the host or on the device; with a
+    // mask [block][column][wy | nw][row of the block], and an entry that its row does not observe is not read either
+    std::fill(hy.begin(), hy.begin() + (size_t)(ry * ncp * ys), 0.0);
     for (long r = 0; r < cnt; ++r) {
       const double* src = Y_test + (n0 + r) * D;
-      double* dst = hy.data() + (size_t)(r / NN_NY) * ncp * NN_NY + r % NN_NY;
-      for (int j = 0; j < nc; ++j) dst[(size_t)j * NN_NY] = src[hcols[j]];
+      double* dst = hy.data() + (size_t)(r / NN_NY) * ncp * NN_NY * ys + r % NN_NY;
+      if (observed) {
+        const uint8_t* o = observed + (n0 + r) * D;
+        for (int j = 0; j < nc; ++j) {
+          const bool on = o[hcols[j]] != 0;
+          dst[(size_t)j * 2 * NN_NY] = on ? src[hcols[j]] : 0.0;
+          dst[(size_t)j * 2 * NN_NY + NN_NY] = on ? -1.0 : -0.0;
+        }
+      } else {
+        for (int j = 0; j < nc; ++j) dst[(size_t)j * NN_NY] = src[hcols[j]];
+      }
     }
-    GP_HIP(c, hipMemcpyAsync(p.y, hy.data(), (size_t)(ry * ncp) * 8, hipMemcpyHostToDevice, st));
+    GP_HIP(c, hipMemcpyAsync(p.y, hy.data(), (size_t)(ry * ncp * ys) * 8, hipMemcpyHostToDevice, st));
     for (long m0 = 0; m0 < n_train; m0 += RT) {
       const long rows = std::min(RT, n_train - m0);
       const double* t = c->Kaug + c->Mp;
@@ -212,7 +248,10 @@ int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const do
       const long tiles = (rows + NN_ROWS - 1) / NN_ROWS;
       const long want = std::min(tiles, std::max<long>(1, (NN_BLOCKS + yb - 1) / yb));
       const int tps = (int)((tiles + want - 1) / want), slices = (int)((tiles + tps - 1) / tps);      // no empty slice
-      GP_LAUNCH(c, st, nn_search_kernel, dim3((unsigned)yb, (unsigned)slices), dim3(256), 0, t, ld, rows, tps, p.y, p.cols, nc, ncp, ry, p.pd, p.pi);
+      if (observed)
+        GP_LAUNCH(c, st, nn_search_kernel<true>, dim3((unsigned)yb, (unsigned)slices), dim3(256), 0, t, ld, rows, tps, p.y, p.cols, nc, ncp, ry, p.pd, p.pi);
+      else
+        GP_LAUNCH(c, st, nn_search_kernel<false>, dim3((unsigned)yb, (unsigned)slices), dim3(256), 0, t, ld, rows, tps, p.y, p.cols, nc, ncp, ry, p.pd, p.pi);
       GP_LAUNCH(c, st, nn_reduce_kernel, dim3((unsigned)((ry + 255) / 256)), dim3(256), 0, p.pd, p.pi, slices, ry, (long long)m0, m0 == 0 ? 1 : 0,
                 p.bd, p.bi);
     }

@@ -467,9 +467,11 @@ class ShardEngine(object):
         return X
 
     # ---- the start of latent inference (gp_nearest_rows) ----------------------------------------------------
-    def nearest_rows(self, Y_test, cols=None, Y_train=None, want_x=True):
+    def nearest_rows(self, Y_test, cols=None, Y_train=None, want_x=True, observed=None):
         """Per row of ``Y_test`` (n, D) the nearest training row in squared Euclidean distance over the output columns ``cols`` (None: all; the
-        other columns may hold NaN), among the resident rows of this engine (``Y_train`` None) or the host rows ``Y_train`` (n_train, D).  Returns
+        other columns may hold NaN) -- or, with ``observed`` (n, D) bool instead of ``cols``, over every row's own observed columns
+        (gp_nearest_rows_masked: an unobserved entry may hold NaN; every row observes something) -- among the resident rows of this engine
+        (``Y_train`` None) or the host rows ``Y_train`` (n_train, D).  Returns
         (dist2 (n,), index (n,) int64, x_near): of equally near rows the lowest index; x_near (n, Q) is the base mean X_mu[index] of the winner,
         None with host rows or ``want_x`` False.  Without training rows every index is -1 and every dist2 inf.  Shards combine by the minimum
         (gparml_amd.init.nearest_start).  The evaluation state is left untouched."""
@@ -477,7 +479,11 @@ class ShardEngine(object):
         assert Y_test.ndim == 2 and Y_test.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y_test.shape, self.D)
         n = Y_test.shape[0]
         Y_test, py = _lib.as_c(Y_test)
+        assert cols is None or observed is None, 'nearest_rows: cols and observed are alternatives'
         pc, nc = None, 0
+        if observed is not None:
+            observed = np.ascontiguousarray(np.atleast_2d(np.asarray(observed)) != 0, dtype=np.uint8)
+            assert observed.shape == Y_test.shape, 'observed shape %s: %s expected' % (observed.shape, Y_test.shape)
         if cols is not None:
             cols = np.ascontiguousarray(np.asarray(cols).reshape(-1), dtype=np.int32)
             pc, nc = cols.ctypes.data_as(_lib._ip), int(cols.size)
@@ -491,9 +497,11 @@ class ShardEngine(object):
             Y_train, pt = _lib.as_c(Y_train)
         dist2, index = np.empty(n), np.empty(n, dtype=np.int64)
         x = np.empty((n, self.Q)) if (want_x and Y_train is None) else None
-        self._ck(self.lib.gp_nearest_rows(self.h, n_train, pt, n, py, pc, nc, dist2.ctypes.data_as(_lib._dp),
-                                          index.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), x.ctypes.data_as(_lib._dp) if x is not None else None),
-                 'gp_nearest_rows')
+        out = (dist2.ctypes.data_as(_lib._dp), index.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), x.ctypes.data_as(_lib._dp) if x is not None else None)
+        if observed is not None:
+            self._ck(self.lib.gp_nearest_rows_masked(self.h, n_train, pt, n, py, observed.ctypes.data_as(_lib._u8p), *out), 'gp_nearest_rows_masked')
+        else:
+            self._ck(self.lib.gp_nearest_rows(self.h, n_train, pt, n, py, pc, nc, *out), 'gp_nearest_rows')
         return dist2, index, x
 
     @property

@@ -210,11 +210,13 @@ def pca(parts, Q, allreduce=None):
 
 
 # ------------------------------------------------------------------------------------------------- nearest start
-def nearest_start(parts, Y_test, cols=None, cutoff=6.0, allreduce=None, rank=0, world=1):
+def nearest_start(parts, Y_test, cols=None, cutoff=6.0, allreduce=None, rank=0, world=1, observed=None):
     """The starting means of latent inference: every row of ``Y_test`` (n, D) gets the embedding of the training row nearest to it over the
     output columns ``cols`` (None: all), as ``Predictor.nearest_training_embeddings`` (predict.py:44-66) does with a k-d tree per shard.
     Returns (X_mu0 (n, Q), dist (n,), owner (n,), index (n,)): the means, the Euclidean distance to the nearest training row (inf without one),
     the part that holds it (counted over all ranks in the order rank, part) and its row there; owner and index are -1 where the mean stayed zero.
+    ``observed`` (n, D) bool instead of ``cols``: every row is compared over its own observed columns, in one masked search per part
+    (``ShardEngine.nearest_rows(observed=)``); the part, rank and cut-off rules are the same.
 
     parts: an iterable (taken one at a time: a generator keeps one shard in memory) of engines whose resident rows and base means are searched
     (``ShardEngine.nearest_rows``), or of (engine, Y_shard, X_shard) for host rows passed through the engine.
@@ -227,18 +229,20 @@ def nearest_start(parts, Y_test, cols=None, cutoff=6.0, allreduce=None, rank=0, 
     own: a sum that gathers), then the winners' rows -- and every rank returns the same arrays."""
     Y_test = numpy.atleast_2d(numpy.asarray(Y_test, dtype=numpy.float64))
     n = Y_test.shape[0]
+    assert cols is None or observed is None, 'nearest_start: cols and observed are alternatives'
+    which = dict(cols=cols) if observed is None else dict(observed=observed)
     best = numpy.full(n, numpy.inf)
     owner, index = numpy.full(n, -1, dtype=numpy.int64), numpy.full(n, -1, dtype=numpy.int64)
     X, n_parts = None, 0
     for k, part in enumerate(parts):
         if isinstance(part, (tuple, list)):
             engine, Ys, Xs = part
-            d2, idx, _ = engine.nearest_rows(Y_test, cols=cols, Y_train=Ys, want_x=False)
+            d2, idx, _ = engine.nearest_rows(Y_test, Y_train=Ys, want_x=False, **which)
             Xs = numpy.asarray(Xs, dtype=numpy.float64)
             x = numpy.zeros((n, Xs.shape[1]))
             x[idx >= 0] = Xs[idx[idx >= 0]]
         else:
-            d2, idx, x = part.nearest_rows(Y_test, cols=cols)
+            d2, idx, x = part.nearest_rows(Y_test, **which)
         if X is None:
             X = numpy.zeros((n, x.shape[1]))
         closer = (d2 < best) & (idx >= 0)                     # strict: an equally near row of a later part does not win

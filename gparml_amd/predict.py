@@ -117,9 +117,11 @@ class Predictor(object):
 
         ``ragged=True``: the observed set of a row is the same, but ALL rows and all their restarts go to ONE ``infer_latent_rows`` call, whatever
         the number of patterns (rows with holes in random places have a pattern each); restarts stay rows of that call and the best L per row is
-        kept, the earliest on ties.  The starts work as above; ``training=...`` still searches once per pattern (a masked nearest-row search is
-        not part of this).  ``start='inducing'`` (``ragged=True`` only) needs no training rows: every row starts at the inducing point whose
-        predicted outputs are nearest to the row over its observed columns (``inducing_start``)."""
+        kept, the earliest on ties.  The starts work as above.  With ``training=...`` and ``nearest='device'`` ONE masked search per training
+        shard serves all rows, each compared over its own observed columns (``init.nearest_start(observed=)``, gp_nearest_rows_masked); with
+        ``nearest='host'`` the k-d trees are still built once per pattern.  ``start='inducing'`` (``ragged=True`` only) needs no training rows:
+        every row starts at the inducing point whose predicted outputs are nearest to the row over its observed columns -- ``inducing_start`` on
+        the host, or with ``nearest='device'`` the same choice by one masked search over the M predicted rows (no cut-off applies)."""
         Y = numpy.atleast_2d(numpy.asarray(Y_test, dtype=float))
         n, Q = Y.shape[0], self.Q
         assert Y.shape[1] == self.D, 'Y_test shape %s: (n, %d) expected' % (Y.shape, self.D)
@@ -182,14 +184,19 @@ class Predictor(object):
         obs[:, cols] = observed
         if starts is None and training is None:                                         # start='inducing'
             Z = numpy.asarray(self.gs['Z'], dtype=float)
-            starts = self.inducing_start(Y, obs, Z, eng.predict(Z)[0])[:, None, :]
+            Mz = eng.predict(Z)[0]
+            if nearest == 'device':                                                     # inducing_start's choice by one masked search over the M rows of Mz
+                starts = Z[eng.nearest_rows(Y, observed=obs, Y_train=Mz, want_x=False)[1]][:, None, :]
+            else:
+                starts = self.inducing_start(Y, obs, Z, Mz)[:, None, :]
+        elif starts is None and nearest == 'device':                                    # the nearest training output: one masked search per shard
+            starts = self._nearest_on_device(eng, Y, training, observed=obs)[:, None, :]
         elif starts is None:                                                            # the nearest training output, searched per pattern
             starts = numpy.empty((n, 1, Q))
             for key in sorted(groups, key=lambda k: groups[k][0]):
                 rows = numpy.asarray(groups[key])
                 c = cols[observed[rows[0]]]
-                find = self._nearest_on_device if nearest == 'device' else None
-                starts[rows, 0] = find(eng, Y[rows], training, c) if find else self.nearest_training_embeddings(Y[rows], training, Q, c)
+                starts[rows, 0] = self.nearest_training_embeddings(Y[rows], training, Q, c)
         k = starts.shape[1]
         m, v, l, _ = eng.infer_latent_rows(numpy.repeat(Y, k, axis=0), starts.reshape(-1, Q), numpy.repeat(X_S0, k, axis=0),
                                            observed=numpy.repeat(obs, k, axis=0), max_iters=iterations, gtol=gtol)
@@ -278,11 +285,12 @@ class Predictor(object):
         return X_mu
 
     @staticmethod
-    def _nearest_on_device(engine, Y_test, training, mask=None):
+    def _nearest_on_device(engine, Y_test, training, mask=None, observed=None):
         """``nearest_training_embeddings`` with the search on the device: every (Y_shard, X_shard) of ``training`` passes through ``engine`` as
-        host rows (init.nearest_start), one shard in memory at a time; the same tie rule and cut-off."""
+        host rows (init.nearest_start), one shard in memory at a time; the same tie rule and cut-off.  ``observed`` (n, D) bool instead of
+        ``mask``: every row over its own observed columns, still one search per shard."""
         from . import init
-        return init.nearest_start(((engine, Ys, Xs) for Ys, Xs in training), Y_test, cols=None if mask is None else list(mask))[0]
+        return init.nearest_start(((engine, Ys, Xs) for Ys, Xs in training), Y_test, cols=None if mask is None else list(mask), observed=observed)[0]
 
     def _optimise(self, X_mu0, X_S0, iterations):
         x0 = numpy.concatenate((X_mu0.flatten(), X_S0.flatten()))

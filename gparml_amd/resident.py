@@ -77,16 +77,17 @@ class ResidentModel(object):
     _stats_x = None
     _stats_version = -1
 
-    def infer_start(self, Y, cols=None, cutoff=6.0):
+    def infer_start(self, Y, cols=None, cutoff=6.0, observed=None):
         """Starting means (n, Q) for the latent inference of the NEW rows Y: the resident base mean of the training row nearest to each over the
         output columns ``cols`` (None: all), zero for a row farther than ``cutoff`` from every training row -- predict.py:44-66 over the resident
-        rows of every shard of every rank (gparml_amd.init.nearest_start on the engines: nothing is uploaded but Y).  COLLECTIVE across ranks,
+        rows of every shard of every rank (gparml_amd.init.nearest_start on the engines: nothing is uploaded but Y).  ``observed`` (n, D) bool
+        instead of ``cols``: every row is compared over its own observed columns (the start of ``infer_latent_rows``).  COLLECTIVE across ranks,
         with this model's group: every rank gets the same means."""
         from . import init
         kw = {}
         if self._dist is not None:
             kw = dict(allreduce=self._allreduce_vector, rank=self._dist.get_rank(self.group), world=self._dist.get_world_size(self.group))
-        return init.nearest_start(self.engines, Y, cols=cols, cutoff=cutoff, **kw)[0]
+        return init.nearest_start(self.engines, Y, cols=cols, cutoff=cutoff, observed=observed, **kw)[0]
 
     def infer(self, flat_array, Y, X_mu, X_S, cols=None, max_iters=100, gtol=1e-5):
         """Latent distributions of NEW rows Y for the model at ``flat_array`` (ShardEngine.infer_latent on the root engine: per-row SCG on the device

@@ -319,6 +319,19 @@ int gp_project_rows(gp_ctx* ctx, int64_t n, const double* Y, const double* mean,
 int gp_nearest_rows(gp_ctx* ctx, int64_t n_train, const double* Y_train,   /* NULL: the resident rows, n_train ignored */
                     int64_t n, const double* Y_test, const int32_t* cols, int n_cols, /* cols NULL: all D columns */
                     double* dist2, int64_t* index, double* x_near);        /* (n,), (n,), (n,Q) or NULL; x_near needs resident rows */
+/* gp_nearest_rows for new rows that each observe their own columns (rows with holes in different places: the start of one gp_infer_latent_rows
+ * call).  observed (n,D), nonzero = observed: the squared distance of new row i to a training row is sum over the observed d of row i, d ascending,
+ * of (y[i][d] - t[d])^2, in the same direct form with one fused multiply-add per term; an unobserved element of Y_test may hold NaN and is never
+ * read, on the host or on the device.  Everything else is gp_nearest_rows' contract: Y_train == NULL: the resident rows (n_train ignored;
+ * GP_ERR_STATE before an upload), whose padding never contributes or wins; otherwise host rows (n_train,D) taken in chunks; any output may be
+ * NULL; x_near resident rows only; no training rows: every index -1 and every dist2 +inf; of equally near rows the lowest index at every level, no
+ * atomics.  Determinism: a new row's result depends on that row, its mask and the training rows only -- it is bit-identical alone, in any batch,
+ * in any chunking of either side and between host rows and resident rows; rows that share one pattern get the bits of gp_nearest_rows with cols =
+ * that pattern.  Synchronous.  Leaves the evaluation state untouched.  GP_ERR_BAD_ARG as gp_nearest_rows (less the column list), and for a NULL
+ * observed with n > 0, a row with no observed column and a non-finite observed element of Y_test; n = 0 writes nothing. */
+int gp_nearest_rows_masked(gp_ctx* ctx, int64_t n_train, const double* Y_train,   /* NULL: the resident rows, n_train ignored */
+                           int64_t n, const double* Y_test, const uint8_t* observed,   /* (n,D), nonzero = observed */
+                           double* dist2, int64_t* index, double* x_near);
 
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
@@ -387,7 +400,7 @@ int gp_debug_force_staging(int on);
  * step of E with a double-double residual.  bench.py times the global step with and without to print their cost.
  * "poison_alloc" (also GPARML_POISON=1 at load time): every allocation without a documented zero contract is filled with NaN bytes and
  * gp_set_globals refills the per-evaluation buffers with them -- a kernel that reads what this evaluation did not write fails
- * deterministically (tests/test_gpu_poison.py).  "nearest_rows", k: gp_nearest_rows takes its new rows k at a time (rounded up to 16) and host
+ * deterministically (tests/test_gpu_poison.py).  "nearest_rows", k: gp_nearest_rows and gp_nearest_rows_masked take their new rows k at a time (rounded up to 16) and host
  * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults.  "infer_patterns", k: a chunk of
  * gp_infer_objective_rows / gp_infer_latent_rows holds at most k distinct patterns (P_cap = k); 0 restores the default. */
 int gp_debug_set_option(const char* name, int value);

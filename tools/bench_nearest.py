@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the start of latent inference (gp_nearest_rows, gparml_amd.init.nearest_start) and print one JSON line.
+"""Time the start of latent inference (gp_nearest_rows, gp_nearest_rows_masked, gparml_amd.init.nearest_start) and print one JSON line.
 
 N = 1e6 resident training rows, D = 100, n = 1e4 new rows, normal data (the per-GPU shard of the benchmark; predict.py:44-66 searches it with a
 k-d tree per shard on the host):
@@ -13,6 +13,18 @@ k-d tree per shard on the host):
                                          training rows for the first --host-n new rows (building the tree included, as the reference pays it per call)
   host_kdtree_s_extrapolated_n           (time per new row) x n: EXTRAPOLATED to the device's n, not measured
   index_differing_from_host              new rows among the first --host-n whose device start differs from the host's
+  masked_all_ms / masked_pair_unmasked_ms  the masked search (ShardEngine.nearest_rows(observed=), gp_nearest_rows_masked) with every column
+                                         observed, and the unmasked search timed in alternation with it; best of --reps each
+  masked_over_unmasked_all               their ratio; masked_all_identical: the two returned the same bits
+  masked_hide10_ms / terms_per_s_masked_hide10
+                                         the masked search with ten random columns hidden per row (NaN there): n N (D - 10) terms
+  masked_hide10_start_host_rows_s        Predictor.infer's ragged device start on those rows: one masked init.nearest_start with the training
+                                         rows passed as host rows (their upload included)
+  masked_perpattern_n / masked_perpattern_device_s / masked_perpattern_device_s_per_row
+                                         the per-pattern device start that it replaces, on the first --pattern-n of those rows: every row has a
+                                         pattern of its own, so one init.nearest_start(cols=) with host rows per row
+  masked_perpattern_device_s_extrapolated_n   (time per row) x n: EXTRAPOLATED to n, not measured
+  masked_start_differing_from_perpattern new rows among the first --pattern-n whose masked start differs from the per-pattern one
 No gate: the exit status is 0 whenever the run completes."""
 import argparse
 import json
@@ -38,6 +50,19 @@ def timed(fn, reps):
     return best
 
 
+def timed_pair(fa, fb, reps):
+    """best of ``reps`` of each, the two alternating after a warm-up of both"""
+    fa()
+    fb()
+    best = [float('inf'), float('inf')]
+    for _ in range(reps):
+        for k, fn in enumerate((fa, fb)):
+            t = time.perf_counter()
+            fn()
+            best[k] = min(best[k], time.perf_counter() - t)
+    return best
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=3)
@@ -46,6 +71,7 @@ def main():
     ap.add_argument('--Q', type=int, default=10)
     ap.add_argument('--n', type=int, default=10000)
     ap.add_argument('--host-n', type=int, default=20, help='new rows of the host k-d tree timing (0: skip it)')
+    ap.add_argument('--pattern-n', type=int, default=200, help='new rows of the per-pattern device start timing (0: skip it)')
     args = ap.parse_args()
     from gparml_amd import init
     from gparml_amd.engine import ShardEngine
@@ -66,6 +92,29 @@ def main():
     out['start_resident_ms'] = timed(lambda: init.nearest_start([eng], Ys), 1) * 1e3
     X_dev, dist, _, _ = init.nearest_start([eng], Ys)
     out['new_rows_within_cutoff'] = int(np.sum(dist < 6.0))
+    # the masked search: all columns observed against the unmasked call, then ten random columns hidden per row
+    ones = np.ones((n, D), dtype=bool)
+    tm, tu = timed_pair(lambda: eng.nearest_rows(Ys, observed=ones), lambda: eng.nearest_rows(Ys), args.reps)
+    out['masked_all_ms'], out['masked_pair_unmasked_ms'], out['masked_over_unmasked_all'] = tm * 1e3, tu * 1e3, tm / tu
+    out['masked_all_identical'] = bool(all(np.array_equal(a, b) for a, b in zip(eng.nearest_rows(Ys, observed=ones), eng.nearest_rows(Ys))))
+    hide = min(10, D - 1)
+    obs = np.ones((n, D), dtype=bool)
+    for i in range(n):
+        obs[i, rs.choice(D, hide, replace=False)] = False
+    Yh = np.where(obs, Ys, np.nan)
+    t = timed(lambda: eng.nearest_rows(Yh, observed=obs), args.reps)
+    out['masked_hide10_ms'], out['terms_per_s_masked_hide10'] = t * 1e3, float(n) * N * (D - hide) / t
+    t = time.perf_counter()
+    X_masked = Predictor._nearest_on_device(eng, Yh, [(Yt, Xt)], observed=obs)
+    out['masked_hide10_start_host_rows_s'] = time.perf_counter() - t
+    if args.pattern_n > 0:
+        pn = min(args.pattern_n, n)
+        t = time.perf_counter()
+        X_pat = np.concatenate([Predictor._nearest_on_device(eng, Yh[i:i + 1], [(Yt, Xt)], np.flatnonzero(obs[i])) for i in range(pn)])
+        out['masked_perpattern_n'], out['masked_perpattern_device_s'] = pn, time.perf_counter() - t
+        out['masked_perpattern_device_s_per_row'] = out['masked_perpattern_device_s'] / pn
+        out['masked_perpattern_device_s_extrapolated_n'] = out['masked_perpattern_device_s_per_row'] * n
+        out['masked_start_differing_from_perpattern'] = int(np.sum(np.any(X_pat != X_masked[:pn], axis=1)))
     eng.close()
     if args.host_n > 0:
         hn = min(args.host_n, n)
