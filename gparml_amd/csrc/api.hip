@@ -757,6 +757,47 @@ extern "C" int gp_predict_grad(gp_ctx* c, int64_t n, const double* X, int flags,
   return run_predict_grad(c, (long)n, X, jac, dvar, metric, logdet);
 }
 
+// ---- pathwise posterior draws (paths.hip) ----
+static bool all_finite(const double* x, size_t n);      // below, with the PCA entries
+
+extern "C" int gp_paths_set(gp_ctx* c, int n_draws, int F, const double* omega, const double* centre, const double* w, const double* eps_u) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n_draws < 1 || F < 1) return fail(c, GP_ERR_BAD_ARG, "gp_paths_set: n_draws and F must be >= 1 (got %d, %d)", n_draws, F);
+  if (!omega || !w || !eps_u) return fail(c, GP_ERR_BAD_ARG, "gp_paths_set: omega, w or eps_u is NULL");
+  GP_TRY(model_ready(c, "gp_paths_set"));
+  const long bytes = paths_operand_bytes(c, n_draws, F);
+  if ((double)n_draws * c->D > 1e9 || (double)F > 1e8 || bytes > (2L << 30))
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_paths_set: the packed operand of %d draws at F = %d would exceed the limit of 2 GiB: set fewer draws at a time", n_draws, F);
+  const size_t D = (size_t)c->D;
+  if (!all_finite(omega, (size_t)F * c->Q) || (centre && !all_finite(centre, (size_t)c->Q)) || !all_finite(w, (size_t)n_draws * 2 * F * D) ||
+      !all_finite(eps_u, (size_t)n_draws * c->M * D))
+    return fail(c, GP_ERR_BAD_ARG, "gp_paths_set: omega, centre, w or eps_u is not finite");
+  return run_paths_set(c, n_draws, F, omega, centre, w, eps_u);
+}
+
+extern "C" int gp_paths_eval(gp_ctx* c, int64_t n, const double* X, int flags, double* out, double* mean) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: n must be >= 0");
+  if (flags != 0) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: flags is reserved and must be 0 (got %d)", flags);
+  if (const int rc = model_ready(c, "gp_paths_eval"); rc != GP_OK) {
+    c->paths.reset();            // the draws were of a model that is gone
+    return rc;
+  }
+  if (!paths_plan_current(c))
+    return fail(c, GP_ERR_STATE, "gp_paths_eval needs gp_paths_set on the model as it is now (none yet, or a global step, new statistics or new globals since)");
+  if (n == 0) return GP_OK;
+  if (!X || !out) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: X or out is NULL");
+  if (!all_finite(X, (size_t)n * c->Q)) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: X is not finite");
+  return run_paths_eval(c, (long)n, X, out, mean);
+}
+
+extern "C" int gp_paths_clear(gp_ctx* c) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_HIP(c, hipSetDevice(c->device));
+  c->paths.reset();
+  return GP_OK;
+}
+
 // gp_infer_objective / gp_infer_latent: gp_predict's preconditions, then the arguments of the new rows
 static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int raw,
                        bool* nothing) {
@@ -1158,6 +1199,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "nearest_rows")) { g_opt_nn_rows.store(std::max(0, value)); return GP_OK; }
   // and the distinct patterns per chunk of gp_infer_objective_rows / gp_infer_latent_rows (infer.hip: P_cap, 0 = the default)
   if (!std::strcmp(name, "infer_patterns")) { g_opt_inf_patterns.store(std::max(0, value)); return GP_OK; }
+  // and the rows per chunk of gp_paths_eval (paths.hip, 0 = the default)
+  if (!std::strcmp(name, "paths_rows")) { g_opt_paths_rows.store(std::max(0, value)); return GP_OK; }
   std::string known;
   for (const auto& o : options) {
     if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }

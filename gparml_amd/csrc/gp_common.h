@@ -99,6 +99,7 @@ struct PcaPlan;    // pca.hip
 struct NnPlan;     // nearest.hip
 struct JointPlan;  // joint.hip
 struct GradPlan;   // grad.hip
+struct PathsPlan;  // paths.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -109,6 +110,7 @@ struct PcaPlanDelete { void operator()(PcaPlan* p) const; };
 struct NnPlanDelete { void operator()(NnPlan* p) const; };
 struct JointPlanDelete { void operator()(JointPlan* p) const; };
 struct GradPlanDelete { void operator()(GradPlan* p) const; };
+struct PathsPlanDelete { void operator()(PathsPlan* p) const; };
 
 }  // namespace gp
 
@@ -271,6 +273,7 @@ struct gp_ctx {
   std::unique_ptr<gp::NnPlan, gp::NnPlanDelete> nn;          // gp_nearest_rows' buffers (nearest.hip)
   std::unique_ptr<gp::JointPlan, gp::JointPlanDelete> joint;  // gp_predict_joint / gp_predict_sample's buffers (joint.hip)
   std::unique_ptr<gp::GradPlan, gp::GradPlanDelete> grad;     // gp_predict_grad's buffers (grad.hip)
+  std::unique_ptr<gp::PathsPlan, gp::PathsPlanDelete> paths;  // gp_paths_set's draws and gp_paths_eval's buffers (paths.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -333,15 +336,21 @@ int launch_lea_rows(gp_ctx* c, hipStream_t st, const LeaRows& a);
 const double* pred_debug_lea(const gp_ctx* c, long* n);               // gp_debug_peek: the uncertain-input plan's LEA, NULL / 0 without one
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
 // gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
-// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed); the chunk's mean rows;
+// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed; big: both products on the
+// 128 x 128-tile kernel whatever the chunk's size, so that a row's bits do not depend on the rows around it -- paths.hip); the chunk's mean rows;
 // the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them)
 int pred_chunk_plan(gp_ctx* c, long* rows);
 const double* pred_chunk_psi1(const gp_ctx* c);
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf);
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big = 0);
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
 // joint.hip
 int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
 int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
+// paths.hip
+long paths_operand_bytes(const gp_ctx* c, int n_draws, int F);       // the packed operand [Wt ; -G ; E] of gp_paths_set (its size limit: api.hip)
+int run_paths_set(gp_ctx* c, int n_draws, int F, const double* omega, const double* centre, const double* w, const double* eps_u);
+bool paths_plan_current(gp_ctx* c);                                  // a plan of the model as it is now; a stale one is dropped
+int run_paths_eval(gp_ctx* c, long n, const double* X, double* out, double* mean);
 // grad.hip
 int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dvar, double* metric, double* logdet);
 // infer.hip
@@ -384,6 +393,7 @@ extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
 extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 off, 1 on where the remainder rule admits it, 2 on wherever it fits (measurements)
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
+extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval
 extern std::atomic<int> g_opt_inf_patterns;                   // infer.hip: distinct patterns per chunk of gp_infer_*_rows
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }

@@ -35,7 +35,7 @@ struct Lifecycle {
   void stats_unpacked() { model_ = false; }             // gp_stats_unpack.  As found: raised before the refusal of an unpack without a pack
   void stats_packed() { packed_ = true; }
   void step_started() { model_ = false; }
-  void step_enqueued() { progress_ = STEP; model_ = true; outcome_pending_ = true; }     // its outcome is still checked (check_global)
+  void step_enqueued() { progress_ = STEP; model_ = true; outcome_pending_ = true; ++steps_; }     // its outcome is still checked (check_global)
   void step_read_back() { outcome_pending_ = false; }
   void phase2_mode(bool embedding_grads) { embedding_mode_ = embedding_grads; }          // the feature layout of the trial point follows it
   void grad_latest_written() { grad_latest_ = true; }   // the resident CG vector; never cleared (as found: it outlives an upload)
@@ -55,6 +55,9 @@ struct Lifecycle {
   bool step_outcome_pending() const { return outcome_pending_; }
   // Inv / Linv / E describe the statistics and the globals as they are now: gp_predict, gp_infer_*
   bool model_current() const { return step_done() && has_globals_ && model_; }
+  // Which global step the model is of: a plan built from Inv / Linv / E (gp_paths_set) keeps the number and is stale once it differs -- model_
+  // rises again only through step_enqueued, so "model_current() and the same number" is "nothing has happened to the model since"
+  long model_serial() const { return steps_; }
   bool grad_latest_ready() const { return phase2_done() && embedding_mode_; }           // GP_ARR_GRAD_LATEST, rebuilt from this evaluation's gradients
   bool has_grad_latest() const { return grad_latest_; }                                 // gp_cg_update(4, 5): the resident copy
   bool prep_is_current(bool fixa) const { return fixa && prep_fixa_; }
@@ -81,6 +84,7 @@ struct Lifecycle {
   bool model_ = false;            // the last global step saw the statistics and globals as they are now
   bool outcome_pending_ = false;  // a global step was enqueued and its scalars / failure flags have not been read back yet
   bool grad_latest_ = false;
+  long steps_ = 0;                // global steps enqueued so far (model_serial)
 };
 
 }  // namespace gp

@@ -265,7 +265,7 @@ const double* pred_debug_lea(const gp_ctx* c, long* n) {
 // One chunk of points through the front of the pipeline: upload, pred_prep_kernel, Psi1*, the mean product into the chunk's G and (fac != NULL) the
 // two inverse-factor products [Lk^-1 k* | La^-1 k*] into fac (leading dimension ldf).  gp_predict keeps the centred inputs and the factor rows in
 // the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf) {
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big) {
   const PredPlan& p = *c->pred;
   const bool unc = X_S != nullptr;
   const PredUnc* u = p.unc.get();
@@ -279,8 +279,8 @@ int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, 
             rows, (int)Q, c->sf2, mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
   GP_TRY_RC(launch_psi1_rows(c, mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
   // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.P1, Mp}, {c->gstep.E, Dp}, {p.G, Dp + 2 * Mp}, (int)Mp, c->beta)));
-  if (fac) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.P1, Mp}, {c->gstep.Linv, Mp}, {fac, ldf}, (int)Mp)));
+  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.P1, Mp}, {c->gstep.E, Dp}, {p.G, Dp + 2 * Mp}, (int)Mp, c->beta).on_big(big)));
+  if (fac) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.P1, Mp}, {c->gstep.Linv, Mp}, {fac, ldf}, (int)Mp).on_big(big)));
   return GP_OK;
 }
 

@@ -315,6 +315,47 @@ class ShardEngine(object):
                                             mean.ctypes.data_as(_lib._dp)), 'gp_predict_sample')
         return draws, mean
 
+    # ---- pathwise posterior function draws (gp_paths_set, gp_paths_eval, gp_paths_clear) ----------------------
+    def paths_set(self, omega, w, eps_u, centre=None):
+        """Fix ``n_draws`` posterior function draws, after a successful global step as ``predict``: ``omega`` (F, Q) the frequencies of the random
+        Fourier prior (the caller draws omega[f, q] ~ N(0, alpha_q)), ``w`` (n_draws, 2F, D) and ``eps_u`` (n_draws, M, D) standard normals,
+        ``centre`` (Q,) the origin of the phases (None: 0).  ``paths_eval`` then evaluates these same functions anywhere, any number of times,
+        until the model changes (new globals, statistics or a global step drop the draws).  An engine holds ONE set of draws at a time: a second
+        ``paths_set`` replaces the first (``paths_token`` changes with every ``paths_set`` and ``paths_clear``, so a holder of draws can tell)."""
+        omega = np.atleast_2d(np.asarray(omega, dtype=np.float64))
+        assert omega.ndim == 2 and omega.shape[1] == self.Q and omega.shape[0] >= 1, 'omega shape %s: (F, %d) expected' % (omega.shape, self.Q)
+        F = omega.shape[0]
+        w, eps_u = np.asarray(w, dtype=np.float64), np.asarray(eps_u, dtype=np.float64)
+        assert w.ndim == 3 and w.shape[0] >= 1 and w.shape[1:] == (2 * F, self.D), 'w shape %s: (n_draws, %d, %d) expected' % (w.shape, 2 * F, self.D)
+        S = w.shape[0]
+        assert eps_u.shape == (S, self.M, self.D), 'eps_u shape %s: (%d, %d, %d) expected' % (eps_u.shape, S, self.M, self.D)
+        pc = None
+        if centre is not None:
+            centre = np.asarray(centre, dtype=np.float64).reshape(-1)
+            assert centre.shape == (self.Q,), 'centre shape %s: (%d,) expected' % (centre.shape, self.Q)
+            centre, pc = _lib.as_c(centre)
+        (omega, po), (w, pw), (eps_u, pe) = _lib.as_c(omega), _lib.as_c(w), _lib.as_c(eps_u)
+        self._ck(self.lib.gp_paths_set(self.h, S, F, po, pc, pw, pe), 'gp_paths_set')
+        self._paths_draws = S
+        self.paths_token = getattr(self, 'paths_token', 0) + 1
+
+    def paths_eval(self, X, want_mean=False):
+        """The draws of ``paths_set`` at the new deterministic inputs X (n, Q), any n: (n_draws, n, D); with ``want_mean`` also ``predict``'s mean
+        (n, D).  A point's values are the same bits alone, in any batch and in any call, so a draw evaluated on two grids agrees exactly where
+        they share points.  The evaluation state is left untouched."""
+        X, px = self._joint_X(X)
+        n = X.shape[0]
+        out = np.empty((getattr(self, '_paths_draws', 0), n, self.D))
+        mean = np.empty((n, self.D)) if want_mean else None
+        self._ck(self.lib.gp_paths_eval(self.h, n, px, 0, out.ctypes.data_as(_lib._dp), mean.ctypes.data_as(_lib._dp) if want_mean else None), 'gp_paths_eval')
+        return (out, mean) if want_mean else out
+
+    def paths_clear(self):
+        """Drop the draws of ``paths_set`` and free their device memory."""
+        self._ck(self.lib.gp_paths_clear(self.h), 'gp_paths_clear')
+        self._paths_draws = 0
+        self.paths_token = getattr(self, 'paths_token', 0) + 1
+
     # ---- derivatives of the prediction with respect to the input (gp_predict_grad) ----------------------------
     def predict_grad(self, X, jac=True, dvar=True, metric=True, logdet=True):
         """Derivatives of ``predict`` at the new deterministic inputs X (n, Q), after a successful global step as ``predict``.  Returns a dict of the

@@ -14,6 +14,47 @@ from .partial_terms import partial_terms
 from .scg_adapted import SCG_adapted
 
 
+class PathDraws(object):
+    """``n_draws`` posterior function draws held on an engine: ``draws(X) -> (n_draws, n, D)``, the SAME functions at every call, any n.  A point's
+    values are the same bits in every call, so a coarse grid and a finer one agree exactly where they share points.  ``close()`` (or a ``with``
+    block) frees the draws -- and the engine, when the object owns it (Predictor.sample_paths).  An engine holds one set of draws at a time: once
+    another ``paths_set`` or ``paths_clear`` has run on the engine (a second ``ResidentModel.sample_paths``), calling this object raises instead of
+    returning the other set's functions, and its ``close()`` leaves the other set alone."""
+
+    def __init__(self, engine, Z, alpha, n_draws, n_features=1024, seed=None, owns_engine=False):
+        self.engine, self._owns = engine, owns_engine
+        Z = numpy.asarray(Z, dtype=float)
+        M, Q = Z.shape
+        self.n_draws, self.n_features = int(n_draws), int(n_features)
+        rs = numpy.random.RandomState(seed)
+        # the order of the three draws is part of what ``seed`` means
+        self.omega = rs.randn(self.n_features, Q) * numpy.sqrt(numpy.asarray(alpha, dtype=float).reshape(-1))
+        w = rs.randn(self.n_draws, 2 * self.n_features, engine.D)
+        eps_u = rs.randn(self.n_draws, M, engine.D)
+        self.centre = Z.mean(axis=0)
+        engine.paths_set(self.omega, w, eps_u, centre=self.centre)
+        self._token = engine.paths_token
+
+    def __call__(self, X, want_mean=False):
+        if self.engine is None or self.engine.paths_token != self._token:
+            raise RuntimeError('these draws are gone: closed, or replaced by a later paths_set / paths_clear on the same engine -- draw again')
+        return self.engine.paths_eval(X, want_mean=want_mean)
+
+    def close(self):
+        if self.engine is not None:
+            if self._owns:
+                self.engine.close()
+            elif self.engine.paths_token == self._token:
+                self.engine.paths_clear()
+            self.engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 class Predictor(object):
     def __init__(self, global_statistics, accumulated_statistics, N_train, D, device=0, partial_terms_class=None, engine_class=None):
         """global_statistics: dict Z (M,Q), sf2, alpha, beta; accumulated_statistics: the five base sums of the trained model
@@ -58,6 +99,18 @@ class Predictor(object):
             return eng.predict_sample(X, n_draws, include_noise=include_noise, jitter=jitter, eps=eps, seed=seed)
         finally:
             eng.close()
+
+    def sample_paths(self, n_draws, n_features=1024, seed=None):
+        """``n_draws`` posterior function draws of the trained model as a callable: ``draws(X) -> (n_draws, n, D)`` at any points X (n, Q), any n,
+        the same functions at every call (ShardEngine.paths_set / paths_eval; Matheron's rule on ``n_features`` random Fourier frequency pairs
+        drawn, like the normals, from numpy.random.RandomState(seed); the phases are centred on the column mean of Z).  The work of a call is
+        linear in n.  The object holds an engine with the trained model: ``close()`` it (or use ``with``)."""
+        eng = self._trained_engine()
+        try:
+            return PathDraws(eng, self.gs['Z'], self.gs['alpha'], n_draws, n_features=n_features, seed=seed, owns_engine=True)
+        except Exception:
+            eng.close()
+            raise
 
     def _predict_grad(self, X, **which):
         eng = self._trained_engine()

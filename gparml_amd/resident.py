@@ -118,6 +118,16 @@ class ResidentModel(object):
         self._refresh_statistics(flat_array)
         return self.engines[0].predict_sample(X, n_draws, include_noise=include_noise, jitter=jitter, eps=eps, seed=seed)
 
+    def sample_paths(self, flat_array, n_draws, n_features=1024, seed=None):
+        """``n_draws`` posterior function draws of the model at ``flat_array`` as a callable ``draws(X) -> (n_draws, n, D)`` (predict.PathDraws on
+        the root engine: the same functions at every call, any n).  The statistics are brought up to date as in ``predict``, with the same
+        collective rule.  The draws belong to that model and the root engine holds one set at a time: after the next evaluation of the model, or a
+        second ``sample_paths``, the earlier callable raises; call ``sample_paths`` again for new draws (nothing is redrawn by itself)."""
+        from .predict import PathDraws
+        self._refresh_statistics(flat_array)
+        Z, _, alpha, _ = split_flat(transform_vec(self._pos, np.asarray(flat_array, dtype=np.float64)), self.M, self.Q)
+        return PathDraws(self.engines[0], Z, alpha, n_draws, n_features=n_features, seed=seed)
+
     def _refresh_statistics(self, flat_array):
         flat_array = np.asarray(flat_array, dtype=np.float64)
         last = self._stats_x

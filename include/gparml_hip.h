@@ -212,6 +212,42 @@ int gp_predict_sample(gp_ctx* ctx, int64_t n, const double* X, int flags, double
  * gp_finish / gp_predict / gp_predict_joint after it give bit-identical results.  Not covered: uncertain inputs, second derivatives. */
 int gp_predict_grad(gp_ctx* ctx, int64_t n, const double* X, int flags, double* jac, double* dvar, double* metric, double* logdet);
 
+/* Pathwise posterior function draws: n_draws sampled functions that can be evaluated at any number of new deterministic inputs, in any number of
+ * calls, each call evaluating the SAME functions (Matheron's rule on a random Fourier prior; csrc/paths.hip).  The work of an
+ * evaluation is linear in n, O(n (F + M) n_draws D); no n x n matrix is formed and n has no limit.
+ * The ARD-RBF prior in F frequency pairs: with frequencies omega (F,Q) and a centre (Q; NULL = 0) the phase of x is
+ *   theta_f(x) = sum_q omega[f][q] (x_q - centre_q)       (difference first, q ascending, one fused multiply-add per term)
+ * and the 2F features are phi(x) = sqrt(sf2 / F) [cos theta_0 .. cos theta_{F-1}, sin theta_0 .. sin theta_{F-1}].  The caller draws
+ * omega[f][q] ~ N(0, alpha_q); phi(x) . phi(x') is then an unbiased estimate of k(x, x') whose diagonal is exactly sf2.  With a = Lk^-1 k(x),
+ * b = La^-1 k(x) as above and Phi_Z (M,2F) the features of the inducing points,
+ *   G_s = Lk^-1 Phi_Z w_s                                   (M,D) once per draw, in gp_paths_set
+ *   out[s][i][d] = mean[i][d] + phi(x_i) . w_s[:,d] - a_i . G_s[:,d] + b_i . eps_u[s][:,d]
+ * w (n_draws,2F,D) and eps_u (n_draws,M,D): standard normals from the caller (there is no device generator).  With an exact prior the draws have
+ * gp_predict_joint's mean and cov (f, not y: the noise enters nowhere); with F pairs the implied covariance differs from it by exactly
+ * P (K_F - K) P^T, K_F = phi phi^T on (X, Z) jointly, P = [I, -k(X,Z) Kmm^-1]: every element of K_F - K has a standard deviation <= sf2 / sqrt(2F).
+ * The coordinates enter through the library's centred frame: x - shift and centre - shift, each rounded once, then their difference.
+ * gp_paths_set: builds the context's plan of the draws (replacing an earlier one): omega, the centre and the packed operand [Wt ; -G ; E] of
+ * (2F rounded up to 16) + 2 Mp rows and n_draws D (rounded up to 128) columns of doubles, Mp = M rounded up to 128.  GP_ERR_UNSUPPORTED when that
+ * operand would exceed 2 GiB (set fewer draws at a time).  Needs gp_predict's preconditions.
+ * gp_paths_eval: X (n,Q); out (n_draws,n,D); mean (n,D) or NULL: gp_predict's mean.  flags is reserved and must be 0.  GP_ERR_STATE without a plan,
+ * and after anything that makes gp_predict return GP_ERR_STATE (new globals, new statistics, a phase 1, a global step): that event also drops the
+ * plan -- the draws belonged to the model of the global step gp_paths_set saw.  gp_paths_clear drops the plan and frees its memory.
+ * A context holds ONE plan: gp_paths_set frees the earlier one before it builds the new one, so a call that fails part way leaves none.  A plan
+ * that such an event has made stale keeps its device memory (up to 2 GiB) until the next gp_paths_eval, gp_paths_set or gp_paths_clear (or
+ * gp_destroy): a caller that is done with its draws calls gp_paths_clear.
+ * GP_ERR_BAD_ARG, decided before anything is launched: n < 0, n_draws < 1, F < 1, flags != 0, a NULL omega, w, eps_u, or X / out with n > 0,
+ * non-finite omega, centre, w, eps_u or X.  n = 0 writes nothing.  All synchronous.  The evaluation state is left untouched: gp_phase2 / gp_finish /
+ * gp_predict / gp_predict_joint after them give bit-identical results.
+ * Determinism: results are bit-identical from run to run, and a point's outputs depend on that point, the plan and the model only -- the same bits
+ * alone, in any batch, in any row order and wherever a chunk boundary falls, so one draw evaluated on two grids agrees exactly at shared points
+ * (every matrix product of this path runs on one fixed GEMM kernel without split-k, whatever the launch size; fixed summation order, no
+ * floating-point atomics).  Rows are taken in chunks of about 64 MB of left operand [phi | a | b].
+ * Not covered: uncertain inputs, noise draws, results kept on the device. */
+int gp_paths_set(gp_ctx* ctx, int n_draws, int F, const double* omega /*(F,Q)*/, const double* centre /*(Q) or NULL = 0*/,
+                 const double* w /*(n_draws,2F,D)*/, const double* eps_u /*(n_draws,M,D)*/);
+int gp_paths_eval(gp_ctx* ctx, int64_t n, const double* X /*(n,Q)*/, int flags, double* out /*(n_draws,n,D)*/, double* mean /*(n,D) or NULL*/);
+int gp_paths_clear(gp_ctx* ctx);
+
 /* ---- latent inference for new rows ---------------------------------------------------------------- */
 /* The bound of n NEW rows y (n,D) under q(x) = N(X_mu, diag X_S), with q(u) frozen at the optimum of the trained model (the statistics of the last
  * global step): per row, with O the observed columns (D_o of them), W and B as for gp_predict, v = W_O y_O and G = W_O W_O^T - D_o B,
@@ -402,7 +438,9 @@ int gp_debug_force_staging(int on);
  * gp_set_globals refills the per-evaluation buffers with them -- a kernel that reads what this evaluation did not write fails
  * deterministically (tests/test_gpu_poison.py).  "nearest_rows", k: gp_nearest_rows and gp_nearest_rows_masked take their new rows k at a time (rounded up to 16) and host
  * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults.  "infer_patterns", k: a chunk of
- * gp_infer_objective_rows / gp_infer_latent_rows holds at most k distinct patterns (P_cap = k); 0 restores the default. */
+ * gp_infer_objective_rows / gp_infer_latent_rows holds at most k distinct patterns (P_cap = k); 0 restores the default.  "paths_rows", k: gp_paths_eval
+ * takes its rows k at a time (any k >= 1: the chunk's buffers are padded to 128 rows, the chunk is not; never more than gp_predict's chunk), so that a
+ * small call spans chunks; 0 restores the default. */
 int gp_debug_set_option(const char* name, int value);
 /* in-place lower Cholesky + inverse of an SPD (n,n) matrix; logdet out; returns GP_ERR_NOT_PD on failure */
 int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet);
