@@ -70,6 +70,11 @@ SIGNATURES = {
     'gp_infer_objective_rows': (ctypes.c_int, [_vp, _i64, _dp, _u8p, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_infer_latent_rows': (ctypes.c_int, [_vp, _i64, _dp, _u8p, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     'gp_kmeans_accumulate': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, ctypes.POINTER(_i64), _dp, _ip]),
+    'gp_select_begin': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_double]),
+    'gp_select_run': (ctypes.c_int, [_vp, ctypes.c_int, _ip, ctypes.POINTER(_i64), _dp]),
+    'gp_select_candidate': (ctypes.c_int, [_vp, _dp, ctypes.POINTER(_i64), _dp, _dp]),
+    'gp_select_apply': (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_double, _i64, _dp]),
+    'gp_select_end': (ctypes.c_int, [_vp]),
     'gp_scatter_accumulate': (ctypes.c_int, [_vp, _i64, _dp, _dp, _dp, _dp]),
     'gp_project_rows': (ctypes.c_int, [_vp, _i64, _dp, _dp, _dp, ctypes.c_int, _dp]),
     'gp_nearest_rows': (ctypes.c_int, [_vp, _i64, _dp, _i64, _dp, _ip, ctypes.c_int, _dp, ctypes.POINTER(_i64), _dp]),

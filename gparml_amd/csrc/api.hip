@@ -963,6 +963,77 @@ extern "C" int gp_project_rows(gp_ctx* c, int64_t n, const double* Y, const doub
   return run_project(c, (long)n, Y, mean, P, Q_out, X);
 }
 
+// ---- greedy conditional-variance selection of the inducing points (csrc/select.hip) ----
+// Nothing of the evaluation is read or written: only the resident X_mu (X == NULL) and the plan's buffers.
+static int select_plan(gp_ctx* c, const char* who) {
+  if (!c->sel) return fail(c, GP_ERR_STATE, "%s before gp_select_begin (or after gp_select_end)", who);
+  GP_HIP(c, hipSetDevice(c->device));
+  return GP_OK;
+}
+
+extern "C" int gp_select_begin(gp_ctx* c, int64_t n, const double* X, int K, double sf2, const double* alpha, double tol) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: n must be >= 0");
+  if (K < 1) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: K must be >= 1");
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: tol must be finite and >= 0");
+  if (!(sf2 > 0.0) || !std::isfinite(sf2)) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: sf2 must be finite and > 0");
+  if (!alpha) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: alpha is NULL");
+  for (int q = 0; q < c->Q; ++q)
+    if (!(alpha[q] >= 0.0) || !std::isfinite(alpha[q])) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: alpha must be finite and >= 0");
+  if (!X) {
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_select_begin: X is NULL (the resident X_mu) before gp_upload_shard");
+    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: X is NULL (the resident X_mu): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
+  } else if (!all_finite(X, (size_t)n * c->Q)) {
+    return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: X is not finite");
+  }
+  GP_HIP(c, hipSetDevice(c->device));
+  c->sel.reset();                    // an earlier plan goes first: its memory counts as free
+  size_t free_b = 0, total_b = 0;
+  GP_HIP(c, hipMemGetInfo(&free_b, &total_b));
+  const double need = 8.0 * (double)K * (double)std::max<int64_t>(n, 1);      // the factor alone, before any rounding: no overflow
+  if (need > (double)free_b || (double)select_bytes(c, (long)n, K, X != nullptr) > (double)free_b)
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_select_begin: the factor of n = %ld rows and K = %d columns takes %.3g bytes, %.3g are free on the device: "
+                "select over fewer rows per shard, or fewer points", (long)n, K, need, (double)free_b);
+  return run_select_begin(c, (long)n, X, K, sf2, alpha, tol);
+}
+
+extern "C" int gp_select_run(gp_ctx* c, int steps, int32_t* n_done, int64_t* rows, double* trace) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_TRY(select_plan(c, "gp_select_run"));
+  if (steps < 0) return fail(c, GP_ERR_BAD_ARG, "gp_select_run: steps must be >= 0");
+  if (!n_done || (steps > 0 && !rows)) return fail(c, GP_ERR_BAD_ARG, "gp_select_run: n_done or rows is NULL");
+  return run_select_run(c, steps, n_done, rows, trace);
+}
+
+extern "C" int gp_select_candidate(gp_ctx* c, double* d, int64_t* row, double* x, double* l) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_TRY(select_plan(c, "gp_select_candidate"));
+  if (!d || !row) return fail(c, GP_ERR_BAD_ARG, "gp_select_candidate: d or row is NULL");
+  return run_select_candidate(c, d, row, x, l);
+}
+
+extern "C" int gp_select_apply(gp_ctx* c, const double* x_p, const double* l_p, double d_p, int64_t own_row, double* trace) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_TRY(select_plan(c, "gp_select_apply"));
+  long n; int K, j;
+  select_info(c, &n, &K, &j);
+  if (j >= K) return fail(c, GP_ERR_STATE, "gp_select_apply: all K = %d steps of this selection are done", K);
+  if (!x_p || (j > 0 && !l_p)) return fail(c, GP_ERR_BAD_ARG, "gp_select_apply: x_p or l_p is NULL");
+  if (!(d_p > 0.0) || !std::isfinite(d_p)) return fail(c, GP_ERR_BAD_ARG, "gp_select_apply: d_p must be finite and > 0");
+  if (own_row < -1 || own_row >= n) return fail(c, GP_ERR_BAD_ARG, "gp_select_apply: own_row = %ld is outside -1 .. n - 1 = %ld", (long)own_row, n - 1);
+  if (!all_finite(x_p, (size_t)c->Q) || !all_finite(l_p, (size_t)j)) return fail(c, GP_ERR_BAD_ARG, "gp_select_apply: x_p or l_p is not finite");
+  return run_select_apply(c, x_p, l_p, d_p, own_row, trace);
+}
+
+extern "C" int gp_select_end(gp_ctx* c) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_TRY(select_plan(c, "gp_select_end"));
+  GP_HIP(c, hipStreamSynchronize(c->stream));
+  ++c->sync_epoch;
+  c->sel.reset();
+  return GP_OK;
+}
+
 // Per new row the nearest training row (csrc/nearest.hip).  Nothing of the evaluation is read or written: only the Y columns of Kaug and the resident
 // X_mu (Y_train == NULL) and the plan's buffers.  One body for both entries (fn names the entry in the messages): masked = every new row has its
 // own observed set (observed (n,D), nonzero = observed), else the one column list cols for all of them.
@@ -1201,6 +1272,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "infer_patterns")) { g_opt_inf_patterns.store(std::max(0, value)); return GP_OK; }
   // and the rows per chunk of gp_paths_eval (paths.hip, 0 = the default)
   if (!std::strcmp(name, "paths_rows")) { g_opt_paths_rows.store(std::max(0, value)); return GP_OK; }
+  // and the host rows per upload chunk of gp_select_begin (select.hip, 0 = the default)
+  if (!std::strcmp(name, "select_rows")) { g_opt_sel_rows.store(std::max(0, value)); return GP_OK; }
   std::string known;
   for (const auto& o : options) {
     if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }

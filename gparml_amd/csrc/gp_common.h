@@ -100,6 +100,7 @@ struct NnPlan;     // nearest.hip
 struct JointPlan;  // joint.hip
 struct GradPlan;   // grad.hip
 struct PathsPlan;  // paths.hip
+struct SelPlan;    // select.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -111,6 +112,7 @@ struct NnPlanDelete { void operator()(NnPlan* p) const; };
 struct JointPlanDelete { void operator()(JointPlan* p) const; };
 struct GradPlanDelete { void operator()(GradPlan* p) const; };
 struct PathsPlanDelete { void operator()(PathsPlan* p) const; };
+struct SelPlanDelete { void operator()(SelPlan* p) const; };
 
 }  // namespace gp
 
@@ -274,6 +276,7 @@ struct gp_ctx {
   std::unique_ptr<gp::JointPlan, gp::JointPlanDelete> joint;  // gp_predict_joint / gp_predict_sample's buffers (joint.hip)
   std::unique_ptr<gp::GradPlan, gp::GradPlanDelete> grad;     // gp_predict_grad's buffers (grad.hip)
   std::unique_ptr<gp::PathsPlan, gp::PathsPlanDelete> paths;  // gp_paths_set's draws and gp_paths_eval's buffers (paths.hip)
+  std::unique_ptr<gp::SelPlan, gp::SelPlanDelete> sel;        // gp_select_begin's state: rows, factor, conditional variances (select.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -361,6 +364,14 @@ int run_infer_rows(gp_ctx* c, int mode, long n, const double* Y, const unsigned 
 const double* infer_debug_lea(const gp_ctx* c, long* n);              // gp_debug_peek: the chunk's LEA, NULL / 0 without a plan
 // kmeans.hip
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
+// select.hip (the plan lives from gp_select_begin to gp_select_end; the entry points check its presence and the arguments: api.hip)
+long select_bytes(const gp_ctx* c, long n, int K, bool host_rows);     // device bytes a plan of this size takes
+int run_select_begin(gp_ctx* c, long n, const double* X, int K, double sf2, const double* alpha, double tol);
+int run_select_run(gp_ctx* c, int steps, int32_t* n_done, int64_t* rows, double* trace);
+int run_select_candidate(gp_ctx* c, double* d, int64_t* row, double* x, double* l);
+int run_select_apply(gp_ctx* c, const double* x_p, const double* l_p, double d_p, int64_t own_row, double* trace);
+void select_info(const gp_ctx* c, long* n, int* K, int* j);
+const double* select_debug(const gp_ctx* c, bool want_L, long* cnt);   // gp_debug_peek: the factor's written columns or d, NULL / 0 without a plan
 // pca.hip
 int run_scatter(gp_ctx* c, long n, const double* Y, const double* centre, double* sum, double* gram);
 int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const double* P, int Q, double* X);
@@ -394,6 +405,7 @@ extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 o
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
 extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval
+extern std::atomic<int> g_opt_sel_rows;                       // select.hip: host rows per upload chunk of gp_select_begin
 extern std::atomic<int> g_opt_inf_patterns;                   // infer.hip: distinct patterns per chunk of gp_infer_*_rows
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }

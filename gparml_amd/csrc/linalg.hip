@@ -1069,6 +1069,10 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
   else if (!std::strcmp(name, "pred_LEA")) src = pred_debug_lea(c, &cnt);
   else if (!std::strcmp(name, "infer_LEA")) src = infer_debug_lea(c, &cnt);
+  else if (!std::strcmp(name, "select_L") || !std::strcmp(name, "select_d")) {
+    src = select_debug(c, name[7] == 'L', &cnt);
+    if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_select_begin .. gp_select_end", name);
+  }
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
   GP_HIP(c, hipStreamSynchronize(c->stream));

@@ -103,14 +103,43 @@ def _device_kmeans(map_reduce, options, names, engine_class=None):
             e.close()
 
 
+def _device_greedy(map_reduce, options, names, sf2, alpha, engine_class=None):
+    """options['init_Z'] == 'greedy': greedy conditional-variance selection (gparml_amd.init.greedy_select) of M rows among the embeddings of
+    ALL shards under the initial kernel (sf2, alpha) -- one temporary engine and one part per device, holding the embeddings of the shards
+    that will live there in the order of their names.  Raises LinAlgError when fewer than M rows can be told apart: nothing is invented."""
+    from . import init
+    if engine_class is None:
+        from .engine import ShardEngine as engine_class
+    devices = map_reduce._devices(options) if hasattr(map_reduce, '_devices') else [int(options.get('device', 0))]
+    rows = {}
+    for i, name in enumerate(names):
+        rows.setdefault(devices[i % len(devices)], []).append(map_reduce.load(options['embeddings'] + '/' + name + '.embedding.npy'))
+    engines = []
+    try:
+        parts = []
+        for dev in sorted(rows):
+            engines.append(engine_class(1, 1, 1, options['Q'], device=dev))
+            parts.append(init.HostRows(engines[-1], numpy.concatenate(rows[dev])))
+        Z, _, trace = init.greedy_select(parts, options['M'], sf2, alpha, tol=options.get('init_Z_tol', 1e-10))
+    finally:
+        for e in engines:
+            e.close()
+    if Z.shape[0] < options['M']:
+        raise numpy.linalg.LinAlgError('greedy initialisation of Z: only K\' = %d of the M = %d inducing points could be selected: the conditional '
+                                       'variance of every remaining row is within tol of zero (last trace residual %.3e)'
+                                       % (Z.shape[0], options['M'], trace[-1] if len(trace) else float('nan')))
+    return Z
+
+
 def init_statistics(map_reduce, options, engine_class=None):
     """parallel_GPLVM.init_statistics (:134-214): the names the backends pass around, the initial global statistics -- inducing points
     Z by k-means over the first shards' embeddings (scipy.cluster.vq.kmeans, topped up with the first embeddings when k-means returns
     fewer than M centres) plus 0.05 * randn, sf2 = alpha = beta = 1 (:179-194), or the ``*_f.npy`` files of a previous run with
     ``options['load']`` (:195-200) -- and the optimisation bounds.  Returns (options, global_statistics).  One-off host work, unless
     ``options['init_Z'] == 'device'``: the k-means then runs on the GPUs over the embeddings of all shards (_device_kmeans; hours of host
-    time at N = 1e6, M = 512 otherwise), with the same top-up and noise.  ``engine_class`` (tests only) replaces
-    ShardEngine there."""
+    time at N = 1e6, M = 512 otherwise), with the same top-up and noise.  ``options['init_Z'] == 'greedy'``: the greedy
+    conditional-variance selection instead (_device_greedy): Z is M data rows chosen under the initial kernel, LinAlgError
+    when the data has fewer than M rows the kernel tells apart.  ``engine_class`` (tests only) replaces ShardEngine there."""
     M, Q = options['M'], options['Q']
     Driver(options, map_reduce)          # fills the *_names entries and the flat bounds exactly as the evaluations expect them
     if not options.get('load'):
@@ -122,6 +151,11 @@ def init_statistics(map_reduce, options, engine_class=None):
             embeddings = numpy.concatenate((embeddings, map_reduce.load(options['embeddings'] + '/' + names[idx] + '.embedding.npy')))
         if embeddings.shape[1] != Q:
             raise Exception('Given Q does not equal existing embedding data dimensions!')
+        if options.get('init_Z') == 'greedy':
+            # kernel-aware placement under the initial sf2 = alpha = 1 below: M data rows, no top-up and no noise (every point stays a data row)
+            Z = _device_greedy(map_reduce, options, names, 1.0, numpy.ones(Q), engine_class)
+            gs = {'Z': Z, 'sf2': numpy.array([[1.0]]), 'alpha': numpy.ones((1, Q)), 'beta': numpy.array([[1.0]])}
+            return options, gs
         if options.get('init_Z') == 'device':
             Z = _device_kmeans(map_reduce, options, names, engine_class)
         else:

@@ -468,6 +468,64 @@ class ShardEngine(object):
                  'gp_kmeans_accumulate')
         return sums, counts, dist2, labels
 
+    # ---- greedy conditional-variance selection of the inducing points (gp_select_*) ---------------------------
+    def select_begin(self, K, sf2, alpha, tol=1e-10, X=None):
+        """Starts a greedy conditional-variance selection (pivoted Cholesky of K_nn, csrc/select.hip) of up to ``K`` rows among the host rows
+        ``X`` (n, Q), or among the resident X_mu of this engine (``X`` None), under the kernel sf2 exp(-1/2 sum_q alpha_q (x_q - z_q)^2); a step
+        needs a conditional variance above ``tol`` sf2.  An engine holds one selection at a time; ``select_end`` frees it.  The evaluation state
+        is left untouched.  Returns the number of rows."""
+        alpha = np.asarray(alpha, dtype=np.float64).reshape(-1)
+        assert alpha.shape == (self.Q,), 'alpha shape %s: (%d,) expected' % (alpha.shape, self.Q)
+        alpha, pa = _lib.as_c(alpha)
+        px, n = None, self.N_s
+        if X is not None:
+            X = np.atleast_2d(np.asarray(X, dtype=np.float64))
+            assert X.ndim == 2 and X.shape[1] == self.Q, 'X shape %s: (n, %d) expected' % (X.shape, self.Q)
+            n = X.shape[0]
+            X, px = _lib.as_c(X)
+        self._ck(self.lib.gp_select_begin(self.h, n, px, int(K), float(sf2), pa, float(tol)), 'gp_select_begin')
+        self._select_n = n
+        return n
+
+    def select_run(self, steps):
+        """Up to ``steps`` further steps of the selection on the device without a host round trip per step (the one-shard path).  Returns
+        (rows (k,) int64, trace (k,)): the pivots found, k <= steps (fewer: the stopping rule, or K reached), and the trace of the Nystrom
+        residual after each."""
+        steps = int(steps)
+        done = ctypes.c_int32(0)
+        rows, trace = np.empty(max(steps, 1), dtype=np.int64), np.empty(max(steps, 1))
+        self._ck(self.lib.gp_select_run(self.h, steps, ctypes.byref(done), rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), trace.ctypes.data_as(_lib._dp)),
+                 'gp_select_run')
+        return rows[:done.value].copy(), trace[:done.value].copy()
+
+    def select_candidate(self, steps_done):
+        """The best unselected local row after ``steps_done`` steps: (d, row, x (Q,), l (steps_done,)); row -1 and d -inf when every row is
+        selected (or there are none)."""
+        d, row = ctypes.c_double(0.0), ctypes.c_int64(-1)
+        x, l = np.zeros(self.Q), np.zeros(max(int(steps_done), 1))
+        self._ck(self.lib.gp_select_candidate(self.h, ctypes.byref(d), ctypes.byref(row), x.ctypes.data_as(_lib._dp), l.ctypes.data_as(_lib._dp)),
+                 'gp_select_candidate')
+        return d.value, row.value, x, l[:int(steps_done)]
+
+    def select_apply(self, x_p, l_p, d_p, own_row=-1):
+        """One step with the pivot (x_p (Q,), l_p (steps done,), d_p) given by the caller; ``own_row`` >= 0: the pivot is this local row.  Returns
+        the local trace after the step.  The same kernels, the same bits as ``select_run``."""
+        x_p, px = _lib.as_c(np.asarray(x_p, dtype=np.float64).reshape(-1))
+        l_p, pl = _lib.as_c(np.asarray(l_p, dtype=np.float64).reshape(-1))
+        assert x_p.shape == (self.Q,), 'x_p shape %s: (%d,) expected' % (x_p.shape, self.Q)
+        t = ctypes.c_double(0.0)
+        self._ck(self.lib.gp_select_apply(self.h, px, pl if l_p.size else None, float(d_p), int(own_row), ctypes.byref(t)), 'gp_select_apply')
+        return t.value
+
+    def select_end(self):
+        self._ck(self.lib.gp_select_end(self.h), 'gp_select_end')
+
+    def select_peek(self, steps_done):
+        """(L (steps_done, n), d (n,)) of the selection in progress as they lie on the device (gp_debug_peek 'select_L', 'select_d'; a test tool)."""
+        n, npad = self._select_n, (max(self._select_n, 1) + 63) // 64 * 64
+        L = self.peek('select_L', max(int(steps_done) * npad, 1))[:int(steps_done) * npad].reshape(int(steps_done), npad)
+        return L[:, :n].copy(), self.peek('select_d', npad)[:n].copy()
+
     # ---- initialisation of the embeddings (gp_scatter_accumulate, gp_project_rows) --------------------------------
     def _rows_arg(self, Y):
         if Y is None:

@@ -1,11 +1,15 @@
-"""The initialisations on the device: the k-means that places the inducing points, the PCA that turns Y into the starting embeddings, and the
-nearest-training-row search that starts the latent inference of new rows.
+"""The initialisations on the device: the k-means and the greedy conditional-variance selection that place the inducing points, the PCA that turns
+Y into the starting embeddings, and the nearest-training-row search that starts the latent inference of new rows.
 
 k-means.  ``parallel_GPLVM.init_statistics`` calls ``scipy.cluster.vq.kmeans(embeddings, M)`` on the host, over the first shards that reach M rows
 (parallel_GPLVM.py:179-186).  A pass of that loop is N K Q distance terms -- an hour of host time at N = 1e6, M = 512 with scipy's twenty
 restarts -- and it has the map-reduce shape of an evaluation: every shard yields per-centre sums, counts and summed
 distances (``ShardEngine.kmeans_accumulate``, csrc/kmeans.hip), which add over shards and ranks.  ``kmeans`` here is scipy's ``_kmeans``
 loop restated on those sums: given the same seeds it returns what ``scipy.cluster.vq.kmeans(X_all, seeds, thresh=thresh)`` returns.
+
+Greedy selection.  ``greedy_select`` is the kernel-aware placement: the pivoted Cholesky factorisation of K_nn (Burt, Rasmussen and van der Wilk
+2019; csrc/select.hip), one deterministic pass of K steps whose every point is a data row and which reports, after every step, the Nystrom
+residual tr(K_nn - K_nm K_mm^-1 K_mn) the collapsed bound is penalised by.  Each part updates its own rows; one pivot per step crosses parts.
 
 PCA (the second half of this file).  ``supporting_functions.PCA`` (supporting_functions.py:102-121: left singular vectors of the centred data,
 each scaled to unit standard deviation) runs over ALL data (local_MapReduce.py:50-65: per-subset PCA "gives rise to rotation problems").  The
@@ -34,6 +38,22 @@ class HostRows(object):
 
     def take_rows(self, idx):
         return self.X[numpy.asarray(idx, dtype=numpy.int64)]
+
+    # greedy_select: the selection lives in the engine, one at a time -- every part of one call needs an engine of its own
+    def select_begin(self, K, sf2, alpha, tol=1e-10):
+        return self.engine.select_begin(K, sf2, alpha, tol=tol, X=self.X)
+
+    def select_run(self, steps):
+        return self.engine.select_run(steps)
+
+    def select_candidate(self, steps_done):
+        return self.engine.select_candidate(steps_done)
+
+    def select_apply(self, x_p, l_p, d_p, own_row=-1):
+        return self.engine.select_apply(x_p, l_p, d_p, own_row=own_row)
+
+    def select_end(self):
+        return self.engine.select_end()
 
 
 class _Ranks(object):
@@ -130,6 +150,72 @@ def kmeans(parts, K, seeds=None, thresh=1e-5, max_iters=1000, restarts=1, rng=No
         if best is None or run[1] < best[1]:
             best = run
     return best
+
+
+# ------------------------------------------------------------------------------------------------- greedy selection
+def greedy_select(parts, K, sf2, alpha, tol=1e-10, dist_group=None):
+    """Greedy conditional-variance selection of up to K rows over the rows of all ``parts`` under the kernel
+    sf2 exp(-1/2 sum_q alpha_q (x_q - z_q)^2).  Returns (Z (K', Q), pivots (K', 2) int64, trace (K',)): the selected rows in the order they were
+    chosen, each as (part, row) -- the part counted over all ranks in the order rank, part -- and after every step the trace of the Nystrom
+    residual over all rows.  K' < K when the largest conditional variance left is <= ``tol`` sf2 (or the rows ran out): the data has no more than
+    K' points the kernel tells apart.
+
+    parts: as for ``kmeans`` -- ShardEngines with resident embeddings, or ``HostRows(engine, X)``, each with an engine of its OWN (an engine
+    holds one selection).  One part and no ranks: every step runs on the device without a host round trip (``select_run``).  Several parts, or
+    ranks: per step every part offers its best row (``select_candidate``), the largest conditional variance wins -- of equal ones the lowest
+    (rank, part, row) -- and every part applies that pivot (``select_apply``); the same pivots and the same bits of L and d as one part.
+    dist_group: a torch.distributed group (True: the default group) whose ranks each hold some of the parts.  COLLECTIVE then: every rank calls
+    with the same K, sf2, alpha and tol, and every rank returns the same arrays."""
+    parts = list(parts)
+    K = int(K)
+    assert parts and K >= 1
+    owners = [id(getattr(p, 'engine', p)) for p in parts]
+    assert len(set(owners)) == len(owners), 'greedy_select: every part needs an engine of its own (an engine holds one selection)'
+    ranks = _Ranks(dist_group, getattr(parts[0], 'device', 0))
+    alpha = numpy.asarray(alpha, dtype=numpy.float64).reshape(-1)
+    Q = alpha.size
+    begun = []
+    try:
+        for p in parts:
+            p.select_begin(K, sf2, alpha, tol=tol)
+            begun.append(p)
+        if len(parts) == 1 and ranks.world == 1:
+            rows, trace = parts[0].select_run(K)
+            Z = numpy.asarray(parts[0].take_rows(rows), dtype=numpy.float64).reshape(len(rows), Q)
+            return Z, numpy.stack([numpy.zeros(len(rows), dtype=numpy.int64), rows], axis=1), trace
+        counts = numpy.zeros(ranks.world)
+        counts[ranks.rank] = len(parts)
+        first_part = int(round(ranks.sum(counts)[:ranks.rank].sum()))
+        Z, pivots, trace = [], [], []
+        for j in range(K):
+            best = (-numpy.inf, -1, -1, None, None)                      # d, part, row, x, l
+            for k, p in enumerate(parts):
+                d, row, x, l = p.select_candidate(j)
+                if row >= 0 and d > best[0]:                             # strict: of equal ones the lowest part
+                    best = (d, k, row, x, l)
+            slots = numpy.zeros(ranks.world)
+            slots[ranks.rank] = best[0]
+            slots = ranks.sum(slots)
+            winner = int(numpy.argmax(slots))                            # the first of equal maxima: the lowest rank
+            d_p = float(slots[winner])
+            if not d_p > float(tol) * float(sf2):                        # the stopping rule, on the bits the device would compare
+                break
+            rec = numpy.full(2 + Q + j, -0.0)                            # -0.0: the identity of the sum, also for a winner's -0.0
+            if winner == ranks.rank:
+                rec[0], rec[1], rec[2:2 + Q], rec[2 + Q:] = first_part + best[1], best[2], best[3], best[4]
+            rec = ranks.sum(rec)
+            x_p, l_p = rec[2:2 + Q], rec[2 + Q:]
+            t = 0.0
+            for k, p in enumerate(parts):
+                t += p.select_apply(x_p, l_p, d_p, own_row=best[2] if (winner == ranks.rank and k == best[1]) else -1)
+            trace.append(float(ranks.sum(numpy.array([t]))[0]))
+            Z.append(numpy.array(x_p))
+            pivots.append((int(round(rec[0])), int(round(rec[1]))))
+        return (numpy.array(Z, dtype=numpy.float64).reshape(len(Z), Q), numpy.array(pivots, dtype=numpy.int64).reshape(len(pivots), 2),
+                numpy.array(trace, dtype=numpy.float64))
+    finally:
+        for p in begun:
+            p.select_end()
 
 
 # ------------------------------------------------------------------------------------------------- PCA

@@ -140,15 +140,21 @@ class ResidentModel(object):
             self._stats_x = np.array(flat_array, copy=True)
             self._stats_version = self.version
 
-    def init_Z(self, K=None, **kw):
+    def init_Z(self, K=None, method='kmeans', **kw):
         """Inducing points for this model by k-means over the resident X_mu of every shard of every rank (gparml_amd.init.kmeans on the engines,
         X = None: nothing is uploaded): (centres (<= K, Q), mean distance, passes); K defaults to M.  The keyword arguments are init.kmeans'
         (seeds, thresh, max_iters, restarts, rng).  COLLECTIVE across ranks, with this model's group.  The caller tops up and adds the
-        reference's noise (parallel_GPLVM.py:182-187) as driver.init_statistics does."""
+        reference's noise (parallel_GPLVM.py:182-187) as driver.init_statistics does.
+        ``method='greedy'``: the greedy conditional-variance selection instead (gparml_amd.init.greedy_select on the engines; keyword arguments
+        sf2 = 1, alpha = ones(Q), tol): (Z (K', Q) of data rows, pivots (K', 2) as (shard, row), the trace after every step)."""
         from . import init
         if self._dist is not None:
             kw.setdefault('dist_group', True if self.group is None else self.group)
-        return init.kmeans(self.engines, self.M if K is None else int(K), **kw)
+        K = self.M if K is None else int(K)
+        if method == 'greedy':
+            return init.greedy_select(self.engines, K, kw.pop('sf2', 1.0), kw.pop('alpha', np.ones(self.Q)), **kw)
+        assert method == 'kmeans', "init_Z: method must be 'kmeans' or 'greedy', got %r" % (method,)
+        return init.kmeans(self.engines, K, **kw)
 
     def init_X(self):
         """Initial embeddings for this model by PCA over the resident Y of every shard of every rank (gparml_amd.init.pca on the engines, Y = None:

@@ -308,6 +308,41 @@ int gp_infer_latent_rows(gp_ctx* ctx, int64_t n, const double* Y, const uint8_t*
 int gp_kmeans_accumulate(gp_ctx* ctx, int64_t n, const double* X, int K, const double* centres,
                          double* sums, int64_t* counts, double* dist2, int32_t* labels);
 
+/* Greedy conditional-variance selection of the inducing points: the pivoted Cholesky factorisation of K_nn (Burt, Rasmussen and van der Wilk 2019),
+ * the kernel-aware alternative to k-means: one deterministic pass of K steps, every selected point a data row, and after every step the Nystrom
+ * residual tr(K_nn - K_nm K_mm^-1 K_mn) of the points chosen so far -- the quantity the collapsed bound is penalised by.
+ *   k(x, z) = sf2 exp(-1/2 sum_q alpha_q (x_q - z_q)^2), the difference first, q ascending with one fused multiply-add per term, the library's exp.
+ *   Start: d_n = sf2.  Step j: the pivot p is the unselected row of largest d, of equal ones the lowest (shard, row); stop before the step when
+ *   d_p <= tol sf2 or j = K.  c_n = (k(x_n, x_p) - sum_{i<j} L_ni L_pi) / sqrt(d_p), i ascending from 0 with one fused multiply-add per term;
+ *   L_nj = c_n; d_n <- d_n - c_n^2 in one fused multiply-add; p is marked and never chosen again; trace_j = sum max(d_n, 0) over the unselected rows.
+ * gp_select_begin builds the context's selection state (an earlier one is freed first): rows X (n,Q) from the host, uploaded in chunks, or
+ *   X == NULL: the resident X_mu (n must equal N_s; GP_ERR_STATE before an upload; it must not be replaced before gp_select_end); sf2 and alpha (Q)
+ *   are arguments because no gp_set_globals can have happened yet.  The factor L is kept on the device, n K doubles: GP_ERR_UNSUPPORTED, naming the
+ *   size, when that exceeds the free bytes gp_memory_info reports -- decided before anything is allocated.
+ * gp_select_run, the one-shard path: enqueues up to `steps` steps (never beyond K in total) with the pivot passed from kernel to kernel on the
+ *   device -- no host round trip per step; the stopping rule raises a device flag that the later steps respect -- and reads back once.
+ *   *n_done steps were made; rows[0 .. n_done) are their pivots, trace[0 .. n_done) the trace after each (both have `steps` entries; trace may be
+ *   NULL).  It may be called again and continues.
+ * gp_select_candidate: what a shard offers to the others: the local best unselected row, its d, its coordinates x (Q) and its row of the factor
+ *   l (steps done so far); x and l may be NULL.  Without an unselected row: *row = -1, *d = -infinity, x and l are not written.
+ * gp_select_apply: one step with the pivot (x_p (Q), l_p (steps done so far), d_p) supplied by the caller; own_row >= 0 marks that local row as
+ *   selected (-1: the pivot is another shard's).  *trace (may be NULL): the local trace after the step.  It runs the update kernel of
+ *   gp_select_run on the same record: the same bits.  The stopping rule is the caller's.
+ * gp_select_end frees the state.
+ * Determinism: a row's L and d depend on that row and on the pivots' data only -- not on the other rows, on the chunking of host rows or on how
+ * the rows are split over shards: the same rows in one context or in several give the same pivots and the same bits of L and d.  Only trace has a
+ * summation order (csrc/select.hip): workgroups of 512 rows, each an LDS tree over its 256 pairs of rows; then thread t of 256 adds the
+ * workgroups t, t + 256, .. in ascending order and a tree adds the threads.  No floating-point atomics.
+ * All five are synchronous at their return and leave the evaluation state untouched: gp_phase2 / gp_finish / gp_predict after them give
+ * bit-identical results.  GP_ERR_STATE for run / candidate / apply / end without a begin, and for an apply after K steps; GP_ERR_BAD_ARG for
+ * n < 0, K < 1, a tol that is negative or not finite, an sf2 that is not positive and finite, a negative or non-finite alpha, non-finite rows,
+ * X == NULL with n != N_s, steps < 0, a d_p that is not positive and finite, an own_row outside -1 .. n - 1.  n = 0 is legal: it finds nothing. */
+int gp_select_begin(gp_ctx* ctx, int64_t n, const double* X /* NULL: the resident X_mu, n == N_s */, int K, double sf2, const double* alpha, double tol);
+int gp_select_run(gp_ctx* ctx, int steps, int32_t* n_done, int64_t* rows, double* trace);
+int gp_select_candidate(gp_ctx* ctx, double* d, int64_t* row, double* x /* (Q) */, double* l /* (steps done) */);
+int gp_select_apply(gp_ctx* ctx, const double* x_p, const double* l_p, double d_p, int64_t own_row /* -1: another shard's */, double* trace);
+int gp_select_end(gp_ctx* ctx);
+
 /* ---- initialisation of the embeddings --------------------------------------------------------------- */
 /* The two device passes of the PCA that turns Y into the starting X_mu: supporting_functions.PCA (supporting_functions.py:102-121) over ALL data
  * (local_MapReduce.py:50-65) in its streaming form -- per shard the column sums and the Gram matrix of the rows shifted by a centre, which add
@@ -440,14 +475,16 @@ int gp_debug_force_staging(int on);
  * training rows k at a time (rounded up to 256), so that a small call spans chunks; 0 restores the defaults.  "infer_patterns", k: a chunk of
  * gp_infer_objective_rows / gp_infer_latent_rows holds at most k distinct patterns (P_cap = k); 0 restores the default.  "paths_rows", k: gp_paths_eval
  * takes its rows k at a time (any k >= 1: the chunk's buffers are padded to 128 rows, the chunk is not; never more than gp_predict's chunk), so that a
- * small call spans chunks; 0 restores the default. */
+ * small call spans chunks; 0 restores the default.  "select_rows", k: gp_select_begin uploads its host rows k at a time (any k >= 1); 0 restores the
+ * default. */
 int gp_debug_set_option(const char* name, int value);
 /* in-place lower Cholesky + inverse of an SPD (n,n) matrix; logdet out; returns GP_ERR_NOT_PD on failure */
 int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double* Ainv, double* logdet);
 /* device-resident timing of the FP64 MFMA GEMM core: `iters` products of the given shape, milliseconds per product (tools/dev_gemm_bench.py) */
 int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int k, int iters, double* ms_out);
 /* raw copy of one of the global step's internal buffers ("Linv", "Inv", "E", "PsiE", "T1", "T2", "dFdK", "Bbar", "Abar", "Bm", "gK", "gs") after a
- * stream synchronisation; n = capacity of out in doubles (tests/devtools/dev_tail_diff.py) */
+ * stream synchronisation; n = capacity of out in doubles (tests/devtools/dev_tail_diff.py).  Between gp_select_begin and gp_select_end also
+ * "select_L", the written columns of the factor [steps done][n rounded up to 64], and "select_d" [n rounded up to 64] (GP_ERR_STATE outside). */
 int gp_debug_peek(gp_ctx* ctx, const char* name, double* out, long n);
 /* the rule the internal matrix products are launched under (csrc/gemm.hip, launch_gemm aborts when it fails: the blocked Cholesky's in-place panel solve raced until
  * round 6): does an operand stored as rows x cols doubles with leading dimension ld, starting at element offset x_off of a buffer, share an element with the result
