@@ -62,6 +62,7 @@ SIGNATURES = {
     'gp_predict_joint': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_predict_sample': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp]),
     'gp_predict_grad': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    'gp_curve_energy': (ctypes.c_int, [_vp, _i64, ctypes.c_int, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_paths_set': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),
     'gp_paths_eval': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_paths_clear': (ctypes.c_int, [_vp]),

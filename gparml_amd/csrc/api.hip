@@ -757,6 +757,18 @@ extern "C" int gp_predict_grad(gp_ctx* c, int64_t n, const double* X, int flags,
   return run_predict_grad(c, (long)n, X, jac, dvar, metric, logdet);
 }
 
+// ---- curve energy (curve.hip) ----
+extern "C" int gp_curve_energy(gp_ctx* c, int64_t n_curves, int T, const double* X, int flags, double* energy, double* seg, double* grad) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (flags != 0) return fail(c, GP_ERR_BAD_ARG, "gp_curve_energy: flags is reserved and must be 0 (got %d)", flags);
+  if (T < 2) return fail(c, GP_ERR_BAD_ARG, "gp_curve_energy: a curve has at least two points (T = %d)", T);
+  if (n_curves > INT64_MAX / ((int64_t)T * c->Q)) return fail(c, GP_ERR_BAD_ARG, "gp_curve_energy: n_curves T Q overflows");
+  bool nothing;
+  GP_TRY(joint_check(c, "gp_curve_energy", n_curves * T, X, 0, INT64_MAX, &nothing));
+  if (nothing || (!energy && !seg && !grad)) return GP_OK;
+  return run_curve_energy(c, (long)n_curves, T, X, energy, seg, grad);
+}
+
 // ---- pathwise posterior draws (paths.hip) ----
 static bool all_finite(const double* x, size_t n);      // below, with the PCA entries
 
@@ -1272,6 +1284,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "infer_patterns")) { g_opt_inf_patterns.store(std::max(0, value)); return GP_OK; }
   // and the rows per chunk of gp_paths_eval (paths.hip, 0 = the default)
   if (!std::strcmp(name, "paths_rows")) { g_opt_paths_rows.store(std::max(0, value)); return GP_OK; }
+  // and the curves per chunk of gp_curve_energy (curve.hip, 0 = the default)
+  if (!std::strcmp(name, "curve_curves")) { g_opt_curve_curves.store(std::max(0, value)); return GP_OK; }
   // and the host rows per upload chunk of gp_select_begin (select.hip, 0 = the default)
   if (!std::strcmp(name, "select_rows")) { g_opt_sel_rows.store(std::max(0, value)); return GP_OK; }
   std::string known;

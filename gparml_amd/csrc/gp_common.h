@@ -101,6 +101,7 @@ struct JointPlan;  // joint.hip
 struct GradPlan;   // grad.hip
 struct PathsPlan;  // paths.hip
 struct SelPlan;    // select.hip
+struct CurvePlan;  // curve.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -113,6 +114,7 @@ struct JointPlanDelete { void operator()(JointPlan* p) const; };
 struct GradPlanDelete { void operator()(GradPlan* p) const; };
 struct PathsPlanDelete { void operator()(PathsPlan* p) const; };
 struct SelPlanDelete { void operator()(SelPlan* p) const; };
+struct CurvePlanDelete { void operator()(CurvePlan* p) const; };
 
 }  // namespace gp
 
@@ -277,6 +279,7 @@ struct gp_ctx {
   std::unique_ptr<gp::GradPlan, gp::GradPlanDelete> grad;     // gp_predict_grad's buffers (grad.hip)
   std::unique_ptr<gp::PathsPlan, gp::PathsPlanDelete> paths;  // gp_paths_set's draws and gp_paths_eval's buffers (paths.hip)
   std::unique_ptr<gp::SelPlan, gp::SelPlanDelete> sel;        // gp_select_begin's state: rows, factor, conditional variances (select.hip)
+  std::unique_ptr<gp::CurvePlan, gp::CurvePlanDelete> curve;  // gp_curve_energy's buffers (curve.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -341,9 +344,11 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
 // gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
 // Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed; big: both products on the
 // 128 x 128-tile kernel whatever the chunk's size, so that a row's bits do not depend on the rows around it -- paths.hip); the chunk's mean rows;
-// the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them)
+// the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them) and that chunk's inputs [cnt][Q] as the
+// caller gave them (curve.hip differences them before the centring rounds them)
 int pred_chunk_plan(gp_ctx* c, long* rows);
 const double* pred_chunk_psi1(const gp_ctx* c);
+const double* pred_chunk_inputs(const gp_ctx* c);
 int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big = 0);
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
 // joint.hip
@@ -356,6 +361,8 @@ bool paths_plan_current(gp_ctx* c);                                  // a plan o
 int run_paths_eval(gp_ctx* c, long n, const double* X, double* out, double* mean);
 // grad.hip
 int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dvar, double* metric, double* logdet);
+// curve.hip
+int run_curve_energy(gp_ctx* c, long n_curves, int T, const double* X, double* energy, double* seg, double* grad);
 // infer.hip
 int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int n_cols, double* X_mu, double* X_S, int raw, int max_iters, double gtol,
               double* L, double* grad_mu, double* grad_S, int* iters);
@@ -406,6 +413,7 @@ extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // pre
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
 extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval
 extern std::atomic<int> g_opt_sel_rows;                       // select.hip: host rows per upload chunk of gp_select_begin
+extern std::atomic<int> g_opt_curve_curves;                   // curve.hip: curves per chunk of gp_curve_energy
 extern std::atomic<int> g_opt_inf_patterns;                   // infer.hip: distinct patterns per chunk of gp_infer_*_rows
 // layout of the free-embedding LE table (csrc/psi2.hip, b_le_kernel): four points interleaved up to the 16-wide latent tables, point-major beyond
 __host__ __device__ constexpr bool le_interleaved(int QT) { return QT <= 16; }

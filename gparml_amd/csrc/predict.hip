@@ -292,6 +292,7 @@ int pred_chunk_plan(gp_ctx* c, long* rows) {
 }
 
 const double* pred_chunk_psi1(const gp_ctx* c) { return c->pred->P1; }
+const double* pred_chunk_inputs(const gp_ctx* c) { return c->pred->in; }
 
 // the mean rows [cnt][D] of the chunk pred_chunk_front has just run, out of G into a device buffer of the caller
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {

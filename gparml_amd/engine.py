@@ -377,6 +377,31 @@ class ShardEngine(object):
         self._ck(self.lib.gp_predict_grad(self.h, n, px, 0, p('jac'), p('dvar'), p('metric'), p('logdet')), 'gp_predict_grad')
         return out
 
+    # ---- energy of curves through latent space (gp_curve_energy) ----------------------------------------------
+    def curve_energy(self, X, want_energy=True, want_segments=False, want_grad=True):
+        """Expected energy of discrete curves X (n_curves, T, Q) -- or one curve (T, Q) -- under the posterior of f, after a successful global
+        step as ``predict``.  Returns a dict of the requested arrays: ``energy`` (n_curves,) 1/2 (T - 1) sum_s seg_s, ``seg`` (n_curves, T - 1)
+        the expected squared length E|f(x_{s+1}) - f(x_s)|^2 of every segment, ``grad`` (n_curves, T, Q) the derivative of ``energy`` with respect
+        to the curve's points (one curve: without the leading axis).  A curve's values are the same bits alone and in any batch.  The noise
+        enters nowhere.  The evaluation state is left untouched."""
+        X = np.asarray(X, dtype=np.float64)
+        single = X.ndim == 2
+        if single:
+            X = X[None]
+        assert X.ndim == 3 and X.shape[2] == self.Q and X.shape[1] >= 2, 'X shape %s: (n_curves, T >= 2, %d) expected' % (X.shape, self.Q)
+        X, px = _lib.as_c(X)
+        n, T = X.shape[0], X.shape[1]
+        out = {}
+        if want_energy:
+            out['energy'] = np.empty(n)
+        if want_segments:
+            out['seg'] = np.empty((n, T - 1))
+        if want_grad:
+            out['grad'] = np.empty((n, T, self.Q))
+        p = lambda k: out[k].ctypes.data_as(_lib._dp) if k in out else None
+        self._ck(self.lib.gp_curve_energy(self.h, n, T, px, 0, p('energy'), p('seg'), p('grad')), 'gp_curve_energy')
+        return {k: v[0] for k, v in out.items()} if single else out
+
     # ---- latent inference for new rows (gp_infer_objective, gp_infer_latent) ---------------------------------
     def _infer_args(self, Y, X_mu, X_S, cols):
         Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))

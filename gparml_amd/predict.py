@@ -55,6 +55,47 @@ class PathDraws(object):
         self.close()
 
 
+def straight_curves(x0, x1, T):
+    """The equally spaced straight lines (n, T, Q) from the rows of x0 to the rows of x1 (n, Q); the endpoints carry the given bits."""
+    x0, x1 = numpy.atleast_2d(numpy.asarray(x0, dtype=float)), numpy.atleast_2d(numpy.asarray(x1, dtype=float))
+    assert x0.shape == x1.shape and x0.ndim == 2 and int(T) >= 2, 'x0 %s, x1 %s: two (n, Q) arrays and T >= 2 expected' % (x0.shape, x1.shape)
+    t = (numpy.arange(int(T)) / (int(T) - 1.0))[None, :, None]
+    X = x0[:, None, :] + t * (x1 - x0)[:, None, :]
+    X[:, 0], X[:, -1] = x0, x1
+    return X
+
+
+def minimise_curves(energy_and_grad, X, iterations=200, gtol=1e-6):
+    """Minimise the sum of the energies of the discrete curves X (n, T, Q) over their interior points, the endpoints held fixed, with
+    scipy's L-BFGS-B.  ``energy_and_grad(X) -> (energy (n,), grad (n, T, Q))`` is called once per function evaluation with all curves (the
+    device's ShardEngine.curve_energy, or a numpy reference).  Stops after ``iterations`` iterations or when the largest gradient component
+    falls to ``gtol``.  Returns (X, info): the curves, and ``evaluations``, ``energy0`` (the energies at the start) and scipy's ``message``."""
+    import scipy.optimize
+    X = numpy.array(X, dtype=float, order='C')
+    assert X.ndim == 3 and X.shape[1] >= 2, 'X shape %s: (n, T >= 2, Q) expected' % (X.shape,)
+    info = {'evaluations': 0, 'energy0': None, 'message': 'nothing to optimise'}
+
+    def fun(v):
+        Y = X.copy()
+        Y[:, 1:-1] = v.reshape(Y[:, 1:-1].shape)
+        e, g = energy_and_grad(Y)
+        e, g = numpy.asarray(e, dtype=float), numpy.asarray(g, dtype=float)
+        if info['energy0'] is None:
+            info['energy0'] = e.copy()
+        info['evaluations'] += 1
+        return float(numpy.sum(e)), g[:, 1:-1].reshape(-1).copy()
+
+    if X.shape[0] == 0 or X.shape[1] == 2:
+        info['energy0'] = numpy.asarray(energy_and_grad(X)[0], dtype=float)
+        info['evaluations'] = 1
+        return X, info
+    res = scipy.optimize.minimize(fun, X[:, 1:-1].reshape(-1), jac=True, method='L-BFGS-B',
+                                  options={'maxiter': int(iterations), 'gtol': float(gtol), 'ftol': 0.0})
+    X[:, 1:-1] = res.x.reshape(X[:, 1:-1].shape)
+    info['message'] = res.message if isinstance(res.message, str) else res.message.decode()
+    return X, info
+
+
 class Predictor(object):
     def __init__(self, global_statistics, accumulated_statistics, N_train, D, device=0, partial_terms_class=None, engine_class=None):
         """global_statistics: dict Z (M,Q), sf2, alpha, beta; accumulated_statistics: the five base sums of the trained model
@@ -135,6 +176,57 @@ class Predictor(object):
         if self.Q <= 64:
             return numpy.exp(0.5 * self._predict_grad(X, jac=False, dvar=False, metric=False, logdet=True)['logdet'])
         return numpy.exp(0.5 * numpy.linalg.slogdet(self.predict_metric(X))[1])
+
+    def curve_energy(self, X, want_energy=True, want_segments=False, want_grad=True):
+        """Expected energy 1/2 (T - 1) sum_s E|f(x_{s+1}) - f(x_s)|^2 of the discrete curves X (n_curves, T, Q) or (T, Q) under the trained model,
+        its per-segment terms and its gradient with respect to the curve's points: a dict of ``energy``, ``seg``, ``grad`` as requested
+        (ShardEngine.curve_energy)."""
+        eng = self._trained_engine()
+        try:
+            return eng.curve_energy(X, want_energy=want_energy, want_segments=want_segments, want_grad=want_grad)
+        finally:
+            eng.close()
+
+    @staticmethod
+    def _length(seg):
+        return numpy.sqrt(numpy.maximum(seg, 0.0)).sum(axis=-1)
+
+    def curve_length(self, X):
+        """The expected length sum_s sqrt(E|f(x_{s+1}) - f(x_s)|^2) of the discrete curves X (n_curves, T, Q) or (T, Q), from ``curve_energy``'s
+        segments."""
+        return self._length(self.curve_energy(X, want_energy=False, want_segments=True, want_grad=False)['seg'])
+
+    def geodesic(self, x0, x1, T=32, X0=None, iterations=200, gtol=1e-6):
+        """The discrete geodesics of T points between the latent points x0 and x1 ((Q,) or, batched, (n, Q)) under the expected metric of the
+        trained model: the curves that minimise ``curve_energy`` with their endpoints held fixed (``minimise_curves``: L-BFGS-B on the host, one
+        device call per function evaluation for all curves), started from the equally spaced straight lines or from ``X0`` (n, T, Q), whose
+        end points are replaced by x0 and x1.  A curve whose energy did not fall keeps its start.  Returns a dict: ``curves`` (n, T, Q),
+        ``energy`` (n,) and ``length`` (n,) from a final ``curve_energy`` call at the returned curves, and ``evaluations`` (a single pair:
+        without the leading axis).  A local minimiser: curves between distant points may need a better start than the straight line."""
+        single = numpy.asarray(x0).ndim == 1
+        X = straight_curves(x0, x1, T)
+        if X0 is not None:
+            X0 = numpy.asarray(X0, dtype=float).reshape((-1,) + X.shape[1:])
+            assert X0.shape == X.shape, 'X0 shape %s: %s expected' % (X0.shape, X.shape)
+            X[:, 1:-1] = X0[:, 1:-1]
+        eng = self._trained_engine()
+        try:
+            def f(Y):
+                out = eng.curve_energy(Y)
+                return out['energy'], out['grad']
+            Xs, info = minimise_curves(f, X, iterations=iterations, gtol=gtol)
+            out = eng.curve_energy(Xs, want_segments=True, want_grad=False)
+            worse = ~(out['energy'] <= info['energy0'])
+            if worse.any():
+                Xs[worse] = X[worse]
+                out = eng.curve_energy(Xs, want_segments=True, want_grad=False)
+        finally:
+            eng.close()
+        res = {'curves': Xs, 'energy': out['energy'], 'length': self._length(out['seg'])}
+        if single:
+            res = {k: v[0] for k, v in res.items()}
+        res['evaluations'] = info['evaluations']
+        return res
 
     def _trained_engine(self):
         """An engine that holds the trained model: the globals, the stored accumulated statistics of the training data and a global step on them."""

@@ -212,6 +212,28 @@ int gp_predict_sample(gp_ctx* ctx, int64_t n, const double* X, int flags, double
  * gp_finish / gp_predict / gp_predict_joint after it give bit-identical results.  Not covered: uncertain inputs, second derivatives. */
 int gp_predict_grad(gp_ctx* ctx, int64_t n, const double* X, int flags, double* jac, double* dvar, double* metric, double* logdet);
 
+/* Expected energy of discrete curves through latent space under the posterior of f, its per-segment terms and its gradient with respect to the
+ * curve's points, at deterministic inputs, after a successful global step as gp_predict (csrc/curve.hip).  X (n_curves,T,Q):
+ * n_curves curves of T >= 2 points x_0 .. x_{T-1} each.  With k_s = psi1(x_s), dk_s = k_{s+1} - k_s, dx_s = x_{s+1} - x_s, kappa_s = k(x_s, x_{s+1}),
+ * [dmu_s | da_s | db_s] = [dk_s^T W | Lk^-1 dk_s | La^-1 dk_s] and the D outputs independent with gp_predict_joint's covariance:
+ *   seg[c][s]     = E|f(x_{s+1}) - f(x_s)|^2 = |dmu_s|^2 + D (|db_s|^2 - |da_s|^2) + 2 D (sf2 - kappa_s)            (n_curves,T-1)
+ *   energy[c]     = 1/2 (T - 1) sum_s seg[c][s], s ascending  (1/2 int |c'|^2 dt on [0,1] with step 1/(T-1))            (n_curves)
+ *   grad[c][t][q] = d energy[c] / d x_tq = (T - 1) [(g_{t-1} - g_t) . dk_t,q + D alpha_q (kappa_{t-1} dx_{t-1,q} - kappa_t dx_{t,q})]   (n_curves,T,Q)
+ * with g_s = W dmu_s - D (Lk^-T da_s - La^-T db_s), g_{-1} = g_{T-1} = 0, and dk_t,q = -alpha_q (x_tq - z_q) o k_t as in gp_predict_grad.  The
+ * expected length of a curve is sum_s sqrt(max(seg[c][s], 0)).  dk_s and sf2 - kappa_s are formed through expm1 of the exponents' difference, never
+ * as a difference of two exponentials, and dx_s from the inputs as given: a curve of any fineness keeps its digits and a repeated point gives
+ * seg = 0 exactly.  The noise enters nowhere: flags is reserved and must be 0.  Any output may be NULL; a subset gives the bits of the full call.
+ * A curve's outputs are the same bits alone, in any batch, in any curve order and wherever a chunk boundary falls; bit-identical from run to run
+ * (fixed summation order that depends on M, Q, D and T alone, no floating-point atomics).  Chunks hold whole curves, max(1, R / T) of them with R
+ * the points of gp_predict's chunk (64 MB / (8 (Dp + 2 Mp)) rounded down to a multiple of 128, at least 128 and at most 16384; Mp, Dp = M, D rounded
+ * up to 128): GP_ERR_UNSUPPORTED for T > R (M = 512, D = 100: T <= 7168) -- split the curve.  Preconditions, state rule and argument errors are
+ * gp_predict_grad's: GP_ERR_STATE unless the last global step succeeded on the statistics and globals as they are now; GP_ERR_BAD_ARG, decided before
+ * anything is launched, for n_curves < 0, T < 2, flags != 0, a NULL X with n_curves > 0 or a non-finite X; n_curves = 0 writes nothing.  Synchronous.
+ * The evaluation state is left untouched: gp_phase2 / gp_finish / gp_predict* after it give bit-identical results.  Not covered: uncertain inputs,
+ * second derivatives, an optimiser on the device (the geodesic solve is host-side: gparml_amd.predict.Predictor.geodesic). */
+int gp_curve_energy(gp_ctx* ctx, int64_t n_curves, int T, const double* X /*(n_curves,T,Q)*/, int flags, double* energy /*(n_curves)*/,
+                    double* seg /*(n_curves,T-1)*/, double* grad /*(n_curves,T,Q)*/);
+
 /* Pathwise posterior function draws: n_draws sampled functions that can be evaluated at any number of new deterministic inputs, in any number of
  * calls, each call evaluating the SAME functions (Matheron's rule on a random Fourier prior; csrc/paths.hip).  The work of an
  * evaluation is linear in n, O(n (F + M) n_draws D); no n x n matrix is formed and n has no limit.
