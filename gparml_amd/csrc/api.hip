@@ -708,6 +708,43 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   return run_predict(c, (long)n, X_mu, X_S, xs_is_raw, flags, mean, var);
 }
 
+// ---- held-out scoring (score.hip): gp_predict's state rule and input checks, then the outputs' own ----
+extern "C" int gp_predict_score(gp_ctx* c, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, const double* Y, const uint8_t* observed,
+                                int flags, double* row_logp, double* row_sse, double* row_chi2, double* cols) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: n must be >= 0");
+  if (flags & ~3) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: unknown flags %d", flags);
+  if ((flags & 2) && X_mu) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: flags bit 1 (the resident variances) needs X_mu == NULL (the resident rows)");
+  GP_TRY(model_ready(c, "gp_predict_score"));
+  const size_t D = (size_t)c->D;
+  const bool resident = X_mu == nullptr;
+  if (resident) {      // the resident rows' own rules come first: they hold for every n, n = 0 included
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_predict_score: X_mu is NULL (the resident rows) before gp_upload_shard");
+    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is NULL (the resident rows): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
+    if (X_S || xs_is_raw) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is NULL (the resident rows): X_S must be NULL and xs_is_raw 0 (flags bit 1 takes the resident variances)");
+  }
+  if (n == 0) {
+    if (cols) std::fill(cols, cols + 5 * D, 0.0);
+    return GP_OK;
+  }
+  if (!resident) {
+    if (!Y) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: Y is NULL with host inputs");
+    const size_t nq = (size_t)n * c->Q;
+    for (size_t i = 0; i < nq; ++i) {
+      if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is not finite");
+      if (X_S && (!std::isfinite(X_S[i]) || (!xs_is_raw && X_S[i] < 0.0))) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_S must be finite and >= 0");
+    }
+  }
+  if (Y) {
+    for (int64_t i = 0; i < n; ++i)
+      for (size_t j = 0; j < D; ++j)
+        if ((!observed || observed[i * D + j]) && !std::isfinite(Y[i * D + j]))       // a hidden entry is never read
+          return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: Y is not finite in an observed entry (row %ld, column %zu)", (long)i, j);
+  }
+  if (!row_logp && !row_sse && !row_chi2 && !cols) return GP_OK;
+  return run_predict_score(c, (long)n, X_mu, X_S, xs_is_raw ? 1 : 0, resident, (flags & 2) != 0, Y, observed, flags, row_logp, row_sse, row_chi2, cols);
+}
+
 // gp_predict_joint / gp_predict_sample: gp_predict's preconditions and argument errors for deterministic inputs, then the size limit
 static int joint_check(gp_ctx* c, const char* who, int64_t n, const double* X, int flags, int64_t n_max, bool* nothing) {
   *nothing = true;

@@ -102,6 +102,7 @@ struct GradPlan;   // grad.hip
 struct PathsPlan;  // paths.hip
 struct SelPlan;    // select.hip
 struct CurvePlan;  // curve.hip
+struct ScorePlan;  // score.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -115,6 +116,7 @@ struct GradPlanDelete { void operator()(GradPlan* p) const; };
 struct PathsPlanDelete { void operator()(PathsPlan* p) const; };
 struct SelPlanDelete { void operator()(SelPlan* p) const; };
 struct CurvePlanDelete { void operator()(CurvePlan* p) const; };
+struct ScorePlanDelete { void operator()(ScorePlan* p) const; };
 
 }  // namespace gp
 
@@ -280,6 +282,7 @@ struct gp_ctx {
   std::unique_ptr<gp::PathsPlan, gp::PathsPlanDelete> paths;  // gp_paths_set's draws and gp_paths_eval's buffers (paths.hip)
   std::unique_ptr<gp::SelPlan, gp::SelPlanDelete> sel;        // gp_select_begin's state: rows, factor, conditional variances (select.hip)
   std::unique_ptr<gp::CurvePlan, gp::CurvePlanDelete> curve;  // gp_curve_energy's buffers (curve.hip)
+  std::unique_ptr<gp::ScorePlan, gp::ScorePlanDelete> score;  // gp_predict_score's buffers (score.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -346,11 +349,22 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
 // 128 x 128-tile kernel whatever the chunk's size, so that a row's bits do not depend on the rows around it -- paths.hip); the chunk's mean rows;
 // the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them) and that chunk's inputs [cnt][Q] as the
 // caller gave them (curve.hip differences them before the centring rounds them)
-int pred_chunk_plan(gp_ctx* c, long* rows);
+int pred_chunk_plan(gp_ctx* c, long* rows, bool uncertain = false);
 const double* pred_chunk_psi1(const gp_ctx* c);
 const double* pred_chunk_inputs(const gp_ctx* c);
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big = 0);
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big = 0, int dev = 0);
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
+// gp_predict's own chunk buffers, for the path that scores a chunk where it lies (score.hip): the centred inputs [rows][Q] (what gp_predict passes as
+// mu), the products G [rows][Dp + 2 Mp] = [mean | Lk^-1 k* | La^-1 k*] and the variance buffer [rows][D]; and the uncertain-input variance in its two
+// steps: B = Ki - P once per call, then per chunk LEA and pred_psi2w_kernel into var [cnt][D] (the plan built with uncertain = true)
+double* pred_chunk_mu(const gp_ctx* c);
+double* pred_chunk_products(const gp_ctx* c);
+double* pred_chunk_var(const gp_ctx* c);
+int pred_unc_begin(gp_ctx* c);
+int pred_chunk_var_unc(gp_ctx* c, long cnt, double noise, double* var);
+// score.hip
+int run_predict_score(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, bool resident, bool resident_S, const double* Y,
+                      const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* cols);
 // joint.hip
 int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
 int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);

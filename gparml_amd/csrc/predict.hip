@@ -264,17 +264,20 @@ const double* pred_debug_lea(const gp_ctx* c, long* n) {
 
 // One chunk of points through the front of the pipeline: upload, pred_prep_kernel, Psi1*, the mean product into the chunk's G and (fac != NULL) the
 // two inverse-factor products [Lk^-1 k* | La^-1 k*] into fac (leading dimension ldf).  gp_predict keeps the centred inputs and the factor rows in
-// the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big) {
+// the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.  dev: X_mu and X_S are
+// device arrays (the resident rows, score.hip) and go to pred_prep_kernel as they are: nothing is uploaded and nothing is staged.
+int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big, int dev) {
   const PredPlan& p = *c->pred;
   const bool unc = X_S != nullptr;
   const PredUnc* u = p.unc.get();
   hipStream_t st = c->stream;
   const long R = p.rows, Mp = c->Mp, Dp = c->Dp, Q = c->Q, rows = round_up(cnt, TILE);
-  double* xin = p.in;
-  double* sin = p.in + R * Q;
-  GP_HIP(c, hipMemcpyAsync(xin, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-  if (unc) GP_HIP(c, hipMemcpyAsync(sin, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+  const double* xin = dev ? X_mu + n0 * Q : p.in.get();
+  const double* sin = dev ? (unc ? X_S + n0 * Q : nullptr) : p.in + R * Q;
+  if (!dev) {
+    GP_HIP(c, hipMemcpyAsync(p.in, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+    if (unc) GP_HIP(c, hipMemcpyAsync(p.in + R * Q, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+  }
   GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, c->shift, cnt,
             rows, (int)Q, c->sf2, mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
   GP_TRY_RC(launch_psi1_rows(c, mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
@@ -284,15 +287,18 @@ int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, 
   return GP_OK;
 }
 
-// the chunk plan for deterministic inputs (built on first use) and its rows per chunk
-int pred_chunk_plan(gp_ctx* c, long* rows) {
-  GP_TRY_RC(pred_alloc(c, false));
+// the chunk plan (built on first use; uncertain: with the buffers of the uncertain-input variance) and its rows per chunk
+int pred_chunk_plan(gp_ctx* c, long* rows, bool uncertain) {
+  GP_TRY_RC(pred_alloc(c, uncertain));
   *rows = c->pred->rows;
   return GP_OK;
 }
 
 const double* pred_chunk_psi1(const gp_ctx* c) { return c->pred->P1; }
 const double* pred_chunk_inputs(const gp_ctx* c) { return c->pred->in; }
+double* pred_chunk_mu(const gp_ctx* c) { return c->pred->mu; }
+double* pred_chunk_products(const gp_ctx* c) { return c->pred->G; }
+double* pred_chunk_var(const gp_ctx* c) { return c->pred->out + c->pred->rows * c->D; }
 
 // the mean rows [cnt][D] of the chunk pred_chunk_front has just run, out of G into a device buffer of the caller
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
@@ -302,22 +308,47 @@ int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
   return GP_OK;
 }
 
+// uncertain inputs, once per call before the first chunk: B = Ki - P of the model as it is now
+int pred_unc_begin(gp_ctx* c) {
+  const long Mp = c->Mp;
+  GP_LAUNCH(c, c->stream, pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, c->gstep.Inv, c->M, c->Mp,
+            c->pred->unc->B);
+  return GP_OK;
+}
+
+// the variances [cnt][D] of the chunk pred_chunk_front has just run with uncertain inputs (the plan built with them, pred_unc_begin called), into var
+int pred_chunk_var_unc(gp_ctx* c, long cnt, double noise, double* var) {
+  const PredPlan& p = *c->pred;
+  const PredUnc* u = p.unc.get();
+  hipStream_t st = c->stream;
+  const long Mp = c->Mp, Dp = c->Dp, M = c->M, Q = c->Q, D = c->D, ldg = Dp + 2 * Mp, rows = round_up(cnt, TILE);
+  LeaRows t;
+  t.mu = p.mu; t.w = u->W; t.v2 = u->V2; t.ld = Q; t.lnc2h = u->lnc2; t.ldl = 1; t.Z = c->Z; t.ldz = Q; t.Q = (int)Q;
+  t.cnt = cnt; t.rows = rows; t.M = (int)M; t.Mp = (int)Mp; t.mask = nullptr; t.LE = nullptr; t.LEA = u->LEA;
+  GP_TRY_RC(launch_lea_rows(c, st, t));
+  PsiWArgs a;
+  a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->gstep.E; a.B = u->B; a.G = p.G; a.ldg = ldg;
+  a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = var;
+  const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
+  // the latent width the kernel keeps in registers: 16, 64, or (0) a run-time Q beyond
+  GP_TRY_RC((for_width<16, 64, 0>(c, "predictive variance kernel", Q <= 16 ? 16 : Q <= 64 ? 64 : 0,
+                                  [&](auto W) -> int { GP_LAUNCH(c, st, pred_psi2w_kernel<W()>, grid, dim3(256), 0, a); return GP_OK; })));
+  return GP_OK;
+}
+
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {
   const bool unc = X_S != nullptr;
   GP_TRY_RC(pred_alloc(c, unc));
   const PredPlan& p = *c->pred;
-  const PredUnc* u = p.unc.get();      // NULL for deterministic inputs (unless an earlier call built it)
   hipStream_t st = c->stream;
-  const long R = p.rows, Mp = c->Mp, Dp = c->Dp, M = c->M, Q = c->Q, D = c->D;
+  const long R = p.rows, Mp = c->Mp, Dp = c->Dp, M = c->M, D = c->D;
   const long ldg = Dp + 2 * Mp;
   const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
-  if (unc && var) {
-    GP_LAUNCH(c, st, pred_bmat_kernel, dim3((unsigned)std::min<long>((Mp * Mp + 255) / 256, 4096)), dim3(256), 0, c->gstep.Inv, (int)M, (int)Mp, u->B);
-  }
+  if (unc && var) GP_TRY_RC(pred_unc_begin(c));
   double* out_mean = p.out;
   double* out_var = p.out + R * D;
   for (long n0 = 0; n0 < n; n0 += R) {
-    const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
+    const long cnt = std::min(R, n - n0);
     GP_TRY_RC(pred_chunk_front(c, X_mu, X_S, raw, n0, cnt, p.mu, !unc && var ? p.G + Dp : nullptr, ldg));
     if (!unc) {
       GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
@@ -331,17 +362,7 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
         GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
       if (var) {
-        LeaRows t;
-        t.mu = p.mu; t.w = u->W; t.v2 = u->V2; t.ld = Q; t.lnc2h = u->lnc2; t.ldl = 1; t.Z = c->Z; t.ldz = Q; t.Q = (int)Q;
-        t.cnt = cnt; t.rows = rows; t.M = (int)M; t.Mp = (int)Mp; t.mask = nullptr; t.LE = nullptr; t.LEA = u->LEA;
-        GP_TRY_RC(launch_lea_rows(c, st, t));
-        PsiWArgs a;
-        a.LEA = u->LEA; a.V2 = u->V2; a.Z = c->Z; a.E = c->gstep.E; a.B = u->B; a.G = p.G; a.ldg = ldg;
-        a.M = (int)M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = (int)D; a.Dp = (int)Dp; a.sf2 = c->sf2; a.beta = c->beta; a.noise = noise; a.var = out_var;
-        const dim3 grid((unsigned)cnt, (unsigned)((D + PW_DW - 1) / PW_DW));
-        // the latent width the kernel keeps in registers: 16, 64, or (0) a run-time Q beyond
-        GP_TRY_RC((for_width<16, 64, 0>(c, "predictive variance kernel", Q <= 16 ? 16 : Q <= 64 ? 64 : 0,
-                                        [&](auto W) -> int { GP_LAUNCH(c, st, pred_psi2w_kernel<W()>, grid, dim3(256), 0, a); return GP_OK; })));
+        GP_TRY_RC(pred_chunk_var_unc(c, cnt, noise, out_var));
         GP_HIP(c, hipMemcpyAsync(var + n0 * D, out_var, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
       }
     }

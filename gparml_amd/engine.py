@@ -281,6 +281,77 @@ class ShardEngine(object):
                                      var.ctypes.data_as(_lib._dp)), 'gp_predict')
         return mean, var
 
+    # ---- held-out scoring (gp_predict_score) ---------------------------------------------------------------------
+    @staticmethod
+    def score_summary(cols):
+        """The figures of ``score`` from the column sums ``cols`` (D, 5) = [count, sum e, sum e^2, sum e^2 / v, sum logp] (those of several shards
+        add first): count, bias = sum e / count, rmse = sqrt(sum e^2 / count), chi2_mean = sum e^2 / v / count and nlpd = -sum logp / count, each
+        per column (D,) and, under ``pooled``, over all columns; a column (or a pool) without a scored entry gives NaN."""
+        cols = np.asarray(cols, dtype=np.float64)
+
+        def figures(s):
+            with np.errstate(invalid='ignore', divide='ignore'):
+                cnt = np.where(s[..., 0] > 0, s[..., 0], np.nan)
+                return dict(count=s[..., 0], bias=s[..., 1] / cnt, rmse=np.sqrt(s[..., 2] / cnt), chi2_mean=s[..., 3] / cnt, nlpd=-s[..., 4] / cnt)
+        out = figures(cols)
+        out['cols'] = cols
+        out['pooled'] = figures(cols.sum(axis=0))
+        return out
+
+    def score(self, Y, X_mu=None, X_S=None, observed=None, include_noise=True, xs_is_raw=False, use_resident_S=False, want_rows=True):
+        """Scores the outputs ``Y`` (n, D) under ``predict``'s mean and variance at the same inputs, on the device (gp_predict_score): per observed
+        entry the Gaussian log density logp = -1/2 ln(2 pi v) - e^2 / (2 v), e = y - mean (uncertain inputs: of the moment-matched Gaussian).
+        ``observed`` (n, D): non-zero where Y is scored; None: where Y is not NaN; the other entries are never read.  ``include_noise`` scores y
+        (variance + 1/beta), the held-out convention; without it f.
+        ``X_mu`` None scores the engine's resident rows at their base means -- with ``use_resident_S`` at their base variances as well -- and ``Y``
+        None then means the resident Y: nothing of size n x D crosses the bus.
+        Returns a dict: ``row_logp``, ``row_sse``, ``row_chi2`` (n,) (None without ``want_rows``), ``cols`` (D, 5) the column sums [count, sum e,
+        sum e^2, sum e^2 / v, sum logp], and from them on the host ``count``, ``bias``, ``rmse``, ``chi2_mean``, ``nlpd`` per column (D,) and
+        ``pooled`` (a dict of the same five over all columns).  FloatingPointError when a scored variance is not > 0 (possible without the noise)."""
+        pm = ps = py = po = None
+        flags = 1 if include_noise else 0
+        if X_mu is None:
+            assert X_S is None and not xs_is_raw, 'score: the resident rows take X_S from the engine (use_resident_S)'
+            n = self.N_s
+            if use_resident_S:
+                flags |= 2
+        else:
+            assert not use_resident_S, 'score: use_resident_S needs the resident rows (X_mu None)'
+            assert Y is not None, 'score: Y is needed with host inputs'
+            X_mu = np.atleast_2d(np.asarray(X_mu, dtype=np.float64))
+            assert X_mu.ndim == 2 and X_mu.shape[1] == self.Q, 'X_mu shape %s: (n, %d) expected' % (X_mu.shape, self.Q)
+            n = X_mu.shape[0]
+            X_mu, pm = _lib.as_c(X_mu)
+            if X_S is not None:
+                X_S = np.atleast_2d(np.asarray(X_S, dtype=np.float64))
+                assert X_S.shape == X_mu.shape, 'X_S shape %s != X_mu shape %s' % (X_S.shape, X_mu.shape)
+                X_S, ps = _lib.as_c(X_S)
+        if Y is not None:
+            Y = np.asarray(Y, dtype=np.float64)
+            Y = Y[:, None] if Y.ndim == 1 else Y
+            assert Y.shape == (n, self.D), 'Y shape %s: (%d, %d) expected' % (Y.shape, n, self.D)
+            Y, py = _lib.as_c(Y)
+            if observed is None and np.isnan(Y).any():
+                observed = ~np.isnan(Y)
+        if observed is not None:
+            observed = np.ascontiguousarray(np.atleast_2d(np.asarray(observed)) != 0, dtype=np.uint8)
+            assert observed.shape == (n, self.D), 'observed shape %s: (%d, %d) expected' % (observed.shape, n, self.D)
+            po = observed.ctypes.data_as(_lib._u8p)
+        rows = [np.empty(n) for _ in range(3)] if want_rows else [None] * 3
+        cols = np.empty((self.D, 5))
+        dp = lambda a: a.ctypes.data_as(_lib._dp) if a is not None else None          # noqa: E731
+        rc = self.lib.gp_predict_score(self.h, n, pm, ps, 1 if xs_is_raw else 0, py, po, flags, dp(rows[0]), dp(rows[1]), dp(rows[2]), dp(cols))
+        if rc != _lib.GP_ERR_NON_FINITE:
+            self._ck(rc, 'gp_predict_score')
+        out = self.score_summary(cols)
+        out['row_logp'], out['row_sse'], out['row_chi2'] = rows
+        try:
+            self._ck(rc, 'gp_predict_score')
+        except FloatingPointError as err:
+            err.result = out            # every row but the named ones is valid: NaN marks the rows and columns of the bad variances
+            raise
+        return out
+
     # ---- joint prediction (gp_predict_joint, gp_predict_sample) ------------------------------------------------
     def _joint_X(self, X):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))

@@ -123,9 +123,11 @@ def evaluate(engines, reduce=None, want_embedding_grads=False, for_each=_each):
             mask = r.mask
 
 
-def refresh_statistics(engines, reduce):
-    """Bring the root engine's global step up to date without an evaluation (predict, infer): phase 1, the reduce, the root's global step."""
+def refresh_statistics(engines, reduce, all_engines=False):
+    """Bring the root engine's global step up to date without an evaluation (predict, infer): phase 1, the reduce, the root's global step.
+    ``all_engines``: the reduced statistics go back to every engine and each runs the global step (scoring the resident rows of every shard)."""
     for e in engines:
         e.phase1()
-    reduce('stats', fan_back=False)
-    reduce.root.global_step(sync=True)
+    reduce('stats', fan_back=all_engines)
+    for e in (engines if all_engines else [reduce.root]):
+        e.global_step(sync=True)

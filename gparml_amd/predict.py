@@ -376,6 +376,27 @@ class Predictor(object):
         mean, var = self.predict_outputs(res[0], res[1], include_noise=include_noise)
         return mean, var, res
 
+    def score(self, Y_test, X_mu, X_S=None, observed=None, include_noise=True):
+        """How well the trained model predicts the outputs ``Y_test`` (n, D) from q(x*) = N(X_mu, diag X_S) (X_S None: from the points X_mu): the
+        Gaussian log predictive density and the errors of every observed entry, reduced on the device (ShardEngine.score: the dict of row values
+        ``row_logp`` / ``row_sse`` / ``row_chi2`` and per-column and ``pooled`` ``count``, ``bias``, ``rmse``, ``chi2_mean``, ``nlpd``).
+        ``observed`` (n, D): the entries to score; None: where Y_test is not NaN."""
+        eng = self._trained_engine()
+        try:
+            return eng.score(Y_test, X_mu, X_S, observed=observed, include_noise=include_noise)
+        finally:
+            eng.close()
+
+    def impute_score(self, Y_true, mask, include_noise=True, **infer_args):
+        """The standard missing-data experiment: the rows of ``Y_true`` (n, D) are embedded from the columns ``mask`` alone, as ``impute`` does
+        (``infer``; its keyword arguments pass through), and the model is scored on exactly the entries that were hidden from it and are known:
+        the columns outside ``mask`` where Y_true is not NaN.  Returns (the dict of ``score``, [X_mu, X_S, L])."""
+        Y = numpy.atleast_2d(numpy.asarray(Y_true, dtype=float))
+        res = self.infer(Y, mask=mask, **infer_args)
+        hidden = numpy.ones(Y.shape, dtype=bool)
+        hidden[:, numpy.unique(numpy.asarray(list(mask), dtype=int))] = False
+        return self.score(Y, res[0], res[1], observed=hidden & ~numpy.isnan(Y), include_noise=include_noise), res
+
     def _partial_terms(self):
         if self._pt is None:
             g = self.gs

@@ -128,17 +128,42 @@ class ResidentModel(object):
         Z, _, alpha, _ = split_flat(transform_vec(self._pos, np.asarray(flat_array, dtype=np.float64)), self.M, self.Q)
         return PathDraws(self.engines[0], Z, alpha, n_draws, n_features=n_features, seed=seed)
 
-    def _refresh_statistics(self, flat_array):
+    def score_training(self, use_S=True, flat_array=None, include_noise=True, want_rows=True):
+        """Scores the training rows where they lie (ShardEngine.score on the resident rows of every shard of this process: per-row fit, outliers,
+        calibration of the predictive variances): the resident Y under the prediction at the resident base means and, with ``use_S``, base
+        variances, for the model at ``flat_array`` (None: the vector of the last evaluation or prediction).  Nothing of size N x D crosses the
+        bus.  Returns the dict of ``ShardEngine.score``: the row values concatenated in shard order, the column sums of the shards added on the
+        host.  Every engine needs the model: unless all of them hold it (the last evaluation was at this vector), phase 1, the reduce and a
+        global step run on all of them first (COLLECTIVE across ranks, as ``predict``); across ranks the caller adds the ranks' ``cols`` and
+        takes ``ShardEngine.score_summary`` of the sum.  A row's values do not depend on how the rows are split over shards as long as every
+        shard's chunks stay on one side of gp_predict_score's kernel threshold (include/gparml_hip.h; 4096 rows per chunk at M = 512); beyond
+        it they agree to rounding."""
+        if flat_array is None:
+            assert self._stats_x is not None, 'score_training: no evaluation or prediction yet: pass flat_array'
+            flat_array = self._stats_x
+        self._refresh_statistics(flat_array, all_engines=True)
+        use_S = bool(use_S) and not self.fixed_embeddings          # fixed embeddings have no variances: the deterministic form, one variance per row
+        parts = [e.score(None, use_resident_S=use_S, include_noise=include_noise, want_rows=want_rows) for e in self.engines]
+        out = ShardEngine.score_summary(sum(p['cols'] for p in parts))
+        for k in ('row_logp', 'row_sse', 'row_chi2'):
+            out[k] = np.concatenate([p[k] for p in parts]) if want_rows else None
+        return out
+
+    _stats_all = False          # every engine holds the model of _stats_x (an evaluation, or a refresh with all_engines), not the root alone
+
+    def _refresh_statistics(self, flat_array, all_engines=False):
+        """Brings the model up to date at ``flat_array`` unless it is: on the root engine, or (``all_engines``) on every engine of this process."""
         flat_array = np.asarray(flat_array, dtype=np.float64)
         last = self._stats_x
         if (last is None or last.shape != flat_array.shape or last.tobytes() != flat_array.tobytes()
-                or self._stats_version != self.version):
+                or self._stats_version != self.version or (all_engines and not self._stats_all and len(self.engines) > 1)):
             Z, sf2, alpha, beta = split_flat(transform_vec(self._pos, flat_array), self.M, self.Q)
             for e in self.engines:
                 e.set_globals(Z, sf2, alpha, beta, N_global=self.N, step_size=0.0)
-            refresh_statistics(self.engines, self._reduce)
+            refresh_statistics(self.engines, self._reduce, all_engines=all_engines)
             self._stats_x = np.array(flat_array, copy=True)
             self._stats_version = self.version
+            self._stats_all = bool(all_engines)
 
     def init_Z(self, K=None, method='kmeans', **kw):
         """Inducing points for this model by k-means over the resident X_mu of every shard of every rank (gparml_amd.init.kmeans on the engines,
@@ -184,6 +209,7 @@ class ResidentModel(object):
         # update of the embeddings -- scg_adapted / gd after an accepted step -- bumps the version: the statistics are then recomputed)
         self._stats_x = np.array(flat_array, dtype=np.float64, copy=True)
         self._stats_version = self.version
+        self._stats_all = True              # every engine ran the replicated global step
         grad = np.concatenate([res['grad_Z'].ravel(), [res['grad_sf2']], res['grad_alpha'], [0.0 if self.fixed_beta else res['grad_beta']]])
         grad = grad * transform_grad_vec(self._pos, flat_array)
         return -res['F'], -grad

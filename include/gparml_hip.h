@@ -178,6 +178,51 @@ int gp_finish(gp_ctx* ctx, double* F, double* grad_Z, double* grad_sf2, double* 
  * GP_ERR_BAD_ARG for n < 0 or a non-finite mean / negative or non-finite variance; n = 0 writes nothing. */
 int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, int flags, double* mean, double* var);
 
+/* Held-out scoring: how well the model predicts given outputs Y (n,D) at the inputs of gp_predict, reduced on the device to one value per row and
+ * five sums per output column (csrc/score.hip).  With m_id and v_id gp_predict's mean and variance at the same inputs and flags
+ * bit 0 (v_id: one value per row for X_S == NULL, one per entry otherwise; bit 0 adds 1/beta exactly as in gp_predict) and e = y_id - m_id, for every
+ * OBSERVED entry:
+ *   logp_id     = -1/2 ln(2 pi v_id) - e^2 / (2 v_id)      computed as e2 = e e, q = e2 / v, logp = -1/2 (ln(2 pi v) + q), each operation rounded once
+ *   row_logp[i] = sum_d logp_id     row_sse[i] = sum_d e^2     row_chi2[i] = sum_d e^2 / v_id                                          (n) each
+ *   cols[d]     = [count_d, sum_i e, sum_i e^2, sum_i e^2 / v_id, sum_i logp_id]                                                       (D,5)
+ * With uncertain inputs this is the density of the MOMENT-MATCHED Gaussian N(m_id, v_id), not of the (non-Gaussian) predictive distribution itself.
+ * observed (n,D) row-major, non-zero = observed, NULL = every entry: an entry of Y with observed == 0 is never read, on the host or on the device,
+ * and may hold NaN; a row with no observed entry is allowed and scores 0.  Any output pointer may be NULL; a subset gives the bits of the full call.
+ * Resident rows: X_mu == NULL scores the context's own rows, as gp_kmeans_accumulate does with X == NULL: n must equal N_s, the inputs are the
+ * resident base means (GP_ARR_X_MU), deterministic unless flags bit 1 is set, which takes the resident base variances as well (in the form they were
+ * uploaded in); X_S must then be NULL and xs_is_raw 0 either way.  Y == NULL then means the resident Y; a host Y (N_s,D) is allowed too.  Nothing of
+ * size n x D crosses the bus in either direction (an optional mask apart).  GP_ERR_STATE when no shard has been uploaded (an engine built from
+ * gp_set_local_statistics alone); flags bit 1 with a non-NULL X_mu is GP_ERR_BAD_ARG.
+ * Everything else is word for word gp_predict's contract: GP_ERR_STATE unless the last global step succeeded on the statistics and globals as they
+ * are now; synchronous; the evaluation state is left untouched, so gp_phase2 / gp_finish / gp_predict* after it give bit-identical results.  n = 0
+ * (host inputs; for the resident rows n = N_s holds first) writes zeros to cols and nothing else.  GP_ERR_BAD_ARG, decided before anything is launched: n < 0, unknown flags, a NULL Y with host inputs and
+ * n > 0, a non-finite observed entry of Y, non-finite X_mu, X_S that is not finite and >= 0 (as gp_predict), resident rows with n != N_s.
+ * A scored entry whose v_id is not > 0 -- var_f at a training input of a nearly noise-free model can round to zero or below, and 1/beta is then
+ * too small to lift it -- gives GP_ERR_NON_FINITE when the call returns: the message names the first such row, that row's three outputs and all
+ * five sums of the columns it is scored in are NaN, every other row's outputs are valid (a device flag written by plain stores: no second pass).
+ * The mean and the variance a row is scored on are gp_predict's bits for that row in a call of the same rows: the same kernels on the same buffers in
+ * the same chunks (rows per chunk: 64 MB / (8 (Dp + 2 Mp)) rounded down to a multiple of 128, at least 128 and at most 16384), so logp formed on the
+ * host from gp_predict's output differs only by the rounding of the division, the logarithm and the sums.  Bit-identical from run to run, no
+ * floating-point atomics.
+ * Row invariance, and its limit.  Keeping gp_predict's bits means keeping gp_predict's choice of matrix-product kernel, which depends on the size of
+ * the launch: a chunk of r rows (rounded up to 128) forms the mean with (r / 128)(Dp / 128) tiles and, for deterministic inputs, the variance's
+ * factors with (r / 128)(2 Mp / 128) tiles; a product of at most 256 tiles runs on the 32 x 32-tile kernel, a larger one on the 128 x 128-tile kernel,
+ * and the two add over the inducing points in different orders.  A row's three outputs are therefore the same bits -- alone, in any batch, in any
+ * row order, on either side of a chunk boundary -- in any two calls that put each of the row's products on the same kernel: always when every
+ * chunk has at most 256 * 128 * 128 / max(Dp, 2 Mp) rows (deterministic; Dp alone for uncertain inputs; 4096 rows at M = 512), and among chunks
+ * beyond that.  Between a small and a large chunk the row's mean and variance agree to the rounding of the products (gp_predict's accuracy), not bit
+ * for bit -- for instance a row alone against the same row in a full chunk of 7168 rows at M = 512, or a short last chunk.  A batch-independent row,
+ * which the other prediction entries obtain by fixing the kernel, and gp_predict's bits cannot both be had; this entry keeps gp_predict's bits.
+ * Summation order (csrc/score.hip).  Rows: a function of D alone -- lane l of a 64-lane wave adds the observed d = l, l + 64, .. in ascending order,
+ * then the lanes are added pairwise at distance 32, 16, .. 1.  Columns: the ORDER is a function of the global row index alone and never of the chunk
+ * size -- the rows are cut into segments of 128 (a chunk is a whole number of them); inside a segment the rows 0 .. 63 and 64 .. 127 are each added
+ * in ascending order and the two halves are added; the segments are then added one by one, in ascending order, into the running total, which starts
+ * at zero.  cols is thus the same bits at every chunk size under which the rows' terms are (the rule above).  Not covered: non-Gaussian or quadrature densities for uncertain inputs, scores of joint (n x n)
+ * predictions, results kept on the device. */
+int gp_predict_score(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, int xs_is_raw, const double* Y /*(n,D)*/,
+                     const uint8_t* observed /*(n,D) or NULL = all*/, int flags, double* row_logp /*(n)*/, double* row_sse /*(n)*/,
+                     double* row_chi2 /*(n)*/, double* cols /*(D,5)*/);
+
 /* Joint posterior at n new deterministic inputs X (n,Q), after a successful global step as gp_predict.  With k_i = psi1(x_i), a_i = Lk^-1 k_i and
  * b_i = La^-1 k_i (Lk, La the Cholesky factors of Kmm and Kmm + beta Psi2):
  *   mean[i][d] = k_i^T W_d (as gp_predict),   cov[i][j] = k(x_i, x_j) - a_i . a_j + b_i . b_j   (one n x n matrix, shared by all D outputs),
