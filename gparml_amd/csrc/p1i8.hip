@@ -11,7 +11,8 @@
 // 2^31 / (6 * 4096) = 87381 rows: one slice of the shard per workgroup, converted to float64 once at the end.  Integer sums do not depend on
 // the order of accumulation: the digit products are bit-identical for any slicing of the shard.
 //
-// What the gate found (exact CPU emulation of this arithmetic, tests/devtools/dev_ozaki_gate.py, and the kernel itself -- they agree to the digit):
+// What the gate found (exact CPU emulation of this arithmetic, tests/devtools/dev_ozaki_gate.py, and the kernel itself; that the kernel IS this
+// arithmetic -- every digit, every integer sum, every rounding of the conversion -- is held by tests/test_gpu_p1_i8_exact.py against tests/i8_ref.py):
 //   * which products are dropped matters more than how many digits are kept.  Psi1's entries span ten decades inside a column and their
 //     density falls with magnitude, so inside a digit cell the remainder has a negative mean: neighbouring digits of ONE number are
 //     correlated, and dropping their cross products biases the DIAGONAL of Psi2 (+1e-12 relative with S = 5 / L = 6, 15 products) -- a jitter
@@ -327,7 +328,9 @@ int p1i8_prepare(gp_ctx* c, int8_t** Sl, long* strideJ, double** Dpart, int row_
     if (S < 1 || (c->Np + S - 1) / S + 32 > 87000) return fail(c, GP_ERR_UNSUPPORTED, "int8 phase 1: partial buffer too small for %d tiles", T);
     // placement: block b runs on XCD b % 8, one workgroup per CU, 32 CUs per XCD.  Whole slices first (every tile of a slice on one XCD: the
     // slice's digits are fetched from HBM once); when a single round fits (T <= 32) the CUs left over on each XCD are pooled into "shared"
-    // slices whose tiles are spread over the XCDs (their digits are fetched by several XCDs: 2 of 18 slices at M = 512, D = 100)
+    // slices whose tiles are spread over the XCDs (their digits are fetched by several XCDs).  With the cost search above the branch places nothing
+    // at any shape the path applies to -- T = 14 (M = 512, D <= 128) now takes s8 = 9, 72 slices, and every other T <= 32 leaves fewer than T / 8
+    // CUs over -- which tests/test_i8_ref_cpu.py enumerates from the restated rule (tests/i8_ref.py: plan)
     std::vector<std::vector<I8Job>> per_xcd(8);
     int n_shared = 0;
     if (T <= SLOTS && S == 8 * (SLOTS / T) && s8 == SLOTS / T) {

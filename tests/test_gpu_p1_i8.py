@@ -6,7 +6,8 @@ Checked with the path switched on (gp_debug_set_option('p1_i8', 1)): (1) the sta
 (p1v2_kernel) -- they differ by the 2^-42 truncation of the operands and the dropped digit products, 3.5e-15 in the exact CPU emulation;
 (2) bound and gradients against the oracle at ragged shapes (five Psi2 row tiles, two Y column blocks, M = 1024); (3) bit-identical repeats
 and independence of the slicing (integer sums); (4) the 80-bit truth of the benchmark workload at N = 1e5: grad_Z as close as with float64
-statistics."""
+statistics.
+The statistics themselves are held element by element to the exact digit arithmetic, independently of p1v2_kernel, by tests/test_gpu_p1_i8_exact.py."""
 import os
 
 import numpy as np
