@@ -91,6 +91,12 @@ SIGNATURES = {
     'gp_cg_max_d': (ctypes.c_int, [_vp, ctypes.c_double, _dp]),
     'gp_cg_abs': (ctypes.c_int, [_vp, _dp]),
     'gp_cg_update': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
+    'gp_lbfgs_begin': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'gp_lbfgs_grad': (ctypes.c_int, [_vp]),
+    'gp_lbfgs_push': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double]),
+    'gp_lbfgs_dots': (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    'gp_lbfgs_direction': (ctypes.c_int, [_vp, _dp]),
+    'gp_lbfgs_end': (ctypes.c_int, [_vp]),
     'gp_debug_gemm': (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_double, _dp, _dp, ctypes.c_double, _dp]),
     'gp_debug_set_option': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     'gp_debug_potrf_inverse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),

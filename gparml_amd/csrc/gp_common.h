@@ -103,6 +103,7 @@ struct PathsPlan;  // paths.hip
 struct SelPlan;    // select.hip
 struct CurvePlan;  // curve.hip
 struct ScorePlan;  // score.hip
+struct LbfgsPlan;  // lbfgs.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -117,6 +118,7 @@ struct PathsPlanDelete { void operator()(PathsPlan* p) const; };
 struct SelPlanDelete { void operator()(SelPlan* p) const; };
 struct CurvePlanDelete { void operator()(CurvePlan* p) const; };
 struct ScorePlanDelete { void operator()(ScorePlan* p) const; };
+struct LbfgsPlanDelete { void operator()(LbfgsPlan* p) const; };
 
 }  // namespace gp
 
@@ -283,6 +285,7 @@ struct gp_ctx {
   std::unique_ptr<gp::SelPlan, gp::SelPlanDelete> sel;        // gp_select_begin's state: rows, factor, conditional variances (select.hip)
   std::unique_ptr<gp::CurvePlan, gp::CurvePlanDelete> curve;  // gp_curve_energy's buffers (curve.hip)
   std::unique_ptr<gp::ScorePlan, gp::ScorePlanDelete> score;  // gp_predict_score's buffers (score.hip)
+  std::unique_ptr<gp::LbfgsPlan, gp::LbfgsPlanDelete> lbfgs;  // gp_lbfgs_begin .. gp_lbfgs_end: the history vectors (lbfgs.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -393,6 +396,8 @@ int run_select_candidate(gp_ctx* c, double* d, int64_t* row, double* x, double* 
 int run_select_apply(gp_ctx* c, const double* x_p, const double* l_p, double d_p, int64_t own_row, double* trace);
 void select_info(const gp_ctx* c, long* n, int* K, int* j);
 const double* select_debug(const gp_ctx* c, bool want_L, long* cnt);   // gp_debug_peek: the factor's written columns or d, NULL / 0 without a plan
+// lbfgs.hip
+const double* lbfgs_debug(const gp_ctx* c, const char* name, long* cnt);     // gp_debug_peek: "lbfgs_s<k>", "lbfgs_y<k>", "lbfgs_g"; NULL / 0 for a vector that holds nothing
 // pca.hip
 int run_scatter(gp_ctx* c, long n, const double* Y, const double* centre, double* sum, double* gram);
 int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const double* P, int Q, double* X);

@@ -1073,6 +1073,11 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
     src = select_debug(c, name[7] == 'L', &cnt);
     if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_select_begin .. gp_select_end", name);
   }
+  else if (!std::strcmp(name, "dir")) { src = c->dir; cnt = 2L * c->N * c->Q; }
+  else if (!std::strncmp(name, "lbfgs_", 6)) {
+    src = lbfgs_debug(c, name, &cnt);
+    if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_lbfgs_begin .. gp_lbfgs_end, or not a vector that holds anything", name);
+  }
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
   GP_HIP(c, hipStreamSynchronize(c->stream));

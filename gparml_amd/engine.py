@@ -195,6 +195,44 @@ class ShardEngine(object):
         self.globals_key = None
         self._ck(self.lib.gp_cg_update(self.h, int(which), float(a)), 'gp_cg_update')
 
+    # ---- resident L-BFGS history (gp_lbfgs_*, csrc/lbfgs.hip) ----------------------------------------------------
+    _lbfgs_m = 0
+
+    def lbfgs_begin(self, m):
+        """Allocates (or clears) the history of ``m`` pairs: 2m + 1 resident vectors of 2 N_s Q doubles, basis order s_0.. | y_0.. | g."""
+        self._ck(self.lib.gp_lbfgs_begin(self.h, int(m)), 'gp_lbfgs_begin')
+        self._lbfgs_m = int(m)
+
+    def lbfgs_grad(self):
+        """g = grad_latest (the start, and after a restart)."""
+        self._ck(self.lib.gp_lbfgs_grad(self.h), 'gp_lbfgs_grad')
+
+    def lbfgs_push(self, slot, step):
+        """s[slot] = step * direction, y[slot] = grad_latest - g, g = grad_latest in one pass; the embeddings do not move."""
+        self._ck(self.lib.gp_lbfgs_push(self.h, int(slot), float(step)), 'gp_lbfgs_push')
+
+    def lbfgs_dots(self, slot=-1):
+        """(3, 2m+1): this shard's inner products of s[slot], y[slot] and g with every basis vector (slot -1: the g row only, zeros above)."""
+        out = np.zeros((3, 2 * self._lbfgs_m + 1))
+        self._ck(self.lib.gp_lbfgs_dots(self.h, int(slot), out.ctypes.data_as(_lib._dp)), 'gp_lbfgs_dots')
+        return out
+
+    def lbfgs_direction(self, coef):
+        """direction = sum_j coef[j] b_j (empty slots and zero coefficients are skipped)."""
+        self.globals_key = None
+        coef, pc = _lib.as_c(np.asarray(coef, dtype=np.float64).reshape(-1))
+        assert coef.shape == (2 * self._lbfgs_m + 1,), 'coef shape %s: (%d,) expected' % (coef.shape, 2 * self._lbfgs_m + 1)
+        self._ck(self.lib.gp_lbfgs_direction(self.h, pc), 'gp_lbfgs_direction')
+
+    def lbfgs_end(self):
+        self._ck(self.lib.gp_lbfgs_end(self.h), 'gp_lbfgs_end')
+        self._lbfgs_m = 0
+
+    def lbfgs_peek(self, name):
+        """A history vector or the direction as it lies on the device, (2, N_s, Q): 's<k>', 'y<k>', 'g' or 'dir' (gp_debug_peek; a test tool)."""
+        n2 = 2 * self.N_s * self.Q
+        return self.peek('dir' if name == 'dir' else 'lbfgs_' + name, n2)[:n2].reshape(2, self.N_s, self.Q).copy()
+
     def scale_stats(self, factor):
         self._ck(self.lib.gp_scale_stats(self.h, float(factor)), 'gp_scale_stats')
 

@@ -10,6 +10,7 @@ import numpy as np
 from .driver import positive_mask, split_flat, transform_grad_vec, transform_vec
 from .engine import ShardEngine
 from .evaluation import BufferReduce, evaluate, refresh_statistics
+from .lbfgs import LbfgsHistory
 
 
 class ResidentModel(object):
@@ -322,3 +323,51 @@ class ResidentGD(_ResidentVectors):
 
     def embeddings_set_grads_update_grad_now(self, folder=None):       # :96-105 grad_now = latest
         self._upd(ShardEngine.CG_GRAD_NEW)
+
+
+class ResidentLBFGS(_ResidentVectors, LbfgsHistory):
+    """The per-point part of an L-BFGS history on the resident vectors (csrc/lbfgs.hip, gp_lbfgs_*): the ring and the Gram matrix are
+    ``lbfgs.LbfgsHistory``'s, on the host; here every shard keeps its slice of the 2 (m + 1) + 1 basis vectors in HBM.  Per accepted step: one
+    fused ``push`` per shard, ONE ``lbfgs_dots`` per shard and ONE ``_allreduce_vector`` of 3 (2 (m + 1) + 1) doubles for the three rows of the
+    Gram matrix that changed, one ``lbfgs_direction`` per shard.  ``slope()`` (g . d) is read from the matrix.  Use as the ``ops`` of
+    ``lbfgs.LBFGS``; m <= 31 (the device holds at most 32 slots, one of them the spare)."""
+
+    def __init__(self, model):
+        _ResidentVectors.__init__(self, model)
+
+    def _local_start(self, n_slots):
+        for e in self.m.engines:
+            e.lbfgs_begin(n_slots)
+            e.lbfgs_grad()
+
+    def _local_reset(self, n_slots):
+        for e in self.m.engines:
+            e.lbfgs_begin(n_slots)          # the same size: the pairs go, g stays
+
+    def _local_dots(self, slot):
+        tot = sum(e.lbfgs_dots(slot) for e in self.m.engines)
+        if self.m._dist is not None:
+            tot = self.m._allreduce_vector(tot.ravel(), 'sum').reshape(tot.shape)
+        return tot
+
+    def _local_push(self, slot, step):
+        for e in self.m.engines:
+            e.lbfgs_push(slot, step)
+
+    def _local_direction(self, coef):
+        for e in self.m.engines:
+            e.lbfgs_direction(coef)
+        self.m.version += 1                 # the direction changed: cached reductions and statistics are stale
+
+    def _local_update_X(self, step):
+        self._upd(ShardEngine.CG_UPDATE_X, step)
+
+    def _local_largest_move(self, step):
+        mx = max(e.cg_dots()[5] for e in self.m.engines)
+        if self.m._dist is not None:
+            mx = self.m._allreduce_scalar(mx, 'max')
+        return abs(step) * mx
+
+    def _local_finish(self):
+        for e in self.m.engines:
+            e.lbfgs_end()

@@ -517,6 +517,36 @@ int gp_cg_abs(gp_ctx* ctx, double* out2);
  *        4 update_grad_new :231-243 | 5 set_grads */
 int gp_cg_update(gp_ctx* ctx, int which, double a);
 
+/* ---- resident L-BFGS history (csrc/lbfgs.hip) -----------------------------------------------------
+ * The vector-free L-BFGS of Chen, Wang and Zhou ("Large-scale L-BFGS using MapReduce", NIPS 2014) on the resident vectors: the context keeps
+ * the basis b = [s_0 .. s_{m-1}, y_0 .. y_{m-1}, g] of 2m + 1 device vectors of 2 N_s Q doubles, laid out like grad_latest.  The two-loop
+ * recursion runs on the host on the (2m+1) x (2m+1) Gram matrix b_i . b_j, whose new rows one gp_lbfgs_dots returns; the new direction is one
+ * linear combination of the basis (gp_lbfgs_direction).  The trial mechanism is the existing one: the direction array of gp_set_direction,
+ * step_size of gp_set_globals, the grad_latest of gp_phase2(ctx, 1), and gp_cg_update(ctx, 2, a) to move the embeddings.  Free embeddings
+ * only (the gp_cg_* rule); the evaluation state is never touched.  An EMPTY slot is a zero vector by definition: it is never read, a dot
+ * against it is exactly 0.0 and its coefficient is ignored (as is a coefficient of exactly 0.0 on a filled slot).
+ *   gp_lbfgs_begin: 1 <= m <= 32; allocates (2m+1) * 16 N_s Q bytes and marks every slot empty and g unset.  A second call clears the
+ *     history: with the same m every slot becomes empty, nothing is reallocated and g stays as it is (a restart); with another m the
+ *     vectors are replaced and g is unset.
+ *   gp_lbfgs_grad: g = grad_latest (the start, and after a restart).
+ *   gp_lbfgs_push, one pass: s[slot] = step * direction, y[slot] = grad_latest - g, g = grad_latest; the slot becomes filled (a filled one is
+ *     overwritten: the ring is the caller's).  Needs g (gp_lbfgs_grad), a direction and a finite step.  The embeddings do not move.
+ *   gp_lbfgs_dots: out (3, 2m+1) = the LOCAL inner products of s[slot], y[slot] and g with every basis vector, in the order above; slot = -1:
+ *     the g row only, the other two rows are zeros.  The caller adds shards and ranks.  Each product is summed in an order that depends on
+ *     2 N_s Q alone (segments of 8192 elements, their partials added in ascending order): the same bits from run to run, on any device, for
+ *     any m.  GP_ERR_STATE for an empty slot, or before g is set.
+ *   gp_lbfgs_direction: direction = sum_j coef[j] * b_j, j ascending over the filled slots and g with coef[j] != 0 (the first term a product,
+ *     each further one a fused multiply-add); all-zero: zeros.  The direction counts as rewritten, as after gp_cg_update(ctx, 0 / 1 / 5).
+ *   gp_lbfgs_end: frees the vectors.
+ * GP_ERR_STATE / GP_ERR_BAD_ARG with a gp_last_error text, before anything is launched: no gp_lbfgs_begin, fixed embeddings, no shard data,
+ * no grad_latest, slot outside 0 .. m-1 (-1 .. m-1 for the dots), a non-finite step or coefficient. */
+int gp_lbfgs_begin(gp_ctx* ctx, int m);
+int gp_lbfgs_grad(gp_ctx* ctx);
+int gp_lbfgs_push(gp_ctx* ctx, int slot, double step);
+int gp_lbfgs_dots(gp_ctx* ctx, int slot, double* out /* (3, 2m+1) */);
+int gp_lbfgs_direction(gp_ctx* ctx, const double* coef /* (2m+1) */);
+int gp_lbfgs_end(gp_ctx* ctx);
+
 /* ---- shard ingest ------------------------------------------------------
  * numpy.genfromtxt(file, delimiter=',') as statistics_mapper / embeddings_mapper call it on every evaluation
  * (local_MapReduce.py:197-199, 325-327): comma-separated floating-point text -> row-major (rows, cols) doubles.
@@ -551,7 +581,9 @@ int gp_debug_potrf_inverse(int device, int n, const double* A, double* L, double
 int gp_debug_gemm_bench(int device, int ta, int tb, int m, int n, int k, int iters, double* ms_out);
 /* raw copy of one of the global step's internal buffers ("Linv", "Inv", "E", "PsiE", "T1", "T2", "dFdK", "Bbar", "Abar", "Bm", "gK", "gs") after a
  * stream synchronisation; n = capacity of out in doubles (tests/devtools/dev_tail_diff.py).  Between gp_select_begin and gp_select_end also
- * "select_L", the written columns of the factor [steps done][n rounded up to 64], and "select_d" [n rounded up to 64] (GP_ERR_STATE outside). */
+ * "select_L", the written columns of the factor [steps done][n rounded up to 64], and "select_d" [n rounded up to 64] (GP_ERR_STATE outside).
+ * "dir": the search direction [2 N_s Q].  Between gp_lbfgs_begin and gp_lbfgs_end also "lbfgs_s<k>", "lbfgs_y<k>" (k = 0 .. m-1, a filled slot)
+ * and "lbfgs_g" (once set), [2 N_s Q] each (GP_ERR_STATE outside, or for a vector that holds nothing). */
 int gp_debug_peek(gp_ctx* ctx, const char* name, double* out, long n);
 /* the rule the internal matrix products are launched under (csrc/gemm.hip, launch_gemm aborts when it fails: the blocked Cholesky's in-place panel solve raced until
  * round 6): does an operand stored as rows x cols doubles with leading dimension ld, starting at element offset x_off of a buffer, share an element with the result
