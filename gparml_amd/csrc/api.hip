@@ -112,6 +112,58 @@ int CgState::alloc(gp_ctx* c) {
 
 using namespace gp;
 
+// ---- argument checks the entry points share (`who` names the entry in the message).  all_finite works blockwise and finds no index ----
+static bool all_finite(const double* x, size_t n) {
+  for (size_t i0 = 0; i0 < n; i0 += 4096) {
+    int ok = 1;        // no short circuit inside a block: the loop vectorises, and is then no slower than a scan that stops at the first bad element
+    for (size_t i = i0, e = std::min(n, i0 + 4096); i < e; ++i) ok &= (int)std::isfinite(x[i]);
+    if (!ok) return false;
+  }
+  return true;
+}
+static int finite_check(gp_ctx* c, const char* who, const char* name, const double* x, size_t n) {
+  return all_finite(x, n) ? GP_OK : fail(c, GP_ERR_BAD_ARG, "%s: %s is not finite", who, name);
+}
+// Inputs at n new rows as the pair X_mu, X_S (NULL: deterministic): finite, and the variances >= 0 unless raw -- or, positive, > 0 in the form the
+// model takes (the infer entries).  Element by element through both arrays: the first bad element decides which of the two is named.
+static int inputs_check(gp_ctx* c, const char* who, int64_t n, const double* X_mu, const double* X_S, int raw, bool positive) {
+  const size_t nq = (size_t)n * c->Q;
+  if (!X_S) return finite_check(c, who, "X_mu", X_mu, nq);
+  for (size_t i = 0; i < nq; ++i) {
+    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X_mu is not finite", who);
+    const double v = positive && raw ? std::log(1.0 + std::exp(X_S[i])) : X_S[i];
+    if (!std::isfinite(X_S[i]) || (positive ? !std::isfinite(v) || !(v > 0.0) : !raw && v < 0.0))
+      return fail(c, GP_ERR_BAD_ARG, positive ? "%s: X_S must be finite and > 0" : "%s: X_S must be finite and >= 0", who);
+  }
+  return GP_OK;
+}
+// A NULL array that stands for the resident rows (`what` says so in the entry's words): they have been uploaded, and n is their count
+static int resident_rows_check(gp_ctx* c, const char* who, const char* what, int64_t n) {
+  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: %s before gp_upload_shard", who, what);
+  if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "%s: %s: n must be N_s = %ld, got %ld", who, what, (long)c->N, (long)n);
+  return GP_OK;
+}
+// Y (n, D) is finite wherever it is observed (a hidden entry is never read).  The column-list form: the same columns in every row, NULL = all D.
+static int observed_cols_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols) {
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < (cols ? n_cols : c->D); ++j)
+      if (!std::isfinite(Y[i * c->D + (cols ? cols[j] : j)])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed column", who);
+  return GP_OK;
+}
+// The per-row mask form (observed (n, D), nonzero = observed; NULL: every entry).  need_one: a row that observes nothing is an error too.
+static int observed_mask_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const uint8_t* observed, bool need_one) {
+  for (int64_t i = 0; i < n; ++i) {
+    int seen = 0;
+    for (int j = 0; j < c->D; ++j) {
+      if (observed && !observed[i * c->D + j]) continue;
+      ++seen;
+      if (!std::isfinite(Y[i * c->D + j])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed entry (row %ld, column %d)", who, (long)i, j);
+    }
+    if (need_one && !seen) return fail(c, GP_ERR_BAD_ARG, "%s: row %ld has no observed column", who, (long)i);
+  }
+  return GP_OK;
+}
+
 extern "C" const char* gp_last_error(const gp_ctx* ctx) { return ctx ? ctx->err.c_str() : gp::g_create_error.c_str(); }
 extern "C" const char* gp_version(void) { return "gparml_hip 0.1 (gfx950, fp64 4x4x4-mfma)"; }
 
@@ -699,11 +751,7 @@ extern "C" int gp_predict(gp_ctx* c, int64_t n, const double* X_mu, const double
   GP_TRY(model_ready(c, "gp_predict"));
   if (n == 0) return GP_OK;
   if (!X_mu) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is NULL");
-  const size_t nq = (size_t)n * c->Q;
-  for (size_t i = 0; i < nq; ++i) {
-    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_mu is not finite");
-    if (X_S && (!std::isfinite(X_S[i]) || (!xs_is_raw && X_S[i] < 0.0))) return fail(c, GP_ERR_BAD_ARG, "gp_predict: X_S must be finite and >= 0");
-  }
+  GP_TRY(inputs_check(c, "gp_predict", n, X_mu, X_S, xs_is_raw, false));
   if (!mean && !var) return GP_OK;
   return run_predict(c, (long)n, X_mu, X_S, xs_is_raw, flags, mean, var);
 }
@@ -719,8 +767,7 @@ extern "C" int gp_predict_score(gp_ctx* c, int64_t n, const double* X_mu, const 
   const size_t D = (size_t)c->D;
   const bool resident = X_mu == nullptr;
   if (resident) {      // the resident rows' own rules come first: they hold for every n, n = 0 included
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_predict_score: X_mu is NULL (the resident rows) before gp_upload_shard");
-    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is NULL (the resident rows): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
+    GP_TRY(resident_rows_check(c, "gp_predict_score", "X_mu is NULL (the resident rows)", n));
     if (X_S || xs_is_raw) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is NULL (the resident rows): X_S must be NULL and xs_is_raw 0 (flags bit 1 takes the resident variances)");
   }
   if (n == 0) {
@@ -729,18 +776,9 @@ extern "C" int gp_predict_score(gp_ctx* c, int64_t n, const double* X_mu, const 
   }
   if (!resident) {
     if (!Y) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: Y is NULL with host inputs");
-    const size_t nq = (size_t)n * c->Q;
-    for (size_t i = 0; i < nq; ++i) {
-      if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_mu is not finite");
-      if (X_S && (!std::isfinite(X_S[i]) || (!xs_is_raw && X_S[i] < 0.0))) return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: X_S must be finite and >= 0");
-    }
+    GP_TRY(inputs_check(c, "gp_predict_score", n, X_mu, X_S, xs_is_raw, false));
   }
-  if (Y) {
-    for (int64_t i = 0; i < n; ++i)
-      for (size_t j = 0; j < D; ++j)
-        if ((!observed || observed[i * D + j]) && !std::isfinite(Y[i * D + j]))       // a hidden entry is never read
-          return fail(c, GP_ERR_BAD_ARG, "gp_predict_score: Y is not finite in an observed entry (row %ld, column %zu)", (long)i, j);
-  }
+  if (Y) GP_TRY(observed_mask_check(c, "gp_predict_score", n, Y, observed, false));
   if (!row_logp && !row_sse && !row_chi2 && !cols) return GP_OK;
   return run_predict_score(c, (long)n, X_mu, X_S, xs_is_raw ? 1 : 0, resident, (flags & 2) != 0, Y, observed, flags, row_logp, row_sse, row_chi2, cols);
 }
@@ -754,9 +792,7 @@ static int joint_check(gp_ctx* c, const char* who, int64_t n, const double* X, i
   if (n == 0) return GP_OK;
   if (!X) return fail(c, GP_ERR_BAD_ARG, "%s: X is NULL", who);
   if (n > n_max) return fail(c, GP_ERR_UNSUPPORTED, "%s: n = %ld is beyond the limit of %ld points of one call (the n x n matrix is held on the device)", who, (long)n, (long)n_max);
-  const size_t nq = (size_t)n * c->Q;
-  for (size_t i = 0; i < nq; ++i)
-    if (!std::isfinite(X[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X is not finite", who);
+  GP_TRY(finite_check(c, who, "X", X, (size_t)n * c->Q));
   *nothing = false;
   return GP_OK;
 }
@@ -777,9 +813,7 @@ extern "C" int gp_predict_sample(gp_ctx* c, int64_t n, const double* X, int flag
   bool nothing;
   GP_TRY(joint_check(c, "gp_predict_sample", n, X, flags, 8192, &nothing));
   if (nothing || n_draws == 0) return GP_OK;
-  const size_t ne = (size_t)n_draws * n * c->D;
-  for (size_t i = 0; i < ne; ++i)
-    if (!std::isfinite(eps[i])) return fail(c, GP_ERR_BAD_ARG, "gp_predict_sample: eps is not finite");
+  GP_TRY(finite_check(c, "gp_predict_sample", "eps", eps, (size_t)n_draws * n * c->D));
   return run_predict_sample(c, (long)n, X, flags, jitter, n_draws, eps, out, mean);
 }
 
@@ -807,8 +841,6 @@ extern "C" int gp_curve_energy(gp_ctx* c, int64_t n_curves, int T, const double*
 }
 
 // ---- pathwise posterior draws (paths.hip) ----
-static bool all_finite(const double* x, size_t n);      // below, with the PCA entries
-
 extern "C" int gp_paths_set(gp_ctx* c, int n_draws, int F, const double* omega, const double* centre, const double* w, const double* eps_u) {
   if (!c) return GP_ERR_BAD_ARG;
   if (n_draws < 1 || F < 1) return fail(c, GP_ERR_BAD_ARG, "gp_paths_set: n_draws and F must be >= 1 (got %d, %d)", n_draws, F);
@@ -836,7 +868,7 @@ extern "C" int gp_paths_eval(gp_ctx* c, int64_t n, const double* X, int flags, d
     return fail(c, GP_ERR_STATE, "gp_paths_eval needs gp_paths_set on the model as it is now (none yet, or a global step, new statistics or new globals since)");
   if (n == 0) return GP_OK;
   if (!X || !out) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: X or out is NULL");
-  if (!all_finite(X, (size_t)n * c->Q)) return fail(c, GP_ERR_BAD_ARG, "gp_paths_eval: X is not finite");
+  GP_TRY(finite_check(c, "gp_paths_eval", "X", X, (size_t)n * c->Q));
   return run_paths_eval(c, (long)n, X, out, mean);
 }
 
@@ -847,29 +879,24 @@ extern "C" int gp_paths_clear(gp_ctx* c) {
   return GP_OK;
 }
 
-// gp_infer_objective / gp_infer_latent: gp_predict's preconditions, then the arguments of the new rows
-static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, const double* X_mu, const double* X_S, int raw,
-                       bool* nothing) {
+// gp_infer_objective / gp_infer_latent and their _rows forms: gp_predict's preconditions, then the arguments of the new rows.  masked: the observed
+// set of every row (observed) in place of the one column list (cols, n_cols)
+static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, bool masked, const uint8_t* observed,
+                       const double* X_mu, const double* X_S, int raw, bool* nothing) {
   *nothing = true;
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
-  if (cols ? (n_cols < 1 || n_cols > c->D) : n_cols != 0)
-    return fail(c, GP_ERR_BAD_ARG, "%s: n_cols must be 1 .. D with a column list and 0 without one", who);
-  for (int j = 0; cols && j < n_cols; ++j)
-    if (cols[j] < 0 || cols[j] >= c->D || (j && cols[j] <= cols[j - 1]))
-      return fail(c, GP_ERR_BAD_ARG, "%s: cols must be strictly increasing in 0 .. D - 1", who);
+  if (!masked) {
+    if (cols ? (n_cols < 1 || n_cols > c->D) : n_cols != 0)
+      return fail(c, GP_ERR_BAD_ARG, "%s: n_cols must be 1 .. D with a column list and 0 without one", who);
+    for (int j = 0; cols && j < n_cols; ++j)
+      if (cols[j] < 0 || cols[j] >= c->D || (j && cols[j] <= cols[j - 1]))
+        return fail(c, GP_ERR_BAD_ARG, "%s: cols must be strictly increasing in 0 .. D - 1", who);
+  }
   GP_TRY(model_ready(c, who));
   if (n == 0) return GP_OK;
-  if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, X_mu or X_S is NULL", who);
-  const size_t nq = (size_t)n * c->Q;
-  for (size_t i = 0; i < nq; ++i) {
-    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X_mu is not finite", who);
-    const double s = raw ? std::log(1.0 + std::exp(X_S[i])) : X_S[i];
-    if (!std::isfinite(X_S[i]) || !std::isfinite(s) || !(s > 0.0)) return fail(c, GP_ERR_BAD_ARG, "%s: X_S must be finite and > 0", who);
-  }
-  const int Do = cols ? n_cols : c->D;
-  for (int64_t i = 0; i < n; ++i)
-    for (int j = 0; j < Do; ++j)
-      if (!std::isfinite(Y[i * c->D + (cols ? cols[j] : j)])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed column", who);
+  if (!Y || (masked && !observed) || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, masked ? "%s: Y, observed, X_mu or X_S is NULL" : "%s: Y, X_mu or X_S is NULL", who);
+  GP_TRY(inputs_check(c, who, n, X_mu, X_S, raw, true));
+  GP_TRY(masked ? observed_mask_check(c, who, n, Y, observed, true) : observed_cols_check(c, who, n, Y, cols, n_cols));
   *nothing = false;
   return GP_OK;
 }
@@ -878,7 +905,7 @@ extern "C" int gp_infer_objective(gp_ctx* c, int64_t n, const double* Y, const i
                                   double* L, double* grad_mu, double* grad_S) {
   if (!c) return GP_ERR_BAD_ARG;
   bool nothing;
-  GP_TRY(infer_check(c, "gp_infer_objective", n, Y, cols, n_cols, X_mu, X_S, xs_is_raw, &nothing));
+  GP_TRY(infer_check(c, "gp_infer_objective", n, Y, cols, n_cols, false, nullptr, X_mu, X_S, xs_is_raw, &nothing));
   if (nothing || (!L && !grad_mu && !grad_S)) return GP_OK;
   return run_infer(c, 0, (long)n, Y, cols, n_cols, const_cast<double*>(X_mu), const_cast<double*>(X_S), xs_is_raw ? 1 : 0, 0, 0.0, L, grad_mu, grad_S, nullptr);
 }
@@ -888,43 +915,16 @@ extern "C" int gp_infer_latent(gp_ctx* c, int64_t n, const double* Y, const int*
   if (!c) return GP_ERR_BAD_ARG;
   if (max_iters < 0 || !(gtol >= 0.0)) return fail(c, GP_ERR_BAD_ARG, "gp_infer_latent: max_iters and gtol must be >= 0");
   bool nothing;
-  GP_TRY(infer_check(c, "gp_infer_latent", n, Y, cols, n_cols, X_mu, X_S, xs_is_raw, &nothing));
+  GP_TRY(infer_check(c, "gp_infer_latent", n, Y, cols, n_cols, false, nullptr, X_mu, X_S, xs_is_raw, &nothing));
   if (nothing) return GP_OK;
   return run_infer(c, 1, (long)n, Y, cols, n_cols, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
-}
-
-// gp_infer_objective_rows / gp_infer_latent_rows: the same, with the observed set of every row in place of the column list
-static int infer_rows_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const uint8_t* observed, const double* X_mu, const double* X_S, int raw,
-                            bool* nothing) {
-  *nothing = true;
-  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
-  GP_TRY(model_ready(c, who));
-  if (n == 0) return GP_OK;
-  if (!Y || !observed || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "%s: Y, observed, X_mu or X_S is NULL", who);
-  const size_t nq = (size_t)n * c->Q;
-  for (size_t i = 0; i < nq; ++i) {
-    if (!std::isfinite(X_mu[i])) return fail(c, GP_ERR_BAD_ARG, "%s: X_mu is not finite", who);
-    const double s = raw ? std::log(1.0 + std::exp(X_S[i])) : X_S[i];
-    if (!std::isfinite(X_S[i]) || !std::isfinite(s) || !(s > 0.0)) return fail(c, GP_ERR_BAD_ARG, "%s: X_S must be finite and > 0", who);
-  }
-  for (int64_t i = 0; i < n; ++i) {
-    int seen = 0;
-    for (int j = 0; j < c->D; ++j) {
-      if (!observed[i * c->D + j]) continue;
-      ++seen;
-      if (!std::isfinite(Y[i * c->D + j])) return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite in an observed entry (row %ld, column %d)", who, (long)i, j);
-    }
-    if (!seen) return fail(c, GP_ERR_BAD_ARG, "%s: row %ld has no observed column", who, (long)i);
-  }
-  *nothing = false;
-  return GP_OK;
 }
 
 extern "C" int gp_infer_objective_rows(gp_ctx* c, int64_t n, const double* Y, const uint8_t* observed, const double* X_mu, const double* X_S, int xs_is_raw,
                                        double* L, double* grad_mu, double* grad_S) {
   if (!c) return GP_ERR_BAD_ARG;
   bool nothing;
-  GP_TRY(infer_rows_check(c, "gp_infer_objective_rows", n, Y, observed, X_mu, X_S, xs_is_raw, &nothing));
+  GP_TRY(infer_check(c, "gp_infer_objective_rows", n, Y, nullptr, 0, true, observed, X_mu, X_S, xs_is_raw, &nothing));
   if (nothing || (!L && !grad_mu && !grad_S)) return GP_OK;
   return run_infer_rows(c, 0, (long)n, Y, observed, const_cast<double*>(X_mu), const_cast<double*>(X_S), xs_is_raw ? 1 : 0, 0, 0.0, L, grad_mu, grad_S, nullptr);
 }
@@ -934,7 +934,7 @@ extern "C" int gp_infer_latent_rows(gp_ctx* c, int64_t n, const double* Y, const
   if (!c) return GP_ERR_BAD_ARG;
   if (max_iters < 0 || !(gtol >= 0.0)) return fail(c, GP_ERR_BAD_ARG, "gp_infer_latent_rows: max_iters and gtol must be >= 0");
   bool nothing;
-  GP_TRY(infer_rows_check(c, "gp_infer_latent_rows", n, Y, observed, X_mu, X_S, xs_is_raw, &nothing));
+  GP_TRY(infer_check(c, "gp_infer_latent_rows", n, Y, nullptr, 0, true, observed, X_mu, X_S, xs_is_raw, &nothing));
   if (nothing) return GP_OK;
   return run_infer_rows(c, 1, (long)n, Y, observed, X_mu, X_S, xs_is_raw ? 1 : 0, max_iters, gtol, L, nullptr, nullptr, iters);
 }
@@ -946,13 +946,10 @@ extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: n must be >= 0");
   if (K < 1) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: K must be >= 1");
   if (!centres) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: centres is NULL");
-  if (!X) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_kmeans_accumulate: X is NULL (the resident X_mu) before gp_upload_shard");
-    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: X is NULL (the resident X_mu): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
-  }
-  const size_t kq = (size_t)K * c->Q, nq = (size_t)n * c->Q;
-  for (size_t i = 0; i < kq; ++i) if (!std::isfinite(centres[i])) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: centres is not finite");
-  for (size_t i = 0; X && i < nq; ++i) if (!std::isfinite(X[i])) return fail(c, GP_ERR_BAD_ARG, "gp_kmeans_accumulate: X is not finite");
+  if (!X) GP_TRY(resident_rows_check(c, "gp_kmeans_accumulate", "X is NULL (the resident X_mu)", n));
+  const size_t kq = (size_t)K * c->Q;
+  GP_TRY(finite_check(c, "gp_kmeans_accumulate", "centres", centres, kq));
+  if (X) GP_TRY(finite_check(c, "gp_kmeans_accumulate", "X", X, (size_t)n * c->Q));
   if (n == 0) {
     if (sums) std::fill(sums, sums + kq, 0.0);
     if (counts) std::fill(counts, counts + K, (int64_t)0);
@@ -966,30 +963,16 @@ extern "C" int gp_kmeans_accumulate(gp_ctx* c, int64_t n, const double* X, int K
 
 // The two passes of the PCA initialisation (csrc/pca.hip).  Nothing of the evaluation is read or written: only the Y columns of Kaug (Y == NULL) and
 // the plan's buffers.
-static bool all_finite(const double* x, size_t n) {
-  for (size_t i0 = 0; i0 < n; i0 += 4096) {
-    bool ok = true;
-    for (size_t i = i0, e = std::min(n, i0 + 4096); i < e; ++i) ok = ok && std::isfinite(x[i]);
-    if (!ok) return false;
-  }
-  return true;
-}
 static int pca_rows_check(gp_ctx* c, const char* who, int64_t n, const double* Y) {
   if (n < 0) return fail(c, GP_ERR_BAD_ARG, "%s: n must be >= 0", who);
-  if (!Y) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: Y is NULL (the resident Y) before gp_upload_shard", who);
-    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "%s: Y is NULL (the resident Y): n must be N_s = %ld, got %ld", who, (long)c->N, (long)n);
-  } else if (!all_finite(Y, (size_t)n * c->D)) {
-    return fail(c, GP_ERR_BAD_ARG, "%s: Y is not finite", who);
-  }
-  return GP_OK;
+  return Y ? finite_check(c, who, "Y", Y, (size_t)n * c->D) : resident_rows_check(c, who, "Y is NULL (the resident Y)", n);
 }
 
 extern "C" int gp_scatter_accumulate(gp_ctx* c, int64_t n, const double* Y, const double* centre, double* sum, double* gram) {
   if (!c) return GP_ERR_BAD_ARG;
   if (!centre) return fail(c, GP_ERR_BAD_ARG, "gp_scatter_accumulate: centre is NULL");
   GP_TRY(pca_rows_check(c, "gp_scatter_accumulate", n, Y));
-  if (!all_finite(centre, (size_t)c->D)) return fail(c, GP_ERR_BAD_ARG, "gp_scatter_accumulate: centre is not finite");
+  GP_TRY(finite_check(c, "gp_scatter_accumulate", "centre", centre, (size_t)c->D));
   if (n == 0) {
     if (sum) std::fill(sum, sum + c->D, 0.0);
     if (gram) std::fill(gram, gram + (size_t)c->D * c->D, 0.0);
@@ -1029,12 +1012,7 @@ extern "C" int gp_select_begin(gp_ctx* c, int64_t n, const double* X, int K, dou
   if (!alpha) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: alpha is NULL");
   for (int q = 0; q < c->Q; ++q)
     if (!(alpha[q] >= 0.0) || !std::isfinite(alpha[q])) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: alpha must be finite and >= 0");
-  if (!X) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_select_begin: X is NULL (the resident X_mu) before gp_upload_shard");
-    if (n != c->N) return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: X is NULL (the resident X_mu): n must be N_s = %ld, got %ld", (long)c->N, (long)n);
-  } else if (!all_finite(X, (size_t)n * c->Q)) {
-    return fail(c, GP_ERR_BAD_ARG, "gp_select_begin: X is not finite");
-  }
+  GP_TRY(X ? finite_check(c, "gp_select_begin", "X", X, (size_t)n * c->Q) : resident_rows_check(c, "gp_select_begin", "X is NULL (the resident X_mu)", n));
   GP_HIP(c, hipSetDevice(c->device));
   c->sel.reset();                    // an earlier plan goes first: its memory counts as free
   size_t free_b = 0, total_b = 0;
@@ -1095,8 +1073,8 @@ static int nearest_entry(gp_ctx* c, const char* fn, int64_t n_train, const doubl
     if (cols[j] < 0 || cols[j] >= c->D) return fail(c, GP_ERR_BAD_ARG, "%s: cols[%d] = %d is outside 0 .. D - 1 = %d", fn, j, cols[j], c->D - 1);
   if (Y_train && x_near) return fail(c, GP_ERR_BAD_ARG, "%s: x_near is the base mean of a resident row: it cannot be asked for with host rows (Y_train)", fn);
   if (!Y_train) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: Y_train is NULL (the resident rows) before gp_upload_shard", fn);
-    n_train = c->N;
+    n_train = c->N;       // the resident rows are all of them: only their presence is left to check
+    GP_TRY(resident_rows_check(c, fn, "Y_train is NULL (the resident rows)", n_train));
   } else if (n_train < 0) {
     return fail(c, GP_ERR_BAD_ARG, "%s: n_train must be >= 0", fn);
   }
@@ -1116,7 +1094,7 @@ static int nearest_entry(gp_ctx* c, const char* fn, int64_t n_train, const doubl
     if (!seen) return fail(c, GP_ERR_BAD_ARG, "%s: row %lld of Y_test has no observed column", fn, (long long)i);
     if (!ok) return fail(c, GP_ERR_BAD_ARG, "%s: Y_test is not finite in an observed column", fn);
   }
-  if (Y_train && !all_finite(Y_train, (size_t)n_train * c->D)) return fail(c, GP_ERR_BAD_ARG, "%s: Y_train is not finite", fn);
+  if (Y_train) GP_TRY(finite_check(c, fn, "Y_train", Y_train, (size_t)n_train * c->D));
   if (!dist2 && !index && !x_near) return GP_OK;
   if (n_train == 0) {
     if (dist2) std::fill(dist2, dist2 + n, std::numeric_limits<double>::infinity());

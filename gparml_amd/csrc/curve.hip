@@ -26,7 +26,7 @@
 // alone, in any batch and on either side of a chunk boundary.  No floating-point atomics; the summation order depends on (M, Q, D, T) alone.  Every
 // buffer belongs to the context's CurvePlan; the evaluation's and gp_predict's buffers are only read.
 // Not covered: uncertain inputs, second derivatives, generating dK inside the GEMM's staging, results kept on the device.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "lane_reduce.h"
 #include <algorithm>
 #include <cmath>
@@ -211,12 +211,12 @@ static int curve_alloc(gp_ctx* c, long curves, int T) {
 }
 
 int run_curve_energy(gp_ctx* c, long n, int T, const double* X, double* energy, double* seg, double* grad) {
-  long prows = 0;
-  GP_TRY_RC(pred_chunk_plan(c, &prows));
-  if (T > prows)
-    return fail(c, GP_ERR_UNSUPPORTED, "gp_curve_energy: a curve of T = %d points exceeds the %ld points of one chunk (chunks hold whole curves): split the curve", T, prows);
+  PredChunk k;
+  GP_TRY_RC(pred_chunk_open(c, false, &k));
+  if (T > k.rows)
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_curve_energy: a curve of T = %d points exceeds the %ld points of one chunk (chunks hold whole curves): split the curve", T, k.rows);
   const int opt = g_opt_curve_curves.load();
-  long per = std::max<long>(1, prows / T);           // per T <= prows: a chunk of curves fits gp_predict's chunk
+  long per = std::max<long>(1, k.rows / T);           // per T <= k.rows: a chunk of curves fits gp_predict's chunk
   if (opt > 0) per = std::min<long>(per, opt);
   GP_TRY_RC(curve_alloc(c, per, T));
   const CurvePlan& p = *c->curve;
@@ -225,11 +225,10 @@ int run_curve_energy(gp_ctx* c, long n, int T, const double* X, double* energy, 
   const double D = c->D;
   for (long c0 = 0; c0 < n; c0 += per) {
     const long nc = std::min(per, n - c0), cnt = nc * T, nseg = nc * (T - 1), rows = round_up(nseg, TILE);
-    GP_TRY_RC(pred_chunk_front(c, X, nullptr, 0, c0 * T, cnt, p.X, nullptr, 0, 1));
-    GP_LAUNCH(c, st, curve_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, pred_chunk_psi1(c), p.X, pred_chunk_inputs(c), c->Zt, c->alpha, nseg, rows,
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X), c0 * T, cnt, pred_into(p.X).on_big()));
+    GP_LAUNCH(c, st, curve_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, k.psi1, p.X, k.inputs, c->Zt, c->alpha, nseg, rows,
               T, c->M, (int)Mp, (int)Q, c->sf2, p.dK, p.kap);
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.dK, Mp}, {c->gstep.E, Dp}, {p.Tm, ldt}, (int)Mp, c->beta).on_big(1)));
-    GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.dK, Mp}, {c->gstep.Linv, Mp}, {p.Tm + Dp, ldt}, (int)Mp).on_big(1)));
+    GP_TRY_RC(pred_project(c, p.dK, rows, {p.Tm, ldt}, {p.Tm + Dp, ldt}, GEMM_BIG));
     if (energy || seg)
       GP_LAUNCH(c, st, curve_seg_kernel, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, p.Tm, ldt, p.kap, nseg, c->M, (int)Mp, c->D, (int)Dp, p.seg);
     if (energy) GP_LAUNCH(c, st, curve_sum_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, p.seg, nc, T, p.energy);
@@ -240,7 +239,7 @@ int run_curve_energy(gp_ctx* c, long n, int T, const double* X, double* energy, 
       GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Mp, 1,
                             gemm_of({p.Tm + Dp + Mp, ldt}, {c->gstep.Linv + Mp * Mp, Mp}, {p.G, Mp}, (int)Mp, D, 1.0).on_big(1)));
       CurveGradArgs a;
-      a.G = p.G; a.P1 = pred_chunk_psi1(c); a.Xc = p.X; a.Xr = pred_chunk_inputs(c); a.Zt = c->Zt; a.alpha = c->alpha; a.kap = p.kap; a.pts = cnt;
+      a.G = p.G; a.P1 = k.psi1; a.Xc = p.X; a.Xr = k.inputs; a.Zt = c->Zt; a.alpha = c->alpha; a.kap = p.kap; a.pts = cnt;
       a.T = T; a.M = c->M; a.Mp = (int)Mp; a.Q = (int)Q; a.D = c->D; a.grad = p.grad;
       // the latent dimensions a wave keeps in registers: 16, 64, or (0) one at a time for any Q
       GP_TRY_RC((for_width<16, 64, 0>(c, "curve gradient kernel", Q <= 16 ? 16 : Q <= 64 ? 64 : 0, [&](auto W) -> int {

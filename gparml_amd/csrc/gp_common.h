@@ -344,27 +344,8 @@ struct LeaRows {
   int Q; long cnt, rows; int M, Mp; const unsigned char* mask; double* LE; double* LEA;
 };
 int launch_lea_rows(gp_ctx* c, hipStream_t st, const LeaRows& a);
-// predict.hip
-const double* pred_debug_lea(const gp_ctx* c, long* n);               // gp_debug_peek: the uncertain-input plan's LEA, NULL / 0 without one
+// predict.hip (its chunk pipeline, which the other features at new inputs share: pred_chunk.h)
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var);
-// gp_predict's chunk pipeline for deterministic inputs, shared with the joint path: the chunk plan and its rows per chunk; one chunk's upload, prep,
-// Psi1* and products (mu [rows][Q]: where the centred inputs go; fac, ldf: where [Lk^-1 k* | La^-1 k*] goes, NULL: not formed; big: both products on the
-// 128 x 128-tile kernel whatever the chunk's size, so that a row's bits do not depend on the rows around it -- paths.hip); the chunk's mean rows;
-// the Psi1* rows [rows][Mp] of the chunk pred_chunk_front has just run (grad.hip builds its operand from them) and that chunk's inputs [cnt][Q] as the
-// caller gave them (curve.hip differences them before the centring rounds them)
-int pred_chunk_plan(gp_ctx* c, long* rows, bool uncertain = false);
-const double* pred_chunk_psi1(const gp_ctx* c);
-const double* pred_chunk_inputs(const gp_ctx* c);
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big = 0, int dev = 0);
-int pred_chunk_mean(gp_ctx* c, long cnt, double* mean);
-// gp_predict's own chunk buffers, for the path that scores a chunk where it lies (score.hip): the centred inputs [rows][Q] (what gp_predict passes as
-// mu), the products G [rows][Dp + 2 Mp] = [mean | Lk^-1 k* | La^-1 k*] and the variance buffer [rows][D]; and the uncertain-input variance in its two
-// steps: B = Ki - P once per call, then per chunk LEA and pred_psi2w_kernel into var [cnt][D] (the plan built with uncertain = true)
-double* pred_chunk_mu(const gp_ctx* c);
-double* pred_chunk_products(const gp_ctx* c);
-double* pred_chunk_var(const gp_ctx* c);
-int pred_unc_begin(gp_ctx* c);
-int pred_chunk_var_unc(gp_ctx* c, long cnt, double noise, double* var);
 // score.hip
 int run_predict_score(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, bool resident, bool resident_S, const double* Y,
                       const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* cols);

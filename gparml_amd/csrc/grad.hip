@@ -20,7 +20,7 @@
 // No floating-point atomics, fixed summation order that depends on Q alone: a point's bits do not depend on the batch.  Every buffer belongs to the
 // context's GradPlan; the evaluation's and gp_predict's buffers are only read.
 // Not covered: uncertain inputs, second derivatives, generating dK inside the GEMM's staging, pinned or pipelined host copies.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "lane_reduce.h"
 #include <algorithm>
 #include <cmath>
@@ -298,10 +298,10 @@ static int grad_alloc(gp_ctx* c, long pts) {
 }
 
 int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dvar, double* metric, double* logdet) {
-  long prows = 0;
-  GP_TRY_RC(pred_chunk_plan(c, &prows));
+  PredChunk k;
+  GP_TRY_RC(pred_chunk_open(c, false, &k));
   const long Q = c->Q, D = c->D, Mp = c->Mp, Dp = c->Dp, ldt = Dp + 2 * Mp;
-  const long pts = std::max<long>(1, prows / Q);     // <= prows: a chunk of points fits gp_predict's chunk; its T has round_up(pts Q, 128) rows
+  const long pts = std::max<long>(1, k.rows / Q);    // <= k.rows: a chunk of points fits gp_predict's chunk; its T has round_up(pts Q, 128) rows
   GP_TRY_RC(grad_alloc(c, pts));
   const GradPlan& p = *c->grad;
   hipStream_t st = c->stream;
@@ -312,11 +312,10 @@ int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dv
   std::vector<int> h_fail(logdet ? (size_t)n : 0);
   for (long n0 = 0; n0 < n; n0 += pts) {
     const long cnt = std::min(pts, n - n0), rows = round_up(cnt * Q, TILE);
-    GP_TRY_RC(pred_chunk_front(c, X, nullptr, 0, n0, cnt, p.X, need_l ? p.R.get() : nullptr, 2 * Mp));
-    GP_LAUNCH(c, st, grad_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, pred_chunk_psi1(c), p.X, c->Zt, c->alpha, cnt, rows, c->M, (int)Mp,
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X), n0, cnt, pred_into(p.X).factors(need_l ? p.R.get() : nullptr, 2 * Mp)));
+    GP_LAUNCH(c, st, grad_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, k.psi1, p.X, c->Zt, c->alpha, cnt, rows, c->M, (int)Mp,
               (int)Q, p.dK);
-    if (need_e) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.dK, Mp}, {c->gstep.E, Dp}, {p.T, ldt}, (int)Mp, c->beta)));
-    if (need_l) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.dK, Mp}, {c->gstep.Linv, Mp}, {p.T + Dp, ldt}, (int)Mp)));
+    GP_TRY_RC(pred_project(c, p.dK, rows, {need_e ? p.T.get() : nullptr, ldt}, {need_l ? p.T + Dp : nullptr, ldt}, GEMM_BY_SIZE));
     GradArgs a;
     a.T = p.T; a.R = p.R; a.alpha = c->alpha; a.ldt = ldt; a.M = c->M; a.Mp = (int)Mp; a.D = (int)D; a.Dp = (int)Dp; a.Q = (int)Q; a.sf2 = c->sf2;
     a.need_e = need_e; a.need_l = need_l;

@@ -18,7 +18,7 @@
 //     out = mean + Lc eps as launch_gemm products against the packed normals [np][draws x D], a group of draws at a time.
 // No floating-point atomics, fixed summation order: results are bit-identical from run to run.  Every buffer belongs to the context's JointPlan
 // (replaced whole when np grows); the evaluation's buffers are only read.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "fexp.h"
 #include <algorithm>
 #include <cmath>
@@ -166,15 +166,6 @@ __global__ void __launch_bounds__(256, STAGED ? 2 : 1) pred_cov_kernel(CovArgs p
   }
 }
 
-// C[i][col] = mean[i][col mod D] for i < n and col < used, else 0: the draws' product then adds Lc eps on top (beta = 1)
-__global__ void __launch_bounds__(256) joint_fill_mean_kernel(const double* __restrict__ mean, long n, int D, long rows, long cols, long used, double* __restrict__ C) {
-  const long total = rows * cols;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const long i = e / cols, col = e - i * cols;
-    C[e] = (i < n && col < used) ? mean[i * D + col % D] : 0.0;
-  }
-}
-
 // the draws' buffers: built on the first gp_predict_sample of a plan
 struct JointDraw {
   DevBuf<double> Linv;        // [np][np] potrf_inverse_batched's inverse diagonal blocks (zero above the block diagonal: its precondition)
@@ -218,11 +209,11 @@ static int joint_alloc(gp_ctx* c, long np, bool draws) {
 // R, the centred inputs and the mean of all n points through gp_predict's chunk pipeline
 static int joint_rows(gp_ctx* c, long n, const double* X) {
   const JointPlan& p = *c->joint;
-  long rows = 0;
-  GP_TRY_RC(pred_chunk_plan(c, &rows));
-  for (long n0 = 0; n0 < n; n0 += rows) {
-    const long cnt = std::min(rows, n - n0);
-    GP_TRY_RC(pred_chunk_front(c, X, nullptr, 0, n0, cnt, p.X + n0 * c->Q, p.R + n0 * 2 * c->Mp, 2L * c->Mp));
+  PredChunk k;
+  GP_TRY_RC(pred_chunk_open(c, false, &k));
+  for (long n0 = 0; n0 < n; n0 += k.rows) {
+    const long cnt = std::min(k.rows, n - n0);
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X), n0, cnt, pred_into(p.X + n0 * c->Q).factors(p.R + n0 * 2 * c->Mp, 2L * c->Mp)));
     GP_TRY_RC(pred_chunk_mean(c, cnt, p.mean + n0 * c->D));
   }
   return GP_OK;
@@ -277,7 +268,7 @@ int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jit
     GP_HIP(c, hipMemsetAsync(d.eps, 0, (size_t)(np * cols) * 8, st));
     for (long s = 0; s < g; ++s)
       GP_HIP(c, hipMemcpy2DAsync(d.eps + s * D, (size_t)cols * 8, eps + (s0 + s) * n * D, (size_t)D * 8, (size_t)D * 8, (size_t)n, hipMemcpyHostToDevice, st));
-    GP_LAUNCH(c, st, joint_fill_mean_kernel, dim3((unsigned)blocks_for(np * cols)), dim3(256), 0, p.mean, n, (int)D, np, cols, g * D, d.out);
+    GP_TRY_RC(pred_fill_mean(c, p.mean, n, np, cols, g * D, d.out));
     // out += Lc eps: Lc [i][k] K_CONTIG, eps [k][column] FREE_CONTIG
     GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)np, (int)cols, 1, gemm_of({p.cov, np}, {d.eps, cols}, {d.out, cols}, (int)np, 1.0, 1.0)));
     for (long s = 0; s < g; ++s)

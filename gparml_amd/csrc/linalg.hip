@@ -5,7 +5,7 @@
 //   Kmm-dependent parts of grad_Z / grad_alpha / grad_sf2 (:146-160, 207-240, 247-254, 286-333).
 // All matrices are padded to multiples of 128 with an identity block, which leaves log-determinants, inverses
 // and every trace unchanged.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "potrf128.h"
 #include "gemm32.h"
 #include "lane_reduce.h"

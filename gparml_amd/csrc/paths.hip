@@ -21,7 +21,7 @@
 // a sum over k in a fixed order that does not depend on its place in the tile, and a feature depends on its row alone.  A point's outputs therefore
 // depend on that point, the plan and the model only: the same bits alone, in any batch, in any row order and wherever a chunk boundary falls.  No
 // floating-point atomics.  Every buffer belongs to the context's PathsPlan; the evaluation's buffers are only read.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include <algorithm>
 #include <cmath>
 
@@ -111,15 +111,6 @@ __global__ void __launch_bounds__(256) paths_pack_kernel(const double* __restric
       const long m = r - Kf;
       B[(Kf + Mp + m) * cols + col] = (m < M && col < used) ? eps[(s * M + m) * D + d] : 0.0;
     }
-  }
-}
-
-// C[i][col] = mean[i][col mod D] for i < cnt and col < used, else 0: the chunk's product then adds the three terms on top (beta = 1)
-__global__ void __launch_bounds__(256) paths_fill_mean_kernel(const double* __restrict__ mean, long cnt, int D, long rows, long cols, long used, double* __restrict__ C) {
-  const long total = rows * cols;
-  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
-    const long i = e / cols, col = e - i * cols;
-    C[e] = (i < cnt && col < used) ? mean[i * D + col % D] : 0.0;
   }
 }
 
@@ -222,9 +213,9 @@ int run_paths_eval(gp_ctx* c, long n, const double* X, double* out, double* mean
   PathsPlan& p = *c->paths;
   hipStream_t st = c->stream;
   const long Mp = c->Mp, Q = c->Q, D = c->D, S = p.S, Kf = p.Kf, cols = p.cols, ldl = Kf + 2 * Mp;
-  long pred_rows = 0;
-  GP_TRY_RC(pred_chunk_plan(c, &pred_rows));
-  const long R = std::min(paths_rows_for(c, p, pred_rows), n), cap = round_up(R, TILE);
+  PredChunk pc;
+  GP_TRY_RC(pred_chunk_open(c, false, &pc));
+  const long R = std::min(paths_rows_for(c, p, pc.rows), n), cap = round_up(R, TILE);
   if (!p.chunk || p.chunk->cap < cap) {
     p.chunk.reset();
     auto k = std::make_unique<PathsChunk>();
@@ -236,10 +227,10 @@ int run_paths_eval(gp_ctx* c, long n, const double* X, double* out, double* mean
   const PathsChunk& k = *p.chunk;
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0), rows = round_up(cnt, TILE);
-    GP_TRY_RC(pred_chunk_front(c, X, nullptr, 0, n0, cnt, k.X, k.L + Kf, ldl, 1));
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X), n0, cnt, pred_into(k.X).factors(k.L + Kf, ldl).on_big()));
     GP_TRY_RC(pred_chunk_mean(c, cnt, k.mean));
     GP_TRY_RC(launch_features(c, k.X, Q, p, cnt, rows, k.L, ldl));
-    GP_LAUNCH(c, st, paths_fill_mean_kernel, dim3((unsigned)blocks_for(rows * cols)), dim3(256), 0, k.mean, cnt, (int)D, rows, cols, S * D, k.C);
+    GP_TRY_RC(pred_fill_mean(c, k.mean, cnt, rows, cols, S * D, k.C));
     // C += [phi | a | b] [Wt ; -G ; E]: the left operand [i][k] K_CONTIG, B [k][column] FREE_CONTIG
     GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)cols, 1, gemm_of({k.L, ldl}, {p.B, cols}, {k.C, cols}, (int)ldl, 1.0, 1.0).on_big(1)));
     GP_LAUNCH(c, st, paths_scatter_kernel, dim3((unsigned)blocks_for(S * cnt * D)), dim3(256), 0, k.C, cnt, (int)S, (int)D, cols, k.T);

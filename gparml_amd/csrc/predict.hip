@@ -17,7 +17,7 @@
 //   and fed as the A operand of v_mfma_f64_4x4x4_4b_f64 against E; the epilogue folds the column dot with E and sum(B o psi2) (both in fixed order).
 // Nothing of [n][M][M] is ever stored.  Every prediction buffer is owned by the context, allocated on first use and bounded by the chunk size
 // (rows points per pass, PredPlan); deleting the context frees them.  The evaluation's buffers are only read: phase 2 / gp_finish after a prediction give the same bits.
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "fexp.h"
 #include "lane_reduce.h"
 #include "varpoint.h"
@@ -78,6 +78,15 @@ __global__ void __launch_bounds__(256) pred_det_rows_kernel(const double* __rest
   sk = wave_sum(sk);
   sa = wave_sum(sa);
   if (lane == 0) var[n] = sf2 - sk + sa + noise;
+}
+
+// C[i][col] = mean[i][col mod D] for i < n and col < used, else 0: the caller's product then adds its terms on top (beta = 1)
+__global__ void __launch_bounds__(256) fill_mean_kernel(const double* __restrict__ mean, long n, int D, long rows, long cols, long used, double* __restrict__ C) {
+  const long total = rows * cols;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long i = e / cols, col = e - i * cols;
+    C[e] = (i < n && col < used) ? mean[i * D + col % D] : 0.0;
+  }
 }
 
 // ---- uncertain inputs: psi2* E on the FP64 matrix core ---------------------------------------------------------------------------------------
@@ -262,49 +271,50 @@ const double* pred_debug_lea(const gp_ctx* c, long* n) {
   return u ? u->LEA.get() : nullptr;
 }
 
-// One chunk of points through the front of the pipeline: upload, pred_prep_kernel, Psi1*, the mean product into the chunk's G and (fac != NULL) the
-// two inverse-factor products [Lk^-1 k* | La^-1 k*] into fac (leading dimension ldf).  gp_predict keeps the centred inputs and the factor rows in
-// the chunk's own buffers (mu = PredPlan::mu, fac = G + Dp); the joint path (joint.hip) collects those of all chunks in its plan.  dev: X_mu and X_S are
-// device arrays (the resident rows, score.hip) and go to pred_prep_kernel as they are: nothing is uploaded and nothing is staged.
-int pred_chunk_front(gp_ctx* c, const double* X_mu, const double* X_S, int raw, long n0, long cnt, double* mu, double* fac, long ldf, int big, int dev) {
+int pred_chunk_open(gp_ctx* c, bool uncertain, PredChunk* k) {
+  GP_TRY_RC(pred_alloc(c, uncertain));
   const PredPlan& p = *c->pred;
-  const bool unc = X_S != nullptr;
+  *k = PredChunk{p.rows, p.in, p.mu, p.P1, p.G, c->Dp + 2L * c->Mp, p.out + p.rows * c->D};
+  return GP_OK;
+}
+
+int pred_project(gp_ctx* c, const double* A, long rows, GemmOut e, GemmOut fac, GemmTile tile) {
+  const long Mp = c->Mp, Dp = c->Dp;
+  if (e.p) GP_TRY_RC(launch_gemm(c, c->stream, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({A, Mp}, {c->gstep.E, Dp}, e, (int)Mp, c->beta).on_big(tile)));
+  if (fac.p) GP_TRY_RC(launch_gemm(c, c->stream, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({A, Mp}, {c->gstep.Linv, Mp}, fac, (int)Mp).on_big(tile)));
+  return GP_OK;
+}
+
+// gp_predict keeps the centred inputs and the factor rows in the chunk's own buffers (PredChunk::mu, G + Dp); joint.hip collects those of all chunks
+int pred_chunk_front(gp_ctx* c, const PredIn& in, long n0, long cnt, const PredOut& out) {
+  const PredPlan& p = *c->pred;
+  const bool unc = in.X_S != nullptr;
   const PredUnc* u = p.unc.get();
   hipStream_t st = c->stream;
   const long R = p.rows, Mp = c->Mp, Dp = c->Dp, Q = c->Q, rows = round_up(cnt, TILE);
-  const double* xin = dev ? X_mu + n0 * Q : p.in.get();
-  const double* sin = dev ? (unc ? X_S + n0 * Q : nullptr) : p.in + R * Q;
-  if (!dev) {
-    GP_HIP(c, hipMemcpyAsync(p.in, X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
-    if (unc) GP_HIP(c, hipMemcpyAsync(p.in + R * Q, X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+  const double* xin = in.device ? in.X_mu + n0 * Q : p.in.get();
+  const double* sin = in.device ? (unc ? in.X_S + n0 * Q : nullptr) : p.in + R * Q;
+  if (!in.device) {
+    GP_HIP(c, hipMemcpyAsync(p.in, in.X_mu + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
+    if (unc) GP_HIP(c, hipMemcpyAsync(p.in + R * Q, in.X_S + n0 * Q, (size_t)cnt * Q * 8, hipMemcpyHostToDevice, st));
   }
-  GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, raw, c->alpha, c->shift, cnt,
-            rows, (int)Q, c->sf2, mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
-  GP_TRY_RC(launch_psi1_rows(c, mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
+  GP_LAUNCH(c, st, pred_prep_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, xin, unc ? sin : (const double*)nullptr, in.raw, c->alpha, c->shift, cnt,
+            rows, (int)Q, c->sf2, out.mu, p.U, p.lnc1, unc ? u->W.get() : nullptr, unc ? u->V2.get() : nullptr, unc ? u->lnc2.get() : nullptr);
+  GP_TRY_RC(launch_psi1_rows(c, out.mu, p.U, p.lnc1, p.P1, cnt, rows, Mp));
   // mean (and, deterministic inputs, the two inverse-factor products) on the MFMA GEMM core
-  GP_TRY_RC(launch_gemm(c, st, K_CONTIG, FREE_CONTIG, (int)rows, (int)Dp, 1, gemm_of({p.P1, Mp}, {c->gstep.E, Dp}, {p.G, Dp + 2 * Mp}, (int)Mp, c->beta).on_big(big)));
-  if (fac) GP_TRY_RC(launch_gemm(c, st, K_CONTIG, K_CONTIG, (int)rows, (int)(2 * Mp), 1, gemm_of({p.P1, Mp}, {c->gstep.Linv, Mp}, {fac, ldf}, (int)Mp).on_big(big)));
-  return GP_OK;
+  return pred_project(c, p.P1, rows, {p.G, Dp + 2 * Mp}, {out.fac, out.ldf}, out.tile);
 }
 
-// the chunk plan (built on first use; uncertain: with the buffers of the uncertain-input variance) and its rows per chunk
-int pred_chunk_plan(gp_ctx* c, long* rows, bool uncertain) {
-  GP_TRY_RC(pred_alloc(c, uncertain));
-  *rows = c->pred->rows;
-  return GP_OK;
-}
-
-const double* pred_chunk_psi1(const gp_ctx* c) { return c->pred->P1; }
-const double* pred_chunk_inputs(const gp_ctx* c) { return c->pred->in; }
-double* pred_chunk_mu(const gp_ctx* c) { return c->pred->mu; }
-double* pred_chunk_products(const gp_ctx* c) { return c->pred->G; }
-double* pred_chunk_var(const gp_ctx* c) { return c->pred->out + c->pred->rows * c->D; }
-
-// the mean rows [cnt][D] of the chunk pred_chunk_front has just run, out of G into a device buffer of the caller
+// (the kernel's variance slot goes to the chunk's own variance buffer, which nobody reads before it is written again)
 int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
   const PredPlan& p = *c->pred;
   GP_LAUNCH(c, c->stream, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, (long)c->Dp + 2L * c->Mp, cnt, 0, c->Mp, c->D, c->Dp, c->sf2,
             0.0, mean, p.out + p.rows * c->D);
+  return GP_OK;
+}
+
+int pred_fill_mean(gp_ctx* c, const double* mean, long n, long rows, long cols, long used, double* C) {
+  GP_LAUNCH(c, c->stream, fill_mean_kernel, dim3((unsigned)blocks_for(rows * cols)), dim3(256), 0, mean, n, c->D, rows, cols, used, C);
   return GP_OK;
 }
 
@@ -338,33 +348,25 @@ int pred_chunk_var_unc(gp_ctx* c, long cnt, double noise, double* var) {
 
 int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, int flags, double* mean, double* var) {
   const bool unc = X_S != nullptr;
-  GP_TRY_RC(pred_alloc(c, unc));
-  const PredPlan& p = *c->pred;
+  PredChunk k;
+  GP_TRY_RC(pred_chunk_open(c, unc, &k));
   hipStream_t st = c->stream;
-  const long R = p.rows, Mp = c->Mp, Dp = c->Dp, M = c->M, D = c->D;
-  const long ldg = Dp + 2 * Mp;
+  const long R = k.rows, D = c->D;
   const double noise = (flags & 1) ? 1.0 / c->beta : 0.0;
   if (unc && var) GP_TRY_RC(pred_unc_begin(c));
-  double* out_mean = p.out;
-  double* out_var = p.out + R * D;
+  double* out_mean = c->pred->out;
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0);
-    GP_TRY_RC(pred_chunk_front(c, X_mu, X_S, raw, n0, cnt, p.mu, !unc && var ? p.G + Dp : nullptr, ldg));
-    if (!unc) {
-      GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, var ? (int)M : 0, (int)Mp, (int)D, (int)Dp,
-                c->sf2, noise, out_mean, out_var);
-      if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
-      if (var) GP_HIP(c, hipMemcpyAsync(var + n0, out_var, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
-    } else {
-      if (mean) {
-        GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p.G, ldg, cnt, 0, (int)Mp, (int)D, (int)Dp,
-                  c->sf2, noise, out_mean, out_var);
-        GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
-      }
-      if (var) {
-        GP_TRY_RC(pred_chunk_var_unc(c, cnt, noise, out_var));
-        GP_HIP(c, hipMemcpyAsync(var + n0 * D, out_var, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
-      }
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X_mu).uncertain(X_S, raw), n0, cnt, pred_into(k.mu).factors(!unc && var ? k.G + c->Dp : nullptr, k.ldg)));
+    if (!unc && var) {      // mean and variance of deterministic inputs in one kernel
+      GP_LAUNCH(c, st, pred_det_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, k.G, k.ldg, cnt, c->M, c->Mp, (int)D, c->Dp, c->sf2, noise, out_mean,
+                k.var);
+    } else if (mean) GP_TRY_RC(pred_chunk_mean(c, cnt, out_mean));
+    if (mean) GP_HIP(c, hipMemcpyAsync(mean + n0 * D, out_mean, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
+    if (!unc && var) GP_HIP(c, hipMemcpyAsync(var + n0, k.var, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+    if (unc && var) {
+      GP_TRY_RC(pred_chunk_var_unc(c, cnt, noise, k.var));
+      GP_HIP(c, hipMemcpyAsync(var + n0 * D, k.var, (size_t)cnt * D * 8, hipMemcpyDeviceToHost, st));
     }
   }
   GP_HIP(c, hipStreamSynchronize(st));

@@ -25,7 +25,7 @@
 // Resident rows (X_mu == NULL): device pointers into the context's X_mu / X_S go straight to pred_prep_kernel and Y is read where it lies, in the
 // columns of Kaug behind Psi1 (leading dimension LDK): nothing is uploaded but an optional mask, nothing is staged.
 // Buffers: ScorePlan, built aside and published whole; every element is written before it is read (DA_RAW: NaN-filled in the poison test mode).
-#include "gp_common.h"
+#include "pred_chunk.h"
 #include "lane_reduce.h"
 #include <algorithm>
 #include <climits>
@@ -210,25 +210,25 @@ int run_predict_score(gp_ctx* c, long n, const double* X_mu, const double* X_S, 
     raw = resident_S && c->xs_raw ? 1 : 0;
   }
   const bool unc = X_S != nullptr;
-  long R = 0;
-  GP_TRY_RC(pred_chunk_plan(c, &R, unc));
+  PredChunk k;
+  GP_TRY_RC(pred_chunk_open(c, unc, &k));
+  const long R = k.rows;
   GP_TRY_RC(score_alloc(c, R, Y != nullptr, observed != nullptr));
   const ScorePlan& p = *c->score;
   hipStream_t st = c->stream;
-  const long Mp = c->Mp, Dp = c->Dp, D = c->D, ldg = Dp + 2 * Mp, d5 = 5 * D;
+  const long Mp = c->Mp, Dp = c->Dp, D = c->D, d5 = 5 * D;
   const int tiles = (int)((D + SC_DW - 1) / SC_DW);
   long long* totbad = p.bad + (R / SC_SEG) * tiles;
-  double* G = pred_chunk_products(c);
   if (unc) GP_TRY_RC(pred_unc_begin(c));
   for (long n0 = 0; n0 < n; n0 += R) {
     const long cnt = std::min(R, n - n0);
     const int segs = (int)((cnt + SC_SEG - 1) / SC_SEG);
-    GP_TRY_RC(pred_chunk_front(c, X_mu, X_S, raw, n0, cnt, pred_chunk_mu(c), unc ? nullptr : G + Dp, ldg, 0, resident ? 1 : 0));
+    GP_TRY_RC(pred_chunk_front(c, pred_at(X_mu).uncertain(X_S, raw).on_device(resident), n0, cnt, pred_into(k.mu).factors(unc ? nullptr : k.G + Dp, k.ldg)));
     ScoreArgs a;
-    a.G = G; a.ldg = ldg; a.var = nullptr;
+    a.G = k.G; a.ldg = k.ldg; a.var = nullptr;
     if (unc) {
-      GP_TRY_RC(pred_chunk_var_unc(c, cnt, (flags & 1) ? 1.0 / c->beta : 0.0, pred_chunk_var(c)));
-      a.var = pred_chunk_var(c);
+      GP_TRY_RC(pred_chunk_var_unc(c, cnt, (flags & 1) ? 1.0 / c->beta : 0.0, k.var));
+      a.var = k.var;
     }
     if (Y) {
       GP_HIP(c, hipMemcpyAsync(p.Y, Y + n0 * D, (size_t)(cnt * D) * 8, hipMemcpyHostToDevice, st));
