@@ -81,6 +81,7 @@ SIGNATURES = {
     'gp_project_rows': (ctypes.c_int, [_vp, _i64, _dp, _dp, _dp, ctypes.c_int, _dp]),
     'gp_nearest_rows': (ctypes.c_int, [_vp, _i64, _dp, _i64, _dp, _ip, ctypes.c_int, _dp, ctypes.POINTER(_i64), _dp]),
     'gp_nearest_rows_masked': (ctypes.c_int, [_vp, _i64, _dp, _i64, _dp, _u8p, _dp, ctypes.POINTER(_i64), _dp]),
+    'gp_knn_rows': (ctypes.c_int, [_vp, _i64, _dp, _i64, _dp, _dp, ctypes.c_int, ctypes.POINTER(_i64), ctypes.c_int, _dp, ctypes.POINTER(_i64)]),
     'gp_last_timings': (ctypes.c_int, [_vp, _dp]),
     'gp_set_timing': (ctypes.c_int, [_vp, ctypes.c_int]),
     'gp_i8_status': (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int), _dp, _dp, _dp, ctypes.POINTER(_i64)]),

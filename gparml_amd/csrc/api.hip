@@ -1115,6 +1115,41 @@ extern "C" int gp_nearest_rows_masked(gp_ctx* c, int64_t n_train, const double* 
   return nearest_entry(c, "gp_nearest_rows_masked", n_train, Y_train, n, Y_test, nullptr, 0, true, observed, dist2, index, x_near);
 }
 
+// The k nearest rows in latent space (csrc/knn.hip).  Nothing of the evaluation is read or written: only the resident X_mu (a NULL side) and the
+// plan's buffers.  Every argument is checked before anything is launched.
+extern "C" int gp_knn_rows(gp_ctx* c, int64_t n_train, const double* X_train, int64_t n, const double* X, const double* weight, int k, const int64_t* skip,
+                           int flags, double* dist2, int64_t* rows) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: n must be >= 0");
+  if (X_train && n_train < 0) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: n_train must be >= 0");
+  if (k < 1) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: k must be >= 1");
+  if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: unknown flags 0x%x (bit 0: every query leaves out its own row)", flags);
+  const bool self = (flags & 1) != 0;
+  if (self && (X_train || X)) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: bit 0 of flags needs the resident rows on both sides (X_train and X NULL)");
+  if (self && skip) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: skip and bit 0 of flags are alternatives");
+  if (k > 32) return fail(c, GP_ERR_UNSUPPORTED, "gp_knn_rows: k = %d, at most 32 neighbours per query", k);
+  if (!X_train) {
+    n_train = c->N;       // the resident rows are all of them: only their presence is left to check
+    GP_TRY(resident_rows_check(c, "gp_knn_rows", "X_train is NULL (the resident X_mu)", n_train));
+  }
+  if (!X) GP_TRY(resident_rows_check(c, "gp_knn_rows", "X is NULL (the resident X_mu as queries)", n));
+  if (X) GP_TRY(finite_check(c, "gp_knn_rows", "X", X, (size_t)n * c->Q));
+  if (X_train) GP_TRY(finite_check(c, "gp_knn_rows", "X_train", X_train, (size_t)n_train * c->Q));
+  for (int q = 0; weight && q < c->Q; ++q)
+    if (!(weight[q] >= 0.0) || !std::isfinite(weight[q])) return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: weight must be finite and >= 0");
+  for (int64_t i = 0; skip && i < n; ++i)
+    if (skip[i] < -1 || skip[i] >= n_train)
+      return fail(c, GP_ERR_BAD_ARG, "gp_knn_rows: skip[%lld] = %lld is outside -1 .. n_train - 1 = %lld", (long long)i, (long long)skip[i], (long long)n_train - 1);
+  if (n == 0 || (!dist2 && !rows)) return GP_OK;
+  if (n_train == 0) {
+    if (dist2) std::fill(dist2, dist2 + n * k, std::numeric_limits<double>::infinity());
+    if (rows) std::fill(rows, rows + n * k, (int64_t)-1);
+    return GP_OK;
+  }
+  GP_HIP(c, hipSetDevice(c->device));
+  return run_knn(c, (long)n_train, X_train, (long)n, X, weight, k, skip, self, dist2, rows);
+}
+
 // ---- final gradients ---------------------------------------------------------------------------------------------
 // final = Kmm parts (global step) + all-reduced data parts (phase 2)
 __global__ void add_kernel(const double* a, const double* b, double* out, long n) {
@@ -1301,6 +1336,8 @@ extern "C" int gp_debug_set_option(const char* name, int value) {
   if (!std::strcmp(name, "paths_rows")) { g_opt_paths_rows.store(std::max(0, value)); return GP_OK; }
   // and the curves per chunk of gp_curve_energy (curve.hip, 0 = the default)
   if (!std::strcmp(name, "curve_curves")) { g_opt_curve_curves.store(std::max(0, value)); return GP_OK; }
+  // and the rows per chunk of either side of gp_knn_rows (knn.hip: as given, with shorter tiles and slices; 0 = the defaults)
+  if (!std::strcmp(name, "knn_rows")) { g_opt_knn_rows.store(std::max(0, value)); return GP_OK; }
   // and the host rows per upload chunk of gp_select_begin (select.hip, 0 = the default)
   if (!std::strcmp(name, "select_rows")) { g_opt_sel_rows.store(std::max(0, value)); return GP_OK; }
   std::string known;

@@ -104,6 +104,7 @@ struct SelPlan;    // select.hip
 struct CurvePlan;  // curve.hip
 struct ScorePlan;  // score.hip
 struct LbfgsPlan;  // lbfgs.hip
+struct KnnPlan;    // knn.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -119,6 +120,7 @@ struct SelPlanDelete { void operator()(SelPlan* p) const; };
 struct CurvePlanDelete { void operator()(CurvePlan* p) const; };
 struct ScorePlanDelete { void operator()(ScorePlan* p) const; };
 struct LbfgsPlanDelete { void operator()(LbfgsPlan* p) const; };
+struct KnnPlanDelete { void operator()(KnnPlan* p) const; };
 
 }  // namespace gp
 
@@ -286,6 +288,7 @@ struct gp_ctx {
   std::unique_ptr<gp::CurvePlan, gp::CurvePlanDelete> curve;  // gp_curve_energy's buffers (curve.hip)
   std::unique_ptr<gp::ScorePlan, gp::ScorePlanDelete> score;  // gp_predict_score's buffers (score.hip)
   std::unique_ptr<gp::LbfgsPlan, gp::LbfgsPlanDelete> lbfgs;  // gp_lbfgs_begin .. gp_lbfgs_end: the history vectors (lbfgs.hip)
+  std::unique_ptr<gp::KnnPlan, gp::KnnPlanDelete> knn;        // gp_knn_rows' buffers (knn.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -385,6 +388,9 @@ int run_project(gp_ctx* c, long n, const double* Y, const double* mean, const do
 // nearest.hip
 int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const double* Y_test, const int* cols, int n_cols, const uint8_t* observed,
                 double* dist2, int64_t* index, double* x_near);
+// knn.hip (X_train / X NULL: the resident X_mu on that side; self: every query leaves out its own row; the arguments are checked in api.hip)
+int run_knn(gp_ctx* c, long n_train, const double* X_train, long n, const double* X, const double* weight, int k, const int64_t* skip, bool self,
+            double* dist2, int64_t* rows);
 // compat.hip
 int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 // comm.hip
@@ -411,6 +417,7 @@ extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip
 extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 off, 1 on where the remainder rule admits it, 2 on wherever it fits (measurements)
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
+extern std::atomic<int> g_opt_knn_rows;                       // knn.hip
 extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval
 extern std::atomic<int> g_opt_sel_rows;                       // select.hip: host rows per upload chunk of gp_select_begin
 extern std::atomic<int> g_opt_curve_curves;                   // curve.hip: curves per chunk of gp_curve_energy

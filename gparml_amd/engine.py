@@ -737,6 +737,46 @@ class ShardEngine(object):
             self._ck(self.lib.gp_nearest_rows(self.h, n_train, pt, n, py, pc, nc, *out), 'gp_nearest_rows')
         return dist2, index, x
 
+    # ---- neighbours in latent space (gp_knn_rows) -----------------------------------------------------------------
+    def knn_rows(self, X=None, k=1, X_train=None, weight=None, skip=None, skip_self=False):
+        """Per query row the ``k`` (1 .. 32) nearest training rows in latent space (csrc/knn.hip): the queries ``X`` (n, Q), or the resident X_mu
+        of this engine (``X`` None), against the host rows ``X_train`` (n_train, Q), or the resident X_mu (``X_train`` None), in the squared
+        distance sum_q weight_q (x_q - t_q)^2 (``weight`` (Q,) finite and >= 0, None: Euclidean; the ARD alpha: the kernel's own metric).
+        ``skip`` (n,) int: per query one training row that is left out (-1: none); ``skip_self`` (both sides resident): every query leaves out
+        its own row.  Returns (dist2 (n, k), rows (n, k) int64): ascending in (dist2, row), an equal distance goes to the lower row; slots
+        beyond the available rows hold -1 and inf.  A query's lists do not depend on the other queries, bit for bit.  Shards merge on the host
+        (gparml_amd.init.knn).  The evaluation state is left untouched."""
+        def rows_arg(A, name):
+            if A is None:
+                return None, None, self.N_s
+            A = np.asarray(A, dtype=np.float64)
+            if A.ndim == 1:
+                A = A.reshape(-1, self.Q)
+            assert A.ndim == 2 and A.shape[1] == self.Q, '%s shape %s: (n, %d) expected' % (name, A.shape, self.Q)
+            A, pa = _lib.as_c(A)
+            return A, pa, A.shape[0]
+        X, px, n = rows_arg(X, 'X')
+        X_train, pt, n_train = rows_arg(X_train, 'X_train')
+        pw = None
+        if weight is not None:
+            weight = np.asarray(weight, dtype=np.float64).reshape(-1)
+            assert weight.shape == (self.Q,), 'weight shape %s: (%d,) expected' % (weight.shape, self.Q)
+            weight, pw = _lib.as_c(weight)
+        ps = None
+        if skip is not None:
+            skip = np.ascontiguousarray(np.asarray(skip).reshape(-1), dtype=np.int64)
+            assert skip.shape == (n,), 'skip shape %s: (%d,) expected' % (skip.shape, n)
+            ps = skip.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        k = int(k)
+        dist2, rows = np.empty((n, max(k, 0))), np.empty((n, max(k, 0)), dtype=np.int64)
+        self._ck(self.lib.gp_knn_rows(self.h, n_train, pt, n, px, pw, k, ps, 1 if skip_self else 0, dist2.ctypes.data_as(_lib._dp),
+                                      rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), 'gp_knn_rows')
+        return dist2, rows
+
+    def knn_queries(self):
+        """The rows ``knn_rows`` searches for with X None (init.knn passes them to the other shards)."""
+        return self.download('X_MU')
+
     @property
     def n_rows(self):
         """Rows ``kmeans_accumulate`` clusters with X None (init.kmeans draws its seeds over them) and ``scatter_accumulate`` sums with Y None."""

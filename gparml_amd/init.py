@@ -20,6 +20,10 @@ per shard the column sums and the Gram matrix of the rows shifted by a centre, `
 Nearest start (the end of this file).  ``predict.test`` starts every new point at the trained embedding of the training output nearest to it,
 searched shard by shard with a k-d tree on the host (predict.py:44-66).  ``ShardEngine.nearest_rows`` (csrc/nearest.hip) yields per shard and new
 row the least squared distance and its row; ``nearest_start`` takes the minimum over shards and ranks with the reference's tie rule and cut-off.
+
+Neighbours in latent space (after it).  ``ShardEngine.knn_rows`` (csrc/knn.hip) yields per shard and query the k nearest rows of the embedding,
+optionally in the ARD metric and without the query's own row; ``knn_merge`` / ``knn`` merge the shards' lists by (distance, shard, row) on the host
+and ``knn_vote`` turns the neighbours' labels into the k-NN classification that GPLVM papers score an embedding by.
 """
 import numpy
 
@@ -38,6 +42,15 @@ class HostRows(object):
 
     def take_rows(self, idx):
         return self.X[numpy.asarray(idx, dtype=numpy.int64)]
+
+    # knn: the rows of this part are the training rows; without queries they are the queries too
+    def knn_rows(self, X=None, k=1, weight=None, skip_self=False):
+        assert X is None or not skip_self, 'knn_rows: skip_self needs the part\'s own rows as queries'
+        skip = numpy.arange(self.n_rows, dtype=numpy.int64) if skip_self else None
+        return self.engine.knn_rows(X=self.X if X is None else X, k=k, X_train=self.X, weight=weight, skip=skip)
+
+    def knn_queries(self):
+        return self.X
 
     # greedy_select: the selection lives in the engine, one at a time -- every part of one call needs an engine of its own
     def select_begin(self, K, sf2, alpha, tol=1e-10):
@@ -357,3 +370,62 @@ def nearest_start(parts, Y_test, cols=None, cutoff=6.0, allreduce=None, rank=0, 
     far = ~(dist < cutoff)
     X[far], owner[far], index[far] = 0.0, -1, -1
     return X, dist, owner, index
+
+
+# ------------------------------------------------------------------------------------------------- neighbours in latent space
+def knn_merge(lists, k):
+    """Merges per-shard neighbour lists into one: ``lists`` holds per shard (dist2 (n, k_s), rows (n, k_s)) as ``ShardEngine.knn_rows`` returns
+    them (row -1: an empty slot).  Returns (dist2 (n, k), shard (n, k), row (n, k)): per query the k least of all pairs in the order
+    (dist2, shard, row), ascending; slots beyond the available rows hold inf, -1, -1.  Pure numpy."""
+    k = int(k)
+    d2 = numpy.concatenate([numpy.asarray(d, dtype=numpy.float64).reshape(len(d), -1) for d, _ in lists], axis=1)
+    row = numpy.concatenate([numpy.asarray(r, dtype=numpy.int64).reshape(len(r), -1) for _, r in lists], axis=1)
+    shard = numpy.concatenate([numpy.full(numpy.asarray(r).reshape(len(r), -1).shape, s, dtype=numpy.int64) for s, (_, r) in enumerate(lists)], axis=1)
+    empty = row < 0
+    d2 = numpy.where(empty, numpy.inf, d2)
+    # lexsort: the last key is the primary one; an empty slot comes behind every row, also behind one at an infinite distance
+    order = numpy.lexsort((row, shard, empty, d2), axis=1)[:, :k]
+    take = lambda a: numpy.take_along_axis(a, order, axis=1)
+    d2, shard, row = take(d2), numpy.where(take(empty), -1, take(shard)), take(row)
+    if d2.shape[1] < k:
+        pad = ((0, 0), (0, k - d2.shape[1]))
+        d2, shard, row = numpy.pad(d2, pad, constant_values=numpy.inf), numpy.pad(shard, pad, constant_values=-1), numpy.pad(row, pad, constant_values=-1)
+    return d2, shard, row
+
+
+def knn(parts, X, k, weight=None, skip_self=False):
+    """The ``k`` nearest training rows of every query over all shards: (dist2 (n, k), shard (n, k), row (n, k)), ascending in
+    (dist2, shard, row); slots beyond the available rows hold inf, -1, -1.
+
+    parts: objects with ``knn_rows(X, k, weight=, skip_self=)`` and ``knn_queries()``: ShardEngines (their resident X_mu are the training rows),
+    or ``HostRows`` for host rows passed through an engine.  ``X`` (n, Q): the queries.  ``X`` None: every shard's own rows are the queries, in
+    shard order (n = all rows), each searched in every shard; with ``skip_self`` a query's own row is left out -- only in its own shard, where
+    it is a row.  ``weight`` (Q,): the metric sum_q weight_q (x_q - t_q)^2 (None: Euclidean).
+    The parts are those of THIS process: merging across the ranks of a dist_group is not done here."""
+    parts = list(parts)
+    assert parts, 'knn: no parts'
+    if X is not None:
+        assert not skip_self, 'knn: skip_self needs the shards\' own rows as queries (X None)'
+        return knn_merge([p.knn_rows(X, k, weight=weight) for p in parts], k)
+    out = []
+    for i, p in enumerate(parts):
+        Xi = p.knn_queries() if len(parts) > 1 else None
+        out.append(knn_merge([q.knn_rows(None, k, weight=weight, skip_self=skip_self) if j == i else q.knn_rows(Xi, k, weight=weight)
+                              for j, q in enumerate(parts)], k))
+    return tuple(numpy.concatenate([o[a] for o in out], axis=0) for a in range(3))
+
+
+def knn_vote(labels_of_neighbours, dist2=None):
+    """k-NN classification from neighbour lists: ``labels_of_neighbours`` (n, k) holds the labels of every query's neighbours, nearest first;
+    slots whose ``dist2`` (n, k) is not finite are empty (None: none is).  Returns (n,) the majority label of every query; a tie goes to the tied
+    label whose nearest member comes first in the list; -1 for a query without neighbours."""
+    L = numpy.asarray(labels_of_neighbours)
+    L = L.reshape(len(L), -1)
+    valid = numpy.ones(L.shape, dtype=bool) if dist2 is None else numpy.isfinite(numpy.asarray(dist2, dtype=numpy.float64).reshape(L.shape))
+    # votes[i, j]: the members of query i's list that carry the label of slot j; argmax takes the first slot of the largest count
+    votes = ((L[:, :, None] == L[:, None, :]) & valid[:, None, :]).sum(axis=2) * valid
+    if L.shape[1] == 0:
+        return numpy.full(len(L), -1, dtype=numpy.int64)
+    best = numpy.argmax(votes, axis=1)
+    out = L[numpy.arange(len(L)), best]
+    return numpy.where(valid.any(axis=1), out, -1)

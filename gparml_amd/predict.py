@@ -228,6 +228,25 @@ class Predictor(object):
         res['evaluations'] = info['evaluations']
         return res
 
+    def knn(self, X, k, training, weight='alpha'):
+        """The ``k`` nearest training embeddings of every latent point of ``X`` (n, Q): (dist2 (n, k), shard (n, k), row (n, k)), ascending in
+        (dist2, shard, row) (gparml_amd.init.knn; csrc/knn.hip).  ``training``: the iterable of (Y_shard, X_shard) pairs ``infer`` takes (only
+        the embeddings X_shard are read), shard = its position there.  ``weight='alpha'``: the distance sum_q alpha_q (x_q - t_q)^2 in the
+        trained kernel's own metric; ``None``: Euclidean; or a (Q,) array.  The search is in latent space: starts for ``infer`` from several
+        neighbours, geodesic graphs for ``geodesic``, local subsets.  The shards of this process only: nothing is merged across ranks."""
+        from . import init
+        cls = self._engine_cls
+        if cls is None:
+            from .engine import ShardEngine as cls
+        if isinstance(weight, str):
+            assert weight == 'alpha', "knn: weight must be 'alpha', None or a (Q,) array, got %r" % (weight,)
+            weight = numpy.asarray(self.gs['alpha'], dtype=float).reshape(-1)
+        eng = cls(1, self.D, self.M, self.Q, device=self.device)         # host rows on both sides: no model, no shard
+        try:
+            return init.knn([init.HostRows(eng, Xs) for _, Xs in training], X, k, weight=weight)
+        finally:
+            eng.close()
+
     def _trained_engine(self):
         """An engine that holds the trained model: the globals, the stored accumulated statistics of the training data and a global step on them."""
         cls = self._engine_cls

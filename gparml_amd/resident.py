@@ -182,6 +182,34 @@ class ResidentModel(object):
         assert method == 'kmeans', "init_Z: method must be 'kmeans' or 'greedy', got %r" % (method,)
         return init.kmeans(self.engines, K, **kw)
 
+    def knn_training(self, k, labels=None, weight='alpha', flat_array=None):
+        """The ``k`` nearest neighbours of every training row among all the others, in latent space, over the resident X_mu of every shard of
+        this process (gparml_amd.init.knn on the engines: nothing is downloaded but the shards' means, which the other shards search for).
+        ``weight='alpha'``: the distance sum_q alpha_q (x_q - t_q)^2 in the kernel's own metric, with the ARD alpha of ``flat_array`` (None: the
+        vector of the last evaluation or prediction), so that a dimension the model switched off counts for nothing; ``None``: Euclidean; or a
+        (Q,) array.  Returns (dist2 (N, k), shard (N, k), row (N, k)) in shard order.  With ``labels`` (N,) in shard order, or one array per
+        shard, it returns the leave-one-out k-NN classification error instead: the fraction of rows whose label differs from the majority label of
+        their k neighbours (init.knn_vote's tie rule).  The shards of THIS process only: merging across the ranks of a dist_group is not done."""
+        from . import init
+        if isinstance(weight, str):
+            assert weight == 'alpha', "knn_training: weight must be 'alpha', None or a (Q,) array, got %r" % (weight,)
+            if flat_array is None:
+                assert self._stats_x is not None, 'knn_training: no evaluation or prediction yet: pass flat_array (or a weight)'
+                flat_array = self._stats_x
+            weight = split_flat(transform_vec(self._pos, np.asarray(flat_array, dtype=np.float64)), self.M, self.Q)[2]
+        d2, shard, row = init.knn(self.engines, None, k, weight=weight, skip_self=True)
+        if labels is None:
+            return d2, shard, row
+        if isinstance(labels, (list, tuple)):
+            per = [np.asarray(l).reshape(-1) for l in labels]
+        else:
+            cuts = np.cumsum([e.N_s for e in self.engines])[:-1]
+            per = np.split(np.asarray(labels).reshape(-1), cuts)
+        assert [len(l) for l in per] == [e.N_s for e in self.engines], 'knn_training: labels do not match the shards'
+        allv, start = np.concatenate(per), np.concatenate([[0], np.cumsum([len(l) for l in per])])
+        neigh = allv[np.where(row >= 0, start[np.maximum(shard, 0)] + row, 0)]
+        return float(np.mean(init.knn_vote(neigh, d2) != allv))
+
     def init_X(self):
         """Initial embeddings for this model by PCA over the resident Y of every shard of every rank (gparml_amd.init.pca on the engines, Y = None:
         nothing is uploaded but the result): supporting_functions.PCA over ALL data, as the reference insists (local_MapReduce.py:50-65).  The

@@ -471,6 +471,34 @@ int gp_nearest_rows_masked(gp_ctx* ctx, int64_t n_train, const double* Y_train, 
                            int64_t n, const double* Y_test, const uint8_t* observed,   /* (n,D), nonzero = observed */
                            double* dist2, int64_t* index, double* x_near);
 
+/* ---- k nearest rows in latent space -------------------------------------------------------------------- */
+/* The neighbours of points in latent space: for each of the n query rows X (n,Q) the k training rows of least weighted squared distance
+ * d2(i,t) = sum_q w_q e_q^2, e_q = x_iq - t_q -- the leave-one-out nearest-neighbour figure of a trained embedding, restarts of the latent inference,
+ * geodesic graphs, local subsets.  Either side may be the context's resident embedding means: X_train == NULL: the resident X_mu (n_train is
+ * ignored); X == NULL: the resident X_mu as queries (n must equal N_s); they are read exactly as gp_kmeans_accumulate reads them with X == NULL,
+ * and the same rows passed as host arrays (the download of GP_ARR_X_MU) give the same bits.  Host rows are taken in chunks through the library's
+ * own buffers.  weight (Q), finite and >= 0 (NULL: all 1): with the ARD alpha the distance is the kernel's own metric.
+ * Distance: the direct form, difference first, q ascending: acc = fma(e, e, acc) without weights; with them p = w_q * e rounded once, then
+ * acc = fma(p, e, acc) (never |x|^2 - 2 x.t + |t|^2, whose cancellation decides near-ties).
+ * Order: a query's list is the k training rows that are least in the pair (d2, row), compared lexicographically, ascending: an equal distance
+ * goes to the lower row index at every level (csrc/knn.hip).  skip (n) or NULL: per query one training row that is left out, -1 = none; bit 0 of
+ * flags (both sides resident): every query leaves out its own row.  Outputs dist2 (n,k) and rows (n,k), either may be NULL; where fewer than k
+ * rows are available (n_train small, a row left out) the remaining slots hold rows = -1 and dist2 = +inf.  1 <= k <= 32 (beyond:
+ * GP_ERR_UNSUPPORTED); any Q.
+ * Determinism: a query's outputs depend on that query, the training rows, the weights and its skip entry only: the same bits alone, in any batch,
+ * in any query order, wherever a chunk or slice boundary of either side falls, and from run to run; there are no atomics.  Synchronous.  Needs an
+ * uploaded shard only when a side is NULL (GP_ERR_STATE before), no global step.  Leaves the evaluation state untouched: gp_phase2 / gp_finish /
+ * gp_predict after it give bit-identical results.  GP_ERR_BAD_ARG, decided before anything is launched, for n < 0, n_train < 0, k < 1, unknown
+ * flags, bit 0 without both sides NULL or together with skip, a resident query side with n != N_s, a non-finite X or X_train, a weight that is
+ * not finite and >= 0, and a skip entry outside [-1, n_train).  n = 0 writes nothing; n_train = 0 writes the padding.  The merge over shards is
+ * the caller's (gparml_amd/init.py: knn). */
+int gp_knn_rows(gp_ctx* ctx, int64_t n_train, const double* X_train,   /* (n_train,Q); NULL: the resident X_mu, n_train ignored */
+                int64_t n, const double* X,                            /* (n,Q); NULL: the resident X_mu as queries, n must equal N_s */
+                const double* weight,                                  /* (Q) finite and >= 0; NULL = all 1 */
+                int k, const int64_t* skip,                            /* (n) or NULL: per query one training row to leave out, -1 = none */
+                int flags,                                             /* bit 0: both sides resident -> every query leaves out its own row */
+                double* dist2, int64_t* rows);                         /* (n,k), (n,k) */
+
 /* ---- results ---------------------------------------------------------------------------------- */
 int gp_download(gp_ctx* ctx, int which, double* dst, int64_t n_doubles);
 /* set the reduced statistics from the host (partial_terms.set_local_statistics, partial_terms.py:54-61) */
