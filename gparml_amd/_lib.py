@@ -60,6 +60,7 @@ SIGNATURES = {
     'gp_set_local_statistics': (ctypes.c_int, [_vp, ctypes.c_double, _dp, _dp, ctypes.c_double, ctypes.c_double]),
     'gp_predict': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]),
     'gp_predict_score': (ctypes.c_int, [_vp, _i64, _dp, _dp, ctypes.c_int, _dp, _u8p, ctypes.c_int, _dp, _dp, _dp, _dp]),
+    'gp_loo_score': (ctypes.c_int, [_vp, ctypes.c_int, _u8p, ctypes.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     'gp_predict_joint': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_predict_sample': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, _dp, _dp, _dp]),
     'gp_predict_grad': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),

@@ -783,6 +783,21 @@ extern "C" int gp_predict_score(gp_ctx* c, int64_t n, const double* X_mu, const 
   return run_predict_score(c, (long)n, X_mu, X_S, xs_is_raw ? 1 : 0, resident, (flags & 2) != 0, Y, observed, flags, row_logp, row_sse, row_chi2, cols);
 }
 
+// ---- leave-one-out / leave-block-out scoring of the resident rows (loo.hip): the argument errors first, then gp_predict_score's state rule ----
+extern "C" int gp_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* lev,
+                            double* var_loo, double* cols) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (block < 1 || block > 128) return fail(c, GP_ERR_BAD_ARG, "gp_loo_score: block must be 1 .. 128, got %d", block);
+  if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_loo_score: unknown flags %d", flags);
+  GP_TRY(model_ready(c, "gp_loo_score"));
+  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_loo_score: the resident rows before gp_upload_shard");
+  if (!c->regime_A)
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_loo_score: the shard has embeddings of non-zero variance: such a row contributes a full-rank psi2 to "
+                "Kmm + beta Psi2, and leaving it out is not a rank-one downdate (fixed embeddings only)");
+  if (!row_logp && !row_sse && !row_chi2 && !lev && !var_loo && !cols) return GP_OK;
+  return run_loo_score(c, block, observed, flags, row_logp, row_sse, row_chi2, lev, var_loo, cols);
+}
+
 // gp_predict_joint / gp_predict_sample: gp_predict's preconditions and argument errors for deterministic inputs, then the size limit
 static int joint_check(gp_ctx* c, const char* who, int64_t n, const double* X, int flags, int64_t n_max, bool* nothing) {
   *nothing = true;

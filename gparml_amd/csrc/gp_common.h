@@ -105,6 +105,7 @@ struct CurvePlan;  // curve.hip
 struct ScorePlan;  // score.hip
 struct LbfgsPlan;  // lbfgs.hip
 struct KnnPlan;    // knn.hip
+struct LooPlan;    // loo.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -121,6 +122,7 @@ struct CurvePlanDelete { void operator()(CurvePlan* p) const; };
 struct ScorePlanDelete { void operator()(ScorePlan* p) const; };
 struct LbfgsPlanDelete { void operator()(LbfgsPlan* p) const; };
 struct KnnPlanDelete { void operator()(KnnPlan* p) const; };
+struct LooPlanDelete { void operator()(LooPlan* p) const; };
 
 }  // namespace gp
 
@@ -289,6 +291,7 @@ struct gp_ctx {
   std::unique_ptr<gp::ScorePlan, gp::ScorePlanDelete> score;  // gp_predict_score's buffers (score.hip)
   std::unique_ptr<gp::LbfgsPlan, gp::LbfgsPlanDelete> lbfgs;  // gp_lbfgs_begin .. gp_lbfgs_end: the history vectors (lbfgs.hip)
   std::unique_ptr<gp::KnnPlan, gp::KnnPlanDelete> knn;        // gp_knn_rows' buffers (knn.hip)
+  std::unique_ptr<gp::LooPlan, gp::LooPlanDelete> loo;        // gp_loo_score's buffers (loo.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -352,6 +355,9 @@ int run_predict(gp_ctx* c, long n, const double* X_mu, const double* X_S, int ra
 // score.hip
 int run_predict_score(gp_ctx* c, long n, const double* X_mu, const double* X_S, int raw, bool resident, bool resident_S, const double* Y,
                       const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* cols);
+// loo.hip (the arguments have been checked: api.hip)
+int run_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* lev,
+                  double* var_loo, double* cols);
 // joint.hip
 int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
 int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);
@@ -410,6 +416,8 @@ int check_global_from(gp_ctx* c, const double* h);
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A /*in: SPD, out: L*/, double* Linv, double* Inv,
                           double* Twork /*batch * Mp * Mp / 2 doubles*/, double* logdet2 /*device, [batch]*/, double* fail_flag /*device, [batch]*/,
                           double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0, bool factor_only = false);
+int potrf_trinv128_tiles(gp_ctx* c, hipStream_t st, int tiles, double* A /*[tiles][128][128] in: SPD, out: L*/, double* Linv, double* fail /*[tiles], zero*/,
+                         double* logdet2 /*[tiles], zero*/);
 // the options of gp_debug_set_option (api.hip holds the table and the ones without a home file), each next to the code it switches
 extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
 extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip

@@ -58,6 +58,14 @@ __global__ void __launch_bounds__(256) panel_copy_kernel(const double* __restric
   }
 }
 
+// `tiles` independent 128 x 128 SPD matrices, stored one after the other with row stride 128: each factorised in place (lower factor, upper part
+// zeroed), its inverse factor into the same place of Linv.  fail [tiles] and logdet2 [tiles] must hold zeros on entry: the kernel raises / adds.
+int potrf_trinv128_tiles(gp_ctx* c, hipStream_t st, int tiles, double* A, double* Linv, double* fail, double* logdet2) {
+  GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
+  GP_LAUNCH(c, st, potrf_trinv128_kernel, dim3((unsigned)tiles), dim3(512), POTRF_LDS_DOUBLES * 8, A, (long)NB, (long)NB * NB, 0, Linv, fail, logdet2);
+  return GP_OK;
+}
+
 // A: [batch][Mp][Mp] SPD in, lower Cholesky factor out (upper zeroed); Linv: L^-1; Inv: A^-1; Twork: batch * Mp * Mp / 2 doubles
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A, double* Linv, double* Inv, double* Twork,
                           double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap, bool factor_only) {

@@ -98,6 +98,9 @@ __device__ __forceinline__ int t16_col(int j, int lane) { return 4 * j + (lane &
 constexpr int LSLD = 34;   // row stride of the spare copy of L_ss
 constexpr int POTRF_LDS_DOUBLES = NB * PLD + 32 + 32 * LSLD + NB;
 
+// POTRF128_NO_KERNEL: the constants and the LDS tile helpers alone, for a second translation unit (loo.hip) that runs the kernel through
+// linalg.hip's potrf_trinv128_tiles -- a __global__ function has one home
+#ifndef POTRF128_NO_KERNEL
 __global__ void __launch_bounds__(512) potrf_trinv128_kernel(double* A, long ld, long bstride, int j, double* Linv, double* fail,
                                                              double* logdet2) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
@@ -336,5 +339,6 @@ __global__ void __launch_bounds__(512) potrf_trinv128_kernel(double* A, long ld,
     }
   }
 }
+#endif  // POTRF128_NO_KERNEL
 
 }  // namespace gp

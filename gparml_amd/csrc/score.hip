@@ -27,29 +27,11 @@
 // Buffers: ScorePlan, built aside and published whole; every element is written before it is read (DA_RAW: NaN-filled in the poison test mode).
 #include "pred_chunk.h"
 #include "lane_reduce.h"
+#include "score_term.h"
 #include <algorithm>
-#include <climits>
 #include <cmath>
 
 namespace gp {
-
-constexpr int SC_SEG = 128;       // rows per segment of the column sums (= TILE: a chunk is a whole number of segments)
-constexpr int SC_DW = 128;        // columns per workgroup of the column pass
-constexpr long long SC_NONE = LLONG_MAX;
-static_assert(SC_SEG == TILE, "gp_predict's chunks are multiples of TILE rows: a segment never straddles two chunks");
-
-struct ScoreTerm { double e, e2, q, lp; };
-// the terms of one scored entry; NaN, all four, when the variance is not > 0
-__device__ __forceinline__ ScoreTerm score_term(double y, double m, double v) {
-#pragma clang fp contract(off)
-  ScoreTerm t;
-  t.e = y - m;
-  t.e2 = t.e * t.e;
-  t.q = t.e2 / v;
-  t.lp = -0.5 * (log(6.283185307179586476925286766559 * v) + t.q);
-  if (!(v > 0.0)) t.e = t.e2 = t.q = t.lp = __builtin_nan("");
-  return t;
-}
 
 struct ScoreArgs {
   const double* G;          // [rows][ldg] the chunk's products: mean in columns 0 .. D, deterministic inputs [Lk^-1 k | La^-1 k] behind Dp

@@ -390,6 +390,39 @@ class ShardEngine(object):
             raise
         return out
 
+    # ---- leave-one-out / leave-block-out scoring of the resident rows (gp_loo_score) ----------------------------
+    def loo(self, block=1, observed=None, include_noise=True, want_rows=True):
+        """Exact leave-one-out (``block`` = 1) or leave-block-out cross-validation of the engine's resident rows, on the device (gp_loo_score): row i
+        is predicted by the model that never saw the rows of its block -- rows [j block, (j + 1) block) of THIS shard form block j, 1 <= block <= 128;
+        for other folds order the rows before the upload -- with the hyper-parameters and inducing points fixed, and scored as ``score`` scores.
+        Fixed embeddings only; the engine's statistics must contain these rows (the caller's obligation: the library cannot tell).
+        ``observed`` (N_s, D): non-zero where an entry is summed (it never enters the downdate); None: every entry.  ``include_noise`` scores y.
+        Returns the dict of ``score`` -- ``row_logp``, ``row_sse``, ``row_chi2`` (None without ``want_rows``), ``cols`` (D, 5) and
+        ``score_summary``'s figures of it -- with ``lev`` (N_s,) the leverages beta |La^-1 k_i|^2 and ``var_loo`` (N_s,) the leave-out variances.
+        LinAlgError when a block cannot be left out (I - H does not factorise), FloatingPointError when a leave-out variance is not > 0: the
+        exception's ``result`` holds the dict, NaN in the rows concerned."""
+        n = self.N_s
+        po = None
+        if observed is not None:
+            observed = np.ascontiguousarray(np.atleast_2d(np.asarray(observed)) != 0, dtype=np.uint8)
+            assert observed.shape == (n, self.D), 'observed shape %s: (%d, %d) expected' % (observed.shape, n, self.D)
+            po = observed.ctypes.data_as(_lib._u8p)
+        rows = [np.empty(n) for _ in range(3)] if want_rows else [None] * 3
+        lev, var, cols = np.empty(n), np.empty(n), np.empty((self.D, 5))
+        dp = lambda a: a.ctypes.data_as(_lib._dp) if a is not None else None          # noqa: E731
+        rc = self.lib.gp_loo_score(self.h, int(block), po, 1 if include_noise else 0, dp(rows[0]), dp(rows[1]), dp(rows[2]), dp(lev), dp(var), dp(cols))
+        if rc not in (_lib.GP_ERR_NON_FINITE, _lib.GP_ERR_NOT_PD):
+            self._ck(rc, 'gp_loo_score')
+        out = self.score_summary(cols)
+        out['row_logp'], out['row_sse'], out['row_chi2'] = rows
+        out['lev'], out['var_loo'] = lev, var
+        try:
+            self._ck(rc, 'gp_loo_score')
+        except (FloatingPointError, np.linalg.LinAlgError) as err:
+            err.result = out
+            raise
+        return out
+
     # ---- joint prediction (gp_predict_joint, gp_predict_sample) ------------------------------------------------
     def _joint_X(self, X):
         X = np.atleast_2d(np.asarray(X, dtype=np.float64))

@@ -150,6 +150,25 @@ class ResidentModel(object):
             out[k] = np.concatenate([p[k] for p in parts]) if want_rows else None
         return out
 
+    def loo_training(self, block=1, flat_array=None, include_noise=True, want_rows=True):
+        """Exact leave-one-out (``block`` = 1) or leave-block-out cross-validation of the training rows where they lie (ShardEngine.loo on every
+        shard of this process), for the model at ``flat_array`` (None: the vector of the last evaluation or prediction) with its hyper-parameters
+        and inducing points held fixed.  Blocks are PER SHARD: rows [j block, (j + 1) block) of a shard; for other folds order the rows before
+        the upload.  The statistics are brought up to date on every engine as ``score_training`` does (COLLECTIVE across ranks).  Returns the dict
+        of ``ShardEngine.loo``: row values, ``lev`` and ``var_loo`` concatenated in shard order (this process's rows); ``cols`` added over the
+        shards and over the ranks (one vector all-reduce) with ``score_summary``'s figures of the sum.  Fixed embeddings only."""
+        assert self.fixed_embeddings, 'loo_training: fixed embeddings only (leaving out a row with a free embedding is not a rank-one downdate)'
+        if flat_array is None:
+            assert self._stats_x is not None, 'loo_training: no evaluation or prediction yet: pass flat_array'
+            flat_array = self._stats_x
+        self._refresh_statistics(flat_array, all_engines=True)
+        parts = [e.loo(block=block, include_noise=include_noise, want_rows=want_rows) for e in self.engines]
+        cols = self._allreduce_vector(sum(p['cols'] for p in parts).reshape(-1)).reshape(self.D, 5)
+        out = ShardEngine.score_summary(cols)
+        for k in ('row_logp', 'row_sse', 'row_chi2', 'lev', 'var_loo'):
+            out[k] = np.concatenate([p[k] for p in parts]) if (want_rows or k in ('lev', 'var_loo')) else None
+        return out
+
     _stats_all = False          # every engine holds the model of _stats_x (an evaluation, or a refresh with all_engines), not the root alone
 
     def _refresh_statistics(self, flat_array, all_engines=False):

@@ -223,6 +223,40 @@ int gp_predict_score(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X
                      const uint8_t* observed /*(n,D) or NULL = all*/, int flags, double* row_logp /*(n)*/, double* row_sse /*(n)*/,
                      double* row_chi2 /*(n)*/, double* cols /*(D,5)*/);
 
+/* Exact leave-one-out and leave-block-out cross-validation of the context's resident rows (X_mu and Y as uploaded, n = N_s), reduced on the device as
+ * gp_predict_score reduces (csrc/loo.hip).  Fixed embeddings and fixed Z, sf2, alpha, beta: with k_i = psi1(x_i), a_i = Lk^-1 k_i,
+ * b_i = La^-1 k_i, m_i = k_i^T W and e_i = y_i - m_i as in gp_predict_joint, row i contributes beta k_i k_i^T to A = Kmm + beta Psi2 and k_i y_i^T to
+ * Psi1^T Y, so Titsias' optimal q(u) of "all data minus the rows of block G" is a rank-g downdate.  Rows [j block, (j + 1) block) form block j (the last
+ * one may be short), 1 <= block <= 128.  With B_G (g,M) the block's rows b_i, H = beta B_G B_G^T and S = I - H:
+ *   E'_G  = S^-1 E_G                                      (g,D) y minus the mean of the model that never saw G
+ *   v'_i  = sf2 - |a_i|^2 + ([S^-1]_ii - 1) / beta        the variance of f at x_i under that model; flags bit 0 adds 1/beta          var_loo (N_s)
+ *   lev_i = H_ii = beta |b_i|^2                           the leverage of row i                                                       lev (N_s)
+ * (block = 1: e' = e / (1 - h), v' = sf2 - |a|^2 + |b|^2 / (1 - h), h = lev).  A jitter the global step added is part of A and Kmm: the identities
+ * hold for the model as factored.  Every OBSERVED entry (i,d) is scored under its own marginal Gaussian N(., v'_i) exactly as gp_predict_score scores:
+ * logp = -1/2 (ln(2 pi v') + e'^2 / v'), each operation rounded once; row_logp, row_sse, row_chi2 (N_s) and cols (D,5) = [count, sum e', sum e'^2,
+ * sum e'^2 / v', sum logp] are gp_predict_score's.  This is the marginal density per entry, not the joint density of a block.
+ * observed (N_s,D) or NULL selects the entries that are summed; it is never an input to H (the model was trained on every entry).  A row with no
+ * observed entry scores 0.  Any output pointer may be NULL; a subset gives the bits of the full call.  Nothing of size N_s x D crosses the bus apart
+ * from the mask.
+ * THE STATISTICS MUST CONTAIN THESE ROWS.  The library cannot tell whether they do: statistics set from elsewhere (gp_set_local_statistics) or a
+ * reduce that left this shard out make the downdate meaningless.  That is the caller's obligation.
+ * State rule, gp_predict_score's word for word: GP_ERR_STATE unless the last global step succeeded on the statistics and globals as they are now;
+ * synchronous; the evaluation state is left untouched, so gp_phase2 / gp_finish / gp_predict* after it give bit-identical results.  In addition
+ * GP_ERR_STATE when no shard is uploaded, GP_ERR_UNSUPPORTED when the shard is not in the fixed-embedding regime (a row whose q(x) has non-zero
+ * variance contributes a full-rank psi2: the downdate is not rank one), GP_ERR_BAD_ARG, before anything is launched, for block outside 1 .. 128 or
+ * unknown flags.
+ * A block whose S does not factorise (the model without it is not proper: GP_ERR_NOT_PD) or a row with v' not > 0 (GP_ERR_NON_FINITE): the message
+ * names the first such row, its outputs (lev excepted, which stays valid) and the column sums it enters are NaN, every other row is valid; device
+ * flags written by plain stores, no second pass.  Blocks of at most 64 rows are factorised several at a time (128 / block whole blocks per 128 x 128
+ * tile, by global row index): a block that fails takes the other blocks of its tile with it.
+ * Determinism: bit-identical from run to run, no floating-point atomics; a row's outputs and cols are the same bits whatever the chunk length (chunks
+ * hold whole tiles; the matrix products run on the 128 x 128-tile kernel whatever the chunk's size).  cols adds in gp_predict_score's order: segments
+ * of 128 rows by global row index, ascending.
+ * Not covered: uncertain inputs / free embeddings; blocks of more than 128 rows or non-contiguous blocks (order the rows before the upload); joint
+ * block densities; per-entry residuals returned to the host; re-optimising the hyper-parameters per fold. */
+int gp_loo_score(gp_ctx* ctx, int block, const uint8_t* observed /*(N_s,D) or NULL = all*/, int flags, double* row_logp /*(N_s)*/,
+                 double* row_sse /*(N_s)*/, double* row_chi2 /*(N_s)*/, double* lev /*(N_s)*/, double* var_loo /*(N_s)*/, double* cols /*(D,5)*/);
+
 /* Joint posterior at n new deterministic inputs X (n,Q), after a successful global step as gp_predict.  With k_i = psi1(x_i), a_i = Lk^-1 k_i and
  * b_i = La^-1 k_i (Lk, La the Cholesky factors of Kmm and Kmm + beta Psi2):
  *   mean[i][d] = k_i^T W_d (as gp_predict),   cov[i][j] = k(x_i, x_j) - a_i . a_j + b_i . b_j   (one n x n matrix, shared by all D outputs),
