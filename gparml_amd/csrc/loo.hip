@@ -7,7 +7,7 @@
 //   v'_i  = sf2 - |a_i|^2 + ([S^-1]_ii - 1) / beta (+ 1/beta)   [S^-1]_ii = the squared norm of column i of X
 //   lev_i = beta |b_i|^2
 // and for g = 1: e' = e / (1 - h), v' = sf2 - |a|^2 + |b|^2 / (1 - h), h = lev.  Every observed entry is then scored as gp_predict_score scores it, by
-// the same function (score_term.h) on (e', v').
+// the same passes (score_pass.h: the one definition of the terms, the row sums, the column sums and their order) on (e', v').
 // Per chunk of gp_predict's pipeline, on the resident rows where they lie (X_mu, and Y in the columns of Kaug behind Psi1):
 //   pred_chunk_front, factors on the 128 x 128-tile kernel (on_big: a row's bits do not depend on the chunk it falls in): G = [mean | a | b];
 //   block > 1, per tile of 128 / block whole blocks (block-diagonal, so small blocks share one factorisation; `grp` = the tile's rows):
@@ -16,9 +16,9 @@
 //     potrf_trinv128_kernel (potrf128.h, the global step's own, through linalg.hip's potrf_trinv128_tiles): L and X = L^-1 per tile, LDS-resident;
 //     loo_solve_kernel    [S^-1]_ii from the columns of X; T = X E and E' = X^T T per 128 columns of D, E in LDS, X read as wave-uniform operands,
 //                         k ascending inside the row's block; E' goes to the window buffer [rows][Dp] for the column pass;
-//   loo_rows_kernel: one wave per row: |a|^2, |b|^2 (the order of score_rows_kernel), lev, v', and the three row sums of score_term over the observed d;
-//   loo_cols_kernel / loo_cols_final_kernel: the column sums in gp_predict_score's order -- segments of 128 rows BY GLOBAL ROW INDEX, rows 0 .. 63 and
-//     64 .. 127 ascending, half 0 + half 1, segments ascending into the running total.  block = 1 recomputes e' from (y, m, 1 - h) as the row pass did.
+//   loo_rows_kernel: one wave per row: |a|^2, |b|^2 (fac_norms), lev, v', and score_row_sums over the observed d;
+//   ScoreTotals::add_segments on LooSrc: gp_predict_score's column pass over the window's whole segments -- segments of 128 rows BY GLOBAL ROW INDEX,
+//     segments ascending into the running total.  block = 1 recomputes e' from (y, m, 1 - h) as the row pass did (LooSrc::resid).
 // Chunks hold whole tiles (rows per chunk: gp_predict's, rounded down to a multiple of grp), so a chunk need not end on a segment: the rows behind
 // the last whole segment stay in the window (E', v', mask: moved to its front) and are summed with the next chunk's.  A block's outputs and the
 // column sums are therefore the same bits wherever a chunk boundary falls.
@@ -29,8 +29,7 @@
 #define POTRF128_NO_KERNEL
 #include "potrf128.h"
 #include "pred_chunk.h"
-#include "lane_reduce.h"
-#include "score_term.h"
+#include "score_pass.h"
 #include <algorithm>
 #include <cmath>
 
@@ -146,154 +145,86 @@ __global__ void __launch_bounds__(512) loo_solve_kernel(const double* __restrict
   }
 }
 
-struct LooArgs {
+// The entries of the window: row w = lead + (row of the chunk), lead = the rows of the segment the previous chunk ended in.  e' comes from Ew, or at
+// block = 1 (no E' buffer; the window is the chunk: lead = 0) from (y - m) / den; it is scored as score_term(e', 0, v').
+struct LooSrc {
+  static constexpr int NFLAGS = 2;
+  const double* Ew;         // [window][Dp] E', NULL with block = 1
+  int Dp;
   const double* G;          // [rows][ldg] the chunk's products [mean | Lk^-1 k | La^-1 k]
   long ldg;
   const double* Y;          // the chunk's resident outputs, row stride ldy
   long ldy;
-  long cnt, n0;             // rows of the chunk, global index of its first row
-  long lead;                // window rows ahead of the chunk's first: rows of the segment the previous chunk ended in
-  int M, Mp, D, Dp, block, grp;
-  double sf2, beta, noise;
-  const double* sinv;       // [rows] block > 1: [S^-1]_ii
-  const double* fail;       // [tiles] block > 1: non-zero = the tile's S did not factorise
-  double* den;              // [rows] block = 1: 1 - h, NaN when that is not > 0 (the window is the chunk: lead = 0)
-  // the window: row w = lead + (row of the chunk)
-  const double* Ew;         // [window][Dp] E', NULL with block = 1
+  double* den;              // [rows] block = 1: 1 - h, NaN when that is not > 0
   const uint8_t* obs;       // [window][D] non-zero = scored; NULL: every entry
   double* vw;               // [window] v'
   uint8_t* stw;             // [window] 1 = the row's S did not factorise
-  double* rowo;             // [5][R] row_logp | row_sse | row_chi2 | lev | var_loo of the chunk
-  long R;
-  long wcnt;                // rows in the window
-  double* part;             // [segments][D][5]
-  long long* bad;           // [segments][tiles][2] first row with v' not > 0 | first row whose S did not factorise; SC_NONE without one
+  long rows, g0;            // rows in the window (the column pass: those of its whole segments), global index of its first row (a multiple of SC_SEG)
+  int D;
+  // e' of window row w, column d; dn: the row's 1 - h (used at block = 1 only)
+  __device__ double resid(long w, int d, double dn) const {
+#pragma clang fp contract(off)
+    if (Ew) return Ew[w * Dp + d];
+    return (Y[w * ldy + d] - G[w * ldg + d]) / dn;
+  }
+  __device__ bool scored(long w, int d) const { return !obs || obs[w * D + d]; }
+  __device__ uint8_t unfactorised(long w) const { return stw[w]; }          // the byte as it lies: the column pass tests it after the entry's loads
+  __device__ double var(long w, int) const { return vw[w]; }
+  __device__ ScoreTerm term(long w, int d) const { return score_term(resid(w, d, Ew ? 0.0 : den[w]), 0.0, vw[w]); }
+};
+// the row pass's view of its row: v' and 1 - h (NaN when that is not > 0, as the row pass stores it in den) are still in its registers
+struct LooRow {
+  const LooSrc& s;
+  double v, dn;
+  __device__ bool scored(long w, int d) const { return s.scored(w, d); }
+  __device__ ScoreTerm term(long w, int d) const { return score_term(s.resid(w, d, dn), 0.0, v); }
 };
 
-// e' of window row w, column d; block = 1 (no E' buffer; the window is the chunk): (y - m) / den, den = the row's 1 - h
-__device__ __forceinline__ double loo_resid(const LooArgs& a, long w, int d, double den) {
-#pragma clang fp contract(off)
-  if (a.Ew) return a.Ew[w * a.Dp + d];
-  return (a.Y[w * a.ldy + d] - a.G[w * a.ldg + d]) / den;
-}
+struct LooArgs {
+  LooSrc src;
+  long cnt;                 // rows of the chunk
+  long lead;                // window rows ahead of the chunk's first
+  int M, Mp, block, grp;
+  double sf2, beta, noise;
+  const double* sinv;       // [rows] block > 1: [S^-1]_ii
+  const double* fail;       // [tiles] block > 1: non-zero = the tile's S did not factorise
+  double* rowo;             // [5][R] row_logp | row_sse | row_chi2 | lev | var_loo of the chunk
+  long R;
+};
 
 __global__ void __launch_bounds__(256) loo_rows_kernel(LooArgs a) {
 #pragma clang fp contract(off)
+  const LooSrc& s = a.src;
   const int lane = threadIdx.x & 63;
   const long n = blockIdx.x * 4L + (threadIdx.x >> 6);
   if (n >= a.cnt) return;
   const long w = a.lead + n;
-  const double* g = a.G + n * a.ldg;
-  // score_rows_kernel's sums, operation for operation
-  double sk = 0.0, sb = 0.0;
-  for (int i = lane; i < a.M; i += 64) {
-    const double x = g[a.Dp + i], b = g[a.Dp + a.Mp + i];
-    sk = fma(x, x, sk);
-    sb = fma(b, b, sb);
-  }
-  sk = wave_sum(sk);
-  sb = wave_sum(sb);
-  const double h = a.beta * sb;
+  const FacNorms f = fac_norms(s.G + n * s.ldg, a.M, s.Dp, a.Mp, lane);
+  const double h = a.beta * f.b2;
   double den = 1.0 - h, extra;
   bool ok;
   if (a.block == 1) {
     ok = den > 0.0;
-    extra = sb / den;
+    extra = f.b2 / den;
   } else {
     ok = a.fail[n / a.grp] == 0.0;
     extra = (a.sinv[n] - 1.0) / a.beta;
   }
   const double nan = __builtin_nan("");
-  const double vrow = ok ? a.sf2 - sk + extra + a.noise : nan;
-  if (lane == 0) {
-    if (a.block == 1) a.den[n] = ok ? den : nan;
-    a.vw[w] = vrow;
-    a.stw[w] = ok ? 0 : 1;
-  }
+  const double vrow = ok ? a.sf2 - f.a2 + extra + a.noise : nan;
   const double dn = ok ? den : nan;
-  const uint8_t* o = a.obs ? a.obs + w * a.D : nullptr;
-  double lp = 0.0, sse = 0.0, chi = 0.0;
-  for (int d = lane; d < a.D; d += 64) {
-    if (o && !o[d]) continue;
-    const double e = loo_resid(a, w, d, dn);
-    const ScoreTerm t = score_term(e, 0.0, vrow);
-    lp += t.lp;
-    sse += t.e2;
-    chi += t.q;
-  }
-  lp = wave_sum(lp);
-  sse = wave_sum(sse);
-  chi = wave_sum(chi);
   if (lane == 0) {
-    a.rowo[n] = lp;
-    a.rowo[a.R + n] = sse;
-    a.rowo[2 * a.R + n] = chi;
+    if (a.block == 1) s.den[n] = dn;
+    s.vw[w] = vrow;
+    s.stw[w] = ok ? 0 : 1;
+  }
+  const RowSums r = score_row_sums(LooRow{s, vrow, dn}, w, s.D, lane);
+  if (lane == 0) {
+    a.rowo[n] = r.lp;
+    a.rowo[a.R + n] = r.sse;
+    a.rowo[2 * a.R + n] = r.chi;
     a.rowo[3 * a.R + n] = h;
     a.rowo[4 * a.R + n] = vrow;
-  }
-}
-
-// grid (segments of the window, ceil(D / SC_DW)): score_cols_kernel's sums over the window's rows
-__global__ void __launch_bounds__(256) loo_cols_kernel(LooArgs a) {
-#pragma clang fp contract(off)
-  __shared__ double sh[5 * SC_DW];
-  __shared__ long long fb[2][256];
-  const int tid = threadIdx.x, cc = tid & (SC_DW - 1), half = tid >> 7;
-  const int d = blockIdx.y * SC_DW + cc;
-  const long r0 = (long)blockIdx.x * SC_SEG + 64L * half;
-  const long r1 = min(r0 + 64, a.wcnt);
-  const long g0 = a.n0 - a.lead;                  // global index of the window's first row (a multiple of SC_SEG)
-  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-  long long first = SC_NONE, firstpd = SC_NONE;
-  if (d < a.D) {
-    for (long i = r0; i < r1; ++i) {
-      if (a.stw[i] && firstpd == SC_NONE) firstpd = g0 + i;        // whether or not the entry is scored
-      if (a.obs && !a.obs[i * a.D + d]) continue;
-      const double v = a.vw[i];
-      const ScoreTerm t = score_term(loo_resid(a, i, d, a.Ew ? 0.0 : a.den[i]), 0.0, v);
-      s[0] += (v > 0.0) ? 1.0 : t.e;
-      s[1] += t.e;
-      s[2] += t.e2;
-      s[3] += t.q;
-      s[4] += t.lp;
-      if (!(v > 0.0) && !a.stw[i] && first == SC_NONE) first = g0 + i;
-    }
-  }
-  fb[0][tid] = first;
-  fb[1][tid] = firstpd;
-  if (half == 1) {
-#pragma unroll
-    for (int k = 0; k < 5; ++k) sh[k * SC_DW + cc] = s[k];
-  }
-  __syncthreads();
-  if (half == 0 && d < a.D) {
-    double* out = a.part + ((long)blockIdx.x * a.D + d) * 5;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) out[k] = s[k] + sh[k * SC_DW + cc];
-  }
-  block_fold<256>([&](int i, int j) { fb[0][i] = min(fb[0][i], fb[0][j]); fb[1][i] = min(fb[1][i], fb[1][j]); });
-  if (tid == 0) {
-    long long* b = a.bad + 2 * ((long)blockIdx.x * gridDim.y + blockIdx.y);
-    b[0] = fb[0][0];
-    b[1] = fb[1][0];
-  }
-}
-
-// score_cols_final_kernel with two flags: tot [D][5] and totbad [2] set from zero / none (first) or carried on
-__global__ void __launch_bounds__(256) loo_cols_final_kernel(const double* __restrict__ part, const long long* __restrict__ bad, int segs, int tiles, long d5,
-                                                             int first, double* __restrict__ tot, long long* __restrict__ totbad) {
-  if (blockIdx.x + 1 < gridDim.x) {
-    const long e = blockIdx.x * 256L + threadIdx.x;
-    if (e >= d5) return;
-    double s = first ? 0.0 : tot[e];
-    for (int g = 0; g < segs; ++g) s += part[g * d5 + e];       // segments ascending, one by one into the running total
-    tot[e] = s;
-    return;
-  }
-  if (threadIdx.x < 2) {
-    long long b = first ? SC_NONE : totbad[threadIdx.x];
-    for (long g = 0; g < (long)segs * tiles; ++g) b = min(b, bad[2 * g + threadIdx.x]);
-    totbad[threadIdx.x] = b;
   }
 }
 
@@ -311,15 +242,13 @@ struct LooPlan {
   DevBuf<double> Ew;          // [SC_SEG + rows][Dp] E'
   DevBuf<double> S, X;        // [tiles][128][128] S -> L, and L^-1
   DevBuf<double> flag;        // [2][tiles] the factorisation's failure flag | its log-determinant (not used)
-  DevBuf<double> part;        // [rows / SC_SEG + 1][D][5]
-  DevBuf<double> tot;         // [D][5]
-  DevBuf<long long> bad;      // [rows / SC_SEG + 1][tiles of D][2] | [2] the call's first bad rows
+  ScoreTotals totals;         // rows / SC_SEG + 1 segments, two flags: first row with v' not > 0 | first row whose S did not factorise
   long tiles = 0;
 };
 void LooPlanDelete::operator()(LooPlan* p) const { delete p; }
 
 static int loo_alloc(gp_ctx* c, long R, int grp, bool mask) {
-  const long D = c->D, Dp = c->Dp, segs = R / SC_SEG + 1, dt = (D + SC_DW - 1) / SC_DW, W = R + SC_SEG;
+  const long D = c->D, Dp = c->Dp, W = R + SC_SEG;
   if (!c->loo || c->loo->rows != R || c->loo->grp != grp) {
     c->loo.reset();
     std::unique_ptr<LooPlan, LooPlanDelete> p(new LooPlan());
@@ -335,9 +264,7 @@ static int loo_alloc(gp_ctx* c, long R, int grp, bool mask) {
       GP_TRY_RC(p->X.alloc(c, (size_t)(p->tiles * NB * NB), DA_RAW));
       GP_TRY_RC(p->flag.alloc(c, (size_t)(2 * p->tiles), DA_RAW));
     }
-    GP_TRY_RC(p->part.alloc(c, (size_t)(segs * D * 5), DA_RAW));
-    GP_TRY_RC(p->tot.alloc(c, (size_t)(D * 5), DA_RAW));
-    GP_TRY_RC(p->bad.alloc(c, (size_t)(2 * segs * dt + 2), DA_RAW));
+    GP_TRY_RC(p->totals.alloc(c, R / SC_SEG + 1, D, LooSrc::NFLAGS));
     p->rows = R;
     p->grp = grp;
     c->loo = std::move(p);
@@ -356,9 +283,7 @@ int run_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, doub
   GP_TRY_RC(loo_alloc(c, R, grp, observed != nullptr));
   const LooPlan& p = *c->loo;
   hipStream_t st = c->stream;
-  const long Mp = c->Mp, Dp = c->Dp, D = c->D, d5 = 5 * D;
-  const int dt = (int)((D + SC_DW - 1) / SC_DW);
-  long long* totbad = p.bad + 2 * (R / SC_SEG + 1) * dt;
+  const long Mp = c->Mp, Dp = c->Dp, D = c->D;
   if (grp) {
     GP_HIP(c, hipFuncSetAttribute((const void*)loo_s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LOO_S_LDS));
     GP_HIP(c, hipFuncSetAttribute((const void*)loo_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LOO_SOLVE_LDS));
@@ -370,32 +295,32 @@ int run_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, doub
     const bool last = n0 + cnt == n;
     GP_TRY_RC(pred_chunk_front(c, pred_at(c->Xmu).on_device(true), n0, cnt, pred_into(k.mu).factors(k.G + Dp, k.ldg).on_big()));
     LooArgs a;
-    a.G = k.G; a.ldg = k.ldg;
-    a.Y = c->Kaug + n0 * c->LDK + Mp; a.ldy = c->LDK;            // the resident Y: the columns of Kaug behind Psi1
-    a.cnt = cnt; a.n0 = n0; a.lead = lead;
-    a.M = c->M; a.Mp = (int)Mp; a.D = (int)D; a.Dp = (int)Dp; a.block = block; a.grp = grp ? grp : 1;
+    LooSrc& s = a.src;
+    s.G = k.G; s.ldg = k.ldg;
+    s.Y = c->Kaug + n0 * c->LDK + Mp; s.ldy = c->LDK;            // the resident Y: the columns of Kaug behind Psi1
+    s.Ew = grp ? p.Ew.get() : nullptr; s.Dp = (int)Dp; s.den = p.den; s.obs = nullptr; s.vw = p.vw; s.stw = p.stw;
+    s.rows = lead + cnt; s.g0 = n0 - lead; s.D = (int)D;
+    a.cnt = cnt; a.lead = lead;
+    a.M = c->M; a.Mp = (int)Mp; a.block = block; a.grp = grp ? grp : 1;
     a.sf2 = c->sf2; a.beta = c->beta; a.noise = (flags & 1) ? 1.0 / c->beta : 0.0;
-    a.sinv = p.sinv; a.fail = p.flag; a.den = p.den; a.Ew = grp ? p.Ew.get() : nullptr; a.obs = nullptr;
-    a.vw = p.vw; a.stw = p.stw; a.rowo = p.rowo; a.R = R; a.wcnt = lead + cnt; a.part = p.part; a.bad = p.bad;
+    a.sinv = p.sinv; a.fail = p.flag; a.rowo = p.rowo; a.R = R;
     if (grp) {
       const int tiles = (int)((cnt + grp - 1) / grp);
       GP_LAUNCH(c, st, loo_s_kernel, dim3((unsigned)tiles), dim3(512), LOO_S_LDS, (const double*)k.G, k.ldg, (int)(Dp + Mp), c->M, cnt, block, grp, c->beta, p.S.get(),
                 p.flag.get(), p.flag + p.tiles);
       GP_TRY_RC(potrf_trinv128_tiles(c, st, tiles, p.S, p.X, p.flag, p.flag + p.tiles));
       GP_LAUNCH(c, st, loo_solve_kernel, dim3((unsigned)tiles, (unsigned)((D + NB - 1) / NB)), dim3(512), LOO_SOLVE_LDS, (const double*)p.X, (const double*)p.flag,
-                (const double*)k.G, k.ldg, a.Y, a.ldy, cnt, block, grp, (int)D, (int)Dp, p.Ew + lead * Dp, p.sinv.get());
+                (const double*)k.G, k.ldg, s.Y, s.ldy, cnt, block, grp, (int)D, (int)Dp, p.Ew + lead * Dp, p.sinv.get());
     }
     if (observed) {
       GP_HIP(c, hipMemcpyAsync(p.obs + lead * D, observed + n0 * D, (size_t)(cnt * D), hipMemcpyHostToDevice, st));
-      a.obs = p.obs;
+      s.obs = p.obs;
     }
     GP_LAUNCH(c, st, loo_rows_kernel, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, a);
-    const int segs = (int)(last ? (a.wcnt + SC_SEG - 1) / SC_SEG : a.wcnt / SC_SEG);
+    const int segs = (int)(last ? (s.rows + SC_SEG - 1) / SC_SEG : s.rows / SC_SEG);
     if (segs > 0) {
-      if (!last) a.wcnt = (long)segs * SC_SEG;
-      GP_LAUNCH(c, st, loo_cols_kernel, dim3((unsigned)segs, (unsigned)dt), dim3(256), 0, a);
-      GP_LAUNCH(c, st, loo_cols_final_kernel, dim3((unsigned)((d5 + 255) / 256) + 1), dim3(256), 0, (const double*)p.part, (const long long*)p.bad, segs, dt, d5,
-                started ? 0 : 1, p.tot.get(), totbad);
+      if (!last) s.rows = (long)segs * SC_SEG;                    // the whole segments; the rest waits for the next chunk
+      GP_TRY_RC(p.totals.add_segments(c, st, s, segs, !started));
       started = true;
     }
     double* const outs[5] = {row_logp, row_sse, row_chi2, lev, var_loo};
@@ -413,17 +338,12 @@ int run_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, doub
     lead = tail;
   }
   long long bad[2] = {SC_NONE, SC_NONE};
-  if (cols) GP_HIP(c, hipMemcpyAsync(cols, p.tot, (size_t)d5 * 8, hipMemcpyDeviceToHost, st));
-  GP_HIP(c, hipMemcpyAsync(bad, totbad, 16, hipMemcpyDeviceToHost, st));
-  GP_HIP(c, hipStreamSynchronize(st));
-  ++c->sync_epoch;
+  GP_TRY_RC(p.totals.read(c, st, cols, bad));
   if (bad[1] != SC_NONE)
     return fail(c, GP_ERR_NOT_PD, "gp_loo_score: S = I - beta B B^T of the rows left out does not factorise (first in row %lld): the model without them is "
                 "not proper, or the statistics do not contain these rows.  The outputs of the rows factorised with it (its block; with block <= 64 the "
                 "%d rows of its tile) and the column sums they enter are NaN, every other row is valid", bad[1], grp ? grp : 1);
-  if (bad[0] != SC_NONE)
-    return fail(c, GP_ERR_NON_FINITE, "gp_loo_score: the leave-out variance of a scored entry is not > 0 (first in row %lld): its row's outputs and its "
-                "columns' sums are NaN, every other row is valid%s", bad[0], (flags & 1) ? "" : " (the variance of f can round to zero or below: score y, flags bit 0)");
+  if (bad[0] != SC_NONE) return score_fail_variance(c, "gp_loo_score", "leave-out", bad[0], flags);
   return GP_OK;
 }
 

@@ -8,7 +8,8 @@
 // two sums of squares of O(sf2) vectors instead of a quadratic form in Ki - P, whose elements are O(cond / sf2) and cancel.
 //   Psi1* rows: psi1_rows (psi1.hip's generic Psi1 kernel on prediction-owned buffers);
 //   [mean | Lk^-1 k* | La^-1 k*] = Psi1* [beta E | Linv^T]: two products on the MFMA GEMM core (launch_gemm);
-//   pred_det_rows_kernel: one wave per point, mean out and var = sf2 - sum of squares + sum of squares (+ 1/beta).
+//   pred_det_rows_kernel: one wave per point, mean out and var = sf2 - sum of squares + sum of squares (+ 1/beta); the two sums are fac_norms
+//     (score_pass.h), the one definition gp_predict_score and gp_loo_score build their variances from too.
 // Uncertain inputs x* ~ N(mu*, diag S*), psi1* = psi1(mu*, S*), psi2* = psi2_point(mu*, S*):
 //   mean_d = psi1*^T W_d,   var_d = sf2 - tr(B psi2*) + W_d^T psi2* W_d - mean_d^2
 //   mean: the same product as above (beta E only);
@@ -20,6 +21,7 @@
 #include "pred_chunk.h"
 #include "fexp.h"
 #include "lane_reduce.h"
+#include "score_pass.h"
 #include "varpoint.h"
 #include <algorithm>
 #include <cmath>
@@ -69,15 +71,8 @@ __global__ void __launch_bounds__(256) pred_det_rows_kernel(const double* __rest
   if (n >= cnt) return;
   const double* g = G + n * ldg;
   for (int d = lane; d < D; d += 64) mean[n * D + d] = g[d];
-  double sk = 0.0, sa = 0.0;
-  for (int i = lane; i < M; i += 64) {
-    const double a = g[Dp + i], b = g[Dp + Mp + i];
-    sk = fma(a, a, sk);
-    sa = fma(b, b, sa);
-  }
-  sk = wave_sum(sk);
-  sa = wave_sum(sa);
-  if (lane == 0) var[n] = sf2 - sk + sa + noise;
+  const FacNorms f = fac_norms(g, M, Dp, Mp, lane);
+  if (lane == 0) var[n] = sf2 - f.a2 + f.b2 + noise;
 }
 
 // C[i][col] = mean[i][col mod D] for i < n and col < used, else 0: the caller's product then adds its terms on top (beta = 1)

@@ -213,7 +213,7 @@ int gp_predict(gp_ctx* ctx, int64_t n, const double* X_mu, const double* X_S, in
  * beyond that.  Between a small and a large chunk the row's mean and variance agree to the rounding of the products (gp_predict's accuracy), not bit
  * for bit -- for instance a row alone against the same row in a full chunk of 7168 rows at M = 512, or a short last chunk.  A batch-independent row,
  * which the other prediction entries obtain by fixing the kernel, and gp_predict's bits cannot both be had; this entry keeps gp_predict's bits.
- * Summation order (csrc/score.hip).  Rows: a function of D alone -- lane l of a 64-lane wave adds the observed d = l, l + 64, .. in ascending order,
+ * Summation order (csrc/score_pass.h, one definition for this entry and gp_loo_score).  Rows: a function of D alone -- lane l of a 64-lane wave adds the observed d = l, l + 64, .. in ascending order,
  * then the lanes are added pairwise at distance 32, 16, .. 1.  Columns: the ORDER is a function of the global row index alone and never of the chunk
  * size -- the rows are cut into segments of 128 (a chunk is a whole number of them); inside a segment the rows 0 .. 63 and 64 .. 127 are each added
  * in ascending order and the two halves are added; the segments are then added one by one, in ascending order, into the running total, which starts

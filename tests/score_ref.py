@@ -40,6 +40,49 @@ def score(Z, sf2, alpha, beta, Psi2, C, Y, X_mu, X_S=None, observed=None, includ
     return out
 
 
+def cols_in_device_order(values, observed, seg=128):
+    """The column sums (D,) of values (n, D) over the observed entries in the summation order the device documents (include/gparml_hip.h, DESIGN.md
+    section 18), in plain float64: per column and per segment of ``seg`` rows by global index, the rows of the first and of the second half each
+    summed one by one in ascending order from 0.0, hidden entries skipped; then half 0 + half 1; then the segments added one by one, ascending,
+    into a total that starts at 0.0."""
+    values, o = np.asarray(values, dtype=np.float64), np.asarray(observed) != 0
+    n, D = values.shape
+    assert o.shape == (n, D) and seg % 2 == 0
+    out = np.empty(D)
+    for d in range(D):
+        total = 0.0
+        for s0 in range(0, n, seg):
+            halves = []
+            for h0 in (s0, s0 + seg // 2):
+                acc = 0.0
+                for i in range(h0, min(h0 + seg // 2, n)):
+                    if o[i, d]:
+                        acc = acc + float(values[i, d])
+                halves.append(acc)
+            total = total + (halves[0] + halves[1])
+        out[d] = total
+    return out
+
+
+def one_entry_mask(n, D, empty_row):
+    """Every row observes exactly one column, (row mod D), and ``empty_row`` none: a row's three outputs are then the bits of its single entry's
+    terms -- the lane sums and the butterfly add only zeros -- so the column sums can be rebuilt exactly from the row outputs."""
+    o = np.zeros((n, D), dtype=bool)
+    o[np.arange(n), np.arange(n) % D] = True
+    o[empty_row] = False
+    return o
+
+
+def check_cols_order(row_logp, row_sse, row_chi2, cols, observed, what):
+    """cols [D][5] of a call under a one_entry_mask against its own row outputs summed in the documented order: bit for bit."""
+    o = np.asarray(observed) != 0
+    assert np.array_equal(cols[:, 0], o.sum(axis=0).astype(float)), what + ': count'
+    for k, rows in ((2, row_sse), (3, row_chi2), (4, row_logp)):
+        assert np.all(np.isfinite(rows)), what
+        want = cols_in_device_order(np.where(o, np.asarray(rows)[:, None], 0.0), o)
+        assert np.array_equal(cols[:, k], want), '%s: cols[:, %d] is not the documented order: %r against %r' % (what, k, cols[:, k], want)
+
+
 def summary(cols):
     """count, bias, rmse, chi2_mean, nlpd per column from the column sums (NaN for a column without a scored entry)."""
     cols = np.asarray(cols, dtype=float)

@@ -175,6 +175,25 @@ def test_bit_identity(cases, shape, block):
         assert np.all(np.abs(full[5] - (vf[:, 0] + extra)) <= 2 * c.tol * d['sf2'] + 8 * EPS * np.abs(full[5]))
 
 
+@pytest.mark.parametrize('block', [1, 5, 128])
+def test_column_sums_in_the_documented_order(cases, block):
+    """gp_predict_score's order of the column sums, pinned independently of the library (tests/test_gpu_score.py has the same test): under a mask in
+    which every row scores one entry, cols[:, 2:5] are the row outputs themselves summed by score_ref.cols_in_device_order, bit for bit -- at the
+    default chunk and at chunks of 128 rows (block 5: chunks of 125, so rows wait in the window for the next chunk's)."""
+    from gparml_amd import _lib
+    c = cases(SHAPES[0])                                    # N = 300, D = 3
+    obs = S.one_entry_mask(c.N, c.D, 200)
+    lib = _lib.load()
+    for rows in (0, 128):
+        lib.gp_debug_set_option(b'predict_rows', rows)
+        try:
+            got = _loo(c.e, block, obs, 1)
+        finally:
+            lib.gp_debug_set_option(b'predict_rows', 0)
+        assert got[0] == 0, c.e.lib.gp_last_error(c.e.h)
+        S.check_cols_order(got[1], got[2], got[3], got[6], obs, 'block %d, chunk %d' % (block, rows))
+
+
 def test_state_is_left_untouched():
     """gp_phase2 / gp_finish / gp_predict after gp_loo_score are bit-identical to a run without it."""
     N, M, Q, D = SHAPES[0]

@@ -336,6 +336,26 @@ def test_resident_rows():
     g.close()
 
 
+def test_column_sums_in_the_documented_order(cases):
+    """The order of the column sums, pinned independently of the library: under a mask in which every row scores one entry, cols[:, 2:5] are the row
+    outputs themselves summed by score_ref.cols_in_device_order, bit for bit -- host rows and resident rows, the default chunk and chunks of 128
+    (300 rows: three segments, the last one ragged)."""
+    from gparml_amd import _lib
+    c = cases(SHAPES[1])                                    # N = 300, D = 3
+    e, N = c.e, c.N
+    Xm = e.download('X_MU')
+    obs = S.one_entry_mask(N, c.D, 200)
+    lib = _lib.load()
+    for rows in (0, 128):
+        lib.gp_debug_set_option(b'predict_rows', rows)
+        try:
+            for name, r in (('host rows', _raw(e, N, Xm, None, c.d['Y'], obs, 1)), ('resident rows', _raw(e, N, None, None, None, obs, 1))):
+                assert r[0] == 0, e.lib.gp_last_error(e.h)
+                S.check_cols_order(r[1], r[2], r[3], r[4], obs, '%s, chunk %d' % (name, rows))
+        finally:
+            lib.gp_debug_set_option(b'predict_rows', 0)
+
+
 def _finish_bits(e):
     e.phase2(True)
     out = e.finish()

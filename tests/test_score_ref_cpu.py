@@ -73,3 +73,19 @@ def test_column_sums_are_the_sums_of_the_terms():
     x = np.linspace(-12, 12, 200001)[:, None]
     p = np.exp(S.score_from(x, np.zeros_like(x), np.full_like(x, 1.7))['terms']['logp'])
     assert abs(p.sum() * (x[1, 0] - x[0, 0]) - 1.0) < 1e-9
+
+
+def test_cols_in_device_order_by_hand():
+    """cols_in_device_order on sums whose value depends on the order: with 2^53 in one half of a segment a 1.0 survives only where it is added
+    to its own half first, and the segments enter the total one by one."""
+    big = 2.0 ** 53
+    v = np.zeros((6, 1))
+    o = np.ones((6, 1), dtype=bool)
+    v[:, 0] = [big, 1.0, 1.0, -big, 1.0, 1.0]              # seg = 4: halves (big + 1 = big, 1 - big), then the segment (1 + 1)
+    assert S.cols_in_device_order(v, o, seg=4)[0] == (big + (1.0 - big)) + 2.0 == 3.0
+    assert S.cols_in_device_order(v, o, seg=2)[0] == 3.0   # (big + 1) + (1 - big) + (1 + 1), each segment whole before it enters: 0 + 1 + 2
+    o[1] = False                                           # a hidden entry is skipped, not added as a zero of another sign or a NaN
+    v[1] = np.nan
+    assert S.cols_in_device_order(v, o, seg=4)[0] == 3.0
+    m = S.one_entry_mask(7, 3, 4)
+    assert np.array_equal(m.sum(axis=1), [1, 1, 1, 1, 0, 1, 1]) and m[5, 2] and m[6, 0]

@@ -11,7 +11,9 @@ n = 130 of them (a full chunk and a ragged one).  Models (Q, D): (3, 5), (20, 5)
 (deterministic, actual and raw X_S; mean only, var only, both; with and without the noise), gp_predict_score (host rows with and without a mask,
 the resident rows with and without their variances), gp_predict_joint and gp_predict_sample (3 draws), gp_predict_grad (all outputs; logdet only
 at Q <= 64, the entry's own limit), gp_paths_set / gp_paths_eval (F = 8, 2 draws, n = 130 and n = 1), gp_curve_energy (5 curves of T = 7, two
-curves per chunk, all outputs).  --compare takes the arrays as bytes: NaN positions and signs of zero count."""
+curves per chunk, all outputs).  One fixed-embedding model, (3, 5), for the scoring passes gp_predict_score and gp_loo_score share: gp_loo_score at
+block 1, 5, 64 and 128 (with and without a mask, flags 0 and 1), gp_predict_score on the resident rows (with and without a mask), each at the
+default chunk and at chunks of 128 rows, and gp_predict at deterministic inputs.  --compare takes the arrays as bytes: NaN positions and signs of zero count."""
 import argparse
 import os
 import sys
@@ -25,10 +27,10 @@ N, M, n = 300, 40, 130
 MODELS = ((3, 5), (20, 5), (70, 5), (3, 130))
 
 
-def trained_engine(Q, D):
+def trained_engine(Q, D, regime='B'):
     from oracle import factorised as Fz
     from gparml_amd.engine import ShardEngine
-    d = Fz.synthetic_shard(N, D, M, Q, regime='B', seed=11, zseed=12, alpha_value=0.5)
+    d = Fz.synthetic_shard(N, D, M, Q, regime=regime, seed=11, zseed=12, alpha_value=0.5)
     e = ShardEngine(N, D, M, Q)
     e.upload_shard(d['Y'], d['X_mu'], d['X_S'])
     Z, alpha = d['Z'].copy(), np.asarray(d['alpha'], dtype=np.float64).reshape(-1).copy()
@@ -96,6 +98,37 @@ def dump_model(Q, D, out):
     e.close()
 
 
+def dump_fixed(lib, out):
+    """The fixed-embedding model (Q, D) = (3, 5) and the scoring passes gp_predict_score and gp_loo_score share (csrc/score_pass.h), at the default
+    chunk and at chunks of 128 rows: 300 rows are three segments with a ragged last one; block 5 makes chunks of 125 rows, block-aligned but not
+    segment-aligned, so rows wait in the window for the next chunk's."""
+    Q, D = 3, 5
+    e, d = trained_engine(Q, D, regime='A')
+    tag = 'fixed_Q%d_D%d/' % (Q, D)
+    rs = np.random.RandomState(100 * Q + D + 1)
+    X = np.ascontiguousarray(rs.randn(n, Q))
+    for noise in (0, 1):
+        out[tag + 'predict/det/noise%d/mean' % noise], out[tag + 'predict/det/noise%d/var' % noise] = predict_raw(e, X, None, 0, noise, True, True)
+    mask = rs.uniform(size=(N, D)) < 0.7
+    mask[:, 0] = True
+    mask[129] = False
+    for rows in (0, 128):
+        assert lib.gp_debug_set_option(b'predict_rows', rows) == 0
+        for mname, obs in (('full', None), ('mask', mask)):
+            r = e.score(None, observed=obs)
+            for k in ('row_logp', 'row_sse', 'row_chi2', 'cols'):
+                out[tag + 'score/resident_%s/chunk%d/%s' % (mname, rows, k)] = r[k]
+            for block in (1, 5, 64, 128):
+                for noise in (0, 1):
+                    try:
+                        r = e.loo(block=block, observed=obs, include_noise=bool(noise))
+                    except (FloatingPointError, np.linalg.LinAlgError) as err:      # the outputs are compared all the same, NaN rows included
+                        r = err.result
+                    for k in ('row_logp', 'row_sse', 'row_chi2', 'lev', 'var_loo', 'cols'):
+                        out[tag + 'loo/block%d/%s/flags%d/chunk%d/%s' % (block, mname, noise, rows, k)] = r[k]
+    e.close()
+
+
 def compare(a, b):
     A, B = np.load(a), np.load(b)
     assert sorted(A.files) == sorted(B.files), 'different arrays: %s' % sorted(set(A.files) ^ set(B.files))
@@ -120,6 +153,8 @@ def main():
     for Q, D in MODELS:
         dump_model(Q, D, out)
         print('model Q = %d, D = %d: %d arrays so far' % (Q, D, len(out)), flush=True)
+    dump_fixed(lib, out)
+    print('fixed-embedding model: %d arrays so far' % len(out), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     np.savez(args.out, **out)
     print('wrote %d arrays to %s (library: %s)' % (len(out), args.out, _lib.LIB_PATH))
