@@ -68,6 +68,9 @@ SIGNATURES = {
     'gp_paths_set': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),
     'gp_paths_eval': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_paths_clear': (ctypes.c_int, [_vp]),
+    'gp_condition_set': (ctypes.c_int, [_vp, _i64, _dp, _dp]),
+    'gp_condition_predict': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp]),
+    'gp_condition_clear': (ctypes.c_int, [_vp]),
     'gp_infer_objective': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_infer_latent': (ctypes.c_int, [_vp, _i64, _dp, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _dp, _ip]),
     'gp_infer_objective_rows': (ctypes.c_int, [_vp, _i64, _dp, _u8p, _dp, _dp, ctypes.c_int, _dp, _dp, _dp]),

@@ -894,6 +894,44 @@ extern "C" int gp_paths_clear(gp_ctx* c) {
   return GP_OK;
 }
 
+// ---- the posterior conditioned on extra observed rows (condition.hip): the order of the checks is gp_paths_set's / gp_paths_eval's ----
+extern "C" int gp_condition_set(gp_ctx* c, int64_t m, const double* Xc, const double* Yc) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (m < 1) return fail(c, GP_ERR_BAD_ARG, "gp_condition_set: m must be >= 1 (got %ld)", (long)m);
+  if (!Xc || !Yc) return fail(c, GP_ERR_BAD_ARG, "gp_condition_set: Xc or Yc is NULL");
+  GP_TRY(model_ready(c, "gp_condition_set"));
+  if (m > 1024)
+    return fail(c, GP_ERR_UNSUPPORTED, "gp_condition_set: m = %ld is beyond the limit of 1024 conditioning rows (the m x m factorisation is held on the device): "
+                "refit with the rows in the statistics", (long)m);
+  GP_TRY(finite_check(c, "gp_condition_set", "Xc", Xc, (size_t)m * c->Q));
+  GP_TRY(finite_check(c, "gp_condition_set", "Yc", Yc, (size_t)m * c->D));
+  return run_condition_set(c, (long)m, Xc, Yc);
+}
+
+extern "C" int gp_condition_predict(gp_ctx* c, int64_t n, const double* X, int flags, double* mean, double* var, double* reduction) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 0) return fail(c, GP_ERR_BAD_ARG, "gp_condition_predict: n must be >= 0");
+  if (flags & ~1) return fail(c, GP_ERR_BAD_ARG, "gp_condition_predict: unknown flags %d", flags);
+  if (const int rc = model_ready(c, "gp_condition_predict"); rc != GP_OK) {
+    c->cond.reset();             // the rows were conditioned on a model that is gone
+    return rc;
+  }
+  if (!cond_plan_current(c))
+    return fail(c, GP_ERR_STATE, "gp_condition_predict needs gp_condition_set on the model as it is now (none yet, or a global step, new statistics or new globals since)");
+  if (n == 0) return GP_OK;
+  if (!X) return fail(c, GP_ERR_BAD_ARG, "gp_condition_predict: X is NULL");
+  GP_TRY(finite_check(c, "gp_condition_predict", "X", X, (size_t)n * c->Q));
+  if (!mean && !var && !reduction) return GP_OK;
+  return run_condition_predict(c, (long)n, X, flags, mean, var, reduction);
+}
+
+extern "C" int gp_condition_clear(gp_ctx* c) {
+  if (!c) return GP_ERR_BAD_ARG;
+  GP_HIP(c, hipSetDevice(c->device));
+  c->cond.reset();
+  return GP_OK;
+}
+
 // gp_infer_objective / gp_infer_latent and their _rows forms: gp_predict's preconditions, then the arguments of the new rows.  masked: the observed
 // set of every row (observed) in place of the one column list (cols, n_cols)
 static int infer_check(gp_ctx* c, const char* who, int64_t n, const double* Y, const int* cols, int n_cols, bool masked, const uint8_t* observed,

@@ -106,6 +106,7 @@ struct ScorePlan;  // score.hip
 struct LbfgsPlan;  // lbfgs.hip
 struct KnnPlan;    // knn.hip
 struct LooPlan;    // loo.hip
+struct CondPlan;   // condition.hip
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -123,6 +124,7 @@ struct ScorePlanDelete { void operator()(ScorePlan* p) const; };
 struct LbfgsPlanDelete { void operator()(LbfgsPlan* p) const; };
 struct KnnPlanDelete { void operator()(KnnPlan* p) const; };
 struct LooPlanDelete { void operator()(LooPlan* p) const; };
+struct CondPlanDelete { void operator()(CondPlan* p) const; };
 
 }  // namespace gp
 
@@ -292,6 +294,7 @@ struct gp_ctx {
   std::unique_ptr<gp::LbfgsPlan, gp::LbfgsPlanDelete> lbfgs;  // gp_lbfgs_begin .. gp_lbfgs_end: the history vectors (lbfgs.hip)
   std::unique_ptr<gp::KnnPlan, gp::KnnPlanDelete> knn;        // gp_knn_rows' buffers (knn.hip)
   std::unique_ptr<gp::LooPlan, gp::LooPlanDelete> loo;        // gp_loo_score's buffers (loo.hip)
+  std::unique_ptr<gp::CondPlan, gp::CondPlanDelete> cond;     // gp_condition_set's rows [V | T] and gp_condition_predict's buffers (condition.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -358,6 +361,10 @@ int run_predict_score(gp_ctx* c, long n, const double* X_mu, const double* X_S, 
 // loo.hip (the arguments have been checked: api.hip)
 int run_loo_score(gp_ctx* c, int block, const uint8_t* observed, int flags, double* row_logp, double* row_sse, double* row_chi2, double* lev,
                   double* var_loo, double* cols);
+// condition.hip (the arguments have been checked: api.hip)
+int run_condition_set(gp_ctx* c, long m, const double* Xc, const double* Yc);
+bool cond_plan_current(gp_ctx* c);                                   // a set of the model as it is now; a stale one is dropped
+int run_condition_predict(gp_ctx* c, long n, const double* X, int flags, double* mean, double* var, double* reduction);
 // joint.hip
 int run_predict_joint(gp_ctx* c, long n, const double* X, int flags, double* mean, double* cov);
 int run_predict_sample(gp_ctx* c, long n, const double* X, int flags, double jitter, int n_draws, const double* eps, double* out, double* mean);

@@ -498,6 +498,35 @@ class ShardEngine(object):
         self._paths_draws = 0
         self.paths_token = getattr(self, 'paths_token', 0) + 1
 
+    # ---- the posterior conditioned on extra observed rows (gp_condition_set, gp_condition_predict, gp_condition_clear) ----
+    def condition(self, Xc, Yc):
+        """Condition the model on ``m`` extra observed rows, after a successful global step as ``predict``: ``Xc`` (m, Q) their deterministic
+        inputs, ``Yc`` (m, D) their outputs, 1 <= m <= 1024.  ``condition_predict`` then predicts as ``predict`` would after a refit on the shard
+        with these rows appended (embeddings fixed), at the cost of one m x m factorisation here and two thin products per query chunk there.
+        Nothing of the model or the evaluation state changes.  An engine holds ONE set at a time: a second ``condition`` replaces the first; a
+        set goes stale when the model changes (new globals, statistics or a global step)."""
+        Xc, Yc = np.atleast_2d(np.asarray(Xc, dtype=np.float64)), np.atleast_2d(np.asarray(Yc, dtype=np.float64))
+        assert Xc.ndim == 2 and Xc.shape[1] == self.Q, 'Xc shape %s: (m, %d) expected' % (Xc.shape, self.Q)
+        assert Yc.shape == (Xc.shape[0], self.D), 'Yc shape %s: (%d, %d) expected' % (Yc.shape, Xc.shape[0], self.D)
+        (Xc, px), (Yc, py) = _lib.as_c(Xc), _lib.as_c(Yc)
+        self._ck(self.lib.gp_condition_set(self.h, Xc.shape[0], px, py), 'gp_condition_set')
+
+    def condition_predict(self, X, include_noise=False, want_reduction=False):
+        """``predict`` at the new deterministic inputs X (n, Q) under the rows of ``condition``: (mean (n, D), var (n, 1)); with
+        ``want_reduction`` also the reduction (n, 1) = var - var' >= 0 of the variance the rows bought.  ``include_noise`` adds 1/beta.  A point's
+        values are the same bits alone and in any batch.  The evaluation state is left untouched."""
+        X, px = self._joint_X(X)
+        n = X.shape[0]
+        mean, var = np.empty((n, self.D)), np.empty((n, 1))
+        red = np.empty((n, 1)) if want_reduction else None
+        self._ck(self.lib.gp_condition_predict(self.h, n, px, 1 if include_noise else 0, mean.ctypes.data_as(_lib._dp), var.ctypes.data_as(_lib._dp),
+                                               red.ctypes.data_as(_lib._dp) if want_reduction else None), 'gp_condition_predict')
+        return (mean, var, red) if want_reduction else (mean, var)
+
+    def condition_clear(self):
+        """Drop the rows of ``condition`` and free their device memory (no error without any)."""
+        self._ck(self.lib.gp_condition_clear(self.h), 'gp_condition_clear')
+
     # ---- derivatives of the prediction with respect to the input (gp_predict_grad) ----------------------------
     def predict_grad(self, X, jac=True, dvar=True, metric=True, logdet=True):
         """Derivatives of ``predict`` at the new deterministic inputs X (n, Q), after a successful global step as ``predict``.  Returns a dict of the

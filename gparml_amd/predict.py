@@ -133,6 +133,17 @@ class Predictor(object):
         finally:
             eng.close()
 
+    def predict_conditioned(self, X, Xc, Yc, include_noise=False, want_reduction=False):
+        """The prediction at the points X (n, Q) of the trained model conditioned on the extra observed rows (Xc (m, Q), Yc (m, D)), m <= 1024,
+        without a refit (ShardEngine.condition / condition_predict): (mean (n, D), var (n, 1)) and, with ``want_reduction``, the reduction
+        (n, 1) of the variance.  Look-ahead posteriors, rows that arrived after training; the stored statistics are not changed."""
+        eng = self._trained_engine()
+        try:
+            eng.condition(Xc, Yc)
+            return eng.condition_predict(X, include_noise=include_noise, want_reduction=want_reduction)
+        finally:
+            eng.close()
+
     def predict_sample(self, X, n_draws, include_noise=False, jitter=1e-8, eps=None, seed=None):
         """``n_draws`` coherent samples (n_draws, n, D) of the outputs at the points X (n, Q), and the mean (n, D) (ShardEngine.predict_sample)."""
         eng = self._trained_engine()

@@ -349,6 +349,37 @@ int gp_paths_set(gp_ctx* ctx, int n_draws, int F, const double* omega /*(F,Q)*/,
 int gp_paths_eval(gp_ctx* ctx, int64_t n, const double* X /*(n,Q)*/, int flags, double* out /*(n_draws,n,D)*/, double* mean /*(n,D) or NULL*/);
 int gp_paths_clear(gp_ctx* ctx);
 
+/* The posterior conditioned on m extra observed rows (Xc, Yc), without a refit: a rank-m update of the model of the last global step, the mirror
+ * image of gp_loo_score's downdate (csrc/condition.hip).  Fixed Z, sf2, alpha, beta; the trained model may have fixed or
+ * free embeddings, the conditioning rows and the queries have deterministic inputs.  With a = Lk^-1 k(x), b = La^-1 k(x), mean and var as
+ * gp_predict has them, B_c (m,M) the rows b of the conditioning inputs and M_c (m,D) their means under the model as it is,
+ *   S = I + beta B_c B_c^T = L L^T,   V = L^-1 B_c,   T = L^-1 (Yc - M_c),   u(x) = V b(x)
+ *   mean'(x)_d = mean(x)_d + beta u(x) . T[:,d]          var'(x) = var(x) - beta |u(x)|^2   (flags bit 0 adds 1/beta, as gp_predict)
+ * which is exactly the prediction of the model whose statistics are Psi2 + K_c^T K_c, Psi1^T Y + K_c^T Yc, sum_YYT + |Yc|^2: what gp_predict
+ * returns after a refit on the shard with these rows appended, embeddings fixed.  S >= I always factorises and |S^-1| <= 1: nothing is amplified.
+ * gp_condition_set: 1 <= m <= 1024; builds the context's set (replacing an earlier one whole): V and T, (m rounded up to 128) x (Mp + Dp) doubles.
+ * One m x m Cholesky factorisation (the global step's own routines) and a few thin products.  GP_ERR_UNSUPPORTED for m > 1024; GP_ERR_NOT_PD only
+ * if the factorisation reports failure, which cannot happen in exact arithmetic.  A call that fails part way leaves the context without a set.
+ * gp_condition_predict: X (n,Q); mean (n,D), var (n), reduction (n) = var - var' = beta |u|^2 >= 0: any may be NULL, and the others keep the bits of
+ * the full call.  The reduction is the difference of the two variances as they are rounded: var - reduction gives the bits of var'.  Variances are
+ * returned unclamped, as gp_predict returns them.  Only X goes to the device and mean, var, reduction come back.
+ * Preconditions and state rule are gp_predict's: GP_ERR_STATE unless the last global step succeeded on the statistics and globals as they are now.
+ * A set made before the statistics or globals changed (new globals, new statistics, a phase 1, a global step) is stale, as a stale draw set of
+ * gp_paths_eval is: gp_condition_predict then answers GP_ERR_STATE, and drops the set, until gp_condition_set is called again; it answers
+ * GP_ERR_STATE without a set too.  gp_condition_clear frees the set and succeeds without one; gp_destroy frees it.
+ * GP_ERR_BAD_ARG, decided before anything is launched: m < 1, a NULL Xc or Yc, non-finite Xc or Yc; n < 0, unknown flags, a NULL X with n > 0,
+ * non-finite X.  n = 0 writes nothing.  All synchronous.  The evaluation state is left untouched: gp_phase2 / gp_finish / gp_predict* after any
+ * of the three give bit-identical results.
+ * Determinism: results are bit-identical from run to run, and a point's outputs depend on that point, the set and the model only -- the same bits
+ * alone, in any batch and at every chunk length (every product runs on one fixed GEMM kernel without split-k; fixed summation order, no
+ * floating-point atomics).
+ * Not covered: uncertain conditioning or query inputs; per-entry masks on Yc; the joint covariance and draws under the conditioning
+ * (cov' = cov - beta U U^T); making the conditioning permanent in the statistics; m > 1024. */
+int gp_condition_set(gp_ctx* ctx, int64_t m, const double* Xc /*(m,Q)*/, const double* Yc /*(m,D)*/);
+int gp_condition_predict(gp_ctx* ctx, int64_t n, const double* X /*(n,Q)*/, int flags, double* mean /*(n,D) or NULL*/, double* var /*(n) or NULL*/,
+                         double* reduction /*(n) or NULL: beta |u|^2 = var - var'*/);
+int gp_condition_clear(gp_ctx* ctx);
+
 /* ---- latent inference for new rows ---------------------------------------------------------------- */
 /* The bound of n NEW rows y (n,D) under q(x) = N(X_mu, diag X_S), with q(u) frozen at the optimum of the trained model (the statistics of the last
  * global step): per row, with O the observed columns (D_o of them), W and B as for gp_predict, v = W_O y_O and G = W_O W_O^T - D_o B,
