@@ -508,7 +508,7 @@ __global__ void grad_latest_kernel(const double* __restrict__ gmu, const double*
     double g = gS[i];
     if (raw) {
       double x = Xs[i];
-      if (have_dir && step != 0.0) x += step * dir[nq + i];
+      if (have_dir && step != 0.0) x = mul_then_add(step, dir[nq + i], x);      // the trial point's own raw variance, bit for bit (prep_elem_kernel)
       g *= softplus_slope(x);      // transformVar_grad, supporting_functions.py:165-168
     }
     out[nq + i] = -g;
@@ -1256,8 +1256,8 @@ __global__ void cg_update_kernel(int which, double a, long nq, double* __restric
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) {
     switch (which) {
       case 0: d[i] = -gnew[i]; break;
-      case 1: d[i] = a * d[i] - gnew[i]; break;
-      case 2: if (i < nq) Xmu[i] += a * d[i]; else Xs[i - nq] += a * d[i]; break;
+      case 1: d[i] = mul_then_add(a, d[i], -gnew[i]); break;
+      case 2: if (i < nq) Xmu[i] = mul_then_add(a, d[i], Xmu[i]); else Xs[i - nq] = mul_then_add(a, d[i], Xs[i - nq]); break;
       case 3: gold[i] = gnew[i]; break;
       case 4: gnew[i] = glatest[i]; break;
       default: { const double g = glatest[i]; gnew[i] = g; gold[i] = g; d[i] = -g; } break;
@@ -1265,22 +1265,47 @@ __global__ void cg_update_kernel(int which, double a, long nq, double* __restric
   }
 }
 // out[0..4] += (g_new.d, d.d, d.(g_latest - g_new), g_new.g_new, g_new.g_old); out[5] = max(out[5], max |d|)
+// The five sums are COMPENSATED (Ogita, Rump, Oishi: Dot2): every product's and every addition's rounding error is kept in a second accumulator,
+// through the thread's loop and the block fold alike, and added once at the end.  The order of the additions is unchanged (a thread's terms in
+// ascending order, block_fold<256>, the blocks in ascending order on the host); the result is the sum as if formed in twice the precision, so the
+// optimiser's alpha and Gamma, which cancel, do not depend on that order beyond the last bits.
+struct TwoSum { double s, e; };
+__host__ __device__ __forceinline__ TwoSum two_sum(double a, double b) {
+#pragma clang fp contract(off)
+  const double t = a + b, z = t - a;
+  return TwoSum{t, (a - (t - z)) + (b - z)};
+}
+__device__ __forceinline__ void dot2_step(double x, double y, double& s, double& c) {
+#pragma clang fp contract(off)
+  const double p = x * y;
+  const double pe = __builtin_fma(x, y, -p);
+  const TwoSum t = two_sum(s, p);
+  s = t.s;
+  c += pe + t.e;
+}
 __global__ void __launch_bounds__(256) cg_dots_kernel(long n2, const double* __restrict__ d, const double* __restrict__ gnew,
                                                       const double* __restrict__ gold, const double* __restrict__ glatest, double* part) {
   __shared__ double red[6][256];
-  double s[6] = {0, 0, 0, 0, 0, 0};
+  __shared__ double cmp[5][256];
+  double s[6] = {0, 0, 0, 0, 0, 0}, c[5] = {0, 0, 0, 0, 0};
   for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) {
     const double di = d[i], gn = gnew[i];
-    s[0] += gn * di; s[1] += di * di; s[2] += di * (glatest[i] - gn); s[3] += gn * gn; s[4] += gn * gold[i];
+    dot2_step(gn, di, s[0], c[0]); dot2_step(di, di, s[1], c[1]); dot2_step(di, glatest[i] - gn, s[2], c[2]);
+    dot2_step(gn, gn, s[3], c[3]); dot2_step(gn, gold[i], s[4], c[4]);
     s[5] = fmax(s[5], fabs(di));
   }
   for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = s[k];
+  for (int k = 0; k < 5; ++k) cmp[k][threadIdx.x] = c[k];
   __syncthreads();
   block_fold<256>([&](int i, int j) {
-    for (int k = 0; k < 5; ++k) red[k][i] += red[k][j];
+    for (int k = 0; k < 5; ++k) {
+      const TwoSum t = two_sum(red[k][i], red[k][j]);
+      red[k][i] = t.s;
+      cmp[k][i] += cmp[k][j] + t.e;
+    }
     red[5][i] = fmax(red[5][i], red[5][j]);
   });
-  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0] + (threadIdx.x < 5 ? cmp[threadIdx.x][0] : 0.0);
 }
 
 static int cg_ready(gp_ctx* c, const char* what) {
@@ -1313,11 +1338,13 @@ static int cg_reduce(gp_ctx* c, double* out6) {
   std::vector<double> h((size_t)nb * 6);
   GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
   GP_HIP(c, hipStreamSynchronize(c->stream));
+  double comp[5] = {0, 0, 0, 0, 0};
   for (int k = 0; k < 6; ++k) out6[k] = 0.0;
   for (int b = 0; b < nb; ++b) {
-    for (int k = 0; k < 5; ++k) out6[k] += h[(size_t)b * 6 + k];
+    for (int k = 0; k < 5; ++k) { const TwoSum t = two_sum(out6[k], h[(size_t)b * 6 + k]); out6[k] = t.s; comp[k] += t.e; }
     out6[5] = std::max(out6[5], h[(size_t)b * 6 + 5]);
   }
+  for (int k = 0; k < 5; ++k) out6[k] += comp[k];
   return GP_OK;
 }
 
@@ -1360,6 +1387,7 @@ extern "C" int gp_cg_abs(gp_ctx* c, double* out2) {
 extern "C" int gp_cg_max_d(gp_ctx* c, double alpha, double* out) {
   if (!c || !out) return GP_ERR_BAD_ARG;
   GP_TRY(cg_ready(c, "gp_cg_max_d"));
+  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_max_d: no search direction (gp_cg_set_grads first)");
   GP_HIP(c, hipSetDevice(c->device));
   double o[6];
   GP_TRY(cg_reduce(c, o));

@@ -1082,6 +1082,16 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
     if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_select_begin .. gp_select_end", name);
   }
   else if (!std::strcmp(name, "dir")) { src = c->dir; cnt = 2L * c->N * c->Q; }
+  // the resident CG vectors and the base embeddings as stored (Xs raw when uploaded raw): tests/test_gpu_resident_vectors.py
+  else if (!std::strcmp(name, "cg_g_new") || !std::strcmp(name, "cg_g_old") || !std::strcmp(name, "cg_g_latest")) {
+    if (!c->life.has_data() || !c->xs_raw)
+      return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' exists only with shard data and free embeddings (raw variances)", name);
+    src = name[5] == 'n' ? c->cg.g_new : name[5] == 'o' ? c->cg.g_old : c->cg.g_latest; cnt = 2L * c->N * c->Q;
+  }
+  else if (!std::strcmp(name, "Xmu") || !std::strcmp(name, "Xs")) {
+    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' before gp_upload_shard", name);
+    src = name[1] == 'm' ? c->Xmu : c->Xs; cnt = (long)c->N * c->Q;
+  }
   else if (!std::strncmp(name, "lbfgs_", 6)) {
     src = lbfgs_debug(c, name, &cnt);
     if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_lbfgs_begin .. gp_lbfgs_end, or not a vector that holds anything", name);

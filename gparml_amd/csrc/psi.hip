@@ -46,8 +46,8 @@ __global__ void __launch_bounds__(256) prep_elem_kernel(PrepArgs a) {
       s = a.Xs[i];
       if (a.raw) {
         if (a.dir && a.step != 0.0) {
-          m += a.step * a.dir[i];
-          s += a.step * a.dir[a.N * a.Q + i];
+          m = mul_then_add(a.step, a.dir[i], m);
+          s = mul_then_add(a.step, a.dir[a.N * a.Q + i], s);
         }
         s = softplus(s);
       }

@@ -10,6 +10,15 @@ namespace gp {
 __device__ __forceinline__ double softplus(double x) { return log(1.0 + exp(x)); }
 __device__ __forceinline__ double softplus_slope(double x) { return 1.0 / (1.0 + exp(-x)); }
 
+// x + a d with the product rounded first, as the reference's NumPy rounds it (local_MapReduce.py:205-211, scg_adapted_local_MapReduce.py:175-214):
+// never contracted into a fused multiply-add.  The trial point, grad_latest's variance transform at it, gp_cg_update's update_d and update_X all
+// go through here, so the resident vectors follow the reference's files to the bit and do not depend on what the compiler chooses to contract.
+__device__ __forceinline__ double mul_then_add(double a, double d, double x) {
+#pragma clang fp contract(off)
+  const double p = a * d;
+  return p + x;
+}
+
 // d1 = alpha S + 1, d2 = 2 alpha S + 1, u = alpha / d1 (Psi1), w = alpha / d2 and v2 = (alpha - w) / 2 = -2 V (psi2)
 struct VarQ { double d1, d2, u, w, v2; };
 __device__ __forceinline__ VarQ var_q(double a, double s) {

@@ -233,6 +233,19 @@ class ShardEngine(object):
         n2 = 2 * self.N_s * self.Q
         return self.peek('dir' if name == 'dir' else 'lbfgs_' + name, n2)[:n2].reshape(2, self.N_s, self.Q).copy()
 
+    def cg_peek(self, name):
+        """A resident vector as it lies on the device (gp_debug_peek; a test tool): 'cg_g_new', 'cg_g_old', 'cg_g_latest' or 'dir' as (2, N_s, Q);
+        'Xmu' or 'Xs' (the base embeddings as stored: raw variances when uploaded raw) as (N_s, Q)."""
+        shape = (self.N_s, self.Q) if name in ('Xmu', 'Xs') else (2, self.N_s, self.Q)
+        n = int(np.prod(shape))
+        return self.peek(name, n)[:n].reshape(shape).copy()
+
+    def cg_max_d(self, alpha):
+        """local max |alpha d| (gp_cg_max_d, scg_adapted_local_MapReduce.py:142-155)"""
+        out = ctypes.c_double()
+        self._ck(self.lib.gp_cg_max_d(self.h, float(alpha), ctypes.byref(out)), 'gp_cg_max_d')
+        return out.value
+
     def scale_stats(self, factor):
         self._ck(self.lib.gp_scale_stats(self.h, float(factor)), 'gp_scale_stats')
 

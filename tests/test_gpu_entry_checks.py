@@ -291,6 +291,34 @@ def test_status_and_message_are_the_parent_commits(world, name, ctx, fn):
     assert got == read_table()[name]
 
 
+@pytest.mark.gpu
+def test_cg_max_d_needs_a_direction_as_dots_and_abs_do():
+    """Not a row of the parent's table: the parent admitted gp_cg_max_d without a direction and reduced whatever the buffers held.  The three
+    reductions now share one rule and one wording; with a direction all three run."""
+    from gparml_amd import _lib
+    lib = _lib.load()
+    h, out, alone = ctypes.c_void_p(), np.zeros(6), ctypes.c_double(-1.0)
+    assert lib.gp_create(ctypes.byref(h), 0, N, D, M, Q) == 0
+    calls = {'gp_cg_dots': lambda: lib.gp_cg_dots(h, p(out)), 'gp_cg_abs': lambda: lib.gp_cg_abs(h, p(out)),
+             'gp_cg_max_d': lambda: lib.gp_cg_max_d(h, 0.5, ctypes.byref(alone))}
+    try:
+        for who, fn in calls.items():                                                    # no data
+            assert fn() == _lib.GP_ERR_STATE and lib.gp_last_error(h).decode() == who + ': no shard data'
+        assert lib.gp_upload_shard(h, p(Y0), p(XMU0), p(np.log(np.expm1(XS0))), 1) == 0
+        for who, fn in calls.items():                                                    # raw variances, no direction
+            assert fn() == _lib.GP_ERR_STATE and lib.gp_last_error(h).decode().startswith(who + ': no ') and 'gp_cg_set_grads first' in lib.gp_last_error(h).decode()
+        assert lib.gp_last_error(h).decode() == 'gp_cg_max_d: no search direction (gp_cg_set_grads first)' and alone.value == -1.0
+        d = _r.randn(2, N, Q)
+        assert lib.gp_set_direction(h, p(d)) == 0
+        for fn in calls.values():
+            assert fn() == 0
+        assert alone.value == 0.5 * np.max(np.abs(d))
+        assert lib.gp_set_direction(h, None) == 0                                        # dropped again
+        assert calls['gp_cg_max_d']() == _lib.GP_ERR_STATE
+    finally:
+        lib.gp_destroy(h)
+
+
 if __name__ == '__main__':          # record: GPARML_LIB=<the parent build> python3 tests/test_gpu_entry_checks.py > table
     from gparml_amd import _lib as _L
     _lib_ = _L.load()

@@ -1,64 +1,13 @@
 """The two optimisers (gparml_amd.scg_adapted, gparml_amd.gd) without a GPU: the split formulation (global part on the
 host, per-point part behind an ``ops`` object) must follow exactly the same trajectory as the same problem with every
-parameter in the host vector.  The numpy ``ops`` below implement the function names of scg_adapted_local_MapReduce.py:29-243
+parameter in the host vector.  The numpy ``ops`` of tests/cg_ref.py implement the function names of scg_adapted_local_MapReduce.py:29-243
 and gd_local_MapReduce.py:14-105 on in-memory vectors (what the reference does through .npy files)."""
 import numpy as np
 import pytest
 
+from cg_ref import NumpyOps
 from gparml_amd.gd import GD
 from gparml_amd.scg_adapted import SCG_adapted
-
-
-class NumpyOps(object):
-    """Per-point part X (shape (n,)) with the reference's trial-point protocol: the objective is evaluated at X + step*d."""
-
-    def __init__(self, X0):
-        self.X = X0.copy()
-        self.latest = np.zeros_like(X0)
-        self.new = self.old = self.d = None
-
-    # scg_adapted_local_MapReduce.py / gd_local_MapReduce.py names
-    def embeddings_set_grads(self, folder=None):
-        self.new, self.old, self.d = self.latest.copy(), self.latest.copy(), -self.latest
-
-    def embeddings_get_grads_mu(self, folder=None):
-        return float(np.dot(self.new, self.d))
-
-    def embeddings_get_grads_kappa(self, folder=None):
-        return float(np.dot(self.d, self.d))
-
-    def embeddings_get_grads_theta(self, folder=None):
-        return float(np.dot(self.d, self.latest - self.new))
-
-    def embeddings_get_grads_current_grad(self, folder=None):
-        return float(np.dot(self.new, self.new)) if not self.gd else float(np.sum(np.abs(self.new)))
-
-    def embeddings_get_grads_gamma(self, folder=None):      # sum grad_new * grad_old (:128-140); |grad_new|^2 is in current_grad
-        return float(np.dot(self.new, self.old))
-
-    def embeddings_get_grads_max_d(self, folder, alpha):
-        return float(np.max(np.abs(alpha * self.d)))
-
-    def embeddings_get_grads_max_gradnow(self, folder=None):
-        return float(np.max(np.abs(self.new)))
-
-    def embeddings_set_grads_reset_d(self, folder=None):
-        self.d = -self.new
-
-    def embeddings_set_grads_update_d(self, folder, gamma):
-        self.d = (gamma * self.d - self.new) if not self.gd else -(self.new + gamma * self.d)
-
-    def embeddings_set_grads_update_X(self, folder, alpha):
-        self.X = self.X + alpha * self.d
-
-    def embeddings_set_grads_update_grad_old(self, folder=None):
-        self.old = self.new.copy()
-
-    def embeddings_set_grads_update_grad_new(self, folder=None):
-        self.new = self.latest.copy()
-
-    embeddings_set_grads_update_grad_now = embeddings_set_grads_update_grad_new
-    gd = False
 
 
 def _problem(n_host=40, n_local=7, seed=0):   # n_host > iterations: the restart after x.size successes (scg_adapted.py:250) counts the host part only
