@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get('GPARML_LIB') or os.path.join(_HERE, 'libgparml_hip.so
 
 GP_OK, GP_ERR_BAD_ARG, GP_ERR_NOT_PD, GP_ERR_NON_FINITE, GP_ERR_HIP, GP_ERR_STATE, GP_ERR_UNSUPPORTED, GP_RETRY_JITTER, GP_ERR_RCCL = range(9)
 GP_COMM_ID_BYTES = 128
+GP_PATHS_WEIGHTS_PER_ROW = 1       # gp_paths_grad: weights (n_draws, n, D), one row per (draw, point)
 
 # gp_download selectors (include/gparml_hip.h)
 ARR = dict(KMM=0, KMM_INV=1, PSI1=2, PSI2_SUM=3, PSI1TY=4, KMM_PLUS_OP_INV=5, DF_DKMM=6, DF_DPSI1TY=7, DF_DPSI2=8,
@@ -68,6 +69,7 @@ SIGNATURES = {
     'gp_paths_set': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),
     'gp_paths_eval': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp]),
     'gp_paths_clear': (ctypes.c_int, [_vp]),
+    'gp_paths_grad': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp, _dp, _dp]),
     'gp_condition_set': (ctypes.c_int, [_vp, _i64, _dp, _dp]),
     'gp_condition_predict': (ctypes.c_int, [_vp, _i64, _dp, ctypes.c_int, _dp, _dp, _dp]),
     'gp_condition_clear': (ctypes.c_int, [_vp]),

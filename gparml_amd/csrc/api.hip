@@ -887,6 +887,29 @@ extern "C" int gp_paths_eval(gp_ctx* c, int64_t n, const double* X, int flags, d
   return run_paths_eval(c, (long)n, X, out, mean);
 }
 
+// the argument errors that need nothing of the model first, then gp_paths_eval's state rule (a model, a current plan), then the arrays
+extern "C" int gp_paths_grad(gp_ctx* c, int64_t n, const double* X, int flags, const double* weights, double* jac, double* grad, double* metric,
+                             double* mean_jac) {
+  if (!c) return GP_ERR_BAD_ARG;
+  if (n < 1) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: n must be >= 1 (got %ld)", (long)n);
+  if (flags & ~GP_PATHS_WEIGHTS_PER_ROW) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: unknown flags %d", flags);
+  if (!jac && !grad && !metric && !mean_jac) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: jac, grad, metric and mean_jac are all NULL");
+  if ((grad != nullptr) != (weights != nullptr)) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: weights go with grad (both, or neither)");
+  if (!X) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: X is NULL");
+  if (const int rc = model_ready(c, "gp_paths_grad"); rc != GP_OK) {
+    c->paths.reset();            // the draws were of a model that is gone
+    return rc;
+  }
+  if (!paths_plan_current(c))
+    return fail(c, GP_ERR_STATE, "gp_paths_grad needs gp_paths_set on the model as it is now (none yet, or a global step, new statistics or new globals since)");
+  const int64_t S = paths_plan_draws(c);
+  if (n > INT64_MAX / (S * c->D * std::max(c->Q, 1) * c->Q)) return fail(c, GP_ERR_BAD_ARG, "gp_paths_grad: n_draws n D Q overflows");
+  GP_TRY(finite_check(c, "gp_paths_grad", "X", X, (size_t)n * c->Q));
+  if (weights)
+    GP_TRY(finite_check(c, "gp_paths_grad", "weights", weights, (flags & GP_PATHS_WEIGHTS_PER_ROW) ? (size_t)S * n * c->D : (size_t)c->D));
+  return run_paths_grad(c, (long)n, X, flags, weights, jac, grad, metric, mean_jac);
+}
+
 extern "C" int gp_paths_clear(gp_ctx* c) {
   if (!c) return GP_ERR_BAD_ARG;
   GP_HIP(c, hipSetDevice(c->device));

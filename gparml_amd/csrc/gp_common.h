@@ -373,6 +373,8 @@ long paths_operand_bytes(const gp_ctx* c, int n_draws, int F);       // the pack
 int run_paths_set(gp_ctx* c, int n_draws, int F, const double* omega, const double* centre, const double* w, const double* eps_u);
 bool paths_plan_current(gp_ctx* c);                                  // a plan of the model as it is now; a stale one is dropped
 int run_paths_eval(gp_ctx* c, long n, const double* X, double* out, double* mean);
+int paths_plan_draws(const gp_ctx* c);                               // n_draws of the plan (there is one)
+int run_paths_grad(gp_ctx* c, long n, const double* X, int flags, const double* weights, double* jac, double* grad, double* metric, double* mean_jac);
 // grad.hip
 int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dvar, double* metric, double* logdet);
 // curve.hip
@@ -433,7 +435,7 @@ extern std::atomic<int> g_opt_p2_rem;                         // p2_rem.hip: 0 o
 extern std::atomic<int> g_opt_pred_rows, g_opt_inf_rows, g_opt_km_rows;   // predict.hip, infer.hip, kmeans.hip (and pca.hip: the same switch)
 extern std::atomic<int> g_opt_nn_rows;                        // nearest.hip
 extern std::atomic<int> g_opt_knn_rows;                       // knn.hip
-extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval
+extern std::atomic<int> g_opt_paths_rows;                     // paths.hip: rows per chunk of gp_paths_eval (gp_paths_grad: k / Q points)
 extern std::atomic<int> g_opt_sel_rows;                       // select.hip: host rows per upload chunk of gp_select_begin
 extern std::atomic<int> g_opt_curve_curves;                   // curve.hip: curves per chunk of gp_curve_energy
 extern std::atomic<int> g_opt_inf_patterns;                   // infer.hip: distinct patterns per chunk of gp_infer_*_rows

@@ -52,6 +52,12 @@ __global__ void __launch_bounds__(256) grad_dk_kernel(const double* __restrict__
   }
 }
 
+// the launch of gp_predict_grad and of gp_paths_grad (paths.hip): pts points of X against P1 = Psi1*, rows = round_up(pts Q, 128) rows of dK
+int grad_launch_dk(gp_ctx* c, const double* P1, const double* X, long pts, long rows, double* dK) {
+  GP_LAUNCH(c, c->stream, grad_dk_kernel, dim3((unsigned)blocks_for(rows * c->Mp / 2)), dim3(256), 0, P1, X, c->Zt, c->alpha, pts, rows, c->M, c->Mp, c->Q, dK);
+  return GP_OK;
+}
+
 struct GradArgs {
   const double* T;      // [rows][ldt] = [jac rows (Dp) | a' (Mp) | b' (Mp)]
   const double* R;      // [points][2 Mp] rows [a | b]
@@ -313,8 +319,7 @@ int run_predict_grad(gp_ctx* c, long n, const double* X, double* jac, double* dv
   for (long n0 = 0; n0 < n; n0 += pts) {
     const long cnt = std::min(pts, n - n0), rows = round_up(cnt * Q, TILE);
     GP_TRY_RC(pred_chunk_front(c, pred_at(X), n0, cnt, pred_into(p.X).factors(need_l ? p.R.get() : nullptr, 2 * Mp)));
-    GP_LAUNCH(c, st, grad_dk_kernel, dim3((unsigned)blocks_for(rows * Mp / 2)), dim3(256), 0, k.psi1, p.X, c->Zt, c->alpha, cnt, rows, c->M, (int)Mp,
-              (int)Q, p.dK);
+    GP_TRY_RC(grad_launch_dk(c, k.psi1, p.X, cnt, rows, p.dK));
     GP_TRY_RC(pred_project(c, p.dK, rows, {need_e ? p.T.get() : nullptr, ldt}, {need_l ? p.T + Dp : nullptr, ldt}, GEMM_BY_SIZE));
     GradArgs a;
     a.T = p.T; a.R = p.R; a.alpha = c->alpha; a.ldt = ldt; a.M = c->M; a.Mp = (int)Mp; a.D = (int)D; a.Dp = (int)Dp; a.Q = (int)Q; a.sf2 = c->sf2;

@@ -50,6 +50,12 @@ int pred_unc_begin(gp_ctx* c);
 int pred_chunk_var_unc(gp_ctx* c, long cnt, double noise, double* var);
 // fill_mean_kernel: C [rows][cols] = mean[i][col mod D] for i < n and col < used, else 0; a product with beta = 1 then adds a draw's terms on top
 int pred_fill_mean(gp_ctx* c, const double* mean, long n, long rows, long cols, long used, double* C);
+// the same with a leading dimension on the source: C [rows][cols] = src[i][col mod D] (row stride lds) for i < n and col < used, else 0 -- the
+// rows of gp_paths_grad are (point, q) rows of the mean's Jacobian.  A sibling kernel: fill_mean_kernel and its callers keep their bits
+int pred_fill_rows(gp_ctx* c, const double* src, long lds, long n, long rows, long cols, long used, double* C);
+// grad.hip's grad_dk_kernel as gp_predict_grad launches it: dK [(i, q)][Mp] = d k(x_i) / d x_q for i < pts, exact zeros in the rows beyond (and in
+// the columns >= M), rows = round_up(pts Q, 128); P1 = Psi1* and X the centred inputs of the chunk pred_chunk_front has just run
+int grad_launch_dk(gp_ctx* c, const double* P1, const double* X, long pts, long rows, double* dK);
 const double* pred_debug_lea(const gp_ctx* c, long* n);               // gp_debug_peek: the uncertain-input plan's LEA, NULL / 0 without one
 
 }  // namespace gp

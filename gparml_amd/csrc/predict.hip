@@ -84,6 +84,15 @@ __global__ void __launch_bounds__(256) fill_mean_kernel(const double* __restrict
   }
 }
 
+// the same from a source with a leading dimension (the Jacobian rows of gp_paths_grad): C[i][col] = src[i lds + col mod D]
+__global__ void __launch_bounds__(256) fill_rows_kernel(const double* __restrict__ src, long lds, long n, int D, long rows, long cols, long used, double* __restrict__ C) {
+  const long total = rows * cols;
+  for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256L) {
+    const long i = e / cols, col = e - i * cols;
+    C[e] = (i < n && col < used) ? src[i * lds + col % D] : 0.0;
+  }
+}
+
 // ---- uncertain inputs: psi2* E on the FP64 matrix core ---------------------------------------------------------------------------------------
 // Workgroup (point n, column tile c0 = 128 blockIdx.y), four waves.  A pass covers 64 rows m (16 per wave); for every chunk of PW_KC rows m' the
 // workgroup stages E[m'][c0 ..] (pW), z_m' (pZ) and LEA[n][m'] (pL) in LDS, and every wave steps through the chunk four m' at a time:
@@ -310,6 +319,11 @@ int pred_chunk_mean(gp_ctx* c, long cnt, double* mean) {
 
 int pred_fill_mean(gp_ctx* c, const double* mean, long n, long rows, long cols, long used, double* C) {
   GP_LAUNCH(c, c->stream, fill_mean_kernel, dim3((unsigned)blocks_for(rows * cols)), dim3(256), 0, mean, n, c->D, rows, cols, used, C);
+  return GP_OK;
+}
+
+int pred_fill_rows(gp_ctx* c, const double* src, long lds, long n, long rows, long cols, long used, double* C) {
+  GP_LAUNCH(c, c->stream, fill_rows_kernel, dim3((unsigned)blocks_for(rows * cols)), dim3(256), 0, src, lds, n, c->D, rows, cols, used, C);
   return GP_OK;
 }
 

@@ -505,6 +505,33 @@ class ShardEngine(object):
         self._ck(self.lib.gp_paths_eval(self.h, n, px, 0, out.ctypes.data_as(_lib._dp), mean.ctypes.data_as(_lib._dp) if want_mean else None), 'gp_paths_eval')
         return (out, mean) if want_mean else out
 
+    def paths_grad(self, X, weights=None, jac=True, metric=True, want_mean=False):
+        """Derivatives of the draws of ``paths_set`` with respect to the input, at the new deterministic inputs X (n, Q).  Returns a dict of the
+        requested arrays: ``jac`` (n_draws, n, D, Q) d out[s, i, d] / d x_q; ``metric`` (n_draws, n, Q, Q) the pull-back metric J_s^T J_s of every
+        sampled surface (symmetric bit for bit); with ``weights`` also ``grad`` (n_draws, n, Q) = sum_d weights[d] jac[s, i, d, :] -- ``weights``
+        (D,) scalarises every draw the same way, ``weights`` (n_draws, n, D) gives every (draw, point) its own (the vector-Jacobian product);
+        with ``want_mean`` also ``mean_jac`` (n, D, Q), the Jacobian of the mean.  A point's values are the same bits alone, in any batch and
+        for any subset of the outputs.  The evaluation state and the draws are left untouched."""
+        X, px = self._joint_X(X)
+        n, Q, S = X.shape[0], self.Q, getattr(self, '_paths_draws', 0)
+        flags, pw = 0, None
+        out = {}
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            assert weights.shape in ((self.D,), (S, n, self.D)), 'weights shape %s: (%d,) or (%d, %d, %d) expected' % (weights.shape, self.D, S, n, self.D)
+            flags = _lib.GP_PATHS_WEIGHTS_PER_ROW if weights.ndim == 3 else 0
+            weights, pw = _lib.as_c(weights)
+            out['grad'] = np.empty((S, n, Q))
+        if jac:
+            out['jac'] = np.empty((S, n, self.D, Q))
+        if metric:
+            out['metric'] = np.empty((S, n, Q, Q))
+        if want_mean:
+            out['mean_jac'] = np.empty((n, self.D, Q))
+        p = lambda k: out[k].ctypes.data_as(_lib._dp) if k in out else None
+        self._ck(self.lib.gp_paths_grad(self.h, n, px, flags, pw, p('jac'), p('grad'), p('metric'), p('mean_jac')), 'gp_paths_grad')
+        return out
+
     def paths_clear(self):
         """Drop the draws of ``paths_set`` and free their device memory."""
         self._ck(self.lib.gp_paths_clear(self.h), 'gp_paths_clear')

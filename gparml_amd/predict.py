@@ -36,9 +36,49 @@ class PathDraws(object):
         self._token = engine.paths_token
 
     def __call__(self, X, want_mean=False):
+        return self._live().paths_eval(X, want_mean=want_mean)
+
+    def _live(self):
         if self.engine is None or self.engine.paths_token != self._token:
             raise RuntimeError('these draws are gone: closed, or replaced by a later paths_set / paths_clear on the same engine -- draw again')
-        return self.engine.paths_eval(X, want_mean=want_mean)
+        return self.engine
+
+    def jacobian(self, X):
+        """d draws(X)[s, i, d] / d x_q: (n_draws, n, D, Q) (ShardEngine.paths_grad)."""
+        return self._live().paths_grad(X, jac=True, metric=False)['jac']
+
+    def metric(self, X):
+        """The pull-back metric J_s^T J_s of every sampled surface at the points X: (n_draws, n, Q, Q), symmetric bit for bit -- a sampled
+        Riemannian geometry where ``Predictor.metric`` gives the expected one."""
+        return self._live().paths_grad(X, jac=False, metric=True)['metric']
+
+    def value_and_grad(self, X, weights):
+        """``(value, grad)`` of the scalarised draws ``sum_d weights[d] draws(X)[s, i, d]``: value (n_draws, n), grad (n_draws, n, Q) with respect
+        to the point -- what climbing a drawn function (Thompson sampling) needs.  ``weights`` (D,), or (n_draws, n, D) for a weight per (draw,
+        point).  Two device calls: the value from ``paths_eval``, the gradient from ``paths_grad``."""
+        eng = self._live()
+        weights = numpy.asarray(weights, dtype=float)
+        out = eng.paths_eval(X)
+        grad = eng.paths_grad(X, weights=weights, jac=False, metric=False)['grad']
+        return numpy.einsum('snd,...d->sn', out, weights) if weights.ndim == 1 else numpy.einsum('snd,snd->sn', out, weights), grad
+
+    def curve_energy(self, X):
+        """Energy of discrete curves X (n_curves, T, Q) on every sampled surface, in ``ShardEngine.curve_energy``'s normalisation:
+        ``energy[s, c] = 1/2 (T - 1) sum_t |f_s(x_{t+1}) - f_s(x_t)|^2`` (n_draws, n_curves) and its gradient with respect to the curve's points
+        (n_draws, n_curves, T, Q).  One ``paths_eval`` for the surface's points and one ``paths_grad`` whose per-row weights are the derivative of
+        the sum with respect to f_s(x_t), ``2 (2 f_t - f_{t-1} - f_{t+1})`` (one-sided at the two ends); the sums over t are formed on the host."""
+        eng = self._live()
+        X = numpy.asarray(X, dtype=float)
+        assert X.ndim == 3 and X.shape[1] >= 2, 'X shape %s: (n_curves, T >= 2, Q) expected' % (X.shape,)
+        C, T, Q = X.shape
+        f = eng.paths_eval(X.reshape(C * T, Q)).reshape(self.n_draws, C, T, -1)
+        df = f[:, :, 1:] - f[:, :, :-1]                                   # (S, C, T - 1, D)
+        half = 0.5 * (T - 1)
+        w = numpy.zeros_like(f)                                           # d sum_t |df_t|^2 / d f_t
+        w[:, :, :-1] -= 2.0 * df
+        w[:, :, 1:] += 2.0 * df
+        grad = eng.paths_grad(X.reshape(C * T, Q), weights=w.reshape(self.n_draws, C * T, -1), jac=False, metric=False)['grad']
+        return half * numpy.sum(df * df, axis=(2, 3)), half * grad.reshape(self.n_draws, C, T, Q)
 
     def close(self):
         if self.engine is not None:

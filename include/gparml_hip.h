@@ -349,6 +349,28 @@ int gp_paths_set(gp_ctx* ctx, int n_draws, int F, const double* omega /*(F,Q)*/,
 int gp_paths_eval(gp_ctx* ctx, int64_t n, const double* X /*(n,Q)*/, int flags, double* out /*(n_draws,n,D)*/, double* mean /*(n,D) or NULL*/);
 int gp_paths_clear(gp_ctx* ctx);
 
+/* Derivatives of the draws of gp_paths_set with respect to the input (csrc/paths.hip).  With a'_q = Lk^-1 dk_q,
+ * b'_q = La^-1 dk_q and the mean's Jacobian of gp_predict_grad,
+ *   jac[s][i][d][q] = d out[s][i][d] / d x_q = jac_mean[i][d][q] + dphi_q(x_i) . w_s[:,d] - a'_q(x_i) . G_s[:,d] + b'_q(x_i) . eps_u[s][:,d]
+ *   dphi_q(x) = [ -(scale sin theta_f) omega[f][q]  (f < F) ;  (scale cos theta_f) omega[f][q] ],    scale = sqrt(sf2 / F)
+ *   grad[s][i][q]      = sum_d weights[..][d] jac[s][i][d][q]        (d ascending; weights (D), or (n_draws,n,D) with GP_PATHS_WEIGHTS_PER_ROW)
+ *   metric[s][i][q][r] = sum_d jac[s][i][d][q] jac[s][i][d][r]       (d ascending; written for q <= r and mirrored from the same value)
+ *   mean_jac[i][d][q]  = the mean's Jacobian as this path computes it (what every draw's jac is with zero normals, bit for bit)
+ * Each output may be NULL; weights is NULL exactly when grad is.  Needs a current plan: GP_ERR_STATE exactly where gp_paths_eval returns it (and the
+ * stale plan is dropped).  GP_ERR_BAD_ARG, decided before anything is launched: n < 1, a NULL or non-finite X, a flag bit other than
+ * GP_PATHS_WEIGHTS_PER_ROW, all four outputs NULL, grad without weights or weights without grad, non-finite weights.  Synchronous; the evaluation
+ * state, the plan and the results of gp_predict / gp_predict_grad / gp_paths_eval are left untouched.  gp_paths_eval's determinism contract holds:
+ * a point's outputs depend on the point, the plan, the model and (grad) its weights only -- the same bits alone, in any batch, in any order,
+ * wherever a chunk boundary falls and for any subset of requested outputs.  Points are taken in chunks of about 64 MB of left operand, one row per
+ * (point, q).  Not covered: uncertain inputs, second derivatives, results kept on the device. */
+#define GP_PATHS_WEIGHTS_PER_ROW 1
+int gp_paths_grad(gp_ctx* ctx, int64_t n, const double* X /*(n,Q)*/, int flags,
+                  const double* weights /* (D), or (n_draws,n,D) with GP_PATHS_WEIGHTS_PER_ROW; NULL iff grad is NULL */,
+                  double* jac      /*(n_draws,n,D,Q) or NULL*/,
+                  double* grad     /*(n_draws,n,Q)   or NULL*/,
+                  double* metric   /*(n_draws,n,Q,Q) or NULL*/,
+                  double* mean_jac /*(n,D,Q) or NULL*/);
+
 /* The posterior conditioned on m extra observed rows (Xc, Yc), without a refit: a rank-m update of the model of the last global step, the mirror
  * image of gp_loo_score's downdate (csrc/condition.hip).  Fixed Z, sf2, alpha, beta; the trained model may have fixed or
  * free embeddings, the conditioning rows and the queries have deterministic inputs.  With a = Lk^-1 k(x), b = La^-1 k(x), mean and var as
