@@ -385,6 +385,8 @@ int run_infer(gp_ctx* c, int mode, long n, const double* Y, const int* cols, int
 int run_infer_rows(gp_ctx* c, int mode, long n, const double* Y, const unsigned char* observed, double* X_mu, double* X_S, int raw, int max_iters,
                    double gtol, double* L, double* grad_mu, double* grad_S, int* iters);
 const double* infer_debug_lea(const gp_ctx* c, long* n);              // gp_debug_peek: the chunk's LEA, NULL / 0 without a plan
+// gp_debug_peek "infer_x", "_gn", "_go", "_d", "_Scur", "_sc", "_si" (ints: *ints set), "_xe", "_fe", "_ge": NULL / 0 before gp_infer_latent, NULL / -1 unknown
+const void* infer_debug_scg(const gp_ctx* c, const char* name, long* cnt, bool* ints);
 // kmeans.hip
 int run_kmeans(gp_ctx* c, long n, const double* X, int K, const double* centres, double* sums, int64_t* counts, double* dist2, int32_t* labels);
 // select.hip (the plan lives from gp_select_begin to gp_select_end; the entry points check its presence and the arguments: api.hip)

@@ -35,6 +35,7 @@
 #include "varpoint.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <numeric>
 #include <unordered_map>
 
@@ -398,7 +399,7 @@ __global__ void __launch_bounds__(256) inf_scg_trial_kernel(ScgArgs a) {
     }
     const double theta = sc[IS_THETA], kappa = sc[IS_KAPPA];
     double lam = sc[IS_LAM];
-    double delta = theta + lam * kappa;
+    double delta = fma(lam, kappa, theta);      // spelt out: tests/infer_scg_ref.py emulates exactly this, one rounding
     if (!(delta > 0.0)) {
       delta = lam * kappa;
       lam = lam - theta / kappa;
@@ -445,7 +446,7 @@ __global__ void __launch_bounds__(256) inf_scg_update_kernel(ScgArgs a) {
       double gg = 0.0, og = 0.0;
       for (int i = 0; i < n2; ++i) { gg = fma(gn[i], gn[i], gg); og = fma(go[i], gn[i], og); }
       const double Gamma = (og - gg) / mu;
-      for (int i = 0; i < n2; ++i) d[i] = Gamma * d[i] - gn[i];
+      for (int i = 0; i < n2; ++i) d[i] = fma(Gamma, d[i], -gn[i]);      // spelt out: tests/infer_scg_ref.py emulates exactly this, one rounding
     }
     si[II_NSUCC] = nsucc;
     si[II_SUCCESS] = ok ? 1 : 0;
@@ -542,6 +543,32 @@ const double* infer_debug_lea(const gp_ctx* c, long* n) {
   const InfChunk* k = c->infer ? c->infer->chunk.get() : nullptr;
   *n = k ? (long)k->LEA.size() : 0;
   return k ? k->LEA.get() : nullptr;
+}
+
+// gp_debug_peek "infer_<t>": the chunk's optimiser state x, gn, go, d ([rows][2Q]), Scur ([rows][Q]), sc ([rows][IS_COUNT]), si ([rows][II_COUNT]
+// ints, without the active-row count behind them: *ints set) and its last evaluation xe, ge ([rows][2Q]), fe ([rows]), as gp_infer_latent left them
+// (tests/test_gpu_infer_scg.py).  NULL with *cnt = 0 before a gp_infer_latent call has built the state, NULL with *cnt = -1 for an unknown name.
+const void* infer_debug_scg(const gp_ctx* c, const char* name, long* cnt, bool* ints) {
+  const InfChunk* k = c->infer ? c->infer->chunk.get() : nullptr;
+  const InfOpt* o = k ? k->opt.get() : nullptr;
+  const char* t = name + 6;          // behind "infer_"
+  const long R = k ? k->rows : 0, n2 = 2L * c->Q;
+  const void* src = nullptr;
+  long per = -1;
+  *ints = false;
+  auto is = [t](const char* s) { return !std::strcmp(t, s); };
+  if (is("x")) { per = n2; if (o) src = o->x.get(); }
+  else if (is("gn")) { per = n2; if (o) src = o->gn.get(); }
+  else if (is("go")) { per = n2; if (o) src = o->go.get(); }
+  else if (is("d")) { per = n2; if (o) src = o->d.get(); }
+  else if (is("Scur")) { per = c->Q; if (o) src = o->Scur.get(); }
+  else if (is("sc")) { per = IS_COUNT; if (o) src = o->sc.get(); }
+  else if (is("si")) { per = II_COUNT; *ints = true; if (o) src = o->si.get(); }
+  else if (is("xe")) { per = n2; if (o) src = k->xe.get(); }
+  else if (is("ge")) { per = n2; if (o) src = k->ge.get(); }
+  else if (is("fe")) { per = 1; if (o) src = k->fe.get(); }
+  *cnt = per < 0 ? -1 : src ? R * per : 0;
+  return src;
 }
 
 static inline unsigned inf_blocks(long n, long cap = 16384) { return (unsigned)std::max<long>(1, std::min<long>((n + 255) / 256, cap)); }

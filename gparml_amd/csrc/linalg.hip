@@ -1050,6 +1050,7 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   GP_HIP(c, hipSetDevice(c->device));
   const long mm = (long)c->Mp * c->Mp, md = (long)c->Mp * c->Dp;
   const double* src = nullptr; long cnt = 0;
+  const void* src_any = nullptr; bool ints = false;      // a buffer that may hold ints (infer_debug_scg)
   if (!std::strcmp(name, "Linv")) { src = c->gstep.Linv; cnt = 2 * mm; }
   else if (!std::strcmp(name, "Inv")) { src = c->gstep.Inv; cnt = 2 * mm; }
   else if (!std::strcmp(name, "E")) { src = c->gstep.E; cnt = md; }
@@ -1077,6 +1078,12 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
   else if (!std::strcmp(name, "pred_LEA")) src = pred_debug_lea(c, &cnt);
   else if (!std::strcmp(name, "infer_LEA")) src = infer_debug_lea(c, &cnt);
+  // the per-row SCG of gp_infer_latent as it lies on the device: tests/test_gpu_infer_scg.py
+  else if (!std::strncmp(name, "infer_", 6)) {
+    src_any = infer_debug_scg(c, name, &cnt, &ints);
+    if (!src_any && cnt < 0) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
+    if (!src_any) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' before gp_infer_latent has built the optimiser's state", name);
+  }
   else if (!std::strcmp(name, "select_L") || !std::strcmp(name, "select_d")) {
     src = select_debug(c, name[7] == 'L', &cnt);
     if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_select_begin .. gp_select_end", name);
@@ -1099,6 +1106,12 @@ extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
   else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
   if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
   GP_HIP(c, hipStreamSynchronize(c->stream));
-  GP_HIP(c, hipMemcpy(out, src, cnt * 8, hipMemcpyDeviceToHost));
+  if (ints) {                                  // widened on the host after the copy
+    std::vector<int> h((size_t)cnt);
+    GP_HIP(c, hipMemcpy(h.data(), src_any, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost));
+    std::copy(h.begin(), h.end(), out);
+    return (int)GP_OK;
+  }
+  GP_HIP(c, hipMemcpy(out, src_any ? src_any : src, cnt * 8, hipMemcpyDeviceToHost));
   return (int)GP_OK;
 }
