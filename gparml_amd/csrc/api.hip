@@ -102,12 +102,6 @@ int Workspace::alloc(gp_ctx* c) {
   capacity = workspace_capacity(c);
   return buf.alloc(c, capacity);
 }
-
-int CgState::alloc(gp_ctx* c) {
-  const size_t n = (size_t)2 * c->N * c->Q;
-  GP_TRY(g_latest.alloc(c, n)); GP_TRY(g_new.alloc(c, n)); GP_TRY(g_old.alloc(c, n));
-  return GP_OK;
-}
 }  // namespace gp
 
 using namespace gp;
@@ -514,9 +508,6 @@ __global__ void grad_latest_kernel(const double* __restrict__ gmu, const double*
     out[nq + i] = -g;
   }
 }
-
-static bool g_force_staging = false;   // test hook: take the cross-device path of gp_buffer_combine on one device
-extern "C" int gp_debug_force_staging(int on) { g_force_staging = on != 0; return GP_OK; }
 
 extern "C" int gp_buffer_combine(gp_ctx* dst, const gp_ctx* src, int which, int op) {
   if (!dst || !src) return GP_ERR_BAD_ARG;
@@ -1269,185 +1260,4 @@ extern "C" int gp_finish(gp_ctx* c, double* F, double* grad_Z, double* grad_sf2,
   if (grad_sf2) *grad_sf2 = c->gstep.h_gs[GS_GRAD_SF2];
   if (grad_beta) *grad_beta = c->gstep.h_gs[GS_GRAD_BETA];
   return GP_OK;
-}
-// ---- resident CG vectors (scg_adapted_local_MapReduce.py:29-243) --------------------------------------------------------
-// which: 0 d = -g_new (reset_d :160-173) | 1 d = a*d - g_new (update_d :175-189) | 2 X += a*d (update_X :191-214)
-//        3 g_old = g_new (:216-229) | 4 g_new = g_latest (:231-243) | 5 set_grads: g_new = g_old = g_latest, d = -g_latest (:29-55)
-__global__ void cg_update_kernel(int which, double a, long nq, double* __restrict__ d, double* __restrict__ gnew, double* __restrict__ gold,
-                                 const double* __restrict__ glatest, double* __restrict__ Xmu, double* __restrict__ Xs) {
-  const long n2 = 2 * nq;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) {
-    switch (which) {
-      case 0: d[i] = -gnew[i]; break;
-      case 1: d[i] = mul_then_add(a, d[i], -gnew[i]); break;
-      case 2: if (i < nq) Xmu[i] = mul_then_add(a, d[i], Xmu[i]); else Xs[i - nq] = mul_then_add(a, d[i], Xs[i - nq]); break;
-      case 3: gold[i] = gnew[i]; break;
-      case 4: gnew[i] = glatest[i]; break;
-      default: { const double g = glatest[i]; gnew[i] = g; gold[i] = g; d[i] = -g; } break;
-    }
-  }
-}
-// out[0..4] += (g_new.d, d.d, d.(g_latest - g_new), g_new.g_new, g_new.g_old); out[5] = max(out[5], max |d|)
-// The five sums are COMPENSATED (Ogita, Rump, Oishi: Dot2): every product's and every addition's rounding error is kept in a second accumulator,
-// through the thread's loop and the block fold alike, and added once at the end.  The order of the additions is unchanged (a thread's terms in
-// ascending order, block_fold<256>, the blocks in ascending order on the host); the result is the sum as if formed in twice the precision, so the
-// optimiser's alpha and Gamma, which cancel, do not depend on that order beyond the last bits.
-struct TwoSum { double s, e; };
-__host__ __device__ __forceinline__ TwoSum two_sum(double a, double b) {
-#pragma clang fp contract(off)
-  const double t = a + b, z = t - a;
-  return TwoSum{t, (a - (t - z)) + (b - z)};
-}
-__device__ __forceinline__ void dot2_step(double x, double y, double& s, double& c) {
-#pragma clang fp contract(off)
-  const double p = x * y;
-  const double pe = __builtin_fma(x, y, -p);
-  const TwoSum t = two_sum(s, p);
-  s = t.s;
-  c += pe + t.e;
-}
-__global__ void __launch_bounds__(256) cg_dots_kernel(long n2, const double* __restrict__ d, const double* __restrict__ gnew,
-                                                      const double* __restrict__ gold, const double* __restrict__ glatest, double* part) {
-  __shared__ double red[6][256];
-  __shared__ double cmp[5][256];
-  double s[6] = {0, 0, 0, 0, 0, 0}, c[5] = {0, 0, 0, 0, 0};
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) {
-    const double di = d[i], gn = gnew[i];
-    dot2_step(gn, di, s[0], c[0]); dot2_step(di, di, s[1], c[1]); dot2_step(di, glatest[i] - gn, s[2], c[2]);
-    dot2_step(gn, gn, s[3], c[3]); dot2_step(gn, gold[i], s[4], c[4]);
-    s[5] = fmax(s[5], fabs(di));
-  }
-  for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = s[k];
-  for (int k = 0; k < 5; ++k) cmp[k][threadIdx.x] = c[k];
-  __syncthreads();
-  block_fold<256>([&](int i, int j) {
-    for (int k = 0; k < 5; ++k) {
-      const TwoSum t = two_sum(red[k][i], red[k][j]);
-      red[k][i] = t.s;
-      cmp[k][i] += cmp[k][j] + t.e;
-    }
-    red[5][i] = fmax(red[5][i], red[5][j]);
-  });
-  if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = red[threadIdx.x][0] + (threadIdx.x < 5 ? cmp[threadIdx.x][0] : 0.0);
-}
-
-static int cg_ready(gp_ctx* c, const char* what) {
-  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: no shard data", what);
-  if (!c->xs_raw) return fail(c, GP_ERR_STATE, "%s: the resident CG vectors exist only for free embeddings (raw variances)", what);
-  return GP_OK;
-}
-
-extern "C" int gp_cg_update(gp_ctx* c, int which, double a) {
-  if (!c) return GP_ERR_BAD_ARG;
-  if (which < 0 || which > 5) return fail(c, GP_ERR_BAD_ARG, "gp_cg_update: which must be 0..5");
-  GP_TRY(cg_ready(c, "gp_cg_update"));
-  if ((which == 4 || which == 5) && !c->life.has_grad_latest()) return fail(c, GP_ERR_STATE, "gp_cg_update: no grad_latest yet (gp_phase2(ctx, 1) first)");
-  GP_HIP(c, hipSetDevice(c->device));
-  const long nq = (long)c->N * c->Q;
-  GP_LAUNCH(c, c->stream, cg_update_kernel, dim3(blocks_for(2 * nq)), dim3(256), 0, which, a, nq, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest,
-            c->Xmu, c->Xs);
-  if (which == 0 || which == 1 || which == 5) c->life.direction_rewritten();
-  if (which == 2) c->life.embeddings_changed();
-  return GP_OK;
-}
-
-extern "C" int gp_cg_set_grads(gp_ctx* c) { return gp_cg_update(c, 5, 0.0); }
-
-static int cg_reduce(gp_ctx* c, double* out6) {
-  const long n2 = 2L * c->N * c->Q;
-  const int nb = std::min(blocks_for(n2), 1024);
-  double* part = c->red;
-  GP_LAUNCH(c, c->stream, cg_dots_kernel, dim3(nb), dim3(256), 0, n2, c->dir, c->cg.g_new, c->cg.g_old, c->cg.g_latest, part);
-  std::vector<double> h((size_t)nb * 6);
-  GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  GP_HIP(c, hipStreamSynchronize(c->stream));
-  double comp[5] = {0, 0, 0, 0, 0};
-  for (int k = 0; k < 6; ++k) out6[k] = 0.0;
-  for (int b = 0; b < nb; ++b) {
-    for (int k = 0; k < 5; ++k) { const TwoSum t = two_sum(out6[k], h[(size_t)b * 6 + k]); out6[k] = t.s; comp[k] += t.e; }
-    out6[5] = std::max(out6[5], h[(size_t)b * 6 + 5]);
-  }
-  for (int k = 0; k < 5; ++k) out6[k] += comp[k];
-  return GP_OK;
-}
-
-extern "C" int gp_cg_dots(gp_ctx* c, double* out6) {
-  if (!c || !out6) return GP_ERR_BAD_ARG;
-  GP_TRY(cg_ready(c, "gp_cg_dots"));
-  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_dots: no search direction (gp_cg_set_grads first)");
-  GP_HIP(c, hipSetDevice(c->device));
-  return cg_reduce(c, out6);
-}
-
-// out[0] += sum |g_new| ; out[1] = max |g_new|   (gd_local_MapReduce.py:38-61)
-__global__ void __launch_bounds__(256) cg_abs_kernel(long n2, const double* __restrict__ gnew, double* part) {
-  __shared__ double red[2][256];
-  double s = 0.0, m = 0.0;
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n2; i += (long)gridDim.x * 256L) { const double a = fabs(gnew[i]); s += a; m = fmax(m, a); }
-  red[0][threadIdx.x] = s; red[1][threadIdx.x] = m;
-  __syncthreads();
-  block_fold<256>([&](int i, int j) { red[0][i] += red[0][j]; red[1][i] = fmax(red[1][i], red[1][j]); });
-  if (threadIdx.x < 2) part[blockIdx.x * 2 + threadIdx.x] = red[threadIdx.x][0];
-}
-
-extern "C" int gp_cg_abs(gp_ctx* c, double* out2) {
-  if (!c || !out2) return GP_ERR_BAD_ARG;
-  GP_TRY(cg_ready(c, "gp_cg_abs"));
-  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_abs: no gradient vectors (gp_cg_set_grads first)");
-  GP_HIP(c, hipSetDevice(c->device));
-  const long n2 = 2L * c->N * c->Q;
-  const int nb = std::min(blocks_for(n2), 1024);
-  double* part = c->red;
-  GP_LAUNCH(c, c->stream, cg_abs_kernel, dim3(nb), dim3(256), 0, n2, c->cg.g_new, part);
-  std::vector<double> h((size_t)nb * 2);
-  GP_HIP(c, hipMemcpyAsync(h.data(), part, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-  GP_HIP(c, hipStreamSynchronize(c->stream));
-  out2[0] = 0.0; out2[1] = 0.0;
-  for (int b = 0; b < nb; ++b) { out2[0] += h[(size_t)b * 2]; out2[1] = std::max(out2[1], h[(size_t)b * 2 + 1]); }
-  return GP_OK;
-}
-
-extern "C" int gp_cg_max_d(gp_ctx* c, double alpha, double* out) {
-  if (!c || !out) return GP_ERR_BAD_ARG;
-  GP_TRY(cg_ready(c, "gp_cg_max_d"));
-  if (!c->life.has_direction()) return fail(c, GP_ERR_STATE, "gp_cg_max_d: no search direction (gp_cg_set_grads first)");
-  GP_HIP(c, hipSetDevice(c->device));
-  double o[6];
-  GP_TRY(cg_reduce(c, o));
-  *out = std::fabs(alpha) * o[5];
-  return GP_OK;
-}
-
-// ---- run-time switches (test hooks, same-box A/B) ----------------------------------------------------------------------------
-// Every option by name; each atomic is defined next to the code it switches (gp_common.h declares them).  A flag stores value != 0, a count max(0, value).
-extern "C" int gp_debug_set_option(const char* name, int value) {
-  using namespace gp;
-  static const struct { const char* name; std::atomic<int>* opt; bool is_flag; } options[] = {
-      {"dd_kipsi2", &g_opt_dd_kipsi2, true},     {"refine_E", &g_opt_refine_E, true},       {"p1_i8", &g_opt_p1_i8, true},
-      {"gs_tail", &g_opt_gs_tail, true},         {"i8_guard_strict", &g_opt_i8_guard_strict, true}, {"xtx_tri", &g_opt_xtx_tri, true},
-      {"residual_dd", &g_opt_residual_dd, true}, {"gemm_big", &g_opt_gemm_big, true},       {"trtri_rec", &g_opt_trtri_rec, true},
-      {"gs_i8", &g_opt_gs_i8, true},             {"poison_alloc", &g_opt_poison, true},     {"predict_rows", &g_opt_pred_rows, false},
-      {"infer_rows", &g_opt_inf_rows, false},    {"kmeans_rows", &g_opt_km_rows, false},    {"alloc_fail_after", &g_alloc_fail_after, false}};
-  if (!name) return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: NULL name");
-  // the A/B switch of phase 2's remainder plan (p2_rem.hip: 0 whole tiles only, 1 the rule, 2 wherever it fits) is taken here and is not one of the
-  // listed options: the list in the message below is pinned, name by name, by tests/test_gemm_overlap_rule.py
-  if (!std::strcmp(name, "p2_rem")) { g_opt_p2_rem.store(std::max(0, std::min(value, 2))); return GP_OK; }
-  // likewise the chunk length of gp_nearest_rows (nearest.hip: rows per chunk, 0 = the default), for the same reason
-  if (!std::strcmp(name, "nearest_rows")) { g_opt_nn_rows.store(std::max(0, value)); return GP_OK; }
-  // and the distinct patterns per chunk of gp_infer_objective_rows / gp_infer_latent_rows (infer.hip: P_cap, 0 = the default)
-  if (!std::strcmp(name, "infer_patterns")) { g_opt_inf_patterns.store(std::max(0, value)); return GP_OK; }
-  // and the rows per chunk of gp_paths_eval (paths.hip, 0 = the default)
-  if (!std::strcmp(name, "paths_rows")) { g_opt_paths_rows.store(std::max(0, value)); return GP_OK; }
-  // and the curves per chunk of gp_curve_energy (curve.hip, 0 = the default)
-  if (!std::strcmp(name, "curve_curves")) { g_opt_curve_curves.store(std::max(0, value)); return GP_OK; }
-  // and the rows per chunk of either side of gp_knn_rows (knn.hip: as given, with shorter tiles and slices; 0 = the defaults)
-  if (!std::strcmp(name, "knn_rows")) { g_opt_knn_rows.store(std::max(0, value)); return GP_OK; }
-  // and the host rows per upload chunk of gp_select_begin (select.hip, 0 = the default)
-  if (!std::strcmp(name, "select_rows")) { g_opt_sel_rows.store(std::max(0, value)); return GP_OK; }
-  std::string known;
-  for (const auto& o : options) {
-    if (!std::strcmp(name, o.name)) { o.opt->store(o.is_flag ? (value ? 1 : 0) : std::max(0, value)); return GP_OK; }
-    known += (known.empty() ? "" : ", ") + std::string(o.name);
-  }
-  return fail(nullptr, GP_ERR_BAD_ARG, "gp_debug_set_option: unknown option '%s' (%s)", name, known.c_str());
 }

@@ -29,6 +29,12 @@ inline bool env_is(const char* name, const char* value) { const char* e = getenv
 
 inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 inline int blocks_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 8192)); }   // grid of a grid-stride kernel over n elements
+// nearest.hip, knn.hip: `tiles` tiles of training rows in slices, for a grid of (blocks, slices) workgroups that aims at `target` of them; no empty slice
+struct SlicePlan { int tps, slices; };     // tiles per slice, slices
+inline SlicePlan slice_plan(long tiles, long blocks, long target) {
+  const long want = std::min(tiles, std::max<long>(1, (target + blocks - 1) / blocks)), tps = (tiles + want - 1) / want;
+  return {(int)tps, (int)((tiles + tps - 1) / tps)};
+}
 // latent width of the packed per-point records of psi1_kernel (Q <= 16: Q rounded up to 2) / psi1_wide_kernel (24, 32, 52, 64); 0: none
 inline int psi1_qp(int Q) { return Q <= 16 ? (Q + 1) / 2 * 2 : Q <= 24 ? 24 : Q <= 32 ? 32 : Q <= 52 ? 52 : Q <= 64 ? 64 : 0; }
 
@@ -204,7 +210,7 @@ struct P2State {
   int poison(gp_ctx* c);
 };
 
-// resident CG vectors (the gp_cg_* functions, api.hip): grad_latest/new/old (2,N,Q) each
+// resident CG vectors (the gp_cg_* functions, cg.hip): grad_latest/new/old (2,N,Q) each
 struct CgState {
   DevBuf<double> g_latest;    // written by gp_phase2 with embedding gradients
   DevBuf<double> g_new;
@@ -397,6 +403,8 @@ int run_select_candidate(gp_ctx* c, double* d, int64_t* row, double* x, double* 
 int run_select_apply(gp_ctx* c, const double* x_p, const double* l_p, double d_p, int64_t own_row, double* trace);
 void select_info(const gp_ctx* c, long* n, int* K, int* j);
 const double* select_debug(const gp_ctx* c, bool want_L, long* cnt);   // gp_debug_peek: the factor's written columns or d, NULL / 0 without a plan
+// cg.hip: the one rule of gp_cg_* and gp_lbfgs_* (`who`): shard data, then free embeddings; `what`: the message's subject and verb, "resident CG vectors exist"
+int resident_ready(gp_ctx* c, const char* who, const char* what);
 // lbfgs.hip
 const double* lbfgs_debug(const gp_ctx* c, const char* name, long* cnt);     // gp_debug_peek: "lbfgs_s<k>", "lbfgs_y<k>", "lbfgs_g"; NULL / 0 for a vector that holds nothing
 // pca.hip
@@ -429,7 +437,8 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
                           double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0, bool factor_only = false);
 int potrf_trinv128_tiles(gp_ctx* c, hipStream_t st, int tiles, double* A /*[tiles][128][128] in: SPD, out: L*/, double* Linv, double* fail /*[tiles], zero*/,
                          double* logdet2 /*[tiles], zero*/);
-// the options of gp_debug_set_option (api.hip holds the table and the ones without a home file), each next to the code it switches
+extern bool g_force_staging;                                  // debug.hip (gp_debug_force_staging): gp_buffer_combine takes its cross-device path on one device
+// the options of gp_debug_set_option (debug.hip holds the table), each next to the code it switches; g_opt_poison and g_alloc_fail_after: devbuf.h
 extern std::atomic<int> g_opt_dd_kipsi2, g_opt_refine_E, g_opt_xtx_tri, g_opt_residual_dd, g_opt_trtri_rec, g_opt_gemm_big, g_opt_gs_tail;   // linalg.hip
 extern std::atomic<int> g_opt_p1_i8, g_opt_i8_guard_strict;   // p1i8.hip
 extern std::atomic<int> g_opt_gs_i8;                          // gsi8.hip

@@ -274,8 +274,7 @@ int run_knn(gp_ctx* c, long n_train, const double* X_train, long n, const double
         t = p.in;
       }
       const long tiles = (rows + tr - 1) / tr;
-      const long want = opt > 0 ? tiles : std::min(tiles, std::max<long>(1, (KNN_BLOCKS + qblocks - 1) / qblocks));
-      const int tps = (int)((tiles + want - 1) / want), slices = (int)((tiles + tps - 1) / tps);      // no empty slice
+      const auto [tps, slices] = opt > 0 ? SlicePlan{1, (int)tiles} : slice_plan(tiles, qblocks, KNN_BLOCKS);      // "knn_rows": a slice per tile
       if ((size_t)slices * cnt * k > part) return fail(c, GP_ERR_UNSUPPORTED, "gp_knn_rows: %d slices of %ld queries exceed the plan's lists", slices, cnt);
       const KnnLaunch a{qblocks, (unsigned)slices, x, cnt, t, rows, (int)Q, tr, tps, weight ? p.w.get() : nullptr, skip ? p.skip.get() : nullptr,
                         self ? (long long)n0 : -1LL, (long long)m0, k, p.pd, p.pi};

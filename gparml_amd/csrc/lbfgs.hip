@@ -177,14 +177,12 @@ const double* lbfgs_debug(const gp_ctx* c, const char* name, long* cnt) {
   return p.v[at];
 }
 
-// the rule of the gp_cg_* functions (api.hip, cg_ready) and the plan's presence; *pp = the plan
+// the rule of the resident vectors (cg.hip; gp_lbfgs_begin asks no more), then the plan's presence; *pp = the plan
+static int lb_vectors_ready(gp_ctx* c, const char* who) { return resident_ready(c, who, "resident L-BFGS history exists"); }
 static int lb_ready(gp_ctx* c, const char* who, LbfgsPlan** pp) {
-  if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "%s: no shard data", who);
-  if (!c->xs_raw) return fail(c, GP_ERR_STATE, "%s: the resident L-BFGS history exists only for free embeddings (raw variances)", who);
-  if (pp) {
-    if (!c->lbfgs) return fail(c, GP_ERR_STATE, "%s before gp_lbfgs_begin (or after gp_lbfgs_end)", who);
-    *pp = c->lbfgs.get();
-  }
+  GP_TRY_RC(lb_vectors_ready(c, who));
+  if (!c->lbfgs) return fail(c, GP_ERR_STATE, "%s before gp_lbfgs_begin (or after gp_lbfgs_end)", who);
+  *pp = c->lbfgs.get();
   return GP_OK;
 }
 
@@ -195,7 +193,7 @@ using namespace gp;
 extern "C" int gp_lbfgs_begin(gp_ctx* c, int m) {
   if (!c) return GP_ERR_BAD_ARG;
   if (m < 1 || m > LB_MMAX) return fail(c, GP_ERR_BAD_ARG, "gp_lbfgs_begin: m must be 1 .. %d, got %d", LB_MMAX, m);
-  GP_TRY_RC(lb_ready(c, "gp_lbfgs_begin", nullptr));
+  GP_TRY_RC(lb_vectors_ready(c, "gp_lbfgs_begin"));
   GP_HIP(c, hipSetDevice(c->device));
   const long n2 = 2L * c->N * c->Q;
   if (!c->lbfgs || c->lbfgs->m != m || c->lbfgs->n2 != n2) {

@@ -5,7 +5,7 @@
 //   Kmm-dependent parts of grad_Z / grad_alpha / grad_sf2 (:146-160, 207-240, 247-254, 286-333).
 // All matrices are padded to multiples of 128 with an identity block, which leaves log-determinants, inverses
 // and every trace unchanged.
-#include "pred_chunk.h"
+#include "gp_common.h"
 #include "potrf128.h"
 #include "gemm32.h"
 #include "lane_reduce.h"
@@ -13,7 +13,6 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 
 namespace gp {
 
@@ -1041,77 +1040,4 @@ extern "C" int gp_debug_dd_product(int device, int product, int form, const int*
   const int rc = gp::dd_product_body(&tmp, device, product, form, dims, beta, jitA, A, B, Csub, Keep, Psi2, out, form_ran);
   if (rc != GP_OK) gp::g_create_error = tmp.err;
   return rc;
-}
-
-// raw copy of an internal buffer of the global step (developer tool, tests/devtools/dev_tail_diff.py; not part of the public header)
-extern "C" int gp_debug_peek(gp_ctx* c, const char* name, double* out, long n) {
-  using namespace gp;
-  if (!c || !name || !out) return GP_ERR_BAD_ARG;
-  GP_HIP(c, hipSetDevice(c->device));
-  const long mm = (long)c->Mp * c->Mp, md = (long)c->Mp * c->Dp;
-  const double* src = nullptr; long cnt = 0;
-  const void* src_any = nullptr; bool ints = false;      // a buffer that may hold ints (infer_debug_scg)
-  if (!std::strcmp(name, "Linv")) { src = c->gstep.Linv; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "Inv")) { src = c->gstep.Inv; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "E")) { src = c->gstep.E; cnt = md; }
-  else if (!std::strcmp(name, "PsiE")) { src = c->gstep.PsiE; cnt = md; }
-  else if (!std::strcmp(name, "T1")) { src = c->gstep.T1; cnt = mm; }
-  else if (!std::strcmp(name, "T2")) { src = c->gstep.T2; cnt = mm; }
-  else if (!std::strcmp(name, "dFdK")) { src = c->gstep.dFdK; cnt = mm; }
-  else if (!std::strcmp(name, "Bbar")) { src = c->gstep.Bbar; cnt = mm; }
-  else if (!std::strcmp(name, "Abar")) { src = c->gstep.Abar; cnt = md; }
-  else if (!std::strcmp(name, "Bm")) { src = c->gstep.Bm; cnt = (long)c->LDK * c->Mp; }
-  else if (!std::strcmp(name, "gK")) { src = c->gstep.gK; cnt = (long)c->M * c->Q + c->Q; }
-  else if (!std::strcmp(name, "gs")) { src = c->gstep.gs; cnt = (long)c->gstep.gs.size(); }
-  // r06 (poison probe, tests/devtools/dev_poison_probe.py): the padded device images of the evaluation's other buffers
-  else if (!std::strcmp(name, "stats")) { src = c->stats; cnt = mm + md + SC_COUNT; }
-  else if (!std::strcmp(name, "Kaug")) { src = c->Kaug; cnt = (long)c->Np * c->LDK; }
-  else if (!std::strcmp(name, "Kmm")) { src = c->gstep.Kmm; cnt = 2 * mm; }
-  else if (!std::strcmp(name, "KmmKeep")) { src = c->gstep.KmmKeep; cnt = mm; }
-  else if (!std::strcmp(name, "Z")) { src = c->Z; cnt = (long)c->Mp * c->Q; }
-  else if (!std::strcmp(name, "Zaug")) { src = c->Zaug; cnt = (long)c->Mp * c->CZp; }
-  else if (!std::strcmp(name, "mu")) { src = c->mu; cnt = (long)c->Np * c->Q; }
-  else if (!std::strcmp(name, "S")) { src = c->S; cnt = (long)c->Np * c->Q; }
-  else if (!std::strcmp(name, "Xa")) { src = c->Xa; cnt = (long)c->Np * c->CXp; }
-  else if (!std::strcmp(name, "grads")) { src = c->grads; cnt = (long)c->M * c->Q + c->Q; }
-  else if (!std::strcmp(name, "Rpart")) { src = c->p2.Rpart; cnt = (long)c->p2.Rpart.size(); }
-  else if (!std::strcmp(name, "LE") || !std::strcmp(name, "LEA")) src = b_debug_table(c, name[2] == 'A', &cnt);
-  else if (!std::strcmp(name, "pred_LEA")) src = pred_debug_lea(c, &cnt);
-  else if (!std::strcmp(name, "infer_LEA")) src = infer_debug_lea(c, &cnt);
-  // the per-row SCG of gp_infer_latent as it lies on the device: tests/test_gpu_infer_scg.py
-  else if (!std::strncmp(name, "infer_", 6)) {
-    src_any = infer_debug_scg(c, name, &cnt, &ints);
-    if (!src_any && cnt < 0) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
-    if (!src_any) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' before gp_infer_latent has built the optimiser's state", name);
-  }
-  else if (!std::strcmp(name, "select_L") || !std::strcmp(name, "select_d")) {
-    src = select_debug(c, name[7] == 'L', &cnt);
-    if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_select_begin .. gp_select_end", name);
-  }
-  else if (!std::strcmp(name, "dir")) { src = c->dir; cnt = 2L * c->N * c->Q; }
-  // the resident CG vectors and the base embeddings as stored (Xs raw when uploaded raw): tests/test_gpu_resident_vectors.py
-  else if (!std::strcmp(name, "cg_g_new") || !std::strcmp(name, "cg_g_old") || !std::strcmp(name, "cg_g_latest")) {
-    if (!c->life.has_data() || !c->xs_raw)
-      return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' exists only with shard data and free embeddings (raw variances)", name);
-    src = name[5] == 'n' ? c->cg.g_new : name[5] == 'o' ? c->cg.g_old : c->cg.g_latest; cnt = 2L * c->N * c->Q;
-  }
-  else if (!std::strcmp(name, "Xmu") || !std::strcmp(name, "Xs")) {
-    if (!c->life.has_data()) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' before gp_upload_shard", name);
-    src = name[1] == 'm' ? c->Xmu : c->Xs; cnt = (long)c->N * c->Q;
-  }
-  else if (!std::strncmp(name, "lbfgs_", 6)) {
-    src = lbfgs_debug(c, name, &cnt);
-    if (!src) return fail(c, GP_ERR_STATE, "gp_debug_peek: '%s' outside gp_lbfgs_begin .. gp_lbfgs_end, or not a vector that holds anything", name);
-  }
-  else return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: unknown buffer '%s'", name);
-  if (n < cnt) return fail(c, GP_ERR_BAD_ARG, "gp_debug_peek: %ld doubles needed", cnt);
-  GP_HIP(c, hipStreamSynchronize(c->stream));
-  if (ints) {                                  // widened on the host after the copy
-    std::vector<int> h((size_t)cnt);
-    GP_HIP(c, hipMemcpy(h.data(), src_any, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost));
-    std::copy(h.begin(), h.end(), out);
-    return (int)GP_OK;
-  }
-  GP_HIP(c, hipMemcpy(out, src_any ? src_any : src, cnt * 8, hipMemcpyDeviceToHost));
-  return (int)GP_OK;
 }

@@ -246,8 +246,7 @@ int run_nearest(gp_ctx* c, long n_train, const double* Y_train, long n, const do
         ld = D;
       }
       const long tiles = (rows + NN_ROWS - 1) / NN_ROWS;
-      const long want = std::min(tiles, std::max<long>(1, (NN_BLOCKS + yb - 1) / yb));
-      const int tps = (int)((tiles + want - 1) / want), slices = (int)((tiles + tps - 1) / tps);      // no empty slice
+      const auto [tps, slices] = slice_plan(tiles, yb, NN_BLOCKS);
       if (observed)
         GP_LAUNCH(c, st, nn_search_kernel<true>, dim3((unsigned)yb, (unsigned)slices), dim3(256), 0, t, ld, rows, tps, p.y, p.cols, nc, ncp, ry, p.pd, p.pi);
       else

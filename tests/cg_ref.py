@@ -1,4 +1,4 @@
-"""Host image of the resident SCG / GD vectors (csrc/api.hip: gp_cg_update, gp_cg_dots, gp_cg_abs, gp_cg_max_d; the trial point of csrc/psi.hip).
+"""Host image of the resident SCG / GD vectors (csrc/cg.hip: gp_cg_update, gp_cg_dots, gp_cg_abs, gp_cg_max_d; the trial point of csrc/psi.hip).
 
 ``NumpyOps``   the reference's helper names (scg_adapted_local_MapReduce.py:29-243, gd_local_MapReduce.py:14-105) on one in-memory vector: what an
                optimiser is handed where no device is involved.  ``FsumOps`` is the same with every reduction through math.fsum (another summation

@@ -41,15 +41,23 @@ def test_different_leading_dimensions_fall_back_to_address_ranges():
 
 
 OPTIONS = ["dd_kipsi2", "refine_E", "p1_i8", "gs_tail", "i8_guard_strict", "xtx_tri", "residual_dd", "gemm_big", "trtri_rec", "gs_i8", "poison_alloc",
-           "predict_rows", "infer_rows", "kmeans_rows", "alloc_fail_after"]
+           "predict_rows", "infer_rows", "kmeans_rows", "alloc_fail_after", "p2_rem", "nearest_rows", "infer_patterns", "paths_rows", "curve_curves",
+           "knn_rows", "select_rows"]
+# the options that hold a count (a chunk length, or the allocations until the injected failure): 0 is the default of each
+COUNTS = ["predict_rows", "infer_rows", "kmeans_rows", "nearest_rows", "infer_patterns", "paths_rows", "curve_curves", "knn_rows", "select_rows",
+          "alloc_fail_after"]
 
 
 def test_an_unknown_option_is_refused_and_the_message_names_every_option():
-    """gp_debug_set_option's table (csrc/api.hip) is the one list of run-time switches: the message for a name outside it is generated from it.  No real
-    option is set here: there is no getter to restore one."""
+    """gp_debug_set_option's table (csrc/debug.hip) is the one list of run-time switches: the message for a name outside it is generated from it.  No
+    flag and no range is set here: there is no getter to restore one.  The counts are set to 0, their default."""
     lib = _lib.load()
     assert lib.gp_debug_set_option(b"no_such_option", 1) == _lib.GP_ERR_BAD_ARG
     msg = lib.gp_last_error(None).decode()
     assert "no_such_option" in msg
     listed = msg[msg.rindex("(") + 1:msg.rindex(")")].split(", ")
     assert sorted(listed) == sorted(OPTIONS), msg
+    assert set(COUNTS) <= set(OPTIONS)
+    for name in COUNTS:
+        assert lib.gp_debug_set_option(name.encode(), 0) == _lib.GP_OK, name
+    assert lib.gp_debug_set_option(None, 1) == _lib.GP_ERR_BAD_ARG
