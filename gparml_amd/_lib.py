@@ -104,6 +104,13 @@ SIGNATURES = {
     'gp_lbfgs_dots': (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     'gp_lbfgs_direction': (ctypes.c_int, [_vp, _dp]),
     'gp_lbfgs_end': (ctypes.c_int, [_vp]),
+    'gp_svi_begin': (ctypes.c_int, [_vp]),
+    'gp_svi_set': (ctypes.c_int, [_vp, _dp, _dp]),
+    'gp_svi_get': (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    'gp_svi_natural_step': (ctypes.c_int, [_vp, ctypes.c_double]),
+    'gp_svi_step': (ctypes.c_int, [_vp, ctypes.c_int]),
+    'gp_svi_publish': (ctypes.c_int, [_vp]),
+    'gp_svi_end': (ctypes.c_int, [_vp]),
     'gp_debug_gemm': (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_double, _dp, _dp, ctypes.c_double, _dp]),
     'gp_debug_set_option': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     'gp_debug_potrf_inverse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),

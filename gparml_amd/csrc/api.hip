@@ -558,6 +558,7 @@ extern "C" int gp_global_step_jitter(gp_ctx* c, int jitter_mask) {
   if (jitter_mask < 0 || jitter_mask > 3) return fail(c, GP_ERR_BAD_ARG, "gp_global_step_jitter: mask must be 0..3");
   GP_HIP(c, hipSetDevice(c->device));
   c->gstep.jitter_mask = jitter_mask;
+  c->gstep.svi_step = false;
   c->life.step_started();
   GP_EV(c, 3);
   const int rc_gs = run_global_step(c);
@@ -575,6 +576,7 @@ extern "C" int gp_global_step(gp_ctx* c) { return gp_global_step_jitter(c, 0); }
 // known to be over: gp_finish, gp_global_status, gp_download of a global-step array.
 static int resolve_i8_check(gp_ctx* c) {
   if (!c->i8.check_pending || !c->life.step_done()) return GP_OK;
+  if (c->gstep.svi_step) return GP_OK;            // gp_svi_step wrote no P: the check stays pending for the next collapsed step
   if (check_global(c) != GP_OK) return GP_OK;     // the caller reports that status itself
   return p1i8_check_finish(c);
 }

@@ -113,6 +113,8 @@ struct LbfgsPlan;  // lbfgs.hip
 struct KnnPlan;    // knn.hip
 struct LooPlan;    // loo.hip
 struct CondPlan;   // condition.hip
+struct SviPlan;    // svi.hip
+struct SviPlanDelete { void operator()(SviPlan* p) const; };
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
 struct BPlanDelete { void operator()(BPlan* p) const; };
@@ -192,6 +194,7 @@ struct GsState {
   std::string gs_msg;
   int jitter_mask = 0;        // bit 0: Kmm, bit 1: Kmm + beta*Psi2 get 1e-7 * I in this global step (partial_terms.py:452-456)
   int retry_mask = 0;         // what a GP_RETRY_JITTER asks the caller to pass to gp_global_step_jitter
+  bool svi_step = false;      // the step whose outcome is pending is a gp_svi_step (svi.hip): the second failure flag is Lambda_v's
   int alloc(gp_ctx* c);
   int poison(gp_ctx* c);
 };
@@ -301,6 +304,7 @@ struct gp_ctx {
   std::unique_ptr<gp::KnnPlan, gp::KnnPlanDelete> knn;        // gp_knn_rows' buffers (knn.hip)
   std::unique_ptr<gp::LooPlan, gp::LooPlanDelete> loo;        // gp_loo_score's buffers (loo.hip)
   std::unique_ptr<gp::CondPlan, gp::CondPlanDelete> cond;     // gp_condition_set's rows [V | T] and gp_condition_predict's buffers (condition.hip)
+  std::unique_ptr<gp::SviPlan, gp::SviPlanDelete> svi;        // gp_svi_begin .. gp_svi_end: q(v) in natural parameters and the whitened statistics (svi.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -422,6 +426,14 @@ int compat_build(gp_ctx* c, int which, DevBuf<double>& out);
 void comm_free(gp_ctx* c);
 // linalg.hip
 int run_global_step(gp_ctx* c);
+// pieces of the global step that gp_svi_step runs on its own matrices: K_mm (into Kmm, and GsState::KmmKeep) with A = K_mm + beta Psi2, the trace jobs'
+// partial sums part [jobs][DOT_BLOCKS], and the K_mm parts of grad_Z / grad_alpha from GsState's dFdK and Bbar into gK
+struct DotJob { const double* x; const double* y; long ld; int rows, cols; int slot; };    // sum over the rows x cols block of x o y -> out[slot]
+struct DotJobs { DotJob j[8]; int n; };
+constexpr int DOT_BLOCKS = 64;
+int launch_build_kmm(gp_ctx* c, hipStream_t st, double* Kmm, double* A, double jitK, double jitA, double* gs_zero /*[GS_HOST] zeroed*/, double* Acopy);
+int launch_dots(gp_ctx* c, hipStream_t st, const DotJobs& jobs, double* part);
+int launch_kmm_grads(gp_ctx* c, hipStream_t st);
 // gsi8.hip: the global step's two double-double-grade products on the int8 matrix core (M >= 1024)
 bool gs_i8_wanted(const gp_ctx* c);
 int run_gs_i8_product(gp_ctx* c, hipStream_t st, const double* A, long lda, int nA, const double* B, long ldb, int nB, int K, double* out, long ldo,
@@ -434,7 +446,7 @@ int check_global_from(gp_ctx* c, const double* h);
 // gp_debug_potrf_inverse memsets its own buffer.  A caller that hands in a reused scratch buffer must clear it first.
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A /*in: SPD, out: L*/, double* Linv, double* Inv,
                           double* Twork /*batch * Mp * Mp / 2 doubles*/, double* logdet2 /*device, [batch]*/, double* fail_flag /*device, [batch]*/,
-                          double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0, bool factor_only = false);
+                          double* splitk_ws /*may be NULL*/, size_t splitk_cap = 0, bool factor_only = false, bool no_inverse = false /*L and L^-1 only*/);
 int potrf_trinv128_tiles(gp_ctx* c, hipStream_t st, int tiles, double* A /*[tiles][128][128] in: SPD, out: L*/, double* Linv, double* fail /*[tiles], zero*/,
                          double* logdet2 /*[tiles], zero*/);
 extern bool g_force_staging;                                  // debug.hip (gp_debug_force_staging): gp_buffer_combine takes its cross-device path on one device

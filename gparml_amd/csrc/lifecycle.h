@@ -26,17 +26,20 @@ struct Lifecycle {
   void origin_moved() { prep_fixa_ = false; }           // gp_set_globals chose a new origin: the centred means are stale
   void globals_set() { has_globals_ = true; start_over(); }
   void prep_ran(bool fixa) { prep_fixa_ = fixa; }       // run_prep_and_generate: the trial point is built (fixa: in the form that outlives the globals)
-  void phase1_ran() { progress_ = STATS; psi1_current_ = true; packed_ = false; model_ = false; }
+  void phase1_ran() { ++inputs_; progress_ = STATS; psi1_current_ = true; packed_ = false; model_ = false; }
   // gp_set_local_statistics.  The lift: statistics from outside admit the global step without a phase 1 -- and, as found, gp_phase2 after it
   // on whatever Psi1 the context holds (psi1_is_current() says which; no entry point asks)
-  void stats_injected() { lift(); packed_ = false; model_ = false; }
-  void stats_combined() { lift(); model_ = false; }     // gp_buffer_combine(statistics).  As found: the packed copy stays "current"
-  void stats_scaled() { packed_ = false; model_ = false; }        // gp_scale_buffer(statistics): the padded buffer is the source of truth
-  void stats_unpacked() { model_ = false; }             // gp_stats_unpack.  As found: raised before the refusal of an unpack without a pack
+  void stats_injected() { ++inputs_; lift(); packed_ = false; model_ = false; }
+  void stats_combined() { ++inputs_; lift(); model_ = false; }     // gp_buffer_combine(statistics).  As found: the packed copy stays "current"
+  void stats_scaled() { ++inputs_; packed_ = false; model_ = false; }        // gp_scale_buffer(statistics): the padded buffer is the source of truth
+  void stats_unpacked() { ++inputs_; model_ = false; }             // gp_stats_unpack.  As found: raised before the refusal of an unpack without a pack
   void stats_packed() { packed_ = true; }
   void step_started() { model_ = false; }
   void step_enqueued() { progress_ = STEP; model_ = true; outcome_pending_ = true; ++steps_; }     // its outcome is still checked (check_global)
   void step_read_back() { outcome_pending_ = false; }
+  // gp_svi_step stands where the global step stands: gp_phase2 and gp_finish follow it, its outcome is checked the same way -- but Inv / Linv / E do
+  // not describe its q(u), so the model stays down until gp_svi_publish (stats_injected) and an ordinary global step
+  void svi_step_enqueued() { progress_ = STEP; model_ = false; outcome_pending_ = true; }
   void phase2_mode(bool embedding_grads) { embedding_mode_ = embedding_grads; }          // the feature layout of the trial point follows it
   void grad_latest_written() { grad_latest_ = true; }   // the resident CG vector; never cleared (as found: it outlives an upload)
   void phase2_ran() { progress_ = PHASE2; }
@@ -58,6 +61,9 @@ struct Lifecycle {
   // Which global step the model is of: a plan built from Inv / Linv / E (gp_paths_set) keeps the number and is stale once it differs -- model_
   // rises again only through step_enqueued, so "model_current() and the same number" is "nothing has happened to the model since"
   long model_serial() const { return steps_; }
+  // Counts everything that changes the statistics buffer or the globals through an entry point: what gp_svi_* derives from both (the whitened
+  // statistics) is kept with the number and is stale once it differs
+  long inputs_serial() const { return inputs_; }
   bool grad_latest_ready() const { return phase2_done() && embedding_mode_; }           // GP_ARR_GRAD_LATEST, rebuilt from this evaluation's gradients
   bool has_grad_latest() const { return grad_latest_; }                                 // gp_cg_update(4, 5): the resident copy
   bool prep_is_current(bool fixa) const { return fixa && prep_fixa_; }
@@ -71,7 +77,7 @@ struct Lifecycle {
   // Data, embeddings, direction or globals changed: the statistics, Psi1 and the step are stale.  progress_ carries two meanings that cannot be
   // parted without changing an outcome -- gp_phase2 and the compat downloads are admitted on the level alone, so after injected statistics they
   // run on a Psi1 the level says nothing about.  psi1_current_ is the second meaning on its own, kept for the table and the later change.
-  void start_over() { progress_ = NONE; psi1_current_ = false; model_ = false; }
+  void start_over() { ++inputs_; progress_ = NONE; psi1_current_ = false; model_ = false; }
   void lift() { if (progress_ < STATS) progress_ = STATS; }
 
   Progress progress_ = NONE;
@@ -85,6 +91,7 @@ struct Lifecycle {
   bool outcome_pending_ = false;  // a global step was enqueued and its scalars / failure flags have not been read back yet
   bool grad_latest_ = false;
   long steps_ = 0;                // global steps enqueued so far (model_serial)
+  long inputs_ = 0;               // changes of the statistics or the globals so far (inputs_serial)
 };
 
 }  // namespace gp

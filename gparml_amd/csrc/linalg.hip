@@ -67,7 +67,7 @@ int potrf_trinv128_tiles(gp_ctx* c, hipStream_t st, int tiles, double* A, double
 
 // A: [batch][Mp][Mp] SPD in, lower Cholesky factor out (upper zeroed); Linv: L^-1; Inv: A^-1; Twork: batch * Mp * Mp / 2 doubles
 int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* A, double* Linv, double* Inv, double* Twork,
-                          double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap, bool factor_only) {
+                          double* logdet2, double* fail_flag, double* splitk_ws, size_t splitk_cap, bool factor_only, bool no_inverse) {
   const int nt = Mp / NB;
   const long ld = Mp, bs = (long)Mp * Mp;
   // a per-device attribute: set on every call (cheap) rather than once per process -- contexts may live on several GPUs
@@ -132,6 +132,7 @@ int potrf_inverse_batched(gp_ctx* c, hipStream_t st, int Mp, int batch, double* 
                             gemm_of({Linv + ((long)i * NB) * ld + (long)i * NB, ld, bs}, {Twork, Mp, (long)NB * Mp}, {Linv + ((long)i * NB) * ld, ld, bs}, NB, -1.0)));
     }
   }
+  if (no_inverse) return GP_OK;
   // A^-1 = X^T X: A(i,k) = X[k][i]: stored [k][i] -> FREE_CONTIG; B(k,j) = X[k][j] -> FREE_CONTIG.  xtx_tri: lower tiles, klow, mirror
   const int xt = g_opt_xtx_tri.load() ? 1 : 0;
   const GemmPlan pl = gemm_plan((long)(Mp / TILE) * (Mp / TILE) * batch, Mp, splitk_ws ? splitk_cap : 0, g_opt_gemm_big.load(), Mp);
@@ -332,9 +333,7 @@ __global__ void __launch_bounds__(256) ddacc_residual_kernel(const double* __res
 }
 
 // sum over the M x M (or M x D) block of x o y; one block per pair, results into out[slot]
-struct DotJob { const double* x; const double* y; long ld; int rows, cols; int slot; };
-struct DotJobs { DotJob j[8]; int n; };
-constexpr int DOT_BLOCKS = 64;
+// (DotJob, DotJobs, DOT_BLOCKS: gp_common.h -- svi.hip describes its traces the same way)
 // virtual block (vbx of DOT_BLOCKS, job vby) by the calling 256-thread workgroup; red: 256 doubles of LDS
 __device__ __forceinline__ void dots_block(const DotJobs& jobs, double* part, int vbx, int vby, double* red) {
   // per-block partial sums part[job][block]; scalars_kernel adds them in a fixed order, so the bound is
@@ -725,7 +724,11 @@ int check_global_from(gp_ctx* c, const double* h) {
     if (singular) {
       // an exactly zero pivot: the reference fails in linalg.inv before any jitter applies (partial_terms.py:60, 95)
       c->gstep.gs_status = GP_ERR_NOT_PD;
-      c->gstep.gs_msg = std::string(h[GS_FLAGS] == 2.0 ? "Kmm" : "Kmm + beta*Psi2") + " is singular (numpy.linalg.inv: Singular matrix)";
+      c->gstep.gs_msg = std::string(h[GS_FLAGS] == 2.0 ? "Kmm" : c->gstep.svi_step ? "Lambda_v" : "Kmm + beta*Psi2") + " is singular (numpy.linalg.inv: Singular matrix)";
+    } else if (c->gstep.svi_step && (failed & 2)) {
+      // gp_svi_step: the second flag is Lambda_v's, the caller's state -- no jitter is added to it
+      c->gstep.gs_status = GP_ERR_NOT_PD;
+      c->gstep.gs_msg = "Lambda_v is not positive definite (gp_svi_set / gp_svi_natural_step left it so)";
     } else if (failed & ~c->gstep.jitter_mask) {
       // first failure of this matrix: the reference continues with 1e-7 * I added (partial_terms.py:452-456)
       c->gstep.retry_mask = c->gstep.jitter_mask | failed;
@@ -800,6 +803,29 @@ static int form_residual(gp_ctx* c, hipStream_t st, int form, const DdProduct& p
   return GP_OK;
 }
 
+// Kmm parts of grad_Z / grad_alpha from dFdK, Bbar, KmmKeep and Psi2 as they stand; alpha partials per row go through T2 (free again)
+int launch_kmm_grads(gp_ctx* c, hipStream_t st) {
+  const int Mp = c->Mp, M = c->M, Q = c->Q;
+  const GsView v = gs_view(c);
+  static const bool kmm_lds = env_flag("GPARML_KMM_LDS", true);
+  if (kmm_lds && M <= 2048)
+    GP_LAUNCH(c, st, kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z,
+              v.Zt, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
+  else
+    GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
+  GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, v.T2, M, Q, v.gK + (long)M * Q);
+  return GP_OK;
+}
+int launch_build_kmm(gp_ctx* c, hipStream_t st, double* Kmm, double* A, double jitK, double jitA, double* gs_zero, double* Acopy) {
+  GP_LAUNCH(c, st, build_kmm_kernel, dim3(c->Mp / 64, c->Mp / 16), dim3(256), 0, c->Z, c->alpha, c->sf2, c->beta, c->stats.get(), c->M, c->Mp, c->Q, Kmm, A,
+            c->gstep.KmmKeep.get(), jitK, jitA, gs_zero, Acopy);
+  return GP_OK;
+}
+int launch_dots(gp_ctx* c, hipStream_t st, const DotJobs& jobs, double* part) {
+  GP_LAUNCH(c, st, dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, jobs, part);
+  return GP_OK;
+}
+
 int run_global_step(gp_ctx* c) {
   hipStream_t st = c->stream;
   const int Mp = c->Mp, Dp = c->Dp, M = c->M, D = c->D, Q = c->Q;
@@ -813,8 +839,7 @@ int run_global_step(gp_ctx* c) {
   const bool gi8 = gs_i8_wanted(c);            // gsi8.hip: both double-double products on the int8 matrix core (M >= 1024)
   const int res_form = residual_form(gi8, Mp, Dp);
   const bool res_dd = g_opt_refine_E.load() && res_form != DD_FORM_ROW;     // the forms that read A's copy
-  GP_LAUNCH(c, st, build_kmm_kernel, dim3(Mp / 64, Mp / 16), dim3(256), 0, v.Z, v.alpha, c->sf2, c->beta, v.Psi2, M, Mp, Q, c->gstep.Kmm, c->gstep.Kmm + mm,
-            v.KmmKeep, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, jitA, v.gs, res_dd ? v.T2 : (double*)nullptr);
+  GP_TRY_RC(launch_build_kmm(c, st, c->gstep.Kmm, c->gstep.Kmm + mm, (c->gstep.jitter_mask & 1) ? 1e-7 : 0.0, jitA, v.gs, res_dd ? v.T2 : (double*)nullptr));
   // one-panel problems (M, D <= 128): the panel kernel, then seven launches of tail_stage_kernel instead of fifteen kernels
   if (Mp == NB && Dp == NB && g_opt_gs_tail.load()) {
     GP_HIP(c, hipFuncSetAttribute((const void*)potrf_trinv128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, POTRF_LDS_DOUBLES * 8));
@@ -863,16 +888,9 @@ int run_global_step(gp_ctx* c) {
   GP_LAUNCH(c, st, assemble_kernel, dim3(1024), dim3(256), 0, v.Ki, v.P, v.T1, v.dFdK, v.E, c->beta, (double)D, Mp, Dp, v.Bbar, v.dFdK, v.Abar, v.Bm);
   double* dpart = v.gs + GS_DOTS;   // [jobs][DOT_BLOCKS]
   // the traces / scalars and the Kmm parts of the gradients both start from the assembled partials and do not touch each other's outputs
-  GP_LAUNCH(c, st, dots_kernel, dim3(DOT_BLOCKS, jobs.n), dim3(256), 0, jobs, dpart);
+  GP_TRY_RC(launch_dots(c, st, jobs, dpart));
   GP_LAUNCH(c, st, scalars_kernel, dim3(1), dim3(64), 0, v.sc, v.gs, jobs, dpart, c->beta, c->sf2, (double)D, (double)c->N_global);
-  // Kmm parts of grad_Z / grad_alpha; alpha partials per row go through T2 (free again)
-  static const bool kmm_lds = env_flag("GPARML_KMM_LDS", true);
-  if (kmm_lds && M <= 2048)
-    GP_LAUNCH(c, st, kmm_grads_lds_kernel, dim3(M), dim3(128), (size_t)2 * 128 * ((M + 127) / 128) * sizeof(double), v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z,
-              v.Zt, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
-  else
-    GP_LAUNCH(c, st, kmm_grads_kernel, dim3(M), dim3(128), 0, v.dFdK, v.KmmKeep, v.Bbar, v.Psi2, v.Z, v.alpha, M, Mp, Q, c->regime_A ? 1 : 0, v.gK, v.T2);
-  GP_LAUNCH(c, st, colsum_kernel, dim3(Q), dim3(256), 0, v.T2, M, Q, v.gK + (long)M * Q);
+  GP_TRY_RC(launch_kmm_grads(c, st));
   return GP_OK;
 }
 

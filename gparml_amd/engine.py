@@ -276,6 +276,60 @@ class ShardEngine(object):
             self.global_status()                # a third failure is GP_ERR_NOT_PD -> LinAlgError
             self._jitter_hint = used
 
+    # ---- explicit q(u), whitened (gp_svi_*, csrc/svi.hip) ----------------------------------------------------------
+    def svi_begin(self):
+        """q(v) := the prior (Lam = I, H = 0); the state lives until svi_end()."""
+        self._ck(self.lib.gp_svi_begin(self.h), 'gp_svi_begin')
+
+    def svi_set(self, Lam, H):
+        """The natural parameters Lam (M, M), symmetric, and H (M, D)."""
+        Lam, pl = _lib.as_c(Lam)
+        H, ph = _lib.as_c(H)
+        assert Lam.shape == (self.M, self.M) and H.shape == (self.M, self.D), 'svi_set: Lam (M, M) and H (M, D) expected'
+        self._ck(self.lib.gp_svi_set(self.h, pl, ph), 'gp_svi_set')
+
+    def svi_get(self, moments=True):
+        """dict(Lam, H) and, with ``moments``, Mv = Lam^-1 H and Sv = Lam^-1 (LinAlgError when Lam does not factorise)."""
+        out = dict(Lam=np.empty((self.M, self.M)), H=np.empty((self.M, self.D)))
+        if moments:
+            out.update(Mv=np.empty((self.M, self.D)), Sv=np.empty((self.M, self.M)))
+        p = [out[k].ctypes.data_as(_lib._dp) if k in out else None for k in ('Lam', 'H', 'Mv', 'Sv')]
+        self._ck(self.lib.gp_svi_get(self.h, *p), 'gp_svi_get')
+        return out
+
+    def svi_natural_step(self, rho):
+        """Lam <- (1 - rho) Lam + rho (I + beta Psi2w), H <- (1 - rho) H + rho beta Cw on the statistics buffer as it stands."""
+        self._ck(self.lib.gp_svi_natural_step(self.h, float(rho)), 'gp_svi_natural_step')
+        self._svi_rhos = list(self._svi_rhos) + [float(rho)]
+
+    _svi_rhos = ()
+
+    def svi_step(self, sync=True, jitter=0):
+        """The uncollapsed bound and its partials where global_step() leaves the collapsed ones; phase2() and finish() follow.  ``sync`` as in
+        global_step(): waits for the outcome and, when K_mm did not factorise, repeats with the 1e-7 jitter on it.  The natural steps since the last
+        svi_step left the state untouched in that case (gp_svi_natural_step skips on a failed K_mm): they are repeated on the jittered K_mm first."""
+        self._ck(self.lib.gp_svi_step(self.h, int(jitter)), 'gp_svi_step')
+        self._jitter_used = int(jitter)
+        if sync:
+            try:
+                self.global_status()
+            except _lib.JitterRetry as r:
+                self._jitter_used = r.mask
+                self._ck(self.lib.gp_svi_step(self.h, r.mask), 'gp_svi_step')       # the mask is the plan's from here on
+                for rho in self._svi_rhos:
+                    self._ck(self.lib.gp_svi_natural_step(self.h, rho), 'gp_svi_natural_step')
+                if self._svi_rhos:
+                    self._ck(self.lib.gp_svi_step(self.h, r.mask), 'gp_svi_step')
+                self.global_status()
+        self._svi_rhos = []          # (sync=False: the caller reads the outcome and repeats both steps itself)
+
+    def svi_publish(self):
+        """Pseudo-statistics of q(u) into the statistics buffer; global_step() next makes the context a predictor of the SVI-trained model."""
+        self._ck(self.lib.gp_svi_publish(self.h), 'gp_svi_publish')
+
+    def svi_end(self):
+        self._ck(self.lib.gp_svi_end(self.h), 'gp_svi_end')
+
     def global_status(self):
         mask = ctypes.c_int(0)
         rc = self.lib.gp_global_status(self.h, ctypes.byref(mask))

@@ -662,6 +662,45 @@ int gp_lbfgs_dots(gp_ctx* ctx, int slot, double* out /* (3, 2m+1) */);
 int gp_lbfgs_direction(gp_ctx* ctx, const double* coef /* (2m+1) */);
 int gp_lbfgs_end(gp_ctx* ctx);
 
+/* ---- explicit q(u) and minibatch training: the whitened uncollapsed bound (gp_svi_*, csrc/svi.hip) -------------------
+ * The collapsed bound solves for q(u) in every global step, so every step needs the statistics of all N rows.  These entries hold q(u) as state
+ * instead: u = L_k v with L_k L_k^T = K_mm, q(v_d) = N(Mv[:, d], Sv) with one Sv for all D columns, kept in natural parameters
+ * Lam = Sv^-1 (M, M) and H = Lam Mv (M, D); the prior is Lam = I, H = 0.  With a = L_k^-1, Psi2w = a Psi2 a^T, Cw = a C, N = N_global and the
+ * statistics as the buffer holds them (a batch's statistics scaled by N / |B| with gp_scale_buffer first):
+ *   L     = -1/2 N D ln 2pi + 1/2 N D ln beta - 1/2 beta sum_YYT + beta tr(Mv^T Cw) - 1/2 beta tr(Psi2w (D Sv + Mv Mv^T))
+ *           - 1/2 beta D (Psi0 - tr Psi2w) - KL - KLu,      KLu = 1/2 D (tr Sv - M + ln|Lam|) + 1/2 tr(Mv^T Mv)
+ *   gp_svi_natural_step(rho):  Lam <- (1 - rho) Lam + rho (I + beta Psi2w),  H <- (1 - rho) H + rho beta Cw      (Psi2w symmetrised: Lam stays
+ *           exactly symmetric).  rho = 1 on full statistics is Titsias' optimum, where L equals the collapsed F and every gradient the collapsed one.
+ *   gp_svi_step: L and its partials with q(v) held fixed, where gp_global_step leaves its own -- with G2 = 1/2 beta D I - 1/2 beta (D Sv + Mv Mv^T),
+ *           Gc = beta Mv, R = 2 G2 Psi2w + Gc Cw^T and Phi(R) = R's strictly lower triangle + half its diagonal:
+ *           dF/dPsi2 = a^T G2 a, dF/dPsi1tY = a^T Gc, dF/dKmm = -a^T 1/2 (Phi(R) + Phi(R)^T) a, the phase-2 operand, F = L,
+ *           grad_beta = 1/2 N D / beta - 1/2 sum_YYT + tr(Mv^T Cw) - 1/2 tr(Psi2w (D Sv + Mv Mv^T)) - 1/2 D (Psi0 - tr Psi2w), grad_sf2 and the
+ *           K_mm parts of grad_Z / grad_alpha by the global step's own formulas on these matrices.  GP_ARR_SCALARS' two log-determinants are
+ *           ln|K_mm| and ln|K_mm| + ln|Lam|.  gp_phase2 and gp_finish follow unchanged (fixed or free embeddings, either want_embedding_grads).
+ *           Asynchronous; the outcome comes through gp_global_status / gp_finish: K_mm not positive definite is GP_RETRY_JITTER with bit 0 (repeat
+ *           gp_svi_step with jitter_mask 1), then GP_ERR_NOT_PD; a Lam that does not factorise is GP_ERR_NOT_PD at once (the caller's state: no
+ *           jitter is added to it).  jitter_mask: 0 or 1; the mask is kept for the natural steps and the publish that follow.
+ *   gp_svi_publish: writes the pseudo-statistics Psi2_eff = L_k (Lam - I) L_k^T / beta and C_eff = L_k H / beta into the statistics buffer (an
+ *           injection of statistics, as gp_set_local_statistics is).  K_mm + beta Psi2_eff = L_k Lam L_k^T, so the ordinary gp_global_step that the
+ *           caller runs next leaves Inv, Linv and E describing q(u) exactly: gp_predict and every other new-input entry then work on the SVI-trained
+ *           model.  The F (and the gradients) of THAT step mean nothing.  Until then the new-input entries refuse (GP_ERR_STATE): gp_svi_step
+ *           leaves no model.
+ *   gp_svi_begin: q(v) := prior; a second call without gp_svi_end is GP_ERR_STATE.  gp_svi_set: Lam symmetric, both finite, else GP_ERR_BAD_ARG
+ *           (not positive definite is reported by the next step).  gp_svi_get: any pointer may be NULL; Mv / Sv factorise Lam (GP_ERR_NOT_PD when that
+ *           fails); synchronous.  gp_svi_natural_step and gp_svi_step need statistics and globals (GP_ERR_STATE), rho in (0, 1] (GP_ERR_BAD_ARG).
+ *           a, Psi2w and Cw are computed once and kept until an entry point changes the statistics or the globals (writes through the raw pointer of
+ *           gp_stats_buffer between a natural step and its gp_svi_step are not seen).  Every gp_svi_* entry before gp_svi_begin: GP_ERR_STATE.
+ *           A natural step on a K_mm that does not factorise leaves the state as it is; the gp_svi_step that follows reports K_mm, and the caller
+ *           repeats the natural step after the gp_svi_step with jitter_mask 1 (ShardEngine.svi_step does).
+ *           gp_svi_end frees the state; the context evaluates as before.  All products are plain float64; results are bit-identical from run to run. */
+int gp_svi_begin(gp_ctx* ctx);
+int gp_svi_set(gp_ctx* ctx, const double* Lam /* (M, M) */, const double* H /* (M, D) */);
+int gp_svi_get(gp_ctx* ctx, double* Lam /* (M, M) */, double* H /* (M, D) */, double* Mv /* (M, D) */, double* Sv /* (M, M) */);
+int gp_svi_natural_step(gp_ctx* ctx, double rho);
+int gp_svi_step(gp_ctx* ctx, int jitter_mask);
+int gp_svi_publish(gp_ctx* ctx);
+int gp_svi_end(gp_ctx* ctx);
+
 /* ---- shard ingest ------------------------------------------------------
  * numpy.genfromtxt(file, delimiter=',') as statistics_mapper / embeddings_mapper call it on every evaluation
  * (local_MapReduce.py:197-199, 325-327): comma-separated floating-point text -> row-major (rows, cols) doubles.
