@@ -111,6 +111,8 @@ SIGNATURES = {
     'gp_svi_step': (ctypes.c_int, [_vp, ctypes.c_int]),
     'gp_svi_publish': (ctypes.c_int, [_vp]),
     'gp_svi_end': (ctypes.c_int, [_vp]),
+    'gp_gather_shard': (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(_i64)]),
+    'gp_scatter_embeddings': (ctypes.c_int, [_vp, _vp, _i64, ctypes.POINTER(_i64)]),
     'gp_debug_gemm': (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.c_double, _dp, _dp, ctypes.c_double, _dp]),
     'gp_debug_set_option': (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
     'gp_debug_potrf_inverse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _dp]),

@@ -272,6 +272,23 @@ static int upload_embeddings(gp_ctx* c, const double* X_mu, const double* X_S, i
   return GP_OK;
 }
 
+// sum_YYT (partial_terms.py:40) of the dense rows dY [n]: 1024 block sums of sumsq_kernel, folded here in ascending order.  The one place the
+// statistic is summed -- gp_upload_shard and gp_gather_shard (gather.hip) both come here, so the same rows give the same bits.  *out is set even
+// when the sum is not finite.
+int gp::sum_yyt(gp_ctx* c, const double* dY, long n, double* out) {
+  const int nb = 1024;
+  double* part = c->red;
+  GP_LAUNCH(c, c->stream, sumsq_kernel, dim3(nb), dim3(256), 0, dY, n, part);
+  std::vector<double> h(nb);
+  hipError_t e = hipMemcpyAsync(h.data(), part, nb * 8, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) return fail(c, GP_ERR_HIP, "sum_YYT failed: %s", hipGetErrorString(e));
+  double s = 0.0;
+  for (double v : h) s += v;
+  *out = s;
+  return std::isfinite(s) ? GP_OK : fail(c, GP_ERR_NON_FINITE, "Y contains non-finite values");
+}
+
 extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, const double* X_S, int xs_is_raw) {
   if (!c) return GP_ERR_BAD_ARG;
   if (!Y || !X_mu || !X_S) return fail(c, GP_ERR_BAD_ARG, "gp_upload_shard: NULL array");
@@ -283,20 +300,7 @@ extern "C" int gp_upload_shard(gp_ctx* c, const double* Y, const double* X_mu, c
   int rc = GP_OK;
   if (e != hipSuccess) rc = fail(c, GP_ERR_HIP, "Y upload failed: %s", hipGetErrorString(e));
   if (rc == GP_OK) rc = run_upload_y(c, dY);
-  if (rc == GP_OK) {
-    // sum_YYT (partial_terms.py:40) once per upload
-    const int nb = 1024;
-    double* part = c->red;
-    GP_LAUNCH(c, c->stream, sumsq_kernel, dim3(nb), dim3(256), 0, dY, (long)nd, part);
-    std::vector<double> h(nb);
-    e = hipMemcpyAsync(h.data(), part, nb * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) rc = fail(c, GP_ERR_HIP, "sum_YYT failed: %s", hipGetErrorString(e));
-    double s = 0.0;
-    for (double v : h) s += v;
-    c->sumYY = s;
-    if (!std::isfinite(s)) rc = fail(c, GP_ERR_NON_FINITE, "Y contains non-finite values");
-  }
+  if (rc == GP_OK) rc = sum_yyt(c, dY, (long)nd, &c->sumYY);      // once per upload
   if (rc != GP_OK) return rc;
   GP_TRY(upload_embeddings(c, X_mu, X_S, xs_is_raw));
   c->life.data_uploaded();

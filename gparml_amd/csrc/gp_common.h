@@ -114,6 +114,7 @@ struct KnnPlan;    // knn.hip
 struct LooPlan;    // loo.hip
 struct CondPlan;   // condition.hip
 struct SviPlan;    // svi.hip
+struct GatherPlan; // gather.hip
 struct SviPlanDelete { void operator()(SviPlan* p) const; };
 struct P1PlanDelete { void operator()(P1Plan* p) const; };
 struct I8PlanDelete { void operator()(I8Plan* p) const; };
@@ -133,6 +134,7 @@ struct LbfgsPlanDelete { void operator()(LbfgsPlan* p) const; };
 struct KnnPlanDelete { void operator()(KnnPlan* p) const; };
 struct LooPlanDelete { void operator()(LooPlan* p) const; };
 struct CondPlanDelete { void operator()(CondPlan* p) const; };
+struct GatherPlanDelete { void operator()(GatherPlan* p) const; };
 
 }  // namespace gp
 
@@ -305,6 +307,7 @@ struct gp_ctx {
   std::unique_ptr<gp::LooPlan, gp::LooPlanDelete> loo;        // gp_loo_score's buffers (loo.hip)
   std::unique_ptr<gp::CondPlan, gp::CondPlanDelete> cond;     // gp_condition_set's rows [V | T] and gp_condition_predict's buffers (condition.hip)
   std::unique_ptr<gp::SviPlan, gp::SviPlanDelete> svi;        // gp_svi_begin .. gp_svi_end: q(v) in natural parameters and the whitened statistics (svi.hip)
+  std::unique_ptr<gp::GatherPlan, gp::GatherPlanDelete> gather;  // gp_gather_shard / gp_scatter_embeddings: the index list and the dense Y rows (gather.hip)
   void* comm = nullptr;       // RCCL communicator of this context's rank (comm.hip; NULL until gp_comm_init)
   int comm_ranks = 0, comm_rank = -1;
   // timing: 2 = HIP events around every phase and the dominant kernels (gp_last_timings reports all eight numbers; the default), 1 = only the
@@ -325,6 +328,8 @@ inline int64_t spack_doubles(const gp_ctx* c) { return (int64_t)c->M * (c->M + 1
 // poison mode (devbuf.h, g_opt_poison): refills a buffer an evaluation must write before it reads (the stages' poison() and api.hip's poison_scratch)
 inline hipError_t poison_fill(gp_ctx* c, const DevBuf<double>& b) { return b.size() ? hipMemsetAsync(b, 0xFF, b.bytes(), c->stream) : hipSuccess; }
 
+// api.hip: sum_YYT of a dense device array [n] in the one summation order of the statistic (gp_upload_shard, gp_gather_shard); synchronises the stream
+int sum_yyt(gp_ctx* c, const double* dY, long n, double* out);
 // psi.hip
 int run_upload_y(gp_ctx* c, const double* dY);
 int run_prep_and_generate(gp_ctx* c);

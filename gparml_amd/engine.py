@@ -56,6 +56,7 @@ class ShardEngine(object):
         X_S, ps = _lib.as_c(X_S)
         self.globals_key = None
         self._ck(self.lib.gp_upload_shard(self.h, pY, pm, ps, 1 if xs_is_raw else 0), 'gp_upload_shard')
+        self.xs_is_raw = bool(xs_is_raw)
 
     def upload_embeddings(self, X_mu, X_S, xs_is_raw=False):
         X_mu = np.asarray(X_mu, dtype=np.float64)
@@ -65,6 +66,30 @@ class ShardEngine(object):
         X_S, ps = _lib.as_c(X_S)
         self.globals_key = None
         self._ck(self.lib.gp_upload_embeddings(self.h, pm, ps, 1 if xs_is_raw else 0), 'gp_upload_embeddings')
+        self.xs_is_raw = bool(xs_is_raw)
+
+    xs_is_raw = False         # the form the resident variances are stored in (the last upload's; gather_from takes the source's)
+
+    @staticmethod
+    def _rows_i64(rows, n):
+        rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.int64)
+        assert rows.shape == (n,), '%d rows for a context of %d' % (rows.size, n)
+        return rows, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+    def gather_from(self, src, rows):
+        """This engine then holds what upload_shard(Y[rows], X_mu[rows], X_S[rows]) of ``src``'s resident arrays would leave, bit for bit, without
+        a host copy (gp_gather_shard): ``rows`` (N_s,) indices into src, any order, repeats allowed; same device, same D and Q."""
+        rows, pr = self._rows_i64(rows, self.N_s)
+        self.globals_key = None
+        self._ck(self.lib.gp_gather_shard(self.h, src.h, self.N_s, pr), 'gp_gather_shard')
+        self.xs_is_raw = src.xs_is_raw
+
+    def scatter_embeddings_to(self, dst, rows):
+        """This engine's X_mu / X_S rows 0 .. N_s - 1 into ``dst``'s rows ``rows`` (strictly ascending), as dst.upload_embeddings of the edited
+        arrays would (gp_scatter_embeddings); Y is never written back."""
+        rows, pr = self._rows_i64(rows, self.N_s)
+        dst.globals_key = None
+        dst._ck(dst.lib.gp_scatter_embeddings(dst.h, self.h, self.N_s, pr), 'gp_scatter_embeddings')
 
     def set_direction(self, d):
         self.globals_key = None

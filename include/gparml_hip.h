@@ -701,6 +701,22 @@ int gp_svi_step(gp_ctx* ctx, int jitter_mask);
 int gp_svi_publish(gp_ctx* ctx);
 int gp_svi_end(gp_ctx* ctx);
 
+/* ---- rows of a resident shard into a batch context, and the embeddings back (csrc/gather.hip) ----
+ * Minibatch training from the shard that is already on the device: nothing of size n x D crosses the bus.
+ *   gp_gather_shard: dst holds exactly what gp_upload_shard(dst, Y[rows], X_mu[rows], X_S[rows], xs_is_raw) would leave, with the arrays and the
+ *           xs_is_raw / fixed-embedding flags src was uploaded with or has since moved to (gp_cg_update, gp_upload_embeddings): Y with its zero
+ *           padding written, the embeddings copied in their stored form (no softplus round trip), sum_YYT bit-identical to that upload's, the
+ *           upload's lifecycle.  n must be dst's N_s; rows (n) host, each in [0, src's N_s), in any order, repeats allowed.  Synchronous.
+ *   gp_scatter_embeddings: src's X_mu / X_S rows 0 .. n-1 into dst's rows rows[i]; dst then stands as after gp_upload_embeddings.  n must be
+ *           src's N_s; rows strictly ascending in [0, dst's N_s) (no row is written twice).  Both contexts hold data and store their variances
+ *           the same way (xs_is_raw, fixed or free).  Y is never written back.  Synchronous.
+ *   Both: D and Q must match, M need not; dst and src are two contexts on one device (another device: GP_ERR_UNSUPPORTED).  Bad indices or counts
+ *           and NULL arguments are GP_ERR_BAD_ARG, a source without data GP_ERR_STATE; every check comes before anything is launched or any
+ *           state changes.  When the streams differ, the read context's stream is finished first and the work runs on the written context's
+ *           (as gp_buffer_combine).  The index list goes through a buffer of the written context that is kept and grown: no allocation per call. */
+int gp_gather_shard(gp_ctx* dst, const gp_ctx* src, int64_t n, const int64_t* rows);
+int gp_scatter_embeddings(gp_ctx* dst, const gp_ctx* src, int64_t n, const int64_t* rows);
+
 /* ---- shard ingest ------------------------------------------------------
  * numpy.genfromtxt(file, delimiter=',') as statistics_mapper / embeddings_mapper call it on every evaluation
  * (local_MapReduce.py:197-199, 325-327): comma-separated floating-point text -> row-major (rows, cols) doubles.
